@@ -10,9 +10,18 @@ BASELINE.json configs[1] (vgg300, batch 32, fp32, one MI355X).  N > 1: one proce
 the batch is sharded (weak scaling, 32 images per GPU), gradients are all-reduced over
 RCCL/xGMI between backward and the update.
 
-Rank 0 prints ONE JSON line: images/s over the whole job, the roofline block of the
-dominant kernel (per-launch HIP events, on the launching stream, over the timed region) and
-the CPU baseline (the fp32 torch-CPU oracle timed on this host; rank 0, N = 1 only).
+Rank 0 prints ONE JSON line: images/s over the whole job (`value`) and the milliseconds of one
+timed step (`ms_per_step`).  A plain run does nothing else: set up, W warmup steps, K timed steps.
+
+--full adds everything else the benchmark measures or checks: the step-0 losses against the stored
+oracle values, the roofline block of the dominant kernel (per-launch HIP events, on the launching
+stream), the CPU baseline (the fp32 torch-CPU oracle timed on this host; rank 0, N = 1 only), and for
+the headline configuration the secondary configurations and the end-to-end blocks.
+
+--dump-outputs DIR writes what the timed path computed in its last timed step as DIR/<name>.npy
+(float32 / float64; a training step: its result, its losses and a fixed sample of the weights, gradients
+and momentum it left behind).  The inputs depend on the arguments alone, so two builds can be compared
+output for output.
 """
 import argparse
 import ctypes as C
@@ -215,11 +224,13 @@ def bench_augment(args, rank, world, local):
     e1.record()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, dict([_sample('images', out.cpu().numpy(), DUMP_MAX_RESULT, 1)]))
     gpu_ms = e0.elapsed_time(e1) / args.steps
     bytes_launch = out.numel() * 4 + packed.size
     ach = bytes_launch / (gpu_ms * 1e-3) / 1e9
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import augment as oa
         ncpu = min(b, 8)
         random.seed(1234 + rank)
@@ -292,10 +303,51 @@ def self_check(out, serialized):
     return 'dominant kernel <= step, kernel sum <= %sstep, fractions in (0, 1]' % ('1.3 x ' if serialized else '')
 
 
+DUMP_BUDGET = 64 << 20       # bytes of all --dump-outputs files together
+DUMP_MAX_RESULT = 12 << 20   # elements of the largest array (48 MB of float32); a larger one is dumped as a fixed sample
+DUMP_ARENA_SAMPLE = 1 << 20  # elements of each of the weight / gradient / momentum arenas (4 MB each)
+
+
+def _sample(name, arr, n, seed):
+    """(name, arr) if arr has at most n elements, else (name + '_sample', n elements of it at fixed seeded positions, in order)."""
+    if arr.size <= n:
+        return name, arr
+    idx = np.sort(np.random.default_rng(seed).choice(arr.size, n, replace=False))
+    return name + '_sample', arr.reshape(-1)[idx]
+
+
+def step_outputs(net, b):
+    """What one training step hands its caller: the [b, A, C+5] result, the four losses, and the arenas the step updated
+    (weights and momentum) or left behind (gradients), each as the same fixed sample of DUMP_ARENA_SAMPLE positions."""
+    import torch
+    from ssd_tensorflow_amd.ssdvgg import LOSS_NAMES
+    L = net.get_losses()
+    out = dict([_sample('result', net._dev_result(b, True), DUMP_MAX_RESULT, 1)])
+    out['losses'] = np.array([L[k] for k in LOSS_NAMES], np.float64)
+    n = net.params_flat.numel()
+    idx = np.sort(np.random.default_rng(0).choice(n, min(n, DUMP_ARENA_SAMPLE), replace=False))
+    idx = torch.from_numpy(idx).to(net.params_flat.device)
+    torch.cuda.synchronize()
+    for name, t in (('params', net.params_flat), ('grads', net.grads_flat), ('momentum', net.momentum_flat)):
+        out[name + ('_sample' if len(idx) < n else '')] = t.index_select(0, idx).cpu().numpy()
+    return out
+
+
+def write_outputs(d, arrays):
+    """--dump-outputs: DIR/<name>.npy per array, float32 (float64 kept), DUMP_BUDGET bytes at most."""
+    arrays = {k: np.ascontiguousarray(v, np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f'[bench] --dump-outputs: {total} bytes > {DUMP_BUDGET}')
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + '.npy'), v)
+
+
 def run_config(a, rank, world, local):
     """One benchmark configuration -> the JSON-able result dict (rank 0; None elsewhere).
     a: namespace with mode, preset, batch, dtype, steps, warmup, bucket_mb, no_overlap, per_layer, no_kernel_events,
-    no_cpu_baseline, zero_input, allow_fallback."""
+    no_cpu_baseline, zero_input, allow_fallback, full, dump_outputs."""
     import torch
     import torch.distributed as dist
     from ssd_tensorflow_amd._lib import lib, check
@@ -303,6 +355,7 @@ def run_config(a, rank, world, local):
     from ssd_tensorflow_amd import parallel
 
     b = a.batch
+    full = getattr(a, 'full', False)
     bucket = int(a.bucket_mb * 1e6 / 4)
     state = {'bucket': bucket}
     sess = Session(local)
@@ -330,9 +383,9 @@ def run_config(a, rank, world, local):
     torch.cuda.synchronize()
 
     # parity guard of the benchmarked configuration itself: the step-0 losses of these very inputs must be the CPU
-    # oracle's (stored by tools/make_bench_expect.py); a mismatch makes the run invalid, so it is fatal
+    # oracle's (stored by tools/make_bench_expect.py); a mismatch makes the run invalid, so it is fatal (--full)
     losses_check = None
-    if training and rank == 0 and not a.zero_input:
+    if full and training and rank == 0 and not a.zero_input:
         want, tol = expected_losses(a.preset, b, a.dtype)
         if want is not None:
             net.eval_step_dev(x, y)
@@ -398,7 +451,7 @@ def run_config(a, rank, world, local):
                 print(f'[bench] bucketed all-reduce failed ({type(e).__name__}: {e}); falling back to a single all-reduce', file=sys.stderr)
             state['bucket'] = 0
             allreduce_mode = 'single, after backward (FALLBACK: the bucketed path failed)'
-    use_events = not a.no_kernel_events
+    use_events = full and not a.no_kernel_events
     # training AND inference run kernels side by side (weight-gradient stream, two forward lanes, heads on a side
     # stream): per-launch events inside such a region do not measure one kernel
     overlapped = a.mode in ('train', 'infer', 'detect') and not a.no_overlap
@@ -458,6 +511,8 @@ def run_config(a, rank, world, local):
             if rank == 0:
                 print(msg + ' -- reported, not fatal (--allow-fallback)', file=sys.stderr)
         dt = float(t.item())
+    if a.dump_outputs and rank == 0:      # before --full's serialized steps move the weights on
+        write_outputs(a.dump_outputs, step_outputs(net, b) if training else dict([_sample('result', net._dev_result(b, True), DUMP_MAX_RESULT, 1)]))
 
     roofline = None
     kernels = {}
@@ -569,14 +624,15 @@ def run_config(a, rank, world, local):
                     out['algorithm'] = ('3x3 / stride 1 trunk layers in the Winograd F(4x4, 3x3) form (%d GEMM launches per step, csrc/winograd.hip); '
                                         'model_tflops / model_mfma_frac price the step by the direct-convolution FLOPs of SURVEY.md 8d '
                                         '(%.2f GFLOP per image), executed_* by the FLOPs the kernels ran' % (nl, flops_img / 1e9))
-        if world == 1 and not a.no_cpu_baseline and a.mode == 'train':
+        if full and world == 1 and not a.no_cpu_baseline and a.mode == 'train':
             out['cpu_baseline'] = cpu_baseline(a.preset)
         else:
             out['cpu_baseline'] = None
-        if a.mode == 'train':
+        if full and a.mode == 'train':
             out['losses_last_step'] = net.get_losses()
             out['losses_check'] = losses_check
-        out['self_check'] = self_check(out, serialize_for_events)
+        if full:
+            out['self_check'] = self_check(out, serialize_for_events)
     sess.close()
     del net, x, y
     torch.cuda.empty_cache()
@@ -693,7 +749,7 @@ def ordered_for_tail(out):
     return o
 
 
-# configurations BASELINE.json names beside the headline; timed by the default invocation with a few steps each so
+# configurations BASELINE.json names beside the headline; timed by --full with a few steps each so
 # that they are driver-run numbers (the headline `value` stays configs[1])
 SECONDARY = [
     # (bf16 blocks: 20 steps -- five 8-ms steps right after a context switch of configurations measured 3-5 % low)
@@ -755,12 +811,21 @@ def main():
     ap.add_argument('--e2e-epochs', type=int, default=1, help='train_e2e: timed epochs')
     ap.add_argument('--e2e-serial-steps', type=int, default=3, help='train_e2e: steps of the serial-feeder comparison (0 = skip)')
     ap.add_argument('--e2e-both', action='store_true', help='train_e2e: run both dtypes in this process')
-    ap.add_argument('--no-e2e', action='store_true', help='skip the end-to-end blocks of the default invocation')
+    ap.add_argument('--no-e2e', action='store_true', help='skip the end-to-end blocks of --full')
     ap.add_argument('--e2e-checkpoint', default='', help='train_e2e: start from this checkpoint and feed the learnable shapes set (detections to collect)')
     ap.add_argument('--pretrain-dir', default='', help='pretrain: directory that receives final.npz')
     ap.add_argument('--pretrain-epochs', type=int, default=40, help='pretrain: epochs of 1024 shapes images at batch 32 (bf16)')
-    ap.add_argument('--no-pretrain', action='store_true', help='default invocation: end-to-end blocks from Xavier weights (no detections)')
+    ap.add_argument('--no-pretrain', action='store_true', help='--full: end-to-end blocks from Xavier weights (no detections)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline: step-0 losses against the oracle, per-kernel events and the roofline block, the CPU '
+                         'baseline, and for the headline configuration the secondary and end-to-end blocks (a plain run only times the steps)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='write what the last timed step computed as DIR/<name>.npy (train, infer and augment modes)')
     args = ap.parse_args()
+    if args.dump_outputs and args.mode not in ('train', 'infer', 'augment'):
+        ap.error('--dump-outputs covers the train, infer and augment modes')
+    if args.per_layer and not args.full:
+        ap.error('--per-layer is a per-kernel measurement: it needs --full')
 
     import torch
     import torch.distributed as dist
@@ -845,7 +910,7 @@ def main():
 
     if args.mode == 'train_e2e':
         r = e2e(args.dtype)
-        if args.e2e_both:      # both dtypes in one process, as the default invocation runs them
+        if args.e2e_both:      # both dtypes in one process, as --full runs them
             r = {'f32' if args.dtype == 'f32' else 'bf16': r}
             other = 'bf16' if args.dtype == 'f32' else 'f32'
             r[other] = e2e(other)
@@ -854,9 +919,9 @@ def main():
         return
     out = run_config(args, rank, world, local)
     headline = (args.mode, args.preset, args.batch, args.dtype) == ('train', 'vgg300', 32, 'f32')
-    if headline and world == 1 and not args.no_secondary and not args.zero_input and not args.per_layer:
+    if headline and world == 1 and args.full and not args.no_secondary and not args.zero_input and not args.per_layer:
         for name, cfg in SECONDARY:
-            sub = argparse.Namespace(**{**vars(args), **cfg, 'no_cpu_baseline': True, 'per_layer': False})
+            sub = argparse.Namespace(**{**vars(args), **cfg, 'no_cpu_baseline': True, 'per_layer': False, 'dump_outputs': ''})
             try:
                 r = run_config(sub, rank, world, local)
                 out[name] = {k: r[k] for k in ('metric', 'value', 'unit', 'ms_per_step', 'host_issue_ms_per_step', 'steps', 'warmup', 'dtype', 'config',

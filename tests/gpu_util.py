@@ -51,3 +51,15 @@ def conv_geom(hi, wi, k, stride, dil, padding):
     extra = 1 if padding == 'BR1' else 0
     keff = (k - 1) * dil + 1
     return 0, 0, (hi + extra - keff) // stride + 1, (wi + extra - keff) // stride + 1
+
+
+# train.py's SSD_PRINT_CHECKSUM record.  Several ranks share one stdout pipe, and a rank's text and its newline may reach the
+# pipe as two writes, so another rank's record can land right behind a number: the value is matched as a number, not as
+# "everything up to the next space".
+CHECKSUM_RE = r'\[checksum\] rank (\d+) step \d+ params ([-+]?\d\.\d+e[-+]\d+)'
+
+
+def rank_checksums(stdout):
+    """-> ({rank: checksum text} of the ranks' [checksum] records, stdout with those records cut out)"""
+    import re
+    return dict(re.findall(CHECKSUM_RE, stdout)), re.sub(CHECKSUM_RE, '', stdout)

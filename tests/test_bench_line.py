@@ -77,3 +77,21 @@ def test_self_check_prices_the_winograd_step_by_executed_flops():
     with pytest.raises(SystemExit):
         b.self_check(dict(base, algorithm='winograd', model_mfma_frac=4.5), True)
     assert 'wino_gemm_128x128' in b.KERNEL_SYMBOLS and 'wino_out_unpool' in b.KERNEL_SYMBOLS
+
+
+def test_dump_outputs_stay_in_budget_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: arrays over the element cap become the same seeded sample every time; float32 / float64 on disk; the
+    budget is enforced."""
+    import numpy as np
+    import pytest
+    b = _bench()
+    big = np.arange(b.DUMP_MAX_RESULT + 10, dtype=np.float32)
+    n1, s1 = b._sample('result', big, b.DUMP_MAX_RESULT, 1)
+    n2, s2 = b._sample('result', big, b.DUMP_MAX_RESULT, 1)
+    assert n1 == 'result_sample' and s1.size == b.DUMP_MAX_RESULT and np.array_equal(s1, s2) and (np.diff(s1) > 0).all()
+    assert b._sample('losses', np.zeros(4), 8, 1)[0] == 'losses'
+    b.write_outputs(str(tmp_path / 'd'), {'a': np.ones((2, 3), np.float16), 'l': np.zeros(4, np.float64)})
+    assert np.load(tmp_path / 'd' / 'a.npy').dtype == np.float32 and np.load(tmp_path / 'd' / 'l.npy').dtype == np.float64
+    with pytest.raises(SystemExit):
+        b.write_outputs(str(tmp_path / 'e'), {'x': np.zeros((b.DUMP_BUDGET // 4 + 1,), np.float32)})
+    assert not (tmp_path / 'e').exists()

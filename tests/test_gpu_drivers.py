@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from ssd_tensorflow_amd import train, infer
+from gpu_util import rank_checksums
 
 pytestmark = pytest.mark.gpu
 
@@ -150,7 +151,6 @@ def test_two_rank_training_on_one_gpu_matches_single_process(tmp_path):
     guards, bucketed all-reduce behind the weight-gradient stream, loss normaliser, an EMPTY shard in the short last
     batch, rank-summed summaries) against one process at the global batch size: same samples per step, so the weights
     must agree to fp32 summation-order accuracy and the two replicas bit for bit."""
-    import re
     import socket
     import subprocess
     import sys
@@ -164,7 +164,7 @@ def test_two_rank_training_on_one_gpu_matches_single_process(tmp_path):
                         '--master-port', str(port), '-m', 'ssd_tensorflow_amd.train', '--name', dp, '--batch-size', '2'] + common,
                        env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    sums = dict(re.findall(r'\[checksum\] rank (\d) step \d+ params (\S+)', r.stdout))
+    sums = rank_checksums(r.stdout)[0]
     assert set(sums) == {'0', '1'} and sums['0'] == sums['1'], r.stdout[-2000:]
     assert '[i] Batch size:            2 x 2 GPU(s)' in r.stdout and '[i] Train  2/2' in r.stdout
     one = str(tmp_path / 'one')
@@ -208,13 +208,13 @@ def test_eight_rank_training_on_one_gpu_matches_single_process(tmp_path):
                         '--master-port', str(port), '-m', 'ssd_tensorflow_amd.train', '--name', dp, '--batch-size', '4'] + common,
                        env=env, cwd=root, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    sums = dict(re.findall(r'\[checksum\] rank (\d) step \d+ params (\S+)', r.stdout))
+    sums, text = rank_checksums(r.stdout)
     assert set(sums) == set('01234567') and len(set(sums.values())) == 1, r.stdout[-2000:]
     assert '[i] Batch size:            4 x 8 GPU(s)' in r.stdout and '[i] Train  1/1' in r.stdout
     assert 'EMPTY shard' not in r.stderr        # (an empty shard of a batch with fewer samples than ranks is expected and silent)
 
     def losses(text, tag):
-        m = re.search(r'\[i\] %s  1/1  total (\S+)  localization (\S+)  confidence (\S+)  l2 (\S+)' % tag, text)
+        m = re.search(r'\[i\] %s  1/1  total (-?\d+\.\d+)  localization (-?\d+\.\d+)  confidence (-?\d+\.\d+)  l2 (-?\d+\.\d+)' % tag, text)
         assert m, text[-1500:]
         return [float(v) for v in m.groups()]
     one = str(tmp_path / 'one32')
@@ -224,7 +224,7 @@ def test_eight_rank_training_on_one_gpu_matches_single_process(tmp_path):
     a, b = np.load(dp + '/final.npz'), np.load(one + '/final.npz')
     assert int(a['__global_step__']) == int(b['__global_step__']) == 3
     for tag in ('Train', 'Valid'):
-        la, lb = losses(r.stdout, tag), losses(r1.stdout, tag)
+        la, lb = losses(text, tag), losses(r1.stdout, tag)
         print(f'    {tag}: 8 ranks {la}  one process {lb}')
         for x, y in zip(la, lb):
             assert abs(x - y) <= 2e-3 * abs(y), (tag, la, lb)

@@ -15,9 +15,9 @@ else
 fi
 echo "pytest rc=$?" >> "$O/pytest.log"
 tail -40 "$O/pytest.log"
-timeout 600 python bench.py > "$O/bench.json" 2> "$O/bench.stderr"; echo "bench rc=$?"
-timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-overlap --per-layer > /dev/null 2> "$O/per_layer_f32.txt"
-timeout 300 python bench.py --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-overlap --per-layer > /dev/null 2> "$O/per_layer_bf16.txt"
+timeout 600 python bench.py --full > "$O/bench.json" 2> "$O/bench.stderr"; echo "bench rc=$?"
+timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-overlap --per-layer > /dev/null 2> "$O/per_layer_f32.txt"
+timeout 300 python bench.py --full --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-overlap --per-layer > /dev/null 2> "$O/per_layer_bf16.txt"
 python - "$O/bench.json" <<'PY'
 import json, sys
 try:
@@ -40,9 +40,9 @@ for x in ${GPU_EXTRA:-}; do
            echo "SSD_GATHER_ROWS_BF16=0" >> "$O/heads_tiles_bf16.txt"; SSD_GATHER_ROWS_BF16=0 timeout 100 python tools/bench_conv.py head1,head0,head2 bf16 >> "$O/heads_tiles_bf16.txt" 2>&1
            cat "$O/heads_tiles_bf16.txt";;
     trace) cd /tmp && export TMPDIR=/tmp
-           rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pd -o d -- python "$R/bench.py" --mode decode --batch 128 --steps 20 --warmup 3 --no-cpu-baseline > "$O/bench_decode_under_rocprof.json" 2>/dev/null
+           rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pd -o d -- python "$R/bench.py" --full --mode decode --batch 128 --steps 20 --warmup 3 --no-cpu-baseline > "$O/bench_decode_under_rocprof.json" 2>/dev/null
            cp /tmp/pd/d_kernel_stats.csv "$O/rocprofv3_kernel_stats_decode.csv"
-           rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pe -o e -- python "$R/bench.py" --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-overlap > "$O/bench_bf16_under_rocprof_serialized.json" 2>/dev/null
+           rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pe -o e -- python "$R/bench.py" --full --dtype bf16 --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-overlap > "$O/bench_bf16_under_rocprof_serialized.json" 2>/dev/null
            cp /tmp/pe/e_kernel_stats.csv "$O/rocprofv3_kernel_stats_bf16_serialized.csv"
            cd "$R"; head -3 "$O/rocprofv3_kernel_stats_decode.csv" | cut -c1-200; grep -E "heads_kernel|loss_|sumsq|detect|reduce_grouped|cast_filters|l2norm" "$O/rocprofv3_kernel_stats_bf16_serialized.csv" | cut -c1-220;;
     headsweep) for t in 0 1 2 3 4 5 6 7 8; do echo "ROWS=0 SSD_TILE_BF16=$t"; SSD_GATHER_ROWS_BF16=0 SSD_TILE_BF16=$t timeout 100 python tools/bench_conv.py head1,head0 bf16; done > "$O/heads_tiles2_bf16.txt" 2>&1; cat "$O/heads_tiles2_bf16.txt";;

@@ -2,7 +2,7 @@
 """Step-0 losses of bench.py's own configurations, computed by the CPU oracle (oracle/ssdvgg_ref.py, fp32 torch-CPU)
 on the very inputs bench.py generates on rank 0: images and boxes from default_rng(1234) in bench.py's draw order,
 labels from the oracle's label encoder, weights = the library's own initialisation (seed 42) restated by
-oracle.ssdvgg_ref.init_params_lib.  Written to tests/golden/bench_expect.json; bench.py refuses to report a training
+oracle.ssdvgg_ref.init_params_lib.  Written to tests/golden/bench_expect.json; bench.py --full refuses to report a training
 number whose step-0 losses differ from these by more than 1e-3 (fp32).
 
     python tools/make_bench_expect.py [vgg300:32 vgg512:16 ...]        (minutes of CPU per configuration)

@@ -14,12 +14,12 @@ cd /tmp && export TMPDIR=/tmp
 
 # 1. kernel trace, one kernel at a time (durations comparable with bench.py's HIP events)
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pa -o a -- \
-    python "$R/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-overlap $EXTRA \
+    python "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-overlap $EXTRA \
     > "$O/bench_under_rocprof_serialized.json" 2>/dev/null
 cp /tmp/pa/a_kernel_stats.csv "$O/rocprofv3_kernel_stats_serialized.csv"
 # 2. kernel trace of the overlapped step (what the headline runs)
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pb -o b -- \
-    python "$R/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-secondary $EXTRA \
+    python "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline --no-secondary $EXTRA \
     > "$O/bench_under_rocprof_overlapped.json" 2>/dev/null
 cp /tmp/pb/b_kernel_stats.csv "$O/rocprofv3_kernel_stats_overlapped.csv"
 # 2b. GPU idle time per step: a trace of overlapped steps only (no per-launch events, no serialized second half)
@@ -50,17 +50,17 @@ for C in FETCH_SIZE WRITE_SIZE; do
     python "$R/tools/pmc_table.py" "$C" /tmp/pdc_$C/c_counter_collection.csv > "$O/decode_pmc_$C.txt"
 done
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pdd -o d -- \
-    python "$R/bench.py" --mode decode --batch 128 --steps 20 --warmup 3 --no-cpu-baseline > "$O/bench_decode_under_rocprof.json" 2>/dev/null
+    python "$R/bench.py" --full --mode decode --batch 128 --steps 20 --warmup 3 --no-cpu-baseline > "$O/bench_decode_under_rocprof.json" 2>/dev/null
 cp /tmp/pdd/d_kernel_stats.csv "$O/rocprofv3_kernel_stats_decode_b128.csv"
 fi
 # 4. per-layer event table + the headline line (with the CPU baseline)
 cd "$R"
-python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-overlap --per-layer $EXTRA > /dev/null 2> "$O/per_layer_events.txt"
-python bench.py $EXTRA > "$O/bench.json" 2> "$O/bench.stderr"
-python bench.py --mode infer --batch 128 --no-cpu-baseline $EXTRA > "$O/bench_infer_b128.json" 2>/dev/null
-python bench.py --preset vgg512 --batch 16 --no-cpu-baseline $EXTRA > "$O/bench_vgg512_b16.json" 2>/dev/null
+python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-overlap --per-layer $EXTRA > /dev/null 2> "$O/per_layer_events.txt"
+python bench.py --full $EXTRA > "$O/bench.json" 2> "$O/bench.stderr"
+python bench.py --full --mode infer --batch 128 --no-cpu-baseline $EXTRA > "$O/bench_infer_b128.json" 2>/dev/null
+python bench.py --full --preset vgg512 --batch 16 --no-cpu-baseline $EXTRA > "$O/bench_vgg512_b16.json" 2>/dev/null
 if [ -z "$EXTRA" ]; then
-    python bench.py --mode decode --batch 128 --no-cpu-baseline > "$O/bench_decode_b128.json" 2>/dev/null
+    python bench.py --full --mode decode --batch 128 --no-cpu-baseline > "$O/bench_decode_b128.json" 2>/dev/null
 fi
 cat "$O/bench.json"
 head -4 "$O/rocprofv3_kernel_stats_serialized.csv" | cut -c1-160
