@@ -2079,7 +2079,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
 
 // =================================================================================
 // Kernel-row weight gradient, 8 waves: 128 input channels x 128 output channels x the three taps of a kernel row per
-// workgroup (padded-raster k order as above), ONE workgroup per CU, an NS-deep ring of 34-KB stages.
+// workgroup (padded-raster k order as above), ONE workgroup per CU, a ring of ROWS8_NS = 4 34-KB stages (measured best of 2..4;
+// the staggered issue below needs at least 3).
 // Why: a CU's LDS-DMA path moves ~55 B/clk at best (tools/probes/dma_rate.hip) and every 1-KB piece costs its issuing
 // wave 60..185 cycles.  The 4-wave kernels above need 64 B/clk to keep the matrix cores busy (32 KB per 16 MFMAs per
 // wave, two workgroups per CU) and run at ~40 % of peak; this tile needs 22 B/clk (34 KB per 24 MFMAs per wave) and
@@ -2087,13 +2088,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
 // (6 accumulator tiles); the bias gradient rides on the matrix cores too (a ones operand against the dy fragments in
 // the two waves of the kh = 0, ct = 0 workgroups) instead of a scalar LDS sweep.
 // =================================================================================
-template <int NS, bool STAGGER = true>
+constexpr int ROWS8_NS = 4;
 __global__ __launch_bounds__(512) void conv_wgrad_bf16_rows8_kernel(WgradRowsArgs p) {
+    constexpr int NS = ROWS8_NS;
     constexpr int BKT = 128, BNT = 128, BP = 64, XROWS = 72, ROWB = 256, CPR = 16;
     constexpr int RPP = 512 / CPR;                              // 32 pixel rows per staging pass of the workgroup
     constexpr int X_N = BP / RPP, Y_N = BP / RPP;               // 2 + 2 full passes; rows 64..71 of x: waves 0 and 1
     constexpr int X_LDS = XROWS * ROWB, STAGE = X_LDS + BP * ROWB;
-    static_assert(NS >= 2 && NS <= 4 && NS * STAGE <= 160 * 1024, "ring");
+    static_assert(NS >= 3 && NS * STAGE <= 160 * 1024, "ring");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int tid = threadIdx.x;
@@ -2268,7 +2270,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_bf16_rows8_kernel(WgradRowsArg
         // with one workgroup per CU all 8 waves would be in it at the same time.  With a ring of >= 3 stages the target
         // buffer is free for the whole iteration, so waves 4..7 (the SIMD partners of waves 0..3) multiply first and
         // issue afterwards: on every SIMD one wave feeds the matrix pipe while the other one issues.
-        const bool late = NS >= 3 && STAGGER && wave >= 4;
+        const bool late = wave >= 4;
         if (!late && it + NS - 1 < niter) issue(it + NS - 1, st_i);
         compute(st_c);
         if (late && it + NS - 1 < niter) issue(it + NS - 1, st_i);
@@ -2400,17 +2402,17 @@ static void check_desc_h(const ConvDesc& d) {
 
 // Tile configurations (pixels x channels, pipeline stages -> workgroups resident per CU):
 //   0: 128x128 x2 (2/CU)   1: 128x64 x2 (2/CU)   2: 64x128 x2 (2/CU)
-//   3: 256x128 x3 (1/CU)   4: 128x128 x4 (1/CU)  5: 128x64 x3 (2/CU)
-//   6: 256x128 x3, 8 waves (1/CU)   7: 256x128 x2, 8 waves (1/CU)   8: 256x64 x2, 8 waves (2/CU)
-//   9: 64x64 x6 (1/CU): the latency-bound small layers (see pick_tile_h)   10: 64x64 x2, k split over 4 wave groups (16 waves, 1/CU)
-constexpr int NCFG_H = 12;
+//   3: 128x128 x4 (1/CU)   4: 128x64 x3 (2/CU)   5: 256x64 x2, 8 waves (2/CU)
+//   6: 64x64 x6 (1/CU): the latency-bound small layers (see pick_tile_h)   7: 64x64 x2, k split over 4 wave groups (16 waves, 1/CU)
+// 0, 1, 2 and 5 compete in the automatic choice; 3, 4, 6 and 7 are promotions of a launch of at most one round of workgroups.
+constexpr int NCFG_H = 8;
 static int pick_tile_h(long long M, int N, int mode, int nk = 0) {
     static const int forced = env_int("SSD_TILE_BF16", -1);      // tuning override
     if (forced >= 0 && forced < NCFG_H) return forced;
-    static const int bm[NCFG_H] = {128, 128, 64, 256, 128, 128, 256, 256, 256, 64, 64, 64}, bn[NCFG_H] = {128, 64, 128, 128, 128, 64, 128, 128, 64, 64, 64, 64};
-    static const int per_cu[NCFG_H] = {2, 2, 2, 1, 1, 2, 1, 1, 2, 1, 1, 2};
+    static const int bm[NCFG_H] = {128, 128, 64, 128, 128, 256, 64, 64}, bn[NCFG_H] = {128, 64, 128, 128, 64, 64, 64, 64};
+    static const int per_cu[NCFG_H] = {2, 2, 2, 1, 2, 2, 1, 1};
     // > 0: in the automatic choice.  256x64 (8 waves) serves the 64-channel layers: conv1_2 forward 427 -> 462, data gradient 423 -> 474 TF/s
-    static const double eff[NCFG_H] = {1.0, 0.85, 0.85, 0.0, 0.0, 0.0, 0.0, 0.0, 0.93, 0.0, 0.0, 0.0};
+    static const double eff[NCFG_H] = {1.0, 0.85, 0.85, 0.0, 0.0, 0.93, 0.0, 0.0};
     int best = 0;
     double bc = 1e300;
     for (int c = 0; c < NCFG_H; ++c) {
@@ -2428,20 +2430,19 @@ static int pick_tile_h(long long M, int N, int mode, int nk = 0) {
     {
         const long long wgs = (long long)cdiv(M, bm[best]) * cdiv(N, bn[best]);
         if (wgs <= 256) {
-            if (best == 0) best = 4;           // 128x128 x4
-            else if (best == 1) best = 5;      // 128x64 x3
+            if (best == 0) best = 3;           // 128x128 x4
+            else if (best == 1) best = 4;      // 128x64 x3
             // Round 4: such a launch's time IS its serial k loop (conv9_2: 18 iterations, the 10x10 map's head: 72) at
             // ~0.7 us per iteration -- one DMA round trip for two tiles in flight.  64x64 tiles stage 16 KB per iteration
             // instead of 24 and a ring of SIX keeps four in flight; the launch also spreads over up to four times the
             // CUs.  Taken while it still fits one workgroup per CU.  SSD_SMALL_TILE=0 switches it off (A/B).
             static const int small_tile = env_int("SSD_SMALL_TILE", 1);
             if (small_tile && (long long)cdiv(M, 64) * cdiv(N, 64) <= 256) {
-                best = 9;
-                // ... and with at least 8 iterations to share, four wave groups split the k loop (conv_gather_bf16_kernel, KSPLIT):
-                // SSD_SMALL_KSPLIT=0 keeps the deep ring
-                static const int ksplit = env_int("SSD_SMALL_KSPLIT", 1);      // 1: four wave groups (16 waves, 128 KB of LDS: needs an EMPTY CU); 2: two groups (8 waves, 64 KB)
-                if (ksplit == 2 && nk >= 8) best = 11;
-                else if (ksplit && nk >= 8) best = 10;
+                best = 6;
+                // ... and with at least 8 iterations to share, four wave groups split the k loop (conv_gather_bf16_kernel, KSPLIT;
+                // 16 waves, 128 KB of LDS: needs an EMPTY CU).  SSD_SMALL_KSPLIT=0 keeps the deep ring
+                static const int ksplit = env_int("SSD_SMALL_KSPLIT", 1);
+                if (ksplit && nk >= 8) best = 7;
             }
         }
     }
@@ -2451,41 +2452,33 @@ static int pick_tile_h(long long M, int N, int mode, int nk = 0) {
 template <int MODE>
 static void launch_gather_cfg(int cfg, GatherArgsH& a, double fl, double by, hipStream_t s, bool unpool = false) {
     static const char* const names[2][NCFG_H] = {
-        {"conv_fwd_bf16_128x128", "conv_fwd_bf16_128x64", "conv_fwd_bf16_64x128", "conv_fwd_bf16_256x128x3", "conv_fwd_bf16_128x128x4",
-         "conv_fwd_bf16_128x64x3", "conv_fwd_bf16_256x128x3_8w", "conv_fwd_bf16_256x128x2_8w", "conv_fwd_bf16_256x64_8w", "conv_fwd_bf16_64x64x6",
-         "conv_fwd_bf16_64x64_k4", "conv_fwd_bf16_64x64_k2"},
-        {"conv_dgrad_bf16_128x128", "conv_dgrad_bf16_128x64", "conv_dgrad_bf16_64x128", "conv_dgrad_bf16_256x128x3",
-         "conv_dgrad_bf16_128x128x4", "conv_dgrad_bf16_128x64x3", "conv_dgrad_bf16_256x128x3_8w", "conv_dgrad_bf16_256x128x2_8w",
-         "conv_dgrad_bf16_256x64_8w", "conv_dgrad_bf16_64x64x6", "conv_dgrad_bf16_64x64_k4", "conv_dgrad_bf16_64x64_k2"}};
+        {"conv_fwd_bf16_128x128", "conv_fwd_bf16_128x64", "conv_fwd_bf16_64x128", "conv_fwd_bf16_128x128x4", "conv_fwd_bf16_128x64x3",
+         "conv_fwd_bf16_256x64_8w", "conv_fwd_bf16_64x64x6", "conv_fwd_bf16_64x64_k4"},
+        {"conv_dgrad_bf16_128x128", "conv_dgrad_bf16_128x64", "conv_dgrad_bf16_64x128", "conv_dgrad_bf16_128x128x4",
+         "conv_dgrad_bf16_128x64x3", "conv_dgrad_bf16_256x64_8w", "conv_dgrad_bf16_64x64x6", "conv_dgrad_bf16_64x64_k4"}};
     static const char* const unpool_names[NCFG_H] = {
-        "conv_dgrad_unpool_bf16_128x128", "conv_dgrad_unpool_bf16_128x64", "conv_dgrad_unpool_bf16_64x128", "conv_dgrad_unpool_bf16_256x128x3",
-        "conv_dgrad_unpool_bf16_128x128x4", "conv_dgrad_unpool_bf16_128x64x3", "conv_dgrad_unpool_bf16_256x128x3_8w", "conv_dgrad_unpool_bf16_256x128x2_8w",
-        "conv_dgrad_unpool_bf16_256x64_8w", "conv_dgrad_unpool_bf16_64x64x6", "conv_dgrad_unpool_bf16_64x64_k4", "conv_dgrad_unpool_bf16_64x64_k2"};
+        "conv_dgrad_unpool_bf16_128x128", "conv_dgrad_unpool_bf16_128x64", "conv_dgrad_unpool_bf16_64x128", "conv_dgrad_unpool_bf16_128x128x4",
+        "conv_dgrad_unpool_bf16_128x64x3", "conv_dgrad_unpool_bf16_256x64_8w", "conv_dgrad_unpool_bf16_64x64x6", "conv_dgrad_unpool_bf16_64x64_k4"};
     const char* label = unpool ? unpool_names[cfg] : names[MODE][cfg];
     switch (cfg) {
     case 0: launch_gather_h<MODE, 2, 2, 2, 2, false, 2>(a, label, fl, by, s); break;
     case 1: launch_gather_h<MODE, 4, 1, 1, 2, false, 2>(a, label, fl, by, s); break;
     case 2: launch_gather_h<MODE, 2, 2, 1, 2, false, 2>(a, label, fl, by, s); break;
-    case 3: launch_gather_h<MODE, 2, 2, 4, 2, false, 3>(a, label, fl, by, s); break;
-    case 4: launch_gather_h<MODE, 2, 2, 2, 2, false, 4>(a, label, fl, by, s); break;
-    case 5: launch_gather_h<MODE, 4, 1, 1, 2, false, 3>(a, label, fl, by, s); break;
-    case 6: launch_gather_h<MODE, 4, 2, 2, 2, false, 3>(a, label, fl, by, s); break;
-    case 7: launch_gather_h<MODE, 4, 2, 2, 2, false, 2>(a, label, fl, by, s); break;
-    case 8: launch_gather_h<MODE, 8, 1, 1, 2, false, 2>(a, label, fl, by, s); break;
-    case 9: launch_gather_h<MODE, 2, 2, 1, 1, false, 6>(a, label, fl, by, s); break;
-    case 11: launch_gather_h<MODE, 2, 2, 1, 1, false, 2, false, 2>(a, label, fl, by, s); break;
+    case 3: launch_gather_h<MODE, 2, 2, 2, 2, false, 4>(a, label, fl, by, s); break;
+    case 4: launch_gather_h<MODE, 4, 1, 1, 2, false, 3>(a, label, fl, by, s); break;
+    case 5: launch_gather_h<MODE, 8, 1, 1, 2, false, 2>(a, label, fl, by, s); break;
+    case 6: launch_gather_h<MODE, 2, 2, 1, 1, false, 6>(a, label, fl, by, s); break;
     default: launch_gather_h<MODE, 2, 2, 1, 1, false, 2, false, 4>(a, label, fl, by, s); break;
     }
 }
 
 // ---- kernel-row gather dispatch ------------------------------------------------------------------------------
-// SSD_GATHER_ROWS_BF16: 0 off, 1 (default) forward everywhere + dgrad of the undilated layers (measured +2..9 %; the
-// dilated mod_conv6 dgrad measured -2 %), 2 everywhere.
+// Forward everywhere + the data gradient of the undilated layers (measured +2..9 %; the dilated mod_conv6 data gradient
+// measured -2 %).
 static bool gather_rows_applicable(const ConvDesc& d, bool dgrad) {
-    static const int on = env_int("SSD_GATHER_ROWS_BF16", 1);
-    if (on == 1 && dgrad && d.dil != 1) return false;
+    if (dgrad && d.dil != 1) return false;
     const int sc = dgrad ? d.Co : d.Ci;            // channels of the gathered tensor: whole 64-channel chunks only
-    return on && sc % 64 == 0 && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.Hi == d.Ho && d.Wi == d.Wo && d.dil >= 1 && d.dil <= 8 &&
+    return sc % 64 == 0 && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.Hi == d.Ho && d.Wi == d.Wo && d.dil >= 1 && d.dil <= 8 &&
            d.pad_h == d.dil && d.pad_w == d.dil;
 }
 // conv1_2-shaped layers (64 -> 64, 3x3, stride 1, SAME, bf16 out), large enough to give every CU several tiles
@@ -2547,12 +2540,11 @@ static bool gather_rows_n64(int M, int N) {
 // instead of 1024 workgroups -- under sustained load (profiles/r04_ag_sustained_tile_sweep_bf16.txt) the 256-row tile is ahead
 // wherever it was tried: conv2_2 forward 957 vs 883 TFLOP/s, conv3_2 1122 vs 1077, conv4_2 1161 vs 1135 (732 workgroups); the
 // half-batch launches of conv3_x in the forward lanes (712 each) had been on 128-row tiles.  SSD_GATHER_ROWS256_BF16: 0 off,
-// 1 this rule, 2 every eligible layer (tests), 3 round 3's rule (1024 workgroups, per launch).
+// 1 this rule, 2 every eligible layer (tests).
 static bool gather_rows256(const ConvDesc& d, int M, int N) {
     static const int on = env_int("SSD_GATHER_ROWS256_BF16", 1);
     if (!on || d.dil != 1) return false;
     if (on == 2) return true;
-    if (on == 3) return cdiv(M, 253) * cdiv(N, 128) >= 1024;
     return (long long)cdiv((long long)M * g_conv_lanes, 253) * cdiv(N, 128) >= 700;
 }
 
@@ -2647,9 +2639,7 @@ static void conv_dgrad_bf16_any(const ConvDesc& d, const bf16_t* dy, const bf16_
                 ++c.nclass;
             }
         c.M = c.cls_M[0]; c.DH = c.cls_DH[0]; c.DW = c.cls_DW[0]; c.ntaps = c.cls_ntaps[0];
-        static const int small_k2 = env_int("SSD_SMALL_KSPLIT", 1) == 2;
-        if (small && small_k2) launch_gather_h<MODE_DGRAD, 2, 2, 1, 1, false, 2, true, 2>(c, "conv_dgrad_bf16_parity_64x64_k2", fl, by, s, c.cls_wg0[c.nclass]);
-        else if (small) launch_gather_h<MODE_DGRAD, 2, 2, 1, 1, false, 2, true, 4>(c, "conv_dgrad_bf16_parity_64x64_k4", fl, by, s, c.cls_wg0[c.nclass]);
+        if (small) launch_gather_h<MODE_DGRAD, 2, 2, 1, 1, false, 2, true, 4>(c, "conv_dgrad_bf16_parity_64x64_k4", fl, by, s, c.cls_wg0[c.nclass]);
         else launch_gather_h<MODE_DGRAD, 2, 2, 2, 2, false, 2, true>(c, "conv_dgrad_bf16_parity_128x128", fl, by, s, c.cls_wg0[c.nclass]);
         return;
     }
@@ -2664,11 +2654,9 @@ static void conv_dgrad_bf16_any(const ConvDesc& d, const bf16_t* dy, const bf16_
     // 64-channel data gradients (conv2_1: 128 -> 64) on the kernel-row gather, 128 x 64 tiles: the per-tap 256 x 64 tile stages
     // 40 KB per 8 MFMAs per wave (52 FLOP per staged byte -- more than a CU's L2 -> LDS path feeds), a kernel row 44 KB per 24
     // (71).  conv2_1 with the fused un-pool 0.180 -> 0.160 ms; 256 x 64 kernel-row tiles 0.185 (two workgroups per CU instead of
-    // three).  profiles/r06_y_*.  SSD_DGRAD_ROWS_C64: 0 per-tap, 1 (default) 128 x 64, 2 256 x 64.
-    static const int rows_c64 = env_int("SSD_DGRAD_ROWS_C64", 1);
-    if (gather_rows_applicable(d, true) && d.Ci == 64 && rows_c64) {
-        if (rows_c64 == 2 && d.dil == 1) launch_gather_rows<MODE_DGRAD, 4, 1>(a, d.dil, unpool ? "conv_dgrad_unpool_bf16_rows_256x64" : "conv_dgrad_bf16_rows_256x64", fl, by, s);
-        else launch_gather_rows<MODE_DGRAD, 2, 1>(a, d.dil, unpool ? "conv_dgrad_unpool_bf16_rows_128x64" : "conv_dgrad_bf16_rows_128x64", fl, by, s);
+    // three).  profiles/r06_y_*.
+    if (gather_rows_applicable(d, true) && d.Ci == 64) {
+        launch_gather_rows<MODE_DGRAD, 2, 1>(a, d.dil, unpool ? "conv_dgrad_unpool_bf16_rows_128x64" : "conv_dgrad_bf16_rows_128x64", fl, by, s);
         return;
     }
     if (gather_rows_applicable(d, true) && d.Ci >= 128) {
@@ -2796,7 +2784,7 @@ void conv_fwd_pool_bf16(const ConvDesc& d, const bf16_t* x, const bf16_t* w_oi, 
 
 // ---- wgrad planning -------------------------------------------------------------------
 struct WgradPlanH {
-    int cfg;        // (channels x n, stages) 0: 128x128x2, 1: 64x64x2, 2: 64x128x2, 3: 128x64x2, 4: 128x128x4 (1/CU), 5: 256x128x3 (1/CU)
+    int cfg;        // (channels x n, stages) 0: 128x128x2, 1: 64x64x2, 2: 64x128x2, 3: 128x64x2
     int bkt, bnt, CT, NT, tiles, nsplit, mchunk;
 };
 
@@ -2810,8 +2798,8 @@ static WgradPlanH plan_wgrad_h(const ConvDesc& d) {
     else if (M < 20000) p.cfg = 2;               // 19x19 maps and smaller: more, smaller tiles (conv5_2 496 -> 544, mod_conv7 347 -> 411 TF/s)
     else p.cfg = 0;
     static const int forced = env_int("SSD_WGRAD_CFG_BF16", -1);      // tuning override
-    if (forced >= 0 && forced < 6 && !(forced == 5 && d.Ci < 256)) p.cfg = forced;
-    p.bkt = p.cfg == 5 ? 256 : (p.cfg == 0 || p.cfg == 3 || p.cfg == 4) ? 128 : 64;
+    if (forced >= 0 && forced < 4) p.cfg = forced;
+    p.bkt = (p.cfg == 0 || p.cfg == 3) ? 128 : 64;
     p.bnt = (p.cfg == 1 || p.cfg == 3) ? 64 : 128;
     p.CT = cdiv(d.Ci, p.bkt);
     p.NT = cdiv(d.Co, p.bnt);
@@ -2840,26 +2828,19 @@ static void launch_wgrad_h(WgradArgsH& a, const WgradPlanH& pl, const char* labe
     HIP_OK(hipGetLastError());
 }
 
-// ---- kernel-row variant (3x3, stride 1, SAME) --------------------------------------------------------------
-// 0: off   1: the 64-input-channel layers (conv1_2, conv2_1)   2: every applicable layer
-static int rows_mode() {
-    static const int v = env_int("SSD_WGRAD_ROWS_BF16", 1);      // tuning / A-B switch
-    return v;
+// ---- kernel-row variant (3x3, stride 1, SAME) for the 64-input-channel layers (conv1_2, conv2_1) ----------------------------
+static bool wgrad_3x3_same(const ConvDesc& d) {
+    return d.KH == 3 && d.KW == 3 && d.stride == 1 && d.dil == 1 && d.pad_h == 1 && d.pad_w == 1 && d.Hi == d.Ho && d.Wi == d.Wo;
 }
-static bool rows_applicable(const ConvDesc& d) {
-    const bool shape = d.KH == 3 && d.KW == 3 && d.stride == 1 && d.dil == 1 && d.pad_h == 1 && d.pad_w == 1 && d.Hi == d.Ho && d.Wi == d.Wo;
-    if (!shape || rows_mode() == 0) return false;
-    return d.Ci <= 64 || rows_mode() >= 2;
-}
+static bool rows_applicable(const ConvDesc& d) { return wgrad_3x3_same(d) && d.Ci <= 64; }
 struct RowsPlan {
-    int tm, tn, CT, NT, schunk, nsplit;
+    int tn, CT, NT, schunk, nsplit;
     long long nslots;
 };
 static RowsPlan plan_rows(const ConvDesc& d) {
     RowsPlan p{};
-    p.tm = d.Ci > 64 ? 2 : 1;
-    p.tn = (p.tm == 1 && d.Co > 64) ? 2 : 1;
-    p.CT = cdiv(d.Ci, 64 * p.tm);
+    p.tn = d.Co > 64 ? 2 : 1;
+    p.CT = cdiv(d.Ci, 64);
     p.NT = cdiv(d.Co, 64 * p.tn);
     p.nslots = (long long)d.B * d.Ho * (d.Wo + 2);
     // tuning override.  Re-measured on the round-2 kernels incl. the slab reduce (gpurun r02_m): conv1_2 0.515 / 0.424 / 0.374 /
@@ -2876,26 +2857,21 @@ static RowsPlan plan_rows(const ConvDesc& d) {
     return p;
 }
 
-// 8-wave variant: SSD_WGRAD_ROWS8_BF16 = 0 off, else the ring depth (2..4) for the layers with >= 128 input channels
-static int rows8_mode() {
-    static const int v = env_int("SSD_WGRAD_ROWS8_BF16", 4);     // tuning / A-B switch (staggered issue needs >= 3 stages; 4 measured best)
-    return v;
-}
+// 8-wave variant for the layers with >= 128 input channels
 static bool rows8_applicable(const ConvDesc& d) {
-    const bool shape = d.KH == 3 && d.KW == 3 && d.stride == 1 && d.dil == 1 && d.pad_h == 1 && d.pad_w == 1 && d.Hi == d.Ho && d.Wi == d.Wo;
     // (round 5 tried the fused heads -- Co = 104 / 152 -- on the per-tap kernel, because a rows8 launch takes every CU's LDS for
     // 60-80 us while backward's latency-bound chain runs beside it: the step did not move, profiles/r05_m_ab_tail_bf16.txt)
-    return shape && rows8_mode() >= 2 && d.Ci >= 128 && rows_mode() != 2;
+    return wgrad_3x3_same(d) && d.Ci >= 128;
 }
 // one workgroup per CU and a single round: the fewest pixel splits (= the least fp32 slab traffic) that fill the chip
 static RowsPlan plan_rows8(const ConvDesc& d) {
     RowsPlan p{};
-    p.tm = 2; p.tn = 2;
+    p.tn = 2;
     p.CT = cdiv(d.Ci, 128);
     p.NT = cdiv(d.Co, 128);
     p.nslots = (long long)d.B * d.Ho * (d.Wo + 2);
     const int jobs = 3 * p.CT * p.NT;
-    // SSD_WGRAD_ROWS8_WGS: workgroup target (A/B switch).  256 = one per CU.  Fewer = fewer pixel splits = proportionally less
+    // Workgroup target: 256 = one per CU.  Fewer = fewer pixel splits = proportionally less
     // fp32 slab traffic (every workgroup leaves 196 KB), at the price of CUs the launch does not use -- which, in the step, the
     // data gradient on the other stream does.
     constexpr int wgs_target = 256;      // (192 ties, 128 loses 9 %: profiles/r04_t_ab_rows8_wgs_bf16.txt)
@@ -2906,46 +2882,34 @@ static RowsPlan plan_rows8(const ConvDesc& d) {
     p.nsplit = cdiv(p.nslots, p.schunk);
     return p;
 }
-template <int NS, bool STAGGER = true>
 static void launch_wgrad_rows8(WgradRowsArgs& a, const char* label, double flops, double bytes, hipStream_t s) {
-    constexpr size_t lds = (size_t)NS * (72 * 256 + 64 * 256);
-    auto kern = conv_wgrad_bf16_rows8_kernel<NS, STAGGER>;
-    static bool once = (set_lds(kern, lds), true);
+    constexpr size_t lds = (size_t)ROWS8_NS * (72 * 256 + 64 * 256);
+    static bool once = (set_lds(conv_wgrad_bf16_rows8_kernel, lds), true);
     (void)once;
     ProfScope prof(label, flops, bytes, s);
-    hipLaunchKernelGGL(kern, dim3(a.nsplit * 3 * a.CT * a.NT), dim3(512), lds, s, a);
+    hipLaunchKernelGGL(conv_wgrad_bf16_rows8_kernel, dim3(a.nsplit * 3 * a.CT * a.NT), dim3(512), lds, s, a);
     HIP_OK(hipGetLastError());
 }
 
-template <int TM, int TN, int NS>
-static void launch_wgrad_rows_ns(WgradRowsArgs& a, const char* label, double flops, double bytes, hipStream_t s) {
-    constexpr size_t lds = NS * (size_t)(72 * 128 * TM + 64 * 128 * TN);
-    auto kern = conv_wgrad_bf16_rows_kernel<TM, TN, NS>;
+template <int TN>
+static void launch_wgrad_rows(WgradRowsArgs& a, const char* label, double flops, double bytes, hipStream_t s) {
+    constexpr int NS = 2;      // (rings of 3 / 4 stages measured slower: see the kernel)
+    constexpr size_t lds = NS * (size_t)(72 * 128 + 64 * 128 * TN);
+    auto kern = conv_wgrad_bf16_rows_kernel<1, TN, NS>;      // (64 input channels per workgroup: TM = 1)
     static bool once = (set_lds(kern, lds), true);
     (void)once;
     ProfScope prof(label, flops, bytes, s);
     hipLaunchKernelGGL(kern, dim3(a.nsplit * 3 * a.CT * a.NT), dim3(256), lds, s, a);
     HIP_OK(hipGetLastError());
 }
-template <int TM, int TN>
-static void launch_wgrad_rows(WgradRowsArgs& a, const char* label, double flops, double bytes, hipStream_t s) {
-    launch_wgrad_rows_ns<TM, TN, 2>(a, label, flops, bytes, s);      // (rings of 3 / 4 stages measured slower: see the kernel)
-}
 
-// ---- column-walk variant (3x3, stride 1, SAME, <= 64 input channels): SSD_WGRAD_COL_BF16 = 0 off, 1 on (default), 2 also small
-// layers (tests).  Measured (profiles/r03_r_col_wgrad_sweep_bf16.txt, r03_s_col_wgrad_ablation_bf16.txt, r03_t_ab_col_wgrad_bf16.txt;
+// ---- column-walk variant (3x3, stride 1, SAME, <= 64 input channels, enough pixels for a round of units).  Measured (profiles/r03_r_col_wgrad_sweep_bf16.txt, r03_s_col_wgrad_ablation_bf16.txt, r03_t_ab_col_wgrad_bf16.txt;
 // kernel + slab reduce, batch 32, post-relu operands): conv1_2 0.386 -> 0.252 ms (551 -> 844 TFLOP/s), conv2_1 0.206 -> 0.175;
 // 512 workgroups (one round of two per CU) beat 768 / 1024; step 7.53 / 7.55 -> 7.41 / 7.38 ms.  Ablations of conv1_2: multiply
 // only 0.212, staging only 0.166, neither 0.049 (launch, first tiles, slabs, reduce): the multiply phase alone runs at
 // 1.3 PFLOP/s, the power-limited rate of the big layers -- what is left is the part of the staging the multiply does not hide.
-static int col_mode() {
-    static const int v = env_int("SSD_WGRAD_COL_BF16", 1);
-    return v;
-}
 static bool col_applicable(const ConvDesc& d) {
-    const bool shape = d.KH == 3 && d.KW == 3 && d.stride == 1 && d.dil == 1 && d.pad_h == 1 && d.pad_w == 1 && d.Hi == d.Ho && d.Wi == d.Wo;
-    if (!shape || col_mode() == 0 || d.Ci > 64) return false;
-    return col_mode() >= 2 || (long long)d.B * d.Ho * d.Wo >= 64LL * 1024;      // enough pixels for a round of units
+    return wgrad_3x3_same(d) && d.Ci <= 64 && (long long)d.B * d.Ho * d.Wo >= 64LL * 1024;
 }
 struct ColPlan { int NT, nstrips, rpu, RC, nunits; };
 static ColPlan plan_col(const ConvDesc& d) {
@@ -3002,10 +2966,7 @@ void conv_wgrad_bf16(const ConvDesc& d, const bf16_t* x, const bf16_t* dy, float
         r.B = d.B; r.H = d.Ho; r.W = d.Wo; r.Ci = d.Ci; r.Co = d.Co; r.pad_h = d.pad_h;
         r.CT = rp.CT; r.NT = rp.NT; r.nslots = rp.nslots; r.schunk = rp.schunk; r.nsplit = rp.nsplit;
         const double fl = conv_flops(d), by = 2.0 * conv_elems(d);
-        const char* label = "conv_wgrad_bf16_rows8_128x128";
-        if (rows8_mode() == 2) launch_wgrad_rows8<2>(r, label, fl, by, s);
-        else if (rows8_mode() == 4) launch_wgrad_rows8<4, true>(r, label, fl, by, s);
-        else launch_wgrad_rows8<3, true>(r, label, fl, by, s);
+        launch_wgrad_rows8(r, "conv_wgrad_bf16_rows8_128x128", fl, by, s);
         wgrad_reduce(ws, rp.nsplit, (size_t)9 * d.Ci * d.Co, d.Co, dw, dbias, w, weight_decay, s);
         return;
     }
@@ -3016,9 +2977,8 @@ void conv_wgrad_bf16(const ConvDesc& d, const bf16_t* x, const bf16_t* dy, float
         r.B = d.B; r.H = d.Ho; r.W = d.Wo; r.Ci = d.Ci; r.Co = d.Co; r.pad_h = d.pad_h;
         r.CT = rp.CT; r.NT = rp.NT; r.nslots = rp.nslots; r.schunk = rp.schunk; r.nsplit = rp.nsplit;
         const double fl = conv_flops(d), by = 2.0 * conv_elems(d);
-        if (rp.tm == 2) launch_wgrad_rows<2, 1>(r, "conv_wgrad_bf16_rows_128x64", fl, by, s);
-        else if (rp.tn == 2) launch_wgrad_rows<1, 2>(r, "conv_wgrad_bf16_rows_64x128", fl, by, s);
-        else launch_wgrad_rows<1, 1>(r, "conv_wgrad_bf16_rows_64x64", fl, by, s);
+        if (rp.tn == 2) launch_wgrad_rows<2>(r, "conv_wgrad_bf16_rows_64x128", fl, by, s);
+        else launch_wgrad_rows<1>(r, "conv_wgrad_bf16_rows_64x64", fl, by, s);
         wgrad_reduce(ws, rp.nsplit, (size_t)9 * d.Ci * d.Co, d.Co, dw, dbias, w, weight_decay, s);
         return;
     }
@@ -3037,8 +2997,6 @@ void conv_wgrad_bf16(const ConvDesc& d, const bf16_t* x, const bf16_t* dy, float
     if (pl.cfg == 1) launch_wgrad_h<2, 2, 1, 1, 2>(a, pl, "conv_wgrad_bf16_64x64", fl, by, s);
     else if (pl.cfg == 2) launch_wgrad_h<2, 2, 1, 2, 2>(a, pl, "conv_wgrad_bf16_64x128", fl, by, s);
     else if (pl.cfg == 3) launch_wgrad_h<2, 2, 2, 1, 2>(a, pl, "conv_wgrad_bf16_128x64", fl, by, s);
-    else if (pl.cfg == 4) launch_wgrad_h<2, 2, 2, 2, 4>(a, pl, "conv_wgrad_bf16_128x128x4", fl, by, s);
-    else if (pl.cfg == 5) launch_wgrad_h<2, 2, 4, 2, 3>(a, pl, "conv_wgrad_bf16_256x128x3", fl, by, s);
     else launch_wgrad_h<2, 2, 2, 2, 2>(a, pl, "conv_wgrad_bf16_128x128", fl, by, s);
     wgrad_reduce(ws, pl.nsplit, (size_t)a.ntaps * d.Ci * d.Co, d.Co, dw, dbias, w, weight_decay, s);
 }

@@ -180,7 +180,6 @@ private:
     hipStream_t s2_ = nullptr;                  // second forward lane: its main stream, which also runs its heads (= wstream_ in a training handle)
     hipEvent_t ev2_h_ = nullptr, ev_l2_ = nullptr, ev_join_ = nullptr, ev2_fmap_[MAX_MAPS] = {};
     int tail_first_ = 0;                 // op index of conv8_1: the extra layers behind it form backward's side chain
-    bool stop_events_ = true;            // data gradients carry their gradient tensor's event (common.h g_stop_event)
     // Issue orders (net.hip build_orders): forward walks fwd_order_ (every multibox head right behind its feature map), backward
     // walks bwd_order_ (reverse graph order)
     std::vector<int> fwd_order_, bwd_order_;
@@ -203,7 +202,6 @@ private:
     std::vector<long long> tail_fwd_off_, tail_bwd_off_; // ... element offsets per op of the forward / data-gradient form (-1: none)
     void pack_tail_filters(hipStream_t s);               // from the fresh bf16 mirrors, one launch (forward, behind cast_filters)
     bool chain_fwd_ = false, chain_bwd_ = false;      // SSD_TAIL_FUSE bit 0 / bit 1: the chain in forward / in backward
-    std::vector<char> in_wgroup_;        // ops whose weight gradient came out of this backward pass' grouped launch
     bool bw_chain_done_ = false;         // this backward pass has issued the chain's data gradients and grouped weight gradients
     void plan_tail_chain();
     // Round 6 (fp32): Winograd layers.  Scratch shared by every such layer: the GEMM results of a forward lane (wino_m_), the

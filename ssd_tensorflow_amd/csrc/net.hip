@@ -266,11 +266,10 @@ void Net::build_orders() {
 // (maps 2 .. n-2) run on the MAIN stream in front of the two big heads.  On the one side stream the four of them ran back to back
 // -- 200 us at 30-66 us each beside the big heads' kernels -- before conv11_2's data gradient could start, and the main stream then
 // waited 316 us for the chain's end (profiles/r05_l_timeline_merged_tail_bf16.txt).  The chain picks their results up through an
-// event per feature map (Tensor::gev), not through a join of the streams.  SSD_BW_SMALL_HEADS_MAIN=0: all of them on the side stream.
+// event per feature map (Tensor::gev), not through a join of the streams.
 int Net::bw_class(const Op& op, int op_index) const {
     if (!(hstream_ && overlap_)) return 0;
-    static const bool small_main = env_i("SSD_BW_SMALL_HEADS_MAIN", 1) != 0;
-    if (op.kind == OP_CONV && op.head >= 2) return (small_main && op.head != heads_.nmaps - 1) ? 0 : 1;      // small maps' heads: a few workgroups each
+    if (op.kind == OP_CONV && op.head >= 2) return op.head != heads_.nmaps - 1 ? 0 : 1;      // small maps' heads: a few workgroups each
     if (op.kind == OP_CONV && op.head < 0 && op_index > tail_first_) return 1;     // conv11_2 ... conv8_2 behind them
     return 0;
 }
@@ -351,7 +350,8 @@ void Net::plan_pool_fusion() {
 //   forward   conv9_1, conv9_2, head3, conv10_1, conv10_2, head4, conv11_1, conv11_2, head5                    (vgg300)
 //   backward  data gradients of head5, head4, head3, conv11_2, conv11_1, conv10_2, conv10_1, conv9_2 in ONE launch (the first
 //             layer's own data gradient accumulates into a tensor the 10x10 head also writes: it stays a launch), then the
-//             weight gradients of all nine layers in ONE grouped launch with a direct epilogue (no slabs, no reduces).
+//             weight gradients of the other eight layers in ONE grouped launch with a direct epilogue (no slabs, no reduces);
+//             the first layer keeps its own weight-gradient launch and slab reduce.
 // 27 launches of round 5 (9 forward, 8 + 10 backward, not counting 9 reduces) become 3 (+ one that packs the filters).
 // SSD_TAIL_FUSE: bit 0 forward, bit 1 backward; default 3; 0 = the per-layer launches.
 void Net::plan_tail_chain() {
@@ -465,7 +465,7 @@ void Net::launch_tail_backward(int b, bool* side_used) {
         if (std::find(written.begin(), written.end(), &in) == written.end()) written.push_back(&in);
     }
     prof_.layer = "tail";
-    const bool carry = stop_events_ && first_out->gev != nullptr;
+    const bool carry = first_out->gev != nullptr;
     g_stop_event = carry ? first_out->gev : nullptr;
     {
         struct Disarm { ~Disarm() { g_stop_event = nullptr; } } disarm;
@@ -492,7 +492,6 @@ void Net::launch_tail_backward(int b, bool* side_used) {
     // (the chain's first layer, on the 10x10 map -- 3200 pixels at batch 32 -- would be the group's straggler with its single pixel
     // split: 50 iterations on 8 workgroups; it keeps its own launch and slab reduce, issued when its turn comes)
     std::vector<WgradGroupItem> items;
-    in_wgroup_.assign(ops_.size(), 0);
     for (int oi = 0; oi < (int)ops_.size(); ++oi) {
         if (!in_chain_[oi]) continue;
         const Op& op = ops_[oi];
@@ -501,7 +500,6 @@ void Net::launch_tail_backward(int b, bool* side_used) {
         WgradGroupItem it{};
         it.d = conv_desc(op, b);
         if (oi == chain_first_) continue;      // (whatever the batch: backward_ranges, which knows no batch, mirrors this)
-        in_wgroup_[oi] = 1;
         it.x = in.h(); it.dy = out.gh();
         it.dw = grads_ + op.w_off; it.dbias = grads_ + op.b_off; it.w = params_ + op.w_off;
         items.push_back(it);
@@ -780,11 +778,10 @@ Net::Net(const char* preset, int num_classes, int max_batch, int device, bool tr
     plan_winograd();
     // Round 5: an event per gradient tensor (round 4: the small heads' feature maps only).  The data-gradient kernel that writes it
     // CARRIES the event (g_stop_event), and the weight-gradient stream / the other class wait for exactly that kernel: no event
-    // packet between two data gradients on the main stream, none inside the side chain.  SSD_STOP_EVENTS=0: round 4's records.
-    stop_events_ = env_i("SSD_STOP_EVENTS", 1) != 0;
+    // packet between two data gradients on the main stream, none inside the side chain.
     if (training_)
         for (const Op& op : ops_)
-            if ((stop_events_ ? op.in != input_t_ : (op.kind == OP_CONV && op.head >= 2)) && !tensors_[op.in].gev)
+            if (op.in != input_t_ && !tensors_[op.in].gev)
                 HIP_OK(hipEventCreateWithFlags(&tensors_[op.in].gev, hipEventDisableTiming));
 }
 
@@ -926,7 +923,6 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
     // One lane runs the eight layers once, at twice the rows per launch and the same latency; the second lane's stream -- idle
     // from here on -- takes every other small head, which used to queue behind each other on the one side stream.
     // (Round 4 merged at the 19x19 maps, i.e. incl. conv5_x / mod_conv6, where two lanes fill each other's partial rounds: slower.)
-    static const bool merge_tail = env_i("SSD_FWD_MERGE_TAIL", 1) != 0;      // A/B switch
     int nl_cur = nl;
     int small_heads = 0;
     for (const int op_index : fwd_order_) {
@@ -947,7 +943,7 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
                 }
             continue;
         }
-        if (nl_cur == 2 && merge_tail && heads_full && op_index == tail_first_) {
+        if (nl_cur == 2 && heads_full && op_index == tail_first_) {
             HIP_OK(hipEventRecord(ev_join_, s2_));
             HIP_OK(hipStreamWaitEvent(stream_, ev_join_, 0));
             lane[0].nb = b;
@@ -1041,7 +1037,7 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
                     break;
                 }
                 // a feature map's producer carries the event its head waits for (common.h g_stop_event; backward_step does the same)
-                const int fh = (stop_events_ && side && op.head < 0 && cs == ln.s) ? head_of(op.out) : -1;
+                const int fh = (side && op.head < 0 && cs == ln.s) ? head_of(op.out) : -1;
                 if (fh >= 0) g_stop_event = ln.ev_fmap[fh];
                 struct CarryScope {
                     bool* flag;
@@ -1184,7 +1180,6 @@ void Net::backward_begin(int b, const float* y) {
     bw_first_on_main_ = false;
     bw_first_fused_ = false;
     bw_chain_done_ = false;
-    in_wgroup_.assign(ops_.size(), 0);
     bw_pos_ = 0;
     bw_b_ = b;
     bw_done_off_ = nfilters_;
@@ -1212,7 +1207,7 @@ bool Net::backward_step(size_t min_floats, size_t* off, size_t* count, bool sync
         if (chain_bwd_ && in_chain_[op_index] && !op_ablated(op.name, op.kind, op.head, op.k)) {
             // Round 6 (plan_tail_chain): the first chain op met issues the chain's data gradients (one launch) and every chain layer's
             // weight gradient (one grouped launch); the other members are skipped when their turn comes -- all but the chain's first
-            // layer, whose data gradient is an ordinary launch below (its weight gradient came out of the group)
+            // layer, whose data and weight gradients are ordinary launches below (launch_tail_backward leaves it out of the group)
             if (!bw_chain_done_) {
                 launch_tail_backward(b, &side_used);
                 bw_chain_done_ = true;
@@ -1242,7 +1237,7 @@ bool Net::backward_step(size_t min_floats, size_t* off, size_t* count, bool sync
             if (side && !on_main) {
                 // (dy written on the main stream but already waited for by the side stream, and this op lives there: the
                 // side stream is the one that is less far ahead -- a small head's weight gradient need not wait for mod_conv7)
-                if (stop_events_ && out.gev && out.gev_set) {
+                if (out.gev && out.gev_set) {
                     HIP_OK(hipStreamWaitEvent(wstream_, out.gev, 0));      // the kernel that wrote dy last (it waited for the earlier writers)
                 } else {
                     const bool from_side = out.gstream == 1 || (cls == 1 && bw_seen_[1][0] >= out.gseq);
@@ -1254,7 +1249,7 @@ bool Net::backward_step(size_t min_floats, size_t* off, size_t* count, bool sync
                 bw_need(0, out);
                 if (on_main) bw_first_on_main_ = true;
             }
-            if (!(bw_first_fused_ && !need_dx) && !(chain_bwd_ && bw_chain_done_ && in_wgroup_[op_index]))      // (conv1_1's came out of conv1_2's data gradient: below; the chain's first layer's out of the grouped launch)
+            if (!(bw_first_fused_ && !need_dx))      // (conv1_1's came out of conv1_2's data gradient: below)
                 launch_wgrad(op_index, b, ws);
             if (need_dx) {
                 bw_need(cls, out);
@@ -1285,7 +1280,7 @@ bool Net::backward_step(size_t min_floats, size_t* off, size_t* count, bool sync
                     lo = bw_final_lo();
                     break;
                 }
-                g_stop_event = stop_events_ ? dst.gev : nullptr;      // the launch carries dst's event (taken by the gather launchers)
+                g_stop_event = dst.gev;      // the launch carries dst's event (taken by the gather launchers)
                 struct Disarm { ~Disarm() { g_stop_event = nullptr; } } disarm;      // (also when the launch throws)
                 if (op.wino_d && cls == 0) {      // Round 6: the Winograd form (its scratch belongs to the main stream)
                     wino_bwd_transform(d, out.gf(), wino_yt_, nullptr, ds);
@@ -1299,7 +1294,7 @@ bool Net::backward_step(size_t min_floats, size_t* off, size_t* count, bool sync
                     if (up) conv_dgrad_unpool_bf16(d, out.gh(), wq_io_ + op.w_off, dst.gh(), up->pool_rec, dst.H, dst.W, ds);
                     else conv_dgrad_bf16(d, out.gh(), wq_io_ + op.w_off, in.gh(), mask ? in.h() : nullptr, in.done > 0, ds);
                 }
-                const bool carried = stop_events_ && dst.gev && g_stop_event == nullptr;
+                const bool carried = dst.gev && g_stop_event == nullptr;
                 bw_wrote(cls, dst, carried);
             }
             bw_conv_done_[op_index] = 1;

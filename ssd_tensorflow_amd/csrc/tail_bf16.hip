@@ -672,10 +672,10 @@ void tail_chain_bf16(const TailStage* stages, int nstages, int nimg, const char*
         if (!stamps_dev) HIP_OK(hipMalloc((void**)&stamps_dev, STAMP_WORDS * 8));
         HIP_OK(hipMemsetAsync(stamps_dev, 0, STAMP_WORDS * 8, s));
     }
-    static const int helpers = env_int("SSD_TAIL_HELPERS", 64);      // A/B switch: 0 = no L2 warm-up workgroups
+    constexpr int helpers = 64;      // L2 warm-up workgroups behind the images' own
     // (a separate prefetch LAUNCH in front of the chain -- every XCD reads every packed filter once -- measured like the helper
     // workgroups, 75 vs 75 us forward, and is gone: profiles/r06_q_tail_chain_prefetch_bf16.txt)
-    SSD_LAUNCH_STOP(tail_chain_bf16_kernel, dim3(nimg + (helpers > 0 ? helpers : 0)), dim3(TAIL_THREADS), (size_t)lds_total, s, tab_dev, nstages, nimg,
+    SSD_LAUNCH_STOP(tail_chain_bf16_kernel, dim3(nimg + helpers), dim3(TAIL_THREADS), (size_t)lds_total, s, tab_dev, nstages, nimg,
                     stamps_on ? stamps_dev : nullptr);
     HIP_OK(hipGetLastError());
     if (stamps_on) {      // (serializes the stream)
