@@ -197,7 +197,7 @@ static void encode_labels_impl(const char* preset, int num_classes, int device, 
                                const int* offsets, int b, float* vec_dev, float* vec_host, hipStream_t s) {
     const Preset& p = get_preset(preset);
     SSD_REQUIRE(b >= 1, "batch must be >= 1");
-    SSD_REQUIRE(num_classes >= 1 && num_classes <= 27, "num_classes must be in 1..27");
+    require_num_classes(num_classes);
     DeviceGuard dev_guard_(device);
     const int ntot = offsets[b];
     SSD_REQUIRE(offsets[0] == 0 && ntot >= 0, "gt_offsets must start at 0 and be non-decreasing");
@@ -260,7 +260,7 @@ int ssd_encode_labels_resident(const char* preset, int num_classes, int device, 
     API_BEGIN
     const Preset& p = get_preset(preset);
     SSD_REQUIRE(b >= 1 && ntot >= 0, "batch must be >= 1 and ntot >= 0");
-    SSD_REQUIRE(num_classes >= 1 && num_classes <= 27, "num_classes must be in 1..27");
+    require_num_classes(num_classes);
     SSD_REQUIRE(gt_offsets_dev && vec_out_dev && ws_dev && (ntot == 0 || (gt_boxes_dev && gt_cls_dev)), "null argument");
     DeviceGuard dev_guard_(device);
     const double* anc;
@@ -298,6 +298,7 @@ int ssd_decode_nms_dev(const char* preset, int num_classes, const double* anchor
 int ssd_decode_nms(const char* preset, int num_classes, int device, const float* pred, int b, float conf_thr, int cap,
                    int max_out, int out_cap, int nms, int* count, float* conf, int* cls, int* idx, int* box) {
     API_BEGIN
+    require_num_classes(num_classes);
     const Preset& p = get_preset(preset);
     SSD_REQUIRE(b >= 1 && out_cap >= 1, "batch and out_cap must be >= 1");
     DeviceGuard dev_guard_(device);

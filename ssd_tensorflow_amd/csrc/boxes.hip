@@ -251,6 +251,7 @@ void encode_labels(const Preset& p, int num_classes, const double* anchors, cons
 // float4 loads, all issued before the first is consumed; rows are then read at an odd stride:
 // conflict-free).  Every anchor whose confidence reaches thr becomes one 64-bit sort key
 //   conf bits << 32 | (32767 - anchor) << 8 | 0x80 | class   (descending sort == conf desc, anchor asc)
+// (class in bits 0-6: up to MAX_CLASSES = 127 classes; below the per-image unique anchor bits, so it never orders keys)
 // A workgroup compacts the keys of its 256 rows in place: ballot prefix per wave, wave totals through LDS,
 // the survivors stored from the first row of the segment on, their number in `bcount`.  A workgroup's rows
 // belong to at most two images (A >= 256): two segments, the second one starting at the image boundary.
@@ -329,6 +330,98 @@ __global__ __launch_bounds__(256) void detect_scan_kernel(int A, int nv, int B, 
     extern __shared__ __attribute__((aligned(16))) float rows[];
     __shared__ int s_cnt[2][4];
     detect_scan_block(blockIdx.x, threadIdx.x, rows, s_cnt, A, nv, B, pred, thr, dense, bcount);
+}
+
+// The same pass for rows of more than SCAN_MAXV values (28..127 classes), where SCAN_ROWS rows would need up to 135 KB of
+// LDS: the workgroup's SCAN_ROWS rows go through LDS in SCANW_CHUNKS chunks of SCANW_ROWS, the next chunk's float4 loads in
+// flight while the current one is ranked, 4 lanes per row.  Each lane takes the first maximum of every 4th class, the 4
+// lanes then keep the larger value, on ties the lower class: the first maximum of the row (a NaN in class 0 wins, as
+// in detect_scan_block).  The dense keys and the per-segment counts are those of detect_scan_kernel (a segment's keys
+// in another order, which the per-image sort does not see).
+constexpr int SCANW_ROWS = 64;
+constexpr int SCANW_CHUNKS = SCAN_ROWS / SCANW_ROWS;
+constexpr int SCANW_MAXV = MAX_CLASSES + 5;
+constexpr int SCANW_LOADS = (SCANW_ROWS * SCANW_MAXV / 4 + 255) / 256;      // float4 per thread and chunk, worst case
+
+__global__ __launch_bounds__(256) void detect_scan_wide_kernel(int A, int nv, int B, const float* __restrict__ pred, float thr,
+                                                               u64* __restrict__ dense, int* __restrict__ bcount) {
+    extern __shared__ __attribute__((aligned(16))) float rows[];      // [SCANW_ROWS][nv]
+    __shared__ int s_cnt[2][4];
+    const int t = threadIdx.x, blk = blockIdx.x;
+    const int r0 = blk * SCAN_ROWS;
+    const int nrows = max(0, min(SCAN_ROWS, B * A - r0));
+    const int lane = t & 63, wv = t >> 6, sub = t & 3, rl = t >> 2;
+    const int img_first = r0 / A;
+    const int boundary = (img_first + 1) * A;
+    const int nfg = nv - 5;
+    float4 v[SCANW_LOADS];
+    auto issue = [&](int q) {             // chunk q's rows start at (r0 + 64 q) * nv floats: 16-byte aligned
+        const int n4 = (max(0, min(SCANW_ROWS, nrows - q * SCANW_ROWS)) * nv) >> 2;
+        const float* src = pred + (size_t)(r0 + q * SCANW_ROWS) * nv;
+#pragma unroll
+        for (int j = 0; j < SCANW_LOADS; ++j) {
+            const int i = t + 256 * j;
+            v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (i < n4) v[j] = *reinterpret_cast<const float4*>(src + (size_t)i * 4);
+        }
+    };
+    issue(0);
+    int tot0 = 0, tot1 = 0;               // keys stored so far per segment (workgroup uniform)
+    for (int q = 0; q < SCANW_CHUNKS; ++q) {
+        const int c0 = q * SCANW_ROWS;
+        const int nr = max(0, min(SCANW_ROWS, nrows - c0));
+        const int nfl = nr * nv, n4 = nfl >> 2;
+        const float* src = pred + (size_t)(r0 + c0) * nv;
+#pragma unroll
+        for (int j = 0; j < SCANW_LOADS; ++j) {
+            const int i = t + 256 * j;
+            if (i < n4) *reinterpret_cast<float4*>(rows + (size_t)i * 4) = v[j];
+        }
+        for (int i = (n4 << 2) + t; i < nfl; i += 256) rows[i] = src[i];
+        __syncthreads();
+        if (q + 1 < SCANW_CHUNKS) issue(q + 1);
+        u64 key = 0ull;
+        int half = 0;
+        if (rl < nr) {                    // uniform over the row's 4 lanes
+            const float* r = rows + (size_t)rl * nv;
+            float conf = -__builtin_inff();
+            int best = sub;
+            for (int c = sub; c < nfg; c += 4)
+                if (r[c] > conf) { conf = r[c]; best = c; }
+#pragma unroll
+            for (int o = 1; o <= 2; o <<= 1) {
+                const float oc = __shfl_xor(conf, o, 64);
+                const int ob = __shfl_xor(best, o, 64);
+                if (oc > conf || (oc == conf && ob < best)) { conf = oc; best = ob; }
+            }
+            if (r[0] != r[0]) { conf = r[0]; best = 0; }
+            const int row = r0 + c0 + rl;
+            half = row >= boundary ? 1 : 0;
+            const int a = row - (img_first + half) * A;
+            if (sub == 0 && !(conf < thr))
+                key = ((u64)__float_as_uint(conf) << 32) | ((u64)(32767 - a) << 8) | (u64)best | (1ull << 7);
+        }
+        const u64 bal0 = __ballot(key != 0ull && half == 0), bal1 = __ballot(key != 0ull && half == 1);
+        if (lane == 0) { s_cnt[0][wv] = __popcll(bal0); s_cnt[1][wv] = __popcll(bal1); }
+        __syncthreads();
+        int base = half ? tot1 : tot0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            if (w < wv) base += s_cnt[half][w];
+        }
+        if (key != 0ull) {
+            const u64 bal = half ? bal1 : bal0;
+            __hip_atomic_store(dense + (size_t)(half ? boundary : r0) + base + __popcll(bal & ((1ull << lane) - 1ull)), key, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+        }
+#pragma unroll
+        for (int w = 0; w < 4; ++w) { tot0 += s_cnt[0][w]; tot1 += s_cnt[1][w]; }
+        __syncthreads();                  // rows and s_cnt are rewritten by the next chunk
+    }
+    if (t == 0 && nrows > 0) {
+        __hip_atomic_store(bcount + blk * 2, tot0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(bcount + blk * 2 + 1, tot1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 }
 
 
@@ -488,7 +581,7 @@ struct DetectArgs {
     DetectOut out;
 };
 // survivors in order -> the caller's arrays, clipped to [:max_out] / out_cap
-template <typename KeyAt, typename BoxAt>
+template <int NCLS, typename KeyAt, typename BoxAt>
 __device__ __forceinline__ void detect_emit(const DetectArgs& p, int b, int m, const unsigned char* alive, KeyAt key_at,
                                             BoxAt box_at, int* s_wtot) {
     const int tid = threadIdx.x;
@@ -514,7 +607,7 @@ __device__ __forceinline__ void detect_emit(const DetectArgs& p, int b, int m, c
             const u64 key = key_at(q);
             const size_t dst = (size_t)b * p.out_cap + o;
             p.out.conf[dst] = __uint_as_float((unsigned)(key >> 32));
-            p.out.cls[dst] = (int)(key & 31ull);
+            p.out.cls[dst] = (int)(key & (u64)(NCLS - 1));
             p.out.idx[dst] = 32767 - (int)((key >> 8) & 0xFFFFull);
             *reinterpret_cast<int4*>(p.out.box + dst * 4) = box_at(q);
         }
@@ -525,12 +618,17 @@ __device__ __forceinline__ void detect_emit(const DetectArgs& p, int b, int m, c
 }
 
 // The per-image phase: rank, decode, NMS and ordered emit of image b by one workgroup of DET_THREADS threads; `smem` = DET_SMEM
-// bytes of the caller's LDS.  Called by detect_image_kernel (one workgroup per image).
+// bytes of the caller's LDS.  Called by detect_image_kernel (one workgroup per image).  NCLS, the class capacity of the
+// per-class tables and of the key's class field (a power of two): 32 up to 27 classes, 128 up to MAX_CLASSES.
+template <int NCLS>
 __device__ __forceinline__ void detect_image_body(const DetectArgs& p, const int b, unsigned char* smem) {
-    __shared__ int firstpos[32], crank[32], ccount[32], segstart[33], order_cls[32];
+    static_assert(NCLS == 32 || NCLS == 128, "class capacity");
+    constexpr u64 CMASK = NCLS - 1;
+    constexpr int CLANES = NCLS > 64 ? NCLS : 64;        // threads of the one-lane-per-class steps (whole waves)
+    __shared__ int firstpos[NCLS], crank[NCLS], ccount[NCLS], segstart[NCLS + 1], order_cls[NCLS];
     __shared__ int s_npresent, s_wtot[DET_WAVES];
-    __shared__ u64 cmax[32];
-    __shared__ int bstart[32];
+    __shared__ u64 cmax[NCLS];
+    __shared__ int bstart[NCLS];
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     u64* g1 = p.keys1 + (size_t)b * p.A2;
@@ -607,7 +705,7 @@ __device__ __forceinline__ void detect_image_body(const DetectArgs& p, const int
             else mykey[r] = ~0ull;
             s_pos[i] = 0; s_cpos[i] = 0;
         }
-        if (tid < 32) { firstpos[tid] = INT_MAX; ccount[tid] = 0; }
+        if (tid < NCLS) { firstpos[tid] = INT_MAX; ccount[tid] = 0; }
         __syncthreads();
         const int m = p.cap >= 0 ? min(n, p.cap) : n;          // detections_cap (ssdutils.py:207-210)
         // The output order is: class groups in first-appearance order of the confidence-sorted list (defaultdict,
@@ -621,26 +719,44 @@ __device__ __forceinline__ void detect_image_body(const DetectArgs& p, const int
 #pragma unroll
             for (int r = 0; r < PER; ++r) {
                 const int i = tid + DET_THREADS * r;
-                myslot[r] = i < n ? atomicAdd(&ccount[(int)(mykey[r] & 31ull)], 1) : 0;      // any order inside the bucket
+                myslot[r] = i < n ? atomicAdd(&ccount[(int)(mykey[r] & CMASK)], 1) : 0;      // any order inside the bucket
                 pos[r] = 0;
             }
             __syncthreads();
+            if constexpr (NCLS <= 64) {
             if (tid < 64) {         // exclusive prefix of the class counts (raw class ids): where each bucket starts
-                const int v = tid < 32 ? ccount[tid] : 0;
+                const int v = tid < NCLS ? ccount[tid] : 0;
                 int inc = v;
 #pragma unroll
-                for (int o = 1; o < 32; o <<= 1) {
+                for (int o = 1; o < NCLS; o <<= 1) {
                     const int t = __shfl_up(inc, o, 64);
                     if (lane >= o) inc += t;
                 }
-                if (tid < 32) bstart[tid] = inc - v;
+                if (tid < NCLS) bstart[tid] = inc - v;
+            }
+            } else {
+            if (tid < 64) {         // the same with NCLS / 64 consecutive classes per lane
+                constexpr int K = NCLS / 64;
+                int v[K], sum = 0;
+#pragma unroll
+                for (int e = 0; e < K; ++e) { v[e] = ccount[K * tid + e]; sum += v[e]; }
+                int inc = sum;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int t = __shfl_up(inc, o, 64);
+                    if (lane >= o) inc += t;
+                }
+                int acc = inc - sum;
+#pragma unroll
+                for (int e = 0; e < K; ++e) { bstart[K * tid + e] = acc; acc += v[e]; }
+            }
             }
             __syncthreads();
             u64* bkey = reinterpret_cast<u64*>(nbox);       // (nbox is written by the placement phase, two barriers on)
 #pragma unroll
             for (int r = 0; r < PER; ++r) {
                 const int i = tid + DET_THREADS * r;
-                if (i < n) bkey[bstart[(int)(mykey[r] & 31ull)] + myslot[r]] = mykey[r];
+                if (i < n) bkey[bstart[(int)(mykey[r] & CMASK)] + myslot[r]] = mykey[r];
             }
             __syncthreads();
 #pragma unroll
@@ -649,7 +765,7 @@ __device__ __forceinline__ void detect_image_body(const DetectArgs& p, const int
                 cpos[r] = 0;
                 if (i < n) {
                     const u64 key = mykey[r];
-                    const int c = (int)(key & 31ull);
+                    const int c = (int)(key & CMASK);
                     const u64* bk = bkey + bstart[c];
                     const int cnt = ccount[c];
                     int cp = 0;
@@ -659,17 +775,20 @@ __device__ __forceinline__ void detect_image_body(const DetectArgs& p, const int
                 }
             }
             __syncthreads();
-            if (tid < 64) {         // one lane per class: its rank among the present classes and where its segment starts
-                const bool present = tid < 32 && ccount[tid & 31] > 0;
-                const u64 mine = present ? cmax[tid & 31] : 0ull;
-                int r = 0, start = 0;
-                for (int c = 0; c < 32; ++c) {
+            if (tid < CLANES) {     // one lane per class: its rank among the present classes and where its segment starts
+                const bool present = tid < NCLS && ccount[tid & (NCLS - 1)] > 0;
+                const u64 mine = present ? cmax[tid & (NCLS - 1)] : 0ull;
+                int r = 0, start = 0, npc = 0;
+                for (int c = 0; c < NCLS; ++c) {
                     const bool before = ccount[c] > 0 && cmax[c] > mine;
                     r += before ? 1 : 0;
                     start += before ? ccount[c] : 0;
+                    if constexpr (NCLS > 64) npc += ccount[c] > 0 ? 1 : 0;
                 }
-                const int np = __popcll(__ballot(present));
-                if (tid < 32) crank[tid] = r;
+                int np;
+                if constexpr (NCLS > 64) np = npc;
+                else np = __popcll(__ballot(present));
+                if (tid < NCLS) crank[tid] = r;
                 if (present) segstart[r] = start;
                 if (tid == 0) { s_npresent = np; segstart[np] = m; }
             }
@@ -696,7 +815,7 @@ __device__ __forceinline__ void detect_image_body(const DetectArgs& p, const int
                     const u64 kj = skey[j];
                     const bool g = kj > ki;
                     gt += g ? 1 : 0;
-                    cgt += (g && ((kj ^ ki) & 31ull) == 0ull) ? 1 : 0;
+                    cgt += (g && ((kj ^ ki) & CMASK) == 0ull) ? 1 : 0;
                 }
                 if (gt) atomicAdd(&s_pos[i], gt);
                 if (cgt) atomicAdd(&s_cpos[i], cgt);
@@ -713,22 +832,25 @@ __device__ __forceinline__ void detect_image_body(const DetectArgs& p, const int
         for (int r = 0; r < PER; ++r) {
             const int i = tid + DET_THREADS * r;
             if (i < n && pos[r] < m) {
-                const int c = (int)(mykey[r] & 31ull);
+                const int c = (int)(mykey[r] & CMASK);
                 atomicMin(&firstpos[c], pos[r]);
                 atomicAdd(&ccount[c], 1);
             }
         }
         __syncthreads();
-        if (tid < 64) {         // one lane per class: its rank among the present classes and where its segment starts
-            const int mine = tid < 32 ? firstpos[tid] : INT_MAX;
-            int r = 0, start = 0;
-            for (int c = 0; c < 32; ++c) {
+        if (tid < CLANES) {     // one lane per class: its rank among the present classes and where its segment starts
+            const int mine = tid < NCLS ? firstpos[tid] : INT_MAX;
+            int r = 0, start = 0, npc = 0;
+            for (int c = 0; c < NCLS; ++c) {
                 const bool before = firstpos[c] < mine;
                 r += before ? 1 : 0;
                 start += before ? ccount[c] : 0;
+                if constexpr (NCLS > 64) npc += firstpos[c] != INT_MAX ? 1 : 0;
             }
-            const int np = __popcll(__ballot(mine != INT_MAX));
-            if (tid < 32) crank[tid] = r;
+            int np;
+            if constexpr (NCLS > 64) np = npc;
+            else np = __popcll(__ballot(mine != INT_MAX));
+            if (tid < NCLS) crank[tid] = r;
             if (p.do_nms && mine != INT_MAX) segstart[r] = start;
             if (tid == 0) {     // decode-only mode: one group in confidence order, no suppression
                 s_npresent = p.do_nms ? np : 0;
@@ -743,7 +865,7 @@ __device__ __forceinline__ void detect_image_body(const DetectArgs& p, const int
             const int i = tid + DET_THREADS * r;
             if (i < n && pos[r] < m) {
                 const u64 key = mykey[r];
-                const int q = p.do_nms ? segstart[crank[(int)(key & 31ull)]] + cpos[r] : pos[r];
+                const int q = p.do_nms ? segstart[crank[(int)(key & CMASK)]] + cpos[r] : pos[r];
                 const int a = 32767 - (int)((key >> 8) & 0xFFFFull);
                 int bx[4], nb[4];
                 decode_box(loc[r], anc[r], bx);
@@ -757,7 +879,7 @@ __device__ __forceinline__ void detect_image_body(const DetectArgs& p, const int
         __syncthreads();
         for (int r = wave; r < s_npresent; r += DET_WAVES) nms_segment(nbox, alive, segstart[r], segstart[r + 1] - segstart[r], lane);
         __syncthreads();
-        detect_emit(p, b, m, alive, [&](int q) { return okey[q]; }, [&](int q) { return box[q]; }, s_wtot);
+        detect_emit<NCLS>(p, b, m, alive, [&](int q) { return okey[q]; }, [&](int q) { return box[q]; }, s_wtot);
         return;
     }
 
@@ -784,25 +906,25 @@ __device__ __forceinline__ void detect_image_body(const DetectArgs& p, const int
     const int m = p.cap >= 0 ? min(n, p.cap) : n;          // detections_cap (ssdutils.py:207-210)
 
     // ---- class groups in first-appearance order (defaultdict, ssdutils.py:311-314) ----
-    if (tid < 32) { firstpos[tid] = INT_MAX; ccount[tid] = 0; }
+    if (tid < NCLS) { firstpos[tid] = INT_MAX; ccount[tid] = 0; }
     __syncthreads();
     for (int i = tid; i < m; i += DET_THREADS) {
-        const int c = (int)(g1[i] & 31ull);
+        const int c = (int)(g1[i] & CMASK);
         atomicMin(&firstpos[c], i);
         atomicAdd(&ccount[c], 1);
     }
     __syncthreads();
-    if (tid < 32) {
+    if (tid < NCLS) {
         int r = 0;
-        for (int c = 0; c < 32; ++c)
+        for (int c = 0; c < NCLS; ++c)
             if (firstpos[c] < firstpos[tid]) ++r;
-        crank[tid] = (firstpos[tid] == INT_MAX) ? 31 : (p.do_nms ? r : 0);
+        crank[tid] = (firstpos[tid] == INT_MAX) ? NCLS - 1 : (p.do_nms ? r : 0);
     }
     __syncthreads();
     if (tid == 0) {
         int np = 0;
         if (p.do_nms) {     // decode-only mode: one group in confidence order, no suppression
-            for (int c = 0; c < 32; ++c)
+            for (int c = 0; c < NCLS; ++c)
                 if (firstpos[c] != INT_MAX) { order_cls[crank[c]] = c; ++np; }
             int acc = 0;
             for (int r = 0; r < np; ++r) { segstart[r] = acc; acc += ccount[order_cls[r]]; }
@@ -817,7 +939,7 @@ __device__ __forceinline__ void detect_image_body(const DetectArgs& p, const int
     u64* k2 = m2 <= DET_LDS_KEYS ? lkeys : g2;
     for (int i = tid; i < m2; i += DET_THREADS) {
         u64 key = ~0ull;
-        if (i < m) key = ((u64)crank[(int)(g1[i] & 31ull)] << 32) | (u64)i;
+        if (i < m) key = ((u64)crank[(int)(g1[i] & CMASK)] << 32) | (u64)i;
         k2[i] = ~key;
     }
     __syncthreads();
@@ -842,12 +964,13 @@ __device__ __forceinline__ void detect_image_body(const DetectArgs& p, const int
     __syncthreads();
 
     // ---- compact survivors in order; the caller's [:max_out] -------------------------------
-    detect_emit(p, b, m, alive, [&](int q) { return g1[(int)((~k2[q]) & 0xFFFFFFFFull)]; }, [&](int q) { return box[q]; }, s_wtot);
+    detect_emit<NCLS>(p, b, m, alive, [&](int q) { return g1[(int)((~k2[q]) & 0xFFFFFFFFull)]; }, [&](int q) { return box[q]; }, s_wtot);
 }
 
+template <int NCLS>
 __global__ __launch_bounds__(DET_THREADS) void detect_image_kernel(DetectArgs p) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[DET_SMEM];
-    detect_image_body(p, blockIdx.x, smem);
+    detect_image_body<NCLS>(p, blockIdx.x, smem);
 }
 
 // (Round 4 also built the pass as ONE launch -- scan workgroups taking a ticket per image, the last arriver running that image's
@@ -876,7 +999,7 @@ size_t detect_ws_bytes(int B, int A) {
 void detect(int A, int num_classes, const double* anchors, const float* pred, int B, float conf_thr, int cap, int max_out,
             int out_cap, bool nms, const DetectOut& out, void* ws, hipStream_t s) {
     SSD_REQUIRE(A <= 32767 && A <= DET_MAX_ALIVE, "detect: at most 32767 anchors (got %d)", A);
-    SSD_REQUIRE(num_classes >= 1 && num_classes <= 27, "detect: 1..27 classes");
+    require_num_classes(num_classes);
     SSD_REQUIRE(A >= SCAN_ROWS, "detect: at least %d anchors", SCAN_ROWS);
     SSD_REQUIRE(out_cap >= 1, "detect: out_cap must be >= 1");
     SSD_REQUIRE((long long)B * A < (1LL << 31), "detect: batch * anchors must stay below 2^31");
@@ -892,10 +1015,17 @@ void detect(int A, int num_classes, const double* anchors, const float* pred, in
     int* nbox = (int*)base;
     const size_t rows = (size_t)B * A;
     const int blocks = (int)((rows + SCAN_ROWS - 1) / SCAN_ROWS);
+    // Up to 27 classes the kernels measured on the 20-class workload (a thread per row, 32-entry class tables); wider rows
+    // take the chunked scan and the 128-entry tables, which the narrow path would outgrow in LDS (scan) and key bits.
+    const bool wide = nv > SCAN_MAXV;
     {
         ProfScope prof("detect_scan", 0.0, (double)rows * nv * 4.0, s);
-        hipLaunchKernelGGL(detect_scan_kernel, dim3(blocks), dim3(256), (size_t)SCAN_ROWS * nv * sizeof(float), s, A, nv, B, pred,
-                           conf_thr, dense, bcount);
+        if (wide)
+            hipLaunchKernelGGL(detect_scan_wide_kernel, dim3(blocks), dim3(256), (size_t)SCANW_ROWS * nv * sizeof(float), s, A, nv, B,
+                               pred, conf_thr, dense, bcount);
+        else
+            hipLaunchKernelGGL(detect_scan_kernel, dim3(blocks), dim3(256), (size_t)SCAN_ROWS * nv * sizeof(float), s, A, nv, B, pred,
+                               conf_thr, dense, bcount);
     }
     DetectArgs a{};
     a.A = A; a.A2 = A2; a.nv = nv; a.B = B; a.anchors = anchors; a.pred = pred;
@@ -903,7 +1033,10 @@ void detect(int A, int num_classes, const double* anchors, const float* pred, in
     a.keys1 = keys1; a.keys2 = keys2; a.box = box; a.nbox = nbox; a.out = out;
     {
         ProfScope prof("detect_image", 0.0, 0.0, s);
-        hipLaunchKernelGGL(detect_image_kernel, dim3(B), dim3(DET_THREADS), 0, s, a);
+        if (wide)
+            hipLaunchKernelGGL(detect_image_kernel<128>, dim3(B), dim3(DET_THREADS), 0, s, a);
+        else
+            hipLaunchKernelGGL(detect_image_kernel<32>, dim3(B), dim3(DET_THREADS), 0, s, a);
     }
     HIP_OK(hipGetLastError());
 }

@@ -40,6 +40,13 @@ inline void fail(const char* fmt, ...) {
         if (!(cond)) ::ssd::fail(__VA_ARGS__);         \
     } while (0)
 
+// The supported class range of every entry point (network, label encoders, decode): the decode's 64-bit candidate
+// key holds the class id in bits 0-6 (boxes.hip), so 1..127 classes, i.e. at most 132 values per anchor row.
+constexpr int MAX_CLASSES = 127;
+inline void require_num_classes(int num_classes) {
+    SSD_REQUIRE(num_classes >= 1 && num_classes <= MAX_CLASSES, "num_classes must be in 1..%d (got %d)", MAX_CLASSES, num_classes);
+}
+
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // RAII: make `device` the calling thread's current HIP device for the scope and put the caller's

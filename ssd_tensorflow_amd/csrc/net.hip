@@ -584,6 +584,7 @@ void Net::pool_fusion(int* out, int cap, int* count) const {
 size_t Net::arena_floats(const char* preset, int num_classes) {
     // cheap: build the graph description only
     const Preset& p = get_preset(preset);
+    require_num_classes(num_classes);
     const int nv = num_classes + 5;
     size_t n = 0;
     auto cv = [&](int k, int ci, int co) { n += (size_t)k * k * ci * co + co; };
@@ -735,7 +736,7 @@ Net::Net(const char* preset, int num_classes, int max_batch, int device, bool tr
          float* ext_params, float* ext_grads, float* ext_momentum, int dtype)
     : preset_(&get_preset(preset)), C_(num_classes), Bmax_(max_batch), device_(device), training_(training), bf16_(dtype == 1) {
     SSD_REQUIRE(dtype == 0 || dtype == 1, "dtype must be 0 (fp32) or 1 (bf16), got %d", dtype);
-    SSD_REQUIRE(num_classes >= 1 && num_classes <= 27, "num_classes must be in 1..27 (got %d)", num_classes);
+    require_num_classes(num_classes);
     SSD_REQUIRE(max_batch >= 1, "max_batch must be >= 1");
     HIP_OK(hipSetDevice(device));
     params_ = ext_params; grads_ = ext_grads; mom_ = ext_momentum;

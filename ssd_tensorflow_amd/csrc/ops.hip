@@ -836,23 +836,41 @@ constexpr int MAXV = 32;   // nvars <= 32  (num_classes <= 27)
 // with 16-byte loads; thread (cell = t & 31, j = t >> 5) works on one anchor from LDS at odd strides.
 constexpr int HCH = 32;
 constexpr int HTHREADS = 256;               // 32 cells x 8 type slots (nj <= 8)
+constexpr int HSLOTS = HTHREADS / HCH;      // box type slots per workgroup
+// Rows wider than MAXV (num_classes > 27) go to heads_wide_kernel on workgroups of hch = 16, 8 or 4 cells, the largest
+// whose LDS tile fits HEAD_LDS_MAX; its HSLOTS * hch anchors then get HTHREADS / (HSLOTS * hch) = 2, 4 or 8 lanes each.
+constexpr size_t HEAD_LDS_MAX = 64 * 1024;
 struct HeadGrid {
     int blk_off[MAX_MAPS + 1];              // first workgroup of each map
     int nchunk[MAX_MAPS];                   // cell chunks per image
     int ldp_max, nj_max;
+    int hch, lg_hch;                        // cells per workgroup (HCH for rows of <= MAXV values), its log2
 };
+static size_t heads_lds_floats(int hch, int ldp_max, int nj_max, int nv) {
+    return (size_t)hch * ldp_max + (size_t)nj_max * hch * nv;
+}
 static HeadGrid head_grid(const HeadLayout& L, int B) {
     HeadGrid g{};
-    int off = 0;
     for (int i = 0; i < L.nmaps; ++i) {
-        g.blk_off[i] = off;
-        g.nchunk[i] = (L.hw[i] + HCH - 1) / HCH;
-        off += g.nchunk[i] * B;
         g.ldp_max = std::max(g.ldp_max, L.ld[i] + 1);
         g.nj_max = std::max(g.nj_max, L.nj[i]);
     }
+    SSD_REQUIRE(g.nj_max <= HSLOTS, "heads: at most %d box types per map", HSLOTS);
+    SSD_REQUIRE(L.nvars <= MAX_CLASSES + 5, "heads: num_classes + 5 must be <= %d", MAX_CLASSES + 5);
+    g.hch = HCH;
+    if (L.nvars > MAXV) {
+        g.hch = HCH / 2;
+        while (g.hch > 4 && heads_lds_floats(g.hch, g.ldp_max, g.nj_max, L.nvars) * sizeof(float) > HEAD_LDS_MAX) g.hch >>= 1;
+        SSD_REQUIRE(heads_lds_floats(g.hch, g.ldp_max, g.nj_max, L.nvars) * sizeof(float) <= HEAD_LDS_MAX, "heads: tile too large");
+    }
+    g.lg_hch = __builtin_ctz(g.hch);
+    int off = 0;
+    for (int i = 0; i < L.nmaps; ++i) {
+        g.blk_off[i] = off;
+        g.nchunk[i] = (L.hw[i] + g.hch - 1) / g.hch;
+        off += g.nchunk[i] * B;
+    }
     for (int i = L.nmaps; i <= MAX_MAPS; ++i) g.blk_off[i] = off;
-    SSD_REQUIRE(g.nj_max <= HTHREADS / HCH, "heads: at most %d box types per map", HTHREADS / HCH);
     return g;
 }
 struct HeadBlock {
@@ -867,8 +885,8 @@ __device__ __forceinline__ HeadBlock head_block(const HeadLayout& L, const HeadG
     HeadBlock r;
     r.map = i;
     r.b = local / G.nchunk[i];
-    r.cell0 = (local - r.b * G.nchunk[i]) * HCH;
-    r.ncell = min(HCH, L.hw[i] - r.cell0);
+    r.cell0 = (local - r.b * G.nchunk[i]) << G.lg_hch;
+    r.ncell = min(G.hch, L.hw[i] - r.cell0);
     return r;
 }
 
@@ -1011,17 +1029,108 @@ __global__ __launch_bounds__(HTHREADS) void heads_kernel(HeadLayout L, HeadGrid 
     }
 }
 
+// heads_kernel for rows of more than MAXV values (num_classes 28..127): same results, same tiles and global runs, but
+// G.hch (16, 8 or 4) cells per workgroup and a group of gl = HTHREADS / (HSLOTS * hch) lanes per anchor.  The lanes of a
+// group stride the anchor's values in LDS (no per-value register arrays, so no spills at any width); max, sum of
+// exponentials, cross-entropy and smooth-L1 meet by xor-shuffles inside the group (one wave holds whole groups).
+template <bool TRAIN>
+__global__ __launch_bounds__(HTHREADS) void heads_wide_kernel(HeadLayout L, HeadGrid G, int B, float* __restrict__ result,
+                                                              const float* __restrict__ labels, float* __restrict__ ce_out,
+                                                              float* __restrict__ sl1_out, unsigned char* __restrict__ pos_out) {
+    extern __shared__ __attribute__((aligned(16))) float hsm[];
+    const HeadBlock k = head_block(L, G);
+    const int hch = G.hch;
+    const int nv = L.nvars, nc = nv - 4;
+    const int ld = L.ld[k.map], ldp = ld + 1, nj = L.nj[k.map], hw = L.hw[k.map];
+    float* hin = hsm;                         // [hch][ldp]   raw head outputs, odd row pitch
+    float* rec = hsm + hch * G.ldp_max;       // [nj][hch][nv] labels in, result out
+    const size_t a0 = (size_t)k.b * L.A + L.off[k.map] + k.cell0;
+    const int nrec = k.ncell * nv;
+    const float* src = L.buf[k.map] + ((size_t)k.b * hw + k.cell0) * ld;      // contiguous, 16-byte aligned rows
+    const int n4 = (k.ncell * ld) >> 2;
+#pragma unroll 4
+    for (int i = threadIdx.x; i < n4; i += HTHREADS) {
+        const f32x4 v = ld4(src + 4 * i);
+        const int row = (4 * i) / ld, col = 4 * i - row * ld;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) hin[row * ldp + col + e] = v[e];
+    }
+    if constexpr (TRAIN)
+        for (int j = 0; j < nj; ++j) run_to_lds(rec + j * hch * nv, labels + (a0 + (size_t)j * hw) * nv, nrec);
+    __syncthreads();
+    const int lg_gl = __builtin_ctz(HTHREADS / HSLOTS) - G.lg_hch, gl = 1 << lg_gl;
+    const int slot = threadIdx.x >> lg_gl, lane = threadIdx.x & (gl - 1);
+    const int cell = slot & (hch - 1), j = slot >> G.lg_hch;
+    if (cell < k.ncell && j < nj) {           // uniform over the lane group
+        const float* z = hin + cell * ldp + j * nv;
+        float* r = rec + (j * hch + cell) * nv;
+        const bool pos = TRAIN && r[nc - 1] == 0.f;     // read before any lane of the group overwrites the record
+        float m = -__builtin_inff();
+        for (int c = lane; c < nc; c += gl) m = fmaxf(m, z[c]);
+        for (int o = gl >> 1; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        // the exponential as in heads_kernel (hardware v_exp_f32 on z - max, log once)
+        float se = 0.f;
+        for (int c = lane; c < nc; c += gl) se += __expf(z[c] - m);
+        for (int o = gl >> 1; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
+        const float lse = m + logf(se);
+        const float inv = 1.f / se;
+        float ce = 0.f, sl = 0.f;
+        for (int c = lane; c < nc; c += gl) {
+            const float zc = z[c];
+            if constexpr (TRAIN) {
+                const float y = r[c];
+                if (y != 0.f) ce += y * (lse - zc);
+            }
+            r[c] = __expf(zc - m) * inv;
+        }
+        for (int c = nc + lane; c < nv; c += gl) {
+            const float zc = z[c];
+            if constexpr (TRAIN) {
+                const float d = zc - r[c];
+                const float ad = fabsf(d);
+                sl += ad < 1.f ? 0.5f * d * d : ad - 0.5f;
+            }
+            r[c] = zc;
+        }
+        if constexpr (TRAIN) {
+            for (int o = gl >> 1; o > 0; o >>= 1) {
+                ce += __shfl_xor(ce, o, 64);
+                sl += __shfl_xor(sl, o, 64);
+            }
+            if (lane == 0) {
+                const size_t idx = a0 + (size_t)j * hw + cell;
+                ce_out[idx] = ce;
+                sl1_out[idx] = pos ? sl : 0.f;
+                pos_out[idx] = pos ? 1 : 0;
+            }
+        }
+    }
+    __syncthreads();
+    for (int jj = 0; jj < nj; ++jj) lds_to_run(result + (a0 + (size_t)jj * hw) * nv, rec + jj * hch * nv, nrec);
+}
+
 static size_t heads_lds_bytes(const HeadLayout& L, const HeadGrid& G) {
-    return ((size_t)HCH * G.ldp_max + (size_t)G.nj_max * HCH * L.nvars) * sizeof(float);
+    return heads_lds_floats(G.hch, G.ldp_max, G.nj_max, L.nvars) * sizeof(float);
+}
+
+// Rows of <= MAXV values keep heads_kernel (one thread per anchor, the row in registers), the 20-class path as measured;
+// wider rows, whose register arrays would spill, take heads_wide_kernel.  Chosen by L.nvars, fixed for a handle.
+template <bool TRAIN>
+static void launch_heads(const HeadLayout& L, const HeadGrid& G, int B, float* result, const float* labels, float* ce, float* sl1,
+                         unsigned char* pos, hipStream_t s) {
+    if (L.nvars <= MAXV)
+        hipLaunchKernelGGL(heads_kernel<TRAIN>, dim3(G.blk_off[MAX_MAPS]), dim3(HTHREADS), heads_lds_bytes(L, G), s, L, G, B, result,
+                           labels, ce, sl1, pos);
+    else
+        hipLaunchKernelGGL(heads_wide_kernel<TRAIN>, dim3(G.blk_off[MAX_MAPS]), dim3(HTHREADS), heads_lds_bytes(L, G), s, L, G, B,
+                           result, labels, ce, sl1, pos);
 }
 
 void heads_result(const HeadLayout& L, int B, float* result, hipStream_t s) {
-    SSD_REQUIRE(L.nvars <= MAXV, "heads: num_classes + 5 must be <= %d", MAXV);
     const int total = B * L.A;
     const HeadGrid G = head_grid(L, B);
     ProfScope prof("heads_result", 0.0, 8.0 * total * L.nvars, s);
-    hipLaunchKernelGGL(heads_kernel<false>, dim3(G.blk_off[MAX_MAPS]), dim3(HTHREADS), heads_lds_bytes(L, G), s, L, G, B, result,
-                       nullptr, nullptr, nullptr, nullptr);
+    launch_heads<false>(L, G, B, result, nullptr, nullptr, nullptr, nullptr, s);
     HIP_OK(hipGetLastError());
 }
 
@@ -1299,7 +1408,6 @@ void l2_partials(const float* filters, size_t nfilters, LossWork& w, hipStream_t
 
 void multibox_loss(const HeadLayout& L, int B, int b_off, int B_total, const float* result, const float* labels, LossWork& w,
                    float weight_decay, float bnorm, hipStream_t s) {
-    SSD_REQUIRE(L.nvars <= MAXV, "heads: num_classes + 5 must be <= %d", MAXV);
     SSD_REQUIRE(L.A <= 32 * LS_THREADS, "loss: at most %d anchors", 32 * LS_THREADS);
     SSD_REQUIRE(B_total <= LS_THREADS / 2, "loss: at most %d images per step", LS_THREADS / 2);
     const int total = B * L.A;
@@ -1307,8 +1415,7 @@ void multibox_loss(const HeadLayout& L, int B, int b_off, int B_total, const flo
     if (!(bnorm > 0.f)) bnorm = (float)B_total;          // reduce_mean over this step's own batch (ssdvgg.py:520,559)
     const size_t o = (size_t)b_off * L.A;                // this launch's slice of the per-anchor work arrays
     ProfScope prof("multibox_loss", 0.0, 12.0 * total * L.nvars, s);
-    hipLaunchKernelGGL(heads_kernel<true>, dim3(G.blk_off[MAX_MAPS]), dim3(HTHREADS), heads_lds_bytes(L, G), s, L, G, B,
-                       const_cast<float*>(result), labels, w.ce + o, w.sl1 + o, w.pos + o);
+    launch_heads<true>(L, G, B, const_cast<float*>(result), labels, w.ce + o, w.sl1 + o, w.pos + o, s);
     const int pt = (L.A + LS_THREADS - 1) / LS_THREADS;
     if (pt <= 9)
         hipLaunchKernelGGL(loss_sample_kernel<9>, dim3(B), dim3(LS_THREADS), 0, s, B_total, b_off, L.A, bnorm, w.ce, w.sl1, w.pos, w.sel, w.sample,
@@ -1333,14 +1440,17 @@ __global__ __launch_bounds__(HTHREADS) void loss_grad_kernel(HeadLayout L, HeadG
                                                              const unsigned char* __restrict__ pos,
                                                              const unsigned char* __restrict__ sel,
                                                              const float* __restrict__ sample) {
-    extern __shared__ __attribute__((aligned(16))) float gsm[];      // [HCH][ld]
+    extern __shared__ __attribute__((aligned(16))) float gsm[];      // [G.hch][ld]
     const HeadBlock k = head_block(L, G);
     const int nv = L.nvars, nc = nv - 4;
     const int ld = L.ld[k.map], nj = L.nj[k.map], hw = L.hw[k.map];
     const int n4 = (k.ncell * ld) >> 2;
     for (int i = threadIdx.x; i < n4; i += HTHREADS) *reinterpret_cast<f32x4*>(gsm + 4 * i) = f32x4{0.f, 0.f, 0.f, 0.f};
     __syncthreads();
-    const int cell = threadIdx.x & (HCH - 1), j = threadIdx.x / HCH;
+    // HSLOTS * G.hch anchors, gl lanes each striding its columns (gl = 1 at G.hch = HCH: one thread per anchor)
+    const int lg_gl = __builtin_ctz(HTHREADS / HSLOTS) - G.lg_hch, gl = 1 << lg_gl;
+    const int slot = threadIdx.x >> lg_gl, lane = threadIdx.x & (gl - 1);
+    const int cell = slot & (G.hch - 1), j = slot >> G.lg_hch;
     if (cell < k.ncell && j < nj) {
         const size_t idx = (size_t)k.b * L.A + L.off[k.map] + (size_t)j * hw + k.cell0 + cell;
         const bool isel = sel[idx], ipos = pos[idx];
@@ -1350,9 +1460,9 @@ __global__ __launch_bounds__(HTHREADS) void loss_grad_kernel(HeadLayout L, HeadG
             const float* y = labels + idx * nv;
             float* dst = gsm + cell * ld + j * nv;
             if (isel)
-                for (int c = 0; c < nc; ++c) dst[c] = (r[c] - y[c]) * wb;
+                for (int c = lane; c < nc; c += gl) dst[c] = (r[c] - y[c]) * wb;
             if (ipos)
-                for (int c = nc; c < nv; ++c) dst[c] = fminf(fmaxf(r[c] - y[c], -1.f), 1.f) * wb;
+                for (int c = nc + lane; c < nv; c += gl) dst[c] = fminf(fmaxf(r[c] - y[c], -1.f), 1.f) * wb;
         }
     }
     __syncthreads();
@@ -1364,7 +1474,7 @@ void multibox_loss_grad(const HeadLayout& L, int B, int b_off, const float* resu
                         hipStream_t s) {
     const int total = B * L.A;
     const HeadGrid G = head_grid(L, B);
-    const size_t lds = (size_t)HCH * (G.ldp_max - 1) * sizeof(float);
+    const size_t lds = (size_t)G.hch * (G.ldp_max - 1) * sizeof(float);
     const size_t o = (size_t)b_off * L.A;
     ProfScope prof("multibox_loss_grad", 0.0, (L.grad_bf16 ? 10.0 : 12.0) * total * L.nvars, s);
     if (L.grad_bf16)

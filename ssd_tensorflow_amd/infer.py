@@ -18,7 +18,7 @@ import numpy as np
 from .average_precision import APCalculator, APs2mAP
 from .ssdvgg import SSDVGG, Session
 from .ssdutils import get_preset_by_name, boxes_from_detection
-from .training_data import VOC_NAMES
+from .training_data import default_class_names
 from .pascal_summary import PascalSummary
 from .utils import Size, str2bool, load_data_source
 
@@ -57,6 +57,16 @@ def sample_generator(samples, image_size, batch_size, device=0):
         yield x, idxs, sizes
 
 
+def resolve_class_names(num_classes, source_names=None, stored=None):
+    """{class id: name}: the data source's names, else the checkpoint's __class_names__, else (a checkpoint written before
+    names were stored, or no checkpoint) the VOC names for 20 classes and 'class_<id>' otherwise."""
+    if source_names is not None:
+        return dict(source_names)
+    if stored is not None:
+        return {i: str(n) for i, n in enumerate(stored)}
+    return dict(enumerate(default_class_names(num_classes)))
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description='SSD inference')
     parser.add_argument('files', type=str, nargs='*', help='image files (anything Pillow decodes, or .npy arrays)')
@@ -75,6 +85,7 @@ def main(argv=None):
     parser.add_argument('--pascal-summary', type=str2bool, default='False', help='dump the detections in Pascal VOC format')
     parser.add_argument('--synthetic', type=int, default=0, help='run on N synthetic images instead of files')
     parser.add_argument('--preset', default=None, help='preset when no checkpoint is given (random weights)')
+    parser.add_argument('--num-classes', type=int, default=20, help='class count when no checkpoint is given (1..127)')
     parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='f32, or bf16 activations on the bf16 matrix cores')
     args = parser.parse_args(argv)
 
@@ -111,7 +122,6 @@ def main(argv=None):
     # ---- data source (infer.py:147-171) ----------------------------------------------------------
     compute_stats = False
     source, samples = None, None
-    lid2name = dict(enumerate(VOC_NAMES))
     if args.data_source:
         print('[i] Configuring the data source...')
         try:
@@ -126,18 +136,25 @@ def main(argv=None):
             print('[i] # classes:         ', source.num_classes)
         except (ImportError, AttributeError, RuntimeError, OSError) as e:
             print('[!] Unable to load data source:', str(e)); return 1
-        lid2name = source.lid2name
         compute_stats = bool(args.compute_stats)
 
     with Session(0) as sess:
         print('[i] Creating the model...')
+        stored_names = None
         if ckpt:
-            pname = str(np.load(ckpt)['__preset__'])
+            with np.load(ckpt, allow_pickle=False) as ck:
+                pname, num_classes = str(ck['__preset__']), int(ck['__num_classes__'])
+                if '__class_names__' in ck.files:
+                    stored_names = ck['__class_names__']
             net = SSDVGG(sess, get_preset_by_name(pname))
             net.build_from_metagraph(None, ckpt, max_batch=args.batch_size, dtype=args.dtype)
         else:
+            num_classes = args.num_classes
             net = SSDVGG(sess, get_preset_by_name(args.preset))
-            net.build_from_vgg(None, 20, max_batch=args.batch_size, training=False, dtype=args.dtype)
+            net.build_from_vgg(None, num_classes, max_batch=args.batch_size, training=False, dtype=args.dtype)
+        lid2name = resolve_class_names(num_classes, source.lid2name if source else None, stored_names)
+        if not source:
+            print('[i] # classes:         ', num_classes)
         size = net.preset.image_size
         # ---- files to analyse (infer.py:177-193) ----------------------------------------------------
         if source:

@@ -130,6 +130,7 @@ def main(argv=None):
     parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='f32, or bf16 activations on the bf16 matrix cores (fp32 master weights, loss and optimizer)')
     parser.add_argument('--synthetic-train', type=int, default=64, help='synthetic training samples per epoch')
     parser.add_argument('--synthetic-valid', type=int, default=16)
+    parser.add_argument('--synthetic-classes', type=int, default=20, help='class count of the synthetic data sets (1..127)')
     parser.add_argument('--augment', type=str2bool, default='False', help="run the reference's train augmentation recipe (process_dataset.py) on the GPU over a uint8 synthetic dataset")
     parser.add_argument('--allreduce-dtype', default='f32', choices=['f32', 'bf16'], help='data parallel: bf16 = the filter gradients cross the links as bf16 messages of half the bytes (fp32 masters, momentum and arenas untouched)')
     parser.add_argument('--allreduce-bucket-mb', type=float, default=44, help='data parallel: all-reduce finished gradient ranges of >= this many MB while backward still runs (0 = one all-reduce after backward); 44 = three buckets: heads ... mod_conv6 | conv5_x + conv4_3/4_2 | the rest')
@@ -180,7 +181,8 @@ def main(argv=None):
 
     try:
         td = TrainingData(args.data_dir, args.preset, args.synthetic_train, args.synthetic_valid, rank=rank, world=world,
-                          augment=args.augment, device=local, data_source=args.data_source)
+                          augment=args.augment, device=local, data_source=args.data_source,
+                          synthetic_classes=args.synthetic_classes)
     except RuntimeError as e:
         print('[!] Unable to load training data:', str(e)); return 1                       # train.py:155-161
     say('[i] # training samples:   ', td.num_train)
@@ -188,6 +190,7 @@ def main(argv=None):
     say('[i] # classes:            ', td.num_classes)
     say('[i] Image size:           ', td.preset.image_size)
 
+    class_names = [td.lid2name[i] for i in range(td.num_classes)]
     lr = compute_lr(lr_values, lr_boundaries)
     bucket = int(args.allreduce_bucket_mb * 1e6 / 4)
     dev = torch.device('cuda', local)
@@ -262,11 +265,11 @@ def main(argv=None):
             # ---- checkpoint (train.py:336-343) -------------------------------------------------
             if (e + 1) % args.checkpoint_interval == 0 and rank == 0:
                 path = '{}/e{}.npz'.format(args.name, e + 1)
-                net.save_checkpoint(path, lr, args.momentum, args.weight_decay)
+                net.save_checkpoint(path, lr, args.momentum, args.weight_decay, class_names=class_names)
                 print('[i] Checkpoint saved:', path)
         if rank == 0:
             path = '{}/final.npz'.format(args.name)
-            net.save_checkpoint(path, lr, args.momentum, args.weight_decay)
+            net.save_checkpoint(path, lr, args.momentum, args.weight_decay, class_names=class_names)
             print('[i] Checkpoint saved:', path)
         if writer is not None:
             writer.close()

@@ -57,6 +57,16 @@ VOC_NAMES = ['aeroplane', 'bicycle', 'bird', 'boat', 'bottle', 'bus', 'car', 'ca
              'horse', 'motorbike', 'person', 'pottedplant', 'sheep', 'sofa', 'train', 'tvmonitor']
 
 DEVICE_SLOTS = 3            # one under the step, one ready, one being filled
+MAX_CLASSES = 127           # the library's range: 1..127 classes (include/ssdvgg_hip.h)
+
+
+def default_class_names(num_classes):
+    """Names of classes no data source names: the VOC names for 20 classes, else 'class_<id>'."""
+    if num_classes == len(VOC_NAMES):
+        return list(VOC_NAMES)
+    return ['class_%d' % i for i in range(num_classes)]
+
+
 CACHE_SYNTHETIC_UP_TO = 4096  # synthetic "files" kept in RAM (a real source reads its files instead)
 
 
@@ -376,7 +386,7 @@ class TrainingData:
 
     def __init__(self, data_dir=None, preset='vgg300', num_train=64, num_valid=16, seed=1234, rank=0, world=1,
                  augment=False, sampler_trials=50, expand_prob=0.5, device=0, device_tensors=True,
-                 data_source='pascal_voc', valid_fraction=0.025, images=None):
+                 data_source='pascal_voc', valid_fraction=0.025, images=None, synthetic_classes=20):
         self.preset = get_preset_by_name(preset) if isinstance(preset, str) else preset
         self.seed, self.rank, self.world = seed, rank, world
         self.epoch = 0
@@ -412,9 +422,12 @@ class TrainingData:
                 'train': _Recipe(self, 'train', self.num_train, 0, _SampleAt(self, 'train', 0), self.train_transforms),
                 'valid': _Recipe(self, 'valid', self.num_valid, 1 << 20, _SampleAt(self, 'valid', 1 << 20), self.valid_transforms)}
         else:
-            self.num_classes = 20
+            # the synthetic sets: `synthetic_classes` class ids ('shapes' draws its textures from the first four)
+            if not 1 <= int(synthetic_classes) <= MAX_CLASSES:
+                raise RuntimeError('synthetic_classes must be in 1..%d (got %s)' % (MAX_CLASSES, synthetic_classes))
+            self.num_classes = int(synthetic_classes)
             self.label_colors = {}
-            self.lid2name = dict(enumerate(VOC_NAMES))
+            self.lid2name = dict(enumerate(default_class_names(self.num_classes)))
             self.lname2id = {n: i for i, n in self.lid2name.items()}
             self.num_train, self.num_valid = num_train, num_valid
             self.augment = bool(augment)
@@ -470,7 +483,7 @@ class TrainingData:
         return encode_labels_batch(self.preset, self.num_classes, bxs, cls)
 
     # ---- the learnable synthetic set ('shapes') --------------------------------------------------------------------
-    SHAPE_CLASSES = 4      # textures, booked under the first four of the 20 class ids (the net keeps the benchmark's shape)
+    SHAPE_CLASSES = 4      # textures, booked under the first four class ids (the net keeps the benchmark's shape)
 
     def _shapes_canvas(self, rng, W, H):
         """uint8 BGR image [H, W, 3] + boxes: 1..3 non-overlapping rectangles of 20..50 % of the frame on low-contrast
@@ -490,7 +503,7 @@ class TrainingData:
                     break
         boxes = []
         for cx, cy, w, h in placed:
-            c = int(rng.integers(0, self.SHAPE_CLASSES))
+            c = int(rng.integers(0, min(self.SHAPE_CLASSES, self.num_classes)))
             x0, x1 = int(round((cx - w / 2) * W)), int(round((cx + w / 2) * W))
             y0, y1 = int(round((cy - h / 2) * H)), int(round((cy + h / 2) * H))
             p = int(rng.integers(5, 12)) * max(1, min(W, H) // 300)          # stripe width in pixels

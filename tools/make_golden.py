@@ -378,5 +378,89 @@ def main():
     print('all golden fixtures written and oracle agrees bit-exactly')
 
 
+def main_c80():
+    """G11 / G12: decode + NMS and labels at 80 classes (the wide kernels), same recipe as G45 / G23."""
+    sys.path.insert(0, ROOT)
+    from oracle import boxes as ob
+    su, ut, tf = import_reference()
+    C = 80
+    for pname in ('vgg300', 'vgg512'):
+        preset = su.get_preset_by_name(pname)
+        ref_anchors = su.get_anchors_for_preset(preset)
+        A = len(ref_anchors)
+        anch_abs = su.anchors2array(ref_anchors, ut.Size(1000, 1000))
+        o_anch = ob.anchors(ob.get_preset(pname))
+
+        # ---- G12 labels: LabelCreatorTransform (compute_location) at 80 classes -----------------------------
+        rng = np.random.default_rng(111 if pname == 'vgg300' else 112)
+        lab = tf.LabelCreatorTransform(preset=preset, num_classes=C)
+        g12 = {}
+        ncase = 8
+        for ci in range(ncase):
+            n = int(rng.integers(1, 7))
+            w = rng.uniform(0.1, 0.6, n); h = rng.uniform(0.1, 0.6, n)
+            g = np.stack([rng.uniform(w / 2, 1 - w / 2), rng.uniform(h / 2, 1 - h / 2), w, h], 1)
+            c = rng.integers(0, C, n)
+            if ci == 0:
+                c[0] = C - 1           # the highest class id
+            boxes = [ut.Box('x', int(k), ut.Point(float(b[0]), float(b[1])), ut.Size(float(b[2]), float(b[3]))) for b, k in zip(g, c)]
+            _, vec, _ = lab(None, None, ut.Sample('f', boxes, ut.Size(1000, 1000)))
+            o_vec = ob.encode_labels(g, c, ob.get_preset(pname), C, o_anch, anch_abs)
+            assert vec.dtype == np.float32 and vec.shape[1] == C + 5 and np.array_equal(vec, o_vec), f'G12 case {ci}'
+            pos = np.nonzero(vec[:, C] == 0)[0]
+            g12[f'gt_{ci}'] = g; g12[f'cls_{ci}'] = c.astype(np.int32)
+            g12[f'pos_{ci}'] = pos.astype(np.int32); g12[f'rows_{ci}'] = vec[pos]
+        g12['ncases'] = np.array([ncase]); g12['num_classes'] = np.array([C])
+        np.savez_compressed(os.path.join(OUT, f'g12_labels_c80_{pname}.npz'), **g12)
+
+        # ---- G11 decode_boxes + suppress_overlaps at 80 classes ----------------------------------------------
+        g11 = {}
+        settings = [(0.5, 200, None), (0.5, None, 200), (0.3, 50, None)]
+        rng = np.random.default_rng(211 if pname == 'vgg300' else 212)
+        npred = 3
+        for pi in range(npred):
+            pred = synth_pred(rng, A, C=C, n_hot=600 if pi == 1 else 300, cluster=6 if pi == 2 else 0, bg=7.0)
+            keep_rows = np.nonzero(pred[:, :C].max(1) >= 0.25)[0]
+            g11[f'predrows_{pi}'] = keep_rows.astype(np.int32)
+            g11[f'predvals_{pi}'] = pred[keep_rows]
+            bgrow = np.zeros(C + 5, np.float32); bgrow[C] = 1
+            dense = np.tile(bgrow, (A, 1)); dense[keep_rows] = pred[keep_rows]
+            pred = dense
+            for si, (thr, cap, max_out) in enumerate(settings):
+                while True:
+                    boxes = su.decode_boxes(pred.copy(), ref_anchors, thr, {}, cap)
+                    confs = np.array([b[0] for b in boxes], np.float32)
+                    if len(np.unique(confs)) == len(confs):
+                        break
+                    assert thr < 0.9, 'fixture must avoid exact ties'
+                    thr = round(thr * 1.2, 4)     # tie order is not contractual: move off it
+                absb = np.array([ut.prop2abs(b[1].center, b[1].size, ut.Size(1000, 1000)) for b in boxes], np.int64).reshape(-1, 4)
+                cls = np.array([b[1].labelid for b in boxes], np.int64)
+                det = ob.decode(pred, o_anch, thr, cap)
+                assert np.array_equal(det['conf'], confs) and np.array_equal(det['cls'], cls), 'G11 decode'
+                assert np.array_equal(ob.nms_roundtrip(det['box']), absb), 'G11 box'
+                sel = su.suppress_overlaps(boxes)
+                if max_out is not None:
+                    sel = sel[:max_out]
+                pos = {float(c): k for k, c in enumerate(confs)}
+                keep = np.array([pos[float(q[0])] for q in sel], np.int64)
+                assert np.array_equal(keep, ob.suppress(det, max_out)), 'G11 keep'
+                tag = f'{pi}_{si}'
+                g11[f'set_{tag}'] = np.array([thr, -1 if cap is None else cap, -1 if max_out is None else max_out], np.float64)
+                g11[f'idx_{tag}'] = det['idx'].astype(np.int32)
+                g11[f'cls_{tag}'] = cls.astype(np.int32)
+                g11[f'conf_{tag}'] = confs
+                g11[f'box_{tag}'] = det['box'].astype(np.int32)
+                g11[f'keep_{tag}'] = keep.astype(np.int32)
+                print(pname, 'c80 pred', pi, 'set', si, 'decoded', len(boxes), 'kept', len(keep), 'classes', len(set(cls.tolist())))
+        g11['npred'] = np.array([npred]); g11['nset'] = np.array([len(settings)])
+        g11['A'] = np.array([A]); g11['num_classes'] = np.array([C])
+        np.savez_compressed(os.path.join(OUT, f'g11_detect_c80_{pname}.npz'), **g11)
+
+
 if __name__ == '__main__':
-    main()
+    if sys.argv[1:] == ['c80']:            # only the 80-class fixtures
+        main_c80()
+    else:
+        main()
+        main_c80()

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times the bare training step (no checks, random inputs) -- the A/B and ablation driver.
-    tools/step_time.py [--dtype bf16|f32] [--preset vgg300] [--batch 32] [--steps 40] [--warmup 10] [--reps 2]
+    tools/step_time.py [--dtype bf16|f32] [--preset vgg300] [--batch 32] [--num-classes 20] [--steps 40] [--warmup 10] [--reps 2]
 prints one line per repetition: ms per step.  Environment switches (SSD_*) select the variant under test."""
 import argparse
 import os
@@ -21,6 +21,7 @@ def main():
     ap.add_argument('--dtype', default='bf16')
     ap.add_argument('--preset', default='vgg300')
     ap.add_argument('--batch', type=int, default=32)
+    ap.add_argument('--num-classes', type=int, default=20)
     ap.add_argument('--steps', type=int, default=40)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--reps', type=int, default=2)
@@ -28,10 +29,10 @@ def main():
     a = ap.parse_args()
     preset = ob.get_preset(a.preset)
     rng = np.random.default_rng(0)
-    x, y, _ = ref.synth_batch(rng, a.batch, preset)
+    x, y, _ = ref.synth_batch(rng, a.batch, preset, a.num_classes)
     with Session(0) as sess:
         net = SSDVGG(sess, a.preset)
-        net.build_from_vgg(None, 20, max_batch=a.batch, dtype=a.dtype)
+        net.build_from_vgg(None, a.num_classes, max_batch=a.batch, dtype=a.dtype)
         net.build_optimizer(learning_rate=1e-4, weight_decay=0.0005, momentum=0.9)
         net.set_stream(torch.cuda.current_stream().cuda_stream)
         xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
