@@ -64,6 +64,9 @@ SIGNATURES = {
     'ssd_create': (i32, [cstr, i32, i32, i32, i32, C.c_ulonglong, vp, vp, vp, C.POINTER(handle)]),
     'ssd_create_dtype': (i32, [cstr, i32, i32, i32, i32, C.c_ulonglong, vp, vp, vp, i32, C.POINTER(handle)]),
     'ssd_get_dtype': (i32, [handle, p_i32]),
+    'ssd_arena_floats_graph': (sz, [cstr, i32, i32]),
+    'ssd_create_graph': (i32, [cstr, i32, i32, i32, i32, C.c_ulonglong, vp, vp, vp, i32, i32, C.POINTER(handle)]),
+    'ssd_graph': (i32, [handle, p_i32]),
     'ssd_destroy': (i32, [handle]),
     'ssd_set_stream': (i32, [handle, vp]),
     'ssd_num_variables': (i32, [handle]),

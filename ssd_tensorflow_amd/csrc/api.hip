@@ -387,6 +387,15 @@ size_t ssd_arena_floats(const char* preset, int num_classes) {
     }
 }
 
+size_t ssd_arena_floats_graph(const char* preset, int num_classes, int graph) {
+    try {
+        return Net::arena_floats(preset, num_classes, graph);
+    } catch (const std::exception& e) {
+        ssd::set_error("%s", e.what());
+        return 0;
+    }
+}
+
 size_t ssd_augment_ws_bytes(int b, int out_w, int out_h) { return augment_ws_bytes(b, out_w, out_h); }
 
 int ssd_augment_batch_dev(const unsigned char* images_dev, const ssd_augment_params* params, int b, int out_w, int out_h,
@@ -420,6 +429,26 @@ int ssd_create_dtype(const char* preset, int num_classes, int max_batch, int dev
                      ext_momentum_dev, dtype);
     SSD_REQUIRE(n->nparams() == Net::arena_floats(preset, num_classes), "arena size mismatch");
     *out = new ssd_net{n};
+    API_END
+}
+
+int ssd_create_graph(const char* preset, int num_classes, int max_batch, int device, int training, unsigned long long seed,
+                     float* ext_params_dev, float* ext_grads_dev, float* ext_momentum_dev, int dtype, int graph, ssd_handle* out) {
+    API_BEGIN
+    SSD_REQUIRE(out != nullptr, "out handle pointer is null");
+    *out = nullptr;
+    DeviceGuard dev_guard_(device);
+    Net* n = new Net(preset, num_classes, max_batch, device, training != 0, seed, ext_params_dev, ext_grads_dev,
+                     ext_momentum_dev, dtype, graph);
+    SSD_REQUIRE(n->nparams() == Net::arena_floats(preset, num_classes, graph), "arena size mismatch");
+    *out = new ssd_net{n};
+    API_END
+}
+
+int ssd_graph(ssd_handle h, int* graph) {
+    API_BEGIN_NET(h)
+    SSD_REQUIRE(h != nullptr && graph != nullptr, "null argument");
+    *graph = n.graph();
     API_END
 }
 

@@ -91,6 +91,16 @@ size_t wino_wgrad_ws_floats(const ConvDesc& d);
 void wino_wgrad(const ConvDesc& d, const float* V, size_t v_ps, const float* Ya, float* dw, float* dbias, const float* w,
                 float weight_decay, float* ws, hipStream_t s);
 
+// ---- convolutions with more than 9 taps (conv_bigk.hip): the fc graph's 7x7 fc6 -------------------------------------------------
+// Stride 1, dilation 1, SAME; channel counts multiples of 4 (fp32) / 8 (bf16).  conv_fwd / conv_dgrad / conv_wgrad and their bf16 forms
+// dispatch here when KH * KW > 9 (the gather kernels carry 9-entry tap tables); the weight gradient needs no workspace.
+bool conv_bigk(const ConvDesc& d);
+double conv_bigk_useful_flops(const ConvDesc& d);          // 2 * Ci * Co * the (pixel, tap) pairs that land inside the image
+void conv_bigk_fwd(const ConvDesc& d, const float* x, const float* w, const float* bias, float* y, bool relu, hipStream_t s);
+void conv_bigk_dgrad(const ConvDesc& d, const float* dy, const float* w, float* dx, const float* mask, bool accumulate, hipStream_t s);
+void conv_bigk_wgrad(const ConvDesc& d, const float* x, const float* dy, float* dw, float* dbias, const float* w, float weight_decay,
+                     hipStream_t s);
+
 // ---- bf16 configuration (conv_bf16.hip): bf16 activations / gradients / filter mirrors, fp32 accumulate ----
 struct bf16_t;
 
@@ -105,6 +115,14 @@ void conv_first_fwd_bf16(const ConvDesc& d, const float* x, const float* w, cons
 size_t conv_first_wgrad_bf16_ws_floats(const ConvDesc& d);
 void conv_first_wgrad_bf16(const ConvDesc& d, const float* x, const bf16_t* dy, float* dw, float* dbias, const float* w,
                            float weight_decay, float* ws, hipStream_t s);
+
+// the bf16 forms of conv_bigk_* (fp32 accumulation; the filter operands are the bf16 mirrors below)
+void conv_bigk_fwd_bf16(const ConvDesc& d, const bf16_t* x, const bf16_t* w_oi, const float* bias, void* y, bool y_f32, bool relu,
+                        hipStream_t s);
+void conv_bigk_dgrad_bf16(const ConvDesc& d, const bf16_t* dy, const bf16_t* w_io, bf16_t* dx, const bf16_t* mask, bool accumulate,
+                          hipStream_t s);
+void conv_bigk_wgrad_bf16(const ConvDesc& d, const bf16_t* x, const bf16_t* dy, float* dw, float* dbias, const float* w,
+                          float weight_decay, hipStream_t s);
 
 // One launch mirrors every layer's fp32 filter [tap][Ci][Co] as bf16 in the same order (io, the data
 // gradient's operand) and transposed [tap][Co][Ci] (oi, the forward operand), at the same offsets.

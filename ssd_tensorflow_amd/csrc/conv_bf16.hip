@@ -2550,6 +2550,7 @@ static bool gather_rows256(const ConvDesc& d, int M, int N) {
 
 void conv_fwd_bf16(const ConvDesc& d, const bf16_t* x, const bf16_t* w_oi, const float* bias, void* y, bool y_f32, bool relu,
                    hipStream_t s) {
+    if (conv_bigk(d)) return conv_bigk_fwd_bf16(d, x, w_oi, bias, y, y_f32, relu, s);
     check_desc_h(d);
     GatherArgsH a{};
     a.src = x; a.wgt = w_oi; a.bias = bias; a.mask = nullptr; a.dst = y;
@@ -2670,6 +2671,7 @@ static void conv_dgrad_bf16_any(const ConvDesc& d, const bf16_t* dy, const bf16_
 
 void conv_dgrad_bf16(const ConvDesc& d, const bf16_t* dy, const bf16_t* w_io, bf16_t* dx, const bf16_t* mask, bool accumulate,
                      hipStream_t s) {
+    if (conv_bigk(d)) return conv_bigk_dgrad_bf16(d, dy, w_io, dx, mask, accumulate, s);
     conv_dgrad_bf16_any(d, dy, w_io, dx, mask, accumulate, s, nullptr, 0, 0);
 }
 
@@ -2931,6 +2933,7 @@ static ColPlan plan_col(const ConvDesc& d) {
 }
 
 size_t conv_wgrad_bf16_ws_floats(const ConvDesc& d) {
+    if (conv_bigk(d)) return 0;      // (conv_bigk_wgrad_bf16: no slabs)
     const size_t per = (size_t)d.KH * d.KW * d.Ci * d.Co + d.Co;
     size_t n = (size_t)plan_wgrad_h(d).nsplit * per;
     if (col_applicable(d)) n = std::max(n, (size_t)plan_col(d).nunits * per);
@@ -2941,6 +2944,7 @@ size_t conv_wgrad_bf16_ws_floats(const ConvDesc& d) {
 
 void conv_wgrad_bf16(const ConvDesc& d, const bf16_t* x, const bf16_t* dy, float* dw, float* dbias, const float* w,
                      float weight_decay, float* ws, hipStream_t s) {
+    if (conv_bigk(d)) return conv_bigk_wgrad_bf16(d, x, dy, dw, dbias, w, weight_decay, s);
     check_desc_h(d);
     if (col_applicable(d)) {
         const ColPlan cp = plan_col(d);

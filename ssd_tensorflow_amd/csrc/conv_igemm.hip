@@ -1324,6 +1324,7 @@ static void conv_fwd_any(const ConvDesc& d, const float* x, const float* w, cons
 }
 
 void conv_fwd(const ConvDesc& d, const float* x, const float* w, const float* bias, float* y, bool relu, hipStream_t s) {
+    if (conv_bigk(d)) return conv_bigk_fwd(d, x, w, bias, y, relu, s);
     conv_fwd_any(d, x, w, bias, y, false, relu, s);
 }
 
@@ -1423,6 +1424,7 @@ static void conv_dgrad_any(const ConvDesc& d, const float* dy, const float* w, f
 
 void conv_dgrad(const ConvDesc& d, const float* dy, const float* w, float* dx, const float* mask, bool accumulate,
                 hipStream_t s) {
+    if (conv_bigk(d)) return conv_bigk_dgrad(d, dy, w, dx, mask, accumulate, s);
     conv_dgrad_any(d, dy, w, dx, mask, accumulate, s);
 }
 
@@ -1495,6 +1497,7 @@ static bool use_first_wgrad(const ConvDesc& d) {
 }
 
 size_t conv_wgrad_ws_floats(const ConvDesc& d) {
+    if (conv_bigk(d)) return 0;      // (conv_bigk_wgrad: no slabs)
     WgradPlan p = plan_wgrad(d);
     size_t n = (size_t)p.nsplit * ((size_t)d.KH * d.KW * d.Ci * d.Co + d.Co);
     if (conv_first_wgrad_f32_applicable(d)) n = std::max(n, conv_first_wgrad_f32_ws_floats(d));
@@ -1614,6 +1617,7 @@ static void conv_wgrad_any(const ConvDesc& d, const float* x, const void* dy, bo
 
 void conv_wgrad(const ConvDesc& d, const float* x, const float* dy, float* dw, float* dbias, const float* w,
                 float weight_decay, float* ws, hipStream_t s) {
+    if (conv_bigk(d)) return conv_bigk_wgrad(d, x, dy, dw, dbias, w, weight_decay, s);
     if (use_first_wgrad(d)) {
         check_desc(d);
         conv_first_wgrad_f32(d, x, dy, dw, dbias, w, weight_decay, ws, s);

@@ -88,10 +88,12 @@ public:
     // dtype 0: fp32 everywhere (BASELINE.json configs[1]); 1: bf16 activations / gradients / filter mirrors with fp32
     // master weights, fp32 accumulation and fp32 loss (configs[2])
     Net(const char* preset, int num_classes, int max_batch, int device, bool training, unsigned long long seed,
-        float* ext_params, float* ext_grads, float* ext_momentum, int dtype = 0);
+        float* ext_params, float* ext_grads, float* ext_momentum, int dtype = 0, int graph = 0);
     ~Net();
 
-    static size_t arena_floats(const char* preset, int num_classes);
+    // graph 0: the a-trous graph (ssdvgg.py __build_vgg_mods_a_trous: 3x3 dilation-6 mod_conv6 and 1x1 mod_conv7, 1024 wide);
+    // 1: the fc graph (ssdvgg.py __build_vgg_mods: VGG-16's fc6 / fc7 as a 7x7 and a 1x1 convolution, 4096 wide, variables fc6/* and fc7/*)
+    static size_t arena_floats(const char* preset, int num_classes, int graph = 0);
 
     void set_stream(hipStream_t s) { stream_ = s; }
     hipStream_t stream() const { return stream_; }
@@ -145,6 +147,7 @@ public:
     int max_batch() const { return Bmax_; }
     bool training() const { return training_; }
     int dtype() const { return bf16_ ? 1 : 0; }
+    int graph() const { return fc_ ? 1 : 0; }
     int device() const { return device_; }
     float* params() { return params_; }
     float* grads() { return grads_; }
@@ -170,6 +173,7 @@ private:
     int C_, Bmax_, device_;
     bool training_;
     bool bf16_ = false;
+    bool fc_ = false;                      // the fc graph (arena_floats)
     bf16_t *wq_io_ = nullptr, *wq_oi_ = nullptr;     // bf16 mirrors of the filter region: [tap][Ci][Co] and [tap][Co][Ci]
     FilterCastPlan cast_plan_;
     hipStream_t stream_ = nullptr;

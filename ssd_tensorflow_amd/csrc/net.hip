@@ -84,10 +84,14 @@ void Net::build_graph() {
     cur = conv("conv5_1", 512, 3, 1, PAD_SAME, 1, true, -1, cur);
     cur = conv("conv5_2", 512, 3, 1, PAD_SAME, 1, true, -1, cur);
     cur = conv("conv5_3", 512, 3, 1, PAD_SAME, 1, true, -1, cur);
-    // a-trous modifications (ssdvgg.py:231-292)
+    // a-trous modifications (ssdvgg.py:231-292), or VGG-16's fully connected layers as convolutions (ssdvgg.py:210-228)
     cur = pool("mod_pool5", 3, 1, cur);
-    cur = conv("mod_conv6", 1024, 3, 1, PAD_SAME, 6, true, -1, cur);
-    const int c7 = cur = conv("mod_conv7", 1024, 1, 1, PAD_SAME, 1, true, -1, cur);
+    if (fc_) {
+        cur = conv("mod_conv6", 4096, 7, 1, PAD_SAME, 1, true, -1, cur);
+    } else {
+        cur = conv("mod_conv6", 1024, 3, 1, PAD_SAME, 6, true, -1, cur);
+    }
+    const int c7 = cur = conv("mod_conv7", fc_ ? 4096 : 1024, 1, 1, PAD_SAME, 1, true, -1, cur);
     // extra feature layers (ssdvgg.py:300-332)
     const bool big = p.nmaps >= 7;
     std::vector<int> fmaps{-1, c7};
@@ -170,8 +174,12 @@ void Net::build_graph() {
         const int ci = tensors_[op.in].C, co = tensors_[op.out].C;
         if (op.head < 0) {
             const size_t n = (size_t)op.KH * op.KW * ci * co;
-            add_var(op.name + "/filter", 4, op.KH, op.KW, ci, co, op.w_off, 1, n, n);
-            add_var(op.name + "/biases", 1, co, 0, 0, 0, op.b_off, 1, co, co);
+            // the fc graph's two layers keep their scopes (mod_conv6 / mod_conv7) but take the SavedModel's variables
+            // (ssdvgg.py:215-228): fc6/weights, fc6/biases, fc7/weights, fc7/biases
+            const bool fcv = fc_ && (op.name == "mod_conv6" || op.name == "mod_conv7");
+            const std::string vn = fcv ? (op.name == "mod_conv6" ? "fc6" : "fc7") : op.name;
+            add_var(vn + (fcv ? "/weights" : "/filter"), 4, op.KH, op.KW, ci, co, op.w_off, 1, n, n);
+            add_var(vn + "/biases", 1, co, 0, 0, 0, op.b_off, 1, co, co);
         } else {
             for (int j = 0; j < p.ntypes[op.head]; ++j) {
                 const std::string base = "classifiers/classifier" + std::to_string(op.head) + "_" + std::to_string(j);
@@ -525,6 +533,9 @@ void Net::plan_winograd() {
         if (op.kind != OP_CONV) continue;
         const ConvDesc d = conv_desc(op, Bmax_);
         if (!wino_applicable(d) || d.Ci * d.Co < min_cc) continue;
+        // the fc graph's map-1 head reads 4096 channels: its input transform would be 2.25 x that 19x19 tensor (472 MB at vgg300
+        // b32) per training handle -- it keeps the direct kernels
+        if (d.Ci > 1024) continue;
         // the multibox heads of the big maps (38x38 / 19x19; vgg512: 64x64 ... 16x16): below that a layer is a handful of tiles
         // whose three launches cost more than the one they replace
         if (op.head >= 0 && (d.Ho < head_min_hw || !(mode & 8))) continue;
@@ -581,20 +592,23 @@ void Net::pool_fusion(int* out, int cap, int* count) const {
     if (count) *count = k;
 }
 
-size_t Net::arena_floats(const char* preset, int num_classes) {
+size_t Net::arena_floats(const char* preset, int num_classes, int graph) {
     // cheap: build the graph description only
     const Preset& p = get_preset(preset);
     require_num_classes(num_classes);
+    SSD_REQUIRE(graph == 0 || graph == 1, "graph must be 0 (a-trous) or 1 (fc), got %d", graph);
     const int nv = num_classes + 5;
+    const int c7 = graph == 1 ? 4096 : 1024;      // mod_conv7's width: the input of conv8_1 and of the map-1 head
     size_t n = 0;
     auto cv = [&](int k, int ci, int co) { n += (size_t)k * k * ci * co + co; };
     cv(3, 3, 64); cv(3, 64, 64); cv(3, 64, 128); cv(3, 128, 128); cv(3, 128, 256); cv(3, 256, 256); cv(3, 256, 256);
     cv(3, 256, 512); cv(3, 512, 512); cv(3, 512, 512); cv(3, 512, 512); cv(3, 512, 512); cv(3, 512, 512);
-    cv(3, 512, 1024); cv(1, 1024, 1024);
-    cv(1, 1024, 256); cv(3, 256, 512); cv(1, 512, 128); cv(3, 128, 256); cv(1, 256, 128); cv(3, 128, 256);
+    if (graph == 1) { cv(7, 512, 4096); cv(1, 4096, 4096); }
+    else { cv(3, 512, 1024); cv(1, 1024, 1024); }
+    cv(1, c7, 256); cv(3, 256, 512); cv(1, 512, 128); cv(3, 128, 256); cv(1, 256, 128); cv(3, 128, 256);
     cv(1, 256, 128); cv(3, 128, 256);
     if (p.nmaps >= 7) { cv(1, 256, 128); cv(3, 128, 256); }
-    static const int fch[] = {512, 1024, 512, 256, 256, 256, 256};
+    const int fch[] = {512, c7, 512, 256, 256, 256, 256};
     for (int i = 0; i < p.nmaps; ++i) cv(3, fch[i], round8(p.ntypes[i] * nv));
     return n + 512;
 }
@@ -733,9 +747,11 @@ void Net::init_weights(unsigned long long seed) {
 }
 
 Net::Net(const char* preset, int num_classes, int max_batch, int device, bool training, unsigned long long seed,
-         float* ext_params, float* ext_grads, float* ext_momentum, int dtype)
-    : preset_(&get_preset(preset)), C_(num_classes), Bmax_(max_batch), device_(device), training_(training), bf16_(dtype == 1) {
+         float* ext_params, float* ext_grads, float* ext_momentum, int dtype, int graph)
+    : preset_(&get_preset(preset)), C_(num_classes), Bmax_(max_batch), device_(device), training_(training), bf16_(dtype == 1),
+      fc_(graph == 1) {
     SSD_REQUIRE(dtype == 0 || dtype == 1, "dtype must be 0 (fp32) or 1 (bf16), got %d", dtype);
+    SSD_REQUIRE(graph == 0 || graph == 1, "graph must be 0 (a-trous) or 1 (fc), got %d", graph);
     require_num_classes(num_classes);
     SSD_REQUIRE(max_batch >= 1, "max_batch must be >= 1");
     HIP_OK(hipSetDevice(device));

@@ -86,6 +86,7 @@ def main(argv=None):
     parser.add_argument('--synthetic', type=int, default=0, help='run on N synthetic images instead of files')
     parser.add_argument('--preset', default=None, help='preset when no checkpoint is given (random weights)')
     parser.add_argument('--num-classes', type=int, default=20, help='class count when no checkpoint is given (1..127)')
+    parser.add_argument('--a-trous', type=str2bool, default='True', help='graph when no checkpoint is given: a-trous (true) or fc (false); a checkpoint carries its own')
     parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='f32, or bf16 activations on the bf16 matrix cores')
     args = parser.parse_args(argv)
 
@@ -151,7 +152,7 @@ def main(argv=None):
         else:
             num_classes = args.num_classes
             net = SSDVGG(sess, get_preset_by_name(args.preset))
-            net.build_from_vgg(None, num_classes, max_batch=args.batch_size, training=False, dtype=args.dtype)
+            net.build_from_vgg(None, num_classes, a_trous=args.a_trous, max_batch=args.batch_size, training=False, dtype=args.dtype)
         lid2name = resolve_class_names(num_classes, source.lid2name if source else None, stored_names)
         if not source:
             print('[i] # classes:         ', num_classes)

@@ -157,13 +157,13 @@ class SSDVGG:
         """ssdvgg.py:96-118.  There is no vgg.zip offline: the VGG-16 trunk starts from
         Xavier-uniform synthetic weights (seed) unless `weights` ({tf_name: array}) or
         `<vgg_dir>/vgg16_ssd.npz` supplies them.  dtype 'f32' (default) or 'bf16' (bf16 activations and
-        filter mirrors on the bf16 matrix cores; fp32 master weights, loss and optimizer)."""
-        if not a_trous:
-            raise NotImplementedError('only the default a_trous=True variant (ssdvgg.py:231) is built')
+        filter mirrors on the bf16 matrix cores; fp32 master weights, loss and optimizer).
+        a_trous=False builds the reference's other graph (ssdvgg.py:210-228): VGG-16's fc6 / fc7 as a 7x7 and a
+        1x1 convolution, 4096 wide, variables fc6/* and fc7/*; its weights come from `<vgg_dir>/vgg16_ssd_fc.npz`."""
         self.num_classes = num_classes + 1
         self.num_vars = num_classes + 5
-        self._create(num_classes, max_batch, training, seed, dtype)
-        path = os.path.join(vgg_dir, 'vgg16_ssd.npz') if vgg_dir else None
+        self._create(num_classes, max_batch, training, seed, dtype, a_trous)
+        path = os.path.join(vgg_dir, 'vgg16_ssd.npz' if a_trous else 'vgg16_ssd_fc.npz') if vgg_dir else None
         if weights is None and path and os.path.exists(path):
             weights = dict(np.load(path))
         if weights:
@@ -177,12 +177,13 @@ class SSDVGG:
         num_classes = int(ck['__num_classes__'])
         self.num_classes = num_classes + 1
         self.num_vars = num_classes + 5
-        self._create(num_classes, max_batch, training, 0, dtype)
+        a_trous = bool(int(ck['__a_trous__'])) if '__a_trous__' in ck.files else True      # (older checkpoints: a-trous)
+        self._create(num_classes, max_batch, training, 0, dtype, a_trous)
         self.load_variables({k: ck[k] for k in ck.files if not k.startswith('__')})
         self._ckpt = ck
         self.__built = True
 
-    def _create(self, num_classes, max_batch, training, seed, dtype='f32'):
+    def _create(self, num_classes, max_batch, training, seed, dtype='f32', a_trous=True):
         import torch
         if dtype not in ('f32', 'bf16'):
             raise ValueError("dtype must be 'f32' or 'bf16', got %r" % (dtype,))
@@ -191,7 +192,9 @@ class SSDVGG:
         self.device = dev
         self.max_batch = int(max_batch)
         self.training = bool(training)
-        n = lib.ssd_arena_floats(self.preset.name.encode(), num_classes)
+        self.a_trous = bool(a_trous)
+        graph = 0 if self.a_trous else 1      # SSD_GRAPH_A_TROUS / SSD_GRAPH_FC
+        n = lib.ssd_arena_floats_graph(self.preset.name.encode(), num_classes, graph)
         if n == 0:
             raise RuntimeError(_lib.last_error())
         tdev = torch.device('cuda', dev)
@@ -199,11 +202,11 @@ class SSDVGG:
         self.grads_flat = torch.zeros(n, dtype=torch.float32, device=tdev) if training else None
         self.momentum_flat = torch.zeros(n, dtype=torch.float32, device=tdev) if training else None
         h = C.c_void_p()
-        check(lib.ssd_create_dtype(self.preset.name.encode(), num_classes, self.max_batch, dev, int(training), seed,
+        check(lib.ssd_create_graph(self.preset.name.encode(), num_classes, self.max_batch, dev, int(training), seed,
                                    self.params_flat.data_ptr(),
                                    self.grads_flat.data_ptr() if training else None,
                                    self.momentum_flat.data_ptr() if training else None,
-                                   1 if dtype == 'bf16' else 0, C.byref(h)))
+                                   1 if dtype == 'bf16' else 0, graph, C.byref(h)))
         self._h = h
         fl = C.c_size_t(); ff = C.c_size_t()
         check(lib.ssd_arenas(h, None, None, None, C.byref(fl), C.byref(ff)))
@@ -331,7 +334,8 @@ class SSDVGG:
         d.update(__preset__=np.array(self.preset.name), __num_classes__=np.array(self._n_classes),
                  __global_step__=np.array(self.global_step), __lr_values__=np.array(lr.values, np.float64),
                  __lr_boundaries__=np.array(lr.boundaries, np.int64), __momentum__=np.array(momentum),
-                 __weight_decay__=np.array(weight_decay), __class_names__=np.array([str(n) for n in names], dtype=np.str_))
+                 __weight_decay__=np.array(weight_decay), __class_names__=np.array([str(n) for n in names], dtype=np.str_),
+                 __a_trous__=np.array(int(self.a_trous)))
         np.savez(path, **d)
 
     # ------------------------------------------------------------------ steps

@@ -128,6 +128,7 @@ def main(argv=None):
     parser.add_argument('--preset', default='vgg300')
     parser.add_argument('--data-source', default='pascal_voc', help='data source module for a real --data-dir')
     parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='f32, or bf16 activations on the bf16 matrix cores (fp32 master weights, loss and optimizer)')
+    parser.add_argument('--a-trous', type=str2bool, default='True', help='a fresh run: the a-trous graph (true) or the fc graph with the whole fc6 / fc7 (false; weights from <vgg-dir>/vgg16_ssd_fc.npz); --continue-training takes the checkpoint\'s')
     parser.add_argument('--synthetic-train', type=int, default=64, help='synthetic training samples per epoch')
     parser.add_argument('--synthetic-valid', type=int, default=16)
     parser.add_argument('--synthetic-classes', type=int, default=20, help='class count of the synthetic data sets (1..127)')
@@ -209,7 +210,7 @@ def main(argv=None):
             net.build_from_metagraph(None, ckpt, max_batch=args.batch_size, training=True, dtype=args.dtype)
             net.build_optimizer_from_metagraph()
         else:
-            net.build_from_vgg(args.vgg_dir, td.num_classes, max_batch=args.batch_size, dtype=args.dtype)
+            net.build_from_vgg(args.vgg_dir, td.num_classes, a_trous=args.a_trous, max_batch=args.batch_size, dtype=args.dtype)
             net.build_optimizer(learning_rate=lr, weight_decay=args.weight_decay, momentum=args.momentum)
         if world > 1:
             torch.distributed.broadcast(net.params_flat, 0)

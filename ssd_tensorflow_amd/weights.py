@@ -23,18 +23,30 @@ def decimate_fc7(fc7_w, fc7_b):
     return np.ascontiguousarray(fc7_w[:, :, 0:4096:4, 0:4096:4], np.float32), np.ascontiguousarray(fc7_b[0:4096:4], np.float32)
 
 
-def vgg16_to_ssd(vgg):
+FC_SHAPES = {'fc6/weights': (7, 7, 512, 4096), 'fc6/biases': (4096,), 'fc7/weights': (1, 1, 4096, 4096), 'fc7/biases': (4096,)}
+
+
+def vgg16_to_ssd(vgg, a_trous=True):
     """{'conv1_1/filter': ..., 'conv1_1/biases': ..., ..., 'fc6/weights', 'fc6/biases', 'fc7/weights',
     'fc7/biases'} (the tensors ssdvgg.py:192-207 reads from the SavedModel, filters HWIO) ->
-    {'conv*/filter|biases', 'mod_conv6|7/filter|biases'} ready for SSDVGG.load_variables."""
+    {'conv*/filter|biases', 'mod_conv6|7/filter|biases'} ready for SSDVGG.load_variables.
+    a_trous=False: the fc graph's variables (ssdvgg.py:210-228), fc6/* and fc7/* kept whole."""
     out = {}
     for n in VGG_CONVS:
         out[n + '/filter'] = np.ascontiguousarray(vgg[n + '/filter'], np.float32)
         out[n + '/biases'] = np.ascontiguousarray(vgg[n + '/biases'], np.float32)
+    if not a_trous:
+        for n, shape in FC_SHAPES.items():
+            a = np.ascontiguousarray(vgg[n], np.float32)
+            if a.shape != shape:
+                raise ValueError(f'{n} must be {list(shape)}, got {list(a.shape)}')
+            out[n] = a
+        return out
     out['mod_conv6/filter'], out['mod_conv6/biases'] = decimate_fc6(vgg['fc6/weights'], vgg['fc6/biases'])
     out['mod_conv7/filter'], out['mod_conv7/biases'] = decimate_fc7(vgg['fc7/weights'], vgg['fc7/biases'])
     return out
 
 
-def save_vgg_npz(path, vgg):
-    np.savez(path, **vgg16_to_ssd(vgg))
+def save_vgg_npz(path, vgg, a_trous=True):
+    """`vgg16_ssd.npz` (a_trous=True) or `vgg16_ssd_fc.npz` (a_trous=False) for build_from_vgg(vgg_dir, a_trous=...)."""
+    np.savez(path, **vgg16_to_ssd(vgg, a_trous))

@@ -14,7 +14,10 @@ LAYERS = [('conv1_2', 300, 64, 64, 3, 1, 1), ('conv2_1', 150, 64, 128, 3, 1, 1),
           # the small tail of the network (latency-bound: a handful of workgroups each)
           ('conv8_1', 19, 1024, 256, 1, 1, 1), ('conv8_2', 19, 256, 512, 3, 2, 1), ('conv9_1', 10, 512, 128, 1, 1, 1),
           ('conv9_2', 10, 128, 256, 3, 2, 1), ('conv10_1', 5, 256, 128, 1, 1, 1), ('conv10_2', 5, 128, 256, 3, 1, 1),
-          ('head2', 10, 512, 152, 3, 1, 1), ('head3', 5, 256, 152, 3, 1, 1)]
+          ('head2', 10, 512, 152, 3, 1, 1), ('head3', 5, 256, 152, 3, 1, 1),
+          # the fc graph (build_from_vgg(a_trous=False)): 7x7 fc6 on the >9-tap kernels, fc7, and the 4096-wide readers
+          ('fc6', 19, 512, 4096, 7, 1, 1), ('fc7', 19, 4096, 4096, 1, 1, 1), ('fc_conv8_1', 19, 4096, 256, 1, 1, 1),
+          ('fc_head1', 19, 4096, 152, 3, 1, 1), ('fc6_512', 32, 512, 4096, 7, 1, 1)]
 only = sys.argv[1].split(',') if len(sys.argv) > 1 and sys.argv[1] != 'all' else None
 BF16 = len(sys.argv) > 2 and sys.argv[2] == 'bf16'
 B = int(os.environ.get("SSD_BENCH_B", "32"))      # batch (SSD_BENCH_B: quantisation / tail experiments)
@@ -65,9 +68,18 @@ def timeit(fns, fl, name):
     print(f'{name:10s} ' + ' | '.join(out), flush=True)
 
 
+def useful_fraction(hw, k):
+    """share of the k x k window products of a stride-1 SAME layer that land inside the image (the rest multiply padding)"""
+    p = (k - 1) // 2
+    inside = sum(0 <= o + t - p < hw for o in range(hw) for t in range(k))
+    return (inside / (hw * k)) ** 2
+
+
 for name, hw, ci, co, k, s, d in LAYERS:
     if only and name not in only:
         continue
+    if k * k > 9:      # TF/s below count executed FLOPs; the useful part excludes the SAME padding
+        print(f'{name:10s} useful / executed FLOPs {useful_fraction(hw, k):.3f}', flush=True)
     if BF16:
         fl, fns = bench_bf16(name, hw, ci, co, k, s, d)
         timeit(fns, fl, name)

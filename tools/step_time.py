@@ -22,6 +22,7 @@ def main():
     ap.add_argument('--preset', default='vgg300')
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--num-classes', type=int, default=20)
+    ap.add_argument('--a-trous', default='true', choices=['true', 'false'], help='false: the fc graph (7x7 fc6, 4096-wide fc7)')
     ap.add_argument('--steps', type=int, default=40)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--reps', type=int, default=2)
@@ -32,7 +33,7 @@ def main():
     x, y, _ = ref.synth_batch(rng, a.batch, preset, a.num_classes)
     with Session(0) as sess:
         net = SSDVGG(sess, a.preset)
-        net.build_from_vgg(None, a.num_classes, max_batch=a.batch, dtype=a.dtype)
+        net.build_from_vgg(None, a.num_classes, a_trous=a.a_trous == 'true', max_batch=a.batch, dtype=a.dtype)
         net.build_optimizer(learning_rate=1e-4, weight_decay=0.0005, momentum=0.9)
         net.set_stream(torch.cuda.current_stream().cuda_stream)
         xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()
