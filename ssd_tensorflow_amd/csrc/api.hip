@@ -5,6 +5,7 @@
 #include "metrics.h"
 #include <vector>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <algorithm>
 
@@ -50,7 +51,7 @@ ProfScope::~ProfScope() {
 using namespace ssd;
 
 struct ssd_net {
-    Net* net;
+    std::unique_ptr<Net> net;
 };
 
 #define API_BEGIN try {
@@ -75,15 +76,6 @@ static Net& N(ssd_handle h) {
     try {                \
         Net& n = N(h);   \
         DeviceGuard dev_guard_(n.device());
-
-namespace {
-struct DevBuf {
-    void* p = nullptr;
-    explicit DevBuf(size_t bytes) { HIP_OK(hipMalloc(&p, bytes ? bytes : 16)); }
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    template <typename T> T* as() { return (T*)p; }
-};
-}  // namespace
 
 // Label encoding is called once per training batch: the anchor tables of a (preset, device) pair and a small
 // growable scratch per device are kept for the life of the process instead of six hipMalloc / hipFree pairs
@@ -406,43 +398,32 @@ int ssd_augment_batch_dev(const unsigned char* images_dev, const ssd_augment_par
     API_END
 }
 
-int ssd_create(const char* preset, int num_classes, int max_batch, int device, int training, unsigned long long seed,
-               float* ext_params_dev, float* ext_grads_dev, float* ext_momentum_dev, ssd_handle* out) {
+static int create_handle(const char* preset, int num_classes, int max_batch, int device, int training, unsigned long long seed,
+                         float* ext_params_dev, float* ext_grads_dev, float* ext_momentum_dev, int dtype, int graph, ssd_handle* out) {
     API_BEGIN
     SSD_REQUIRE(out != nullptr, "out handle pointer is null");
     *out = nullptr;
     DeviceGuard dev_guard_(device);
-    Net* n = new Net(preset, num_classes, max_batch, device, training != 0, seed, ext_params_dev, ext_grads_dev,
-                     ext_momentum_dev);
-    SSD_REQUIRE(n->nparams() == Net::arena_floats(preset, num_classes), "arena size mismatch");
-    *out = new ssd_net{n};
+    auto n = std::make_unique<Net>(preset, num_classes, max_batch, device, training != 0, seed, ext_params_dev, ext_grads_dev,
+                                   ext_momentum_dev, dtype, graph);
+    SSD_REQUIRE(n->nparams() == Net::arena_floats(preset, num_classes, graph), "arena size mismatch");
+    *out = new ssd_net{std::move(n)};
     API_END
+}
+
+int ssd_create(const char* preset, int num_classes, int max_batch, int device, int training, unsigned long long seed,
+               float* ext_params_dev, float* ext_grads_dev, float* ext_momentum_dev, ssd_handle* out) {
+    return create_handle(preset, num_classes, max_batch, device, training, seed, ext_params_dev, ext_grads_dev, ext_momentum_dev, 0, 0, out);
 }
 
 int ssd_create_dtype(const char* preset, int num_classes, int max_batch, int device, int training, unsigned long long seed,
                      float* ext_params_dev, float* ext_grads_dev, float* ext_momentum_dev, int dtype, ssd_handle* out) {
-    API_BEGIN
-    SSD_REQUIRE(out != nullptr, "out handle pointer is null");
-    *out = nullptr;
-    DeviceGuard dev_guard_(device);
-    Net* n = new Net(preset, num_classes, max_batch, device, training != 0, seed, ext_params_dev, ext_grads_dev,
-                     ext_momentum_dev, dtype);
-    SSD_REQUIRE(n->nparams() == Net::arena_floats(preset, num_classes), "arena size mismatch");
-    *out = new ssd_net{n};
-    API_END
+    return create_handle(preset, num_classes, max_batch, device, training, seed, ext_params_dev, ext_grads_dev, ext_momentum_dev, dtype, 0, out);
 }
 
 int ssd_create_graph(const char* preset, int num_classes, int max_batch, int device, int training, unsigned long long seed,
                      float* ext_params_dev, float* ext_grads_dev, float* ext_momentum_dev, int dtype, int graph, ssd_handle* out) {
-    API_BEGIN
-    SSD_REQUIRE(out != nullptr, "out handle pointer is null");
-    *out = nullptr;
-    DeviceGuard dev_guard_(device);
-    Net* n = new Net(preset, num_classes, max_batch, device, training != 0, seed, ext_params_dev, ext_grads_dev,
-                     ext_momentum_dev, dtype, graph);
-    SSD_REQUIRE(n->nparams() == Net::arena_floats(preset, num_classes, graph), "arena size mismatch");
-    *out = new ssd_net{n};
-    API_END
+    return create_handle(preset, num_classes, max_batch, device, training, seed, ext_params_dev, ext_grads_dev, ext_momentum_dev, dtype, graph, out);
 }
 
 int ssd_graph(ssd_handle h, int* graph) {
@@ -461,10 +442,7 @@ int ssd_get_dtype(ssd_handle h, int* dtype) {
 
 int ssd_destroy(ssd_handle h) {
     API_BEGIN
-    if (h) {
-        delete h->net;
-        delete h;
-    }
+    delete h;
     API_END
 }
 
@@ -822,17 +800,20 @@ int ssd_op_conv2d_wgrad_bf16(const void* x, const void* dy, float* dw, float* db
                     dbias, w, weight_decay, ws, (hipStream_t)stream);
     API_END
 }
-namespace {
-struct TailPacked {      // a filter mirror packed for the chain kernel into a temporary buffer
-    void* p = nullptr;
-    TailPacked(const ConvDesc& d, bool dgrad, const void* mirror, hipStream_t s) {
-        HIP_OK(hipMalloc(&p, tail_chain_packed_elems(d, dgrad) * 2));
-        const TailPackItem it{d, dgrad, mirror, p};
-        tail_chain_pack_filters(&it, 1, s);
-    }
-    ~TailPacked() { if (p) (void)hipFree(p); }
-};
-}  // namespace
+// one stage as a chain launch (unit-parity entry points: the step packs its filters once per weight update); the packed filter and
+// the stage table are the call's own, freed on return
+static void tail_chain_op(TailStage t, const void* mirror, int b, const char* label, hipStream_t s) {
+    int device = 0;
+    HIP_OK(hipGetDevice(&device));
+    HipOwner tmp(device);
+    TailTables tables{tmp, {}};
+    void* packed = tmp.mem(tail_chain_packed_elems(t.d, t.dgrad) * 2);
+    const TailPackItem it{t.d, t.dgrad, mirror, packed};
+    tail_chain_pack_filters(&it, 1, s);
+    t.wgt_packed = packed;
+    tail_chain_bf16(&t, 1, b, label, s, tables);
+    HIP_OK(hipStreamSynchronize(s));
+}
 int ssd_op_conv2d_fwd_bf16_chain(const void* x, const void* w_oi, const float* bias, void* y, int y_f32, int b, int hi, int wi, int ci,
                                  int ho, int wo, int co, int kh, int kw, int stride, int dil, int pad_h, int pad_w, int relu,
                                  void* stream) {
@@ -840,10 +821,7 @@ int ssd_op_conv2d_fwd_bf16_chain(const void* x, const void* w_oi, const float* b
     TailStage t{};
     t.d = mk(1, hi, wi, ci, ho, wo, co, kh, kw, stride, dil, pad_h, pad_w);
     t.dgrad = false; t.src = x; t.bias = bias; t.dst = y; t.relu = relu != 0; t.out_f32 = y_f32 != 0;
-    TailPacked tmp(t.d, false, w_oi, (hipStream_t)stream);      // (unit-parity entry point: the step packs once per weight update)
-    t.wgt_packed = tmp.p;
-    tail_chain_bf16(&t, 1, b, "tail_fwd_bf16", (hipStream_t)stream);
-    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+    tail_chain_op(t, w_oi, b, "tail_fwd_bf16", (hipStream_t)stream);
     API_END
 }
 int ssd_op_conv2d_dgrad_bf16_chain(const void* dy, const void* w_io, void* dx, const void* mask, int accumulate, int b, int hi, int wi,
@@ -853,10 +831,7 @@ int ssd_op_conv2d_dgrad_bf16_chain(const void* dy, const void* w_io, void* dx, c
     TailStage t{};
     t.d = mk(1, hi, wi, ci, ho, wo, co, kh, kw, stride, dil, pad_h, pad_w);
     t.dgrad = true; t.src = dy; t.mask = mask; t.dst = dx; t.accum = accumulate != 0;
-    TailPacked tmp(t.d, true, w_io, (hipStream_t)stream);
-    t.wgt_packed = tmp.p;
-    tail_chain_bf16(&t, 1, b, "tail_dgrad_bf16", (hipStream_t)stream);
-    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+    tail_chain_op(t, w_io, b, "tail_dgrad_bf16", (hipStream_t)stream);
     API_END
 }
 int ssd_op_conv2d_wgrad_bf16_direct(const void* x, const void* dy, float* dw, float* dbias, const float* w, float weight_decay, int b,

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <algorithm>
 #include <cstdio>
 #include <cstdarg>
 #include <cstdint>
@@ -67,6 +68,79 @@ struct DeviceGuard {
     }
     DeviceGuard(const DeviceGuard&) = delete;
     DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+
+// Device memory that frees itself: an op's temporaries, and every buffer a HipOwner hands out.
+struct DevBuf {
+    void* p = nullptr;
+    explicit DevBuf(size_t bytes) { HIP_OK(hipMalloc(&p, bytes ? bytes : 16)); }
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    template <typename T> T* as() { return (T*)p; }
+};
+
+// Everything a handle (or a call) takes from HIP, in one place: device memory, mapped pinned host memory, events, streams.  Its
+// destructor makes `device` current, synchronises it, releases all of it and puts the caller's device back -- as a member of the
+// handle it runs on destruction and when the handle's constructor throws part-way.  What a caller provides is never taken.
+class HipOwner {
+public:
+    explicit HipOwner(int device) : device_(device) {}
+    ~HipOwner() {
+        int prev = device_;
+        (void)hipGetDevice(&prev);
+        (void)hipSetDevice(device_);
+        (void)hipDeviceSynchronize();
+        for (hipStream_t s : streams_)
+            if (s) (void)hipStreamDestroy(s);
+        for (hipEvent_t e : events_)
+            if (e) (void)hipEventDestroy(e);
+        for (void* h : pinned_) (void)hipHostFree(h);
+        mem_.clear();
+        if (prev != device_) (void)hipSetDevice(prev);
+    }
+    HipOwner(const HipOwner&) = delete;
+    HipOwner& operator=(const HipOwner&) = delete;
+
+    // (each resource gets its slot before HIP is asked for it: a failure leaves nothing untracked)
+    void* mem(size_t bytes) { return mem_.emplace_back(bytes).p; }
+    void* pinned(size_t bytes, void** dev) {      // mapped: *dev = the device's view of the returned host memory
+        void*& h = pinned_.emplace_back();
+        HIP_OK(hipHostMalloc(&h, bytes, hipHostMallocMapped));
+        HIP_OK(hipHostGetDevicePointer(dev, h, 0));
+        return h;
+    }
+    hipEvent_t event() {
+        hipEvent_t& e = events_.emplace_back();
+        HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        return e;
+    }
+    hipStream_t stream() {
+        hipStream_t& s = streams_.emplace_back();
+        HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        return s;
+    }
+    // give back early what pinned() / stream() handed out; anything else (a caller's stream) is left alone
+    void free_pinned(void* h) {
+        if (take(pinned_, h)) HIP_OK(hipHostFree(h));
+    }
+    void free_stream(hipStream_t s) {
+        if (take(streams_, s)) (void)hipStreamDestroy(s);
+    }
+
+private:
+    template <typename T> static bool take(std::vector<T>& v, T x) {
+        auto it = std::find(v.begin(), v.end(), x);
+        if (it == v.end()) return false;
+        v.erase(it);
+        return true;
+    }
+    int device_;
+    std::vector<DevBuf> mem_;
+    std::vector<void*> pinned_;
+    std::vector<hipEvent_t> events_;
+    std::vector<hipStream_t> streams_;
 };
 
 // Per-launch timing with HIP events on the launching stream (bench.py's roofline block).

@@ -188,7 +188,13 @@ struct TailPackItem {
     void* packed;
 };
 void tail_chain_pack_filters(const TailPackItem* items, int n, hipStream_t s);      // one launch
-void tail_chain_bf16(const TailStage* stages, int nstages, int nimg, const char* label, hipStream_t s);
+// The stage tables tail_chain_bf16 has uploaded into `owner`'s device memory, found again by content.  The caller keeps the store
+// as long as the launches may run: a handle for its life (one table per direction and lane start), an op for the call.
+struct TailTables {
+    HipOwner& owner;
+    std::vector<std::pair<std::vector<char>, const void*>> uploaded;
+};
+void tail_chain_bf16(const TailStage* stages, int nstages, int nimg, const char* label, hipStream_t s, TailTables& tables);
 // the weight gradients of several small layers in ONE launch, each with a single pixel split and the direct epilogue
 // (dw = x^T dy + weight_decay * w, dbias = column sums of dy): no slabs, no reduce launches
 struct WgradGroupItem {

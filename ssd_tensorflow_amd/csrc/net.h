@@ -73,14 +73,13 @@ struct Variable {
     size_t count() const { return rows * width; }
 };
 
-// one output slot of the decode + NMS pass: packed [count | conf | cls | idx | box] in HBM + pinned host mirror
+// one output slot of the decode + NMS pass: packed [count | conf | cls | idx | box] in pinned, device-mapped host memory
 struct DetectSlot {
-    char* dev = nullptr;
+    char* dev = nullptr;            // the device's view of `host` (no HBM copy, no transfer)
     char* host = nullptr;
     size_t bytes = 0, used = 0;
     int b = 0, out_cap = 0;
-    bool mapped = false;            // dev IS the device's view of the pinned host buffer (no HBM copy, no transfer)
-    hipEvent_t ready = nullptr;     // recorded behind the pass (behind the device-to-host copy when !mapped)
+    hipEvent_t ready = nullptr;     // recorded behind the pass
 };
 
 class Net {
@@ -134,11 +133,11 @@ public:
     void pool_fusion(int* out, int cap, int* count) const;      // per 2x2 stride-2 pool in graph order: bit 0 fused forward, bit 1 fused backward
 
     void detect_last(int b, float thr, int cap, int max_out, int out_cap, bool nms, int* count, float* conf, int* cls, int* idx, int* box);
-    // asynchronous form: kernels + one device-to-host copy enqueued; dev_out (optional) = the HBM arrays of the slot
+    // asynchronous form: the kernels enqueued; dev_out (optional) = the device's view of the slot's arrays
     const DetectSlot& detect_last_dev(int b, float thr, int cap, int max_out, int out_cap, bool nms, DetectOut* dev_out);
-    // host copy of the latest (which = 0) or the previous (which = 1) pass; waits for that slot's copy only
+    // host copy of the latest (which = 0) or the previous (which = 1) pass; waits for that slot's pass only
     void detect_fetch(int which, int* count, float* conf, int* cls, int* idx, int* box);
-    // the pinned host mirror of that slot itself (valid until the second-next pass); waits for the slot's copy only
+    // the pinned host memory of that slot itself (valid until the second-next pass); waits for the slot's pass only
     void detect_host(int which, DetectOut* host, int* b, int* out_cap);
 
     const Preset& preset() const { return *preset_; }
@@ -167,7 +166,6 @@ private:
     ConvDesc conv_desc(const Op& op, int b) const;
     float current_lr() const;
     const Variable& find_var(const char* name) const;
-    void* dalloc(size_t bytes);
 
     const Preset* preset_;
     int C_, Bmax_, device_;
@@ -228,8 +226,6 @@ private:
     void bw_wrote(int x, Tensor& t, bool carried = false);
     size_t bw_final_lo() const;          // lowest arena offset such that every filter at or above it has its final gradient
     bool overlap_ = true;
-    bool own_wstream_ = true;
-    bool s2_is_w_ = false;                 // the second forward lane's stream IS the weight-gradient stream (four streams in all)
 
     std::vector<Tensor> tensors_;
     std::vector<Op> ops_;
@@ -240,7 +236,6 @@ private:
 
     size_t nparams_ = 0, nfilters_ = 0, scale_off_ = 0;
     float *params_ = nullptr, *grads_ = nullptr, *mom_ = nullptr;
-    bool own_params_ = false, own_grads_ = false, own_mom_ = false;
 
     float* result_ = nullptr;
     float *x_stage_ = nullptr, *y_stage_ = nullptr;
@@ -262,7 +257,6 @@ private:
     DetectSlot det_slot_[2];
     int det_cur_ = 0;
     void detect_slot_carve(const DetectSlot& sl, DetectOut& d, char* base) const;
-    std::vector<void*> allocs_;
 
     std::vector<float> lr_values_{0.001f};
     std::vector<long long> lr_bounds_;
@@ -271,6 +265,10 @@ private:
     Profiler prof_;
     int bw_pos_ = 0, bw_b_ = 0;          // next entry of bwd_order_
     size_t bw_done_off_ = 0;
+    // Every buffer, pinned page, event and stream above that the handle made itself.  Declared after every member that holds its
+    // handles, so it is destroyed before them: the device is synchronised before the members above (prof_'s events) go.
+    HipOwner hip_;
+    TailTables tail_tables_{hip_, {}};   // the tail chain's stage tables (one per direction and lane start) in hip_'s memory
 };
 
 }  // namespace ssd

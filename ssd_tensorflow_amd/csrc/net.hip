@@ -408,7 +408,7 @@ void Net::plan_tail_chain() {
             total += tail_chain_packed_elems(d, true);
         }
     }
-    wq_tail_ = (bf16_t*)dalloc(total * 2);
+    wq_tail_ = (bf16_t*)hip_.mem(total * 2);
     chain_fwd_ = (mode & 1) != 0;
     chain_bwd_ = (mode & 2) != 0 && training_;
 }
@@ -442,7 +442,7 @@ void Net::launch_tail_forward(int b0, int nb, hipStream_t s) {
         st.push_back(t);
     }
     prof_.layer = "tail";
-    tail_chain_bf16(st.data(), (int)st.size(), nb, "tail_fwd_bf16", s);
+    tail_chain_bf16(st.data(), (int)st.size(), nb, "tail_fwd_bf16", s, tail_tables_);
 }
 
 // The chain's part of backward (see plan_tail_chain): called when backward_step meets the chain's first op in its order.
@@ -477,7 +477,7 @@ void Net::launch_tail_backward(int b, bool* side_used) {
     g_stop_event = carry ? first_out->gev : nullptr;
     {
         struct Disarm { ~Disarm() { g_stop_event = nullptr; } } disarm;
-        tail_chain_bf16(st.data(), (int)st.size(), b, "tail_dgrad_bf16", ds);
+        tail_chain_bf16(st.data(), (int)st.size(), b, "tail_dgrad_bf16", ds, tail_tables_);
     }
     for (Tensor* t : written) {      // one kernel wrote them all: the carried event (if any) stands for every one of them
         t->gstream = cls;
@@ -545,15 +545,15 @@ void Net::plan_winograd() {
         if (!(op.wino_f || op.wino_d)) continue;
         const size_t u = (size_t)36 * d.Ci * d.Co, uf = (size_t)36 * d.Ci * wino_kpad(d.Co), t = (size_t)36 * wino_tiles(d);
         if (op.wino_f) {
-            op.wino_U = (float*)dalloc(u * sizeof(float));
+            op.wino_U = (float*)hip_.mem(u * sizeof(float));
             // the input's transform: kept per layer by a training handle (the weight gradient reads it), per-stream scratch otherwise
-            if (training_) op.wino_V = (float*)dalloc(t * d.Ci * sizeof(float));
+            if (training_) op.wino_V = (float*)hip_.mem(t * d.Ci * sizeof(float));
             else v_max = std::max(v_max, t * d.Ci);
             m_max = std::max(m_max, t * d.Co);
         }
-        if (op.wino_f && op.wino_d) op.wino_bits = dalloc((size_t)wino_tiles(d) * (d.Ci / 4) * 8);      // (against the fp32 mask: 23.47 -> 23.02 ms, profiles/r06_be_*)
+        if (op.wino_f && op.wino_d) op.wino_bits = hip_.mem((size_t)wino_tiles(d) * (d.Ci / 4) * 8);      // (against the fp32 mask: 23.47 -> 23.02 ms, profiles/r06_be_*)
         if (op.wino_d) {
-            op.wino_Uf = (float*)dalloc(uf * sizeof(float));
+            op.wino_Uf = (float*)hip_.mem(uf * sizeof(float));
             HIP_OK(hipMemset(op.wino_Uf, 0, uf * sizeof(float)));      // (rows Co ... kpad(Co) - 1 of every position stay zero)
             yt_max = std::max(yt_max, t * wino_kpad(d.Co));
             xw_max = std::max(xw_max, t * d.Ci);
@@ -569,16 +569,16 @@ void Net::plan_winograd() {
         wino_any_d_ |= op.wino_d;
     }
     if (wino_plan_.n + wino_plan_first_.n + wino_plan_flip_.n == 0) return;
-    HIP_OK(hipEventCreateWithFlags(&ev_wino_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_wino_first_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_wino_flip_, hipEventDisableTiming));
-    if (m_max) for (int l = 0; l < 3; ++l) wino_m_[l] = (float*)dalloc(m_max * sizeof(float));
-    if (v_max) for (int l = 0; l < 3; ++l) wino_vs_[l] = (float*)dalloc(v_max * sizeof(float));
+    ev_wino_ = hip_.event();
+    ev_wino_first_ = hip_.event();
+    ev_wino_flip_ = hip_.event();
+    if (m_max) for (int l = 0; l < 3; ++l) wino_m_[l] = (float*)hip_.mem(m_max * sizeof(float));
+    if (v_max) for (int l = 0; l < 3; ++l) wino_vs_[l] = (float*)hip_.mem(v_max * sizeof(float));
     if (training_) {
-        wino_yt_ = (float*)dalloc(yt_max * sizeof(float));
-        wino_xw_ = (float*)dalloc(xw_max * sizeof(float));
-        wino_ya_ = (float*)dalloc(yt_max * sizeof(float));
-        wino_slab_ = (float*)dalloc(slab_max * sizeof(float));
+        wino_yt_ = (float*)hip_.mem(yt_max * sizeof(float));
+        wino_xw_ = (float*)hip_.mem(xw_max * sizeof(float));
+        wino_ya_ = (float*)hip_.mem(yt_max * sizeof(float));
+        wino_slab_ = (float*)hip_.mem(slab_max * sizeof(float));
     }
 }
 
@@ -613,17 +613,6 @@ size_t Net::arena_floats(const char* preset, int num_classes, int graph) {
     return n + 512;
 }
 
-// ---------------------------------------------------------------------------------
-// memory
-// ---------------------------------------------------------------------------------
-void* Net::dalloc(size_t bytes) {
-    void* p = nullptr;
-    if (bytes == 0) bytes = 16;
-    HIP_OK(hipMalloc(&p, bytes));
-    allocs_.push_back(p);
-    return p;
-}
-
 ConvDesc Net::conv_desc(const Op& op, int b) const {
     const Tensor& in = tensors_[op.in];
     const Tensor& out = tensors_[op.out];
@@ -640,10 +629,10 @@ void Net::alloc() {
     for (size_t i = 0; i < tensors_.size(); ++i) {
         Tensor& t = tensors_[i];
         if ((int)i == input_t_) continue;
-        t.data = dalloc(t.per_image() * B * (t.data_f32 ? 4 : 2));
+        t.data = hip_.mem(t.per_image() * B * (t.data_f32 ? 4 : 2));
         HIP_OK(hipMemset(t.data, 0, t.per_image() * B * (t.data_f32 ? 4 : 2)));
         if (training_) {
-            t.grad = dalloc(t.per_image() * B * (t.grad_f32 ? 4 : 2));
+            t.grad = hip_.mem(t.per_image() * B * (t.grad_f32 ? 4 : 2));
             HIP_OK(hipMemset(t.grad, 0, t.per_image() * B * (t.grad_f32 ? 4 : 2)));   // head pad columns stay 0 forever
         }
     }
@@ -652,13 +641,13 @@ void Net::alloc() {
         heads_.dbuf[i] = tensors_[head_t_[i]].grad;
     }
     if (bf16_) {
-        wq_io_ = (bf16_t*)dalloc(nfilters_ * 2);
-        wq_oi_ = (bf16_t*)dalloc(nfilters_ * 2);
+        wq_io_ = (bf16_t*)hip_.mem(nfilters_ * 2);
+        wq_oi_ = (bf16_t*)hip_.mem(nfilters_ * 2);
     }
-    if (!params_) { params_ = (float*)dalloc(nparams_ * sizeof(float)); own_params_ = true; }
+    if (!params_) params_ = (float*)hip_.mem(nparams_ * sizeof(float));
     if (training_) {
-        if (!grads_) { grads_ = (float*)dalloc(nparams_ * sizeof(float)); own_grads_ = true; }
-        if (!mom_) { mom_ = (float*)dalloc(nparams_ * sizeof(float)); own_mom_ = true; }
+        if (!grads_) grads_ = (float*)hip_.mem(nparams_ * sizeof(float));
+        if (!mom_) mom_ = (float*)hip_.mem(nparams_ * sizeof(float));
         HIP_OK(hipMemset(grads_, 0, nparams_ * sizeof(float)));
         HIP_OK(hipMemset(mom_, 0, nparams_ * sizeof(float)));
         // split-M slab workspace: one region per layer (the reduces of a backward stage run as one grouped launch at its
@@ -675,8 +664,8 @@ void Net::alloc() {
                 op.ws_off = ws_total;
                 ws_total += (ws + 63) / 64 * 64;
             }
-        wgrad_ws_ = (float*)dalloc(ws_total * sizeof(float));
-        l2_ws_ = (float*)dalloc(l2norm_bwd_ws_floats(B * 64 * 64, 512) * sizeof(float));
+        wgrad_ws_ = (float*)hip_.mem(ws_total * sizeof(float));
+        l2_ws_ = (float*)hip_.mem(l2norm_bwd_ws_floats(B * 64 * 64, 512) * sizeof(float));
         size_t pws = 0;
         for (auto& op : ops_)
             if (op.kind == OP_POOL) {
@@ -685,37 +674,34 @@ void Net::alloc() {
                 PoolDesc d{B, in.H, in.W, in.C, out.H, out.W, op.k, op.stride, op.pad_h, op.pad_w};
                 pws = std::max(pws, maxpool_bwd_ws_bytes(d));
             }
-        pool_ws_ = dalloc(pws);
+        pool_ws_ = hip_.mem(pws);
         // 2x2 pools whose input has no other consumer keep a forward record for their backward (ops.h)
         for (auto& op : ops_)
             if (op.kind == OP_POOL) {
                 const Tensor& in = tensors_[op.in];
                 const Tensor& out = tensors_[op.out];
                 PoolDesc d{B, in.H, in.W, in.C, out.H, out.W, op.k, op.stride, op.pad_h, op.pad_w};
-                if (maxpool_rec_applicable(d) && in.consumers == 1) op.pool_rec = dalloc(maxpool_rec_bytes(d));
+                if (maxpool_rec_applicable(d) && in.consumers == 1) op.pool_rec = hip_.mem(maxpool_rec_bytes(d));
             }
     }
-    result_ = (float*)dalloc((size_t)B * A * nv * sizeof(float));
-    x_stage_ = (float*)dalloc((size_t)B * preset_->image_h * preset_->image_w * 3 * sizeof(float));
-    y_stage_ = (float*)dalloc((size_t)B * A * nv * sizeof(float));
-    loss_ws_ = dalloc(loss_work_bytes(B, A));
+    result_ = (float*)hip_.mem((size_t)B * A * nv * sizeof(float));
+    x_stage_ = (float*)hip_.mem((size_t)B * preset_->image_h * preset_->image_w * 3 * sizeof(float));
+    y_stage_ = (float*)hip_.mem((size_t)B * A * nv * sizeof(float));
+    loss_ws_ = hip_.mem(loss_work_bytes(B, A));
     loss_work_carve(lw_, loss_ws_, B, A);
     HIP_OK(hipMemset(loss_ws_, 0, loss_work_bytes(B, A)));
     // The four losses are written by the loss kernel's final block straight into pinned, device-mapped host memory: a
     // 16-byte device-to-host copy would be a blit kernel of its own on the critical path between the loss and its
     // gradient (12 us of launch gap + the kernel in the rocprofv3 trace, tools/trace_gaps.py).
     // A ring of LOSS_RING such slots (one per forward pass) lets the host read step k - 1's losses while step k runs.
-    HIP_OK(hipHostMalloc((void**)&losses_host_, LOSS_RING * 4 * sizeof(float), hipHostMallocMapped));
+    void* dp = nullptr;
+    losses_host_ = static_cast<float*>(hip_.pinned(LOSS_RING * 4 * sizeof(float), &dp));
     for (int i = 0; i < LOSS_RING * 4; ++i) losses_host_[i] = 0.f;
-    {
-        void* dp = nullptr;
-        HIP_OK(hipHostGetDevicePointer(&dp, losses_host_, 0));
-        losses_dev_ = static_cast<float*>(dp);
-        lw_.losses = losses_dev_;
-    }
-    for (int i = 0; i < LOSS_RING; ++i) HIP_OK(hipEventCreateWithFlags(&ev_loss_[i], hipEventDisableTiming));
-    anchors_dev_ = (double*)dalloc((size_t)A * 4 * sizeof(double));
-    anchors_abs_dev_ = (int*)dalloc((size_t)A * 4 * sizeof(int));
+    losses_dev_ = static_cast<float*>(dp);
+    lw_.losses = losses_dev_;
+    for (int i = 0; i < LOSS_RING; ++i) ev_loss_[i] = hip_.event();
+    anchors_dev_ = (double*)hip_.mem((size_t)A * 4 * sizeof(double));
+    anchors_abs_dev_ = (int*)hip_.mem((size_t)A * 4 * sizeof(int));
     anchors_device(*preset_, anchors_dev_, anchors_abs_dev_, nullptr);
     HIP_OK(hipDeviceSynchronize());
 }
@@ -749,7 +735,7 @@ void Net::init_weights(unsigned long long seed) {
 Net::Net(const char* preset, int num_classes, int max_batch, int device, bool training, unsigned long long seed,
          float* ext_params, float* ext_grads, float* ext_momentum, int dtype, int graph)
     : preset_(&get_preset(preset)), C_(num_classes), Bmax_(max_batch), device_(device), training_(training), bf16_(dtype == 1),
-      fc_(graph == 1) {
+      fc_(graph == 1), hip_(device) {
     SSD_REQUIRE(dtype == 0 || dtype == 1, "dtype must be 0 (fp32) or 1 (bf16), got %d", dtype);
     SSD_REQUIRE(graph == 0 || graph == 1, "graph must be 0 (a-trous) or 1 (fc), got %d", graph);
     require_num_classes(num_classes);
@@ -761,20 +747,20 @@ Net::Net(const char* preset, int num_classes, int max_batch, int device, bool tr
     init_weights(seed);
     const char* ov = getenv("SSD_OVERLAP_WGRAD");
     overlap_ = !(ov && ov[0] == '0');
-    HIP_OK(hipStreamCreateWithFlags(&hstream_, hipStreamNonBlocking));      // (a high-priority side stream was measured again in round 5: +-0)
-    HIP_OK(hipEventCreateWithFlags(&ev_h_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_cast_, hipEventDisableTiming));
+    hstream_ = hip_.stream();      // (a high-priority side stream was measured again in round 5: +-0)
+    ev_h_ = hip_.event();
+    ev_cast_ = hip_.event();
 
-    HIP_OK(hipEventCreateWithFlags(&ev2_h_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_l2_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags(&ev_m2s_, hipEventDisableTiming));
-    for (int i = 0; i < MAX_MAPS; ++i) HIP_OK(hipEventCreateWithFlags(&ev2_fmap_[i], hipEventDisableTiming));
-    for (int i = 0; i < MAX_MAPS; ++i) HIP_OK(hipEventCreateWithFlags(&ev_fmap_[i], hipEventDisableTiming));
+    ev2_h_ = hip_.event();
+    ev_l2_ = hip_.event();
+    ev_join_ = hip_.event();
+    ev_m2s_ = hip_.event();
+    for (int i = 0; i < MAX_MAPS; ++i) ev2_fmap_[i] = hip_.event();
+    for (int i = 0; i < MAX_MAPS; ++i) ev_fmap_[i] = hip_.event();
     if (training_) {
-        HIP_OK(hipStreamCreateWithFlags(&wstream_, hipStreamNonBlocking));
-        HIP_OK(hipEventCreateWithFlags(&ev_dy_, hipEventDisableTiming));
-        HIP_OK(hipEventCreateWithFlags(&ev_w_, hipEventDisableTiming));
+        wstream_ = hip_.stream();
+        ev_dy_ = hip_.event();
+        ev_w_ = hip_.event();
     }
     // FEW streams: the hardware runs four queues side by side (ROCm's default GPU_MAX_HW_QUEUES); a fifth
     // active stream is time-multiplexed onto one of them, and which two streams then share a queue depends on creation
@@ -784,12 +770,7 @@ Net::Net(const char* preset, int num_classes, int max_batch, int device, bool tr
     // (forward / backward), so they are ONE stream, and the second lane runs its heads on its own main stream as well: THREE
     // streams beside the caller's measure the same as four (bf16 4142 vs 4081 images/s, r02_w) and leave the fourth queue to
     // a data-parallel caller's collective stream.
-    if (training_) {
-        s2_ = wstream_;
-        s2_is_w_ = true;
-    } else {
-        HIP_OK(hipStreamCreateWithFlags(&s2_, hipStreamNonBlocking));
-    }
+    s2_ = training_ ? wstream_ : hip_.stream();
     plan_pool_fusion();
     plan_tail_chain();
     plan_winograd();
@@ -799,47 +780,11 @@ Net::Net(const char* preset, int num_classes, int max_batch, int device, bool tr
     if (training_)
         for (const Op& op : ops_)
             if (op.in != input_t_ && !tensors_[op.in].gev)
-                HIP_OK(hipEventCreateWithFlags(&tensors_[op.in].gev, hipEventDisableTiming));
+                tensors_[op.in].gev = hip_.event();
 }
 
 Net::~Net() {
     if (g_prof == &prof_) g_prof = nullptr;
-    int prev_dev = device_;
-    (void)hipGetDevice(&prev_dev);
-    (void)hipSetDevice(device_);
-    (void)hipDeviceSynchronize();
-    for (DetectSlot& sl : det_slot_) {
-        if (sl.dev && !sl.mapped) (void)hipFree(sl.dev);
-        if (sl.host) (void)hipHostFree(sl.host);
-        if (sl.ready) (void)hipEventDestroy(sl.ready);
-    }
-    if (hstream_) {
-        (void)hipStreamDestroy(hstream_);
-        (void)hipEventDestroy(ev_h_);
-        (void)hipEventDestroy(ev_cast_);
-        if (ev_wino_) (void)hipEventDestroy(ev_wino_);
-        if (ev_wino_first_) (void)hipEventDestroy(ev_wino_first_);
-        if (ev_wino_flip_) (void)hipEventDestroy(ev_wino_flip_);
-        if (!s2_is_w_) (void)hipStreamDestroy(s2_);
-        (void)hipEventDestroy(ev2_h_);
-        (void)hipEventDestroy(ev_l2_);
-        (void)hipEventDestroy(ev_join_);
-        (void)hipEventDestroy(ev_m2s_);
-        for (int i = 0; i < MAX_MAPS; ++i) (void)hipEventDestroy(ev2_fmap_[i]);
-        for (int i = 0; i < MAX_MAPS; ++i) (void)hipEventDestroy(ev_fmap_[i]);
-    }
-    if (wstream_) {
-        if (own_wstream_) (void)hipStreamDestroy(wstream_);
-        (void)hipEventDestroy(ev_dy_);
-        (void)hipEventDestroy(ev_w_);
-    }
-    for (Tensor& t : tensors_)
-        if (t.gev) (void)hipEventDestroy(t.gev);
-    for (void* p : allocs_) (void)hipFree(p);
-    if (losses_host_) (void)hipHostFree(losses_host_);
-    for (int i = 0; i < LOSS_RING; ++i)
-        if (ev_loss_[i]) (void)hipEventDestroy(ev_loss_[i]);
-    if (prev_dev != device_) (void)hipSetDevice(prev_dev);
 }
 
 // ---------------------------------------------------------------------------------
@@ -1413,10 +1358,9 @@ std::vector<std::pair<size_t, size_t>> Net::backward_ranges(size_t min_floats) c
 
 void Net::set_wgrad_stream(hipStream_t s) {
     SSD_REQUIRE(training_, "handle was created with training = 0");
-    if (own_wstream_ && wstream_) (void)hipStreamDestroy(wstream_);
+    hip_.free_stream(wstream_);      // (the handle's own: the hardware queues go by which streams exist)
     wstream_ = s;
-    own_wstream_ = false;
-    if (s2_is_w_) s2_ = s;      // the second forward lane lives on the weight-gradient stream
+    s2_ = s;      // a training handle's second forward lane lives on the weight-gradient stream
 }
 
 void Net::backward(int b, const float* y) {
@@ -1587,9 +1531,9 @@ void Net::activation(const char* name, int b, float* out, size_t count) {
 // ---------------------------------------------------------------------------------
 // decode + NMS of the last result
 // ---------------------------------------------------------------------------------
-// Two output slots alternate, each one packed device buffer [count | conf | cls | idx | box] with a pinned
-// host mirror: the kernels and ONE device-to-host copy are enqueued, an event marks the copy, and the
-// caller collects a slot later (detect_fetch) -- e.g. after it has launched the next batch -- or at once.
+// Two output slots alternate, each one packed buffer [count | conf | cls | idx | box] in pinned, device-mapped
+// host memory: the kernels are enqueued, an event marks their end, and the caller collects a slot later
+// (detect_fetch) -- e.g. after it has launched the next batch -- or at once.
 static size_t det_count_bytes(int b) { return ((size_t)b * 4 + 255) / 256 * 256; }
 
 void Net::detect_slot_carve(const DetectSlot& sl, DetectOut& d, char* base) const {
@@ -1606,12 +1550,12 @@ const DetectSlot& Net::detect_last_dev(int b, float thr, int cap, int max_out, i
     SSD_REQUIRE(out_cap >= 1, "out_cap must be >= 1");
     const int A = preset_->num_anchors;
     if (!detect_ws_) {
-        detect_ws_ = dalloc(detect_ws_bytes(Bmax_, A));
+        detect_ws_ = hip_.mem(detect_ws_bytes(Bmax_, A));
     }
     det_cur_ ^= 1;
     DetectSlot& sl = det_slot_[det_cur_];
     if (!sl.ready) {
-        HIP_OK(hipEventCreateWithFlags(&sl.ready, hipEventDisableTiming));
+        sl.ready = hip_.event();
     } else {
         HIP_OK(hipEventSynchronize(sl.ready));      // the slot's previous copy must have landed before it is reused
     }
@@ -1619,24 +1563,15 @@ const DetectSlot& Net::detect_last_dev(int b, float thr, int cap, int max_out, i
     // device-mapped host memory from the per-image kernel's ordered emit -- like the four losses (alloc()): a
     // device-to-host copy of the whole [b][out_cap] arrays is a blit KERNEL of its own behind the pass (13 us per batch of
     // 128 in the rocprofv3 trace, a third of the pass) plus one more launch for the host to issue.
-    const bool mapped = true;
     const size_t need = det_count_bytes(b) + (size_t)b * out_cap * 28;
     if (need > sl.bytes) {
-        if (sl.dev && !sl.mapped) HIP_OK(hipFree(sl.dev));
-        if (sl.host) HIP_OK(hipHostFree(sl.host));
+        if (sl.host) hip_.free_pinned(sl.host);
         sl.dev = sl.host = nullptr;
         sl.bytes = 0;
         const size_t grow = std::max(need, det_count_bytes(Bmax_) + (size_t)Bmax_ * std::min(out_cap, 200) * 28);
-        sl.mapped = mapped;
-        if (mapped) {
-            HIP_OK(hipHostMalloc((void**)&sl.host, grow, hipHostMallocMapped));
-            void* dp = nullptr;
-            HIP_OK(hipHostGetDevicePointer(&dp, sl.host, 0));
-            sl.dev = static_cast<char*>(dp);
-        } else {
-            HIP_OK(hipMalloc((void**)&sl.dev, grow));
-            HIP_OK(hipHostMalloc((void**)&sl.host, grow));
-        }
+        void* dp = nullptr;
+        sl.host = static_cast<char*>(hip_.pinned(grow, &dp));
+        sl.dev = static_cast<char*>(dp);
         sl.bytes = grow;
     }
     sl.b = b; sl.out_cap = out_cap; sl.used = need;
@@ -1645,7 +1580,6 @@ const DetectSlot& Net::detect_last_dev(int b, float thr, int cap, int max_out, i
     DetectOut d;
     detect_slot_carve(sl, d, sl.dev);
     detect(A, C_, anchors_dev_, result_, b, thr, cap, max_out, out_cap, nms, d, detect_ws_, stream_);
-    if (!sl.mapped) HIP_OK(hipMemcpyAsync(sl.host, sl.dev, need, hipMemcpyDeviceToHost, stream_));
     HIP_OK(hipEventRecord(sl.ready, stream_));
     if (dev_out) *dev_out = d;
     return sl;

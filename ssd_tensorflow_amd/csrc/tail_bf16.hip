@@ -34,7 +34,6 @@
 #include "bf16.h"
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
 #ifndef TAIL_ABL
@@ -56,7 +55,7 @@ constexpr int TAIL_LDS_MAX = 160 * 1024;
 enum { TF_RELU = 1, TF_ACCUM = 2, TF_OUT_F32 = 4, TF_LOAD_IN = 8, TF_LOAD_OUT = 16, TF_KTAIL = 32 };
 
 // One stage of the chain as the kernel reads it: a table in DEVICE memory (read with scalar loads through a constant-address-space
-// pointer), built and cached by tail_chain_bf16.  Everything a wave would otherwise compute with integer divisions -- its task, its
+// pointer), built by tail_chain_bf16 and kept in the caller's TailTables.  Everything a wave would otherwise compute with integer divisions -- its task, its
 // k range -- is tabulated by the host: with 16 waves per CU every instruction of the per-stage setup is issued 16 times.
 struct TailStageK {
     const bf16_t* src;      // gathered tensor of THIS launch's first image
@@ -453,32 +452,17 @@ struct Region {
     int off, bytes, first, last;
 };
 
-// the stage tables live in device memory: one upload per distinct table (a handle has a few: per direction and lane shape)
-struct TableCache {
-    struct Entry { int device; std::vector<char> bytes; void* dev; };
-    std::mutex mu;
-    std::vector<Entry> entries;
-    const TailStageK* get(const TailStageK* tab, int n) {
-        int device = 0;
-        HIP_OK(hipGetDevice(&device));
-        const size_t bytes = (size_t)n * sizeof(TailStageK);
-        std::lock_guard<std::mutex> lock(mu);
-        for (const Entry& e : entries)
-            if (e.device == device && e.bytes.size() == bytes && !memcmp(e.bytes.data(), tab, bytes)) return static_cast<const TailStageK*>(e.dev);
-        if (entries.size() >= 256) {      // (a long-lived process that keeps creating handles: start over)
-            for (Entry& e : entries) (void)hipFree(e.dev);
-            entries.clear();
-        }
-        Entry e;
-        e.device = device;
-        e.bytes.assign(reinterpret_cast<const char*>(tab), reinterpret_cast<const char*>(tab) + bytes);
-        HIP_OK(hipMalloc(&e.dev, bytes));
-        HIP_OK(hipMemcpy(e.dev, tab, bytes, hipMemcpyHostToDevice));
-        entries.push_back(std::move(e));
-        return static_cast<const TailStageK*>(entries.back().dev);
-    }
-};
-TableCache g_tables;
+// the stage table in device memory: one upload per distinct table of a store
+const TailStageK* upload_table(TailTables& tables, const std::vector<TailStageK>& tab) {
+    const char* p = reinterpret_cast<const char*>(tab.data());
+    const size_t bytes = tab.size() * sizeof(TailStageK);
+    for (const auto& e : tables.uploaded)
+        if (e.first.size() == bytes && !memcmp(e.first.data(), p, bytes)) return static_cast<const TailStageK*>(e.second);
+    void* dev = tables.owner.mem(bytes);
+    HIP_OK(hipMemcpy(dev, p, bytes, hipMemcpyHostToDevice));
+    tables.uploaded.emplace_back(std::vector<char>(p, p + bytes), dev);
+    return static_cast<const TailStageK*>(dev);
+}
 
 }  // namespace
 
@@ -523,7 +507,7 @@ bool tail_chain_stage_supported(const ConvDesc& d) {
            cdiv(d.Co, 16) * cdiv(cdiv(Mo, 16), TAIL_MG) <= TAIL_MAX_TASKS && cdiv(d.Ci, 16) * cdiv(cdiv(Mi, 16), TAIL_MG) <= TAIL_MAX_TASKS;
 }
 
-void tail_chain_bf16(const TailStage* stages, int nstages, int nimg, const char* label, hipStream_t s) {
+void tail_chain_bf16(const TailStage* stages, int nstages, int nimg, const char* label, hipStream_t s, TailTables& tables) {
     SSD_REQUIRE(nstages >= 1 && nstages <= TAIL_MAX_STAGES, "tail chain: 1..%d stages (got %d)", TAIL_MAX_STAGES, nstages);
     SSD_REQUIRE(nimg >= 1, "tail chain: no images");
     std::vector<TailStageK> tab(nstages);
@@ -661,7 +645,7 @@ void tail_chain_bf16(const TailStage* stages, int nstages, int nimg, const char*
         lds_total = std::max(lds_total, k.scratch_off + scratch);
     }
     SSD_REQUIRE(lds_total <= TAIL_LDS_MAX, "tail chain: the stages' feature maps need %d bytes of LDS (limit %d)", lds_total, TAIL_LDS_MAX);
-    const TailStageK* tab_dev = g_tables.get(tab.data(), nstages);
+    const TailStageK* tab_dev = upload_table(tables, tab);
     static bool once = (set_lds(tail_chain_bf16_kernel, TAIL_LDS_MAX), true);
     (void)once;
     ProfScope prof(label, flops, bytes, s);

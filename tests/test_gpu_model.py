@@ -372,3 +372,42 @@ def test_staged_backward_equals_plain_and_ranges_tile_the_filters():
     assert hi == 0
     assert all(cnt >= 4_000_000 for _, cnt in ranges[:-1])
     sess.close()
+
+
+def test_destroyed_handles_give_their_memory_back():
+    """Four cycles of create, step, destroy of three handles -- fp32 training (Winograd layers), bf16 training stepped at two batch
+    sizes (the tail chain's stage tables), fp32 inference with a detect pass: the device's free memory after the last cycle is
+    where it was after the first (which also pays for the code objects and whatever the runtime keeps)."""
+    import gc
+    b = 8
+    preset = ob.get_preset('vgg300')
+    x, y, _ = ref.synth_batch(np.random.default_rng(6), b, preset)
+    xt = torch.from_numpy(x).cuda(); yt = torch.from_numpy(y).cuda()
+
+    def cycle():
+        with Session(0) as sess:
+            for dtype, batches in (('f32', (b,)), ('bf16', (b, 3))):
+                net = SSDVGG(sess, 'vgg300')
+                net.build_from_vgg(None, 20, max_batch=b, dtype=dtype)
+                net.build_optimizer(learning_rate=0.001)
+                for nb in batches:
+                    net.forward_backward_dev(xt[:nb], yt[:nb])
+                    net.apply_gradients_dev(1.0)
+            net = SSDVGG(sess, 'vgg300')
+            net.build_from_vgg(None, 20, max_batch=b, training=False)
+            r = net.infer(x)
+            net.detect_last(b, float(np.quantile(r[:, :, :20].max(-1), 0.999)), None, 200)
+            torch.cuda.synchronize()
+            alive = torch.cuda.mem_get_info()[0]
+        del net
+        gc.collect()
+        torch.cuda.empty_cache()
+        return alive, torch.cuda.mem_get_info()[0]
+
+    free = [cycle() for _ in range(4)]
+    held = free[0][1] - free[0][0]
+    drift = free[0][1] - free[-1][1]
+    print(f'    three handles hold {held / 2**20:.0f} MiB; free memory after cycles 1..4 (MiB): {[f / 2**20 for _, f in free]}')
+    bound = 64 << 20
+    assert held > 16 * bound, 'the handles are too small for the bound to show a leak'
+    assert drift < bound, f'{drift / 2**20:.0f} MiB less free after four cycles than after one'
