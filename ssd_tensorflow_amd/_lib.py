@@ -60,6 +60,12 @@ SIGNATURES = {
     'ssd_arena_floats': (sz, [cstr, i32]),
     'ssd_augment_ws_bytes': (sz, [i32, i32, i32]),
     'ssd_augment_batch_dev': (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+    'ssd_annotate_rect': (i32, [vp, i32, i32, vp]),
+    'ssd_annotate_glyph': (i32, [i32, vp]),
+    'ssd_annotate_style_create': (i32, [i32, i32, vp, vp, C.POINTER(vp)]),
+    'ssd_annotate_style_destroy': (i32, [vp]),
+    'ssd_annotate_ws_bytes': (sz, [i32, i32]),
+    'ssd_annotate_batch_dev': (i32, [vp, i32, vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, i32, vp, vp]),
     'ssd_sampler_trials': (i32, [vp, i32, vp, vp, i32, i32, vp, i32, vp, vp]),
     'ssd_create': (i32, [cstr, i32, i32, i32, i32, C.c_ulonglong, vp, vp, vp, C.POINTER(handle)]),
     'ssd_create_dtype': (i32, [cstr, i32, i32, i32, i32, C.c_ulonglong, vp, vp, vp, i32, C.POINTER(handle)]),

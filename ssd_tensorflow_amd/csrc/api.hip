@@ -2,6 +2,7 @@
 #include "../../include/ssdvgg_hip.h"
 #include "net.h"
 #include "augment.h"
+#include "annotate.h"
 #include "metrics.h"
 #include <vector>
 #include <map>
@@ -395,6 +396,57 @@ int ssd_augment_batch_dev(const unsigned char* images_dev, const ssd_augment_par
     API_BEGIN
     SSD_REQUIRE(images_dev && params && out_dev && ws_dev, "null argument");
     augment_batch(images_dev, params, b, out_w, out_h, out_dev, ws_dev, (hipStream_t)stream);
+    API_END
+}
+
+// ---------------------------------------------------------------------------------- drawing
+struct ssd_annotate_style_s {
+    ssd::AnnotateStyle* style;
+};
+
+int ssd_annotate_rect(const int box1000[4], int w, int h, int out[4]) {
+    API_BEGIN
+    annotate_rect(box1000, w, h, out);
+    API_END
+}
+
+int ssd_annotate_glyph(int ch, unsigned char rows[7]) {
+    API_BEGIN
+    annotate_glyph(ch, rows);
+    API_END
+}
+
+int ssd_annotate_style_create(int device, int num_classes, const unsigned char* colors_bgr, const char* names, ssd_annotate_style* out) {
+    API_BEGIN
+    SSD_REQUIRE(out != nullptr, "out style pointer is null");
+    *out = nullptr;
+    require_num_classes(num_classes);
+    DeviceGuard dev_guard_(device);
+    std::unique_ptr<AnnotateStyle, void (*)(AnnotateStyle*)> st(annotate_style_create(device, num_classes, colors_bgr, names), annotate_style_destroy);
+    *out = new ssd_annotate_style_s{st.get()};
+    st.release();
+    API_END
+}
+
+int ssd_annotate_style_destroy(ssd_annotate_style s) {
+    API_BEGIN
+    if (s) {
+        annotate_style_destroy(s->style);
+        delete s;
+    }
+    API_END
+}
+
+size_t ssd_annotate_ws_bytes(int b, int out_cap) { return annotate_ws_bytes(b, out_cap); }
+
+int ssd_annotate_batch_dev(const void* src_dev, int src_is_f32, const ssd_annotate_image* images, int b, const int* count_dev,
+                           const int* cls_dev, const int* box_dev, int out_cap, int boxes_on_1000_grid, ssd_annotate_style style,
+                           int rgb_out, void* dst_dev, int dst_is_f32, void* ws_dev, void* stream) {
+    API_BEGIN
+    SSD_REQUIRE(style && style->style, "annotate: null style");
+    DeviceGuard dev_guard_(annotate_style_device(style->style));
+    annotate_batch(src_dev, src_is_f32 != 0, images, b, count_dev, cls_dev, box_dev, out_cap, boxes_on_1000_grid != 0, style->style,
+                   rgb_out != 0, dst_dev, dst_is_f32 != 0, ws_dev, (hipStream_t)stream);
     API_END
 }
 

@@ -1,0 +1,75 @@
+#!/usr/bin/env python3
+"""Deployment tool: the counterpart of the reference's detect.py (:41-125) over the HIP library.  Image files in; per image
+`<name>.txt` with one '{label} {labelid} {cx} {cy} {w} {h}' line per detection (detect.py:119-122) and the image with the
+detections drawn on it (annotate.py) out.  --model is a checkpoint .npz: it already carries the preset, the
+graph and the class names the reference reads from its .pb + training-data pickle.  Threshold 0.5, NMS, [:200]
+(detect.py:111-112)."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+from .annotate import Style, write_image
+from .infer import sample_generator, resolve_class_names
+from .ssdvgg import SSDVGG, Session
+from .ssdutils import get_preset_by_name, boxes_from_detection
+from .utils import default_colors
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description='SSD inference')
+    parser.add_argument('files', nargs='*')
+    parser.add_argument('--model', default='model300.npz', help='model file (a checkpoint .npz)')
+    parser.add_argument('--training-data', default='', help='unused: the checkpoint carries the preset and the class names')
+    parser.add_argument('--output-dir', default='test-out', help='output directory')
+    parser.add_argument('--batch-size', type=int, default=32, help='batch size')
+    parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='f32, or bf16 activations on the bf16 matrix cores')
+    args = parser.parse_args(argv)
+
+    print('[i] Model:         ', args.model)
+    print('[i] Training data: ', args.training_data)
+    print('[i] Output dir:    ', args.output_dir)
+    print('[i] Batch size:    ', args.batch_size)
+    if not os.path.exists(args.model):
+        print('[!] Cannot find model ' + args.model); return 1
+    files = [f for f in args.files if os.path.exists(f) or os.path.exists(f + '.npy')]
+    os.makedirs(args.output_dir, exist_ok=True)
+
+    with Session(0) as sess:
+        with np.load(args.model, allow_pickle=False) as ck:
+            pname, num_classes = str(ck['__preset__']), int(ck['__num_classes__'])
+            stored = ck['__class_names__'] if '__class_names__' in ck.files else None
+        net = SSDVGG(sess, get_preset_by_name(pname))
+        net.build_from_metagraph(None, args.model, max_batch=args.batch_size, dtype=args.dtype)
+        lid2name = resolve_class_names(num_classes, None, stored)
+        names = [str(lid2name[i]) for i in range(num_classes)]
+        colors = default_colors(names)
+        style = Style([colors[n] for n in names], names, sess.device)
+
+        def collect(pending):
+            ticket, idxs, drawn = pending
+            images = drawn.get()
+            for i, det in enumerate(ticket.get()):
+                name = os.path.basename(files[idxs[i]])
+                with open(os.path.join(args.output_dir, name + '.txt'), 'w') as f:
+                    for _, box in boxes_from_detection(det, lid2name):
+                        f.write('{} {} {} {} {} {}\n'.format(box.label, box.labelid, box.center.x, box.center.y, box.size.w, box.size.h))
+                write_image(os.path.join(args.output_dir, name), images[i])
+
+        pending = None
+        for x, idxs, sizes, sources in sample_generator(files, net.preset.image_size, args.batch_size, with_sources=True):
+            net.infer_dev(x)
+            ticket = net.detect_last_launch(x.shape[0], 0.5, None, 200)                      # detect.py:111-112
+            drawn = net.annotate_last_launch(*sources, style)
+            if pending:
+                collect(pending)
+            pending = (ticket, idxs, drawn)
+        if pending:
+            collect(pending)
+        style.close()
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

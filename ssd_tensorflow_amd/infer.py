@@ -6,8 +6,9 @@ VOC summary files.  Same flags (infer.py:62-89) plus --synthetic / --preset / --
 The loop is pipelined: images are resized on the GPU (the augmentation kernel's cv2.INTER_LINEAR path),
 the net and decode + NMS run on the result where it lies, and the (small) detections of batch k are
 collected after batch k+1 has been launched -- the [b, A, C+5] predictions only come to the host for
---dump-predictions.  Files: anything Pillow decodes, or .npy arrays (uint8 / float32 BGR); cv2 drawing
-(--annotate) is out of scope.
+--dump-predictions.  Files: anything Pillow decodes, or .npy arrays (uint8 / float32 BGR).  --annotate draws the
+detections on the original-size image on the GPU, from the source bytes the resize was fed with and the decode's
+device-visible output (annotate.py), and writes it to <output-dir>/<basename>.
 """
 import argparse
 import os
@@ -20,12 +21,14 @@ from .ssdvgg import SSDVGG, Session
 from .ssdutils import get_preset_by_name, boxes_from_detection
 from .training_data import default_class_names
 from .pascal_summary import PascalSummary
-from .utils import Size, str2bool, load_data_source
+from .utils import Size, str2bool, load_data_source, default_colors
 
 
-def sample_generator(samples, image_size, batch_size, device=0):
+def sample_generator(samples, image_size, batch_size, device=0, with_sources=False):
     """infer.py:44-54: cv2.resize(cv2.imread(file), image_size).astype(float32) per batch -- here a batch of load +
-    INTER_LINEAR resize plans executed by the augmentation kernel; yields (CUDA tensor [b,H,W,3], indices, sizes)."""
+    INTER_LINEAR resize plans executed by the augmentation kernel; yields (CUDA tensor [b,H,W,3], indices, sizes).
+    with_sources: a fourth item (device tensor, byte offsets, [(h, w)]) of the pixels to draw on: the packed original-size
+    uint8 images the resize read, or, for float inputs, the network-size batch itself."""
     from . import transforms as T
     for offset in range(0, len(samples), batch_size):
         files = samples[offset:offset + batch_size]
@@ -45,8 +48,14 @@ def sample_generator(samples, image_size, batch_size, device=0):
         import torch
         dev = torch.device('cuda', device)
         x = torch.empty((len(files), image_size.h, image_size.w, 3), dtype=torch.float32, device=dev)
+        sources = None
+        if with_sources and plans and len(plans) != len(files):
+            raise ValueError('uint8 and float images cannot share an annotated batch')
         if plans:
-            res = T.augment_batch(plans, image_size.w, image_size.h, device=device)
+            res = T.augment_batch(plans, image_size.w, image_size.h, device=device, return_images=with_sources)
+            if with_sources:
+                res, packed, offs = res
+                sources = (packed, offs, [(s.h, s.w) for s in sizes])
             k = 0
             for i, r in enumerate(ready):
                 if r is None:
@@ -54,7 +63,13 @@ def sample_generator(samples, image_size, batch_size, device=0):
         for i, r in enumerate(ready):
             if r is not None:
                 x[i] = torch.from_numpy(r).to(dev)
-        yield x, idxs, sizes
+        if with_sources:
+            if sources is None:
+                n = image_size.h * image_size.w * 12
+                sources = (x, [i * n for i in range(len(files))], [(image_size.h, image_size.w)] * len(files))
+            yield x, idxs, sizes, sources
+        else:
+            yield x, idxs, sizes
 
 
 def resolve_class_names(num_classes, source_names=None, stored=None):
@@ -74,7 +89,7 @@ def main(argv=None):
     parser.add_argument('--checkpoint', type=int, default=-1, help='checkpoint to restore; -1 is the most recent')
     parser.add_argument('--training-data', default='', help='unused: class names come from the data source (VOC defaults)')
     parser.add_argument('--output-dir', default='test-output', help='directory for the resulting predictions')
-    parser.add_argument('--annotate', type=str2bool, default='False', help='out of scope (cv2 drawing)')
+    parser.add_argument('--annotate', type=str2bool, default='False', help='write the images with the detections drawn on them')
     parser.add_argument('--dump-predictions', type=str2bool, default='False', help='Dump raw predictions')
     parser.add_argument('--compute-stats', type=str2bool, default='True', help='Compute the mAP stats')
     parser.add_argument('--data-source', default=None, help='Use test files from the data source')
@@ -99,8 +114,7 @@ def main(argv=None):
     print('[i] Sample:            ', args.sample)
     print('[i] Threshold:         ', args.threshold)
     print('[i] Pascal summary:    ', args.pascal_summary)
-    if args.annotate:
-        print('[!] --annotate needs OpenCV drawing, which this build does not have'); return 1
+    print('[i] Annotate:          ', args.annotate)
 
     # ---- checkpoint lookup (infer.py:111-126) --------------------------------------------------
     ckpt = None
@@ -179,6 +193,13 @@ def main(argv=None):
         print('[i] Number of files:   ', len(files))
         ap_calc = APCalculator() if compute_stats else None
         pascal_summary = PascalSummary() if args.pascal_summary else None                    # infer.py:208-209
+        style = None
+        if args.annotate:                                                                    # infer.py:242-247
+            from .annotate import Style, write_image
+            names = [str(lid2name.get(i, 'class_%d' % i)) for i in range(num_classes)]
+            cmap = dict(getattr(source, 'colors', None) or {}) if source else {}
+            cmap = {**default_colors(names), **cmap}
+            style = Style([cmap[n] for n in names], names, sess.device)
 
         def name_of(i):
             return files[i] if isinstance(files[i], str) else f'{i:06d}.npy'
@@ -187,7 +208,10 @@ def main(argv=None):
 
         def collect(pending):
             nonlocal total
-            ticket, idxs, sizes = pending
+            ticket, idxs, sizes, drawn = pending
+            if drawn is not None:
+                for i, img in enumerate(drawn.get()):
+                    write_image(os.path.join(args.output_dir, os.path.basename(name_of(idxs[i]))), img)
             for i, det in enumerate(ticket.get()):
                 # decode_boxes(enc, anchors, threshold, lid2name, None); suppress_overlaps(boxes)[:200]  (infer.py:233-235)
                 boxes = boxes_from_detection(det, lid2name)
@@ -198,18 +222,22 @@ def main(argv=None):
                     pascal_summary.add_detections(name_of(idxs[i]), boxes, img_size=sizes[i])
 
         pending = None
-        for x, idxs, sizes in sample_generator(files, size, args.batch_size):
+        for batch in sample_generator(files, size, args.batch_size, with_sources=style is not None):
+            x, idxs, sizes = batch[:3]
             net.infer_dev(x)                                                                 # infer.py:225-227
             ticket = net.detect_last_launch(x.shape[0], args.threshold, None, 200)
+            drawn = net.annotate_last_launch(*batch[3], style) if style is not None else None
             if args.dump_predictions:                                                        # infer.py:251-254
                 enc_boxes = net._dev_result(x.shape[0], True)
                 for i in range(x.shape[0]):
                     np.save(os.path.join(args.output_dir, os.path.basename(name_of(idxs[i])) + '.npy'), enc_boxes[i])
             if pending:
                 collect(pending)
-            pending = (ticket, idxs, sizes)
+            pending = (ticket, idxs, sizes, drawn)
         if pending:
             collect(pending)
+        if style is not None:
+            style.close()
 
         if compute_stats:                                                                    # infer.py:269-273
             aps = ap_calc.compute_aps()

@@ -101,6 +101,17 @@ class _Detections:
         return _DetectionList(*views, oc, net=self.net, serial=self.serial)
 
 
+class _Annotated:
+    """Ticket of SSDVGG.annotate_last_launch."""
+    def __init__(self, host, done, offs, shapes):
+        self.host, self.done, self.offs, self.shapes = host, done, offs, shapes
+
+    def get(self):
+        from . import annotate as A
+        self.done.synchronize()
+        return A.unpack(self.host.numpy(), self.offs, self.shapes)
+
+
 class LearningRate:
     """compute_lr's result (train.py:43-47): piecewise-constant values over global_step."""
     def __init__(self, values, boundaries):
@@ -500,6 +511,7 @@ class SSDVGG:
 
     def set_stream(self, stream_ptr):
         check(lib.ssd_set_stream(self._h, stream_ptr))
+        self._stream_ptr = int(stream_ptr or 0)
 
     def _det_caps(self, cap, mo):
         cap = -1 if cap is None else int(cap)
@@ -514,12 +526,39 @@ class SSDVGG:
         ticket whose get() yields what detect_last returns.  Two output slots alternate in the handle, so a
         caller may launch the next batch before it collects this one (infer.py:225-235, pipelined)."""
         cap, mo, out_cap = self._det_caps(detections_cap, max_out)
+        count_dev = C.c_void_p(); cls_dev = C.c_void_p(); box_dev = C.c_void_p()
         check(lib.ssd_detect_last_dev(self._h, b, float(confidence_threshold), cap, mo, out_cap, 1 if nms else 0,
-                                      None, None, None, None, None))
+                                      C.byref(count_dev), None, C.byref(cls_dev), None, C.byref(box_dev)))
         self._det_serial = getattr(self, '_det_serial', 0) + 1
+        self._det_dev = (self._det_serial, count_dev.value, cls_dev.value, box_dev.value, b, out_cap)      # (annotate_last_launch)
         if not hasattr(self, '_det_views'):
             self._det_views = {}
         return _Detections(self, self._det_serial, b, out_cap)
+
+    def annotate_last_launch(self, src, src_offs, src_shapes, style, dst_shapes=None, rgb_out=False):
+        """Enqueue, right behind the decode that detect_last_launch has just launched and on the same stream, the drawing of its
+        detections (annotate.annotate_batch; the boxes are read from the pass's device-visible slot, nothing waits).  src: a
+        torch uint8 or float32 CUDA tensor holding image i as [h][w][3] BGR at byte offset src_offs[i] (src_shapes[i] = (h, w));
+        dst_shapes: other output sizes (float32 sources only: cv2.resize first); fewer images than the pass held: its first ones.  Returns a ticket whose get() yields the
+        uint8 [h, w, 3] images from pinned host memory; collect it with the pass's detections."""
+        import torch
+        from . import annotate as A
+        det = getattr(self, '_det_dev', None)
+        if det is None or det[0] != self._det_serial:
+            raise RuntimeError('annotate_last_launch needs a detect_last_launch right before it')
+        _, count_dev, cls_dev, box_dev, b, out_cap = det
+        if not 1 <= len(src_shapes) <= b:      # (fewer: the first images of the pass)
+            raise ValueError('%d images for a detection pass of %d' % (len(src_shapes), b))
+        ptr = getattr(self, '_stream_ptr', 0)
+        stream = torch.cuda.ExternalStream(ptr, device=src.device) if ptr else torch.cuda.default_stream(src.device)
+        with torch.cuda.stream(stream):
+            dst, offs, shapes = A.annotate_batch(src, src_offs, src_shapes, count_dev, cls_dev, box_dev, out_cap, style,
+                                                 dst_shapes=dst_shapes, rgb_out=rgb_out, stream=ptr or None)
+            host = torch.empty(dst.shape, dtype=dst.dtype, pin_memory=True)
+            host.copy_(dst, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(stream)
+        return _Annotated(host, done, offs, shapes)
 
     def detect_last(self, b, confidence_threshold=0.5, detections_cap=200, max_out=None, nms=True):
         """decode + NMS of the last step's result without leaving the GPU (train.py:275-277)."""

@@ -1,7 +1,8 @@
 """Scalar summaries of the training driver: the counterparts of the reference's LossSummary and
 PrecisionSummary (utils.py:151-199, 236-283) with the same tags, accumulation and per-epoch push --
 written as JSON lines (`{"tag": ..., "value": ..., "step": ...}`) instead of TensorBoard event files
-(there is no TensorFlow here; image summaries are cv2 drawing and stay out)."""
+(there is no TensorFlow here).  ImageSummary (utils.py:201-233) writes its annotated pictures as PNG files next to them; they
+are drawn on the GPU (annotate.py)."""
 import json
 import os
 
@@ -11,6 +12,7 @@ class SummaryWriter:
 
     def __init__(self, logdir):
         os.makedirs(logdir, exist_ok=True)
+        self.logdir = logdir
         self.path = os.path.join(logdir, 'scalars.jsonl')
         self._f = open(self.path, 'a')
 
@@ -64,3 +66,55 @@ class PrecisionSummary:
         for label in self.labels:
             if label in APs:
                 self.writer.add_scalar(self.sample_name + '_AP_' + label, APs[label], epoch)
+
+
+class ImageSummary:
+    """utils.py:201-233 / train.py:273-281, 298-306, 328-329: up to three annotated samples of an epoch, 512 x 512 RGB, written as
+    `<logdir>/<sample_name>_img/e<epoch>_<i>.png`.  The pictures arrive drawn: StepLoop.run_epoch resizes, draws and converts
+    them on the GPU from the batch tensor and the decode's output and collects them here with that batch's detections."""
+    SIZE = 512
+    COUNT = 3
+
+    def __init__(self, writer, sample_name, colors, lid2name):
+        self.writer, self.sample_name = writer, sample_name
+        self.names = [str(lid2name[i]) for i in range(len(lid2name))]
+        from .utils import default_colors
+        cmap = {**default_colors(self.names), **dict(colors or {})}
+        self.colors = [cmap[n] for n in self.names]
+        self.samples = []
+        self._reserved = 0
+        self._style = None
+
+    def style(self, device):
+        if self._style is None:
+            from .annotate import Style
+            self._style = Style(self.colors, self.names, device)
+        return self._style
+
+    def room(self):
+        """how many more pictures this epoch takes"""
+        return self.COUNT - self._reserved
+
+    def reserve(self, k):
+        self._reserved += k
+
+    def add(self, images):
+        self.samples.extend(a.copy() for a in images)
+
+    def push(self, epoch, samples=None):
+        """samples: [h, w, 3] uint8 RGB arrays (default: the ones collected since the last push); nothing is written when empty"""
+        samples = self.samples if samples is None else samples
+        if samples and self.writer is not None:
+            from .annotate import png_bytes
+            d = os.path.join(self.writer.logdir, self.sample_name + '_img')
+            os.makedirs(d, exist_ok=True)
+            for i, img in enumerate(samples):
+                with open(os.path.join(d, 'e%d_%d.png' % (epoch, i)), 'wb') as f:
+                    f.write(png_bytes(img))
+        self.samples = []
+        self._reserved = 0
+
+    def close(self):
+        if self._style is not None:
+            self._style.close()
+            self._style = None

@@ -2,7 +2,7 @@
 """Training driver: the counterpart of the reference's train.py loop (train.py:247-343) over
 the HIP library.  Same flags (train.py:55-80) plus --preset / --synthetic-train / --synthetic-valid /
 --augment / --dtype / --allreduce-bucket-mb / --allreduce-dtype.  Scalar summaries go to <tensorboard-dir>/<name>/scalars.jsonl
-(summaries.py); image summaries and TensorBoard event files are out of scope.
+(summaries.py), the annotated image summaries as PNG files; TensorBoard event files are out of scope.
 
     python -m ssd_tensorflow_amd.train --name run1 --epochs 2 --batch-size 8
     python -m torch.distributed.run --nproc-per-node 8 -m ssd_tensorflow_amd.train ...   # data parallel
@@ -25,7 +25,7 @@ from . import _lib, parallel
 from .average_precision import APCalculator, APs2mAP
 from .ssdutils import boxes_from_detection
 from .ssdvgg import SSDVGG, Session, LearningRate
-from .summaries import SummaryWriter, LossSummary, PrecisionSummary
+from .summaries import SummaryWriter, LossSummary, PrecisionSummary, ImageSummary
 from .training_data import TrainingData
 from .utils import str2bool
 
@@ -67,13 +67,31 @@ class StepLoop:
         if loss_summary is not None:
             loss_summary.add(*self.booked(loss_batch, count))
 
-    def collect(self, dets, gt_boxes, calc):
+    def collect(self, dets, gt_boxes, drawn, calc, image_samples=None):
         if dets is None:
             return
+        if drawn is not None:
+            image_samples.add(drawn.get())
         for gt, det in zip(gt_boxes, dets.get()):
             calc.add_detections(gt, boxes_from_detection(det, self.td.lid2name))
 
-    def run_epoch(self, generator, train, loss_summary, ap_calc, with_ap):
+    def annotate_launch(self, x, n, image_samples):
+        """train.py:273-281, 298-306: the first three samples of the epoch that have a decode, drawn on the GPU behind that
+        decode: cv2.resize(512, 512) -> draw_box per detection -> clamp -> uint8 RGB (summaries.ImageSummary)."""
+        if image_samples is None or self.rank != 0 or image_samples.room() <= 0:
+            return None
+        import torch
+        if not (hasattr(x, 'is_cuda') and x.is_cuda):
+            x = torch.from_numpy(x).to(torch.device('cuda', self.net.device))
+        k = min(image_samples.room(), n)
+        h, w = int(x.shape[1]), int(x.shape[2])
+        size = image_samples.SIZE
+        drawn = self.net.annotate_last_launch(x.contiguous(), [i * h * w * 12 for i in range(k)], [(h, w)] * k, image_samples.style(self.net.device),
+                                              dst_shapes=[(size, size)] * k, rgb_out=True)
+        image_samples.reserve(k)
+        return drawn
+
+    def run_epoch(self, generator, train, loss_summary, ap_calc, with_ap, image_samples=None):
         net, sess, td, world = self.net, self.sess, self.td, self.world
         pending_det = None
         pending_loss = None                     # sample count of the launched step whose losses are not booked yet
@@ -101,13 +119,14 @@ class StepLoop:
                 continue
             # decode + NMS of the batch just computed, on the GPU (train.py:275-277)
             launched = net.detect_last_launch(n, 0.5, 200, None)
+            drawn = self.annotate_launch(x, n, image_samples)
             if pending_det:
-                self.collect(pending_det[0], pending_det[1], ap_calc)
-            pending_det = (launched, gt_boxes)
+                self.collect(*pending_det, ap_calc, image_samples)
+            pending_det = (launched, gt_boxes, drawn)
         if pending_loss is not None:
             self.book(net.get_losses_step(0), pending_loss, loss_summary)
         if pending_det:
-            self.collect(pending_det[0], pending_det[1], ap_calc)
+            self.collect(*pending_det, ap_calc, image_samples)
 
 
 def main(argv=None):
@@ -224,6 +243,8 @@ def main(argv=None):
         validation_ap = PrecisionSummary(writer, 'validation', labels)
         training_loss = LossSummary(writer, 'training', td.num_train)
         validation_loss = LossSummary(writer, 'validation', td.num_valid)
+        training_imgs = ImageSummary(writer, 'training', td.label_colors, td.lid2name) if rank == 0 else None      # train.py:248-249
+        validation_imgs = ImageSummary(writer, 'validation', td.label_colors, td.lid2name) if rank == 0 else None
 
         loop = StepLoop(net, sess, td, args.batch_size, args.num_workers, world, rank, bucket, args.allreduce_dtype)
 
@@ -244,8 +265,8 @@ def main(argv=None):
         say('[i] Training...')
         for e in range(start_epoch, args.epochs):
             td.epoch = e
-            loop.run_epoch(td.train_generator, True, training_loss, training_ap_calc, e > 0)
-            loop.run_epoch(td.valid_generator, False, validation_loss, validation_ap_calc, e > 0)
+            loop.run_epoch(td.train_generator, True, training_loss, training_ap_calc, e > 0, training_imgs)
+            loop.run_epoch(td.valid_generator, False, validation_loss, validation_ap_calc, e > 0, validation_imgs)
             # ---- summaries (train.py:311-331) -----------------------------------------------------
             tl = training_loss.push(e + 1, rank_sum)
             vl = validation_loss.push(e + 1, rank_sum)
@@ -260,6 +281,9 @@ def main(argv=None):
             validation_ap.push(e + 1, vmAP, vAPs)
             if e > 0:
                 say('[i] mAP  {:>2}/{}  training {:.4f}  validation {:.4f}'.format(e + 1, args.epochs, mAP, vmAP))
+            if rank == 0:                                                                       # train.py:328-329
+                training_imgs.push(e + 1)
+                validation_imgs.push(e + 1)
             training_ap_calc.clear(); validation_ap_calc.clear()
             if writer is not None:
                 writer.flush()
@@ -274,6 +298,8 @@ def main(argv=None):
             print('[i] Checkpoint saved:', path)
         if writer is not None:
             writer.close()
+        if rank == 0:
+            training_imgs.close(); validation_imgs.close()
         td.close()
         if os.environ.get('SSD_PRINT_CHECKSUM'):      # replica agreement check of the multi-rank tests
             print('[checksum] rank %d step %d params %.12e' % (rank, net.global_step, float(net.params_flat.double().sum())), flush=True)

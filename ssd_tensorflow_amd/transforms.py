@@ -520,9 +520,10 @@ def plan_params(plans, width, height):
     return arr, packed
 
 
-def augment_batch(plans, width, height, device=0, out=None):
+def augment_batch(plans, width, height, device=0, out=None, return_images=False):
     """Run a batch of ImagePlans on the GPU, on torch's current stream.  Returns a torch float32 tensor
-    [b, height, width, 3] on `device` (what training_data.py:100-104 stacks on the host)."""
+    [b, height, width, 3] on `device` (what training_data.py:100-104 stacks on the host); with return_images also the
+    packed uint8 device tensor of the source images and their byte offsets in it (infer.py draws on them)."""
     import torch
     arr, packed = plan_params(plans, width, height)
     dev = torch.device('cuda', device)
@@ -534,6 +535,8 @@ def augment_batch(plans, width, height, device=0, out=None):
     check(lib.ssd_augment_batch_dev(images.data_ptr(), C.cast(arr, C.c_void_p), b, width, height, out.data_ptr(), ws.data_ptr(),
                                     torch.cuda.current_stream(dev).cuda_stream))
     # the scratch tensors are released in stream order by torch's allocator; the parameter structs were copied by the call
+    if return_images:
+        return out, images, [int(arr[i].src_off) for i in range(b)]
     return out
 
 

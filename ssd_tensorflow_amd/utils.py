@@ -69,3 +69,44 @@ def load_data_source(data_source):
     except ImportError:
         module = importlib.import_module('source_' + data_source)
     return module.get_source()
+
+
+def default_colors(names):
+    """{name: (b, g, r)} for a list of class names no data source colours: the VOC colours for the VOC names
+    (source_pascal_voc), else evenly spaced hues at full saturation, deterministic in the list's order."""
+    import colorsys
+    from .source_pascal_voc import VOC_NAMES, label_defs
+    names = [str(n) for n in names]
+    if names == list(VOC_NAMES):
+        return {l.name: tuple(l.color) for l in label_defs}
+    out = {}
+    for i, n in enumerate(names):
+        r, g, b = colorsys.hsv_to_rgb(i / max(len(names), 1), 1.0, 1.0)
+        out[n] = (int(round(b * 255)), int(round(g * 255)), int(round(r * 255)))
+    return out
+
+
+def draw_box(img, box, color, device=None):
+    """utils.py:138-148: draw one Box on `img` IN PLACE -- a numpy uint8 or float32 [H, W, 3] BGR array -- through the HIP
+    library (annotate.py; the rule is in include/ssdvgg_hip.h).  A float image stays float and is not clamped, like the
+    reference's.  `color`: (b, g, r)."""
+    import numpy as np
+    import torch
+    from . import _lib
+    from . import annotate as A
+    if not isinstance(img, np.ndarray) or img.ndim != 3 or img.shape[2] != 3 or img.dtype not in (np.uint8, np.float32):
+        raise ValueError('draw_box needs a uint8 or float32 [H, W, 3] numpy array')
+    h, w = img.shape[:2]
+    rect = prop2abs(box.center, box.size, Size(w, h))
+    dev = torch.device('cuda', _lib.device() if device is None else int(device))
+    style = A.Style([tuple(int(c) for c in color)], ['' if box.label is None else str(box.label)], dev.index)
+    try:
+        is_f = img.dtype == np.float32
+        src = torch.from_numpy(np.ascontiguousarray(img)).to(dev)
+        count = torch.ones(1, dtype=torch.int32, device=dev)
+        cls = torch.zeros(1, dtype=torch.int32, device=dev)
+        rect_t = torch.tensor([rect], dtype=torch.int32, device=dev)
+        dst, offs, shapes = A.annotate_batch(src, [0], [(h, w)], count, cls, rect_t, 1, style, boxes_on_1000_grid=False, dst_float=is_f)
+        img[...] = A.unpack(dst.cpu().numpy(), offs, shapes)[0]
+    finally:
+        style.close()

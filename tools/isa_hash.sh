@@ -4,7 +4,7 @@
 # usage: tools/isa_hash.sh ssd_tensorflow_amd/csrc > new.txt ; (same on the parent's tree) > old.txt ; diff old.txt new.txt
 src=${1:-ssd_tensorflow_amd/csrc}; tmp=$(mktemp -d)
 for f in "$src"/*.hip; do
-  b=$(basename "$f" .hip); extra=""; case $b in boxes|metrics|augment|planner) extra=-ffp-contract=off;; esac
+  b=$(basename "$f" .hip); extra=""; case $b in boxes|metrics|augment|annotate|planner) extra=-ffp-contract=off;; esac
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $extra --cuda-device-only --no-gpu-bundle-output -c "$f" -o "$tmp/$b.co" &
 done
 wait
