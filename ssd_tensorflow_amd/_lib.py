@@ -66,6 +66,12 @@ SIGNATURES = {
     'ssd_annotate_style_destroy': (i32, [vp]),
     'ssd_annotate_ws_bytes': (sz, [i32, i32]),
     'ssd_annotate_batch_dev': (i32, [vp, i32, vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, i32, vp, vp]),
+    'ssd_jpeg_info': (i32, [vp, sz, p_i32, p_i32, p_i32, p_i32, p_i32]),
+    'ssd_jpeg_coef_bytes': (sz, [vp, sz]),
+    'ssd_jpeg_entropy_decode': (i32, [vp, sz, vp, sz, vp, p_i32]),
+    'ssd_jpeg_entropy_decode_batch': (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
+    'ssd_jpeg_ws_bytes': (sz, [vp, i32]),
+    'ssd_jpeg_decode_batch_dev': (i32, [vp, sz, vp, i32, vp, sz, vp, sz, vp]),
     'ssd_sampler_trials': (i32, [vp, i32, vp, vp, i32, i32, vp, i32, vp, vp]),
     'ssd_create': (i32, [cstr, i32, i32, i32, i32, C.c_ulonglong, vp, vp, vp, C.POINTER(handle)]),
     'ssd_create_dtype': (i32, [cstr, i32, i32, i32, i32, C.c_ulonglong, vp, vp, vp, i32, C.POINTER(handle)]),

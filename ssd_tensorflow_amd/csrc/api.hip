@@ -3,6 +3,7 @@
 #include "net.h"
 #include "augment.h"
 #include "annotate.h"
+#include "jpeg.h"
 #include "metrics.h"
 #include <vector>
 #include <map>
@@ -387,6 +388,62 @@ size_t ssd_arena_floats_graph(const char* preset, int num_classes, int graph) {
         ssd::set_error("%s", e.what());
         return 0;
     }
+}
+
+int ssd_jpeg_info(const unsigned char* bytes, size_t n, int* width, int* height, int* components, int* sampling, int* status) {
+    if (status) *status = SSD_JPEG_ERROR;
+    API_BEGIN
+    SSD_REQUIRE(status != nullptr, "status is null");
+    ssd_jpeg_desc d;
+    const int st = jpeg_parse_header(bytes, n, &d);
+    if (width) *width = d.width;
+    if (height) *height = d.height;
+    if (components) *components = d.components;
+    if (sampling) *sampling = d.hs * 16 + d.vs;
+    *status = st;
+    API_END
+}
+
+size_t ssd_jpeg_coef_bytes(const unsigned char* bytes, size_t n) {
+    try {
+        ssd_jpeg_desc d;
+        return jpeg_parse_header(bytes, n, &d) == SSD_JPEG_OK ? jpeg_coef_bytes(d) : 0;
+    } catch (const std::exception& e) {
+        ssd::set_error("%s", e.what());
+        return 0;
+    }
+}
+
+int ssd_jpeg_entropy_decode(const unsigned char* bytes, size_t n, short* coef_out, size_t coef_cap_bytes, ssd_jpeg_desc* desc,
+                            int* status) {
+    if (status) *status = SSD_JPEG_ERROR;
+    API_BEGIN
+    SSD_REQUIRE(status != nullptr && desc != nullptr, "null argument");
+    *status = jpeg_entropy_decode(bytes, n, coef_out, coef_cap_bytes, desc);
+    API_END
+}
+
+int ssd_jpeg_entropy_decode_batch(const unsigned char* const* files, const size_t* sizes, int n, int threads, short* coef_out,
+                                  const unsigned long long* offsets, ssd_jpeg_desc* descs, int* status_out) {
+    API_BEGIN
+    jpeg_entropy_decode_batch(files, sizes, n, threads, coef_out, offsets, descs, status_out);
+    API_END
+}
+
+size_t ssd_jpeg_ws_bytes(const ssd_jpeg_desc* descs, int n) {
+    try {
+        return jpeg_ws_bytes(descs, n);
+    } catch (const std::exception& e) {
+        ssd::set_error("%s", e.what());
+        return 0;
+    }
+}
+
+int ssd_jpeg_decode_batch_dev(const short* coef_dev, size_t coef_bytes, const ssd_jpeg_desc* descs, int n, unsigned char* dst_dev,
+                              size_t dst_bytes, void* ws_dev, size_t ws_bytes, void* stream) {
+    API_BEGIN
+    jpeg_decode_batch(coef_dev, coef_bytes, descs, n, dst_dev, dst_bytes, ws_dev, ws_bytes, (hipStream_t)stream);
+    API_END
 }
 
 size_t ssd_augment_ws_bytes(int b, int out_w, int out_h) { return augment_ws_bytes(b, out_w, out_h); }

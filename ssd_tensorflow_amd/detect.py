@@ -25,6 +25,8 @@ def main(argv=None):
     parser.add_argument('--output-dir', default='test-out', help='output directory')
     parser.add_argument('--batch-size', type=int, default=32, help='batch size')
     parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='f32, or bf16 activations on the bf16 matrix cores')
+    parser.add_argument('--decoder', default='gpu', choices=['pillow', 'gpu'],
+                        help='gpu: baseline JPEGs are decoded on the GPU, other files as with pillow (same pixels); pillow: every file is decoded on the host')
     args = parser.parse_args(argv)
 
     print('[i] Model:         ', args.model)
@@ -58,7 +60,7 @@ def main(argv=None):
                 write_image(os.path.join(args.output_dir, name), images[i])
 
         pending = None
-        for x, idxs, sizes, sources in sample_generator(files, net.preset.image_size, args.batch_size, with_sources=True):
+        for x, idxs, sizes, sources in sample_generator(files, net.preset.image_size, args.batch_size, with_sources=True, decoder=args.decoder):
             net.infer_dev(x)
             ticket = net.detect_last_launch(x.shape[0], 0.5, None, 200)                      # detect.py:111-112
             drawn = net.annotate_last_launch(*sources, style)

@@ -6,7 +6,8 @@ VOC summary files.  Same flags (infer.py:62-89) plus --synthetic / --preset / --
 The loop is pipelined: images are resized on the GPU (the augmentation kernel's cv2.INTER_LINEAR path),
 the net and decode + NMS run on the result where it lies, and the (small) detections of batch k are
 collected after batch k+1 has been launched -- the [b, A, C+5] predictions only come to the host for
---dump-predictions.  Files: anything Pillow decodes, or .npy arrays (uint8 / float32 BGR).  --annotate draws the
+--dump-predictions.  Files: anything Pillow decodes, or .npy arrays (uint8 / float32 BGR).  --decoder gpu (the default) decodes baseline
+JPEGs on the GPU instead (jpeg.py; same pixels; --decoder pillow: the host decode).  --annotate draws the
 detections on the original-size image on the GPU, from the source bytes the resize was fed with and the decode's
 device-visible output (annotate.py), and writes it to <output-dir>/<basename>.
 """
@@ -24,14 +25,42 @@ from .pascal_summary import PascalSummary
 from .utils import Size, str2bool, load_data_source, default_colors
 
 
-def sample_generator(samples, image_size, batch_size, device=0, with_sources=False):
+def _has_jpeg_candidates(files):
+    """the batch is for jpeg.decode_batch: all items are files, at least one of them is not a .npy array (a batch of arrays
+    alone is packed and uploaded as before), and the arrays among them are uint8"""
+    if not all(isinstance(f, str) for f in files):
+        return False
+    arrays = [f if f.endswith('.npy') else f + '.npy' for f in files if f.endswith('.npy') or os.path.exists(f + '.npy')]
+    return len(arrays) < len(files) and all(np.load(a, mmap_mode='r').dtype == np.uint8 for a in arrays)
+
+
+def sample_generator(samples, image_size, batch_size, device=0, with_sources=False, decoder='pillow'):
     """infer.py:44-54: cv2.resize(cv2.imread(file), image_size).astype(float32) per batch -- here a batch of load +
     INTER_LINEAR resize plans executed by the augmentation kernel; yields (CUDA tensor [b,H,W,3], indices, sizes).
     with_sources: a fourth item (device tensor, byte offsets, [(h, w)]) of the pixels to draw on: the packed original-size
-    uint8 images the resize read, or, for float inputs, the network-size batch itself."""
+    uint8 images the resize read, or, for float inputs, the network-size batch itself.
+    decoder='gpu': a batch of files is decoded by jpeg.decode_batch (baseline JPEGs on the GPU, anything else loaded as before
+    and copied into the same device buffer), the resize plans read that buffer and it is also the buffer to draw on; the pixels
+    never exist on the host.  Batches of arrays alone (--synthetic, .npy files) take the path below either way."""
     from . import transforms as T
     for offset in range(0, len(samples), batch_size):
         files = samples[offset:offset + batch_size]
+        if decoder == 'gpu' and _has_jpeg_candidates(files):
+            from . import jpeg
+            packed, offs, shapes, _ = jpeg.decode_batch(files, device=device)
+            plans = []
+            for i in range(len(files)):
+                plan = T.ImagePlan((packed, offs[i], shapes[i]))
+                plan.resize = (image_size.w, image_size.h, T.INTER_LINEAR)
+                plans.append(plan)
+            x = T.augment_batch(plans, image_size.w, image_size.h, device=device)
+            idxs = list(range(offset, offset + len(files)))
+            sizes = [Size(w, h) for h, w in shapes]
+            if with_sources:
+                yield x, idxs, sizes, (packed, offs, shapes)
+            else:
+                yield x, idxs, sizes
+            continue
         plans, idxs, sizes, ready = [], [], [], []
         for i, f in enumerate(files):
             img = f if isinstance(f, np.ndarray) else T.load_image_bgr(f)
@@ -103,6 +132,8 @@ def main(argv=None):
     parser.add_argument('--num-classes', type=int, default=20, help='class count when no checkpoint is given (1..127)')
     parser.add_argument('--a-trous', type=str2bool, default='True', help='graph when no checkpoint is given: a-trous (true) or fc (false); a checkpoint carries its own')
     parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='f32, or bf16 activations on the bf16 matrix cores')
+    parser.add_argument('--decoder', default='gpu', choices=['pillow', 'gpu'],
+                        help='gpu: baseline JPEGs are decoded on the GPU, other files as with pillow (same pixels); pillow: every file is decoded on the host')
     args = parser.parse_args(argv)
 
     print('[i] Project name:      ', args.name)
@@ -222,7 +253,7 @@ def main(argv=None):
                     pascal_summary.add_detections(name_of(idxs[i]), boxes, img_size=sizes[i])
 
         pending = None
-        for batch in sample_generator(files, size, args.batch_size, with_sources=style is not None):
+        for batch in sample_generator(files, size, args.batch_size, with_sources=style is not None, decoder=args.decoder):
             x, idxs, sizes = batch[:3]
             net.infer_dev(x)                                                                 # infer.py:225-227
             ticket = net.detect_last_launch(x.shape[0], args.threshold, None, 200)

@@ -52,11 +52,24 @@ class ImagePlan:
     """Stands in for the ndarray `data` of the reference between loading and the batch kernel."""
 
     def __init__(self, image):
-        image = np.ascontiguousarray(image)
-        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
-            raise ValueError('ImagePlan needs a uint8 [H, W, 3] BGR image, got %s %s' % (image.dtype, image.shape))
-        self.image = image
-        self.src = Size(image.shape[1], image.shape[0])
+        """image: a uint8 [H, W, 3] BGR host array, or pixels that already lie on the GPU as a triple (uint8 device tensor, byte
+        offset of the [H][W][3] BGR image in it, (H, W)) -- what jpeg.decode_batch returns; augment_batch then uploads nothing."""
+        self.device_src = None
+        if isinstance(image, tuple):
+            buf, off, (h, w) = image
+            if str(buf.dtype) != 'torch.uint8' or not buf.is_cuda or not buf.is_contiguous():
+                raise ValueError('a device source needs a contiguous uint8 CUDA tensor')
+            if h < 1 or w < 1 or off < 0 or off + h * w * 3 > buf.numel():
+                raise ValueError('a %d x %d image at offset %d does not fit the %d-byte device buffer' % (w, h, off, buf.numel()))
+            self.image = None
+            self.device_src = (buf, int(off))
+            self.src = Size(int(w), int(h))
+        else:
+            image = np.ascontiguousarray(image)
+            if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+                raise ValueError('ImagePlan needs a uint8 [H, W, 3] BGR image, got %s %s' % (image.dtype, image.shape))
+            self.image = image
+            self.src = Size(image.shape[1], image.shape[0])
         self.brightness = None
         self.distort = []              # [(kind, value)] kind: 0 contrast, 1 saturation, 2 hue
         self.reorder = [0, 1, 2]
@@ -137,7 +150,10 @@ class Transform:
 
 def load_image_bgr(filename):
     """cv2.imread(filename) without OpenCV: a .npy file holds the uint8 BGR array itself; anything else is
-    decoded by Pillow (RGB -> BGR).  Decoder parity with OpenCV is unpinned (no cv2 in the build container)."""
+    decoded by Pillow (RGB -> BGR).  Decoder parity with OpenCV: pinned for baseline / extended-sequential Huffman JPEGs,
+    greyscale or YCbCr at 4:4:4, 4:2:2 or 4:2:0 -- cv2.imread and Pillow both run libjpeg-turbo's default integer path there, and
+    tests/golden/j1_jpeg.npz holds its pixels (jpeg.py decodes the same class on the GPU, byte for byte).  Progressive or CMYK
+    JPEGs, EXIF orientation (ignored here, as Pillow does) and every other format remain unpinned (no cv2 in the build container)."""
     if filename.endswith('.npy'):
         return np.load(filename)
     if os.path.exists(filename + '.npy'):
@@ -473,13 +489,20 @@ def _step_val(kind, val):
 
 
 def plan_params(plans, width, height):
-    """(ctypes array of ssd_augment_params, packed uint8 image bytes) for a list of ImagePlans"""
+    """(ctypes array of ssd_augment_params, packed uint8 image bytes) for a list of ImagePlans.  Plans whose pixels are device
+    sources must all lie in one device buffer: src_off is their offset in it and the packed array is None."""
     arr = (_Params * len(plans))()
-    offs, off = [], 0
-    for p in plans:
-        offs.append(off)
-        off += (p.image.size + 15) // 16 * 16
-    packed = np.empty(off, np.uint8)
+    on_device = [getattr(p, 'device_src', None) is not None for p in plans]
+    if any(on_device):
+        if not all(on_device) or any(p.device_src[0] is not plans[0].device_src[0] for p in plans):
+            raise ValueError('the plans of a batch must be all host arrays or all sources in ONE device buffer')
+        offs, packed = [p.device_src[1] for p in plans], None
+    else:
+        offs, off = [], 0
+        for p in plans:
+            offs.append(off)
+            off += (p.image.size + 15) // 16 * 16
+        packed = np.empty(off, np.uint8)
     for i, p in enumerate(plans):
         if p.resize is None:
             raise ValueError('plan %d was not resized: the batch needs one output size (ResizeTransform last)' % i)
@@ -514,20 +537,25 @@ def plan_params(plans, width, height):
             q.post_kind[k] = kind
             q.post_val[k] = _step_val(kind, val)
         q.out_flip = int(p.out_flip)
-        n = p.image.size
-        packed[offs[i]:offs[i] + n] = p.image.reshape(-1)
-        packed[offs[i] + n:offs[i] + (n + 15) // 16 * 16] = 0
+        if packed is not None:
+            n = p.image.size
+            packed[offs[i]:offs[i] + n] = p.image.reshape(-1)
+            packed[offs[i] + n:offs[i] + (n + 15) // 16 * 16] = 0
     return arr, packed
 
 
 def augment_batch(plans, width, height, device=0, out=None, return_images=False):
     """Run a batch of ImagePlans on the GPU, on torch's current stream.  Returns a torch float32 tensor
     [b, height, width, 3] on `device` (what training_data.py:100-104 stacks on the host); with return_images also the
-    packed uint8 device tensor of the source images and their byte offsets in it (infer.py draws on them)."""
+    packed uint8 device tensor of the source images and their byte offsets in it (infer.py draws on them).  Plans built on device
+    sources (ImagePlan((buffer, offset, (h, w))), jpeg.decode_batch) read that buffer where it lies: nothing is uploaded but the
+    parameter structs."""
     import torch
     arr, packed = plan_params(plans, width, height)
     dev = torch.device('cuda', device)
-    images = torch.from_numpy(packed).to(dev)
+    images = torch.from_numpy(packed).to(dev) if packed is not None else plans[0].device_src[0]
+    if images.device != dev:
+        raise ValueError('the device sources lie on %s, the batch runs on %s' % (images.device, dev))
     b = len(plans)
     if out is None:
         out = torch.empty((b, height, width, 3), dtype=torch.float32, device=dev)
