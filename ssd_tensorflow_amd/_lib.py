@@ -160,6 +160,9 @@ SIGNATURES = {
     'ssd_op_l2norm_fwd': (i32, [vp, vp, vp, i32, i32, vp]),
     'ssd_op_l2norm_bwd_ws_floats': (sz, [i32, i32]),
     'ssd_op_l2norm_bwd': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    'ssd_op_multibox_loss_ws_bytes': (sz, [i32, p_i32, p_i32, i32, C.POINTER(sz), p_i32]),
+    'ssd_op_multibox_loss': (i32, [i32, p_i32, p_i32, i32, C.POINTER(vp), vp, vp, vp, i32, i32, i32, f32, vp, sz, f32, vp]),
+    'ssd_op_multibox_loss_grad': (i32, [i32, p_i32, p_i32, i32, C.POINTER(vp), i32, vp, vp, vp, i32, i32, i32, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

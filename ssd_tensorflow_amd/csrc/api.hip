@@ -1175,4 +1175,60 @@ int ssd_op_l2norm_bwd(const float* x, const float* scale, const float* dy, float
     API_END
 }
 
+// the multibox loss on a caller-given head layout: the step's own launchers (ops.h) on the caller's buffers
+static HeadLayout loss_op_layout(int nmaps, const int* hw, const int* nj, int num_classes, int b, int b_off, int b_total) {
+    SSD_REQUIRE(hw && nj, "null layout");
+    SSD_REQUIRE(num_classes >= 1 && num_classes <= MAX_CLASSES, "num_classes must be 1..%d", MAX_CLASSES);
+    SSD_REQUIRE(b >= 1 && b_off >= 0 && b_off + b <= b_total, "samples %d..%d of %d", b_off, b_off + b, b_total);
+    return head_layout(nmaps, hw, nj, num_classes + 5);
+}
+size_t ssd_op_multibox_loss_ws_bytes(int nmaps, const int* hw, const int* nj, int b_total, size_t* offsets, int* num_anchors) {
+    try {
+        const HeadLayout L = loss_op_layout(nmaps, hw, nj, 1, 1, 0, b_total);      // the workspace does not depend on the class count
+        if (num_anchors) *num_anchors = L.A;
+        if (offsets) {
+            alignas(16) static char base;          // never dereferenced: the carve is pointer arithmetic only
+            LossWork w;
+            loss_work_carve(w, &base, b_total, L.A);
+            const void* parts[6] = {w.ce, w.sl1, w.pos, w.sel, w.sample, w.losses};
+            for (int i = 0; i < 6; ++i) offsets[i] = (size_t)((uintptr_t)parts[i] - (uintptr_t)&base);
+        }
+        return loss_work_bytes(b_total, L.A);
+    } catch (const std::exception& e) {
+        ssd::set_error("%s", e.what());
+        return 0;
+    }
+}
+int ssd_op_multibox_loss(int nmaps, const int* hw, const int* nj, int num_classes, void* const* heads, const float* labels,
+                         float* result, void* ws, int b, int b_off, int b_total, float bnorm, const float* filters,
+                         size_t nfilters, float weight_decay, void* stream) {
+    API_BEGIN
+    HeadLayout L = loss_op_layout(nmaps, hw, nj, num_classes, b, b_off, b_total);
+    SSD_REQUIRE(heads && labels && result && ws, "null buffer");
+    for (int i = 0; i < nmaps; ++i) {
+        SSD_REQUIRE(heads[i], "null head buffer %d", i);
+        L.buf[i] = static_cast<float*>(heads[i]);
+    }
+    LossWork w;
+    loss_work_carve(w, ws, b_total, L.A);
+    if (filters) l2_partials(filters, nfilters, w, (hipStream_t)stream);
+    multibox_loss(L, b, b_off, b_total, result, labels, w, weight_decay, bnorm, (hipStream_t)stream);
+    API_END
+}
+int ssd_op_multibox_loss_grad(int nmaps, const int* hw, const int* nj, int num_classes, void* const* grads, int grads_bf16,
+                              const float* labels, const float* result, void* ws, int b, int b_off, int b_total, void* stream) {
+    API_BEGIN
+    HeadLayout L = loss_op_layout(nmaps, hw, nj, num_classes, b, b_off, b_total);
+    SSD_REQUIRE(grads && labels && result && ws, "null buffer");
+    for (int i = 0; i < nmaps; ++i) {
+        SSD_REQUIRE(grads[i], "null gradient buffer %d", i);
+        L.dbuf[i] = grads[i];
+    }
+    L.grad_bf16 = grads_bf16 ? 1 : 0;
+    LossWork w;
+    loss_work_carve(w, ws, b_total, L.A);
+    multibox_loss_grad(L, b, b_off, result, labels, w, (hipStream_t)stream);
+    API_END
+}
+
 }  // extern "C"

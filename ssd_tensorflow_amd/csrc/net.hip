@@ -10,9 +10,6 @@ namespace ssd {
 
 static bool first_layer_kernel(const ConvDesc& d) { return d.Ci * d.KH * d.KW <= 32 && d.Co == 64; }
 
-// fused head width: a multiple of 8 channels = whole 16-byte pieces in fp32 and in bf16 rows
-static int round8(int n) { return (n + 7) / 8 * 8; }
-
 // ---------------------------------------------------------------------------------
 // graph (ssdvgg.py:190-372)
 // ---------------------------------------------------------------------------------
@@ -117,20 +114,18 @@ void Net::build_graph() {
         fmaps[0] = op.out;
     }
     SSD_REQUIRE((int)fmaps.size() == p.nmaps, "feature map count mismatch");
-    heads_ = HeadLayout{};
-    heads_.nmaps = p.nmaps; heads_.A = p.num_anchors; heads_.nvars = nv;
+    {
+        int hw[MAX_MAPS];
+        for (int i = 0; i < p.nmaps; ++i) hw[i] = p.map_size[i] * p.map_size[i];
+        heads_ = head_layout(p.nmaps, hw, p.ntypes, nv);
+    }
+    SSD_REQUIRE(heads_.A == p.num_anchors, "head layout has %d anchors, preset says %d", heads_.A, p.num_anchors);
     for (int i = 0; i < p.nmaps; ++i) {
         SSD_REQUIRE(tensors_[fmaps[i]].H == p.map_size[i], "feature map %d is %d, preset says %d", i, tensors_[fmaps[i]].H,
                     p.map_size[i]);
-        const int co = round8(p.ntypes[i] * nv);
-        const int t = conv("heads/map" + std::to_string(i), co, 3, 1, PAD_SAME, 1, false, i, fmaps[i]);
-        head_t_.push_back(t);
-        heads_.hw[i] = p.map_size[i] * p.map_size[i];
-        heads_.nj[i] = p.ntypes[i];
-        heads_.ld[i] = co;
-        heads_.off[i] = p.off[i];
+        SSD_REQUIRE(heads_.off[i] == p.off[i], "head layout: map %d starts at anchor %d, preset says %d", i, heads_.off[i], p.off[i]);
+        head_t_.push_back(conv("heads/map" + std::to_string(i), heads_.ld[i], 3, 1, PAD_SAME, 1, false, i, fmaps[i]));
     }
-    heads_.off[p.nmaps] = p.off[p.nmaps];
     heads_.grad_bf16 = bf16_ ? 1 : 0;
     if (bf16_) {
         for (size_t i = 0; i < tensors_.size(); ++i) tensors_[i].data_f32 = tensors_[i].grad_f32 = false;
@@ -609,7 +604,7 @@ size_t Net::arena_floats(const char* preset, int num_classes, int graph) {
     cv(1, 256, 128); cv(3, 128, 256);
     if (p.nmaps >= 7) { cv(1, 256, 128); cv(3, 128, 256); }
     const int fch[] = {512, c7, 512, 256, 256, 256, 256};
-    for (int i = 0; i < p.nmaps; ++i) cv(3, fch[i], round8(p.ntypes[i] * nv));
+    for (int i = 0; i < p.nmaps; ++i) cv(3, fch[i], head_ld(p.ntypes[i], nv));
     return n + 512;
 }
 

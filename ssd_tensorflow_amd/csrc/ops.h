@@ -62,6 +62,11 @@ struct HeadLayout {
     void* dbuf[MAX_MAPS];            // same shape, gradients: fp32, or bf16 when grad_bf16
     int grad_bf16;
 };
+// row stride of a map's fused head buffer: its nj box types' nvars values, rounded up to 8 channels (whole 16-byte
+// pieces in fp32 and in bf16 rows)
+inline int head_ld(int nj, int nvars) { return (nj * nvars + 7) / 8 * 8; }
+// the layout of nmaps maps of hw[i] cells and nj[i] box types: ld, off[] and A filled in, buffers null, fp32 gradients
+HeadLayout head_layout(int nmaps, const int* hw, const int* nj, int nvars);
 // result[b][a][:] = (softmax(logits), loc) in the reference's anchor order
 // (map -> box type -> row -> col, ssdvgg.py:63,365 == ssdutils.py:104-116).
 void heads_result(const HeadLayout& L, int B, float* result, hipStream_t s);

@@ -849,6 +849,23 @@ struct HeadGrid {
 static size_t heads_lds_floats(int hch, int ldp_max, int nj_max, int nv) {
     return (size_t)hch * ldp_max + (size_t)nj_max * hch * nv;
 }
+HeadLayout head_layout(int nmaps, const int* hw, const int* nj, int nvars) {
+    SSD_REQUIRE(nmaps >= 1 && nmaps <= MAX_MAPS, "heads: 1..%d feature maps", MAX_MAPS);
+    HeadLayout L{};
+    L.nmaps = nmaps; L.nvars = nvars;
+    int off = 0;
+    for (int i = 0; i < nmaps; ++i) {
+        SSD_REQUIRE(hw[i] >= 1 && nj[i] >= 1, "heads: map %d has no anchors", i);
+        L.hw[i] = hw[i];
+        L.nj[i] = nj[i];
+        L.ld[i] = head_ld(nj[i], nvars);
+        L.off[i] = off;
+        off += nj[i] * hw[i];
+    }
+    L.off[nmaps] = L.A = off;
+    return L;
+}
+
 static HeadGrid head_grid(const HeadLayout& L, int B) {
     HeadGrid g{};
     for (int i = 0; i < L.nmaps; ++i) {
