@@ -1005,7 +1005,8 @@ int ssd_op_conv2d_wino_fwd(const float* x, const float* w, const float* bias, fl
         HIP_OK(hipMemsetAsync(k.Uf, 0, (size_t)36 * d.Ci * wino_kpad(d.Co) * sizeof(float), (hipStream_t)stream));      // the pad rows
         wino_filter(d, w, k.U, k.Uf, (hipStream_t)stream);
     }
-    wino_fwd(d, x, k.U, bias, y, relu != 0, k.V, (size_t)wino_tiles(d) * d.Ci, k.Mx, y_pool, rec, (hipStream_t)stream, relu_bits);
+    wino_fwd(d, x, k.U, bias, y, relu != 0, k.V, (size_t)wino_tiles(d) * d.Ci, k.Mx, y_pool, rec, (hipStream_t)stream, relu_bits,
+             (flags & 4) != 0);
     API_END
 }
 int ssd_op_conv2d_wino_dgrad(const float* dy, const float* w, float* dx, const float* mask, const void* mask_bits, int accumulate,
@@ -1020,7 +1021,7 @@ int ssd_op_conv2d_wino_dgrad(const float* dy, const float* w, float* dx, const f
         wino_filter(d, w, k.U, k.Uf, (hipStream_t)stream);
     }
     wino_bwd_transform(d, dy, k.Yt, nullptr, (hipStream_t)stream);
-    wino_dgrad(d, k.Yt, k.Uf, dx, mask, accumulate != 0, k.Mx, rec, uh, uw, (hipStream_t)stream, mask_bits);
+    wino_dgrad(d, k.Yt, k.Uf, dx, mask, accumulate != 0, k.Mx, rec, uh, uw, (hipStream_t)stream, mask_bits, (flags & 4) != 0);
     API_END
 }
 int ssd_op_conv2d_wino_wgrad(const float* x, const float* dy, float* dw, float* dbias, const float* w, float weight_decay, float* ws,

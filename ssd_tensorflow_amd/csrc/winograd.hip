@@ -8,7 +8,8 @@
 //
 //   forward        V = B^T d B  per 6x6 input tile            [36][T][Ci]     (wino_in_kernel; kept for the weight gradient)
 //                  M_p = V_p . U_p,  U = G g G^T               36 GEMMs [T x Ci] . [Ci x Co]  (wino_gemm_nn_kernel, one launch)
-//                  y = A^T M A + bias, relu                    (wino_out_kernel)
+//                  y = A^T M A + bias, relu                    (wino_out_kernel; conv1_2 / conv2_1: GEMMs and this step are one
+//                                                               kernel that keeps M in registers, wino_gemm_out_kernel)
 //   data gradient  the same three steps on dy with U' = G rot180(g)^T G^T ([36][Co][Ci]), masked by the producer's relu
 //   weight grad.   dU_p = V_p^T . (A dy A^T)_p                 36 GEMMs [Ci x T] . [T x Co], split over T into slabs (wino_gemm_tn_kernel)
 //                  dg = G^T (sum of slabs, fixed order) G + weight_decay g;  dbias = column sums of dy = a weighted sum of the
@@ -57,9 +58,9 @@ __device__ __forceinline__ void a6(const f32x4 e0, const f32x4 e1, const f32x4 e
     u[5] = e3;
 }
 // A^T (4x6) applied to a 6-vector: the output transform
-__device__ __forceinline__ void at4(const f32x4 m0, const f32x4 m1, const f32x4 m2, const f32x4 m3, const f32x4 m4, const f32x4 m5,
-                                    f32x4* y) {
-    const f32x4 s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
+template <class V>
+__device__ __forceinline__ void at4(const V m0, const V m1, const V m2, const V m3, const V m4, const V m5, V* y) {
+    const V s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
     y[0] = m0 + s12 + s34;
     y[1] = 0.75f * d12 + 1.5f * d34;
     y[2] = 0.5625f * s12 + 2.25f * s34;
@@ -170,46 +171,52 @@ struct WinoOutArgs {
     int UH, UW;                        // MODE 3: un-pooled size
 };
 
+// The transform's three steps as device functions: wino_out_kernel runs them on 4 channels of one tile read back from M, the fused
+// kernel (wino_gemm_out_kernel) on its own accumulators, whose lanes hold 4 channels of one tile too -- one piece of arithmetic in one
+// order, so both give the same bits.
+// o = A^T M A, M's value at position (r, s) from m(r, s): columns first
+template <class F>
+__device__ __forceinline__ void wino_out_transform(F m, f32x4 (&o)[4][4]) {
+    typedef f32x4 V;
+    V c[4][6];
+#pragma unroll
+    for (int s = 0; s < 6; ++s) {
+        V mm[6];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) mm[r] = m(r, s);
+        V y[4];
+        at4(mm[0], mm[1], mm[2], mm[3], mm[4], mm[5], y);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) c[r][s] = y[r];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) at4(c[r][0], c[r][1], c[r][2], c[r][3], c[r][4], c[r][5], o[r]);
+}
+
+// MODE 0 / 2: + bias, relu
+__device__ __forceinline__ void wino_out_bias_relu(f32x4 (&o)[4][4], const f32x4 bv, int relu) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            f32x4 v = o[r][s] + bv;
+            if (relu) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+            }
+            o[r][s] = v;
+        }
+}
+
+// The finished 4x4 pixels of tile t, channels 4 q ... 4 q + 3, to where MODE sends them.
 template <int MODE>
-__global__ __launch_bounds__(256) void wino_out_kernel(WinoOutArgs p) {
-    const int c4n = p.N >> 2;
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    const int q = idx % c4n, t = idx / c4n;
-    if (t >= p.T) return;
+__device__ __forceinline__ void wino_out_store(const WinoOutArgs& p, int t, int q, f32x4 (&o)[4][4]) {
+    typedef f32x4 V;
+    const int c4n = p.N >> 2, ch = q * 4;
     const int j = t % p.tw, t2 = t / p.tw;
     const int i = t2 % p.th, b = t2 / p.th;
     const int D = (MODE == 0 || MODE == 1) ? p.D : 1;
     const int hb = (i % D) + D * 4 * (i / D), wb = (j % D) + D * 4 * (j / D);      // (wino_in_kernel)
-    const float* src = p.M + (size_t)t * p.N + q * 4;
-    f32x4 c[4][6];
-#pragma unroll
-    for (int s = 0; s < 6; ++s) {
-        f32x4 m[6];
-#pragma unroll
-        for (int r = 0; r < 6; ++r) m[r] = *reinterpret_cast<const f32x4*>(src + (size_t)(r * 6 + s) * p.m_ps);
-        f32x4 y[4];
-        at4(m[0], m[1], m[2], m[3], m[4], m[5], y);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) c[r][s] = y[r];
-    }
-    f32x4 o[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) at4(c[r][0], c[r][1], c[r][2], c[r][3], c[r][4], c[r][5], o[r]);
-
-    if constexpr (MODE == 0 || MODE == 2) {
-        const f32x4 bv = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + q * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                f32x4 v = o[r][s] + bv;
-                if (p.relu) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
-                }
-                o[r][s] = v;
-            }
-    }
     if constexpr (MODE == 0) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -218,7 +225,7 @@ __global__ __launch_bounds__(256) void wino_out_kernel(WinoOutArgs p) {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 const int w = wb + D * s;
-                if (w < p.W) *reinterpret_cast<f32x4*>(p.y + ((size_t)(b * p.H + h) * p.W + w) * p.N + q * 4) = o[r][s];
+                if (w < p.W) *reinterpret_cast<V*>(p.y + ((size_t)(b * p.H + h) * p.W + w) * p.N + ch) = o[r][s];
             }
         }
     } else if constexpr (MODE == 1) {
@@ -231,19 +238,19 @@ __global__ __launch_bounds__(256) void wino_out_kernel(WinoOutArgs p) {
             for (int s = 0; s < 4; ++s) {
                 const int w = wb + D * s;
                 if (w >= p.W) continue;
-                const size_t e0 = ((size_t)(b * p.H + h) * p.W + w) * p.N + q * 4;
-                f32x4 v = o[r][s];
-                if (p.accum) v += *reinterpret_cast<const f32x4*>(p.y + e0);
+                const size_t e0 = ((size_t)(b * p.H + h) * p.W + w) * p.N + ch;
+                V v = o[r][s];
+                if (p.accum) v += *reinterpret_cast<const V*>(p.y + e0);
                 if (p.mask_bits) {
                     const unsigned mb = (unsigned)(mbits >> ((r * 4 + s) * 4)) & 15u;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = (mb >> e) & 1u ? v[e] : 0.f;
                 } else if (p.mask) {
-                    const f32x4 mk = *reinterpret_cast<const f32x4*>(p.mask + e0);
+                    const V mk = *reinterpret_cast<const V*>(p.mask + e0);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = mk[e] > 0.f ? v[e] : 0.f;
                 }
-                *reinterpret_cast<f32x4*>(p.y + e0) = v;
+                *reinterpret_cast<V*>(p.y + e0) = v;
             }
         }
     } else if constexpr (MODE == 2) {
@@ -261,7 +268,7 @@ __global__ __launch_bounds__(256) void wino_out_kernel(WinoOutArgs p) {
                 if (pw >= p.PW) continue;
                 const bool okw = 4 * j + 2 * wc + 1 < p.W;
                 const bool ok[4] = {true, okw, okh, okw && okh};
-                f32x4 mm = o[2 * wr][2 * wc];
+                V mm = o[2 * wr][2 * wc];
                 unsigned rec = 0;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -276,7 +283,7 @@ __global__ __launch_bounds__(256) void wino_out_kernel(WinoOutArgs p) {
                     rec |= (a | (best > 0.f ? 4u : 0u)) << (3 * e);
                 }
                 const size_t pix = (size_t)(b * p.PH + ph) * p.PW + pw;
-                *reinterpret_cast<f32x4*>(p.y + pix * p.N + q * 4) = mm;
+                *reinterpret_cast<V*>(p.y + pix * p.N + ch) = mm;
                 if (p.pool_rec) p.pool_rec[pix * c4n + q] = (unsigned short)rec;
             }
         }
@@ -294,17 +301,31 @@ __global__ __launch_bounds__(256) void wino_out_kernel(WinoOutArgs p) {
                 for (int cq = 0; cq < 4; ++cq) {
                     const int uh = 2 * h + (cq >> 1), uw = 2 * w + (cq & 1);
                     if (uh >= p.UH || uw >= p.UW) continue;
-                    f32x4 v;
+                    V v;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const unsigned re = (rec >> (3 * e)) & 7u;
                         v[e] = ((re & 3u) == (unsigned)cq && (re & 4u)) ? o[r][s][e] : 0.f;
                     }
-                    *reinterpret_cast<f32x4*>(p.y + ((size_t)(b * p.UH + uh) * p.UW + uw) * p.N + q * 4) = v;
+                    *reinterpret_cast<V*>(p.y + ((size_t)(b * p.UH + uh) * p.UW + uw) * p.N + ch) = v;
                 }
             }
         }
     }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void wino_out_kernel(WinoOutArgs p) {
+    const int c4n = p.N >> 2;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const int q = idx % c4n, t = idx / c4n;
+    if (t >= p.T) return;
+    const float* src = p.M + (size_t)t * p.N + q * 4;
+    f32x4 o[4][4];
+    wino_out_transform([&](int r, int s) { return *reinterpret_cast<const f32x4*>(src + (size_t)(r * 6 + s) * p.m_ps); }, o);
+    if constexpr (MODE == 0 || MODE == 2)
+        wino_out_bias_relu(o, p.bias ? *reinterpret_cast<const f32x4*>(p.bias + q * 4) : f32x4{0.f, 0.f, 0.f, 0.f}, p.relu);
+    wino_out_store<MODE>(p, t, q, o);
 }
 
 // ---- filter transforms ------------------------------------------------------------------------------------------------------------
@@ -471,6 +492,135 @@ __global__ __launch_bounds__(256) void wino_gemm_nn_kernel(WinoGemmArgs p) {
                 if (m < p.M) Cp[(size_t)m * p.N + n] = acc[mi][ni][r];
             }
         }
+}
+
+// ---- GEMM + output transform in one kernel: M never goes to memory -----------------------------------------------------------------
+// For the layers whose GEMMs are short in k and narrow in n (conv1_2, conv2_1: 16 FLOP per byte of M), writing M and reading it back
+// is most of the pass's HBM traffic.  Here a 512-thread workgroup owns 32 tiles x 64 channels at ALL 36 positions: wave w = (tile
+// block w >> 2, channel block w & 3) keeps a 16 x 16 block of every position in accumulators (v_mfma_f32_16x16x4_f32: 36 x 4 = 144
+// registers).  The MFMA's rows are CHANNELS and its columns tiles (U is its first operand), so a lane of every accumulator holds
+// tile lane % 16 and channels 4 (lane / 16) ... + 3: what a thread of wino_out_kernel holds, at all 36 positions.  A^T M A and the
+// stores are that kernel's device functions on registers: no LDS round trip, no barrier.
+// The loop is one DMA-staged pipeline over (position, 64 k): a stage is V's 32 x 64 block as two 32-k halves in wino_gemm_nn_kernel's
+// swizzled 128-byte rows (one ds_read_b128 per 8 k: a lane takes two of its four values) and U's 64 x 64 block k-major with the
+// 16-byte chunks of row k swizzled by k & 4 (the ds_read_b32 of k and k + 4 by the two halves of a 32-lane group hit different
+// banks).  Four stages of 24 KB: three are in flight behind the one computed.  The operands of the next 32 k are read into registers
+// while the MFMAs of the current 32 run, across the stage's barrier too, so the matrix pipe has work while a wave waits.
+// k order: wino_gemm_nn_kernel's chain visits k = 8 g + {0, 4, 1, 5, 2, 6, 3, 7} (32x32x2: lane half = k + 4); the four k slots of a
+// 16x16x4 instruction (lane / 16) are fed {0, 4, 1, 5} then {2, 6, 3, 7}, so every sum is the same fmaf chain: the same bits.
+struct WinoFusedArgs {
+    const float* A;
+    const float* Bm;
+    int M, N, K;                  // N a multiple of 64, K = 64 or 128
+    size_t a_ps, b_ps;
+    int NT;
+    WinoOutArgs out;              // (M / m_ps unused)
+};
+
+template <int MODE, int KS>      // KS = K / 64 stages per position: the loop is straight-line code, every LDS address an immediate
+__global__ __launch_bounds__(512) void wino_gemm_out_kernel(WinoFusedArgs p) {
+    constexpr int NS = 4, total = 36 * KS, A_BYTES = 32 * 64 * 4, B_BYTES = 64 * 64 * 4, STAGE = A_BYTES + B_BYTES;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    unsigned char* const lds = reinterpret_cast<unsigned char*>(smem);
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int wg = xcd_remap(blockIdx.x, gridDim.x);
+    const int nt = wg % p.NT, mt = wg / p.NT;
+    const int m0 = mt * 32, n0 = nt * 64;
+
+    // staging: A half (tid >> 8), row (tid & 255) >> 3, chunk tid & 7; B rows 4 (8 j + wave) ... + 3, chunk lane & 15
+    const int ar = (tid & 255) >> 3;
+    const unsigned a_off = m0 + ar < p.M ? (unsigned)((m0 + ar) * p.K + (tid >> 8) * 32 + (((tid & 7) ^ ((ar >> 1) & 7)) * 4)) * 4u : WOOB;
+    unsigned b_off[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int k = (j * 8 + wave) * 4 + (lane >> 4);
+        b_off[j] = (unsigned)(k * p.N + n0 + (((lane & 15) ^ ((wave & 1) * 4)) * 4)) * 4u;
+    }
+    const unsigned a_bytes = (unsigned)((size_t)p.M * p.K * 4u), b_bytes = (unsigned)((size_t)p.K * p.N * 4u);
+    auto issue = [&](int st) {
+        const int pos = st / KS, kh = st % KS;
+        const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.A + (size_t)pos * p.a_ps), 0, a_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t b_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.Bm + (size_t)pos * p.b_ps), 0, b_bytes, 0x00020000);
+        unsigned char* S = lds + (st & (NS - 1)) * STAGE + wave * 1024;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(a_rs, LDS_PTR(S), 16, (int)a_off, kh * 256, 0, 0);
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(b_rs, LDS_PTR(S + A_BYTES + j * 8192), 16, (int)b_off[j], kh * 64 * p.N * 4, 0, 0);
+    };
+
+    const int tb = wave >> 2, cb = wave & 3;
+    const int li = lane & 15, ks = lane >> 4;      // the MFMA's row (channel) / column (tile) and k slot
+    const bool khi = ks >> 1;
+    const int row = tb * 16 + li;
+    const int a_row = row * 128 + (((ks & 1) ^ ((row >> 1) & 7)) * 16);
+    const int b_col = A_BYTES + ((ks & 1) * 4 + (ks >> 1)) * 256 + (((cb * 4 + (li >> 2)) ^ ((ks & 1) * 4)) * 16) + (li & 3) * 4;
+    struct Frag {      // the operands of 32 k: per 8 k, V's chunk (this lane's two values are elements khi and khi + 2) and U's two values
+        f32x4 v[4];
+        float u[4][2];
+    };
+    auto fetch = [&](int st, int half, Frag& f) {
+        const unsigned char* S = lds + (st & (NS - 1)) * STAGE;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f.v[g] = *reinterpret_cast<const f32x4*>(S + half * 4096 + (a_row ^ (g * 32)));
+            f.u[g][0] = *reinterpret_cast<const float*>(S + b_col + (half * 32 + g * 8) * 256);
+            f.u[g][1] = *reinterpret_cast<const float*>(S + b_col + (half * 32 + g * 8 + 2) * 256);
+        }
+    };
+    auto mma = [&](const Frag& f, f32x4& acc) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(f.u[g][0], khi ? f.v[g][1] : f.v[g][0], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(f.u[g][1], khi ? f.v[g][3] : f.v[g][2], acc, 0, 0, 0);
+        }
+    };
+    // stage st has landed for every wave, and every wave has read all of stage st - 1, whose buffer takes stage st + NS - 1
+    auto arrive = [&](int st) {
+        // (this wave's part has landed once at most the NS - 2 stages issued behind it, 3 loads each, are in flight)
+        if (st + NS - 2 < total) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (st + NS - 1 < total) issue(st + NS - 1);
+    };
+
+    f32x4 acc[36];
+#pragma unroll
+    for (int i = 0; i < 36; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int st = 0; st < NS - 1; ++st) issue(st);
+    Frag f0, f1;
+    arrive(0);
+    fetch(0, 0, f0);
+#pragma unroll
+    for (int pos = 0; pos < 36; ++pos) {
+#pragma unroll
+        for (int kh = 0; kh < KS; ++kh) {
+            const int it = pos * KS + kh;
+            // (the scheduler would sink every read to its use and wait for it there: keep the reads one half ahead of their MFMAs)
+            fetch(it, 1, f1);
+            __builtin_amdgcn_sched_barrier(0);
+            mma(f0, acc[pos]);
+            __builtin_amdgcn_sched_barrier(0);
+            if (it + 1 < total) {
+                arrive(it + 1);
+                fetch(it + 1, 0, f0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            mma(f1, acc[pos]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+
+    const int t = m0 + tb * 16 + li;      // this lane's tile; its channels: quad q
+    if (t >= p.out.T) return;
+    const int q = (n0 >> 2) + cb * 4 + ks;
+    f32x4 o[4][4];
+    wino_out_transform([&](int r, int s) { return acc[r * 6 + s]; }, o);
+    if constexpr (MODE == 0 || MODE == 2)
+        wino_out_bias_relu(o, p.out.bias ? *reinterpret_cast<const f32x4*>(p.out.bias + q * 4) : f32x4{0.f, 0.f, 0.f, 0.f}, p.out.relu);
+    wino_out_store<MODE>(p.out, t, q, o);
 }
 
 // ---- the 36 GEMMs of the weight gradient: dU_p[Ci x Co] = sum_t V_p[t][Ci] . Ya_p[t][Co], split over t into slabs ---------------------
@@ -773,14 +923,48 @@ static void launch_out(WinoOutArgs& a, const char* label, double bytes, hipStrea
     HIP_OK(hipGetLastError());
 }
 
+// Which passes take wino_gemm_out_kernel instead of GEMM + output transform: by shape alone, never by the transform's mode, unless
+// SSD_WINO_FUSE_OUT=0 or the caller asks for two launches (the C ABI's flags bit 2).  Undilated, k and n of 64 or 128 and not both 128:
+// the passes whose M traffic outweighs their MFMA time.  Same box, batch 32, ms of input transform + GEMM + output transform, fused /
+// two launches (tools/bench_conv.py, profiles/wino_fuse_out_bench_conv.txt):
+//   conv1_2 forward (k 64, n 64)  1.198 / 1.562      conv1_2 data gradient (k 64, n 64)   1.395 / 1.724
+//   conv2_1 forward (k 64, n 128) 0.524 / 0.680      conv2_1 data gradient (k 128, n 64)  0.650 / 0.669
+// k = n = 128 (conv2_2) stays on two launches: its GEMM runs at 104 TF/s against this kernel's 59 - 70 (a 32 x 64 block per workgroup
+// reads U from L2 once per 32 tiles), so there the matrix pipe, not M, is what the pass waits for.
+static bool fuse_out(const ConvDesc& d, int N, int K, bool two_launch) {
+    static const int on = env_int("SSD_WINO_FUSE_OUT", 1);
+    return on && !two_launch && d.dil == 1 && (N == 64 || N == 128) && (K == 64 || K == 128) && !(N == 128 && K == 128);
+}
+// out_bytes: what the epilogue reads and writes besides the operands
+template <int MODE>
+static void launch_fused(const float* A, size_t a_ps, const float* Bm, int K, const WinoOutArgs& o, double out_bytes, hipStream_t s) {
+    constexpr size_t lds = 4 * (size_t)(32 * 64 + 64 * 64) * 4;
+    WinoFusedArgs a{};
+    a.A = A; a.Bm = Bm; a.M = o.T; a.N = o.N; a.K = K; a.a_ps = a_ps; a.b_ps = (size_t)K * o.N; a.NT = o.N / 64; a.out = o;
+    ProfScope prof("wino_gemm_out_32x64", 2.0 * 36 * a.M * (double)a.N * a.K, 4.0 * 36 * ((double)a.M * a.K + (double)a.K * a.N) + out_bytes, s);
+    if (K == 64) {
+        auto kern = wino_gemm_out_kernel<MODE, 1>;
+        static bool once = (set_lds(kern, lds), true);
+        (void)once;
+        SSD_LAUNCH_STOP(kern, dim3(cdiv(a.M, 32) * a.NT), dim3(512), lds, s, a);
+    } else {
+        auto kern = wino_gemm_out_kernel<MODE, 2>;
+        static bool once = (set_lds(kern, lds), true);
+        (void)once;
+        SSD_LAUNCH_STOP(kern, dim3(cdiv(a.M, 32) * a.NT), dim3(512), lds, s, a);
+    }
+    HIP_OK(hipGetLastError());
+}
+
 size_t wino_fwd_ws_floats(const ConvDesc& d) { return (size_t)36 * wino_tiles(d) * d.Co; }
 
 void wino_fwd(const ConvDesc& d, const float* x, const float* U, const float* bias, float* y, bool relu, float* V, size_t v_ps,
-              float* Mws, float* y_pool, void* pool_rec, hipStream_t s, void* relu_bits) {
+              float* Mws, float* y_pool, void* pool_rec, hipStream_t s, void* relu_bits, bool two_launch) {
     require(d);
     const int T = wino_tiles(d);
     launch_in(x, V, nullptr, d.B, d.Hi, d.Wi, d.Ci, d.Ci, d.dil, v_ps, 0, s, static_cast<unsigned long long*>(relu_bits));
-    gemm_nn(V, v_ps, U, Mws, (size_t)T * d.Co, T, d.Co, d.Ci, s);
+    const bool fused = fuse_out(d, d.Co, d.Ci, two_launch);
+    if (!fused) gemm_nn(V, v_ps, U, Mws, (size_t)T * d.Co, T, d.Co, d.Ci, s);
     WinoOutArgs a{};
     a.M = Mws; a.m_ps = (size_t)T * d.Co; a.bias = bias; a.relu = relu; a.H = d.Ho; a.W = d.Wo; a.N = d.Co;
     a.th = tiles_1d(d.Ho, d.dil); a.tw = tiles_1d(d.Wo, d.dil); a.T = T; a.D = d.dil;
@@ -788,10 +972,14 @@ void wino_fwd(const ConvDesc& d, const float* x, const float* U, const float* bi
     if (y_pool) {
         SSD_REQUIRE(d.dil == 1, "winograd: the fused pool is for undilated layers");
         a.y = y_pool; a.pool_rec = static_cast<unsigned short*>(pool_rec); a.PH = (d.Ho + 1) / 2; a.PW = (d.Wo + 1) / 2;
-        launch_out<2>(a, "wino_out_pool", mb + 4.0 * d.B * a.PH * a.PW * d.Co, s);
+        const double ob = 4.0 * d.B * a.PH * a.PW * d.Co;
+        if (fused) launch_fused<2>(V, v_ps, U, d.Ci, a, ob, s);
+        else launch_out<2>(a, "wino_out_pool", mb + ob, s);
     } else {
         a.y = y;
-        launch_out<0>(a, "wino_out", mb + 4.0 * d.B * d.Ho * d.Wo * d.Co, s);
+        const double ob = 4.0 * d.B * d.Ho * d.Wo * d.Co;
+        if (fused) launch_fused<0>(V, v_ps, U, d.Ci, a, ob, s);
+        else launch_out<0>(a, "wino_out", mb + ob, s);
     }
 }
 
@@ -804,10 +992,12 @@ void wino_bwd_transform(const ConvDesc& d, const float* dy, float* Yt, float* Ya
 }
 
 void wino_dgrad(const ConvDesc& d, const float* Yt, const float* Uflip, float* dx, const float* mask, bool accumulate, float* Xws,
-                const void* unpool_rec, int UH, int UW, hipStream_t s, const void* mask_bits) {
+                const void* unpool_rec, int UH, int UW, hipStream_t s, const void* mask_bits, bool two_launch) {
     require(d);
     const int T = wino_tiles(d);
-    gemm_nn(Yt, (size_t)T * wino_kpad(d.Co), Uflip, Xws, (size_t)T * d.Ci, T, d.Ci, wino_kpad(d.Co), s);
+    const size_t yt_ps = (size_t)T * wino_kpad(d.Co);
+    const bool fused = fuse_out(d, d.Ci, wino_kpad(d.Co), two_launch);
+    if (!fused) gemm_nn(Yt, yt_ps, Uflip, Xws, (size_t)T * d.Ci, T, d.Ci, wino_kpad(d.Co), s);
     WinoOutArgs a{};
     a.M = Xws; a.m_ps = (size_t)T * d.Ci; a.y = dx; a.mask = mask; a.accum = accumulate; a.H = d.Hi; a.W = d.Wi; a.N = d.Ci;
     a.mask_bits = mask ? static_cast<const unsigned long long*>(mask_bits) : nullptr;
@@ -816,9 +1006,13 @@ void wino_dgrad(const ConvDesc& d, const float* Yt, const float* Uflip, float* d
     if (unpool_rec) {
         SSD_REQUIRE(d.dil == 1, "winograd: the un-pooling form is for undilated layers");
         a.unpool_rec = static_cast<const unsigned short*>(unpool_rec); a.UH = UH; a.UW = UW;
-        launch_out<3>(a, "wino_out_unpool", mb + 4.0 * d.B * UH * UW * d.Ci, s);
+        const double ob = 4.0 * d.B * UH * UW * d.Ci;
+        if (fused) launch_fused<3>(Yt, yt_ps, Uflip, wino_kpad(d.Co), a, ob, s);
+        else launch_out<3>(a, "wino_out_unpool", mb + ob, s);
     } else {
-        launch_out<1>(a, "wino_out_dgrad", mb + 4.0 * d.B * d.Hi * d.Wi * d.Ci * (mask && !a.mask_bits ? 2 : 1), s);
+        const double ob = 4.0 * d.B * d.Hi * d.Wi * d.Ci * (mask && !a.mask_bits ? 2 : 1);
+        if (fused) launch_fused<1>(Yt, yt_ps, Uflip, wino_kpad(d.Co), a, ob, s);
+        else launch_out<1>(a, "wino_out_dgrad", mb + ob, s);
     }
 }
 
