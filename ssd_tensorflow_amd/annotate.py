@@ -148,3 +148,38 @@ def write_image(path, bgr):
     with open(path, 'wb') as f:
         f.write(png_bytes(rgb))
     return path
+
+
+def is_jpeg_name(path):
+    return os.path.splitext(path)[1].lower() in ('.jpg', '.jpeg')
+
+
+class GpuJpegWriter:
+    """The drivers' --encoder gpu: annotated pictures whose output name ends in .jpg / .jpeg are encoded from the annotation
+    launch's device buffer by jpeg.encode_launch and never reach the host as pixels; the other names of a batch go
+    through write_image as before.  launch() right behind annotate_last_launch, write() where the batch is collected."""
+
+    def __init__(self, quality=95):
+        self.quality = int(quality)
+
+    def launch(self, net, sources, style, paths):
+        """paths: the output path of every image of the batch.  Returns the ticket write() takes."""
+        jpg = [i for i, p in enumerate(paths) if is_jpeg_name(p)]
+        drawn = net.annotate_last_launch(*sources, style, keep_device=bool(jpg), to_host=len(jpg) < len(paths))
+        enc = None
+        if jpg:
+            from . import jpeg
+            enc = jpeg.encode_launch(drawn.dev, [drawn.offs[i] for i in jpg], [drawn.shapes[i] for i in jpg], quality=self.quality,
+                                     stream=drawn.stream)
+        return drawn, enc, jpg, list(paths)
+
+    def write(self, ticket):
+        drawn, enc, jpg, paths = ticket
+        if enc is not None:
+            for i, data in zip(jpg, enc.get()):
+                with open(paths[i], 'wb') as f:
+                    f.write(data)
+        if len(jpg) < len(paths):
+            images = drawn.get()
+            for i in sorted(set(range(len(paths))) - set(jpg)):
+                write_image(paths[i], images[i])

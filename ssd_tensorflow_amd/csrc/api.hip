@@ -4,6 +4,7 @@
 #include "augment.h"
 #include "annotate.h"
 #include "jpeg.h"
+#include "jpeg_enc.h"
 #include "metrics.h"
 #include <vector>
 #include <map>
@@ -443,6 +444,66 @@ int ssd_jpeg_decode_batch_dev(const short* coef_dev, size_t coef_bytes, const ss
                               size_t dst_bytes, void* ws_dev, size_t ws_bytes, void* stream) {
     API_BEGIN
     jpeg_decode_batch(coef_dev, coef_bytes, descs, n, dst_dev, dst_bytes, ws_dev, ws_bytes, (hipStream_t)stream);
+    API_END
+}
+
+int ssd_jpeg_quant_tables(int quality, unsigned short* luma, unsigned short* chroma) {
+    API_BEGIN
+    jpeg_quant_tables(quality, luma, chroma);
+    API_END
+}
+
+size_t ssd_jpeg_enc_coef_bytes(const int* shapes, int n, int sampling) {
+    try {
+        return jpeg_enc_coef_bytes(shapes, n, sampling);
+    } catch (const std::exception& e) {
+        ssd::set_error("%s", e.what());
+        return 0;
+    }
+}
+
+size_t ssd_jpeg_enc_ws_bytes(const int* shapes, int n, int sampling) {
+    try {
+        return jpeg_enc_ws_bytes(shapes, n, sampling);
+    } catch (const std::exception& e) {
+        ssd::set_error("%s", e.what());
+        return 0;
+    }
+}
+
+int ssd_jpeg_encode_batch_dev(const unsigned char* src_dev, size_t src_bytes, const unsigned long long* src_offs, const int* shapes,
+                              int n, int quality, int sampling, short* coef_dev, size_t coef_bytes, ssd_jpeg_desc* descs_out,
+                              void* ws_dev, size_t ws_bytes, void* stream) {
+    API_BEGIN
+    jpeg_encode_batch(src_dev, src_bytes, src_offs, shapes, n, quality, sampling, coef_dev, coef_bytes, descs_out, ws_dev, ws_bytes,
+                      (hipStream_t)stream);
+    API_END
+}
+
+size_t ssd_jpeg_file_bound(const ssd_jpeg_desc* desc) {
+    try {
+        SSD_REQUIRE(desc != nullptr, "null argument");
+        return jpeg_file_bound(*desc);
+    } catch (const std::exception& e) {
+        ssd::set_error("%s", e.what());
+        return 0;
+    }
+}
+
+int ssd_jpeg_entropy_encode(const short* coef, size_t coef_bytes, const ssd_jpeg_desc* desc, unsigned char* out, size_t out_cap,
+                            size_t* out_size) {
+    if (out_size) *out_size = 0;
+    API_BEGIN
+    SSD_REQUIRE(desc != nullptr && out_size != nullptr, "null argument");
+    *out_size = jpeg_entropy_encode(coef, coef_bytes, *desc, out, out_cap);
+    API_END
+}
+
+int ssd_jpeg_entropy_encode_batch(const short* coef, size_t coef_bytes, const ssd_jpeg_desc* descs, int n, int threads,
+                                  unsigned char* out, size_t out_bytes, const unsigned long long* out_offsets,
+                                  unsigned long long* out_sizes) {
+    API_BEGIN
+    jpeg_entropy_encode_batch(coef, coef_bytes, descs, n, threads, out, out_bytes, out_offsets, out_sizes);
     API_END
 }
 

@@ -10,7 +10,7 @@ import sys
 
 import numpy as np
 
-from .annotate import Style, write_image
+from .annotate import Style, write_image, GpuJpegWriter
 from .infer import sample_generator, resolve_class_names
 from .ssdvgg import SSDVGG, Session
 from .ssdutils import get_preset_by_name, boxes_from_detection
@@ -27,6 +27,9 @@ def main(argv=None):
     parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='f32, or bf16 activations on the bf16 matrix cores')
     parser.add_argument('--decoder', default='gpu', choices=['pillow', 'gpu'],
                         help='gpu: baseline JPEGs are decoded on the GPU, other files as with pillow (same pixels); pillow: every file is decoded on the host')
+    parser.add_argument('--encoder', default='pillow', choices=['pillow', 'gpu'],
+                        help='gpu: annotated pictures named .jpg / .jpeg are encoded as baseline JPEG on the GPU (what cv2.imwrite writes), other names as with pillow; pillow: every picture is encoded on the host')
+    parser.add_argument('--jpeg-quality', type=int, default=95, help='--encoder gpu: JPEG quality 1..100 (95 = cv2.imwrite)')
     args = parser.parse_args(argv)
 
     print('[i] Model:         ', args.model)
@@ -49,21 +52,30 @@ def main(argv=None):
         colors = default_colors(names)
         style = Style([colors[n] for n in names], names, sess.device)
 
+        writer = GpuJpegWriter(args.jpeg_quality) if args.encoder == 'gpu' else None
+
         def collect(pending):
             ticket, idxs, drawn = pending
-            images = drawn.get()
+            if writer is not None:
+                writer.write(drawn)
+            else:
+                images = drawn.get()
             for i, det in enumerate(ticket.get()):
                 name = os.path.basename(files[idxs[i]])
                 with open(os.path.join(args.output_dir, name + '.txt'), 'w') as f:
                     for _, box in boxes_from_detection(det, lid2name):
                         f.write('{} {} {} {} {} {}\n'.format(box.label, box.labelid, box.center.x, box.center.y, box.size.w, box.size.h))
-                write_image(os.path.join(args.output_dir, name), images[i])
+                if writer is None:
+                    write_image(os.path.join(args.output_dir, name), images[i])
 
         pending = None
         for x, idxs, sizes, sources in sample_generator(files, net.preset.image_size, args.batch_size, with_sources=True, decoder=args.decoder):
             net.infer_dev(x)
             ticket = net.detect_last_launch(x.shape[0], 0.5, None, 200)                      # detect.py:111-112
-            drawn = net.annotate_last_launch(*sources, style)
+            if writer is not None:
+                drawn = writer.launch(net, sources, style, [os.path.join(args.output_dir, os.path.basename(files[i])) for i in idxs])
+            else:
+                drawn = net.annotate_last_launch(*sources, style)
             if pending:
                 collect(pending)
             pending = (ticket, idxs, drawn)

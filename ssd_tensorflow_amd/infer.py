@@ -134,6 +134,9 @@ def main(argv=None):
     parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='f32, or bf16 activations on the bf16 matrix cores')
     parser.add_argument('--decoder', default='gpu', choices=['pillow', 'gpu'],
                         help='gpu: baseline JPEGs are decoded on the GPU, other files as with pillow (same pixels); pillow: every file is decoded on the host')
+    parser.add_argument('--encoder', default='pillow', choices=['pillow', 'gpu'],
+                        help='--annotate: gpu: pictures named .jpg / .jpeg are encoded as baseline JPEG on the GPU (what cv2.imwrite writes), other names as with pillow; pillow: every picture is encoded on the host')
+    parser.add_argument('--jpeg-quality', type=int, default=95, help='--encoder gpu: JPEG quality 1..100 (95 = cv2.imwrite)')
     args = parser.parse_args(argv)
 
     print('[i] Project name:      ', args.name)
@@ -226,11 +229,12 @@ def main(argv=None):
         pascal_summary = PascalSummary() if args.pascal_summary else None                    # infer.py:208-209
         style = None
         if args.annotate:                                                                    # infer.py:242-247
-            from .annotate import Style, write_image
+            from .annotate import Style, write_image, GpuJpegWriter
             names = [str(lid2name.get(i, 'class_%d' % i)) for i in range(num_classes)]
             cmap = dict(getattr(source, 'colors', None) or {}) if source else {}
             cmap = {**default_colors(names), **cmap}
             style = Style([cmap[n] for n in names], names, sess.device)
+        writer = GpuJpegWriter(args.jpeg_quality) if style is not None and args.encoder == 'gpu' else None
 
         def name_of(i):
             return files[i] if isinstance(files[i], str) else f'{i:06d}.npy'
@@ -240,7 +244,9 @@ def main(argv=None):
         def collect(pending):
             nonlocal total
             ticket, idxs, sizes, drawn = pending
-            if drawn is not None:
+            if drawn is not None and writer is not None:
+                writer.write(drawn)
+            elif drawn is not None:
                 for i, img in enumerate(drawn.get()):
                     write_image(os.path.join(args.output_dir, os.path.basename(name_of(idxs[i]))), img)
             for i, det in enumerate(ticket.get()):
@@ -257,7 +263,10 @@ def main(argv=None):
             x, idxs, sizes = batch[:3]
             net.infer_dev(x)                                                                 # infer.py:225-227
             ticket = net.detect_last_launch(x.shape[0], args.threshold, None, 200)
-            drawn = net.annotate_last_launch(*batch[3], style) if style is not None else None
+            if writer is not None:
+                drawn = writer.launch(net, batch[3], style, [os.path.join(args.output_dir, os.path.basename(name_of(i))) for i in idxs])
+            else:
+                drawn = net.annotate_last_launch(*batch[3], style) if style is not None else None
             if args.dump_predictions:                                                        # infer.py:251-254
                 enc_boxes = net._dev_result(x.shape[0], True)
                 for i in range(x.shape[0]):

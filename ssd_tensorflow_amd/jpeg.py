@@ -3,6 +3,10 @@ its Huffman stream on host threads; dequantisation, the inverse DCT, chroma upsa
 packed [h][w][3] uint8 BGR pixels where `transforms.augment_batch` and `annotate` read them.  The pixels equal libjpeg-turbo's
 default decode (what cv2.imread and Pillow produce) byte for byte.
 
+`encode_batch` is the way back, cv2.imwrite(<name>.jpg) without the CPU front half (csrc/jpeg_enc.hip): colour
+conversion, chroma downsampling, the forward DCT and quantisation run on the GPU on the same packed layout, Huffman coding and the
+file framing on host threads of the library; the files equal the ones libjpeg-turbo (cv2.imwrite, Pillow) writes byte for byte.
+
 A file outside the supported class (progressive, CMYK, unusual sampling, ...: status UNSUPPORTED), a non-JPEG file or a .npy array
 is loaded by `transforms.load_image_bgr` and copied into the same packed buffer.  A corrupt JPEG raises JpegError.
 """
@@ -173,3 +177,123 @@ def decode(file_or_bytes, device=0):
     dst, offs, sizes, _ = decode_batch([file_or_bytes], device=device, threads=1)
     h, w = sizes[0]
     return dst[offs[0]:offs[0] + h * w * 3].cpu().numpy().reshape(h, w, 3)
+
+
+# ------------------------------------------------------------------------------------------------ encoding
+SAMPLING = {'4:4:4': 0x11, '4:2:2': 0x21, '4:2:0': 0x22}
+
+
+def quant_tables(quality):
+    """(luma, chroma) uint16 [64] quantisation tables of a libjpeg quality 1..100, natural order"""
+    luma, chroma = np.zeros(64, np.uint16), np.zeros(64, np.uint16)
+    if lib.ssd_jpeg_quant_tables(int(quality), luma.ctypes.data, chroma.ctypes.data) != 0:
+        raise JpegError(last_error())
+    return luma, chroma
+
+
+def entropy_encode(coef, desc):
+    """Host only: the JFIF file (bytes) of one image's int16 coefficients and Desc (coef_off relative to `coef`)."""
+    coef = np.ascontiguousarray(coef, np.int16)
+    cap = lib.ssd_jpeg_file_bound(C.byref(desc))
+    if cap == 0:
+        raise JpegError(last_error())
+    out, size = np.empty(cap, np.uint8), C.c_size_t()
+    if lib.ssd_jpeg_entropy_encode(coef.ctypes.data, coef.nbytes, C.byref(desc), out.ctypes.data, cap, C.byref(size)) != 0:
+        raise JpegError(last_error())
+    return out[:size.value].tobytes()
+
+
+def entropy_encode_batch(coef, descs, threads=None):
+    """Host only: the JFIF files (list of bytes) of n images on up to `threads` host threads (default min(8, n); never derived from
+    the machine's core count).  coef: int16 numpy array; descs: Desc array with coef_off relative to `coef`."""
+    n = len(descs)
+    threads = min(8, max(n, 1)) if threads is None else int(threads)
+    offsets = (C.c_ulonglong * (n + 1))()
+    for i in range(n):
+        cap = lib.ssd_jpeg_file_bound(C.byref(descs[i]))
+        if cap == 0:
+            raise JpegError('image %d: %s' % (i, last_error()))
+        offsets[i + 1] = offsets[i] + cap
+    out = np.empty(max(int(offsets[n]), 16), np.uint8)               # (an upper bound: the pages behind a file are never touched)
+    sizes = (C.c_ulonglong * n)()
+    if lib.ssd_jpeg_entropy_encode_batch(coef.ctypes.data, coef.nbytes, descs, n, threads, out.ctypes.data, out.size, offsets, sizes) != 0:
+        raise JpegError(last_error())
+    return [out[offsets[i]:offsets[i] + sizes[i]].tobytes() for i in range(n)]
+
+
+class _Encoding:
+    """Ticket of encode_launch: the device stage and the copy of its coefficients are in flight."""
+    def __init__(self, host, descs, done, threads, keep):
+        self.host, self.descs, self.done, self.threads, self._keep = host, descs, done, threads, keep
+
+    def get(self):
+        """list of bytes, one JFIF file per image (waits for the copy, then runs the host stage)"""
+        self.done.synchronize()
+        self._keep = None
+        return entropy_encode_batch(self.host.numpy(), self.descs, self.threads)
+
+
+def encode_launch(src, offs=None, shapes=None, quality=95, subsampling='4:2:0', threads=None, stream=None, device=0):
+    """Enqueue the device stage of encode_batch and the device-to-host copy of the coefficients (into pinned memory) on `stream`
+    (a torch stream; default the current one); returns a ticket whose get() runs the host stage."""
+    import torch
+    if subsampling not in SAMPLING:
+        raise ValueError('subsampling must be one of 4:4:4, 4:2:2, 4:2:0 (got %r)' % (subsampling,))
+    if not hasattr(src, 'data_ptr'):                                  # host arrays: packed at 16-byte aligned offsets and uploaded
+        imgs = [np.ascontiguousarray(a) for a in src]
+        for a in imgs:
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError('encode_batch takes uint8 [H, W, 3] BGR images, got %s %s' % (a.dtype, a.shape))
+        shapes, offs, total = [a.shape[:2] for a in imgs], [], 0
+        for a in imgs:
+            offs.append(total)
+            total += (a.size + 15) // 16 * 16
+        stage = torch.empty((max(total, 16),), dtype=torch.uint8, pin_memory=True)
+        host = stage.numpy()
+        for a, o in zip(imgs, offs):
+            host[o:o + a.size] = a.reshape(-1)
+        dev = torch.device('cuda', device)
+    else:
+        if src.dtype != torch.uint8 or not src.is_contiguous():
+            raise ValueError('encode_batch takes a contiguous uint8 device tensor, got %s' % (src.dtype,))
+        stage, dev = None, src.device
+    n = len(shapes)
+    if n < 1 or len(offs) != n:
+        raise ValueError('one offset per image and at least one image')
+    threads = min(8, n) if threads is None else int(threads)
+    shp = (C.c_int * (2 * n))(*[int(v) for hw in shapes for v in hw[:2]])
+    src_offs = (C.c_ulonglong * n)(*[int(o) for o in offs])
+    sampling = SAMPLING[subsampling]
+    coef_bytes, ws_bytes = lib.ssd_jpeg_enc_coef_bytes(shp, n, sampling), lib.ssd_jpeg_enc_ws_bytes(shp, n, sampling)
+    if coef_bytes == 0 or ws_bytes == 0:
+        raise JpegError(last_error())
+    descs = (Desc * n)()
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+        cur = torch.cuda.current_stream(dev)
+        if stage is not None:
+            src = stage.to(dev, non_blocking=True)
+        coef_dev = torch.empty((coef_bytes // 2,), dtype=torch.int16, device=dev)
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        if lib.ssd_jpeg_encode_batch_dev(src.data_ptr(), src.numel(), src_offs, shp, n, int(quality), sampling, coef_dev.data_ptr(),
+                                         coef_bytes, descs, ws.data_ptr(), ws_bytes, cur.cuda_stream) != 0:
+            raise JpegError(last_error())
+        host = torch.empty((coef_bytes // 2,), dtype=torch.int16, pin_memory=True)
+        host.copy_(coef_dev, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(cur)
+    # (src, coef_dev and ws stay referenced until the copy has finished: another stream's allocations cannot take them before)
+    return _Encoding(host, descs, done, threads, (src, coef_dev, ws, stage))
+
+
+def encode_batch(src, offs=None, shapes=None, quality=95, subsampling='4:2:0', threads=None, stream=None, device=0):
+    """cv2.imwrite's JPEG bytes of a batch: list of bytes, one JFIF file per image.  src: a uint8 device tensor that holds image i as
+    [h][w][3] BGR at byte offset offs[i] (shapes[i] = (h, w); the layout annotate_batch and decode_batch write), or a list of
+    uint8 [h, w, 3] BGR host arrays, which are uploaded.  Device stage (one launch), one device-to-host copy of the int16
+    coefficients into pinned memory, then the host stage on up to `threads` threads (default min(8, n)).  quality 95 and 4:2:0
+    are cv2.imwrite's defaults."""
+    return encode_launch(src, offs, shapes, quality, subsampling, threads, stream, device).get()
+
+
+def encode(image, quality=95, subsampling='4:2:0', device=0):
+    """One uint8 [h, w, 3] BGR picture as the bytes of a JFIF file (through the GPU)."""
+    return encode_batch([image], quality=quality, subsampling=subsampling, threads=1, device=device)[0]

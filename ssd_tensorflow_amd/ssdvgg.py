@@ -102,12 +102,15 @@ class _Detections:
 
 
 class _Annotated:
-    """Ticket of SSDVGG.annotate_last_launch."""
-    def __init__(self, host, done, offs, shapes):
-        self.host, self.done, self.offs, self.shapes = host, done, offs, shapes
+    """Ticket of SSDVGG.annotate_last_launch.  With keep_device: `dev` is the packed device tensor the drawing wrote (image i as
+    [h][w][3] at byte offset offs[i], shapes[i] = (h, w)) and `stream` the torch stream it was written on."""
+    def __init__(self, host, done, offs, shapes, dev=None, stream=None):
+        self.host, self.done, self.offs, self.shapes, self.dev, self.stream = host, done, offs, shapes, dev, stream
 
     def get(self):
         from . import annotate as A
+        if self.host is None:
+            raise RuntimeError('annotate_last_launch(to_host=False) keeps the pictures on the GPU: there are no host pixels to get')
         self.done.synchronize()
         return A.unpack(self.host.numpy(), self.offs, self.shapes)
 
@@ -535,12 +538,14 @@ class SSDVGG:
             self._det_views = {}
         return _Detections(self, self._det_serial, b, out_cap)
 
-    def annotate_last_launch(self, src, src_offs, src_shapes, style, dst_shapes=None, rgb_out=False):
+    def annotate_last_launch(self, src, src_offs, src_shapes, style, dst_shapes=None, rgb_out=False, keep_device=False, to_host=True):
         """Enqueue, right behind the decode that detect_last_launch has just launched and on the same stream, the drawing of its
         detections (annotate.annotate_batch; the boxes are read from the pass's device-visible slot, nothing waits).  src: a
         torch uint8 or float32 CUDA tensor holding image i as [h][w][3] BGR at byte offset src_offs[i] (src_shapes[i] = (h, w));
         dst_shapes: other output sizes (float32 sources only: cv2.resize first); fewer images than the pass held: its first ones.  Returns a ticket whose get() yields the
-        uint8 [h, w, 3] images from pinned host memory; collect it with the pass's detections."""
+        uint8 [h, w, 3] images from pinned host memory; collect it with the pass's detections.  keep_device: the ticket also
+        carries the device tensor (`dev`, `offs`, `shapes`, `stream`: what jpeg.encode_launch takes); to_host=False: the pixels are
+        not copied to the host at all (get() then raises)."""
         import torch
         from . import annotate as A
         det = getattr(self, '_det_dev', None)
@@ -554,11 +559,13 @@ class SSDVGG:
         with torch.cuda.stream(stream):
             dst, offs, shapes = A.annotate_batch(src, src_offs, src_shapes, count_dev, cls_dev, box_dev, out_cap, style,
                                                  dst_shapes=dst_shapes, rgb_out=rgb_out, stream=ptr or None)
-            host = torch.empty(dst.shape, dtype=dst.dtype, pin_memory=True)
-            host.copy_(dst, non_blocking=True)
+            host = None
+            if to_host:
+                host = torch.empty(dst.shape, dtype=dst.dtype, pin_memory=True)
+                host.copy_(dst, non_blocking=True)
             done = torch.cuda.Event()
             done.record(stream)
-        return _Annotated(host, done, offs, shapes)
+        return _Annotated(host, done, offs, shapes, dst if keep_device else None, stream if keep_device else None)
 
     def detect_last(self, b, confidence_threshold=0.5, detections_cap=200, max_out=None, nms=True):
         """decode + NMS of the last step's result without leaving the GPU (train.py:275-277)."""
