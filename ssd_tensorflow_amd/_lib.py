@@ -79,6 +79,10 @@ SIGNATURES = {
     'ssd_jpeg_file_bound': (sz, [vp]),
     'ssd_jpeg_entropy_encode': (i32, [vp, sz, vp, vp, sz, C.POINTER(sz)]),
     'ssd_jpeg_entropy_encode_batch': (i32, [vp, sz, vp, i32, i32, vp, sz, vp, vp]),
+    'ssd_jpeg_file_header': (i32, [vp, vp]),
+    'ssd_jpeg_huff_ws_bytes': (sz, [vp, i32]),
+    'ssd_jpeg_huff_out_bytes': (sz, [vp, i32]),
+    'ssd_jpeg_huffman_batch_dev': (i32, [vp, sz, vp, i32, vp, sz, vp, vp, sz, vp]),
     'ssd_sampler_trials': (i32, [vp, i32, vp, vp, i32, i32, vp, i32, vp, vp]),
     'ssd_create': (i32, [cstr, i32, i32, i32, i32, C.c_ulonglong, vp, vp, vp, C.POINTER(handle)]),
     'ssd_create_dtype': (i32, [cstr, i32, i32, i32, i32, C.c_ulonglong, vp, vp, vp, i32, C.POINTER(handle)]),

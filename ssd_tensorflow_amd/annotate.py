@@ -159,8 +159,8 @@ class GpuJpegWriter:
     launch's device buffer by jpeg.encode_launch and never reach the host as pixels; the other names of a batch go
     through write_image as before.  launch() right behind annotate_last_launch, write() where the batch is collected."""
 
-    def __init__(self, quality=95):
-        self.quality = int(quality)
+    def __init__(self, quality=95, entropy='host'):
+        self.quality, self.entropy = int(quality), entropy
 
     def launch(self, net, sources, style, paths):
         """paths: the output path of every image of the batch.  Returns the ticket write() takes."""
@@ -170,7 +170,7 @@ class GpuJpegWriter:
         if jpg:
             from . import jpeg
             enc = jpeg.encode_launch(drawn.dev, [drawn.offs[i] for i in jpg], [drawn.shapes[i] for i in jpg], quality=self.quality,
-                                     stream=drawn.stream)
+                                     stream=drawn.stream, entropy=self.entropy)
         return drawn, enc, jpg, list(paths)
 
     def write(self, ticket):

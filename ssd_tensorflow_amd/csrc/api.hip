@@ -5,6 +5,7 @@
 #include "annotate.h"
 #include "jpeg.h"
 #include "jpeg_enc.h"
+#include "jpeg_huff.h"
 #include "metrics.h"
 #include <vector>
 #include <map>
@@ -504,6 +505,38 @@ int ssd_jpeg_entropy_encode_batch(const short* coef, size_t coef_bytes, const ss
                                   unsigned long long* out_sizes) {
     API_BEGIN
     jpeg_entropy_encode_batch(coef, coef_bytes, descs, n, threads, out, out_bytes, out_offsets, out_sizes);
+    API_END
+}
+
+int ssd_jpeg_file_header(const ssd_jpeg_desc* desc, unsigned char* out) {
+    API_BEGIN
+    SSD_REQUIRE(desc != nullptr, "null argument");
+    jpeg_file_header(*desc, out);
+    API_END
+}
+
+size_t ssd_jpeg_huff_ws_bytes(const ssd_jpeg_desc* descs, int n) {
+    try {
+        return jpeg_huff_ws_bytes(descs, n);
+    } catch (const std::exception& e) {
+        ssd::set_error("%s", e.what());
+        return 0;
+    }
+}
+
+size_t ssd_jpeg_huff_out_bytes(const ssd_jpeg_desc* descs, int n) {
+    try {
+        return jpeg_huff_out_bytes(descs, n);
+    } catch (const std::exception& e) {
+        ssd::set_error("%s", e.what());
+        return 0;
+    }
+}
+
+int ssd_jpeg_huffman_batch_dev(const short* coef_dev, size_t coef_bytes, const ssd_jpeg_desc* descs, int n, unsigned char* out_dev,
+                               size_t out_bytes, ssd_jpeg_file_rec* files_dev, void* ws_dev, size_t ws_bytes, void* stream) {
+    API_BEGIN
+    jpeg_huffman_batch(coef_dev, coef_bytes, descs, n, out_dev, out_bytes, files_dev, ws_dev, ws_bytes, (hipStream_t)stream);
     API_END
 }
 

@@ -8,6 +8,7 @@
 // It walks all images of the batch through a per-image prefix table of workgroups; nothing synchronises per image.
 //
 // Host half: Huffman coding with the Annex K tables + the file framing, native, batched and multi-threaded, one image per task.
+// (jpeg_huff.hip is the same half on the GPU; it shares the header writer, the code tables and the descriptor rules below.)
 // Every write is bounds-checked against the capacity the caller states.
 #include "jpeg_enc.h"
 #include <atomic>
@@ -429,9 +430,8 @@ void write_dht(Writer& W, int tc_th, const unsigned char* counts, const unsigned
     W.bytes(counts, 16); W.bytes(vals, (size_t)total);
 }
 
-size_t entropy_encode(const short* coef, const ssd_jpeg_desc& d, unsigned char* out, size_t out_cap) {
-    Writer W{out, out + out_cap};
-    // jcmarker.c: write_file_header, write_frame_header, write_scan_header
+// jcmarker.c: write_file_header, write_frame_header, write_scan_header -- the HEADER_BYTES in front of the scan
+void write_header(Writer& W, const ssd_jpeg_desc& d) {
     static const unsigned char APP0[18] = {0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
     W.be16(0xFFD8);
     W.bytes(APP0, sizeof APP0);
@@ -449,6 +449,11 @@ size_t entropy_encode(const short* coef, const ssd_jpeg_desc& d, unsigned char* 
     write_dht(W, 0x11, AC_CHROMA_BITS, AC_CHROMA_VALS, 162);
     static const unsigned char SOS[14] = {0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
     W.bytes(SOS, sizeof SOS);
+}
+
+size_t entropy_encode(const short* coef, const ssd_jpeg_desc& d, unsigned char* out, size_t out_cap) {
+    Writer W{out, out + out_cap};
+    write_header(W, d);
     const EncTablesHost& T = enc_tables();
     int pred[3] = {0, 0, 0};
     for (int y = 0; y < d.mcus_y; ++y)
@@ -471,6 +476,25 @@ size_t entropy_encode(const short* coef, const ssd_jpeg_desc& d, unsigned char* 
 }
 
 }  // namespace
+
+static_assert(HEADER_BYTES == SSD_JPEG_HEADER_BYTES, "the header the host stage writes");
+
+void jpeg_require_enc_desc(const ssd_jpeg_desc& d, size_t coef_bytes, int i) { require_enc_desc(d, coef_bytes, i); }
+
+void jpeg_file_header(const ssd_jpeg_desc& d, unsigned char* out) {
+    SSD_REQUIRE(out, "jpeg: null argument");
+    require_enc_desc(d, (size_t)-1, 0);
+    Writer W{out, out + HEADER_BYTES};
+    write_header(W, d);
+}
+
+void jpeg_huff_code_tables(unsigned dc[2][16], unsigned ac[2][256]) {
+    const EncTablesHost& T = enc_tables();
+    for (int t = 0; t < 2; ++t) {
+        for (int k = 0; k < 16; ++k) dc[t][k] = T.dc[t].code[k] | ((unsigned)T.dc[t].len[k] << 16);
+        for (int k = 0; k < 256; ++k) ac[t][k] = T.ac[t].code[k] | ((unsigned)T.ac[t].len[k] << 16);
+    }
+}
 
 size_t jpeg_file_bound(const ssd_jpeg_desc& d) {
     SSD_REQUIRE(d.width >= 1 && d.height >= 1 && d.width <= 16384 && d.height <= 16384, "jpeg: size %d x %d", d.width, d.height);

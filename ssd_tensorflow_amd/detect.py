@@ -30,6 +30,8 @@ def main(argv=None):
     parser.add_argument('--encoder', default='pillow', choices=['pillow', 'gpu'],
                         help='gpu: annotated pictures named .jpg / .jpeg are encoded as baseline JPEG on the GPU (what cv2.imwrite writes), other names as with pillow; pillow: every picture is encoded on the host')
     parser.add_argument('--jpeg-quality', type=int, default=95, help='--encoder gpu: JPEG quality 1..100 (95 = cv2.imwrite)')
+    parser.add_argument('--jpeg-entropy', default='host', choices=['host', 'gpu'],
+                        help='--encoder gpu: host: Huffman coding on host threads; gpu: on the GPU as well, only the files come back (same bytes)')
     args = parser.parse_args(argv)
 
     print('[i] Model:         ', args.model)
@@ -52,7 +54,7 @@ def main(argv=None):
         colors = default_colors(names)
         style = Style([colors[n] for n in names], names, sess.device)
 
-        writer = GpuJpegWriter(args.jpeg_quality) if args.encoder == 'gpu' else None
+        writer = GpuJpegWriter(args.jpeg_quality, args.jpeg_entropy) if args.encoder == 'gpu' else None
 
         def collect(pending):
             ticket, idxs, drawn = pending

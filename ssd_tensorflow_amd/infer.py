@@ -137,6 +137,8 @@ def main(argv=None):
     parser.add_argument('--encoder', default='pillow', choices=['pillow', 'gpu'],
                         help='--annotate: gpu: pictures named .jpg / .jpeg are encoded as baseline JPEG on the GPU (what cv2.imwrite writes), other names as with pillow; pillow: every picture is encoded on the host')
     parser.add_argument('--jpeg-quality', type=int, default=95, help='--encoder gpu: JPEG quality 1..100 (95 = cv2.imwrite)')
+    parser.add_argument('--jpeg-entropy', default='host', choices=['host', 'gpu'],
+                        help='--encoder gpu: host: Huffman coding on host threads; gpu: on the GPU as well, only the files come back (same bytes)')
     args = parser.parse_args(argv)
 
     print('[i] Project name:      ', args.name)
@@ -234,7 +236,7 @@ def main(argv=None):
             cmap = dict(getattr(source, 'colors', None) or {}) if source else {}
             cmap = {**default_colors(names), **cmap}
             style = Style([cmap[n] for n in names], names, sess.device)
-        writer = GpuJpegWriter(args.jpeg_quality) if style is not None and args.encoder == 'gpu' else None
+        writer = GpuJpegWriter(args.jpeg_quality, args.jpeg_entropy) if style is not None and args.encoder == 'gpu' else None
 
         def name_of(i):
             return files[i] if isinstance(files[i], str) else f'{i:06d}.npy'

@@ -6,6 +6,8 @@ default decode (what cv2.imread and Pillow produce) byte for byte.
 `encode_batch` is the way back, cv2.imwrite(<name>.jpg) without the CPU front half (csrc/jpeg_enc.hip): colour
 conversion, chroma downsampling, the forward DCT and quantisation run on the GPU on the same packed layout, Huffman coding and the
 file framing on host threads of the library; the files equal the ones libjpeg-turbo (cv2.imwrite, Pillow) writes byte for byte.
+With entropy='gpu' Huffman coding and the framing run on the GPU as well (csrc/jpeg_huff.hip) and only the files'
+own bytes come to the host; the bytes are the same.
 
 A file outside the supported class (progressive, CMYK, unusual sampling, ...: status UNSUPPORTED), a non-JPEG file or a .npy array
 is loaded by `transforms.load_image_bgr` and copied into the same packed buffer.  A corrupt JPEG raises JpegError.
@@ -221,6 +223,25 @@ def entropy_encode_batch(coef, descs, threads=None):
     return [out[offsets[i]:offsets[i] + sizes[i]].tobytes() for i in range(n)]
 
 
+class FileRec(C.Structure):
+    """ssd_jpeg_file_rec (include/ssdvgg_hip.h)"""
+    _fields_ = [('offset', C.c_ulonglong), ('size', C.c_ulonglong), ('status', C.c_int), ('reserved', C.c_int)]
+
+
+ENTROPY = ('host', 'gpu')
+HUFF_REFUSALS = {1: 'jpeg: a DC difference needs more than 11 bits, baseline Huffman codes 11',
+                 2: 'jpeg: an AC coefficient needs more than 10 bits, baseline Huffman codes 10'}
+_copy_streams = {}
+
+
+def file_header(desc):
+    """Host only: the 623 bytes in front of the scan (SOI ... SOS) of the file of this Desc"""
+    out = np.empty(623, np.uint8)
+    if lib.ssd_jpeg_file_header(C.byref(desc), out.ctypes.data) != 0:
+        raise JpegError(last_error())
+    return out.tobytes()
+
+
 class _Encoding:
     """Ticket of encode_launch: the device stage and the copy of its coefficients are in flight."""
     def __init__(self, host, descs, done, threads, keep):
@@ -233,12 +254,46 @@ class _Encoding:
         return entropy_encode_batch(self.host.numpy(), self.descs, self.threads)
 
 
-def encode_launch(src, offs=None, shapes=None, quality=95, subsampling='4:2:0', threads=None, stream=None, device=0):
+class _DeviceEncoding:
+    """Ticket of encode_launch(entropy='gpu'): both device stages and the copy of the file records are in flight."""
+    def __init__(self, recs, out, done, keep):
+        self.recs, self.out, self.done, self._keep = recs, out, done, keep
+
+    def get(self):
+        """list of bytes, one JFIF file per image: waits for the records, then copies exactly the files' bytes, on a stream of
+        its own (the caller's stream may hold the next batch's kernels by now)"""
+        import torch
+        self.done.synchronize()
+        n = self.recs.numel() // C.sizeof(FileRec)
+        recs = (FileRec * n).from_buffer_copy(self.recs.numpy().tobytes())
+        for i in range(n):
+            if recs[i].status != 0:
+                self._keep = self.out = None
+                raise JpegError('image %d: %s' % (i, HUFF_REFUSALS.get(recs[i].status, 'jpeg: status %d' % recs[i].status)))
+        total = int(recs[n - 1].offset + recs[n - 1].size)
+        dev = self.out.device
+        if dev.index not in _copy_streams:
+            _copy_streams[dev.index] = torch.cuda.Stream(dev)
+        side = _copy_streams[dev.index]
+        host = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
+        with torch.cuda.stream(side):
+            host.copy_(self.out[:total], non_blocking=True)
+        side.synchronize()
+        self._keep = self.out = None
+        data = host.numpy()
+        return [data[r.offset:r.offset + r.size].tobytes() for r in recs]
+
+
+def encode_launch(src, offs=None, shapes=None, quality=95, subsampling='4:2:0', threads=None, stream=None, device=0, entropy='host'):
     """Enqueue the device stage of encode_batch and the device-to-host copy of the coefficients (into pinned memory) on `stream`
-    (a torch stream; default the current one); returns a ticket whose get() runs the host stage."""
+    (a torch stream; default the current one); returns a ticket whose get() runs the host stage.  entropy='gpu': the Huffman
+    stage is enqueued behind the device stage, with a copy of the n file records; get() fetches the files' bytes (`threads` is
+    not used)."""
     import torch
     if subsampling not in SAMPLING:
         raise ValueError('subsampling must be one of 4:4:4, 4:2:2, 4:2:0 (got %r)' % (subsampling,))
+    if entropy not in ENTROPY:
+        raise ValueError("entropy must be 'host' or 'gpu' (got %r)" % (entropy,))
     if not hasattr(src, 'data_ptr'):                                  # host arrays: packed at 16-byte aligned offsets and uploaded
         imgs = [np.ascontiguousarray(a) for a in src]
         for a in imgs:
@@ -277,6 +332,21 @@ def encode_launch(src, offs=None, shapes=None, quality=95, subsampling='4:2:0', 
         if lib.ssd_jpeg_encode_batch_dev(src.data_ptr(), src.numel(), src_offs, shp, n, int(quality), sampling, coef_dev.data_ptr(),
                                          coef_bytes, descs, ws.data_ptr(), ws_bytes, cur.cuda_stream) != 0:
             raise JpegError(last_error())
+        if entropy == 'gpu':
+            huff_ws_bytes, out_bytes = lib.ssd_jpeg_huff_ws_bytes(descs, n), lib.ssd_jpeg_huff_out_bytes(descs, n)
+            if huff_ws_bytes == 0 or out_bytes == 0:
+                raise JpegError(last_error())
+            huff_ws = torch.empty((huff_ws_bytes,), dtype=torch.uint8, device=dev)
+            out = torch.empty((out_bytes,), dtype=torch.uint8, device=dev)
+            recs_dev = torch.empty((n * C.sizeof(FileRec),), dtype=torch.uint8, device=dev)
+            if lib.ssd_jpeg_huffman_batch_dev(coef_dev.data_ptr(), coef_bytes, descs, n, out.data_ptr(), out_bytes, recs_dev.data_ptr(),
+                                              huff_ws.data_ptr(), huff_ws_bytes, cur.cuda_stream) != 0:
+                raise JpegError(last_error())
+            recs = torch.empty((n * C.sizeof(FileRec),), dtype=torch.uint8, pin_memory=True)
+            recs.copy_(recs_dev, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(cur)
+            return _DeviceEncoding(recs, out, done, (src, coef_dev, ws, stage, huff_ws, recs_dev))
         host = torch.empty((coef_bytes // 2,), dtype=torch.int16, pin_memory=True)
         host.copy_(coef_dev, non_blocking=True)
         done = torch.cuda.Event()
@@ -285,15 +355,16 @@ def encode_launch(src, offs=None, shapes=None, quality=95, subsampling='4:2:0', 
     return _Encoding(host, descs, done, threads, (src, coef_dev, ws, stage))
 
 
-def encode_batch(src, offs=None, shapes=None, quality=95, subsampling='4:2:0', threads=None, stream=None, device=0):
+def encode_batch(src, offs=None, shapes=None, quality=95, subsampling='4:2:0', threads=None, stream=None, device=0, entropy='host'):
     """cv2.imwrite's JPEG bytes of a batch: list of bytes, one JFIF file per image.  src: a uint8 device tensor that holds image i as
     [h][w][3] BGR at byte offset offs[i] (shapes[i] = (h, w); the layout annotate_batch and decode_batch write), or a list of
     uint8 [h, w, 3] BGR host arrays, which are uploaded.  Device stage (one launch), one device-to-host copy of the int16
     coefficients into pinned memory, then the host stage on up to `threads` threads (default min(8, n)).  quality 95 and 4:2:0
-    are cv2.imwrite's defaults."""
-    return encode_launch(src, offs, shapes, quality, subsampling, threads, stream, device).get()
+    are cv2.imwrite's defaults.  entropy='gpu': Huffman coding and the framing on the GPU too (seven more launches), then one copy
+    of the n file records and one of the files' own bytes; the same files."""
+    return encode_launch(src, offs, shapes, quality, subsampling, threads, stream, device, entropy).get()
 
 
-def encode(image, quality=95, subsampling='4:2:0', device=0):
+def encode(image, quality=95, subsampling='4:2:0', device=0, entropy='host'):
     """One uint8 [h, w, 3] BGR picture as the bytes of a JFIF file (through the GPU)."""
-    return encode_batch([image], quality=quality, subsampling=subsampling, threads=1, device=device)[0]
+    return encode_batch([image], quality=quality, subsampling=subsampling, threads=1, device=device, entropy=entropy)[0]
