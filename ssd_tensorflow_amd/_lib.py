@@ -72,6 +72,10 @@ SIGNATURES = {
     'ssd_jpeg_entropy_decode_batch': (i32, [vp, vp, i32, i32, vp, vp, vp, vp]),
     'ssd_jpeg_ws_bytes': (sz, [vp, i32]),
     'ssd_jpeg_decode_batch_dev': (i32, [vp, sz, vp, i32, vp, sz, vp, sz, vp]),
+    'ssd_jpeg_scan_segments': (sz, [vp, sz]),
+    'ssd_jpeg_scan_plan': (i32, [vp, sz, vp, vp, p_i32]),
+    'ssd_jpeg_huffdec_ws_bytes': (sz, [vp, vp, i32]),
+    'ssd_jpeg_huffdec_batch_dev': (i32, [vp, sz, vp, vp, i32, vp, sz, vp, vp, sz, i32, vp]),
     'ssd_jpeg_quant_tables': (i32, [i32, vp, vp]),
     'ssd_jpeg_enc_coef_bytes': (sz, [vp, i32, i32]),
     'ssd_jpeg_enc_ws_bytes': (sz, [vp, i32, i32]),

@@ -6,6 +6,7 @@
 #include "jpeg.h"
 #include "jpeg_enc.h"
 #include "jpeg_huff.h"
+#include "jpeg_huffdec.h"
 #include "metrics.h"
 #include <vector>
 #include <map>
@@ -445,6 +446,40 @@ int ssd_jpeg_decode_batch_dev(const short* coef_dev, size_t coef_bytes, const ss
                               size_t dst_bytes, void* ws_dev, size_t ws_bytes, void* stream) {
     API_BEGIN
     jpeg_decode_batch(coef_dev, coef_bytes, descs, n, dst_dev, dst_bytes, ws_dev, ws_bytes, (hipStream_t)stream);
+    API_END
+}
+
+size_t ssd_jpeg_scan_segments(const unsigned char* bytes, size_t n) {
+    try {
+        return jpeg_scan_segments(bytes, n);
+    } catch (const std::exception& e) {
+        ssd::set_error("%s", e.what());
+        return 0;
+    }
+}
+
+int ssd_jpeg_scan_plan(const unsigned char* bytes, size_t n, ssd_jpeg_desc* desc, ssd_jpeg_plan* plan, int* status) {
+    if (status) *status = SSD_JPEG_ERROR;
+    API_BEGIN
+    SSD_REQUIRE(status != nullptr && desc != nullptr && plan != nullptr, "null argument");
+    *status = jpeg_scan_plan(bytes, n, desc, plan);
+    API_END
+}
+
+size_t ssd_jpeg_huffdec_ws_bytes(const ssd_jpeg_plan* plans, const ssd_jpeg_desc* descs, int n) {
+    try {
+        return jpeg_huffdec_ws_bytes(plans, descs, n);
+    } catch (const std::exception& e) {
+        ssd::set_error("%s", e.what());
+        return 0;
+    }
+}
+
+int ssd_jpeg_huffdec_batch_dev(const unsigned char* files_dev, size_t files_bytes, const ssd_jpeg_plan* plans,
+                               const ssd_jpeg_desc* descs, int n, short* coef_dev, size_t coef_bytes, ssd_jpeg_huffdec_rec* recs_dev,
+                               void* ws_dev, size_t ws_bytes, int max_rounds, void* stream) {
+    API_BEGIN
+    jpeg_huffdec_batch(files_dev, files_bytes, plans, descs, n, coef_dev, coef_bytes, recs_dev, ws_dev, ws_bytes, max_rounds, (hipStream_t)stream);
     API_END
 }
 

@@ -326,7 +326,87 @@ int entropy_decode(const unsigned char* bytes, size_t n, short* coef, size_t cap
     return SSD_JPEG_OK;
 }
 
+void export_table(const HuffTable& h, ssd_jpeg_huff_table& t) {
+    memcpy(t.fast_len, h.fast_len, sizeof t.fast_len);
+    memcpy(t.fast_val, h.fast_val, sizeof t.fast_val);
+    memcpy(t.maxcode, h.maxcode, sizeof t.maxcode);
+    memcpy(t.mincode, h.mincode, sizeof t.mincode);
+    memcpy(t.valptr, h.valptr, sizeof t.valptr);
+    memcpy(t.vals, h.vals, sizeof t.vals);
+    t.maxcode[0] = -1; t.mincode[0] = 0; t.valptr[0] = 0;      // (length 0 is never used)
+}
+
+// the selectors of one table class -> at most two slots; false: the scan selects three different tables
+bool assign_tables(const Parsed& P, const int* sel, const HuffTable* src, int* slot_out, ssd_jpeg_huff_table* dst) {
+    int used[2], nu = 0;
+    for (int c = 0; c < P.d.components; ++c) {
+        int s = -1;
+        for (int u = 0; u < nu; ++u)
+            if (used[u] == sel[c]) s = u;
+        if (s < 0) {
+            if (nu == 2) return false;
+            used[nu] = sel[c];
+            export_table(src[sel[c]], dst[nu]);
+            s = nu++;
+        }
+        slot_out[c] = s;
+    }
+    for (int c = P.d.components; c < 3; ++c) slot_out[c] = 0;
+    return true;
+}
+
 }  // namespace
+
+size_t jpeg_scan_segments(const unsigned char* bytes, size_t n) {
+    std::vector<Parsed> holder(1);
+    Parsed& P = holder[0];
+    if (parse(bytes, n, P) != SSD_JPEG_OK) return 0;
+    const long long mcus = (long long)P.d.mcus_x * P.d.mcus_y;
+    return (size_t)(P.dri ? (mcus + P.dri - 1) / P.dri : 1);
+}
+
+// The markers as entropy_decode sees them, then the segments by a byte search alone: a segment runs up to the first FF that no
+// 00 follows (Bits::fill's rule), and between two segments stands FF .. FF Dn with the index Bits::restart expects.
+int jpeg_scan_plan(const unsigned char* bytes, size_t n, ssd_jpeg_desc* desc, ssd_jpeg_plan* plan) {
+    SSD_REQUIRE(desc && plan, "jpeg: null argument");
+    std::vector<Parsed> holder(1);
+    Parsed& P = holder[0];
+    const int st = parse(bytes, n, P);
+    if (st != SSD_JPEG_OK) { memset(desc, 0, sizeof *desc); return st; }
+    *desc = P.d;
+    const long long mcus = (long long)P.d.mcus_x * P.d.mcus_y;
+    const long long expect = P.dri ? (mcus + P.dri - 1) / P.dri : 1;
+    SSD_REQUIRE(plan->seg != nullptr && plan->seg_cap >= expect, "jpeg: the segment array holds %d entries, the scan has %lld", plan->seg_cap, expect);
+    plan->file_bytes = n;
+    plan->scan_pos = P.scan_pos;
+    plan->restart_interval = P.dri;
+    plan->segments = (int)expect;
+    if (n >= ((size_t)1 << 30)) return SSD_JPEG_TO_HOST;
+    if (!assign_tables(P, P.comp_td, P.dc, plan->dc_sel, plan->dc) || !assign_tables(P, P.comp_ta, P.ac, plan->ac_sel, plan->ac))
+        return SSD_JPEG_TO_HOST;
+    size_t p = P.scan_pos;
+    for (long long s = 0; s < expect; ++s) {
+        const size_t begin = p;
+        size_t end = n;
+        while (p < n) {
+            const unsigned char* q = static_cast<const unsigned char*>(memchr(bytes + p, 0xFF, n - p));
+            if (!q) break;
+            const size_t at = (size_t)(q - bytes);
+            if (at + 1 < n && bytes[at + 1] == 0) { p = at + 2; continue; }
+            end = at;
+            break;
+        }
+        plan->seg[s].begin = (unsigned)begin;
+        plan->seg[s].end = (unsigned)end;
+        if (s + 1 == expect) break;
+        p = end;
+        if (!(p + 1 < n)) return SSD_JPEG_TO_HOST;                     // no marker where a restart is due
+        while (p + 2 < n && bytes[p + 1] == 0xFF) ++p;
+        if (bytes[p + 1] != 0xD0 + (int)(s & 7)) return SSD_JPEG_TO_HOST;
+        p += 2;
+    }
+    return SSD_JPEG_OK;
+}
 
 int jpeg_parse_header(const unsigned char* bytes, size_t n, ssd_jpeg_desc* desc) {
     std::vector<Parsed> holder(1);

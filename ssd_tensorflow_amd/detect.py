@@ -27,6 +27,8 @@ def main(argv=None):
     parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='f32, or bf16 activations on the bf16 matrix cores')
     parser.add_argument('--decoder', default='gpu', choices=['pillow', 'gpu'],
                         help='gpu: baseline JPEGs are decoded on the GPU, other files as with pillow (same pixels); pillow: every file is decoded on the host')
+    parser.add_argument('--decoder-entropy', default='host', choices=['host', 'gpu'],
+                        help='--decoder gpu: host: Huffman decoding on host threads; gpu: on the GPU as well, only the files\' bytes go to the device (same pixels)')
     parser.add_argument('--encoder', default='pillow', choices=['pillow', 'gpu'],
                         help='gpu: annotated pictures named .jpg / .jpeg are encoded as baseline JPEG on the GPU (what cv2.imwrite writes), other names as with pillow; pillow: every picture is encoded on the host')
     parser.add_argument('--jpeg-quality', type=int, default=95, help='--encoder gpu: JPEG quality 1..100 (95 = cv2.imwrite)')
@@ -71,7 +73,8 @@ def main(argv=None):
                     write_image(os.path.join(args.output_dir, name), images[i])
 
         pending = None
-        for x, idxs, sizes, sources in sample_generator(files, net.preset.image_size, args.batch_size, with_sources=True, decoder=args.decoder):
+        for x, idxs, sizes, sources in sample_generator(files, net.preset.image_size, args.batch_size, with_sources=True, decoder=args.decoder,
+                                                         decoder_entropy=args.decoder_entropy):
             net.infer_dev(x)
             ticket = net.detect_last_launch(x.shape[0], 0.5, None, 200)                      # detect.py:111-112
             if writer is not None:

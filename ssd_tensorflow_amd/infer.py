@@ -34,20 +34,20 @@ def _has_jpeg_candidates(files):
     return len(arrays) < len(files) and all(np.load(a, mmap_mode='r').dtype == np.uint8 for a in arrays)
 
 
-def sample_generator(samples, image_size, batch_size, device=0, with_sources=False, decoder='pillow'):
+def sample_generator(samples, image_size, batch_size, device=0, with_sources=False, decoder='pillow', decoder_entropy='host'):
     """infer.py:44-54: cv2.resize(cv2.imread(file), image_size).astype(float32) per batch -- here a batch of load +
     INTER_LINEAR resize plans executed by the augmentation kernel; yields (CUDA tensor [b,H,W,3], indices, sizes).
     with_sources: a fourth item (device tensor, byte offsets, [(h, w)]) of the pixels to draw on: the packed original-size
     uint8 images the resize read, or, for float inputs, the network-size batch itself.
     decoder='gpu': a batch of files is decoded by jpeg.decode_batch (baseline JPEGs on the GPU, anything else loaded as before
     and copied into the same device buffer), the resize plans read that buffer and it is also the buffer to draw on; the pixels
-    never exist on the host.  Batches of arrays alone (--synthetic, .npy files) take the path below either way."""
+    never exist on the host; decoder_entropy='gpu': the Huffman stage of that decode runs on the GPU too.  Batches of arrays alone (--synthetic, .npy files) take the path below either way."""
     from . import transforms as T
     for offset in range(0, len(samples), batch_size):
         files = samples[offset:offset + batch_size]
         if decoder == 'gpu' and _has_jpeg_candidates(files):
             from . import jpeg
-            packed, offs, shapes, _ = jpeg.decode_batch(files, device=device)
+            packed, offs, shapes, _ = jpeg.decode_batch(files, device=device, entropy=decoder_entropy)
             plans = []
             for i in range(len(files)):
                 plan = T.ImagePlan((packed, offs[i], shapes[i]))
@@ -134,6 +134,8 @@ def main(argv=None):
     parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='f32, or bf16 activations on the bf16 matrix cores')
     parser.add_argument('--decoder', default='gpu', choices=['pillow', 'gpu'],
                         help='gpu: baseline JPEGs are decoded on the GPU, other files as with pillow (same pixels); pillow: every file is decoded on the host')
+    parser.add_argument('--decoder-entropy', default='host', choices=['host', 'gpu'],
+                        help='--decoder gpu: host: Huffman decoding on host threads; gpu: on the GPU as well, only the files\' bytes go to the device (same pixels)')
     parser.add_argument('--encoder', default='pillow', choices=['pillow', 'gpu'],
                         help='--annotate: gpu: pictures named .jpg / .jpeg are encoded as baseline JPEG on the GPU (what cv2.imwrite writes), other names as with pillow; pillow: every picture is encoded on the host')
     parser.add_argument('--jpeg-quality', type=int, default=95, help='--encoder gpu: JPEG quality 1..100 (95 = cv2.imwrite)')
@@ -261,7 +263,8 @@ def main(argv=None):
                     pascal_summary.add_detections(name_of(idxs[i]), boxes, img_size=sizes[i])
 
         pending = None
-        for batch in sample_generator(files, size, args.batch_size, with_sources=style is not None, decoder=args.decoder):
+        for batch in sample_generator(files, size, args.batch_size, with_sources=style is not None, decoder=args.decoder,
+                                      decoder_entropy=args.decoder_entropy):
             x, idxs, sizes = batch[:3]
             net.infer_dev(x)                                                                 # infer.py:225-227
             ticket = net.detect_last_launch(x.shape[0], args.threshold, None, 200)

@@ -1,7 +1,8 @@
 """cv2.imread for baseline JPEGs without the CPU decode (csrc/jpeg.hip): the library parses the file and decodes
 its Huffman stream on host threads; dequantisation, the inverse DCT, chroma upsampling and YCbCr -> BGR run on the GPU and leave
 packed [h][w][3] uint8 BGR pixels where `transforms.augment_batch` and `annotate` read them.  The pixels equal libjpeg-turbo's
-default decode (what cv2.imread and Pillow produce) byte for byte.
+default decode (what cv2.imread and Pillow produce) byte for byte.  With decode_batch(entropy='gpu') the Huffman streams are
+decoded on the GPU as well (csrc/jpeg_huffdec.hip): the host parses the markers and copies the files' own bytes.
 
 `encode_batch` is the way back, cv2.imwrite(<name>.jpg) without the CPU front half (csrc/jpeg_enc.hip): colour
 conversion, chroma downsampling, the forward DCT and quantisation run on the GPU on the same packed layout, Huffman coding and the
@@ -19,7 +20,7 @@ import numpy as np
 
 from ._lib import lib, last_error
 
-OK, UNSUPPORTED, ERROR = 0, 1, 2
+OK, UNSUPPORTED, ERROR, TO_HOST = 0, 1, 2, 3       # TO_HOST (SSD_JPEG_TO_HOST) never leaves decode_batch
 MAX_L1 = 15000                   # SSD_JPEG_MAX_L1
 
 
@@ -83,6 +84,45 @@ def entropy_decode_batch(datas, threads=None, coef=None):
     return buf, list(offsets), descs, st, (last_error() if ERROR in st else '')
 
 
+class HuffTable(C.Structure):
+    """ssd_jpeg_huff_table (include/ssdvgg_hip.h)"""
+    _fields_ = [('fast_len', C.c_ubyte * 512), ('fast_val', C.c_ubyte * 512), ('maxcode', C.c_int * 17), ('mincode', C.c_int * 17),
+                ('valptr', C.c_int * 17), ('vals', C.c_ubyte * 256)]
+
+
+class Segment(C.Structure):
+    """ssd_jpeg_segment"""
+    _fields_ = [('begin', C.c_uint), ('end', C.c_uint)]
+
+
+class Plan(C.Structure):
+    """ssd_jpeg_plan"""
+    _fields_ = [('file_off', C.c_ulonglong), ('file_bytes', C.c_ulonglong), ('scan_pos', C.c_ulonglong), ('restart_interval', C.c_int),
+                ('segments', C.c_int), ('seg', C.POINTER(Segment)), ('seg_cap', C.c_int), ('dc_sel', C.c_int * 3), ('ac_sel', C.c_int * 3),
+                ('dc', HuffTable * 2), ('ac', HuffTable * 2)]
+
+
+class HuffdecRec(C.Structure):
+    """ssd_jpeg_huffdec_rec"""
+    _fields_ = [('status', C.c_int), ('max_l1', C.c_int)]
+
+
+def scan_plan(data, plan=None):
+    """Host only, no bit decoded: (status, Desc, Plan) of one file; the Plan (segment ranges in plan.seg[0 .. plan.segments), the
+    selected Huffman tables) is usable when the status is OK.  TO_HOST: entropy_decode decides.  JpegError for a corrupt header.
+    plan: a Plan to fill (an element of a Plan array), default a new one."""
+    a, ptr, n = _buf(data)
+    cap = lib.ssd_jpeg_scan_segments(ptr, n)
+    segs = (Segment * max(cap, 1))()
+    plan = Plan() if plan is None else plan
+    plan.seg, plan.seg_cap = segs, max(cap, 1)
+    plan._segs = segs                                            # (keeps the array alive with the plan)
+    d, st = Desc(), C.c_int()
+    if lib.ssd_jpeg_scan_plan(ptr, n, C.byref(d), C.byref(plan), st) != 0:
+        raise JpegError(last_error())
+    return st.value, d, plan
+
+
 def _read(item):
     """bytes of a file that may be a JPEG, else None (arrays, .npy files, files with a .npy beside them: load_image_bgr's rules)"""
     if isinstance(item, (bytes, bytearray, memoryview)):
@@ -110,12 +150,97 @@ def _fallback(item, data):
     return img
 
 
-def decode_batch(files_or_bytes, device=0, threads=None, stream=None):
+def _huffdec_gpu(datas, dev, max_rounds):
+    """The Huffman stage of decode_batch(entropy='gpu') for a list of bytes: plans on the calling thread, one pinned copy of the
+    files' bytes, the launches, one copy of the records, one wait.  Returns (device int16 coefficient tensor or None, Desc array,
+    statuses, messages): status OK with the descriptor complete (coef_off inside the tensor, max_l1), UNSUPPORTED, or ERROR with
+    the host stage's message; files the device stage hands over have been through entropy_decode and uploaded."""
+    import torch
+    n = len(datas)
+    descs, plans, keep = (Desc * n)(), (Plan * n)(), []
+    status, msgs = [ERROR] * n, [''] * n
+    for k, data in enumerate(datas):
+        try:
+            status[k], d, plan = scan_plan(data, plans[k])
+            keep.append(plan._segs)                              # (the segment arrays live until the launches have copied them)
+            C.memmove(C.byref(descs[k]), C.byref(d), C.sizeof(Desc))
+        except JpegError as e:
+            msgs[k] = str(e)
+    run = [k for k in range(n) if status[k] == OK]
+    host = [k for k in range(n) if status[k] == TO_HOST]
+    coef_off, total = {}, 0
+    for k in run + host:
+        coef_off[k] = total
+        total += lib.ssd_jpeg_coef_bytes(*_buf(datas[k])[1:])
+    if not total:
+        return None, descs, status, msgs
+    s = torch.cuda.current_stream(dev)
+    coef_dev = torch.empty((total // 2,), dtype=torch.int16, device=dev)
+    if run:
+        file_off, fbytes = [], 0
+        for k in run:
+            file_off.append(fbytes)
+            fbytes += (len(datas[k]) + 15) // 16 * 16
+        stage = torch.empty((fbytes,), dtype=torch.uint8, pin_memory=True)
+        view = stage.numpy()
+        rp, rd = (Plan * len(run))(), (Desc * len(run))()
+        for j, k in enumerate(run):
+            view[file_off[j]:file_off[j] + len(datas[k])] = np.frombuffer(datas[k], np.uint8)
+            C.memmove(C.byref(rp[j]), C.byref(plans[k]), C.sizeof(Plan))
+            C.memmove(C.byref(rd[j]), C.byref(descs[k]), C.sizeof(Desc))
+            rp[j].file_off = file_off[j]
+            for c in range(3):
+                rd[j].coef_off[c] += coef_off[k] // 2
+        files_dev = stage.to(dev, non_blocking=True)
+        ws_bytes = lib.ssd_jpeg_huffdec_ws_bytes(rp, rd, len(run))
+        if ws_bytes == 0:
+            raise RuntimeError(last_error())
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        recs_dev = torch.empty((len(run) * C.sizeof(HuffdecRec),), dtype=torch.uint8, device=dev)
+        if lib.ssd_jpeg_huffdec_batch_dev(files_dev.data_ptr(), files_dev.numel(), rp, rd, len(run), coef_dev.data_ptr(), total,
+                                          recs_dev.data_ptr(), ws.data_ptr(), ws_bytes, int(max_rounds), s.cuda_stream) != 0:
+            raise RuntimeError(last_error())
+        recs_host = torch.empty((len(run) * C.sizeof(HuffdecRec),), dtype=torch.uint8, pin_memory=True)
+        recs_host.copy_(recs_dev, non_blocking=True)
+        s.synchronize()                                          # the one wait
+        recs = (HuffdecRec * len(run)).from_buffer_copy(recs_host.numpy().tobytes())
+        for j, k in enumerate(run):
+            if recs[j].status == OK:
+                C.memmove(C.byref(descs[k]), C.byref(rd[j]), C.sizeof(Desc))
+                descs[k].max_l1 = recs[j].max_l1
+                if recs[j].max_l1 > MAX_L1:
+                    status[k] = UNSUPPORTED                      # the range guard: the caller's fallback decodes it
+            else:
+                status[k] = TO_HOST
+                host.append(k)
+    for k in sorted(host):                                       # the host stage decides: status, message, coefficients
+        try:
+            status[k], d, coef = entropy_decode(datas[k])
+        except JpegError as e:
+            status[k], msgs[k] = ERROR, str(e)
+            continue
+        if status[k] == OK:
+            C.memmove(C.byref(descs[k]), C.byref(d), C.sizeof(Desc))
+            for c in range(3):
+                descs[k].coef_off[c] += coef_off[k] // 2
+            nel = lib.ssd_jpeg_coef_bytes(*_buf(datas[k])[1:]) // 2
+            up = torch.empty((nel,), dtype=torch.int16, pin_memory=True)
+            up.numpy()[:] = coef[:nel]
+            coef_dev[coef_off[k] // 2:coef_off[k] // 2 + nel].copy_(up, non_blocking=True)
+    return coef_dev, descs, status, msgs
+
+
+def decode_batch(files_or_bytes, device=0, threads=None, stream=None, entropy='host', _max_rounds=0):
     """Decode a batch onto the GPU: (packed uint8 device tensor, byte offsets, [(h, w)], fallbacks).  Image i lies at
     offsets[i] (a multiple of 16; ascending unless there are fallbacks, which lie behind the decoded images) as [h][w][3] BGR;
     the bytes between images hold nothing.  One pinned staging buffer, one
     host-to-device copy, two kernel launches, all on `stream` (default: torch's current stream of `device`).  `fallbacks`: indices
-    of the items the library did not decode (unsupported JPEGs, other formats, arrays): loaded as load_image_bgr does and copied in."""
+    of the items the library did not decode (unsupported JPEGs, other formats, arrays): loaded as load_image_bgr does and copied in.
+    entropy='gpu': the Huffman stage runs on the GPU too (csrc/jpeg_huffdec.hip): the files' own bytes are copied
+    instead of the coefficients, and the call waits once for one small record per file; a file whose decode the device stage
+    cannot certify goes through the host stage.  The same return value and the same exceptions; `threads` is not used."""
+    if entropy not in ENTROPY:
+        raise ValueError("entropy must be 'host' or 'gpu' (got %r)" % (entropy,))
     import torch
     items = list(files_or_bytes)
     n = len(items)
@@ -129,8 +254,15 @@ def decode_batch(files_or_bytes, device=0, threads=None, stream=None):
         pinned.append(t)
         return t.numpy()
 
-    gpu, descs = [], None
-    if cand:
+    gpu, descs, coef_dev = [], None, None
+    if cand and entropy == 'gpu':
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+            coef_dev, descs, status, msgs = _huffdec_gpu([datas[i] for i in cand], dev, _max_rounds)
+        for k, i in enumerate(cand):                             # (the host path names the first bad file of the list, as "file k")
+            if status[k] == ERROR:
+                raise JpegError('%s: file %d: %s' % (items[i] if isinstance(items[i], str) else 'item %d' % i, k, msgs[k]))
+        gpu = [(k, i) for k, i in enumerate(cand) if status[k] == OK]
+    elif cand:
         coef, coef_offs, descs, status, err = entropy_decode_batch([datas[i] for i in cand], threads, alloc)
         for k, i in enumerate(cand):
             if status[k] == ERROR:
@@ -162,7 +294,8 @@ def decode_batch(files_or_bytes, device=0, threads=None, stream=None):
             for j, (k, i) in enumerate(gpu):
                 C.memmove(C.byref(run[j]), C.byref(descs[k]), C.sizeof(Desc))
                 run[j].dst_off = offsets[i]
-            coef_dev = pinned[0].to(dev, non_blocking=True)
+            if coef_dev is None:
+                coef_dev = pinned[0].to(dev, non_blocking=True)
             ws_bytes = lib.ssd_jpeg_ws_bytes(run, len(gpu))
             if ws_bytes == 0:
                 raise RuntimeError(last_error())
@@ -174,9 +307,9 @@ def decode_batch(files_or_bytes, device=0, threads=None, stream=None):
     return dst, offsets, sizes, fallbacks
 
 
-def decode(file_or_bytes, device=0):
+def decode(file_or_bytes, device=0, entropy='host'):
     """One image as a uint8 [h, w, 3] BGR numpy array (through the GPU)."""
-    dst, offs, sizes, _ = decode_batch([file_or_bytes], device=device, threads=1)
+    dst, offs, sizes, _ = decode_batch([file_or_bytes], device=device, threads=1, entropy=entropy)
     h, w = sizes[0]
     return dst[offs[0]:offs[0] + h * w * 3].cpu().numpy().reshape(h, w, 3)
 
