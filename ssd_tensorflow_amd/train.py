@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Training driver: the counterpart of the reference's train.py loop (train.py:247-343) over
 the HIP library.  Same flags (train.py:55-80) plus --preset / --synthetic-train / --synthetic-valid /
---augment / --dtype / --allreduce-bucket-mb / --allreduce-dtype.  Scalar summaries go to <tensorboard-dir>/<name>/scalars.jsonl
+--augment / --decoder / --cache-gb / --dtype / --allreduce-bucket-mb / --allreduce-dtype.  Scalar summaries go to <tensorboard-dir>/<name>/scalars.jsonl
 (summaries.py), the annotated image summaries as PNG files; TensorBoard event files are out of scope.
 
     python -m ssd_tensorflow_amd.train --name run1 --epochs 2 --batch-size 8
@@ -144,6 +144,8 @@ def main(argv=None):
     parser.add_argument('--weight-decay', type=float, default=0.0005, help='L2 normalization factor')
     parser.add_argument('--continue-training', type=str2bool, default='False', help='continue training from the latest checkpoint')
     parser.add_argument('--num-workers', type=int, default=0, help='number of parallel generators')
+    parser.add_argument('--decoder', default='pillow', choices=['pillow', 'gpu'], help='a real --data-dir: pillow = the workers decode the files; gpu = they run the Huffman stage only and the GPU decodes in front of the augmentation kernel')
+    parser.add_argument('--cache-gb', type=float, default=0, help='--decoder gpu: keep up to this many GB of decoded pictures in HBM; a cached picture costs no file read, no decode and no upload from its second epoch on (0 = off)')
     parser.add_argument('--preset', default='vgg300')
     parser.add_argument('--data-source', default='pascal_voc', help='data source module for a real --data-dir')
     parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='f32, or bf16 activations on the bf16 matrix cores (fp32 master weights, loss and optimizer)')
@@ -173,6 +175,8 @@ def main(argv=None):
     say('[i] Weight decay:         ', args.weight_decay)
     say('[i] Continue:             ', args.continue_training)
     say('[i] Number of workers:    ', args.num_workers)
+    say('[i] Decoder:              ', args.decoder)
+    say('[i] Picture cache (GB):   ', args.cache_gb)
 
     try:
         lr_values = [float(v) for v in args.lr_values.split(';')]
@@ -199,10 +203,12 @@ def main(argv=None):
         except OSError as e:
             print('[!] Cannot create directory {}: {}'.format(args.name, e)); return 1      # train.py:143-145
 
+    if args.cache_gb < 0 or (args.cache_gb and args.decoder != 'gpu'):
+        print('[!] --cache-gb keeps pictures decoded on the GPU: it needs --decoder gpu and a size >= 0'); return 1
     try:
         td = TrainingData(args.data_dir, args.preset, args.synthetic_train, args.synthetic_valid, rank=rank, world=world,
                           augment=args.augment, device=local, data_source=args.data_source,
-                          synthetic_classes=args.synthetic_classes)
+                          synthetic_classes=args.synthetic_classes, decoder=args.decoder, cache_bytes=int(args.cache_gb * 1e9))
     except RuntimeError as e:
         print('[!] Unable to load training data:', str(e)); return 1                       # train.py:155-161
     say('[i] # training samples:   ', td.num_train)

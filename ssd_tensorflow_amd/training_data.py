@@ -36,6 +36,11 @@ Sources:
     of the reference's own classes; here the same sample lists and the same recipes
     (transforms.build_train_transforms / build_valid_transforms) are built in process.  Images are
     decoded by transforms.load_image_bgr (.npy arrays or Pillow; decoder parity with OpenCV unpinned).
+
+decoder='gpu' (DESIGN.md 17): the workers run only the Huffman stage of a JPEG (ssd_jpeg_entropy_decode, host only) and ship int16
+coefficients; the feeder launches ssd_jpeg_decode_batch_dev in front of the augmentation kernel, so the pixels are born in HBM too.
+cache_bytes > 0 keeps them there (_SourceArena): from the second epoch on a cached sample costs its worker no file and the bus
+nothing but its parameter record and boxes.
 """
 import multiprocessing as mp
 import os
@@ -57,6 +62,8 @@ VOC_NAMES = ['aeroplane', 'bicycle', 'bird', 'boat', 'bottle', 'bus', 'car', 'ca
              'horse', 'motorbike', 'person', 'pottedplant', 'sheep', 'sofa', 'train', 'tvmonitor']
 
 DEVICE_SLOTS = 3            # one under the step, one ready, one being filled
+DECODERS = ('pillow', 'gpu')
+SRC_PIXELS, SRC_COEF, SRC_CACHED = 0, 1, 2      # 'src_kind' of a sample (decoder='gpu'): pixels in 'packed', coefficients in 'coef', nothing
 MAX_CLASSES = 127           # the library's range: 1..127 classes (include/ssdvgg_hip.h)
 
 
@@ -98,6 +105,9 @@ class _Recipe:
         self.pool = None
         self.active = False
         self.dev = None                        # this data set's device-side slot ring + feeder stream (TrainingData._device_ring)
+        # decoder='gpu' on a data set of files: JPEGs travel as coefficients and are decoded in front of the augmentation kernel
+        self.gpu_decode = td.decoder == 'gpu' and td._real_dataset and transforms is not None
+        self.stats = None                      # the feeder_stats of this data set's live generator
 
     def __getstate__(self):      # what a worker needs: not the pool it belongs to, nothing that lives on the GPU
         st = dict(self.__dict__)
@@ -107,17 +117,18 @@ class _Recipe:
         return st
 
     # ---- host half of a batch: runs in a worker process or, for num_workers == 0, in the caller --------------------
-    def plan(self, epoch, idx):
-        """(The transforms draw from the module-level `random`, seeded per sample below.  In the serial generator this runs in the
+    def plan(self, epoch, idx, known=None):
+        """known (decoder='gpu'): {position in idx: (h, w)} of the samples whose pixels the training process holds in HBM.
+        (The transforms draw from the module-level `random`, seeded per sample below.  In the serial generator this runs in the
         caller's process: its generator state is put back afterwards -- the reference never reseeds, and whatever else draws from
         `random` in the driver must not become a function of the last sample index.)"""
         state = random.getstate()
         try:
-            return self._plan(epoch, idx)
+            return self._plan(epoch, idx, known)
         finally:
             random.setstate(state)
 
-    def _plan(self, epoch, idx):
+    def _plan(self, epoch, idx, known=None):
         td = self.td
         if self.transforms is None:                              # preset-sized float32 synthetic images
             imgs, gts = [], []
@@ -135,12 +146,16 @@ class _Recipe:
         preset_images = getattr(loader, 'images', None)
         plans, gts = [], []
         try:
-            for i in idx:
+            for k, i in enumerate(idx):
                 s = self.sample_at(int(i))
                 if not isinstance(s, Sample):                    # synthetic: the pixels travel with the record
                     loader.images, sample = s
                 else:
                     loader.images, sample = preset_images, s
+                if self.gpu_decode:                                  # the file is read once per sample, or not at all
+                    loader.kept = None
+                    if known and k in known and isinstance(s, Sample):
+                        loader.kept = (s.filename, T.DeferredJpeg(None, known[k], s.filename))
                 random.seed(td._sample_seed(self.salt, epoch, int(i)))
                 # run_transforms until at least one anchor is positive, at most 50 times (training_data.py:88-98);
                 # the label of a try is only LOOKED at there (num_bg < rows), so the test runs on the host and the
@@ -154,15 +169,61 @@ class _Recipe:
                 plans.append(args[0]); gts.append(args[2].boxes)
         finally:
             loader.images = preset_images
-        arr, packed = T.plan_params(plans, td.preset.image_size.w, td.preset.image_size.h)
-        return dict({'params': np.frombuffer(arr, np.uint8).copy(), 'packed': packed}, **_gt_packed(gts, td.num_classes)), gts
+            if self.gpu_decode:
+                loader.kept = None
+        W, H = td.preset.image_size.w, td.preset.image_size.h
+        if not self.gpu_decode:
+            arr, packed = T.plan_params(plans, W, H)
+            return dict({'params': np.frombuffer(arr, np.uint8).copy(), 'packed': packed}, **_gt_packed(gts, td.num_classes)), gts
+        coef, descs = self._entropy_stage(plans)
+        arr, packed = T.plan_params(plans, W, H)
+        kind = np.array([SRC_PIXELS if p.jpeg is None else SRC_COEF if p.jpeg.data is not None else SRC_CACHED for p in plans], np.int32)
+        for d, k in zip(descs, np.flatnonzero(kind == SRC_COEF)):
+            d.dst_off = arr[k].src_off
+        return dict({'params': np.frombuffer(arr, np.uint8).copy(), 'packed': packed, 'coef': coef,
+                     'descs': np.frombuffer(b''.join(bytes(d) for d in descs), np.uint8).copy(), 'src_kind': kind},
+                    **_gt_packed(gts, td.num_classes)), gts
+
+    @staticmethod
+    def _entropy_stage(plans):
+        """The Huffman stage of the batch's deferred JPEGs, host only: (int16 coefficients of all of them, each file's at a
+        16-byte aligned offset; their ssd_jpeg_desc records, coef_off relative to that array).  A file the 32-bit range guard
+        refuses becomes a host-pixel plan in place (its decisions stand: they depend on the size alone); a corrupt stream raises
+        JpegError with the file's name."""
+        import ctypes as C
+        from . import jpeg as J, transforms as T
+        from ._lib import lib, last_error
+        todo = [p for p in plans if p.jpeg is not None and p.jpeg.data is not None]
+        bufs = [J._buf(p.jpeg.data) for p in todo]
+        sizes = [(lib.ssd_jpeg_coef_bytes(a[1], a[2]) + 15) // 16 * 16 for a in bufs]
+        coef = np.zeros(sum(sizes) // 2, np.int16)
+        descs, off = [], 0
+        for p, (_, ptr, n), size in zip(todo, bufs, sizes):
+            d, st = J.Desc(), C.c_int()
+            if lib.ssd_jpeg_entropy_decode(ptr, n, coef.ctypes.data + off, size, C.byref(d), st) != 0:
+                raise J.JpegError('%s: %s' % (p.jpeg.filename, last_error()))
+            if st.value != J.OK:                                 # the range guard (max_l1 > SSD_JPEG_MAX_L1): the pixel path
+                img = np.ascontiguousarray(T.load_image_bgr(p.jpeg.filename))
+                if img.dtype != np.uint8 or img.shape != (p.src.h, p.src.w, 3):
+                    raise ValueError('%s: the decoded image is %s %s, its header says %d x %d' %
+                                     (p.jpeg.filename, img.dtype, img.shape, p.src.w, p.src.h))
+                coef[off // 2:(off + size) // 2] = 0
+                p.image, p.jpeg = img, None
+                continue
+            for c in range(3):
+                d.coef_off[c] += off // 2
+            descs.append(d)
+            off += size
+        return coef[:off // 2], descs
 
     def slot_bytes(self, batch_size):
         td = self.td
         W, H = td.preset.image_size.w, td.preset.image_size.h
         if self.transforms is None:
             return batch_size * (H * W * 3 * 4 + 4096) + 8192
-        return batch_size * (td._max_image_bytes + 16 + 256 + 4096) + 8192
+        # (decoder='gpu': a sample travels as pixels OR as coefficients, and the coefficients' bound is the larger one)
+        per_image = max(td._max_image_bytes, td._max_coef_bytes + 512 if self.gpu_decode else 0)
+        return batch_size * (per_image + 16 + 256 + 4096) + 8192
 
 
 def _worker_main(recipe, tasks, results, anchors_abs=None):
@@ -186,12 +247,58 @@ def _worker_main(recipe, tasks, results, anchors_abs=None):
             continue
         if task is None:
             break
-        gen, seq, slot, epoch, idx = task
+        gen, seq, slot, epoch, idx, known = task
         try:
-            arrays, gts = recipe.plan(epoch, idx)
+            arrays, gts = recipe.plan(epoch, idx, known)
             results.put((gen, seq), slot, arrays, gts)
         except BaseException:
             results.put_error((gen, seq), slot, traceback.format_exc())
+
+
+class _SourceArena:
+    """Where the source pixels of decoder='gpu' batches lie: ONE uint8 device buffer (ssd_augment_batch_dev reads all sources of a
+    batch from one buffer) of `cache_bytes` that decoded pictures are appended to and never leave, plus a scratch tail with one
+    region per data set and device slot (and one for each data set's serial generator) for the pictures that are not kept.
+    Append-only: an entry is never moved, evicted or rewritten, so a reader needs no more than stream order behind the append
+    that wrote its entry -- `event` is recorded behind the last append and a batch enqueued on another stream waits for it first.
+    `lock` is held from placing a batch's pictures until that event is recorded: two data sets' feeder threads share the arena."""
+
+    def __init__(self, cache_bytes, max_image_bytes):
+        self.cache_bytes = int(cache_bytes) // 256 * 256
+        self.max_image_bytes = int(max_image_bytes)
+        self.image_bytes = (self.max_image_bytes + 16 + 255) // 256 * 256
+        self.buf, self.batch = None, 0
+        self.table = {}                        # (data set, sample index) -> (byte offset, h, w)
+        self.used = 0
+        self.event, self.event_stream = None, None
+        self.lock = threading.Lock()
+
+    def ensure(self, batch_size, dev, busy):
+        """The buffer with scratch regions for batches of batch_size.  A larger batch than any before needs a larger tail: the
+        buffer is replaced and the entries copied to the same offsets, which only works while no generator is using it."""
+        import torch
+        with self.lock:
+            if self.buf is not None and self.batch >= batch_size:
+                return
+            if self.buf is not None and busy:
+                raise RuntimeError('a larger batch size needs a larger source arena: finish the live generators first')
+            size = self.cache_bytes + 2 * (DEVICE_SLOTS + 1) * batch_size * self.image_bytes
+            buf = torch.empty((size,), dtype=torch.uint8, device=dev)
+            cur = torch.cuda.current_stream(dev)
+            if self.buf is not None and self.used:
+                if self.event is not None:
+                    cur.wait_event(self.event)
+                buf[:self.used].copy_(self.buf[:self.used])
+                self.event = torch.cuda.Event()
+                self.event.record(cur)
+                self.event_stream = cur.cuda_stream
+            self.buf, self.batch = buf, batch_size
+
+    def region(self, which, slot):
+        """(byte offset, bytes) of the scratch of a data set's device slot (None: its serial generator)"""
+        r = (0 if which == 'train' else DEVICE_SLOTS + 1) + (0 if slot is None else 1 + slot)
+        n = self.batch * self.image_bytes
+        return self.cache_bytes + r * n, n
 
 
 class _SharedImageCache:
@@ -386,7 +493,14 @@ class TrainingData:
 
     def __init__(self, data_dir=None, preset='vgg300', num_train=64, num_valid=16, seed=1234, rank=0, world=1,
                  augment=False, sampler_trials=50, expand_prob=0.5, device=0, device_tensors=True,
-                 data_source='pascal_voc', valid_fraction=0.025, images=None, synthetic_classes=20):
+                 data_source='pascal_voc', valid_fraction=0.025, images=None, synthetic_classes=20, decoder='pillow', cache_bytes=0):
+        if decoder not in DECODERS:
+            raise ValueError("decoder must be 'pillow' or 'gpu' (got %r)" % (decoder,))
+        if int(cache_bytes) < 0 or (cache_bytes and decoder != 'gpu'):
+            raise ValueError("cache_bytes keeps pictures decoded on the GPU: it needs decoder='gpu' and a size >= 0")
+        self.decoder, self.cache_bytes = decoder, int(cache_bytes)
+        self._arena = None
+        self._max_coef_bytes = 0
         self.preset = get_preset_by_name(preset) if isinstance(preset, str) else preset
         self.seed, self.rank, self.world = seed, rank, world
         self.epoch = 0
@@ -396,7 +510,8 @@ class TrainingData:
         self._synthetic_cache = _SharedImageCache(CACHE_SYNTHETIC_UP_TO)
         # where a prefetched epoch's time went (seconds, reset by every gen_batch call with workers): the consumer waiting
         # for a batch, the feeder thread waiting for the workers / for a free device slot / uploading
-        self.feeder_stats = dict(consumer_wait=0.0, worker_wait=0.0, slot_wait=0.0, upload=0.0, batches=0)
+        # decoder='gpu': samples whose JPEG the GPU decoded / that travelled as pixels / that were served from the arena
+        self.feeder_stats = dict(consumer_wait=0.0, worker_wait=0.0, slot_wait=0.0, upload=0.0, batches=0, decoded=0, fallbacks=0, cache_hits=0)
         from . import transforms as T
         # 'shapes': the learnable synthetic set (textured rectangles, class = texture; _shapes_canvas) -- same plumbing as
         # 'synthetic', whose uniform-noise images carry nothing a detector could learn
@@ -415,9 +530,14 @@ class TrainingData:
             self.train_samples, self.valid_samples = list(source.train_samples), list(source.valid_samples)
             self.num_train, self.num_valid = len(self.train_samples), len(self.valid_samples)
             self.augment = True
-            self.train_transforms = T.build_train_transforms(self.preset, self.num_classes, sampler_trials, expand_prob, images)
-            self.valid_transforms = T.build_valid_transforms(self.preset, self.num_classes, images)
+            self.train_transforms = T.build_train_transforms(self.preset, self.num_classes, sampler_trials, expand_prob, images, decoder)
+            self.valid_transforms = T.build_valid_transforms(self.preset, self.num_classes, images, decoder)
             self._max_image_bytes = max([s.imgsize.w * s.imgsize.h * 3 for s in self.train_samples + self.valid_samples] + [1])
+            if decoder == 'gpu':
+                # int16 coefficients: at most 6 bytes per pixel of the MCU-padded frame (4:4:4; an MCU is at most 16 x 16)
+                self._max_coef_bytes = max([6 * ((s.imgsize.w + 15) // 16 * 16) * ((s.imgsize.h + 15) // 16 * 16)
+                                            for s in self.train_samples + self.valid_samples] + [1])
+                self._arena = _SourceArena(self.cache_bytes, self._max_image_bytes)
             self._recipes = {
                 'train': _Recipe(self, 'train', self.num_train, 0, _SampleAt(self, 'train', 0), self.train_transforms),
                 'valid': _Recipe(self, 'valid', self.num_valid, 1 << 20, _SampleAt(self, 'valid', 1 << 20), self.valid_transforms)}
@@ -449,7 +569,7 @@ class TrainingData:
     # ---- what travels to a worker process (forkserver / spawn start: _start_context) ------------------------------
     def __getstate__(self):
         st = dict(self.__dict__)
-        for k in ('_upload_hook', 'train_generator', 'valid_generator'):
+        for k in ('_upload_hook', 'train_generator', 'valid_generator', '_arena'):
             st[k] = None
         return st
 
@@ -463,6 +583,8 @@ class TrainingData:
                 r.pool.close()
                 r.pool = None
             r.dev = None
+        if self._arena is not None:            # the cached pictures go with the buffer
+            self._arena = _SourceArena(self.cache_bytes, self._arena.max_image_bytes)
 
     def __del__(self):
         try:
@@ -575,12 +697,97 @@ class TrainingData:
         d = {'batch': batch_size, 'stream': torch.cuda.Stream(device=dev),
              'images': [torch.empty((batch_size, H, W, 3), dtype=torch.float32, device=dev) for _ in range(DEVICE_SLOTS)],
              'labels': [torch.empty((batch_size, A, nv), dtype=torch.float32, device=dev) for _ in range(DEVICE_SLOTS)],
-             'packed': [None] * DEVICE_SLOTS, 'enc_ws': [None] * DEVICE_SLOTS,
+             'packed': [None] * DEVICE_SLOTS, 'enc_ws': [None] * DEVICE_SLOTS, 'jpeg_ws': [None] * DEVICE_SLOTS,
              'ws': [torch.empty((lib.ssd_augment_ws_bytes(batch_size, W, H),), dtype=torch.uint8, device=dev) for _ in range(DEVICE_SLOTS)]}
         recipe.dev = d
         return d
 
-    def _upload(self, arrays, gts, slot=None, ring=None):
+    def _known(self, recipe, idx):
+        """{position in idx: (h, w)} of the samples whose pixels lie in the arena (what a task tells its worker), else None"""
+        arena = self._arena
+        if arena is None or not arena.table or not recipe.gpu_decode:
+            return None
+        hits = {k: arena.table.get((recipe.which, int(i))) for k, i in enumerate(idx)}
+        return {k: (e[1], e[2]) for k, e in hits.items() if e is not None} or None
+
+    def _decode_sources(self, recipe, idx, arrays, slot, ring, coef_dev, packed_dev):
+        """decoder='gpu': the batch's source pictures into the arena, on torch's current stream -> (arena buffer, the batch's
+        ssd_augment_params with src_off = where each picture lies in it).  coef_dev / packed_dev: the worker's 'coef' and 'packed'
+        arrays on the GPU (uint8 views).  A picture that is not cached yet is decoded (copied, for a fallback's pixels) into the
+        arena's next free bytes and entered; when the arena is full, or the sample was cached while its task was under way, into
+        this slot's scratch region.  Nothing is waited for."""
+        import ctypes as C
+        import torch
+        from . import jpeg as J, transforms as T
+        from ._lib import lib, check, last_error
+        arena, stats = self._arena, recipe.stats          # (the stats of THIS data set's generator: two may be live)
+        dev = torch.device('cuda', self.device)
+        cur = torch.cuda.current_stream(dev)
+        b = len(idx)
+        kind = arrays['src_kind']
+        params = (T._Params * b).from_buffer_copy(arrays['params'].tobytes())
+        nd = int(np.count_nonzero(kind == SRC_COEF))
+        if arrays['descs'].nbytes != nd * C.sizeof(J.Desc):
+            raise RuntimeError('the batch carries %d descriptor bytes for %d JPEGs' % (arrays['descs'].nbytes, nd))
+        descs = (J.Desc * max(nd, 1)).from_buffer_copy(arrays['descs'].tobytes() if nd else bytes(C.sizeof(J.Desc)))
+        with arena.lock:
+            buf = arena.buf
+            if arena.event is not None and arena.event_stream != cur.cuda_stream:
+                cur.wait_event(arena.event)          # entries appended on another stream (the other data set's feeder)
+            base, room = arena.region(recipe.which, slot)
+            scratch, j, at, appended = 0, 0, 0, False
+            for k in range(b):
+                h, w = params[k].src_h, params[k].src_w
+                n = h * w * 3
+                need = (n + 15) // 16 * 16
+                key = (recipe.which, int(idx[k]))
+                entry = arena.table.get(key)
+                if kind[k] == SRC_CACHED:
+                    if entry is None or entry[1:] != (h, w):
+                        raise RuntimeError('sample %d of the %s set was planned as cached and is not in the arena' % (idx[k], recipe.which))
+                    off = entry[0]
+                    stats['cache_hits'] += 1
+                else:
+                    if entry is None and arena.used + need <= arena.cache_bytes:
+                        off = arena.used
+                        arena.used += need
+                        arena.table[key] = (off, h, w)
+                        appended = True
+                    else:
+                        if scratch + need > room:
+                            raise RuntimeError('a batch of the %s set needs more than the %d bytes of source scratch its sample list announced '
+                                               '(images larger than their imgsize?)' % (recipe.which, room))
+                        off = base + scratch
+                        scratch += need
+                    if kind[k] == SRC_COEF:
+                        descs[j].dst_off = off
+                        j += 1
+                        stats['decoded'] += 1
+                    else:
+                        if at + n > packed_dev.numel():
+                            raise RuntimeError("the batch's 'packed' array is shorter than its host-pixel samples")
+                        buf[off:off + n].copy_(packed_dev[at:at + n], non_blocking=True)
+                        at += need
+                        stats['fallbacks'] += 1
+                params[k].src_off = off
+            if nd:
+                ws_bytes = lib.ssd_jpeg_ws_bytes(descs, nd)
+                if ws_bytes == 0:
+                    raise RuntimeError(last_error())
+                ws = ring['jpeg_ws'][slot] if ring is not None else None
+                if ws is None or ws.numel() < ws_bytes:          # (allocated under the current stream: the feeder's, in the ring)
+                    ws = torch.empty((ws_bytes + ws_bytes // 4,), dtype=torch.uint8, device=dev)
+                    if ring is not None:
+                        ring['jpeg_ws'][slot] = ws
+                check(lib.ssd_jpeg_decode_batch_dev(coef_dev.data_ptr(), coef_dev.numel(), descs, nd, buf.data_ptr(), buf.numel(),
+                                                    ws.data_ptr(), ws.numel(), cur.cuda_stream))
+            if appended:
+                arena.event = torch.cuda.Event()
+                arena.event.record(cur)
+                arena.event_stream = cur.cuda_stream
+        return buf, params
+
+    def _upload(self, arrays, gts, slot=None, ring=None, recipe=None, idx=None):
         """Source bytes up, augmentation + label kernels on torch's current stream -> (images, labels) of this batch.
         slot None: fresh tensors (the serial generator); else the device slot to fill."""
         if self._upload_hook is not None:
@@ -601,7 +808,16 @@ class TrainingData:
                 images = src.to(dev, non_blocking=True) if self.device_tensors else arrays['images']
         else:
             packed, params = arrays['packed'], arrays['params']
-            if ring is not None:
+            if 'descs' in arrays:                # decoder='gpu': coefficients and the fallbacks' pixels up, the decode in front
+                as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.uint8)).to(dev)
+                staged, params = self._decode_sources(recipe, idx, arrays, slot, ring, as_dev(arrays['coef']), as_dev(packed))
+                if ring is not None:
+                    images, ws = ring['images'][slot][:b], ring['ws'][slot]
+                else:
+                    images = torch.empty((b, H, W, 3), dtype=torch.float32, device=dev)
+                    ws = torch.empty((lib.ssd_augment_ws_bytes(b, W, H),), dtype=torch.uint8, device=dev)
+                params = np.frombuffer(params, np.uint8)
+            elif ring is not None:
                 if ring['packed'][slot] is None or ring['packed'][slot].numel() < packed.size:
                     ring['packed'][slot] = torch.empty((max(packed.size, ring['batch'] * (self._max_image_bytes + 16)),), dtype=torch.uint8, device=dev)
                 staged = ring['packed'][slot][:packed.size]
@@ -618,7 +834,7 @@ class TrainingData:
         labels = self._labels(gts, out=ring['labels'][slot][:b] if ring is not None else None)
         return images, labels
 
-    def _upload_async(self, ring, slot_arr, arrays, gts, dslot):
+    def _upload_async(self, ring, slot_arr, arrays, gts, dslot, recipe=None, idx=None):
         """The prefetching feeder's upload: ONE host-to-device transfer of the slot's used prefix (source bytes, parameter
         records, boxes), then the augmentation and label kernels, all enqueued on torch's current stream; nothing is waited
         for.  `arrays` are views into slot_arr (pinned when the registration succeeded): the slot must stay untouched until
@@ -633,19 +849,25 @@ class TrainingData:
         base = slot_arr.ctypes.data
         offs = {k: v.ctypes.data - base for k, v in arrays.items()}
         big = 'images' if 'images' in arrays else None
-        small = [k for k in arrays if k != big]
+        small = [k for k in arrays if k != big and arrays[k].nbytes]
         lo = min(offs[k] for k in small)
         hi = max(offs[k] + arrays[k].nbytes for k in small)
         need = hi - lo
         staged = ring['packed'][dslot]
         if staged is None or staged.numel() < need:
-            cap = max(need, ring['batch'] * (getattr(self, '_max_image_bytes', 0) + 16 + 256 + 4096) + 8192)
+            per_image = max(getattr(self, '_max_image_bytes', 0), self._max_coef_bytes + 512 if self._max_coef_bytes else 0)
+            cap = max(need, ring['batch'] * (per_image + 16 + 256 + 4096) + 8192)
             staged = ring['packed'][dslot] = torch.empty((cap,), dtype=torch.uint8, device=dev)
         staged[:need].copy_(torch.from_numpy(slot_arr[lo:hi]), non_blocking=True)
         sp = staged.data_ptr() - lo
         images = ring['images'][dslot][:b]
         if big:
             images.copy_(torch.from_numpy(arrays['images']), non_blocking=True)
+        elif 'descs' in arrays:
+            part = lambda k: staged[offs[k] - lo:offs[k] - lo + arrays[k].nbytes] if arrays[k].nbytes else staged[:0]
+            src, params = self._decode_sources(recipe, idx, arrays, dslot, ring, part('coef'), part('packed'))
+            check(lib.ssd_augment_batch_dev(src.data_ptr(), C.cast(params, C.c_void_p), b, W, H, images.data_ptr(),
+                                            ring['ws'][dslot].data_ptr(), stream))
         else:
             check(lib.ssd_augment_batch_dev(sp + offs['packed'], C.c_void_p(arrays['params'].ctypes.data), b, W, H, images.data_ptr(),
                                             ring['ws'][dslot].data_ptr(), stream))
@@ -663,16 +885,23 @@ class TrainingData:
         def gen_batch(batch_size, num_workers=0):
             sampler = ShardSampler(recipe.total, batch_size, self.rank, self.world, self.seed + recipe.salt)
             batches = list(sampler.batches_with_count(self.epoch))
+            arena = self._arena if recipe.gpu_decode and self._upload_hook is None else None
+            if arena is not None:
+                import torch
+                arena.ensure(batch_size, torch.device('cuda', self.device), any(r.active for r in self._recipes.values()))
             if num_workers and num_workers > 0 and (self.device_tensors or self._upload_hook is not None):
                 yield from self._prefetched(recipe, batches, self.epoch, batch_size, int(num_workers))
                 return
+            if arena is not None:
+                self.feeder_stats.update(decoded=0, fallbacks=0, cache_hits=0)
+                recipe.stats = self.feeder_stats
             for idx, count in batches:
                 if len(idx) == 0:              # an empty shard of a short last batch: the rank still takes the step
                     self.global_count = count
                     yield None, None, []
                     continue
-                arrays, gts = recipe.plan(self.epoch, idx)
-                images, labels = self._upload(arrays, gts)
+                arrays, gts = recipe.plan(self.epoch, idx, self._known(recipe, idx) if arena is not None else None)
+                images, labels = self._upload(arrays, gts, recipe=recipe, idx=idx)
                 self.global_count = count
                 yield images, labels, gts
         return gen_batch
@@ -706,7 +935,10 @@ class TrainingData:
         for s in range(DEVICE_SLOTS):
             dev_free.put((s, None))
         cancel = threading.Event()
-        stats = self.feeder_stats = dict(consumer_wait=0.0, worker_wait=0.0, slot_wait=0.0, upload=0.0, host_slot_wait=0.0, batches=0)
+        stats = self.feeder_stats = dict(consumer_wait=0.0, worker_wait=0.0, slot_wait=0.0, upload=0.0, host_slot_wait=0.0, batches=0,
+                                         decoded=0, fallbacks=0, cache_hits=0)
+        cached = use_gpu and recipe.gpu_decode
+        recipe.stats = stats
         clock = time.perf_counter
         inflight = []          # (host slot, event behind its upload): the slot returns to the pool when the event has passed
 
@@ -733,7 +965,7 @@ class TrainingData:
                         else:
                             slot = pool.free_slots.pop()
                             pool.outstanding[(gen, next_submit)] = slot
-                            pool.tasks.put((gen, next_submit, slot, epoch, np.asarray(idx)))
+                            pool.tasks.put((gen, next_submit, slot, epoch, np.asarray(idx), self._known(recipe, idx) if cached else None))
                         next_submit += 1
                     if next_upload in done:
                         item = done.pop(next_upload)
@@ -756,14 +988,16 @@ class TrainingData:
                         if use_gpu:
                             slot_arr = pool.results.array_pool[hslot]
                             in_slot = all(isinstance(v, np.ndarray) and v.base is not None and
-                                          slot_arr.ctypes.data <= v.ctypes.data < slot_arr.ctypes.data + slot_arr.nbytes for v in arrays.values())
+                                          (v.nbytes == 0 or slot_arr.ctypes.data <= v.ctypes.data < slot_arr.ctypes.data + slot_arr.nbytes)
+                                          for v in arrays.values())
+                            idx = batches[next_upload][0]
                             with torch.cuda.stream(fstream):
                                 if released is not None:
                                     fstream.wait_event(released)
                                 if in_slot:      # enqueue and move on: the consumer's stream waits for the event, not this thread
-                                    images, labels = self._upload_async(ring, slot_arr, arrays, gts, dslot)
+                                    images, labels = self._upload_async(ring, slot_arr, arrays, gts, dslot, recipe, idx)
                                 else:            # a batch that did not fit its slot came through the pipe: the serial upload
-                                    images, labels = self._upload(arrays, gts, dslot, ring)
+                                    images, labels = self._upload(arrays, gts, dslot, ring, recipe, idx)
                                 ev = torch.cuda.Event()
                                 ev.record(fstream)
                             inflight.append((hslot, ev))

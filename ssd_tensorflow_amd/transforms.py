@@ -48,14 +48,31 @@ MAX_POST = 4         # ssd_augment_params.post_kind / post_val
 INTER_NEAREST, INTER_LINEAR, INTER_CUBIC, INTER_AREA, INTER_LANCZOS4 = 0, 1, 2, 3, 4
 
 
+class DeferredJpeg:
+    """A JPEG that is decoded later, on the GPU, into the batch's source buffer: the file's bytes and the (h, w) its
+    header states.  data None: the pixels already lie on the GPU (training_data's arena) and only the size is known here."""
+
+    def __init__(self, data, size, filename=None):
+        self.data, self.size, self.filename = data, (int(size[0]), int(size[1])), filename
+
+
 class ImagePlan:
     """Stands in for the ndarray `data` of the reference between loading and the batch kernel."""
 
     def __init__(self, image):
         """image: a uint8 [H, W, 3] BGR host array, or pixels that already lie on the GPU as a triple (uint8 device tensor, byte
-        offset of the [H][W][3] BGR image in it, (H, W)) -- what jpeg.decode_batch returns; augment_batch then uploads nothing."""
+        offset of the [H][W][3] BGR image in it, (H, W)) -- what jpeg.decode_batch returns; augment_batch then uploads nothing --
+        or a DeferredJpeg: no pixels yet, the plan knows the size alone (all a transform ever reads)."""
         self.device_src = None
-        if isinstance(image, tuple):
+        self.jpeg = None
+        if isinstance(image, DeferredJpeg):
+            h, w = image.size
+            if h < 1 or w < 1:
+                raise ValueError('a deferred JPEG needs a size, got %d x %d' % (w, h))
+            self.image = None
+            self.jpeg = image
+            self.src = Size(w, h)
+        elif isinstance(image, tuple):
             buf, off, (h, w) = image
             if str(buf.dtype) != 'torch.uint8' or not buf.is_cuda or not buf.is_contiguous():
                 raise ValueError('a device source needs a contiguous uint8 CUDA tensor')
@@ -166,16 +183,46 @@ def load_image_bgr(filename):
         return np.ascontiguousarray(np.asarray(im.convert('RGB'))[:, :, ::-1])
 
 
+DECODERS = ('pillow', 'gpu')
+
+
 class ImageLoaderTransform(Transform):
     """transforms.py:38-43 reads gt.filename with cv2.imread.  Here the pixels come from `images` (a mapping
-    filename -> uint8 BGR array) when given, else from load_image_bgr (a .npy array or a Pillow decode)."""
+    filename -> uint8 BGR array) when given, else from load_image_bgr (a .npy array or a Pillow decode).
+    decoder='gpu' (default 'pillow'): a JPEG of the class jpeg.py decodes is only READ -- once per sample: `kept` holds the last
+    file's source for the further tries of the feeder's redraw loop -- and becomes a DeferredJpeg plan; every other file
+    (unsupported JPEGs, other formats, .npy arrays) is loaded as before.  A corrupt header raises jpeg.JpegError."""
     def __call__(self, data, label, gt):
         images = getattr(self, 'images', None)
         if images is not None and gt.filename in images:
             return ImagePlan(images[gt.filename]), label, gt
         if isinstance(gt.filename, str):
+            if getattr(self, 'decoder', 'pillow') == 'gpu':
+                return ImagePlan(self._source(gt.filename)), label, gt
             return ImagePlan(load_image_bgr(gt.filename)), label, gt
         raise RuntimeError('cannot load %r' % (gt.filename,))
+
+    def _source(self, filename):
+        kept = getattr(self, 'kept', None)
+        if kept is not None and kept[0] == filename:
+            return kept[1]
+        if filename.endswith('.npy') or os.path.exists(filename + '.npy'):      # load_image_bgr's rules: an array, no file to defer
+            return load_image_bgr(filename)
+        from . import jpeg
+        with open(filename, 'rb') as f:
+            data = f.read()
+        src = None
+        if data[:2] == b'\xff\xd8':
+            try:
+                w, h, _, _, status = jpeg.info(data)
+            except jpeg.JpegError as e:
+                raise jpeg.JpegError('%s: %s' % (filename, e))
+            if status == jpeg.OK:
+                src = DeferredJpeg(data, (h, w), filename)
+        if src is None:
+            src = load_image_bgr(filename)
+        self.kept = (filename, src)
+        return src
 
 
 class LabelCreatorTransform(Transform):
@@ -488,21 +535,37 @@ def _step_val(kind, val):
     return float(val[0] + 4 * val[1] + 16 * val[2]) if kind == 4 else float(val)      # a permutation travels as a base-4 code
 
 
-def plan_params(plans, width, height):
+def plan_params(plans, width, height, src_offs=None):
     """(ctypes array of ssd_augment_params, packed uint8 image bytes) for a list of ImagePlans.  Plans whose pixels are device
-    sources must all lie in one device buffer: src_off is their offset in it and the packed array is None."""
+    sources must all lie in one device buffer: src_off is their offset in it and the packed array is None.
+    Deferred JPEGs may stand among host arrays: src_off is then an offset in the batch's source region, where the caller decodes
+    the JPEGs and copies the host arrays; `packed` holds the host arrays alone, in order, each padded to 16 bytes.  src_offs gives
+    every plan's offset; None assigns them as jpeg.decode_batch does: the deferred pictures first, the host arrays behind (in one
+    run: `packed` lies at the first host array's offset), each at a multiple of 16."""
     arr = (_Params * len(plans))()
     on_device = [getattr(p, 'device_src', None) is not None for p in plans]
+    deferred = [getattr(p, 'jpeg', None) is not None for p in plans]
     if any(on_device):
         if not all(on_device) or any(p.device_src[0] is not plans[0].device_src[0] for p in plans):
             raise ValueError('the plans of a batch must be all host arrays or all sources in ONE device buffer')
         offs, packed = [p.device_src[1] for p in plans], None
     else:
-        offs, off = [], 0
-        for p in plans:
-            offs.append(off)
-            off += (p.image.size + 15) // 16 * 16
-        packed = np.empty(off, np.uint8)
+        nbytes = [(p.src.w * p.src.h * 3 + 15) // 16 * 16 for p in plans]
+        host = [i for i in range(len(plans)) if not deferred[i]]
+        if src_offs is None:
+            offs, off = [0] * len(plans), 0
+            for i in [i for i in range(len(plans)) if deferred[i]] + host:
+                offs[i] = off
+                off += nbytes[i]
+        else:
+            offs = [int(o) for o in src_offs]
+            if len(offs) != len(plans) or any(o < 0 or o % 16 for o in offs):
+                raise ValueError('src_offs: one non-negative multiple of 16 per plan')
+        packed = np.empty(sum(nbytes[i] for i in host), np.uint8)
+        pack_at, at = {}, 0
+        for i in host:
+            pack_at[i] = at
+            at += nbytes[i]
     for i, p in enumerate(plans):
         if p.resize is None:
             raise ValueError('plan %d was not resized: the batch needs one output size (ResizeTransform last)' % i)
@@ -537,10 +600,10 @@ def plan_params(plans, width, height):
             q.post_kind[k] = kind
             q.post_val[k] = _step_val(kind, val)
         q.out_flip = int(p.out_flip)
-        if packed is not None:
-            n = p.image.size
-            packed[offs[i]:offs[i] + n] = p.image.reshape(-1)
-            packed[offs[i] + n:offs[i] + (n + 15) // 16 * 16] = 0
+        if packed is not None and not deferred[i]:
+            n, at = p.image.size, pack_at[i]
+            packed[at:at + n] = p.image.reshape(-1)
+            packed[at + n:at + (n + 15) // 16 * 16] = 0
     return arr, packed
 
 
@@ -551,6 +614,8 @@ def augment_batch(plans, width, height, device=0, out=None, return_images=False)
     sources (ImagePlan((buffer, offset, (h, w))), jpeg.decode_batch) read that buffer where it lies: nothing is uploaded but the
     parameter structs."""
     import torch
+    if any(getattr(p, 'jpeg', None) is not None for p in plans):
+        raise ValueError('augment_batch runs plans whose pixels exist; deferred JPEGs are decoded by the training feeder (training_data.py)')
     arr, packed = plan_params(plans, width, height)
     dev = torch.device('cuda', device)
     images = torch.from_numpy(packed).to(dev) if packed is not None else plans[0].device_src[0]
@@ -577,8 +642,10 @@ def build_sampler(overlap, trials):
                             min_jaccard_overlap=overlap, max_trials=trials)
 
 
-def build_train_transforms(preset, num_classes, sampler_trials, expand_prob, images=None):
+def build_train_transforms(preset, num_classes, sampler_trials, expand_prob, images=None, decoder='pillow'):
     """process_dataset.py:66-140"""
+    if decoder not in DECODERS:
+        raise ValueError("decoder must be 'pillow' or 'gpu' (got %r)" % (decoder,))
     tf_resize = ResizeTransform(width=preset.image_size.w, height=preset.image_size.h,
                                 algorithms=[INTER_LINEAR, INTER_AREA, INTER_NEAREST, INTER_CUBIC, INTER_LANCZOS4])
     tf_rnd_brightness = RandomTransform(prob=0.5, transform=BrightnessTransform(delta=32))
@@ -593,11 +660,13 @@ def build_train_transforms(preset, num_classes, sampler_trials, expand_prob, ima
     samplers = [SamplerTransform(sample=False)] + [build_sampler(o, sampler_trials) for o in (0.1, 0.3, 0.5, 0.7, 0.9, 1.0)]
     tf_sample_picker = SamplePickerTransform(samplers=samplers)
     tf_rnd_flip = RandomTransform(prob=0.5, transform=HorizontalFlipTransform())
-    return [ImageLoaderTransform(images=images), tf_rnd_brightness, tf_distort, tf_rnd_reorder_channels, tf_rnd_expand,
+    return [ImageLoaderTransform(images=images, decoder=decoder), tf_rnd_brightness, tf_distort, tf_rnd_reorder_channels, tf_rnd_expand,
             tf_sample_picker, tf_rnd_flip, LabelCreatorTransform(preset=preset, num_classes=num_classes), tf_resize]
 
 
-def build_valid_transforms(preset, num_classes, images=None):
+def build_valid_transforms(preset, num_classes, images=None, decoder='pillow'):
     """process_dataset.py:143-153"""
-    return [ImageLoaderTransform(images=images), LabelCreatorTransform(preset=preset, num_classes=num_classes),
+    if decoder not in DECODERS:
+        raise ValueError("decoder must be 'pillow' or 'gpu' (got %r)" % (decoder,))
+    return [ImageLoaderTransform(images=images, decoder=decoder), LabelCreatorTransform(preset=preset, num_classes=num_classes),
             ResizeTransform(width=preset.image_size.w, height=preset.image_size.h, algorithms=[INTER_LINEAR])]
