@@ -167,6 +167,16 @@ SIGNATURES = {
     'ssd_op_conv2d_dgrad_first_wgrad_bf16': (i32, [vp, vp, vp, vp, vp, vp, vp, f32, vp, i32, i32, i32, vp]),
     'ssd_pool_fusion': (i32, [handle, p_i32, i32, p_i32]),
     'ssd_debug_set_ablate': (i32, [cstr]),
+    'ssd_fp8_calibrate_dev': (i32, [handle, vp, i32, i32]),
+    'ssd_fp8_num_scales': (i32, [handle, p_i32]),
+    'ssd_fp8_scale_name': (i32, [handle, i32, C.c_char_p, i32]),
+    'ssd_fp8_get_scales': (i32, [handle, vp, i32]),
+    'ssd_fp8_set_scales': (i32, [handle, vp, i32]),
+    'ssd_op_quantize_fp8': (i32, [vp, i32, sz, f32, vp, vp]),
+    'ssd_op_absmax_bf16': (i32, [vp, sz, vp, i32, vp]),
+    'ssd_op_quantize_filter_fp8': (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    'ssd_op_conv2d_fwd_fp8': (i32, [vp, vp, f32, vp, vp, vp, vp, i32, f32] + [i32] * 14 + [vp]),
+    'ssd_op_maxpool_fwd_fp8': (i32, [vp, vp] + [i32] * 10 + [vp]),
     'ssd_op_maxpool_fwd': (i32, [vp, vp] + [i32] * 10 + [vp]),
     'ssd_op_maxpool_bwd': (i32, [vp, vp, vp, i32, i32] + [i32] * 10 + [vp]),
     'ssd_op_clock_monitor': (i32, [vp, i32, C.c_uint, vp]),

@@ -641,6 +641,7 @@ static int create_handle(const char* preset, int num_classes, int max_batch, int
     API_BEGIN
     SSD_REQUIRE(out != nullptr, "out handle pointer is null");
     *out = nullptr;
+    SSD_REQUIRE(!(dtype == SSD_DTYPE_FP8 && training), "SSD_DTYPE_FP8 is inference only: create the handle with training = 0");
     DeviceGuard dev_guard_(device);
     auto n = std::make_unique<Net>(preset, num_classes, max_batch, device, training != 0, seed, ext_params_dev, ext_grads_dev,
                                    ext_momentum_dev, dtype, graph);
@@ -820,6 +821,35 @@ int ssd_eval_step_dev(ssd_handle h, const float* x_dev, const float* y_dev, int 
 int ssd_infer_dev(ssd_handle h, const float* x_dev, int b) {
     API_BEGIN_NET(h)
     n.forward(x_dev, b, false, nullptr);
+    API_END
+}
+// fp8 handle: activation scales (net.hip plan_fp8)
+int ssd_fp8_calibrate_dev(ssd_handle h, const float* x_dev, int b, int accumulate) {
+    API_BEGIN_NET(h)
+    SSD_REQUIRE(x_dev != nullptr, "null argument");
+    n.fp8_calibrate(x_dev, b, accumulate != 0);
+    API_END
+}
+int ssd_fp8_num_scales(ssd_handle h, int* count) {
+    API_BEGIN_NET(h)
+    SSD_REQUIRE(count != nullptr, "null argument");
+    *count = n.fp8_num_scales();
+    API_END
+}
+int ssd_fp8_scale_name(ssd_handle h, int i, char* name, int name_cap) {
+    API_BEGIN_NET(h)
+    SSD_REQUIRE(name != nullptr && name_cap > 0, "null argument");
+    snprintf(name, name_cap, "%s", n.fp8_scale_name(i));
+    API_END
+}
+int ssd_fp8_get_scales(ssd_handle h, float* scales, int count) {
+    API_BEGIN_NET(h)
+    n.fp8_get_scales(scales, count);
+    API_END
+}
+int ssd_fp8_set_scales(ssd_handle h, const float* scales, int count) {
+    API_BEGIN_NET(h)
+    n.fp8_set_scales(scales, count);
     API_END
 }
 int ssd_result_dev(ssd_handle h, const float** result_dev) {
@@ -1180,6 +1210,40 @@ int ssd_op_conv2d_wgrad(const float* x, const float* dy, float* dw, float* dbias
     API_BEGIN
     conv_wgrad(mk(b, hi, wi, ci, ho, wo, co, kh, kw, stride, dil, pad_h, pad_w), x, dy, dw, dbias, w, weight_decay, ws,
                (hipStream_t)stream);
+    API_END
+}
+// fp8 inference kernels (conv_fp8.hip)
+int ssd_op_quantize_fp8(const void* x, int x_f32, size_t n, float scale, void* y8, void* stream) {
+    API_BEGIN
+    quantize_fp8(x, x_f32 != 0, n, scale, (unsigned char*)y8, (hipStream_t)stream);
+    API_END
+}
+int ssd_op_absmax_bf16(const void* x, size_t n, float* out_dev, int accumulate, void* stream) {
+    API_BEGIN
+    absmax_bf16((const bf16_t*)x, n, out_dev, accumulate != 0, (hipStream_t)stream);
+    API_END
+}
+int ssd_op_quantize_filter_fp8(const float* w, void* w8, float* s_w, int taps, int ci, int co, void* stream) {
+    API_BEGIN
+    SSD_REQUIRE(w && w8 && s_w && taps >= 1 && ci >= 1 && co >= 1, "quantize_filter_fp8: null argument or empty filter");
+    FilterQuantPlan plan;
+    plan.add(0, 0, 0, taps, ci, co);
+    quantize_filters_fp8(plan, w, (unsigned char*)w8, s_w, (hipStream_t)stream);
+    API_END
+}
+int ssd_op_conv2d_fwd_fp8(const void* x8, const void* w8, float s_in, const float* s_w, const float* bias, void* y, void* y8,
+                          int out_mode, float s_out, int b, int hi, int wi, int ci, int ho, int wo, int co, int kh, int kw, int stride,
+                          int dil, int pad_h, int pad_w, int relu, void* stream) {
+    API_BEGIN
+    conv_fwd_fp8(mk(b, hi, wi, ci, ho, wo, co, kh, kw, stride, dil, pad_h, pad_w), (const unsigned char*)x8, (const unsigned char*)w8, s_in,
+                 s_w, bias, y, (unsigned char*)y8, out_mode, s_out, relu != 0, (hipStream_t)stream);
+    API_END
+}
+int ssd_op_maxpool_fwd_fp8(const void* x8, void* y8, int b, int hi, int wi, int c, int ho, int wo, int k, int stride, int pad_h,
+                           int pad_w, void* stream) {
+    API_BEGIN
+    PoolDesc d{b, hi, wi, c, ho, wo, k, stride, pad_h, pad_w};
+    maxpool_fwd_fp8(d, (const unsigned char*)x8, (unsigned char*)y8, (hipStream_t)stream);
     API_END
 }
 int ssd_op_maxpool_fwd(const float* x, float* y, int b, int hi, int wi, int c, int ho, int wo, int k, int stride, int pad_h,

@@ -208,4 +208,35 @@ struct WgradGroupItem {
 int conv_wgrad_group_bf16_max();
 void conv_wgrad_group_bf16(const WgradGroupItem* items, int n, float weight_decay, hipStream_t s);
 
+// ---- fp8 inference kernels (conv_fp8.hip): OCP e4m3fn codes, one fp32 scale per activation tensor and per output channel ----
+// code = RNE(clamp(v / s, -448, 448)); y = relu?(acc * (s_in * s_w[co]) + bias[co]) in fp32, then one of the output forms.
+enum { FP8_OUT_BF16 = 0, FP8_OUT_F32 = 1, FP8_OUT_E4M3 = 2, FP8_OUT_BF16_E4M3 = 3 };
+// KH * KW <= 9, Ci a multiple of 64, Co a multiple of 8, any stride / dilation / leading padding; why (optional) = the reason text
+bool conv_fwd_fp8_supported(const ConvDesc& d, const char** why);
+// the shapes on which the step executor prefers this kernel to conv_fwd_bf16 (Ci >= 256; measured: conv_fp8.hip)
+bool conv_fwd_fp8_worthwhile(const ConvDesc& d);
+// x8 [B,Hi,Wi,Ci] and w8 [tap][Co][Ci] e4m3; y: bf16 or fp32 [B,Ho,Wo,Co] (unused by FP8_OUT_E4M3), y8: e4m3 at scale s_out
+// (FP8_OUT_E4M3 and FP8_OUT_BF16_E4M3).  Anything unsupported throws before a launch.
+void conv_fwd_fp8(const ConvDesc& d, const unsigned char* x8, const unsigned char* w8, float s_in, const float* s_w, const float* bias,
+                  void* y, unsigned char* y8, int out_mode, float s_out, bool relu, hipStream_t s);
+// One launch quantises every listed layer's fp32 filter [tap][Ci][Co] (element offset off in w) into its e4m3 image
+// [tap][Co][Ci] (byte offset off8 in w8) with s_w[offs + co] = absmax_co / 448 (1 for an all-zero channel).
+struct FilterQuantPlan {
+    static constexpr int MAX_LAYERS = 48;
+    struct Layer {
+        size_t off, off8, offs;
+        int taps, ci, co;
+    } L[MAX_LAYERS];
+    int n = 0;
+    void add(size_t off, size_t off8, size_t offs, int taps, int ci, int co);
+};
+void quantize_filters_fp8(const FilterQuantPlan& plan, const float* w, unsigned char* w8, float* s_w, hipStream_t s);
+// n values, bf16 or fp32 -> e4m3 at one scale
+void quantize_fp8(const void* x, bool x_f32, size_t n, float scale, unsigned char* y8, hipStream_t s);
+// *out = max(|x|) over the finite values (accumulate: the maximum with what *out holds); the reduction of calibration
+void absmax_bf16(const bf16_t* x, size_t n, float* out, bool accumulate, hipStream_t s);
+struct PoolDesc;
+// max-pooling on e4m3 codes of either sign; C a multiple of 16; cells outside the image never win
+void maxpool_fwd_fp8(const PoolDesc& d, const unsigned char* x8, unsigned char* y8, hipStream_t s);
+
 }  // namespace ssd

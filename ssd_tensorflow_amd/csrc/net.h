@@ -27,6 +27,11 @@ struct Tensor {
     bool grad_f32 = true;    // storage of grad
     void* data = nullptr;
     void* grad = nullptr;
+    // fp8 handle (net.hip plan_fp8): the tensor's e4m3 image for its fp8 readers and its scale; wants16: it also has a reader
+    // that takes the bf16 form
+    unsigned char* data8 = nullptr;
+    float scale = 0.f;
+    bool wants16 = true;
     size_t per_image() const { return (size_t)H * W * C; }
     const float* f() const { return static_cast<const float*>(data); }
     float* gf() const { return static_cast<float*>(grad); }
@@ -54,6 +59,10 @@ struct Op {
     int pool_after = -1, unpool = -1;
     // head op: index of the feature map, else -1
     int head = -1;
+    // fp8 handle (net.hip plan_fp8): a convolution that runs on conv_fwd_fp8 / a pool that runs on e4m3 bytes; sw_off = the
+    // layer's per-channel filter scales
+    bool fp8 = false;
+    size_t sw_off = 0;
     // Round 6 (fp32): the Winograd F(4x4, 3x3) form of this layer's passes (net.hip plan_winograd; conv.h wino_*): forward, data
     // gradient, weight gradient; the layer's filter transforms [36][Ci][Co] / [36][Co][Ci] and its input's transform [36][tiles][Ci]
     // (written by forward, read by the weight gradient)
@@ -85,7 +94,8 @@ struct DetectSlot {
 class Net {
 public:
     // dtype 0: fp32 everywhere (BASELINE.json configs[1]); 1: bf16 activations / gradients / filter mirrors with fp32
-    // master weights, fp32 accumulation and fp32 loss (configs[2])
+    // master weights, fp32 accumulation and fp32 loss (configs[2]); 2: fp8, an inference-only bf16 handle whose eligible
+    // trunk convolutions (conv3_2 ... mod_conv7) run on e4m3 operands (plan_fp8)
     Net(const char* preset, int num_classes, int max_batch, int device, bool training, unsigned long long seed,
         float* ext_params, float* ext_grads, float* ext_momentum, int dtype = 0, int graph = 0);
     ~Net();
@@ -145,7 +155,13 @@ public:
     int nvars() const { return C_ + 5; }
     int max_batch() const { return Bmax_; }
     bool training() const { return training_; }
-    int dtype() const { return bf16_ ? 1 : 0; }
+    int dtype() const { return fp8_ ? 2 : bf16_ ? 1 : 0; }
+    // fp8 handle: one scale per tensor that a convolution writes as e4m3, in graph order
+    void fp8_calibrate(const float* x_dev, int b, bool accumulate);      // the graph on the bf16 kernels; scale = max(absmax, tiny) / 448
+    int fp8_num_scales() const;
+    const char* fp8_scale_name(int i) const;
+    void fp8_get_scales(float* out, int n) const;
+    void fp8_set_scales(const float* v, int n);
     int graph() const { return fc_ ? 1 : 0; }
     int device() const { return device_; }
     float* params() { return params_; }
@@ -172,6 +188,17 @@ private:
     bool training_;
     bool bf16_ = false;
     bool fc_ = false;                      // the fc graph (arena_floats)
+    // fp8 handle: e4m3 filter images [tap][Co][Ci] at the filters' arena offsets + per-channel scales, refreshed from the
+    // fp32 masters by every forward pass like the bf16 mirrors (one launch, behind cast_filters)
+    bool fp8_ = false;
+    bool fp8_calibrated_ = false, fp8_as_bf16_ = false;      // fp8_as_bf16_: this pass is the calibration run
+    unsigned char* w8_ = nullptr;
+    float *sw8_ = nullptr, *absmax8_ = nullptr;
+    FilterQuantPlan quant_plan_;
+    std::vector<int> fp8_scaled_;          // the tensors that own a scale (pool outputs share their input's)
+    void plan_fp8();
+    void fp8_share_pool_scales();
+    void require_fp8() const;
     bf16_t *wq_io_ = nullptr, *wq_oi_ = nullptr;     // bf16 mirrors of the filter region: [tap][Ci][Co] and [tap][Co][Ci]
     FilterCastPlan cast_plan_;
     hipStream_t stream_ = nullptr;

@@ -334,6 +334,7 @@ void Net::plan_pool_fusion() {
         }
         if (prod < 0 || cons < 0 || ops_[prod].kind != OP_CONV || ops_[cons].kind != OP_CONV) continue;
         if (!ops_[prod].relu || ops_[prod].head >= 0) continue;
+        if (pl.fp8 || ops_[prod].fp8) continue;      // (fp8 handle: a pool on e4m3 bytes / behind an fp8 layer is a launch of its own)
         const ConvDesc dp = conv_desc(ops_[prod], Bmax_), dc = conv_desc(ops_[cons], Bmax_);
         const bool in_bf16 = bf16_ && !tensors_[ops_[prod].in].data_f32;
         if ((mode & 1) && (bf16_ ? (in_bf16 && conv_fwd_pool_bf16_supported(dp)) : conv_fwd_pool_supported(dp))) {
@@ -577,6 +578,129 @@ void Net::plan_winograd() {
     }
 }
 
+// fp8 handle.  Eligible: a trunk convolution in front of conv8_1 (no multibox head, not in the tail chain) that is not conv_bigk,
+// reads an activation (not the image), has Ci % 64 == 0 and is of a shape on which the fp8 kernel measured faster than the bf16 one
+// (conv_fwd_fp8_worthwhile) -- a-trous graph: conv3_2 ... conv5_3, mod_conv6, mod_conv7.  A tensor read by such a layer is kept as
+// e4m3 (data8).  A pool between two fp8 layers runs on the bytes and its output shares its input's scale.  Where the e4m3 form is
+// needed behind a bf16 producer (conv3_1's output in the a-trous graph) a quantise pass of its own makes it.  A tensor with any non-fp8 reader (conv4_3: the l2 norm; mod_conv7's output: its head and conv8_1) keeps its
+// bf16 form as well (wants16).  Runs before plan_pool_fusion, which leaves the fp8 layers' pools alone.
+void Net::plan_fp8() {
+    size_t nsw = 0;
+    for (Tensor& t : tensors_) t.wants16 = false;
+    std::vector<int> producer(tensors_.size(), -1);
+    for (int i = 0; i < (int)ops_.size(); ++i) {
+        Op& op = ops_[i];
+        producer[op.out] = i;
+        if (op.kind != OP_CONV) continue;
+        const ConvDesc d = conv_desc(op, Bmax_);
+        op.fp8 = op.head < 0 && i < tail_first_ && !conv_bigk(d) && !tensors_[op.in].data_f32 && conv_fwd_fp8_supported(d, nullptr) &&
+                 conv_fwd_fp8_worthwhile(d);
+    }
+    auto need8 = [&](Tensor& t) {
+        if (!t.data8) t.data8 = static_cast<unsigned char*>(hip_.mem(t.per_image() * Bmax_));
+    };
+    for (int i = (int)ops_.size() - 1; i >= 0; --i) {      // readers before their producers: a pool learns from its consumer
+        Op& op = ops_[i];
+        Tensor& in = tensors_[op.in];
+        Tensor& out = tensors_[op.out];
+        if (op.kind == OP_POOL) {
+            const int prod = producer[op.in];
+            op.fp8 = out.data8 != nullptr && prod >= 0 && ops_[prod].kind == OP_CONV && ops_[prod].fp8;
+            if (op.fp8) {
+                need8(in);
+                if (out.wants16) in.wants16 = true;      // the bf16 pool beside it needs its bf16 input
+            } else {
+                in.wants16 = true;
+            }
+        } else if (op.kind == OP_CONV && op.fp8) {
+            need8(in);
+        } else {
+            in.wants16 = true;
+        }
+    }
+    for (int t : head_t_) tensors_[t].wants16 = true;      // (fp32, read by the loss / result pass)
+    for (Op& op : ops_) {
+        if (op.kind == OP_CONV && op.fp8) {
+            const Tensor& in = tensors_[op.in];
+            const Tensor& out = tensors_[op.out];
+            op.sw_off = nsw;
+            quant_plan_.add(op.w_off, op.w_off, nsw, op.KH * op.KW, in.C, out.C);
+            nsw += out.C;
+        }
+        Tensor& out = tensors_[op.out];
+        if (!out.data8) continue;
+        if (!op.fp8) out.wants16 = true;      // a bf16 op writes bf16; the quantise pass behind it makes the e4m3 form
+        if (!(op.kind == OP_POOL && op.fp8)) fp8_scaled_.push_back(op.out);
+    }
+    SSD_REQUIRE(!fp8_scaled_.empty(), "no layer of this graph is eligible for fp8");
+    w8_ = static_cast<unsigned char*>(hip_.mem(nfilters_));
+    sw8_ = static_cast<float*>(hip_.mem(nsw * sizeof(float)));
+    absmax8_ = static_cast<float*>(hip_.mem(fp8_scaled_.size() * sizeof(float)));
+}
+
+void Net::require_fp8() const { SSD_REQUIRE(fp8_, "not an fp8 handle (SSD_DTYPE_FP8)"); }
+
+void Net::fp8_share_pool_scales() {
+    for (const Op& op : ops_)      // graph order: a pool comes behind its input's producer
+        if (op.kind == OP_POOL && op.fp8) tensors_[op.out].scale = tensors_[op.in].scale;
+}
+
+int Net::fp8_num_scales() const {
+    require_fp8();
+    return (int)fp8_scaled_.size();
+}
+
+const char* Net::fp8_scale_name(int i) const {
+    require_fp8();
+    SSD_REQUIRE(i >= 0 && i < (int)fp8_scaled_.size(), "fp8 scale index %d outside 0..%zu", i, fp8_scaled_.size() - 1);
+    return tensors_[fp8_scaled_[i]].name.c_str();
+}
+
+void Net::fp8_get_scales(float* out, int n) const {
+    require_fp8();
+    SSD_REQUIRE(out && n == (int)fp8_scaled_.size(), "the handle has %zu fp8 scales, got room for %d", fp8_scaled_.size(), n);
+    for (int i = 0; i < n; ++i) out[i] = tensors_[fp8_scaled_[i]].scale;
+}
+
+void Net::fp8_set_scales(const float* v, int n) {
+    require_fp8();
+    SSD_REQUIRE(v && n == (int)fp8_scaled_.size(), "the handle has %zu fp8 scales, got %d", fp8_scaled_.size(), n);
+    for (int i = 0; i < n; ++i)
+        SSD_REQUIRE(v[i] > 0.f && v[i] < INFINITY, "fp8 scale %d (%s) must be positive and finite, got %g", i, fp8_scale_name(i), (double)v[i]);
+    HIP_OK(hipStreamSynchronize(stream_));      // (no pass in flight reads a scale: they travel as kernel arguments; this orders the caller's view)
+    for (int i = 0; i < n; ++i) tensors_[fp8_scaled_[i]].scale = v[i];
+    fp8_share_pool_scales();
+    fp8_calibrated_ = true;
+}
+
+// The handle's graph on the bf16 kernels, then the absmax of every scaled tensor's bf16 form: scale = max(absmax, tiny) / 448,
+// with `accumulate` the larger of that and the scale already there.
+void Net::fp8_calibrate(const float* x_dev, int b, bool accumulate) {
+    require_fp8();
+    struct Scope {
+        bool& f;
+        Scope(bool& f_) : f(f_) { f = true; }
+        ~Scope() { f = false; }
+    } scope(fp8_as_bf16_);
+    forward(x_dev, b, false, nullptr);
+    const int n = (int)fp8_scaled_.size();
+    for (int i = 0; i < n; ++i) {
+        const Tensor& t = tensors_[fp8_scaled_[i]];
+        absmax_bf16(t.h(), (size_t)b * t.per_image(), absmax8_ + i, false, stream_);
+    }
+    std::vector<float> am(n);
+    HIP_OK(hipMemcpyAsync(am.data(), absmax8_, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    HIP_OK(hipStreamSynchronize(stream_));
+    constexpr float tiny = 1e-20f;
+    for (int i = 0; i < n; ++i) {
+        Tensor& t = tensors_[fp8_scaled_[i]];
+        const float s = std::max(am[i], tiny) / 448.0f;
+        t.scale = (accumulate && fp8_calibrated_) ? std::max(t.scale, s) : s;
+    }
+    fp8_share_pool_scales();
+    fp8_calibrated_ = true;
+}
+
 void Net::pool_fusion(int* out, int cap, int* count) const {
     int k = 0;
     for (const Op& op : ops_)
@@ -729,9 +853,10 @@ void Net::init_weights(unsigned long long seed) {
 
 Net::Net(const char* preset, int num_classes, int max_batch, int device, bool training, unsigned long long seed,
          float* ext_params, float* ext_grads, float* ext_momentum, int dtype, int graph)
-    : preset_(&get_preset(preset)), C_(num_classes), Bmax_(max_batch), device_(device), training_(training), bf16_(dtype == 1),
-      fc_(graph == 1), hip_(device) {
-    SSD_REQUIRE(dtype == 0 || dtype == 1, "dtype must be 0 (fp32) or 1 (bf16), got %d", dtype);
+    : preset_(&get_preset(preset)), C_(num_classes), Bmax_(max_batch), device_(device), training_(training), bf16_(dtype == 1 || dtype == 2),
+      fc_(graph == 1), fp8_(dtype == 2), hip_(device) {
+    SSD_REQUIRE(dtype >= 0 && dtype <= 2, "dtype must be 0 (fp32), 1 (bf16) or 2 (fp8), got %d", dtype);
+    SSD_REQUIRE(!(fp8_ && training), "SSD_DTYPE_FP8 is inference only: create the handle with training = 0");
     SSD_REQUIRE(graph == 0 || graph == 1, "graph must be 0 (a-trous) or 1 (fc), got %d", graph);
     require_num_classes(num_classes);
     SSD_REQUIRE(max_batch >= 1, "max_batch must be >= 1");
@@ -766,6 +891,7 @@ Net::Net(const char* preset, int num_classes, int max_batch, int device, bool tr
     // streams beside the caller's measure the same as four (bf16 4142 vs 4081 images/s, r02_w) and leave the fourth queue to
     // a data-parallel caller's collective stream.
     s2_ = training_ ? wstream_ : hip_.stream();
+    if (fp8_) plan_fp8();
     plan_pool_fusion();
     plan_tail_chain();
     plan_winograd();
@@ -793,6 +919,9 @@ Net::~Net() {
 // reduction, which the last per-sample workgroup of either lane performs (ops.hip).
 void Net::forward(const float* x, int b, bool train_mode, const float* y) {
     SSD_REQUIRE(b >= 1 && b <= Bmax_, "batch %d outside 1..%d (max_batch)", b, Bmax_);
+    SSD_REQUIRE(!fp8_ || fp8_as_bf16_ || fp8_calibrated_,
+                "the fp8 handle has no activation scales yet: call ssd_fp8_calibrate_dev or ssd_fp8_set_scales before inference");
+    const bool run8 = fp8_ && !fp8_as_bf16_;      // this pass runs the fp8 layers on e4m3 operands (the calibration pass does not)
     g_prof = &prof_;
     tensors_[input_t_].data = const_cast<float*>(x);
     pool_arg_op_ = -1;
@@ -850,6 +979,8 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
         // the fp32 master itself); the first layer that reads a mirror waits for it
         prof_.layer = "filters";
         cast_filters(cast_plan_, params_, wq_io_, wq_oi_, side ? hstream_ : stream_);
+        // ... and the e4m3 filter images with their per-channel scales, under the same rule (one more launch)
+        if (run8) quantize_filters_fp8(quant_plan_, params_, w8_, sw8_, side ? hstream_ : stream_);
         if (chain_first_ >= 0) pack_tail_filters(side ? hstream_ : stream_);
         if (side) {
             HIP_OK(hipEventRecord(ev_cast_, hstream_));
@@ -991,6 +1122,8 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
                     else
                         conv_fwd_pool_bf16(d, reinterpret_cast<const bf16_t*>(xin), wq_oi_ + op.w_off, params_ + op.b_off,
                                            reinterpret_cast<bf16_t*>(at(pt, run_b0)), rec, cs);
+                    if (run8 && pt.data8)      // the pooled tensor feeds an fp8 layer: the boundary's quantise pass
+                        quantize_fp8(at(pt, run_b0), false, (size_t)run_nb * pt.per_image(), pt.scale, pt.data8 + (size_t)run_b0 * pt.per_image(), cs);
                     break;
                 }
                 // a feature map's producer carries the event its head waits for (common.h g_stop_event; backward_step does the same)
@@ -1009,8 +1142,15 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
                     conv_first_fwd_bf16(d, xin, params_ + op.w_off, params_ + op.b_off, static_cast<bf16_t*>(yout), op.relu, cs);
                 else if (in.data_f32)
                     conv_fwd_smallc_bf16out(d, xin, params_ + op.w_off, params_ + op.b_off, static_cast<bf16_t*>(yout), op.relu, cs);
+                else if (run8 && op.fp8)      // e4m3 operands; the output in the form(s) its readers take
+                    conv_fwd_fp8(d, in.data8 + (size_t)run_b0 * in.per_image(), w8_ + op.w_off, in.scale, sw8_ + op.sw_off, params_ + op.b_off, yout,
+                                 out.data8 ? out.data8 + (size_t)run_b0 * out.per_image() : nullptr,
+                                 out.data8 ? (out.wants16 ? FP8_OUT_BF16_E4M3 : FP8_OUT_E4M3) : FP8_OUT_BF16, out.scale, op.relu, cs);
                 else
                     conv_fwd_bf16(d, reinterpret_cast<const bf16_t*>(xin), wq_oi_ + op.w_off, params_ + op.b_off, yout, out.data_f32, op.relu, cs);
+                // a bf16 layer in front of an fp8 one: a boundary with a quantise pass of its own
+                if (run8 && out.data8 && !op.fp8)
+                    quantize_fp8(yout, false, (size_t)run_nb * out.per_image(), out.scale, out.data8 + (size_t)run_b0 * out.per_image(), cs);
                 break;
             }
             case OP_POOL: {
@@ -1026,8 +1166,14 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
                     if (bf16_) maxpool_fwd_arg(d, reinterpret_cast<const bf16_t*>(at(in, ln.b0)), reinterpret_cast<bf16_t*>(at(out, ln.b0)), arg, ln.s);
                     else maxpool_fwd_arg(d, reinterpret_cast<const float*>(at(in, ln.b0)), reinterpret_cast<float*>(at(out, ln.b0)), arg, ln.s);
                     pool_arg_op_ = op_index;
-                } else if (bf16_) maxpool_fwd(d, reinterpret_cast<const bf16_t*>(at(in, ln.b0)), reinterpret_cast<bf16_t*>(at(out, ln.b0)), ln.s);
-                else maxpool_fwd(d, reinterpret_cast<const float*>(at(in, ln.b0)), reinterpret_cast<float*>(at(out, ln.b0)), ln.s);
+                } else if (run8 && op.fp8) {      // on e4m3 bytes (the output shares the input's scale); bf16 as well where someone reads that
+                    maxpool_fwd_fp8(d, in.data8 + (size_t)ln.b0 * in.per_image(), out.data8 + (size_t)ln.b0 * out.per_image(), ln.s);
+                    if (out.wants16) maxpool_fwd(d, reinterpret_cast<const bf16_t*>(at(in, ln.b0)), reinterpret_cast<bf16_t*>(at(out, ln.b0)), ln.s);
+                } else if (bf16_) {
+                    maxpool_fwd(d, reinterpret_cast<const bf16_t*>(at(in, ln.b0)), reinterpret_cast<bf16_t*>(at(out, ln.b0)), ln.s);
+                    if (run8 && out.data8)      // a bf16 pool in front of an fp8 layer
+                        quantize_fp8(at(out, ln.b0), false, (size_t)nb * out.per_image(), out.scale, out.data8 + (size_t)ln.b0 * out.per_image(), ln.s);
+                } else maxpool_fwd(d, reinterpret_cast<const float*>(at(in, ln.b0)), reinterpret_cast<float*>(at(out, ln.b0)), ln.s);
                 break;
             }
             case OP_L2NORM:
@@ -1479,7 +1625,7 @@ void Net::save_variable(const char* name, float* host, size_t count, int which) 
 }
 
 void Net::activation_shape(const char* name, int* H, int* W, int* C) const {
-    if (name && !strncmp(name, "grad:", 5)) name += 5;
+    if (name && (!strncmp(name, "grad:", 5) || !strncmp(name, "bf16:", 5))) name += 5;
     for (const Tensor& t : tensors_)
         if (t.name == name) {
             *H = t.H; *W = t.W; *C = t.C;
@@ -1490,8 +1636,12 @@ void Net::activation_shape(const char* name, int* H, int* W, int* C) const {
 
 void Net::activation(const char* name, int b, float* out, size_t count) {
     // "grad:<scope>" returns d(loss)/d(pre-activation) of that layer from the last backward
+    // "bf16:<scope>" (fp8 handle) returns the bf16 form of a tensor that is also kept as e4m3 (the default for such a tensor
+    // is its dequantised e4m3 form)
     const bool want_grad = name && !strncmp(name, "grad:", 5);
     if (want_grad) name += 5;
+    const bool want_bf16 = name && !strncmp(name, "bf16:", 5);
+    if (want_bf16) name += 5;
     for (size_t ti = 0; ti < tensors_.size(); ++ti) {
         const Tensor& t = tensors_[ti];
         if (t.name != name || !t.data) continue;
@@ -1508,6 +1658,17 @@ void Net::activation(const char* name, int b, float* out, size_t count) {
                     count);
         const void* src = want_grad ? t.grad : t.data;
         HIP_OK(hipStreamSynchronize(stream_));
+        if (t.data8 && !want_grad && !want_bf16) {      // an fp8 tensor: its codes times its scale (exact in fp32)
+            std::vector<unsigned char> hc(count);
+            HIP_OK(hipMemcpy(hc.data(), t.data8, count, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < count; ++i) {
+                const int c = hc[i], e = (c >> 3) & 15, m = c & 7;
+                const float v = (e == 15 && m == 7) ? NAN : e == 0 ? ldexpf((float)m, -9) : ldexpf(1.f + m / 8.f, e - 7);
+                out[i] = (c & 0x80 ? -v : v) * t.scale;
+            }
+            return;
+        }
+        SSD_REQUIRE(!(fp8_ && !want_grad && !t.wants16), "activation %s of the fp8 handle has no bf16 form", name);
         if (want_grad ? t.grad_f32 : t.data_f32) {
             HIP_OK(hipMemcpy(out, src, count * sizeof(float), hipMemcpyDeviceToHost));
         } else {        // bf16 storage: widen on the host (exact)

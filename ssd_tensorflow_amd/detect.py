@@ -11,7 +11,7 @@ import sys
 import numpy as np
 
 from .annotate import Style, write_image, GpuJpegWriter
-from .infer import sample_generator, resolve_class_names
+from .infer import sample_generator, resolve_class_names, add_fp8_arguments, fp8_batches
 from .ssdvgg import SSDVGG, Session
 from .ssdutils import get_preset_by_name, boxes_from_detection
 from .utils import default_colors
@@ -24,7 +24,9 @@ def main(argv=None):
     parser.add_argument('--training-data', default='', help='unused: the checkpoint carries the preset and the class names')
     parser.add_argument('--output-dir', default='test-out', help='output directory')
     parser.add_argument('--batch-size', type=int, default=32, help='batch size')
-    parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='f32, or bf16 activations on the bf16 matrix cores')
+    parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16', 'fp8'],
+                        help='f32, bf16 activations on the bf16 matrix cores, or fp8: the bf16 net with conv3_2 ... mod_conv7 on e4m3 operands')
+    add_fp8_arguments(parser)
     parser.add_argument('--decoder', default='gpu', choices=['pillow', 'gpu'],
                         help='gpu: baseline JPEGs are decoded on the GPU, other files as with pillow (same pixels); pillow: every file is decoded on the host')
     parser.add_argument('--decoder-entropy', default='host', choices=['host', 'gpu'],
@@ -73,8 +75,9 @@ def main(argv=None):
                     write_image(os.path.join(args.output_dir, name), images[i])
 
         pending = None
-        for x, idxs, sizes, sources in sample_generator(files, net.preset.image_size, args.batch_size, with_sources=True, decoder=args.decoder,
-                                                         decoder_entropy=args.decoder_entropy):
+        for x, idxs, sizes, sources in fp8_batches(net, sample_generator(files, net.preset.image_size, args.batch_size, with_sources=True,
+                                                                          decoder=args.decoder, decoder_entropy=args.decoder_entropy),
+                                                   args.fp8_calibration, args.fp8_calibrate_images):
             net.infer_dev(x)
             ticket = net.detect_last_launch(x.shape[0], 0.5, None, 200)                      # detect.py:111-112
             if writer is not None:

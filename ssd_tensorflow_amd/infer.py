@@ -101,6 +101,46 @@ def sample_generator(samples, image_size, batch_size, device=0, with_sources=Fal
             yield x, idxs, sizes
 
 
+def add_fp8_arguments(parser):
+    """--fp8-calibration / --fp8-calibrate-images of the deployment tools (their --dtype fp8)"""
+    parser.add_argument('--fp8-calibration', default=None, metavar='FILE.npz',
+                        help='--dtype fp8: activation scales; loaded if the file exists, else written after calibrating on the first inputs')
+    parser.add_argument('--fp8-calibrate-images', type=int, default=32,
+                        help='--dtype fp8 without stored scales: this many of the first inputs calibrate the net before the first inference')
+
+
+def fp8_batches(net, batches, calibration_file=None, calibrate_images=32):
+    """The batches of sample_generator, unchanged, for a net that is not fp8.  For an fp8 net the scales are in place before the
+    first batch is handed on: from calibration_file if it exists, else from the first calibrate_images inputs (whole batches
+    are held back for that and handed on afterwards, so every input is still inferred), written to calibration_file if given."""
+    if getattr(net, 'dtype', None) != 'fp8':
+        yield from batches
+        return
+    if calibration_file and os.path.exists(calibration_file):
+        with np.load(calibration_file, allow_pickle=False) as f:
+            net.fp8_scales = {k: float(f[k]) for k in f.files}
+        print('[i] fp8 scales:         loaded from', calibration_file)
+        yield from batches
+        return
+    held, seen = [], 0
+    batches = iter(batches)
+    for batch in batches:
+        take = min(batch[0].shape[0], max(int(calibrate_images), 1) - seen)
+        net.calibrate_fp8(batch[0][:take], accumulate=seen > 0)
+        held.append(batch)
+        seen += take
+        if seen >= calibrate_images:
+            break
+    if not held:
+        return
+    print('[i] fp8 scales:         calibrated on the first', seen, 'inputs')
+    if calibration_file:
+        with open(calibration_file, 'wb') as f:      # (a file object: numpy leaves the name as given)
+            np.savez(f, **net.fp8_scales)
+    yield from held
+    yield from batches
+
+
 def resolve_class_names(num_classes, source_names=None, stored=None):
     """{class id: name}: the data source's names, else the checkpoint's __class_names__, else (a checkpoint written before
     names were stored, or no checkpoint) the VOC names for 20 classes and 'class_<id>' otherwise."""
@@ -131,7 +171,9 @@ def main(argv=None):
     parser.add_argument('--preset', default=None, help='preset when no checkpoint is given (random weights)')
     parser.add_argument('--num-classes', type=int, default=20, help='class count when no checkpoint is given (1..127)')
     parser.add_argument('--a-trous', type=str2bool, default='True', help='graph when no checkpoint is given: a-trous (true) or fc (false); a checkpoint carries its own')
-    parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='f32, or bf16 activations on the bf16 matrix cores')
+    parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16', 'fp8'],
+                        help='f32, bf16 activations on the bf16 matrix cores, or fp8: the bf16 net with conv3_2 ... mod_conv7 on e4m3 operands')
+    add_fp8_arguments(parser)
     parser.add_argument('--decoder', default='gpu', choices=['pillow', 'gpu'],
                         help='gpu: baseline JPEGs are decoded on the GPU, other files as with pillow (same pixels); pillow: every file is decoded on the host')
     parser.add_argument('--decoder-entropy', default='host', choices=['host', 'gpu'],
@@ -263,8 +305,8 @@ def main(argv=None):
                     pascal_summary.add_detections(name_of(idxs[i]), boxes, img_size=sizes[i])
 
         pending = None
-        for batch in sample_generator(files, size, args.batch_size, with_sources=style is not None, decoder=args.decoder,
-                                      decoder_entropy=args.decoder_entropy):
+        for batch in fp8_batches(net, sample_generator(files, size, args.batch_size, with_sources=style is not None, decoder=args.decoder,
+                                                       decoder_entropy=args.decoder_entropy), args.fp8_calibration, args.fp8_calibrate_images):
             x, idxs, sizes = batch[:3]
             net.infer_dev(x)                                                                 # infer.py:225-227
             ticket = net.detect_last_launch(x.shape[0], args.threshold, None, 200)

@@ -171,7 +171,8 @@ class SSDVGG:
         """ssdvgg.py:96-118.  There is no vgg.zip offline: the VGG-16 trunk starts from
         Xavier-uniform synthetic weights (seed) unless `weights` ({tf_name: array}) or
         `<vgg_dir>/vgg16_ssd.npz` supplies them.  dtype 'f32' (default) or 'bf16' (bf16 activations and
-        filter mirrors on the bf16 matrix cores; fp32 master weights, loss and optimizer).
+        filter mirrors on the bf16 matrix cores; fp32 master weights, loss and optimizer), or -- training=False only --
+        'fp8': the bf16 net with conv3_2 ... mod_conv7 on e4m3 operands; call calibrate_fp8 or set fp8_scales before infer.
         a_trous=False builds the reference's other graph (ssdvgg.py:210-228): VGG-16's fc6 / fc7 as a 7x7 and a
         1x1 convolution, 4096 wide, variables fc6/* and fc7/*; its weights come from `<vgg_dir>/vgg16_ssd_fc.npz`."""
         self.num_classes = num_classes + 1
@@ -199,8 +200,10 @@ class SSDVGG:
 
     def _create(self, num_classes, max_batch, training, seed, dtype='f32', a_trous=True):
         import torch
-        if dtype not in ('f32', 'bf16'):
-            raise ValueError("dtype must be 'f32' or 'bf16', got %r" % (dtype,))
+        if dtype not in ('f32', 'bf16', 'fp8'):
+            raise ValueError("dtype must be 'f32', 'bf16' or 'fp8', got %r" % (dtype,))
+        if dtype == 'fp8' and training:
+            raise ValueError("dtype 'fp8' is inference only: build with training=False")
         self.dtype = dtype
         dev = self.session.device if self.session is not None else 0
         self.device = dev
@@ -220,7 +223,7 @@ class SSDVGG:
                                    self.params_flat.data_ptr(),
                                    self.grads_flat.data_ptr() if training else None,
                                    self.momentum_flat.data_ptr() if training else None,
-                                   1 if dtype == 'bf16' else 0, graph, C.byref(h)))
+                                   {'f32': 0, 'bf16': 1, 'fp8': 2}[dtype], graph, C.byref(h)))
         self._h = h
         fl = C.c_size_t(); ff = C.c_size_t()
         check(lib.ssd_arenas(h, None, None, None, C.byref(fl), C.byref(ff)))
@@ -428,6 +431,46 @@ class SSDVGG:
         res = np.empty((x.shape[0], self.preset.num_anchors, self.num_vars), np.float32)
         check(lib.ssd_infer(self._h, np_ptr(x), x.shape[0], np_ptr(res)))
         return res
+
+    # ------------------------------------------------------------------ fp8 inference (dtype='fp8')
+    def calibrate_fp8(self, x, accumulate=False):
+        """Set the fp8 activation scales from a batch (numpy or a torch tensor on this net's GPU): the graph runs once on the
+        bf16 kernels and every e4m3 tensor gets scale = max(absmax, tiny) / 448; accumulate=True keeps the larger of that and
+        the scale already there (several calibration batches)."""
+        import torch
+        if self._is_cuda(x):
+            x, _ = self._dev_xy(x, None)
+        else:
+            x = torch.from_numpy(self._check_x(x)).to(torch.device('cuda', self.device))
+        check(lib.ssd_fp8_calibrate_dev(self._h, x.data_ptr(), x.shape[0], int(bool(accumulate))))
+
+    def _fp8_names(self):
+        n = C.c_int()
+        check(lib.ssd_fp8_num_scales(self._h, C.byref(n)))
+        names = []
+        for i in range(n.value):
+            buf = C.create_string_buffer(128)
+            check(lib.ssd_fp8_scale_name(self._h, i, buf, 128))
+            names.append(buf.value.decode())
+        return names
+
+    @property
+    def fp8_scales(self):
+        """{tensor name: scale} of an fp8 net, in graph order (0.0 before calibration)."""
+        names = self._fp8_names()
+        v = np.zeros(len(names), np.float32)
+        check(lib.ssd_fp8_get_scales(self._h, np_ptr(v), len(names)))
+        return dict(zip(names, (float(s) for s in v)))
+
+    @fp8_scales.setter
+    def fp8_scales(self, scales):
+        names = self._fp8_names()
+        missing = [n for n in names if n not in scales]
+        extra = [n for n in scales if n not in names]
+        if missing or extra:
+            raise ValueError(f'fp8_scales needs exactly {names}; missing {missing}, unknown {extra}')
+        v = np.array([scales[n] for n in names], np.float32)
+        check(lib.ssd_fp8_set_scales(self._h, np_ptr(v), len(names)))
 
     def activation(self, name, b):
         H = C.c_int(); W = C.c_int(); Ch = C.c_int()
