@@ -1239,6 +1239,14 @@ int ssd_op_conv2d_fwd_fp8(const void* x8, const void* w8, float s_in, const floa
                  s_w, bias, y, (unsigned char*)y8, out_mode, s_out, relu != 0, (hipStream_t)stream);
     API_END
 }
+int ssd_op_conv2d_fwd_fp8_bigk(const void* x8, const void* w8, float s_in, const float* s_w, const float* bias, void* y, void* y8,
+                               int out_mode, float s_out, int b, int hi, int wi, int ci, int ho, int wo, int co, int kh, int kw, int stride,
+                               int dil, int pad_h, int pad_w, int relu, void* stream) {
+    API_BEGIN
+    conv_bigk_fwd_fp8(mk(b, hi, wi, ci, ho, wo, co, kh, kw, stride, dil, pad_h, pad_w), (const unsigned char*)x8, (const unsigned char*)w8,
+                      s_in, s_w, bias, y, (unsigned char*)y8, out_mode, s_out, relu != 0, (hipStream_t)stream);
+    API_END
+}
 int ssd_op_maxpool_fwd_fp8(const void* x8, void* y8, int b, int hi, int wi, int c, int ho, int wo, int k, int stride, int pad_h,
                            int pad_w, void* stream) {
     API_BEGIN

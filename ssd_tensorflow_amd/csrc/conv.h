@@ -219,6 +219,13 @@ bool conv_fwd_fp8_worthwhile(const ConvDesc& d);
 // (FP8_OUT_E4M3 and FP8_OUT_BF16_E4M3).  Anything unsupported throws before a launch.
 void conv_fwd_fp8(const ConvDesc& d, const unsigned char* x8, const unsigned char* w8, float s_in, const float* s_w, const float* bias,
                   void* y, unsigned char* y8, int out_mode, float s_out, bool relu, hipStream_t s);
+// The same contract for 10 ... 121 taps (KH, KW <= 11): the fc graph's 7x7 fc6.  Also requires the filter image taps * Co * Ci
+// below the 32-bit offsets; 9 taps or fewer are refused (conv_fwd_fp8 runs them).
+bool conv_bigk_fwd_fp8_supported(const ConvDesc& d, const char** why);
+// whether the step executor puts such a layer on e4m3 (SSD_FP8_BIGK, read per handle; the default is measured: conv_fp8.hip)
+bool conv_bigk_fwd_fp8_worthwhile(const ConvDesc& d);
+void conv_bigk_fwd_fp8(const ConvDesc& d, const unsigned char* x8, const unsigned char* w8, float s_in, const float* s_w, const float* bias,
+                       void* y, unsigned char* y8, int out_mode, float s_out, bool relu, hipStream_t s);
 // One launch quantises every listed layer's fp32 filter [tap][Ci][Co] (element offset off in w) into its e4m3 image
 // [tap][Co][Ci] (byte offset off8 in w8) with s_w[offs + co] = absmax_co / 448 (1 for an all-zero channel).
 struct FilterQuantPlan {

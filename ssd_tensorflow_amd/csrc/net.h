@@ -59,7 +59,7 @@ struct Op {
     int pool_after = -1, unpool = -1;
     // head op: index of the feature map, else -1
     int head = -1;
-    // fp8 handle (net.hip plan_fp8): a convolution that runs on conv_fwd_fp8 / a pool that runs on e4m3 bytes; sw_off = the
+    // fp8 handle (net.hip plan_fp8): a convolution that runs on conv_fwd_fp8 or conv_bigk_fwd_fp8 / a pool that runs on e4m3 bytes; sw_off = the
     // layer's per-channel filter scales
     bool fp8 = false;
     size_t sw_off = 0;

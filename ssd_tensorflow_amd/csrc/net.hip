@@ -578,9 +578,11 @@ void Net::plan_winograd() {
     }
 }
 
-// fp8 handle.  Eligible: a trunk convolution in front of conv8_1 (no multibox head, not in the tail chain) that is not conv_bigk,
+// fp8 handle.  Eligible: a trunk convolution in front of conv8_1 (no multibox head, not in the tail chain) that
 // reads an activation (not the image), has Ci % 64 == 0 and is of a shape on which the fp8 kernel measured faster than the bf16 one
-// (conv_fwd_fp8_worthwhile) -- a-trous graph: conv3_2 ... conv5_3, mod_conv6, mod_conv7.  A tensor read by such a layer is kept as
+// (conv_fwd_fp8_worthwhile) -- a-trous graph: conv3_2 ... conv5_3, mod_conv6, mod_conv7.  A layer with more than 9 taps (the fc
+// graph's 7x7 mod_conv6) runs on conv_bigk_fwd_fp8 where conv_bigk_fwd_fp8_worthwhile says so (SSD_FP8_BIGK); otherwise it stays on
+// conv_bigk_fwd_bf16 with a quantise pass behind it.  A tensor read by such a layer is kept as
 // e4m3 (data8).  A pool between two fp8 layers runs on the bytes and its output shares its input's scale.  Where the e4m3 form is
 // needed behind a bf16 producer (conv3_1's output in the a-trous graph) a quantise pass of its own makes it.  A tensor with any non-fp8 reader (conv4_3: the l2 norm; mod_conv7's output: its head and conv8_1) keeps its
 // bf16 form as well (wants16).  Runs before plan_pool_fusion, which leaves the fp8 layers' pools alone.
@@ -593,8 +595,9 @@ void Net::plan_fp8() {
         producer[op.out] = i;
         if (op.kind != OP_CONV) continue;
         const ConvDesc d = conv_desc(op, Bmax_);
-        op.fp8 = op.head < 0 && i < tail_first_ && !conv_bigk(d) && !tensors_[op.in].data_f32 && conv_fwd_fp8_supported(d, nullptr) &&
-                 conv_fwd_fp8_worthwhile(d);
+        const bool kernel8 = conv_bigk(d) ? conv_bigk_fwd_fp8_supported(d, nullptr) && conv_bigk_fwd_fp8_worthwhile(d)
+                                          : conv_fwd_fp8_supported(d, nullptr) && conv_fwd_fp8_worthwhile(d);
+        op.fp8 = op.head < 0 && i < tail_first_ && !tensors_[op.in].data_f32 && kernel8;
     }
     auto need8 = [&](Tensor& t) {
         if (!t.data8) t.data8 = static_cast<unsigned char*>(hip_.mem(t.per_image() * Bmax_));
@@ -664,7 +667,11 @@ void Net::fp8_get_scales(float* out, int n) const {
 
 void Net::fp8_set_scales(const float* v, int n) {
     require_fp8();
-    SSD_REQUIRE(v && n == (int)fp8_scaled_.size(), "the handle has %zu fp8 scales, got %d", fp8_scaled_.size(), n);
+    if (!v || n != (int)fp8_scaled_.size()) {      // (e.g. scales saved from another plan: SSD_FP8_BIGK moves the fc graph's)
+        std::string names;
+        for (int t : fp8_scaled_) names += (names.empty() ? "" : ", ") + tensors_[t].name;
+        SSD_REQUIRE(false, "the handle has %zu fp8 scales (%s), got %d", fp8_scaled_.size(), names.c_str(), n);
+    }
     for (int i = 0; i < n; ++i)
         SSD_REQUIRE(v[i] > 0.f && v[i] < INFINITY, "fp8 scale %d (%s) must be positive and finite, got %g", i, fp8_scale_name(i), (double)v[i]);
     HIP_OK(hipStreamSynchronize(stream_));      // (no pass in flight reads a scale: they travel as kernel arguments; this orders the caller's view)
@@ -1143,9 +1150,10 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
                 else if (in.data_f32)
                     conv_fwd_smallc_bf16out(d, xin, params_ + op.w_off, params_ + op.b_off, static_cast<bf16_t*>(yout), op.relu, cs);
                 else if (run8 && op.fp8)      // e4m3 operands; the output in the form(s) its readers take
-                    conv_fwd_fp8(d, in.data8 + (size_t)run_b0 * in.per_image(), w8_ + op.w_off, in.scale, sw8_ + op.sw_off, params_ + op.b_off, yout,
-                                 out.data8 ? out.data8 + (size_t)run_b0 * out.per_image() : nullptr,
-                                 out.data8 ? (out.wants16 ? FP8_OUT_BF16_E4M3 : FP8_OUT_E4M3) : FP8_OUT_BF16, out.scale, op.relu, cs);
+                    (conv_bigk(d) ? conv_bigk_fwd_fp8 : conv_fwd_fp8)(      // (more than 9 taps: the fc graph's mod_conv6)
+                        d, in.data8 + (size_t)run_b0 * in.per_image(), w8_ + op.w_off, in.scale, sw8_ + op.sw_off, params_ + op.b_off, yout,
+                        out.data8 ? out.data8 + (size_t)run_b0 * out.per_image() : nullptr,
+                        out.data8 ? (out.wants16 ? FP8_OUT_BF16_E4M3 : FP8_OUT_E4M3) : FP8_OUT_BF16, out.scale, op.relu, cs);
                 else
                     conv_fwd_bf16(d, reinterpret_cast<const bf16_t*>(xin), wq_oi_ + op.w_off, params_ + op.b_off, yout, out.data_f32, op.relu, cs);
                 // a bf16 layer in front of an fp8 one: a boundary with a quantise pass of its own

@@ -172,7 +172,8 @@ class SSDVGG:
         Xavier-uniform synthetic weights (seed) unless `weights` ({tf_name: array}) or
         `<vgg_dir>/vgg16_ssd.npz` supplies them.  dtype 'f32' (default) or 'bf16' (bf16 activations and
         filter mirrors on the bf16 matrix cores; fp32 master weights, loss and optimizer), or -- training=False only --
-        'fp8': the bf16 net with conv3_2 ... mod_conv7 on e4m3 operands; call calibrate_fp8 or set fp8_scales before infer.
+        'fp8': the bf16 net with conv3_2 ... mod_conv7 (the fc graph's 7x7 fc6 included) on e4m3 operands; call calibrate_fp8 or set
+        fp8_scales before infer.
         a_trous=False builds the reference's other graph (ssdvgg.py:210-228): VGG-16's fc6 / fc7 as a 7x7 and a
         1x1 convolution, 4096 wide, variables fc6/* and fc7/*; its weights come from `<vgg_dir>/vgg16_ssd_fc.npz`."""
         self.num_classes = num_classes + 1

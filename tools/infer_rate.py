@@ -7,6 +7,13 @@ no second lane, no side stream, so an event interval is one kernel's duration), 
 fp8 only if the rounds separate: max(fp8) < min(bf16).
 
     python tools/infer_rate.py [--batch 128] [--rounds 5] [--passes 20] [--out profiles/fp8_infer_rate.txt]
+
+--a-trous false measures the fc graph with three handles from the same tests/fc_ref.py weights: bf16, fp8 created
+under SSD_FP8_BIGK=0 (the 7x7 fc6 on conv_bigk_fwd_bf16 with a quantise pass behind it) and fp8 under SSD_FP8_BIGK=1 (fc6 on
+e4m3), the same tables with one column per handle, then the kernels of mod_pool5, mod_conv6, mod_conv7 and the filter images one
+by one, with fc6's rate from its executed FLOPs.
+
+    python tools/infer_rate.py --a-trous false --out profiles/fp8_fc_infer_rate.txt
 """
 import argparse
 import ctypes as C
@@ -32,8 +39,8 @@ def timed_passes(net, x, passes):
     return e0.elapsed_time(e1) / passes
 
 
-def layer_times(net, x, passes):
-    """{layer: ms per pass} from the handle's per-launch events (labels 'kernel:layer')"""
+def layer_times(net, x, passes, by_label=None):
+    """{layer: ms per pass} from the handle's per-launch events (labels 'kernel:layer'); by_label (a dict) gets {label: ms}"""
     from ssd_tensorflow_amd._lib import lib, check
     check(lib.ssd_profile_enable(net._h, 2))
     for _ in range(passes):
@@ -47,7 +54,13 @@ def layer_times(net, x, passes):
             label, cnt, ms, fl, by = line.split('\t')
             layer = label.split(':', 1)[1] if ':' in label else label
             out[layer] = out.get(layer, 0.0) + float(ms) / passes
+            if by_label is not None:
+                by_label[label] = by_label.get(label, 0.0) + float(ms) / passes
     return out
+
+
+def mmm(v):
+    return '%10.4f (%.4f..%.4f)' % (statistics.median(v), min(v), max(v))
 
 
 def main():
@@ -56,6 +69,7 @@ def main():
     ap.add_argument('--batch', type=int, default=128)
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--passes', type=int, default=20)
+    ap.add_argument('--a-trous', default='true', choices=['true', 'false'], help="false: the fc graph, three handles (SSD_FP8_BIGK 0 / 1)")
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     import torch
@@ -68,56 +82,106 @@ def main():
         print(text, flush=True)
         lines.append(text)
 
+    fc = args.a_trous == 'false'
     preset = ob.get_preset(args.preset)
-    w = ref.init_params(preset, 20, seed=42, alive=True)
+    if fc:
+        sys.path.insert(0, os.path.join(ROOT, 'tests'))
+        import fc_ref
+        w = fc_ref.init_params(preset, 20, seed=42)
+        handles = [('bf16', 'bf16', None), ('fp8/bigk0', 'fp8', '0'), ('fp8/bigk1', 'fp8', '1')]      # (name, dtype, SSD_FP8_BIGK)
+    else:
+        w = ref.init_params(preset, 20, seed=42, alive=True)
+        handles = [('bf16', 'bf16', None), ('fp8', 'fp8', None)]
     x = torch.from_numpy(ref.synth_images(np.random.default_rng(5), args.batch, preset)).cuda()
     with Session(0) as sess:
         nets = {}
-        for dt in ('bf16', 'fp8'):
-            nets[dt] = SSDVGG(sess, args.preset)
-            nets[dt].build_from_vgg(None, 20, max_batch=args.batch, training=False, weights=w, dtype=dt)
-        nets['fp8'].calibrate_fp8(x[:32])
+        for name, dt, bigk in handles:
+            saved = os.environ.get('SSD_FP8_BIGK')
+            if bigk is not None:
+                os.environ['SSD_FP8_BIGK'] = bigk      # read when the handle is created
+            try:
+                nets[name] = SSDVGG(sess, args.preset)
+                nets[name].build_from_vgg(None, 20, a_trous=not fc, max_batch=args.batch, training=False, weights=w, dtype=dt)
+            finally:
+                if bigk is not None:
+                    os.environ.pop('SSD_FP8_BIGK')
+                    if saved is not None:
+                        os.environ['SSD_FP8_BIGK'] = saved
+            if dt == 'fp8':
+                nets[name].calibrate_fp8(x[:32])
+        last = handles[-1][0]                 # the handle under test: every comparison is this one against another
         for dt in nets:                       # warm-up: code objects, clocks
             timed_passes(nets[dt], x, 5)
-        say('# tools/infer_rate.py: %s, batch %d, resident input, %d interleaved rounds of %d passes per handle, %s'
-            % (args.preset, args.batch, args.rounds, args.passes, torch.cuda.get_device_name(0)))
+        say('# tools/infer_rate.py: %s%s, batch %d, resident input, %d interleaved rounds of %d passes per handle, %s'
+            % (args.preset, ' fc graph' if fc else '', args.batch, args.rounds, args.passes, torch.cuda.get_device_name(0)))
+        if fc:
+            for name in nets:
+                if name != 'bf16':
+                    say('# %s scales: %s' % (name, ' '.join(nets[name].fp8_scales)))
         ms = {dt: [] for dt in nets}
         for r in range(args.rounds):
             for dt in nets:
                 ms[dt].append(timed_passes(nets[dt], x, args.passes))
-        say('# %-6s %14s %26s %12s' % ('handle', 'ms/batch', '(min..max over rounds)', 'ms/image'))
+        say('# %-9s %14s %26s %12s' % ('handle', 'ms/batch', '(min..max over rounds)', 'ms/image') if fc else
+            '# %-6s %14s %26s %12s' % ('handle', 'ms/batch', '(min..max over rounds)', 'ms/image'))
         for dt in nets:
             v = ms[dt]
-            say('  %-6s %14.3f %15.3f..%.3f %14.4f' % (dt, statistics.median(v), min(v), max(v), statistics.median(v) / args.batch))
-        ratios = [a / b for a, b in zip(ms['bf16'], ms['fp8'])]
-        sep = max(ms['fp8']) < min(ms['bf16']) or max(ms['bf16']) < min(ms['fp8'])
-        say('# bf16 time / fp8 time: median %.3f, per round %s; the rounds %s' % (statistics.median(ratios), ' '.join('%.3f' % q for q in ratios),
-                                                                                'separate the two handles' if sep else 'do NOT separate the two handles'))
+            say(('  %-9s %14.3f %15.3f..%.3f %14.4f' if fc else '  %-6s %14.3f %15.3f..%.3f %14.4f')
+                % (dt, statistics.median(v), min(v), max(v), statistics.median(v) / args.batch))
+        for other in [h[0] for h in handles[:-1]]:
+            ratios = [a / b for a, b in zip(ms[other], ms[last])]
+            sep = max(ms[last]) < min(ms[other]) or max(ms[other]) < min(ms[last])
+            say('# %s time / %s time: median %.3f, per round %s; the rounds %s'
+                % (other, last, statistics.median(ratios), ' '.join('%.3f' % q for q in ratios),
+                   'separate the two handles' if sep else 'do NOT separate the two handles'))
         # ---- per layer, one stream
         for dt in nets:
             check(lib.ssd_set_overlap(nets[dt]._h, 0))
             layer_times(nets[dt], x, 2)
         per = {dt: [] for dt in nets}
+        lab = {dt: [] for dt in nets}
         for r in range(args.rounds):
             for dt in nets:
-                per[dt].append(layer_times(nets[dt], x, max(args.passes // 4, 2)))
-        layers = [k for k in per['bf16'][0] if k in per['fp8'][0]]
+                lab[dt].append({})
+                per[dt].append(layer_times(nets[dt], x, max(args.passes // 4, 2), lab[dt][-1]))
+        layers = [k for k in per['bf16'][0] if all(k in per[dt][0] for dt in nets)]
         say('# per layer on one stream (kernel events, ms per batch): median (min..max); fp8 includes the layer\'s e4m3 outputs')
-        say('# %-18s %28s %28s %8s  %s' % ('layer', 'bf16', 'fp8', 'ratio', 'verdict'))
+        if fc:
+            say('# verdict: %s against bf16; a quantise pass behind a bf16 layer counts with that layer' % last)
+        say('# %-18s ' % 'layer' + ' '.join('%28s' % dt for dt in nets) + ' %8s  %s' % ('ratio', 'verdict'))
         tot = {dt: 0.0 for dt in nets}
         for k in layers:
-            a = [p[k] for p in per['bf16']]
-            f = [p[k] for p in per['fp8']]
-            tot['bf16'] += statistics.median(a); tot['fp8'] += statistics.median(f)
+            cols = {dt: [p[k] for p in per[dt]] for dt in nets}
+            for dt in nets:
+                tot[dt] += statistics.median(cols[dt])
+            a, f = cols['bf16'], cols[last]
             verdict = 'fp8 faster' if max(f) < min(a) else ('fp8 SLOWER' if max(a) < min(f) else 'not separated')
-            say('  %-18s %10.4f (%.4f..%.4f) %10.4f (%.4f..%.4f) %8.3f  %s' % (k, statistics.median(a), min(a), max(a), statistics.median(f),
-                                                                               min(f), max(f), statistics.median(a) / max(statistics.median(f), 1e-9), verdict))
-        only8 = [k for k in per['fp8'][0] if k not in per['bf16'][0]]
-        for k in only8:
-            f = [p[k] for p in per['fp8']]
-            tot['fp8'] += statistics.median(f)
-            say('  %-18s %28s %10.4f (%.4f..%.4f)' % (k, '-', statistics.median(f), min(f), max(f)))
-        say('# sum of the kernels per batch, one stream: bf16 %.3f ms, fp8 %.3f ms' % (tot['bf16'], tot['fp8']))
+            say('  %-18s ' % k + ' '.join(mmm(cols[dt]) for dt in nets) + ' %8.3f  %s' % (statistics.median(a) / max(statistics.median(f), 1e-9), verdict))
+        for dt in nets:
+            for k in per[dt][0]:
+                if k not in layers:
+                    f = [p.get(k, 0.0) for p in per[dt]]
+                    tot[dt] += statistics.median(f)
+                    say('  %-18s only in %s: %s' % (k, dt, mmm(f)) if fc else '  %-18s %28s %s' % (k, '-', mmm(f)))
+        say('# sum of the kernels per batch, one stream: ' + ', '.join('%s %.3f ms' % (dt, tot[dt]) for dt in nets))
+        if fc:
+            # ---- the kernels around fc6 one by one; fc6's rate from its executed FLOPs 2 * pixels * Ci * Co * taps
+            fmap = preset['maps'][1][0]
+            flops6 = 2.0 * args.batch * fmap * fmap * 512 * 4096 * 49
+            say('# kernels of mod_pool5, mod_conv6, mod_conv7 and the filter images (ms per batch); mod_conv6: TF/s from 2*pixels*Ci*Co*49 = %.1f GFLOP' % (flops6 / 1e9))
+            for dt in nets:
+                for label in lab[dt][0]:
+                    layer = label.split(':', 1)[1] if ':' in label else label
+                    if layer in ('mod_pool5', 'mod_conv6', 'mod_conv7', 'filters'):
+                        v = [p.get(label, 0.0) for p in lab[dt]]
+                        rate = '  %.0f TF/s' % (flops6 / (statistics.median(v) * 1e-3) / 1e12) if layer == 'mod_conv6' and 'conv' in label.split(':')[0] else ''
+                        say('  %-10s %-44s %s%s' % (dt, label, mmm(v), rate))
+            k0, k1 = [p['mod_conv6'] for p in per['fp8/bigk0']], [p['mod_conv6'] for p in per['fp8/bigk1']]
+            a = [p['mod_conv6'] for p in per['bf16']]
+            say('# rule (DESIGN.md 18): mod_conv6 row max(fp8/bigk1) %.4f %s min(bf16) %.4f; whole handle max(bigk1) %.3f %s min(bigk0) %.3f'
+                % (max(k1), '<' if max(k1) < min(a) else '>=', min(a), max(ms['fp8/bigk1']), '<' if max(ms['fp8/bigk1']) < min(ms['fp8/bigk0']) else '>=',
+                   min(ms['fp8/bigk0'])))
+            say('# %s: not measured' % ('vgg512' if args.preset == 'vgg300' else 'vgg300'))
     if args.out:
         with open(args.out, 'w') as f:
             f.write('\n'.join(lines) + '\n')
