@@ -642,6 +642,7 @@ static int create_handle(const char* preset, int num_classes, int max_batch, int
     SSD_REQUIRE(out != nullptr, "out handle pointer is null");
     *out = nullptr;
     SSD_REQUIRE(!(dtype == SSD_DTYPE_FP8 && training), "SSD_DTYPE_FP8 is inference only: create the handle with training = 0");
+    SSD_REQUIRE(!(dtype == SSD_DTYPE_MXFP8 && training), "SSD_DTYPE_MXFP8 is inference only: create the handle with training = 0");
     DeviceGuard dev_guard_(device);
     auto n = std::make_unique<Net>(preset, num_classes, max_batch, device, training != 0, seed, ext_params_dev, ext_grads_dev,
                                    ext_momentum_dev, dtype, graph);
@@ -1252,6 +1253,27 @@ int ssd_op_maxpool_fwd_fp8(const void* x8, void* y8, int b, int hi, int wi, int 
     API_BEGIN
     PoolDesc d{b, hi, wi, c, ho, wo, k, stride, pad_h, pad_w};
     maxpool_fwd_fp8(d, (const unsigned char*)x8, (unsigned char*)y8, (hipStream_t)stream);
+    API_END
+}
+// mxfp8 inference kernels (conv_mxfp8.hip)
+int ssd_op_quantize_mxfp8(const void* x, int x_f32, size_t rows, int c, void* y8, void* yscales, void* stream) {
+    API_BEGIN
+    quantize_mxfp8(x, x_f32 != 0, rows, c, (unsigned char*)y8, (unsigned char*)yscales, (hipStream_t)stream);
+    API_END
+}
+int ssd_op_conv2d_fwd_mxfp8(const void* x8, const void* xscales, const void* w8, const float* s_w, const float* bias, void* y, void* y8,
+                            void* yscales, int out_mode, int b, int hi, int wi, int ci, int ho, int wo, int co, int kh, int kw, int stride,
+                            int dil, int pad_h, int pad_w, int relu, void* stream) {
+    API_BEGIN
+    conv_fwd_mxfp8(mk(b, hi, wi, ci, ho, wo, co, kh, kw, stride, dil, pad_h, pad_w), (const unsigned char*)x8, (const unsigned char*)xscales,
+                   (const unsigned char*)w8, s_w, bias, y, (unsigned char*)y8, (unsigned char*)yscales, out_mode, relu != 0, (hipStream_t)stream);
+    API_END
+}
+int ssd_op_maxpool_fwd_mxfp8(const void* x8, const void* xscales, void* y8, void* yscales, int b, int hi, int wi, int c, int ho, int wo, int k,
+                             int stride, int pad_h, int pad_w, void* stream) {
+    API_BEGIN
+    PoolDesc d{b, hi, wi, c, ho, wo, k, stride, pad_h, pad_w};
+    maxpool_fwd_mxfp8(d, (const unsigned char*)x8, (const unsigned char*)xscales, (unsigned char*)y8, (unsigned char*)yscales, (hipStream_t)stream);
     API_END
 }
 int ssd_op_maxpool_fwd(const float* x, float* y, int b, int hi, int wi, int c, int ho, int wo, int k, int stride, int pad_h,

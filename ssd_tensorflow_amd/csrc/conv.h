@@ -246,4 +246,17 @@ struct PoolDesc;
 // max-pooling on e4m3 codes of either sign; C a multiple of 16; cells outside the image never win
 void maxpool_fwd_fp8(const PoolDesc& d, const unsigned char* x8, unsigned char* y8, hipStream_t s);
 
+// ---- mxfp8 inference kernels (conv_mxfp8.hip): e4m3 codes [B,H,W,C] + one E8M0 scale byte per pixel and 32 channels [B,H,W,C/32] ----
+// scale rule on the bits of the block's fp32 absmax: x = clamp(E - 8 + (mantissa > 0x600000), -127, 127), byte x + 127 (an all-zero
+// block: byte 0); codes = RNE(clamp(ldexp(v, -x), -448, 448)).  Filters as for fp8.  y = relu?(acc * s_w[co] + bias[co]) in fp32.
+enum { FP8_OUT_MX = 4, FP8_OUT_BF16_MX = 5 };      // beside FP8_OUT_BF16 and FP8_OUT_F32: codes + scales / bf16 and codes + scales
+// conv_fwd_fp8's eligibility (conv_fwd_fp8_supported); an MX output needs Co % 32 == 0.  xs is read in whole dwords: its allocation
+// must be readable up to its size rounded up to 4 bytes.  Anything unsupported throws before a launch.
+void conv_fwd_mxfp8(const ConvDesc& d, const unsigned char* x8, const unsigned char* xs, const unsigned char* w8, const float* s_w,
+                    const float* bias, void* y, unsigned char* y8, unsigned char* ys, int out_mode, bool relu, hipStream_t s);
+// bf16 or fp32 [rows][C] -> codes [rows][C] + scales [rows][C / 32]; C a multiple of 32
+void quantize_mxfp8(const void* x, bool x_f32, size_t rows, int C, unsigned char* y8, unsigned char* ys, hipStream_t s);
+// max-pooling of MX tensors: the maximum of the dequantised cells per channel, quantised again per block; C a multiple of 32
+void maxpool_fwd_mxfp8(const PoolDesc& d, const unsigned char* x8, const unsigned char* xs, unsigned char* y8, unsigned char* ys, hipStream_t s);
+
 }  // namespace ssd

@@ -31,6 +31,8 @@ struct Tensor {
     // that takes the bf16 form
     unsigned char* data8 = nullptr;
     float scale = 0.f;
+    // mxfp8 handle: the E8M0 block scales of data8, one byte per pixel and 32 channels, written by the tensor's producer
+    unsigned char* scale8 = nullptr;
     bool wants16 = true;
     size_t per_image() const { return (size_t)H * W * C; }
     const float* f() const { return static_cast<const float*>(data); }
@@ -95,7 +97,8 @@ class Net {
 public:
     // dtype 0: fp32 everywhere (BASELINE.json configs[1]); 1: bf16 activations / gradients / filter mirrors with fp32
     // master weights, fp32 accumulation and fp32 loss (configs[2]); 2: fp8, an inference-only bf16 handle whose eligible
-    // trunk convolutions (conv3_2 ... mod_conv7) run on e4m3 operands (plan_fp8)
+    // trunk convolutions (conv3_2 ... mod_conv7) run on e4m3 operands (plan_fp8); 3: mxfp8, the same layers with E8M0 block scales
+    // chosen by each producer (conv_mxfp8.hip): no per-tensor scales, no calibration
     Net(const char* preset, int num_classes, int max_batch, int device, bool training, unsigned long long seed,
         float* ext_params, float* ext_grads, float* ext_momentum, int dtype = 0, int graph = 0);
     ~Net();
@@ -155,7 +158,7 @@ public:
     int nvars() const { return C_ + 5; }
     int max_batch() const { return Bmax_; }
     bool training() const { return training_; }
-    int dtype() const { return fp8_ ? 2 : bf16_ ? 1 : 0; }
+    int dtype() const { return mx_ ? 3 : fp8_ ? 2 : bf16_ ? 1 : 0; }
     // fp8 handle: one scale per tensor that a convolution writes as e4m3, in graph order
     void fp8_calibrate(const float* x_dev, int b, bool accumulate);      // the graph on the bf16 kernels; scale = max(absmax, tiny) / 448
     int fp8_num_scales() const;
@@ -191,6 +194,7 @@ private:
     // fp8 handle: e4m3 filter images [tap][Co][Ci] at the filters' arena offsets + per-channel scales, refreshed from the
     // fp32 masters by every forward pass like the bf16 mirrors (one launch, behind cast_filters)
     bool fp8_ = false;
+    bool mx_ = false;                      // an fp8 handle (fp8_ is set) of the mxfp8 kind: block scales in Tensor::scale8
     bool fp8_calibrated_ = false, fp8_as_bf16_ = false;      // fp8_as_bf16_: this pass is the calibration run
     unsigned char* w8_ = nullptr;
     float *sw8_ = nullptr, *absmax8_ = nullptr;

@@ -595,12 +595,15 @@ void Net::plan_fp8() {
         producer[op.out] = i;
         if (op.kind != OP_CONV) continue;
         const ConvDesc d = conv_desc(op, Bmax_);
-        const bool kernel8 = conv_bigk(d) ? conv_bigk_fwd_fp8_supported(d, nullptr) && conv_bigk_fwd_fp8_worthwhile(d)
+        // (mxfp8: there is no MX form of the kernel for more than 9 taps; the fc graph's fc6 stays on bf16 with a quantise pass behind it)
+        const bool kernel8 = conv_bigk(d) ? !mx_ && conv_bigk_fwd_fp8_supported(d, nullptr) && conv_bigk_fwd_fp8_worthwhile(d)
                                           : conv_fwd_fp8_supported(d, nullptr) && conv_fwd_fp8_worthwhile(d);
         op.fp8 = op.head < 0 && i < tail_first_ && !tensors_[op.in].data_f32 && kernel8;
     }
     auto need8 = [&](Tensor& t) {
         if (!t.data8) t.data8 = static_cast<unsigned char*>(hip_.mem(t.per_image() * Bmax_));
+        // (+ 8: conv_fwd_mxfp8 reads the scales in whole dwords)
+        if (mx_ && !t.scale8) t.scale8 = static_cast<unsigned char*>(hip_.mem(t.per_image() / 32 * Bmax_ + 8));
     };
     for (int i = (int)ops_.size() - 1; i >= 0; --i) {      // readers before their producers: a pool learns from its consumer
         Op& op = ops_[i];
@@ -633,15 +636,18 @@ void Net::plan_fp8() {
         Tensor& out = tensors_[op.out];
         if (!out.data8) continue;
         if (!op.fp8) out.wants16 = true;      // a bf16 op writes bf16; the quantise pass behind it makes the e4m3 form
-        if (!(op.kind == OP_POOL && op.fp8)) fp8_scaled_.push_back(op.out);
+        if (!(op.kind == OP_POOL && op.fp8) && !mx_) fp8_scaled_.push_back(op.out);      // (mxfp8: no tensor owns a scale)
     }
-    SSD_REQUIRE(!fp8_scaled_.empty(), "no layer of this graph is eligible for fp8");
+    SSD_REQUIRE(quant_plan_.n > 0, "no layer of this graph is eligible for fp8");
     w8_ = static_cast<unsigned char*>(hip_.mem(nfilters_));
     sw8_ = static_cast<float*>(hip_.mem(nsw * sizeof(float)));
-    absmax8_ = static_cast<float*>(hip_.mem(fp8_scaled_.size() * sizeof(float)));
+    if (!mx_) absmax8_ = static_cast<float*>(hip_.mem(fp8_scaled_.size() * sizeof(float)));
 }
 
-void Net::require_fp8() const { SSD_REQUIRE(fp8_, "not an fp8 handle (SSD_DTYPE_FP8)"); }
+void Net::require_fp8() const {
+    SSD_REQUIRE(!mx_, "an mxfp8 handle has no calibration scales (SSD_DTYPE_MXFP8): every producer chooses its block scales itself");
+    SSD_REQUIRE(fp8_, "not an fp8 handle (SSD_DTYPE_FP8)");
+}
 
 void Net::fp8_share_pool_scales() {
     for (const Op& op : ops_)      // graph order: a pool comes behind its input's producer
@@ -860,10 +866,10 @@ void Net::init_weights(unsigned long long seed) {
 
 Net::Net(const char* preset, int num_classes, int max_batch, int device, bool training, unsigned long long seed,
          float* ext_params, float* ext_grads, float* ext_momentum, int dtype, int graph)
-    : preset_(&get_preset(preset)), C_(num_classes), Bmax_(max_batch), device_(device), training_(training), bf16_(dtype == 1 || dtype == 2),
-      fc_(graph == 1), fp8_(dtype == 2), hip_(device) {
-    SSD_REQUIRE(dtype >= 0 && dtype <= 2, "dtype must be 0 (fp32), 1 (bf16) or 2 (fp8), got %d", dtype);
-    SSD_REQUIRE(!(fp8_ && training), "SSD_DTYPE_FP8 is inference only: create the handle with training = 0");
+    : preset_(&get_preset(preset)), C_(num_classes), Bmax_(max_batch), device_(device), training_(training), bf16_(dtype >= 1 && dtype <= 3),
+      fc_(graph == 1), fp8_(dtype == 2 || dtype == 3), mx_(dtype == 3), hip_(device) {
+    SSD_REQUIRE(dtype >= 0 && dtype <= 3, "dtype must be 0 (fp32), 1 (bf16), 2 (fp8) or 3 (mxfp8), got %d", dtype);
+    SSD_REQUIRE(!(fp8_ && training), "%s is inference only: create the handle with training = 0", mx_ ? "SSD_DTYPE_MXFP8" : "SSD_DTYPE_FP8");
     SSD_REQUIRE(graph == 0 || graph == 1, "graph must be 0 (a-trous) or 1 (fc), got %d", graph);
     require_num_classes(num_classes);
     SSD_REQUIRE(max_batch >= 1, "max_batch must be >= 1");
@@ -926,7 +932,7 @@ Net::~Net() {
 // reduction, which the last per-sample workgroup of either lane performs (ops.hip).
 void Net::forward(const float* x, int b, bool train_mode, const float* y) {
     SSD_REQUIRE(b >= 1 && b <= Bmax_, "batch %d outside 1..%d (max_batch)", b, Bmax_);
-    SSD_REQUIRE(!fp8_ || fp8_as_bf16_ || fp8_calibrated_,
+    SSD_REQUIRE(!fp8_ || mx_ || fp8_as_bf16_ || fp8_calibrated_,
                 "the fp8 handle has no activation scales yet: call ssd_fp8_calibrate_dev or ssd_fp8_set_scales before inference");
     const bool run8 = fp8_ && !fp8_as_bf16_;      // this pass runs the fp8 layers on e4m3 operands (the calibration pass does not)
     g_prof = &prof_;
@@ -956,6 +962,13 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
     };
     auto at = [](const Tensor& t, int b0, bool grad = false) -> char* {      // first element of sample b0
         return static_cast<char*>(grad ? t.grad : t.data) + (size_t)b0 * t.per_image() * ((grad ? t.grad_f32 : t.data_f32) ? 4 : 2);
+    };
+    // the stand-alone quantise pass behind a bf16 producer: samples b0 ... b0 + nb of t's bf16 form (src) into its e4m3 form
+    auto quantize8 = [&](const Tensor& t, const void* src, int b0, int nb, hipStream_t s) {
+        if (mx_)
+            quantize_mxfp8(src, false, (size_t)nb * t.H * t.W, t.C, t.data8 + (size_t)b0 * t.per_image(), t.scale8 + (size_t)b0 * (t.per_image() / 32), s);
+        else
+            quantize_fp8(src, false, (size_t)nb * t.per_image(), t.scale, t.data8 + (size_t)b0 * t.per_image(), s);
     };
     if (side && (bf16_ || train_mode || nl == 2)) {
         HIP_OK(hipEventRecord(ev_fmap_[MAX_MAPS - 1], stream_));      // everything issued so far (the previous step's update)
@@ -1130,7 +1143,7 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
                         conv_fwd_pool_bf16(d, reinterpret_cast<const bf16_t*>(xin), wq_oi_ + op.w_off, params_ + op.b_off,
                                            reinterpret_cast<bf16_t*>(at(pt, run_b0)), rec, cs);
                     if (run8 && pt.data8)      // the pooled tensor feeds an fp8 layer: the boundary's quantise pass
-                        quantize_fp8(at(pt, run_b0), false, (size_t)run_nb * pt.per_image(), pt.scale, pt.data8 + (size_t)run_b0 * pt.per_image(), cs);
+                        quantize8(pt, at(pt, run_b0), run_b0, run_nb, cs);
                     break;
                 }
                 // a feature map's producer carries the event its head waits for (common.h g_stop_event; backward_step does the same)
@@ -1149,6 +1162,11 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
                     conv_first_fwd_bf16(d, xin, params_ + op.w_off, params_ + op.b_off, static_cast<bf16_t*>(yout), op.relu, cs);
                 else if (in.data_f32)
                     conv_fwd_smallc_bf16out(d, xin, params_ + op.w_off, params_ + op.b_off, static_cast<bf16_t*>(yout), op.relu, cs);
+                else if (run8 && op.fp8 && mx_)      // e4m3 operands with block scales; the output in the form(s) its readers take
+                    conv_fwd_mxfp8(d, in.data8 + (size_t)run_b0 * in.per_image(), in.scale8 + (size_t)run_b0 * (in.per_image() / 32), w8_ + op.w_off,
+                                   sw8_ + op.sw_off, params_ + op.b_off, yout, out.data8 ? out.data8 + (size_t)run_b0 * out.per_image() : nullptr,
+                                   out.data8 ? out.scale8 + (size_t)run_b0 * (out.per_image() / 32) : nullptr,
+                                   out.data8 ? (out.wants16 ? FP8_OUT_BF16_MX : FP8_OUT_MX) : FP8_OUT_BF16, op.relu, cs);
                 else if (run8 && op.fp8)      // e4m3 operands; the output in the form(s) its readers take
                     (conv_bigk(d) ? conv_bigk_fwd_fp8 : conv_fwd_fp8)(      // (more than 9 taps: the fc graph's mod_conv6)
                         d, in.data8 + (size_t)run_b0 * in.per_image(), w8_ + op.w_off, in.scale, sw8_ + op.sw_off, params_ + op.b_off, yout,
@@ -1157,8 +1175,7 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
                 else
                     conv_fwd_bf16(d, reinterpret_cast<const bf16_t*>(xin), wq_oi_ + op.w_off, params_ + op.b_off, yout, out.data_f32, op.relu, cs);
                 // a bf16 layer in front of an fp8 one: a boundary with a quantise pass of its own
-                if (run8 && out.data8 && !op.fp8)
-                    quantize_fp8(yout, false, (size_t)run_nb * out.per_image(), out.scale, out.data8 + (size_t)run_b0 * out.per_image(), cs);
+                if (run8 && out.data8 && !op.fp8) quantize8(out, yout, run_b0, run_nb, cs);
                 break;
             }
             case OP_POOL: {
@@ -1175,12 +1192,16 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
                     else maxpool_fwd_arg(d, reinterpret_cast<const float*>(at(in, ln.b0)), reinterpret_cast<float*>(at(out, ln.b0)), arg, ln.s);
                     pool_arg_op_ = op_index;
                 } else if (run8 && op.fp8) {      // on e4m3 bytes (the output shares the input's scale); bf16 as well where someone reads that
-                    maxpool_fwd_fp8(d, in.data8 + (size_t)ln.b0 * in.per_image(), out.data8 + (size_t)ln.b0 * out.per_image(), ln.s);
+                    if (mx_)                      // (mxfp8: on the dequantised cells, with block scales of its own)
+                        maxpool_fwd_mxfp8(d, in.data8 + (size_t)ln.b0 * in.per_image(), in.scale8 + (size_t)ln.b0 * (in.per_image() / 32),
+                                          out.data8 + (size_t)ln.b0 * out.per_image(), out.scale8 + (size_t)ln.b0 * (out.per_image() / 32), ln.s);
+                    else
+                        maxpool_fwd_fp8(d, in.data8 + (size_t)ln.b0 * in.per_image(), out.data8 + (size_t)ln.b0 * out.per_image(), ln.s);
                     if (out.wants16) maxpool_fwd(d, reinterpret_cast<const bf16_t*>(at(in, ln.b0)), reinterpret_cast<bf16_t*>(at(out, ln.b0)), ln.s);
                 } else if (bf16_) {
                     maxpool_fwd(d, reinterpret_cast<const bf16_t*>(at(in, ln.b0)), reinterpret_cast<bf16_t*>(at(out, ln.b0)), ln.s);
                     if (run8 && out.data8)      // a bf16 pool in front of an fp8 layer
-                        quantize_fp8(at(out, ln.b0), false, (size_t)nb * out.per_image(), out.scale, out.data8 + (size_t)ln.b0 * out.per_image(), ln.s);
+                        quantize8(out, at(out, ln.b0), ln.b0, nb, ln.s);
                 } else maxpool_fwd(d, reinterpret_cast<const float*>(at(in, ln.b0)), reinterpret_cast<float*>(at(out, ln.b0)), ln.s);
                 break;
             }
@@ -1634,9 +1655,11 @@ void Net::save_variable(const char* name, float* host, size_t count, int which) 
 
 void Net::activation_shape(const char* name, int* H, int* W, int* C) const {
     if (name && (!strncmp(name, "grad:", 5) || !strncmp(name, "bf16:", 5))) name += 5;
+    const bool want_scale = name && !strncmp(name, "scale:", 6);      // (mxfp8 handle: one value per pixel and 32 channels)
+    if (want_scale) name += 6;
     for (const Tensor& t : tensors_)
         if (t.name == name) {
-            *H = t.H; *W = t.W; *C = t.C;
+            *H = t.H; *W = t.W; *C = want_scale ? t.C / 32 : t.C;
             return;
         }
     fail("no such activation: %s", name ? name : "(null)");
@@ -1650,6 +1673,9 @@ void Net::activation(const char* name, int b, float* out, size_t count) {
     if (want_grad) name += 5;
     const bool want_bf16 = name && !strncmp(name, "bf16:", 5);
     if (want_bf16) name += 5;
+    // "scale:<scope>" (mxfp8 handle) returns the block scales 2^x of an MX tensor, [b, H, W, C / 32]
+    const bool want_scale = name && !want_grad && !want_bf16 && !strncmp(name, "scale:", 6);
+    if (want_scale) name += 6;
     for (size_t ti = 0; ti < tensors_.size(); ++ti) {
         const Tensor& t = tensors_[ti];
         if (t.name != name || !t.data) continue;
@@ -1662,17 +1688,30 @@ void Net::activation(const char* name, int b, float* out, size_t count) {
             SSD_REQUIRE(!(op.kind == OP_POOL && op.fused_bwd && op.out == (int)ti && want_grad),
                         "gradient of %s is not materialised: the pool's backward is fused into its consumer's data gradient (SSD_POOL_FUSE=0 keeps it)", name);
         }
+        if (want_scale) {
+            SSD_REQUIRE(t.scale8 != nullptr, "activation %s has no block scales (not an MX tensor of an mxfp8 handle)", name);
+            SSD_REQUIRE(count == t.per_image() / 32 * b, "scale:%s holds %zu floats for b=%d, got %zu", name, t.per_image() / 32 * b, b, count);
+            HIP_OK(hipStreamSynchronize(stream_));
+            std::vector<unsigned char> hs(count);
+            HIP_OK(hipMemcpy(hs.data(), t.scale8, count, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < count; ++i) out[i] = ldexpf(1.f, (int)hs[i] - 127);
+            return;
+        }
         SSD_REQUIRE(count == t.per_image() * b, "activation %s holds %zu floats for b=%d, got %zu", name, t.per_image() * b, b,
                     count);
         const void* src = want_grad ? t.grad : t.data;
         HIP_OK(hipStreamSynchronize(stream_));
         if (t.data8 && !want_grad && !want_bf16) {      // an fp8 tensor: its codes times its scale (exact in fp32)
-            std::vector<unsigned char> hc(count);
+            std::vector<unsigned char> hc(count), hs;
             HIP_OK(hipMemcpy(hc.data(), t.data8, count, hipMemcpyDeviceToHost));
+            if (t.scale8) {      // an MX tensor: its codes times their blocks' 2^x
+                hs.resize(count / 32);
+                HIP_OK(hipMemcpy(hs.data(), t.scale8, count / 32, hipMemcpyDeviceToHost));
+            }
             for (size_t i = 0; i < count; ++i) {
                 const int c = hc[i], e = (c >> 3) & 15, m = c & 7;
                 const float v = (e == 15 && m == 7) ? NAN : e == 0 ? ldexpf((float)m, -9) : ldexpf(1.f + m / 8.f, e - 7);
-                out[i] = (c & 0x80 ? -v : v) * t.scale;
+                out[i] = t.scale8 ? ldexpf(c & 0x80 ? -v : v, (int)hs[i / 32] - 127) : (c & 0x80 ? -v : v) * t.scale;
             }
             return;
         }

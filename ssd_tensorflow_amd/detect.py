@@ -11,7 +11,7 @@ import sys
 import numpy as np
 
 from .annotate import Style, write_image, GpuJpegWriter
-from .infer import sample_generator, resolve_class_names, add_fp8_arguments, fp8_batches
+from .infer import sample_generator, resolve_class_names, add_fp8_arguments, check_fp8_arguments, fp8_batches
 from .ssdvgg import SSDVGG, Session
 from .ssdutils import get_preset_by_name, boxes_from_detection
 from .utils import default_colors
@@ -24,8 +24,9 @@ def main(argv=None):
     parser.add_argument('--training-data', default='', help='unused: the checkpoint carries the preset and the class names')
     parser.add_argument('--output-dir', default='test-out', help='output directory')
     parser.add_argument('--batch-size', type=int, default=32, help='batch size')
-    parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16', 'fp8'],
-                        help='f32, bf16 activations on the bf16 matrix cores, or fp8: the bf16 net with conv3_2 ... mod_conv7 on e4m3 operands')
+    parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16', 'fp8', 'mxfp8'],
+                        help='f32, bf16 activations on the bf16 matrix cores, fp8: the bf16 net with conv3_2 ... mod_conv7 on e4m3 operands '
+                             '(calibrated scales), or mxfp8: the same layers with block scales chosen from the data (no calibration)')
     add_fp8_arguments(parser)
     parser.add_argument('--decoder', default='gpu', choices=['pillow', 'gpu'],
                         help='gpu: baseline JPEGs are decoded on the GPU, other files as with pillow (same pixels); pillow: every file is decoded on the host')
@@ -37,6 +38,7 @@ def main(argv=None):
     parser.add_argument('--jpeg-entropy', default='host', choices=['host', 'gpu'],
                         help='--encoder gpu: host: Huffman coding on host threads; gpu: on the GPU as well, only the files come back (same bytes)')
     args = parser.parse_args(argv)
+    check_fp8_arguments(parser, args)
 
     print('[i] Model:         ', args.model)
     print('[i] Training data: ', args.training_data)

@@ -109,8 +109,14 @@ def add_fp8_arguments(parser):
                         help='--dtype fp8 without stored scales: this many of the first inputs calibrate the net before the first inference')
 
 
+def check_fp8_arguments(parser, args):
+    """--fp8-calibration with --dtype mxfp8 is an argument error: such a net has nothing to calibrate"""
+    if args.dtype == 'mxfp8' and args.fp8_calibration:
+        parser.error('--fp8-calibration does not apply to --dtype mxfp8: an mxfp8 net has no calibration scales')
+
+
 def fp8_batches(net, batches, calibration_file=None, calibrate_images=32):
-    """The batches of sample_generator, unchanged, for a net that is not fp8.  For an fp8 net the scales are in place before the
+    """The batches of sample_generator, unchanged, for a net that is not fp8 (an mxfp8 net among them: it needs no scales).  For an fp8 net the scales are in place before the
     first batch is handed on: from calibration_file if it exists, else from the first calibrate_images inputs (whole batches
     are held back for that and handed on afterwards, so every input is still inferred), written to calibration_file if given."""
     if getattr(net, 'dtype', None) != 'fp8':
@@ -171,8 +177,9 @@ def main(argv=None):
     parser.add_argument('--preset', default=None, help='preset when no checkpoint is given (random weights)')
     parser.add_argument('--num-classes', type=int, default=20, help='class count when no checkpoint is given (1..127)')
     parser.add_argument('--a-trous', type=str2bool, default='True', help='graph when no checkpoint is given: a-trous (true) or fc (false); a checkpoint carries its own')
-    parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16', 'fp8'],
-                        help='f32, bf16 activations on the bf16 matrix cores, or fp8: the bf16 net with conv3_2 ... mod_conv7 on e4m3 operands')
+    parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16', 'fp8', 'mxfp8'],
+                        help='f32, bf16 activations on the bf16 matrix cores, fp8: the bf16 net with conv3_2 ... mod_conv7 on e4m3 operands '
+                             '(calibrated scales), or mxfp8: the same layers with block scales chosen from the data (no calibration)')
     add_fp8_arguments(parser)
     parser.add_argument('--decoder', default='gpu', choices=['pillow', 'gpu'],
                         help='gpu: baseline JPEGs are decoded on the GPU, other files as with pillow (same pixels); pillow: every file is decoded on the host')
@@ -184,6 +191,7 @@ def main(argv=None):
     parser.add_argument('--jpeg-entropy', default='host', choices=['host', 'gpu'],
                         help='--encoder gpu: host: Huffman coding on host threads; gpu: on the GPU as well, only the files come back (same bytes)')
     args = parser.parse_args(argv)
+    check_fp8_arguments(parser, args)
 
     print('[i] Project name:      ', args.name)
     print('[i] Batch size:        ', args.batch_size)

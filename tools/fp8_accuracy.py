@@ -11,6 +11,10 @@ in mAP, from the held-out set's object counts -- the allowance for fp8 against b
 fc6 on the bf16 kernel) and under SSD_FP8_BIGK=1 (fc6 on e4m3), and the allowance is applied to the second.
 
     python tools/fp8_accuracy.py --a-trous false --out profiles/fp8_fc_accuracy.txt
+
+--mxfp8 adds a fourth row (a-trous graph): the mxfp8 handle, which is not calibrated; the allowance is applied to it.
+
+    python tools/fp8_accuracy.py --mxfp8 --out profiles/mxfp8_accuracy.txt
 """
 import argparse
 import contextlib
@@ -42,9 +46,12 @@ def main():
     ap.add_argument('--checkpoint', default='', help='evaluate this checkpoint instead of training one')
     ap.add_argument('--calibrate-images', type=int, default=32)
     ap.add_argument('--a-trous', default='true', choices=['true', 'false'], help='false: the fc graph, fp8 under SSD_FP8_BIGK 0 and 1')
+    ap.add_argument('--mxfp8', action='store_true', help='a-trous graph: a fourth row, the mxfp8 handle (no calibration)')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     fc = args.a_trous == 'false'
+    if args.mxfp8 and fc:
+        ap.error('--mxfp8 evaluates the a-trous graph')
     from ssd_tensorflow_amd import train
     from ssd_tensorflow_amd.average_precision import APCalculator, APs2mAP
     from ssd_tensorflow_amd.ssdutils import boxes_from_detection
@@ -85,6 +92,8 @@ def main():
         with Session(0) as sess:
             # (handle name, dtype, SSD_FP8_BIGK while the handle is created)
             handles = [('f32', 'f32', None), ('bf16', 'bf16', None)] + ([('fp8/bigk0', 'fp8', '0'), ('fp8/bigk1', 'fp8', '1')] if fc else [('fp8', 'fp8', None)])
+            if args.mxfp8:
+                handles.append(('mxfp8', 'mxfp8', None))
             for name, dt, bigk in handles:
                 saved = os.environ.get('SSD_FP8_BIGK')
                 if bigk is not None:
@@ -120,7 +129,9 @@ def main():
         last = handles[-1][0]
         diff = results['bf16'][0] - results[last][0]
         say('# one missed object per class changes mAP by %.4f; bf16 - %s = %+.4f: %s' % (allow, last, diff, 'within it' if diff <= allow else 'BELOW it'))
-        say('# fp8 activation scales calibrated on the first %d training images' % args.calibrate_images)
+        if args.mxfp8:
+            say('# bf16 - fp8 = %+.4f' % (results['bf16'][0] - results['fp8'][0]))
+        say('# fp8 activation scales calibrated on the first %d training images' % args.calibrate_images + ('; mxfp8: nothing to calibrate' if args.mxfp8 else ''))
     if args.out:
         with open(args.out, 'w') as f:
             f.write('\n'.join(lines) + '\n')

@@ -14,6 +14,11 @@ e4m3), the same tables with one column per handle, then the kernels of mod_pool5
 by one, with fc6's rate from its executed FLOPs.
 
     python tools/infer_rate.py --a-trous false --out profiles/fp8_fc_infer_rate.txt
+
+--mxfp8 adds the mxfp8 handle as the handle under test beside bf16 and fp8 (a-trous graph): the ratios and verdicts
+are then mxfp8 against each of the two, and the per-layer table has its pools and quantise passes.
+
+    python tools/infer_rate.py --mxfp8 --out profiles/mxfp8_infer_rate.txt
 """
 import argparse
 import ctypes as C
@@ -70,8 +75,11 @@ def main():
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--passes', type=int, default=20)
     ap.add_argument('--a-trous', default='true', choices=['true', 'false'], help="false: the fc graph, three handles (SSD_FP8_BIGK 0 / 1)")
+    ap.add_argument('--mxfp8', action='store_true', help='a-trous graph: a third handle, mxfp8, as the handle under test')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.mxfp8 and args.a_trous == 'false':
+        ap.error('--mxfp8 measures the a-trous graph')
     import torch
     from oracle import boxes as ob, ssdvgg_ref as ref
     from ssd_tensorflow_amd._lib import lib, check
@@ -91,7 +99,7 @@ def main():
         handles = [('bf16', 'bf16', None), ('fp8/bigk0', 'fp8', '0'), ('fp8/bigk1', 'fp8', '1')]      # (name, dtype, SSD_FP8_BIGK)
     else:
         w = ref.init_params(preset, 20, seed=42, alive=True)
-        handles = [('bf16', 'bf16', None), ('fp8', 'fp8', None)]
+        handles = [('bf16', 'bf16', None), ('fp8', 'fp8', None)] + ([('mxfp8', 'mxfp8', None)] if args.mxfp8 else [])
     x = torch.from_numpy(ref.synth_images(np.random.default_rng(5), args.batch, preset)).cuda()
     with Session(0) as sess:
         nets = {}
@@ -146,7 +154,7 @@ def main():
                 per[dt].append(layer_times(nets[dt], x, max(args.passes // 4, 2), lab[dt][-1]))
         layers = [k for k in per['bf16'][0] if all(k in per[dt][0] for dt in nets)]
         say('# per layer on one stream (kernel events, ms per batch): median (min..max); fp8 includes the layer\'s e4m3 outputs')
-        if fc:
+        if fc or args.mxfp8:
             say('# verdict: %s against bf16; a quantise pass behind a bf16 layer counts with that layer' % last)
         say('# %-18s ' % 'layer' + ' '.join('%28s' % dt for dt in nets) + ' %8s  %s' % ('ratio', 'verdict'))
         tot = {dt: 0.0 for dt in nets}
@@ -155,14 +163,19 @@ def main():
             for dt in nets:
                 tot[dt] += statistics.median(cols[dt])
             a, f = cols['bf16'], cols[last]
-            verdict = 'fp8 faster' if max(f) < min(a) else ('fp8 SLOWER' if max(a) < min(f) else 'not separated')
+            tag = 'mxfp8' if args.mxfp8 else 'fp8'
+            verdict = tag + ' faster' if max(f) < min(a) else (tag + ' SLOWER' if max(a) < min(f) else 'not separated')
+            if args.mxfp8:      # ... and against the fp8 handle's row
+                g = cols['fp8']
+                verdict += '; against fp8 %.3f %s' % (statistics.median(g) / max(statistics.median(f), 1e-9),
+                                                      'faster' if max(f) < min(g) else ('SLOWER' if max(g) < min(f) else 'not separated'))
             say('  %-18s ' % k + ' '.join(mmm(cols[dt]) for dt in nets) + ' %8.3f  %s' % (statistics.median(a) / max(statistics.median(f), 1e-9), verdict))
         for dt in nets:
             for k in per[dt][0]:
                 if k not in layers:
                     f = [p.get(k, 0.0) for p in per[dt]]
                     tot[dt] += statistics.median(f)
-                    say('  %-18s only in %s: %s' % (k, dt, mmm(f)) if fc else '  %-18s %28s %s' % (k, '-', mmm(f)))
+                    say('  %-18s only in %s: %s' % (k, dt, mmm(f)) if fc or args.mxfp8 else '  %-18s %28s %s' % (k, '-', mmm(f)))
         say('# sum of the kernels per batch, one stream: ' + ', '.join('%s %.3f ms' % (dt, tot[dt]) for dt in nets))
         if fc:
             # ---- the kernels around fc6 one by one; fc6's rate from its executed FLOPs 2 * pixels * Ci * Co * taps
