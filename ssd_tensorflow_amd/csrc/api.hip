@@ -1269,6 +1269,14 @@ int ssd_op_conv2d_fwd_mxfp8(const void* x8, const void* xscales, const void* w8,
                    (const unsigned char*)w8, s_w, bias, y, (unsigned char*)y8, (unsigned char*)yscales, out_mode, relu != 0, (hipStream_t)stream);
     API_END
 }
+int ssd_op_conv2d_fwd_mxfp8_bigk(const void* x8, const void* xscales, const void* w8, const float* s_w, const float* bias, void* y, void* y8,
+                                 void* yscales, int out_mode, int b, int hi, int wi, int ci, int ho, int wo, int co, int kh, int kw, int stride,
+                                 int dil, int pad_h, int pad_w, int relu, void* stream) {
+    API_BEGIN
+    conv_bigk_fwd_mxfp8(mk(b, hi, wi, ci, ho, wo, co, kh, kw, stride, dil, pad_h, pad_w), (const unsigned char*)x8, (const unsigned char*)xscales,
+                        (const unsigned char*)w8, s_w, bias, y, (unsigned char*)y8, (unsigned char*)yscales, out_mode, relu != 0, (hipStream_t)stream);
+    API_END
+}
 int ssd_op_maxpool_fwd_mxfp8(const void* x8, const void* xscales, void* y8, void* yscales, int b, int hi, int wi, int c, int ho, int wo, int k,
                              int stride, int pad_h, int pad_w, void* stream) {
     API_BEGIN

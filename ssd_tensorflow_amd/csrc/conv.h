@@ -254,6 +254,13 @@ enum { FP8_OUT_MX = 4, FP8_OUT_BF16_MX = 5 };      // beside FP8_OUT_BF16 and FP
 // must be readable up to its size rounded up to 4 bytes.  Anything unsupported throws before a launch.
 void conv_fwd_mxfp8(const ConvDesc& d, const unsigned char* x8, const unsigned char* xs, const unsigned char* w8, const float* s_w,
                     const float* bias, void* y, unsigned char* y8, unsigned char* ys, int out_mode, bool relu, hipStream_t s);
+// The same contract for 10 ... 121 taps (KH, KW <= 11): the fc graph's 7x7 fc6.  conv_bigk_fwd_fp8_supported's shapes,
+// Co % 32 == 0 for an MX output mode, the scale tensors below the 32-bit offsets; 9 taps or fewer are refused (conv_fwd_mxfp8 runs them).
+bool conv_bigk_fwd_mxfp8_supported(const ConvDesc& d, int out_mode, const char** why);
+// whether the step executor puts such a layer on MX operands (SSD_MXFP8_BIGK, read per handle; unset = 0: conv_mxfp8.hip)
+bool conv_bigk_fwd_mxfp8_worthwhile(const ConvDesc& d);
+void conv_bigk_fwd_mxfp8(const ConvDesc& d, const unsigned char* x8, const unsigned char* xs, const unsigned char* w8, const float* s_w,
+                         const float* bias, void* y, unsigned char* y8, unsigned char* ys, int out_mode, bool relu, hipStream_t s);
 // bf16 or fp32 [rows][C] -> codes [rows][C] + scales [rows][C / 32]; C a multiple of 32
 void quantize_mxfp8(const void* x, bool x_f32, size_t rows, int C, unsigned char* y8, unsigned char* ys, hipStream_t s);
 // max-pooling of MX tensors: the maximum of the dequantised cells per channel, quantised again per block; C a multiple of 32

@@ -581,7 +581,8 @@ void Net::plan_winograd() {
 // fp8 handle.  Eligible: a trunk convolution in front of conv8_1 (no multibox head, not in the tail chain) that
 // reads an activation (not the image), has Ci % 64 == 0 and is of a shape on which the fp8 kernel measured faster than the bf16 one
 // (conv_fwd_fp8_worthwhile) -- a-trous graph: conv3_2 ... conv5_3, mod_conv6, mod_conv7.  A layer with more than 9 taps (the fc
-// graph's 7x7 mod_conv6) runs on conv_bigk_fwd_fp8 where conv_bigk_fwd_fp8_worthwhile says so (SSD_FP8_BIGK); otherwise it stays on
+// graph's 7x7 mod_conv6) runs on conv_bigk_fwd_fp8 where conv_bigk_fwd_fp8_worthwhile says so (SSD_FP8_BIGK; an mxfp8 handle: on conv_bigk_fwd_mxfp8 where
+// conv_bigk_fwd_mxfp8_worthwhile says so, SSD_MXFP8_BIGK); otherwise it stays on
 // conv_bigk_fwd_bf16 with a quantise pass behind it.  A tensor read by such a layer is kept as
 // e4m3 (data8).  A pool between two fp8 layers runs on the bytes and its output shares its input's scale.  Where the e4m3 form is
 // needed behind a bf16 producer (conv3_1's output in the a-trous graph) a quantise pass of its own makes it.  A tensor with any non-fp8 reader (conv4_3: the l2 norm; mod_conv7's output: its head and conv8_1) keeps its
@@ -595,9 +596,11 @@ void Net::plan_fp8() {
         producer[op.out] = i;
         if (op.kind != OP_CONV) continue;
         const ConvDesc d = conv_desc(op, Bmax_);
-        // (mxfp8: there is no MX form of the kernel for more than 9 taps; the fc graph's fc6 stays on bf16 with a quantise pass behind it)
-        const bool kernel8 = conv_bigk(d) ? !mx_ && conv_bigk_fwd_fp8_supported(d, nullptr) && conv_bigk_fwd_fp8_worthwhile(d)
-                                          : conv_fwd_fp8_supported(d, nullptr) && conv_fwd_fp8_worthwhile(d);
+        // (mxfp8: the fc graph's fc6 stays on bf16 with a quantise pass behind it unless SSD_MXFP8_BIGK=1 -- conv_bigk_fwd_mxfp8_worthwhile;
+        // asked with the most demanding output mode, so that whichever form the readers below take can be launched)
+        const bool kernel8 = !conv_bigk(d) ? conv_fwd_fp8_supported(d, nullptr) && conv_fwd_fp8_worthwhile(d)
+                             : mx_         ? conv_bigk_fwd_mxfp8_supported(d, FP8_OUT_BF16_MX, nullptr) && conv_bigk_fwd_mxfp8_worthwhile(d)
+                                           : conv_bigk_fwd_fp8_supported(d, nullptr) && conv_bigk_fwd_fp8_worthwhile(d);
         op.fp8 = op.head < 0 && i < tail_first_ && !tensors_[op.in].data_f32 && kernel8;
     }
     auto need8 = [&](Tensor& t) {
@@ -1163,10 +1166,11 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
                 else if (in.data_f32)
                     conv_fwd_smallc_bf16out(d, xin, params_ + op.w_off, params_ + op.b_off, static_cast<bf16_t*>(yout), op.relu, cs);
                 else if (run8 && op.fp8 && mx_)      // e4m3 operands with block scales; the output in the form(s) its readers take
-                    conv_fwd_mxfp8(d, in.data8 + (size_t)run_b0 * in.per_image(), in.scale8 + (size_t)run_b0 * (in.per_image() / 32), w8_ + op.w_off,
-                                   sw8_ + op.sw_off, params_ + op.b_off, yout, out.data8 ? out.data8 + (size_t)run_b0 * out.per_image() : nullptr,
-                                   out.data8 ? out.scale8 + (size_t)run_b0 * (out.per_image() / 32) : nullptr,
-                                   out.data8 ? (out.wants16 ? FP8_OUT_BF16_MX : FP8_OUT_MX) : FP8_OUT_BF16, op.relu, cs);
+                    (conv_bigk(d) ? conv_bigk_fwd_mxfp8 : conv_fwd_mxfp8)(      // (more than 9 taps: the fc graph's mod_conv6 under SSD_MXFP8_BIGK=1)
+                        d, in.data8 + (size_t)run_b0 * in.per_image(), in.scale8 + (size_t)run_b0 * (in.per_image() / 32), w8_ + op.w_off,
+                        sw8_ + op.sw_off, params_ + op.b_off, yout, out.data8 ? out.data8 + (size_t)run_b0 * out.per_image() : nullptr,
+                        out.data8 ? out.scale8 + (size_t)run_b0 * (out.per_image() / 32) : nullptr,
+                        out.data8 ? (out.wants16 ? FP8_OUT_BF16_MX : FP8_OUT_MX) : FP8_OUT_BF16, op.relu, cs);
                 else if (run8 && op.fp8)      // e4m3 operands; the output in the form(s) its readers take
                     (conv_bigk(d) ? conv_bigk_fwd_fp8 : conv_fwd_fp8)(      // (more than 9 taps: the fc graph's mod_conv6)
                         d, in.data8 + (size_t)run_b0 * in.per_image(), w8_ + op.w_off, in.scale, sw8_ + op.sw_off, params_ + op.b_off, yout,

@@ -179,7 +179,8 @@ def main(argv=None):
     parser.add_argument('--a-trous', type=str2bool, default='True', help='graph when no checkpoint is given: a-trous (true) or fc (false); a checkpoint carries its own')
     parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16', 'fp8', 'mxfp8'],
                         help='f32, bf16 activations on the bf16 matrix cores, fp8: the bf16 net with conv3_2 ... mod_conv7 on e4m3 operands '
-                             '(calibrated scales), or mxfp8: the same layers with block scales chosen from the data (no calibration)')
+                             '(calibrated scales), or mxfp8: the same layers with block scales chosen from the data (no calibration; the fc graph\'s 7x7 fc6 joins '
+                             'them when the environment has SSD_MXFP8_BIGK=1)')
     add_fp8_arguments(parser)
     parser.add_argument('--decoder', default='gpu', choices=['pillow', 'gpu'],
                         help='gpu: baseline JPEGs are decoded on the GPU, other files as with pillow (same pixels); pillow: every file is decoded on the host')

@@ -174,7 +174,8 @@ class SSDVGG:
         filter mirrors on the bf16 matrix cores; fp32 master weights, loss and optimizer), or -- training=False only --
         'fp8': the bf16 net with conv3_2 ... mod_conv7 (the fc graph's 7x7 fc6 included) on e4m3 operands; call calibrate_fp8 or set
         fp8_scales before infer; or 'mxfp8': the same layers with one E8M0 block scale per pixel and 32 channels, chosen by each
-        producer from its own values -- no calibration, infer works at once and an image's result depends on that image alone.
+        producer from its own values -- no calibration, infer works at once and an image's result depends on that image alone
+        (the fc graph's 7x7 fc6 stays on bf16 unless the environment has SSD_MXFP8_BIGK=1 when the net is built).
         a_trous=False builds the reference's other graph (ssdvgg.py:210-228): VGG-16's fc6 / fc7 as a 7x7 and a
         1x1 convolution, 4096 wide, variables fc6/* and fc7/*; its weights come from `<vgg_dir>/vgg16_ssd_fc.npz`."""
         self.num_classes = num_classes + 1

@@ -15,6 +15,11 @@ fc6 on the bf16 kernel) and under SSD_FP8_BIGK=1 (fc6 on e4m3), and the allowanc
 --mxfp8 adds a fourth row (a-trous graph): the mxfp8 handle, which is not calibrated; the allowance is applied to it.
 
     python tools/fp8_accuracy.py --mxfp8 --out profiles/mxfp8_accuracy.txt
+
+--a-trous false --mxfp8: the fc graph with the mxfp8 handle under SSD_MXFP8_BIGK=0 and, last, under SSD_MXFP8_BIGK=1 (fc6 on MX
+operands); the allowance is applied to the last.
+
+    python tools/fp8_accuracy.py --a-trous false --mxfp8 --out profiles/mxfp8_fc_accuracy.txt
 """
 import argparse
 import contextlib
@@ -46,12 +51,10 @@ def main():
     ap.add_argument('--checkpoint', default='', help='evaluate this checkpoint instead of training one')
     ap.add_argument('--calibrate-images', type=int, default=32)
     ap.add_argument('--a-trous', default='true', choices=['true', 'false'], help='false: the fc graph, fp8 under SSD_FP8_BIGK 0 and 1')
-    ap.add_argument('--mxfp8', action='store_true', help='a-trous graph: a fourth row, the mxfp8 handle (no calibration)')
+    ap.add_argument('--mxfp8', action='store_true', help='further rows: the mxfp8 handle (no calibration); fc graph: under SSD_MXFP8_BIGK 0 and 1')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     fc = args.a_trous == 'false'
-    if args.mxfp8 and fc:
-        ap.error('--mxfp8 evaluates the a-trous graph')
     from ssd_tensorflow_amd import train
     from ssd_tensorflow_amd.average_precision import APCalculator, APs2mAP
     from ssd_tensorflow_amd.ssdutils import boxes_from_detection
@@ -90,22 +93,27 @@ def main():
         say('# held-out set: %d images, objects per class %s' % (sum(len(g) for _, g in held), dict(sorted(counts.items()))))
         results = {}
         with Session(0) as sess:
-            # (handle name, dtype, SSD_FP8_BIGK while the handle is created)
-            handles = [('f32', 'f32', None), ('bf16', 'bf16', None)] + ([('fp8/bigk0', 'fp8', '0'), ('fp8/bigk1', 'fp8', '1')] if fc else [('fp8', 'fp8', None)])
-            if args.mxfp8:
-                handles.append(('mxfp8', 'mxfp8', None))
-            for name, dt, bigk in handles:
-                saved = os.environ.get('SSD_FP8_BIGK')
-                if bigk is not None:
-                    os.environ['SSD_FP8_BIGK'] = bigk
+            # (handle name, dtype, the switch set while the handle is created, its value)
+            F8, MX = 'SSD_FP8_BIGK', 'SSD_MXFP8_BIGK'
+            handles = [('f32', 'f32', None, None), ('bf16', 'bf16', None, None)]
+            if fc and args.mxfp8:
+                handles += [('fp8', 'fp8', F8, '1'), ('mxfp8/bigk0', 'mxfp8', MX, '0'), ('mxfp8/bigk1', 'mxfp8', MX, '1')]
+            elif fc:
+                handles += [('fp8/bigk0', 'fp8', F8, '0'), ('fp8/bigk1', 'fp8', F8, '1')]
+            else:
+                handles += [('fp8', 'fp8', None, None)] + ([('mxfp8', 'mxfp8', None, None)] if args.mxfp8 else [])
+            for name, dt, switch, bigk in handles:
+                saved = os.environ.get(switch) if switch else None
+                if switch:
+                    os.environ[switch] = bigk
                 try:
                     net = SSDVGG(sess, 'vgg300')
                     net.build_from_metagraph(None, ckpt, max_batch=32, dtype=dt)
                 finally:
-                    if bigk is not None:
-                        os.environ.pop('SSD_FP8_BIGK')
+                    if switch:
+                        os.environ.pop(switch)
                         if saved is not None:
-                            os.environ['SSD_FP8_BIGK'] = saved
+                            os.environ[switch] = saved
                 assert net.a_trous == (not fc)
                 if dt == 'fp8':
                     net.calibrate_fp8(calib)
@@ -124,7 +132,7 @@ def main():
                 net.close()
         say('# VOC07 (11-point) AP on the held-out images, detections above 0.5 after NMS')
         for dt, (m, aps, ndet) in results.items():
-            say(('  %-9s' if fc else '  %-5s') % dt + ' mAP %.4f   %s   (%d detections)' % (m, '  '.join('%s %.4f' % (k, v) for k, v in sorted(aps.items())), ndet))
+            say(('  %-11s' if fc else '  %-5s') % dt + ' mAP %.4f   %s   (%d detections)' % (m, '  '.join('%s %.4f' % (k, v) for k, v in sorted(aps.items())), ndet))
         allow = one_miss_allowance(counts)
         last = handles[-1][0]
         diff = results['bf16'][0] - results[last][0]

@@ -19,6 +19,12 @@ by one, with fc6's rate from its executed FLOPs.
 are then mxfp8 against each of the two, and the per-layer table has its pools and quantise passes.
 
     python tools/infer_rate.py --mxfp8 --out profiles/mxfp8_infer_rate.txt
+
+--a-trous false --mxfp8 measures the fc graph's mxfp8 handle with its 7x7 fc6 on MX operands: four handles from the
+same weights -- bf16, fp8 (SSD_FP8_BIGK=1, calibrated), mxfp8 under SSD_MXFP8_BIGK=0 (fc6 on conv_bigk_fwd_bf16 with a quantise pass
+behind it) and, the handle under test, mxfp8 under SSD_MXFP8_BIGK=1.
+
+    python tools/infer_rate.py --a-trous false --mxfp8 --out profiles/mxfp8_fc_infer_rate.txt
 """
 import argparse
 import ctypes as C
@@ -74,12 +80,11 @@ def main():
     ap.add_argument('--batch', type=int, default=128)
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--passes', type=int, default=20)
-    ap.add_argument('--a-trous', default='true', choices=['true', 'false'], help="false: the fc graph, three handles (SSD_FP8_BIGK 0 / 1)")
-    ap.add_argument('--mxfp8', action='store_true', help='a-trous graph: a third handle, mxfp8, as the handle under test')
+    ap.add_argument('--a-trous', default='true', choices=['true', 'false'], help="false: the fc graph, three handles (SSD_FP8_BIGK 0 / 1)"
+                    "; with --mxfp8 four (SSD_MXFP8_BIGK 0 / 1)")
+    ap.add_argument('--mxfp8', action='store_true', help='a further handle, mxfp8, as the handle under test (fc graph: under SSD_MXFP8_BIGK=1)')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
-    if args.mxfp8 and args.a_trous == 'false':
-        ap.error('--mxfp8 measures the a-trous graph')
     import torch
     from oracle import boxes as ob, ssdvgg_ref as ref
     from ssd_tensorflow_amd._lib import lib, check
@@ -96,25 +101,30 @@ def main():
         sys.path.insert(0, os.path.join(ROOT, 'tests'))
         import fc_ref
         w = fc_ref.init_params(preset, 20, seed=42)
-        handles = [('bf16', 'bf16', None), ('fp8/bigk0', 'fp8', '0'), ('fp8/bigk1', 'fp8', '1')]      # (name, dtype, SSD_FP8_BIGK)
+        # (name, dtype, the switch read when the handle is created, its value)
+        if args.mxfp8:
+            handles = [('bf16', 'bf16', None, None), ('fp8', 'fp8', 'SSD_FP8_BIGK', '1'), ('mxfp8/bigk0', 'mxfp8', 'SSD_MXFP8_BIGK', '0'),
+                       ('mxfp8/bigk1', 'mxfp8', 'SSD_MXFP8_BIGK', '1')]
+        else:
+            handles = [('bf16', 'bf16', None, None), ('fp8/bigk0', 'fp8', 'SSD_FP8_BIGK', '0'), ('fp8/bigk1', 'fp8', 'SSD_FP8_BIGK', '1')]
     else:
         w = ref.init_params(preset, 20, seed=42, alive=True)
-        handles = [('bf16', 'bf16', None), ('fp8', 'fp8', None)] + ([('mxfp8', 'mxfp8', None)] if args.mxfp8 else [])
+        handles = [('bf16', 'bf16', None, None), ('fp8', 'fp8', None, None)] + ([('mxfp8', 'mxfp8', None, None)] if args.mxfp8 else [])
     x = torch.from_numpy(ref.synth_images(np.random.default_rng(5), args.batch, preset)).cuda()
     with Session(0) as sess:
         nets = {}
-        for name, dt, bigk in handles:
-            saved = os.environ.get('SSD_FP8_BIGK')
-            if bigk is not None:
-                os.environ['SSD_FP8_BIGK'] = bigk      # read when the handle is created
+        for name, dt, switch, bigk in handles:
+            saved = os.environ.get(switch) if switch else None
+            if switch:
+                os.environ[switch] = bigk      # read when the handle is created
             try:
                 nets[name] = SSDVGG(sess, args.preset)
                 nets[name].build_from_vgg(None, 20, a_trous=not fc, max_batch=args.batch, training=False, weights=w, dtype=dt)
             finally:
-                if bigk is not None:
-                    os.environ.pop('SSD_FP8_BIGK')
+                if switch:
+                    os.environ.pop(switch)
                     if saved is not None:
-                        os.environ['SSD_FP8_BIGK'] = saved
+                        os.environ[switch] = saved
             if dt == 'fp8':
                 nets[name].calibrate_fp8(x[:32])
         last = handles[-1][0]                 # the handle under test: every comparison is this one against another
@@ -124,17 +134,17 @@ def main():
             % (args.preset, ' fc graph' if fc else '', args.batch, args.rounds, args.passes, torch.cuda.get_device_name(0)))
         if fc:
             for name in nets:
-                if name != 'bf16':
+                if nets[name].dtype == 'fp8':
                     say('# %s scales: %s' % (name, ' '.join(nets[name].fp8_scales)))
         ms = {dt: [] for dt in nets}
         for r in range(args.rounds):
             for dt in nets:
                 ms[dt].append(timed_passes(nets[dt], x, args.passes))
-        say('# %-9s %14s %26s %12s' % ('handle', 'ms/batch', '(min..max over rounds)', 'ms/image') if fc else
+        say('# %-11s %14s %26s %12s' % ('handle', 'ms/batch', '(min..max over rounds)', 'ms/image') if fc else
             '# %-6s %14s %26s %12s' % ('handle', 'ms/batch', '(min..max over rounds)', 'ms/image'))
         for dt in nets:
             v = ms[dt]
-            say(('  %-9s %14.3f %15.3f..%.3f %14.4f' if fc else '  %-6s %14.3f %15.3f..%.3f %14.4f')
+            say(('  %-11s %14.3f %15.3f..%.3f %14.4f' if fc else '  %-6s %14.3f %15.3f..%.3f %14.4f')
                 % (dt, statistics.median(v), min(v), max(v), statistics.median(v) / args.batch))
         for other in [h[0] for h in handles[:-1]]:
             ratios = [a / b for a, b in zip(ms[other], ms[last])]
@@ -165,10 +175,10 @@ def main():
             a, f = cols['bf16'], cols[last]
             tag = 'mxfp8' if args.mxfp8 else 'fp8'
             verdict = tag + ' faster' if max(f) < min(a) else (tag + ' SLOWER' if max(a) < min(f) else 'not separated')
-            if args.mxfp8:      # ... and against the fp8 handle's row
-                g = cols['fp8']
-                verdict += '; against fp8 %.3f %s' % (statistics.median(g) / max(statistics.median(f), 1e-9),
-                                                      'faster' if max(f) < min(g) else ('SLOWER' if max(g) < min(f) else 'not separated'))
+            for other in (['fp8'] + (['mxfp8/bigk0'] if fc else []) if args.mxfp8 else []):      # ... and against these handles' rows
+                g = cols[other]
+                verdict += '; against %s %.3f %s' % (other, statistics.median(g) / max(statistics.median(f), 1e-9),
+                                                     'faster' if max(f) < min(g) else ('SLOWER' if max(g) < min(f) else 'not separated'))
             say('  %-18s ' % k + ' '.join(mmm(cols[dt]) for dt in nets) + ' %8.3f  %s' % (statistics.median(a) / max(statistics.median(f), 1e-9), verdict))
         for dt in nets:
             for k in per[dt][0]:
@@ -188,12 +198,15 @@ def main():
                     if layer in ('mod_pool5', 'mod_conv6', 'mod_conv7', 'filters'):
                         v = [p.get(label, 0.0) for p in lab[dt]]
                         rate = '  %.0f TF/s' % (flops6 / (statistics.median(v) * 1e-3) / 1e12) if layer == 'mod_conv6' and 'conv' in label.split(':')[0] else ''
-                        say('  %-10s %-44s %s%s' % (dt, label, mmm(v), rate))
-            k0, k1 = [p['mod_conv6'] for p in per['fp8/bigk0']], [p['mod_conv6'] for p in per['fp8/bigk1']]
+                        say('  %-11s %-44s %s%s' % (dt, label, mmm(v), rate))
+            n0, n1 = handles[-2][0], handles[-1][0]      # the same dtype with the switch 0 and 1
+            k0, k1 = [p['mod_conv6'] for p in per[n0]], [p['mod_conv6'] for p in per[n1]]
             a = [p['mod_conv6'] for p in per['bf16']]
-            say('# rule (DESIGN.md 18): mod_conv6 row max(fp8/bigk1) %.4f %s min(bf16) %.4f; whole handle max(bigk1) %.3f %s min(bigk0) %.3f'
-                % (max(k1), '<' if max(k1) < min(a) else '>=', min(a), max(ms['fp8/bigk1']), '<' if max(ms['fp8/bigk1']) < min(ms['fp8/bigk0']) else '>=',
-                   min(ms['fp8/bigk0'])))
+            say('# rule (DESIGN.md 18): mod_conv6 row max(%s) %.4f %s min(bf16) %.4f; whole handle max(bigk1) %.3f %s min(bigk0) %.3f'
+                % (n1, max(k1), '<' if max(k1) < min(a) else '>=', min(a), max(ms[n1]), '<' if max(ms[n1]) < min(ms[n0]) else '>=', min(ms[n0])))
+            if args.mxfp8:
+                say('# mod_conv6 row (a quantise pass behind a bf16 layer counts with it): max(%s) %.4f %s min(%s) %.4f'
+                    % (n1, max(k1), '<' if max(k1) < min(k0) else '>=', n0, min(k0)))
             say('# %s: not measured' % ('vgg512' if args.preset == 'vgg300' else 'vgg300'))
     if args.out:
         with open(args.out, 'w') as f:
