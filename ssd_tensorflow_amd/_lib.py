@@ -132,6 +132,10 @@ SIGNATURES = {
     'ssd_detect_fetch': (i32, [handle, i32, vp, vp, vp, vp, vp]),
     'ssd_detect_host': (i32, [handle, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), p_i32, p_i32]),
     'ssd_nms_boxes': (i32, [i32, i32, vp, vp, vp, C.c_double, vp, p_i32]),
+    'ssd_merge_tiles_limits': (i32, [p_i32, p_i32, p_i32]),
+    'ssd_merge_tiles_ws_bytes': (sz, [i32, i32]),
+    'ssd_merge_tiles_dev': (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'ssd_merge_tiles': (i32, [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     'ssd_set_overlap': (i32, [handle, i32]),
     'ssd_profile_enable': (i32, [handle, i32]),
     'ssd_profile_report': (i32, [handle, C.c_char_p, sz]),

@@ -343,6 +343,74 @@ int ssd_nms_boxes(int device, int n, const int* box_abs, const float* conf, cons
     API_END
 }
 
+static_assert(sizeof(ssd_tile) == sizeof(MergeTile), "ssd_tile is boxes.h's MergeTile");
+
+int ssd_merge_tiles_limits(int* max_tiles, int* max_candidates, int* lds_keys) {
+    API_BEGIN
+    if (max_tiles) *max_tiles = MERGE_MAX_TILES;
+    if (max_candidates) *max_candidates = MERGE_MAX_CAND;
+    if (lds_keys) *lds_keys = MERGE_LDS_KEYS;
+    API_END
+}
+
+size_t ssd_merge_tiles_ws_bytes(int n_tiles, int tile_cap) {
+    try {
+        return merge_tiles_ws_bytes(n_tiles, tile_cap);
+    } catch (const std::exception& e) {
+        ssd::set_error("%s", e.what());
+        return 0;
+    }
+}
+
+int ssd_merge_tiles_dev(const ssd_tile* tiles, int n_tiles, int n_images, int tile_cap, const int* count_dev, const float* conf_dev,
+                        const int* cls_dev, const int* idx_dev, const int* box_dev, int edge_margin, int max_out, int out_cap,
+                        int* count_out, float* conf_out, int* cls_out, int* idx_out, int* tile_out, int* box_out, void* ws_dev,
+                        void* stream) {
+    API_BEGIN
+    merge_tiles(reinterpret_cast<const MergeTile*>(tiles), n_tiles, n_images, tile_cap, count_dev, conf_dev, cls_dev, idx_dev, box_dev,
+                edge_margin, max_out, out_cap, count_out, conf_out, cls_out, idx_out, tile_out, box_out, ws_dev, (hipStream_t)stream);
+    API_END
+}
+
+int ssd_merge_tiles(int device, const ssd_tile* tiles, int n_tiles, int n_images, int tile_cap, const int* count, const float* conf,
+                    const int* cls, const int* idx, const int* box, int edge_margin, int max_out, int out_cap, int* count_out,
+                    float* conf_out, int* cls_out, int* idx_out, int* tile_out, int* box_out) {
+    API_BEGIN
+    SSD_REQUIRE(tiles && count && conf && cls && idx && box && count_out && cls_out && box_out, "ssd_merge_tiles: null argument");
+    merge_tiles_check(reinterpret_cast<const MergeTile*>(tiles), n_tiles, n_images, tile_cap, out_cap);
+    const size_t ws_bytes = merge_tiles_ws_bytes(n_tiles, tile_cap);
+    for (int t = 0; t < n_tiles; ++t)
+        for (int j = 0; j < std::min(count[t], tile_cap); ++j) {
+            const int c = cls[(size_t)t * tile_cap + j];
+            SSD_REQUIRE(c >= 0 && c < MAX_CLASSES, "ssd_merge_tiles: tile %d, record %d: class id %d outside 0..%d", t, j, c,
+                        MAX_CLASSES - 1);
+        }
+    DeviceGuard dev_guard_(device);
+    const size_t nin = (size_t)n_tiles * tile_cap, nout = (size_t)n_images * out_cap;
+    DevBuf dcount((size_t)n_tiles * 4), dconf(nin * 4), dcls(nin * 4), didx(nin * 4), dbox(nin * 16), ws(ws_bytes);
+    DevBuf ocount((size_t)n_images * 4), oconf(nout * 4), ocls(nout * 4), oidx(nout * 4), otile(nout * 4), obox(nout * 16);
+    HIP_OK(hipMemcpy(dcount.p, count, (size_t)n_tiles * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(dconf.p, conf, nin * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(dcls.p, cls, nin * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(didx.p, idx, nin * 4, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(dbox.p, box, nin * 16, hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(oconf.p, 0, nout * 4));
+    HIP_OK(hipMemset(ocls.p, 0, nout * 4));
+    HIP_OK(hipMemset(oidx.p, 0, nout * 4));
+    HIP_OK(hipMemset(otile.p, 0, nout * 4));
+    HIP_OK(hipMemset(obox.p, 0, nout * 16));
+    merge_tiles(reinterpret_cast<const MergeTile*>(tiles), n_tiles, n_images, tile_cap, dcount.as<int>(), dconf.as<float>(),
+                dcls.as<int>(), didx.as<int>(), dbox.as<int>(), edge_margin, max_out, out_cap, ocount.as<int>(), oconf.as<float>(),
+                ocls.as<int>(), oidx.as<int>(), otile.as<int>(), obox.as<int>(), ws.p, nullptr);
+    HIP_OK(hipMemcpy(count_out, ocount.p, (size_t)n_images * 4, hipMemcpyDeviceToHost));
+    if (conf_out) HIP_OK(hipMemcpy(conf_out, oconf.p, nout * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(cls_out, ocls.p, nout * 4, hipMemcpyDeviceToHost));
+    if (idx_out) HIP_OK(hipMemcpy(idx_out, oidx.p, nout * 4, hipMemcpyDeviceToHost));
+    if (tile_out) HIP_OK(hipMemcpy(tile_out, otile.p, nout * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(box_out, obox.p, nout * 16, hipMemcpyDeviceToHost));
+    API_END
+}
+
 int ssd_average_precision(int device, int n_det, const float* det_box, const float* det_conf, const int* det_cls,
                           const int* det_sample, int n_gt, const double* gt_box, const int* gt_cls, const int* gt_sample,
                           int num_classes, double minoverlap, double* ap_out, int* present_out) {

@@ -59,4 +59,22 @@ size_t nms_boxes_ws_bytes(int n, int ngroups);
 void nms_boxes_device(int n, int ngroups, const int* boxes, const float* conf, const int* group, double thr, int* keep, void* ws,
                       hipStream_t s);
 
+// Tiled detection: the decode_boxes records of a picture's tiles -> one detection list per picture.
+// MergeTile is ssd_tile of the public header: a window (x0, y0, w, h) of a picture of img_w x img_h source pixels,
+// interior = which of its edges lie inside the picture (1 left, 2 right, 4 top, 8 bottom), image = the picture's index.
+struct MergeTile { int x0, y0, w, h, img_w, img_h, interior, image; };
+constexpr int MERGE_MAX_TILES = 256;       // tiles of one picture (8 bits of the sort key)
+constexpr int MERGE_MAX_CAND = 32768;      // tiles of one picture * tile_cap (one survivor flag each in LDS)
+constexpr int MERGE_LDS_KEYS = 2048;       // up to this many candidates (rounded up to a power of two) the sort runs in LDS
+constexpr int MERGE_MAX_SIDE = 1000000;    // picture side: keeps 1000 * origin + 999 * extent below 2^31
+size_t merge_tiles_ws_bytes(int n_tiles, int tile_cap);
+// tiles: HOST array, pictures ascending 0 .. n_images-1 (copied by the call); count [n_tiles], conf / cls / idx [n_tiles][tile_cap],
+// box [n_tiles][tile_cap][4] as detect() writes them with nms = false and out_cap = tile_cap; the outputs as DetectOut per
+// picture plus tile_out (index of the tile inside its picture); conf_out, idx_out, tile_out may be null.  box and box_out
+// 16-byte aligned.  Asynchronous on s; every limit is checked before anything is enqueued.
+void merge_tiles_check(const MergeTile* tiles, int n_tiles, int n_images, int tile_cap, int out_cap);      // the limits alone
+void merge_tiles(const MergeTile* tiles, int n_tiles, int n_images, int tile_cap, const int* count, const float* conf, const int* cls,
+                 const int* idx, const int* box, int edge_margin, int max_out, int out_cap, int* count_out, float* conf_out,
+                 int* cls_out, int* idx_out, int* tile_out, int* box_out, void* ws, hipStream_t s);
+
 }  // namespace ssd

@@ -5,6 +5,7 @@
 #include "boxes.h"
 #include <cmath>
 #include <climits>
+#include <vector>
 
 namespace ssd {
 
@@ -1037,6 +1038,327 @@ void detect(int A, int num_classes, const double* anchors, const float* pred, in
             hipLaunchKernelGGL(detect_image_kernel<128>, dim3(B), dim3(DET_THREADS), 0, s, a);
         else
             hipLaunchKernelGGL(detect_image_kernel<32>, dim3(B), dim3(DET_THREADS), 0, s, a);
+    }
+    HIP_OK(hipGetLastError());
+}
+
+// =================================================================================
+// tiled detection: the boxes of a picture's tiles merged into one detection list
+// =================================================================================
+// One workgroup per picture.  Its tiles' decode_boxes records (ssd_decode_nms_dev with nms = 0: confidence order, integer
+// boxes on the tile's 1000 grid) are gathered, records that an interior tile edge has cut are dropped, and every survivor becomes
+//   pre-key = order(conf) << 30 | (255 - tile) << 22 | (32767 - anchor) << 7 | class      (62 bits)
+// stored densely (ballot prefix, no atomics on memory) with its source slot beside it.  A class' place among the groups
+// is the place of its best record in the confidence-sorted union (defaultdict, ssdutils.py:311-314), i.e. the rank of
+// max(pre-key) per class, which an LDS atomicMax finds without a sort.  ONE descending sort of
+//   key = (127 - class rank) << 55 | pre-key >> 7
+// then yields the output order: class groups in first-appearance order, inside a group confidence descending, equal
+// confidences by tile, then anchor.  The sorted records are mapped into the picture's 1000 grid, suppressed per class by
+// nms_segment (one wave per class) and emitted in order.  Up to MRG_LDS_KEYS candidates sort in LDS, more in the picture's
+// (L2-resident) workspace region.
+__device__ __forceinline__ unsigned float_order_bits(float f);      // (defined with nms_boxes_kernel below)
+constexpr int MRG_THREADS = 512;
+constexpr int MRG_WAVES = MRG_THREADS / 64;
+constexpr int MRG_NCLS = 128;
+static_assert(MERGE_MAX_TILES <= 256 && MAX_CLASSES < MRG_NCLS, "key fields");
+
+struct MergeArgs {
+    const MergeTile* tiles;     // [n_tiles]
+    const int* img_first;       // [n_images + 1] first tile of every picture
+    const int* reg_off;         // [n_images] first workspace element of every picture
+    int tile_cap, edge_margin, max_out, out_cap;
+    const int* count; const float* conf; const int* cls; const int* idx; const int* box;
+    u64* keys; unsigned* vals; int4* mbox; int4* nbox;
+    int* count_out; float* conf_out; int* cls_out; int* idx_out; int* tile_out; int* box_out;
+};
+
+// descending bitonic sort of n2 (power of two) unique keys with a 32-bit payload by one workgroup
+__device__ __forceinline__ void merge_sort_desc(u64* keys, unsigned* vals, int n2) {
+    for (int k = 2; k <= n2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = threadIdx.x; i < n2; i += MRG_THREADS) {
+                const int ixj = i ^ j;
+                if (ixj > i) {
+                    const u64 a = keys[i], b = keys[ixj];
+                    const bool up = (i & k) == 0;
+                    if (up ? (a < b) : (a > b)) {
+                        const unsigned va = vals[i], vb = vals[ixj];
+                        keys[i] = b; keys[ixj] = a;
+                        vals[i] = vb; vals[ixj] = va;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// a tile-grid coordinate (0..999) on the picture's 1000 grid: floor((1000 * origin + v * extent) / picture), at most 999.
+// origin + extent <= picture <= MERGE_MAX_SIDE keeps the numerator below 2^31.
+__device__ __forceinline__ int merge_map(int v, int origin, int extent, int picture) {
+    const unsigned num = 1000u * (unsigned)origin + (unsigned)min(max(v, 0), 999) * (unsigned)extent;
+    return min((int)(num / (unsigned)picture), 999);
+}
+
+__global__ __launch_bounds__(MRG_THREADS) void merge_tiles_kernel(MergeArgs p) {
+    __shared__ __attribute__((aligned(16))) u64 lkeys[MERGE_LDS_KEYS];
+    __shared__ unsigned lvals[MERGE_LDS_KEYS];
+    __shared__ unsigned char alive[MERGE_MAX_CAND];
+    __shared__ int s_tcnt[MERGE_MAX_TILES];
+    __shared__ u64 cmax[MRG_NCLS];
+    __shared__ int ccount[MRG_NCLS], crank[MRG_NCLS], segstart[MRG_NCLS + 1];
+    __shared__ int s_npresent, s_wtot[MRG_WAVES];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int T0 = p.img_first[b], nt = p.img_first[b + 1] - T0;
+    const int cap = p.tile_cap;
+    const int slots = nt * cap;                              // <= MERGE_MAX_CAND (checked on the host)
+    const size_t R = (size_t)p.reg_off[b];
+    u64* gkeys = p.keys + R;
+    unsigned* gvals = p.vals + R;
+    int4* mbox = p.mbox + R;
+    int4* nbox = p.nbox + R;
+    const int4* box_in = reinterpret_cast<const int4*>(p.box);
+
+    for (int t = tid; t < nt; t += MRG_THREADS) s_tcnt[t] = min(max(p.count[T0 + t], 0), cap);      // count may exceed the cap
+    if (tid < MRG_NCLS) { cmax[tid] = 0ull; ccount[tid] = 0; }
+    __syncthreads();
+
+    // ---- gather, edge drop, dense pre-keys ------------------------------------------------------------
+    int n = 0;
+    for (int f0 = 0; f0 < slots; f0 += MRG_THREADS) {
+        const int f = f0 + tid;
+        bool ok = false;
+        u64 pre = 0ull;
+        if (f < slots) {
+            const int t = f / cap, j = f - t * cap;
+            if (j < s_tcnt[t]) {
+                const size_t src = (size_t)(T0 + t) * cap + j;
+                const int4 bx = box_in[src];                  // xmin, xmax, ymin, ymax
+                const int in = p.tiles[T0 + t].interior, m = p.edge_margin;
+                const bool cut = m >= 0 && (((in & 1) && bx.x <= m) || ((in & 2) && bx.y >= 999 - m) || ((in & 4) && bx.z <= m) ||
+                                            ((in & 8) && bx.w >= 999 - m));
+                if (!cut) {
+                    ok = true;
+                    const float cf = p.conf[src] + 0.f;       // -0 orders as +0: by float value
+                    pre = ((u64)float_order_bits(cf) << 30) | ((u64)(255 - t) << 22) | ((u64)(32767 - (p.idx[src] & 32767)) << 7) |
+                          (u64)(p.cls[src] & (MRG_NCLS - 1));
+                }
+            }
+        }
+        const u64 bal = __ballot(ok);
+        if (lane == 0) s_wtot[wave] = __popcll(bal);
+        __syncthreads();
+        int wbase = n, tot = 0;
+#pragma unroll
+        for (int i = 0; i < MRG_WAVES; ++i) {
+            if (i < wave) wbase += s_wtot[i];
+            tot += s_wtot[i];
+        }
+        if (ok) {
+            const int g = wbase + __popcll(bal & ((1ull << lane) - 1ull));
+            const int c = (int)(pre & (u64)(MRG_NCLS - 1));
+            gkeys[g] = pre;
+            gvals[g] = (unsigned)f;
+            atomicMax(reinterpret_cast<unsigned long long*>(&cmax[c]), (unsigned long long)pre);
+            atomicAdd(&ccount[c], 1);
+        }
+        n += tot;
+        __syncthreads();
+    }
+
+    // ---- class groups in first-appearance order of the sorted union = by their best record ------------
+    if (tid < MRG_NCLS) {
+        const bool present = ccount[tid] > 0;
+        const u64 mine = cmax[tid];
+        int r = 0, np = 0;
+        for (int c = 0; c < MRG_NCLS; ++c) {
+            const bool pc = ccount[c] > 0;
+            r += (pc && cmax[c] > mine) ? 1 : 0;
+            np += pc ? 1 : 0;
+        }
+        crank[tid] = present ? r : MRG_NCLS - 1;
+        if (tid == 0) { s_npresent = np; segstart[np] = n; }
+    }
+    __syncthreads();
+
+    // ---- the one sort -----------------------------------------------------------------------------------
+    const int n2 = next_pow2(n > 1 ? n : 1);
+    const bool in_lds = n2 <= MERGE_LDS_KEYS;
+    if (in_lds) {
+        for (int i = tid; i < n2; i += MRG_THREADS) {
+            u64 k = 0ull;                                     // padding sorts last: a real key's rank field is >= 1
+            if (i < n) {
+                const u64 pre = gkeys[i];
+                k = ((u64)(MRG_NCLS - 1 - crank[(int)(pre & (u64)(MRG_NCLS - 1))]) << 55) | (pre >> 7);
+                lvals[i] = gvals[i];
+            } else {
+                lvals[i] = 0u;
+            }
+            lkeys[i] = k;
+        }
+        __syncthreads();
+        merge_sort_desc(lkeys, lvals, n2);
+        for (int i = tid; i < n; i += MRG_THREADS) { gkeys[i] = lkeys[i]; gvals[i] = lvals[i]; }
+    } else {
+        for (int i = tid; i < n2; i += MRG_THREADS) {         // n2 <= the region's size, a power of two >= slots
+            u64 k = 0ull;
+            if (i < n) {
+                const u64 pre = gkeys[i];
+                k = ((u64)(MRG_NCLS - 1 - crank[(int)(pre & (u64)(MRG_NCLS - 1))]) << 55) | (pre >> 7);
+            } else {
+                gvals[i] = 0u;
+            }
+            gkeys[i] = k;
+        }
+        __syncthreads();
+        merge_sort_desc(gkeys, gvals, n2);
+    }
+    __syncthreads();
+
+    // ---- segment starts, boxes on the picture's grid ----------------------------------------------------
+    for (int q = tid; q < n; q += MRG_THREADS) {
+        const int r = MRG_NCLS - 1 - (int)(gkeys[q] >> 55);
+        if (q == 0 || (MRG_NCLS - 1 - (int)(gkeys[q - 1] >> 55)) != r) segstart[r] = q;
+        const int f = (int)gvals[q];
+        const int t = f / cap, j = f - t * cap;
+        const MergeTile tl = p.tiles[T0 + t];
+        const int4 bx = box_in[(size_t)(T0 + t) * cap + j];
+        int o[4], nb[4];
+        o[0] = merge_map(bx.x, tl.x0, tl.w, tl.img_w); o[1] = merge_map(bx.y, tl.x0, tl.w, tl.img_w);
+        o[2] = merge_map(bx.z, tl.y0, tl.h, tl.img_h); o[3] = merge_map(bx.w, tl.y0, tl.h, tl.img_h);
+        nms_roundtrip(o, nb);
+        mbox[q] = make_int4(o[0], o[1], o[2], o[3]);
+        nbox[q] = make_int4(nb[0], nb[1], nb[2], nb[3]);
+        alive[q] = 1;
+    }
+    __syncthreads();
+
+    // ---- greedy NMS: one wave per class segment ---------------------------------------------------------
+    for (int r = wave; r < s_npresent; r += MRG_WAVES) nms_segment(nbox, alive, segstart[r], segstart[r + 1] - segstart[r], lane);
+    __syncthreads();
+
+    // ---- survivors in order; the caller's [:max_out] ----------------------------------------------------
+    int limit = p.out_cap;
+    if (p.max_out >= 0 && p.max_out < limit) limit = p.max_out;
+    int total = 0;
+    for (int q0 = 0; q0 < n; q0 += MRG_THREADS) {
+        const int q = q0 + tid;
+        const bool keep = q < n && alive[q];
+        const u64 bal = __ballot(keep);
+        if (lane == 0) s_wtot[wave] = __popcll(bal);
+        __syncthreads();
+        int wbase = total, tot = 0;
+#pragma unroll
+        for (int i = 0; i < MRG_WAVES; ++i) {
+            if (i < wave) wbase += s_wtot[i];
+            tot += s_wtot[i];
+        }
+        const int o = wbase + __popcll(bal & ((1ull << lane) - 1ull));
+        if (keep && o < limit) {
+            const int f = (int)gvals[q];
+            const int t = f / cap, j = f - t * cap;
+            const size_t src = (size_t)(T0 + t) * cap + j;
+            const size_t dst = (size_t)b * p.out_cap + o;
+            if (p.conf_out) p.conf_out[dst] = p.conf[src];
+            p.cls_out[dst] = p.cls[src] & (MRG_NCLS - 1);
+            if (p.idx_out) p.idx_out[dst] = p.idx[src];
+            if (p.tile_out) p.tile_out[dst] = t;
+            *reinterpret_cast<int4*>(p.box_out + dst * 4) = mbox[q];
+        }
+        total += tot;
+        __syncthreads();
+    }
+    if (tid == 0) p.count_out[b] = p.max_out >= 0 ? min(total, p.max_out) : total;
+}
+
+// workspace: the tile table and the per-picture offsets, then per picture a region of pow2(tiles * tile_cap) elements of
+// each of keys (8 B), payload (4 B), mapped box (16 B) and NMS box (16 B); the regions sum to < 2 * n_tiles * tile_cap.
+static size_t merge_head_bytes(int n_tiles) {
+    return ((size_t)n_tiles * sizeof(MergeTile) + (size_t)(2 * n_tiles + 2) * sizeof(int) + 255) / 256 * 256;
+}
+
+size_t merge_tiles_ws_bytes(int n_tiles, int tile_cap) {
+    SSD_REQUIRE(n_tiles >= 1 && tile_cap >= 1, "merge_tiles: n_tiles and tile_cap must be >= 1 (got %d, %d)", n_tiles, tile_cap);
+    SSD_REQUIRE((long long)n_tiles * tile_cap < (1LL << 28), "merge_tiles: n_tiles * tile_cap must stay below 2^28");
+    return merge_head_bytes(n_tiles) + 2 * (size_t)n_tiles * tile_cap * (8 + 4 + 16 + 16) + 256;
+}
+
+// every limit of merge_tiles; fills the table that goes to the device: the tiles, then img_first [n_tiles + 1] and reg_off [n_tiles + 1]
+static void merge_plan(const MergeTile* tiles, int n_tiles, int n_images, int tile_cap, int out_cap, std::vector<int>& head) {
+    SSD_REQUIRE(tiles != nullptr, "merge_tiles: null argument");
+    SSD_REQUIRE(n_tiles >= 1 && n_images >= 1, "merge_tiles: at least one tile and one picture (got %d, %d)", n_tiles, n_images);
+    SSD_REQUIRE(tile_cap >= 1, "merge_tiles: tile_cap must be >= 1 (got %d)", tile_cap);
+    SSD_REQUIRE(out_cap >= 1, "merge_tiles: out_cap must be >= 1 (got %d)", out_cap);
+    SSD_REQUIRE((long long)n_tiles * tile_cap < (1LL << 28), "merge_tiles: n_tiles * tile_cap must stay below 2^28");
+    SSD_REQUIRE(tiles[0].image == 0 && tiles[n_tiles - 1].image == n_images - 1,
+                "merge_tiles: image indices must ascend from 0 to n_images - 1 = %d (first %d, last %d)", n_images - 1, tiles[0].image,
+                tiles[n_tiles - 1].image);
+    head.assign((size_t)n_tiles * 8 + 2 * (size_t)n_tiles + 2, 0);
+    MergeTile* ht = reinterpret_cast<MergeTile*>(head.data());
+    int* first = head.data() + (size_t)n_tiles * 8;
+    int* reg = first + n_tiles + 1;
+    size_t off = 0;
+    for (int t = 0, img = -1; t < n_tiles; ++t) {
+        const MergeTile& tl = tiles[t];
+        const int im = tl.image;
+        SSD_REQUIRE(im == img || im == img + 1, "merge_tiles: image indices must ascend without gaps (tile %d: image %d after %d)", t, im,
+                    img);
+        SSD_REQUIRE(tl.img_w >= 1 && tl.img_h >= 1 && tl.img_w <= MERGE_MAX_SIDE && tl.img_h <= MERGE_MAX_SIDE,
+                    "merge_tiles: tile %d: picture of %d x %d outside 1..%d", t, tl.img_w, tl.img_h, MERGE_MAX_SIDE);
+        SSD_REQUIRE(tl.x0 >= 0 && tl.y0 >= 0 && tl.w >= 1 && tl.h >= 1 && tl.x0 <= tl.img_w - tl.w && tl.y0 <= tl.img_h - tl.h,
+                    "merge_tiles: tile %d (%d, %d, %d x %d) leaves its %d x %d picture", t, tl.x0, tl.y0, tl.w, tl.h, tl.img_w, tl.img_h);
+        SSD_REQUIRE(tl.interior >= 0 && tl.interior <= 15, "merge_tiles: tile %d: interior = %d outside 0..15", t, tl.interior);
+        if (im != img) {
+            img = im;
+            first[img] = t;
+        } else {
+            SSD_REQUIRE(tl.img_w == tiles[t - 1].img_w && tl.img_h == tiles[t - 1].img_h,
+                        "merge_tiles: tile %d: the tiles of picture %d disagree about its size", t, im);
+        }
+        ht[t] = tl;
+    }
+    first[n_images] = n_tiles;
+    for (int i = 0; i < n_images; ++i) {
+        const int nt = first[i + 1] - first[i];
+        SSD_REQUIRE(nt <= MERGE_MAX_TILES, "merge_tiles: picture %d has %d tiles, at most %d", i, nt, MERGE_MAX_TILES);
+        SSD_REQUIRE((long long)nt * tile_cap <= MERGE_MAX_CAND, "merge_tiles: picture %d: %d tiles x tile_cap %d exceeds %d candidates", i,
+                    nt, tile_cap, MERGE_MAX_CAND);
+        reg[i] = (int)off;
+        off += (size_t)pow2_ge(nt * tile_cap);
+    }
+}
+
+void merge_tiles_check(const MergeTile* tiles, int n_tiles, int n_images, int tile_cap, int out_cap) {
+    std::vector<int> head;
+    merge_plan(tiles, n_tiles, n_images, tile_cap, out_cap, head);
+}
+
+void merge_tiles(const MergeTile* tiles, int n_tiles, int n_images, int tile_cap, const int* count, const float* conf, const int* cls,
+                 const int* idx, const int* box, int edge_margin, int max_out, int out_cap, int* count_out, float* conf_out,
+                 int* cls_out, int* idx_out, int* tile_out, int* box_out, void* ws, hipStream_t s) {
+    // every limit is checked before anything is enqueued
+    SSD_REQUIRE(tiles && count && conf && cls && idx && box && count_out && cls_out && box_out && ws, "merge_tiles: null argument");
+    std::vector<int> head;
+    merge_plan(tiles, n_tiles, n_images, tile_cap, out_cap, head);
+    const size_t total = 2 * (size_t)n_tiles * tile_cap;      // the regions end below it: each is below twice its slots
+    char* base = (char*)ws;
+    MergeArgs a{};
+    a.tiles = reinterpret_cast<const MergeTile*>(base);
+    a.img_first = reinterpret_cast<const int*>(base) + (size_t)n_tiles * 8;
+    a.reg_off = a.img_first + n_tiles + 1;
+    HIP_OK(hipMemcpyAsync(base, head.data(), head.size() * sizeof(int), hipMemcpyHostToDevice, s));      // (pageable: copied by the call)
+    base += merge_head_bytes(n_tiles);
+    a.keys = (u64*)base; base += total * 8;
+    a.mbox = (int4*)base; base += total * 16;
+    a.nbox = (int4*)base; base += total * 16;
+    a.vals = (unsigned*)base;
+    a.tile_cap = tile_cap; a.edge_margin = edge_margin; a.max_out = max_out; a.out_cap = out_cap;
+    a.count = count; a.conf = conf; a.cls = cls; a.idx = idx; a.box = box;
+    a.count_out = count_out; a.conf_out = conf_out; a.cls_out = cls_out; a.idx_out = idx_out; a.tile_out = tile_out; a.box_out = box_out;
+    {
+        ProfScope prof("merge_tiles", 0.0, 0.0, s);
+        hipLaunchKernelGGL(merge_tiles_kernel, dim3(n_images), dim3(MRG_THREADS), 0, s, a);
     }
     HIP_OK(hipGetLastError());
 }

@@ -38,6 +38,8 @@ def main(argv=None):
     parser.add_argument('--jpeg-quality', type=int, default=95, help='--encoder gpu: JPEG quality 1..100 (95 = cv2.imwrite)')
     parser.add_argument('--jpeg-entropy', default='host', choices=['host', 'gpu'],
                         help='--encoder gpu: host: Huffman coding on host threads; gpu: on the GPU as well, only the files come back (same bytes)')
+    from .tiling import add_arguments as add_tile_arguments
+    add_tile_arguments(parser)
     args = parser.parse_args(argv)
     check_fp8_arguments(parser, args)
 
@@ -78,7 +80,23 @@ def main(argv=None):
                     write_image(os.path.join(args.output_dir, name), images[i])
 
         pending = None
-        for x, idxs, sizes, sources in fp8_batches(net, sample_generator(files, net.preset.image_size, args.batch_size, with_sources=True,
+        if args.tile:       #  windows of the source picture through the net, their boxes merged on the GPU
+            from . import tiling
+            detector = tiling.TiledDetector(net, args.tile, args.tile_overlap, args.tile_whole, args.tile_edge_margin, 0.5, 200, 200)
+            for k, (packed, offs, shapes, idxs) in enumerate(tiling.source_batches(files, args.batch_size, sess.device, args.decoder,
+                                                                                  args.decoder_entropy)):
+                if k == 0:
+                    tiling.fp8_ready(detector, (packed, offs, shapes), args.fp8_calibration, args.fp8_calibrate_images)
+                ticket = detector.launch(packed, offs, shapes)
+                if writer is not None:
+                    drawn = writer.launch(detector, (packed, offs, shapes), style,
+                                          [os.path.join(args.output_dir, os.path.basename(files[i])) for i in idxs])
+                else:
+                    drawn = detector.annotate_last_launch(packed, offs, shapes, style)
+                if pending:
+                    collect(pending)
+                pending = (ticket, idxs, drawn)
+        for x, idxs, sizes, sources in () if args.tile else fp8_batches(net, sample_generator(files, net.preset.image_size, args.batch_size, with_sources=True,
                                                                           decoder=args.decoder, decoder_entropy=args.decoder_entropy),
                                                    args.fp8_calibration, args.fp8_calibrate_images):
             net.infer_dev(x)

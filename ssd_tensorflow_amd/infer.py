@@ -191,8 +191,14 @@ def main(argv=None):
     parser.add_argument('--jpeg-quality', type=int, default=95, help='--encoder gpu: JPEG quality 1..100 (95 = cv2.imwrite)')
     parser.add_argument('--jpeg-entropy', default='host', choices=['host', 'gpu'],
                         help='--encoder gpu: host: Huffman coding on host threads; gpu: on the GPU as well, only the files come back (same bytes)')
+    from .tiling import add_arguments as add_tile_arguments
+    add_tile_arguments(parser)
     args = parser.parse_args(argv)
     check_fp8_arguments(parser, args)
+    if args.tile and args.dump_predictions:
+        parser.error('--dump-predictions does not apply to --tile: a tiled picture has one prediction tensor per window')
+    if args.tile and args.synthetic:
+        parser.error('--synthetic inputs are network-size float arrays: --tile reads source pictures')
 
     print('[i] Project name:      ', args.name)
     print('[i] Batch size:        ', args.batch_size)
@@ -314,7 +320,23 @@ def main(argv=None):
                     pascal_summary.add_detections(name_of(idxs[i]), boxes, img_size=sizes[i])
 
         pending = None
-        for batch in fp8_batches(net, sample_generator(files, size, args.batch_size, with_sources=style is not None, decoder=args.decoder,
+        if args.tile:       #  windows of the source picture through the net, their boxes merged on the GPU
+            from . import tiling
+            detector = tiling.TiledDetector(net, args.tile, args.tile_overlap, args.tile_whole, args.tile_edge_margin, args.threshold, 200, 200)
+            for k, (packed, offs, shapes, idxs) in enumerate(tiling.source_batches(files, args.batch_size, sess.device, args.decoder,
+                                                                                  args.decoder_entropy)):
+                if k == 0:
+                    tiling.fp8_ready(detector, (packed, offs, shapes), args.fp8_calibration, args.fp8_calibrate_images)
+                ticket = detector.launch(packed, offs, shapes)
+                if writer is not None:
+                    drawn = writer.launch(detector, (packed, offs, shapes), style,
+                                          [os.path.join(args.output_dir, os.path.basename(name_of(i))) for i in idxs])
+                else:
+                    drawn = detector.annotate_last_launch(packed, offs, shapes, style) if style is not None else None
+                if pending:
+                    collect(pending)
+                pending = (ticket, idxs, [Size(w, h) for h, w in shapes], drawn)
+        for batch in () if args.tile else fp8_batches(net, sample_generator(files, size, args.batch_size, with_sources=style is not None, decoder=args.decoder,
                                                        decoder_entropy=args.decoder_entropy), args.fp8_calibration, args.fp8_calibrate_images):
             x, idxs, sizes = batch[:3]
             net.infer_dev(x)                                                                 # infer.py:225-227

@@ -127,6 +127,60 @@ def detect_batch(pred, preset, confidence_threshold=0.01, detections_cap=200, ma
     return out
 
 
+def merge_tile_lists(tiles, count, conf, cls, idx, box, tile_cap, max_out=200, edge_margin=2, out_cap=None):
+    """ssd_merge_tiles on host arrays: tiles = [(image, Tile, (W, H))] with the images ascending from 0; count [n_tiles], conf /
+    cls / idx [n_tiles, tile_cap], box [n_tiles, tile_cap, 4] as detect_batch(nms=False) lays a tile's records out.  Returns one
+    dict per picture: conf, cls, idx, tile, box (the detections of tiling.TiledDetector, for tests and notebooks)."""
+    from .tiling import tile_structs
+    n_tiles, tile_cap = len(tiles), int(tile_cap)
+    n_images = (max(t[0] for t in tiles) + 1) if tiles else 0
+    count = np.ascontiguousarray(count, np.int32).reshape(n_tiles)
+    conf = np.ascontiguousarray(conf, np.float32).reshape(n_tiles, max(tile_cap, 0))
+    cls = np.ascontiguousarray(cls, np.int32).reshape(n_tiles, max(tile_cap, 0))
+    idx = np.ascontiguousarray(idx, np.int32).reshape(n_tiles, max(tile_cap, 0))
+    box = np.ascontiguousarray(box, np.int32).reshape(n_tiles, max(tile_cap, 0), 4)
+    mo = -1 if max_out is None else int(max_out)
+    if out_cap is None:
+        per_image = max([sum(1 for t in tiles if t[0] == i) for i in range(n_images)] + [1])
+        out_cap = max(mo, 1) if mo >= 0 else max(per_image * tile_cap, 1)
+    g = max(n_images, 1)
+    ocount = np.zeros(g, np.int32)
+    oconf = np.zeros((g, out_cap), np.float32)
+    ocls, oidx, otile = (np.zeros((g, out_cap), np.int32) for _ in range(3))
+    obox = np.zeros((g, out_cap, 4), np.int32)
+    check(lib.ssd_merge_tiles(_lib.device(), C.cast(tile_structs(tiles), C.c_void_p), n_tiles, n_images, tile_cap, np_ptr(count),
+                              np_ptr(conf), np_ptr(cls), np_ptr(idx), np_ptr(box), int(edge_margin), mo, int(out_cap), np_ptr(ocount),
+                              np_ptr(oconf), np_ptr(ocls), np_ptr(oidx), np_ptr(otile), np_ptr(obox)))
+    out = []
+    for i in range(n_images):
+        n = min(int(ocount[i]), out_cap)
+        out.append(dict(conf=oconf[i, :n], cls=ocls[i, :n], idx=oidx[i, :n], tile=otile[i, :n], box=obox[i, :n]))
+    return out
+
+
+def detect_tiles(pred, preset, tiles, thr, tile_cap=200, max_out=200, edge_margin=2):
+    """Tiled detection on host predictions: pred [n_tiles, A, C+5], one row of anchors per tile; tiles = [(image, Tile, (W, H))]
+    (tiling.plan_tiles), the images ascending from 0.  Every tile is decoded (decode_boxes, the first tile_cap records), the
+    records of a picture are merged on the GPU (ssd_merge_tiles: edge drop, the picture's 1000 grid, one NMS over all tiles).
+    The mirror of detect_batch; returns one dict per picture: conf, cls, idx, tile, box."""
+    pred = np.ascontiguousarray(pred, np.float32)
+    if pred.ndim != 3 or pred.shape[0] != len(tiles):
+        raise ValueError('pred must be [n_tiles, A, C+5] with one entry per tile')
+    n_tiles, A, nv = pred.shape
+    p = _preset_for(A) if preset is None else preset
+    tile_cap = int(tile_cap)
+    if tile_cap < 1:
+        raise ValueError('merge_tiles: tile_cap must be >= 1 (got %d)' % tile_cap)
+    count = np.zeros(n_tiles, np.int32)
+    conf = np.zeros((n_tiles, tile_cap), np.float32)
+    cls = np.zeros((n_tiles, tile_cap), np.int32)
+    idx = np.zeros((n_tiles, tile_cap), np.int32)
+    box = np.zeros((n_tiles, tile_cap, 4), np.int32)
+    check(lib.ssd_decode_nms(_pname(p), nv - 5, _lib.device(), np_ptr(pred), n_tiles, float(thr), tile_cap, -1, tile_cap, 0,
+                             np_ptr(count), np_ptr(conf), np_ptr(cls), np_ptr(idx), np_ptr(box)))
+    return merge_tile_lists(tiles, count, conf, cls, idx, box, tile_cap, max_out, edge_margin)
+
+
 def boxes_from_detection(det, lid2name={}):
     """dict from detect_batch -> the reference's list of (confidence, Box)."""
     res = []
