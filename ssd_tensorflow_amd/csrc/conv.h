@@ -209,9 +209,12 @@ int conv_wgrad_group_bf16_max();
 void conv_wgrad_group_bf16(const WgradGroupItem* items, int n, float weight_decay, hipStream_t s);
 
 // ---- fp8 inference kernels (conv_fp8.hip): OCP e4m3fn codes, one fp32 scale per activation tensor and per output channel ----
+// (The four e4m3 convolutions below -- fp8 and mxfp8, up to 9 taps and 10 ... 121 -- are one kernel, one shape check and one host path:
+// conv_fp8_detail.h.  The entry points differ in the format, the tap range they accept and the workgroup order.)
 // code = RNE(clamp(v / s, -448, 448)); y = relu?(acc * (s_in * s_w[co]) + bias[co]) in fp32, then one of the output forms.
 enum { FP8_OUT_BF16 = 0, FP8_OUT_F32 = 1, FP8_OUT_E4M3 = 2, FP8_OUT_BF16_E4M3 = 3 };
-// KH * KW <= 9, Ci a multiple of 64, Co a multiple of 8, any stride / dilation / leading padding; why (optional) = the reason text
+// KH * KW <= 9, Ci a multiple of 64, Co a multiple of 8, any stride / dilation / leading padding, no empty tensor, every tensor and the
+// filter image below the 32-bit offsets; why (optional) = the reason text, a string literal
 bool conv_fwd_fp8_supported(const ConvDesc& d, const char** why);
 // the shapes on which the step executor prefers this kernel to conv_fwd_bf16 (Ci >= 256; measured: conv_fp8.hip)
 bool conv_fwd_fp8_worthwhile(const ConvDesc& d);
@@ -219,8 +222,7 @@ bool conv_fwd_fp8_worthwhile(const ConvDesc& d);
 // (FP8_OUT_E4M3 and FP8_OUT_BF16_E4M3).  Anything unsupported throws before a launch.
 void conv_fwd_fp8(const ConvDesc& d, const unsigned char* x8, const unsigned char* w8, float s_in, const float* s_w, const float* bias,
                   void* y, unsigned char* y8, int out_mode, float s_out, bool relu, hipStream_t s);
-// The same contract for 10 ... 121 taps (KH, KW <= 11): the fc graph's 7x7 fc6.  Also requires the filter image taps * Co * Ci
-// below the 32-bit offsets; 9 taps or fewer are refused (conv_fwd_fp8 runs them).
+// The same contract for 10 ... 121 taps (KH, KW <= 11): the fc graph's 7x7 fc6.  9 taps or fewer are refused (conv_fwd_fp8 runs them).
 bool conv_bigk_fwd_fp8_supported(const ConvDesc& d, const char** why);
 // whether the step executor puts such a layer on e4m3 (SSD_FP8_BIGK, read per handle; the default is measured: conv_fp8.hip)
 bool conv_bigk_fwd_fp8_worthwhile(const ConvDesc& d);

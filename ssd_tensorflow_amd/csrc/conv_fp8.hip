@@ -1,18 +1,10 @@
-// fp8 (OCP e4m3fn) inference kernels for gfx950 (MI355X): the forward gather convolution of conv_bf16.hip restated for
-// e4m3 operands on the block-scaled matrix instruction v_mfma_scale_f32_32x32x64_f8f6f4 (format selector 0 = e4m3 for both
-// operands, every block scale 2^0), plus what surrounds it: filter quantisation (per output channel), activation
-// quantisation (per tensor), the absmax reduction calibration needs and max-pooling on e4m3 bytes.  DESIGN.md 18.
+// fp8 (OCP e4m3fn) inference kernels for gfx950 (MI355X): the forward gather convolution on e4m3 operands at one fp32 scale per
+// activation tensor -- the kernel and its host path are conv_fp8_detail.h's, instantiated here with MX = false -- plus what surrounds
+// it: filter quantisation (per output channel), activation quantisation (per tensor), the absmax reduction calibration needs and
+// max-pooling on e4m3 bytes.  DESIGN.md 18; more than 9 taps (the fc graph's 7 x 7 fc6): DESIGN.md 19.
 //
 // Numeric contract: code = RNE(clamp(v / s, -448, 448)); products of two e4m3 numbers are exact in fp32, the MFMA adds in
 // fp32; epilogue in fp32: y = relu?(acc * (s_in * s_w[co]) + bias[co]), then bf16 / fp32 / e4m3 at the consumer's scale.
-//
-// Operand layout (tools/probes/fp8_probe.hip pins it on the hardware): lane l holds row l & 31 of its operand and the 32
-// consecutive k = 32 (l >> 5) + j, one byte each, in 8 registers -- two 16-byte LDS reads.  A tile row is 64 k = 64 bytes,
-// filled by LDS-DMA (lane-linear, 16 bytes per lane, zero fill of padding by an out-of-range offset, like the bf16 tiles).
-// Swizzle for 64-byte rows: LDS slot p of row r holds the global 16-byte chunk p ^ ((r >> 2) & 3).  A ds_read_b128 lane
-// group is 16 rows of one k half ({0-3, 12-15, 20-27} or {4-11, 16-19, 28-31}, MI355X LDS banking); row r's slot sits at
-// 16-byte unit 4 (r & 3) + slot of the 256-byte bank line, and the four rows of a group that share r & 3 have four
-// different (r >> 2) & 3, so the group covers all 16 units: conflict-free.
 #include "conv.h"
 #include "conv_detail.h"
 #include "conv_fp8_detail.h"
@@ -22,229 +14,15 @@
 
 namespace ssd {
 
-struct GatherArgs8 {
-    const unsigned char* src;      // e4m3 [B][SH][SW][SC]
-    const unsigned char* wgt;      // e4m3 [tap][DN][SC]
-    const float* bias;             // [DN] or nullptr
-    const float* s_w;              // [DN] filter scales
-    void* dst;                     // bf16 or fp32 [M][DN] (modes 0, 1, 3)
-    unsigned char* dst8;           // e4m3 [M][DN] (modes 2, 3)
-    float s_in, s_out;
-    int M, DH, DW, DN;
-    int SH, SW, SC;
-    int ntaps, mul, relu, mode, NT;
-    int tap_dh[9], tap_dw[9];
-};
-
-// One pipeline iteration = one tap of one 64-channel chunk: BM pixel rows and BN filter rows of 64 bytes each.  At half the
-// bytes per k of the bf16 tiles the ring is twice as deep for the same LDS (NS stages; the fp32 epilogue tile sets the size).
-template <int WM, int WN, int TM, int TN, int NS>
-__global__ __launch_bounds__(64 * WM * WN) void conv_fwd_fp8_kernel(GatherArgs8 pp) {
-    const GatherArgs8& p = pp;
-    constexpr int NTHR = 64 * WM * WN;
-    constexpr int RPP_S = NTHR / 4;                   // tile rows one staging pass covers (4 lanes per 64-byte row)
-    constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
-    constexpr int A_N = BM / RPP_S, B_N = BN / RPP_S; // DMA instructions per thread and tile
-    constexpr int STAGE = (BM + BN) * KB8;
-    constexpr int LDC = BN + 4;
-    static_assert(BM % RPP_S == 0 && BN % RPP_S == 0 && RPP_S % 16 == 0, "tile vs staging pass");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int wg = xcd_remap(blockIdx.x, gridDim.x);
-    const int mt = wg / p.NT, nt = wg - mt * p.NT;
-    const int m0 = mt * BM, n0 = nt * BN;
-
-    // ---- staging: thread -> rows (tid >> 2) + RPP_S i, LDS slot tid & 3, global chunk slot ^ ((row >> 2) & 3)
-    const int a_ck = ((tid & 3) ^ ((tid >> 4) & 3)) * 16;
-    unsigned a_off[A_N], a_msk[A_N];
-#pragma unroll
-    for (int i = 0; i < A_N; ++i) {
-        const int m = m0 + (tid >> 2) + RPP_S * i;
-        const int mm = m < p.M ? m : 0;
-        const int ow = mm % p.DW;
-        const int t2 = mm / p.DW;
-        const int oh = t2 % p.DH;
-        const int b = t2 / p.DH;
-        const int rh = oh * p.mul, rw = ow * p.mul;
-        a_off[i] = (unsigned)((b * p.SH * p.SW + rh * p.SW + rw) * p.SC + a_ck);
-        unsigned mk = 0;
-        if (m < p.M)
-            for (int t = 0; t < p.ntaps; ++t) {
-                const int sh = rh + p.tap_dh[t], sw = rw + p.tap_dw[t];
-                if ((unsigned)sh < (unsigned)p.SH && (unsigned)sw < (unsigned)p.SW) mk |= 1u << t;
-            }
-        a_msk[i] = mk;
-    }
-    unsigned b_off[B_N], b_ok[B_N];
-#pragma unroll
-    for (int i = 0; i < B_N; ++i) {
-        const int n = n0 + (tid >> 2) + RPP_S * i;
-        b_ok[i] = 0u - (unsigned)(n < p.DN);
-        b_off[i] = (unsigned)((n < p.DN ? n : 0) * p.SC + a_ck);
-    }
-    const __amdgpu_buffer_rsrc_t src_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<unsigned char*>(p.src), 0, (unsigned)((size_t)(p.M / (p.DH * p.DW)) * p.SH * p.SW * p.SC), 0x00020000);
-    const __amdgpu_buffer_rsrc_t wgt_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.wgt), 0, (unsigned)((size_t)p.ntaps * p.DN * p.SC), 0x00020000);
-
-    const int nk = (p.SC / KB8) * p.ntaps;      // SC is a multiple of 64 (host check): no channel-chunk mask
-
-    auto issue = [&](int kiter, int stage) {
-        const int cc = kiter / p.ntaps;
-        const int tap = kiter - cc * p.ntaps;
-        unsigned char* As = smem + stage * STAGE + wave * 1024;        // wave-uniform: 16 rows x 64 B per DMA
-        unsigned char* Bs = As + BM * KB8;
-        const unsigned toff = (unsigned)((p.tap_dh[tap] * p.SW + p.tap_dw[tap]) * p.SC + cc * KB8);
-#pragma unroll
-        for (int i = 0; i < A_N; ++i) {
-            const unsigned m = 0u - ((a_msk[i] >> tap) & 1u);
-            const unsigned off = ((a_off[i] + toff) & m) | (OOB8 & ~m);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(src_rsrc, LDS_PTR8(As + i * (RPP_S * KB8)), 16, off, 0, 0, 0);
-        }
-        const unsigned woff = (unsigned)(tap * p.DN * p.SC + cc * KB8);
-#pragma unroll
-        for (int i = 0; i < B_N; ++i) {
-            const unsigned m = b_ok[i];
-            const unsigned off = ((b_off[i] + woff) & m) | (OOB8 & ~m);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(wgt_rsrc, LDS_PTR8(Bs + i * (RPP_S * KB8)), 16, off, 0, 0, 0);
-        }
-    };
-
-    // ---- accumulators: D rows = output channels (filter operand first), D cols = pixels, as in conv_bf16.hip
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-    const int wm = wave / WN, wn = wave - wm * WN;
-    const int li = lane & 31, lh = lane >> 5;
-    // fragment = chunks 2 lh and 2 lh + 1 of row li: slots (2 lh) ^ f and (2 lh) ^ f ^ 1, f = (row >> 2) & 3 = (li >> 2) & 3
-    const int q0 = ((2 * lh) ^ ((li >> 2) & 3)) * 16;
-    const int a_row = (wm * 32 * TM + li) * KB8 + q0;
-    const int b_row = BM * KB8 + (wn * 32 * TN + li) * KB8 + q0;
-
-    auto load_frag = [&](const unsigned char* S, int addr) -> i32x8 {
-        const i32x4 lo = *reinterpret_cast<const i32x4*>(S + addr);
-        const i32x4 hi = *reinterpret_cast<const i32x4*>(S + (addr ^ 16));
-        return i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    };
-    auto compute = [&](int stage) {
-        const unsigned char* S = smem + stage * STAGE;
-        i32x8 a[TM], b[TN];
-#pragma unroll
-        for (int mi = 0; mi < TM; ++mi) a[mi] = load_frag(S, a_row + mi * 32 * KB8);
-#pragma unroll
-        for (int ni = 0; ni < TN; ++ni) b[ni] = load_frag(S, b_row + ni * 32 * KB8);
-#pragma unroll
-        for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < TN; ++ni)
-                acc[mi][ni] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(b[ni], a[mi], acc[mi][ni], 0, 0, 0, SCALE_ONE, 0, SCALE_ONE);
-    };
-
-    // ---- main loop: NS stages; tiles k+1 .. k+NS-1 stream in while tile k is multiplied
-#pragma unroll
-    for (int t = 0; t < NS - 1; ++t)
-        if (t < nk) issue(t, t);
-    int st_c = 0, st_i = NS - 1;
-    for (int k = 0; k < nk; ++k) {
-        const int later = nk - 1 - k;
-        wait_tiles_and_sync8<A_N + B_N, (NS - 2 > 4 ? 4 : NS - 2)>(later < NS - 2 ? later : NS - 2);      // tile k visible; stage st_i is free
-        if (k + NS - 1 < nk) issue(k + NS - 1, st_i);
-        compute(st_c);
-        st_c = st_c + 1 == NS ? 0 : st_c + 1;
-        st_i = st_i + 1 == NS ? 0 : st_i + 1;
-    }
-    __syncthreads();
-
-    // ---- epilogue through an fp32 LDS tile [BM][BN + 4]: dequantise, bias, relu, one rounding per output format
-    float* Cs = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < TN; ++ni)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int ml = wm * 32 * TM + mi * 32 + li;
-                const int nl = wn * 32 * TN + ni * 32 + 8 * g + 4 * lh;
-                const f32x16& c = acc[mi][ni];
-                *reinterpret_cast<f32x4*>(Cs + ml * LDC + nl) = f32x4{c[4 * g], c[4 * g + 1], c[4 * g + 2], c[4 * g + 3]};
-            }
-    __syncthreads();
-    constexpr int TPR = BN / 8;               // threads per row, 8 channels each
-    constexpr int RPP = NTHR / TPR;           // rows per pass
-    const int cg = tid % TPR, r0 = tid / TPR;
-    const int n = n0 + cg * 8;
-    if (n >= p.DN) return;
-    float sc[8], bv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        sc[e] = p.s_in * p.s_w[n + e];
-        bv[e] = p.bias ? p.bias[n + e] : 0.f;
-    }
-#pragma unroll
-    for (int ps = 0; ps < BM / RPP; ++ps) {
-        const int ml = r0 + ps * RPP;
-        const int m = m0 + ml;
-        if (m >= p.M) continue;
-        const size_t o = (size_t)m * p.DN + n;
-        const f32x4 c0 = *reinterpret_cast<const f32x4*>(Cs + ml * LDC + cg * 8);
-        const f32x4 c1 = *reinterpret_cast<const f32x4*>(Cs + ml * LDC + cg * 8 + 4);
-        float v[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            v[e] = v[e] * sc[e] + bv[e];
-            if (p.relu) v[e] = v[e] > 0.f ? v[e] : 0.f;
-        }
-        if (p.mode == FP8_OUT_F32) {
-            float* d = reinterpret_cast<float*>(p.dst) + o;
-            *reinterpret_cast<f32x4*>(d) = f32x4{v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<f32x4*>(d + 4) = f32x4{v[4], v[5], v[6], v[7]};
-        } else if (p.mode != FP8_OUT_E4M3) {
-            *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(p.dst) + o) =
-                u32x4{pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
-        }
-        if (p.mode == FP8_OUT_E4M3 || p.mode == FP8_OUT_BF16_E4M3) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = v[e] / p.s_out;
-            *reinterpret_cast<u32x2*>(p.dst8 + o) = u32x2{pack4_e4m3(v[0], v[1], v[2], v[3]), pack4_e4m3(v[4], v[5], v[6], v[7])};
-        }
-    }
-}
-
-template <int WM, int WN, int TM, int TN, int NS>
-static void launch_fwd8(GatherArgs8& a, const char* label, double flops, double bytes, hipStream_t s) {
-    constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
-    constexpr size_t stages = NS * (size_t)(BM + BN) * KB8, ctile = (size_t)BM * (BN + 4) * 4;
-    constexpr size_t lds = stages > ctile ? stages : ctile;
-    static_assert(lds <= 160 * 1024, "LDS");
-    auto kern = conv_fwd_fp8_kernel<WM, WN, TM, TN, NS>;
-    static bool once = (set_lds(kern, lds), true);
-    (void)once;
-    a.NT = cdiv(a.DN, BN);
-    ProfScope prof(label, flops, bytes, s);
-    SSD_LAUNCH_STOP(kern, dim3(cdiv(a.M, BM) * a.NT), dim3(64 * WM * WN), lds, s, a);
-    HIP_OK(hipGetLastError());
-}
-
-bool conv_fwd_fp8_supported(const ConvDesc& d, const char** why) {
-    const char* w = nullptr;
-    if (d.KH * d.KW > 9 || d.KH * d.KW < 1) w = "fp8 conv: at most 9 taps";
-    else if (d.Ci % 64 != 0) w = "fp8 conv: Ci must be a multiple of 64";
-    else if (d.Co % 8 != 0) w = "fp8 conv: Co must be a multiple of 8";
-    else if (d.stride < 1 || d.dil < 1) w = "fp8 conv: stride and dilation must be positive";
-    else if ((long long)d.B * d.Hi * d.Wi * d.Ci >= (1LL << 31) - 16 || (long long)d.B * d.Ho * d.Wo * d.Co >= (1LL << 31) - 16)
-        w = "fp8 conv: a tensor of this layer exceeds the 32-bit offsets: lower the batch";
+static bool supported_fp8(bool bigk, const ConvDesc& d, const char** why) {
+    const char* w = conv_e4m3_refusal(false, bigk, d, -1);
     if (why) *why = w;
     return w == nullptr;
 }
+bool conv_fwd_fp8_supported(const ConvDesc& d, const char** why) { return supported_fp8(false, d, why); }
+bool conv_bigk_fwd_fp8_supported(const ConvDesc& d, const char** why) { return supported_fp8(true, d, why); }
 
-// Where an fp8 handle uses this kernel.  Interleaved rounds against the bf16 handle at batch 128 (tools/infer_rate.py,
+// Where an fp8 handle uses the kernel for up to 9 taps.  Interleaved rounds against the bf16 handle at batch 128 (tools/infer_rate.py,
 // profiles/fp8_infer_rate_all_layers.txt, profiles/fp8_infer_rate.txt): every layer with at least 256 input channels
 // ran 1.09 ... 1.46 x faster than its bf16 kernel in every round; the layers with 64 or 128 did not (conv1_2 0.42 x, conv2_1
 // 0.91 x, conv2_2 not separated and it loses its fused pool, conv3_1 1.10 x in one run and not separated in the next) -- there a tap
@@ -253,313 +31,26 @@ bool conv_fwd_fp8_supported(const ConvDesc& d, const char** why) {
 // They stay on bf16.  SSD_FP8_ALL=1 (read per handle) takes every supported layer: the A/B that produced the table.
 bool conv_fwd_fp8_worthwhile(const ConvDesc& d) { return d.Ci >= 256 || env_int("SSD_FP8_ALL", 0) == 1; }
 
-// Tiles: 0 = 128 x 128, four stages of 16 KB (the fp32 epilogue tile's 66 KB sets the allocation: two workgroups per CU);
-// 1 = 64 x 64, six stages, where the 128 x 128 tiling would leave CUs empty.  SSD_TILE_FP8 forces one (tests, tuning).
-void conv_fwd_fp8(const ConvDesc& d, const unsigned char* x8, const unsigned char* w8, float s_in, const float* s_w, const float* bias,
-                  void* y, unsigned char* y8, int out_mode, float s_out, bool relu, hipStream_t s) {
-    const char* why = nullptr;
-    SSD_REQUIRE(conv_fwd_fp8_supported(d, &why), "%s (got %dx%d taps, Ci %d, Co %d)", why, d.KH, d.KW, d.Ci, d.Co);
-    SSD_REQUIRE(out_mode >= FP8_OUT_BF16 && out_mode <= FP8_OUT_BF16_E4M3, "fp8 conv: unknown output mode %d", out_mode);
-    const bool wants8 = out_mode == FP8_OUT_E4M3 || out_mode == FP8_OUT_BF16_E4M3;
-    SSD_REQUIRE(!wants8 || (y8 != nullptr && s_out > 0.f), "fp8 conv: an e4m3 output needs its buffer and a positive scale");
-    SSD_REQUIRE(out_mode == FP8_OUT_E4M3 || y != nullptr, "fp8 conv: null output");
-    SSD_REQUIRE(x8 && w8 && s_w && s_in > 0.f, "fp8 conv: null operand or non-positive input scale");
-    GatherArgs8 a{};
-    a.src = x8; a.wgt = w8; a.bias = bias; a.s_w = s_w; a.dst = y; a.dst8 = y8; a.s_in = s_in; a.s_out = wants8 ? s_out : 1.f;
-    a.M = d.B * d.Ho * d.Wo; a.DH = d.Ho; a.DW = d.Wo; a.DN = d.Co;
-    a.SH = d.Hi; a.SW = d.Wi; a.SC = d.Ci;
-    a.ntaps = d.KH * d.KW; a.mul = d.stride; a.relu = relu; a.mode = out_mode;
-    for (int kh = 0; kh < d.KH; ++kh)
-        for (int kw = 0; kw < d.KW; ++kw) {
-            a.tap_dh[kh * d.KW + kw] = kh * d.dil - d.pad_h;
-            a.tap_dw[kh * d.KW + kw] = kw * d.dil - d.pad_w;
-        }
-    const double fl = conv_flops(d);
-    const double by = (double)d.B * d.Hi * d.Wi * d.Ci + (double)d.KH * d.KW * d.Ci * d.Co +
-                      (double)d.B * d.Ho * d.Wo * d.Co * (out_mode == FP8_OUT_F32 ? 4 : out_mode == FP8_OUT_BF16 ? 2 : out_mode == FP8_OUT_E4M3 ? 1 : 3);
-    int cfg = env_int("SSD_TILE_FP8", -1);
-    if (cfg != 0 && cfg != 1) cfg = (long long)cdiv(a.M, 128) * cdiv(a.DN, 128) <= 256 ? 1 : 0;
-    if (cfg == 0) launch_fwd8<2, 2, 2, 2, 4>(a, "conv_fwd_fp8_128x128", fl, by, s);
-    else launch_fwd8<2, 2, 1, 1, 6>(a, "conv_fwd_fp8_64x64x6", fl, by, s);
-}
-
-// =================================================================================
-// More than 9 taps (the fc graph's 7 x 7 fc6): conv_fwd_fp8_kernel's per-tap gather, ring and epilogue with the
-// two things that stop at 9 taps restated.  The tap's offset is computed from (kh, kw, dil, pad) when its tile is issued
-// (wave-uniform counters, no table in the kernel arguments).  A row's validity is kept separably: bit kh of the low half-word
-// = kernel row kh lands on an image row for this pixel, bit 16 + kw = kernel column kw lands on an image column; a tap is
-// inside the image exactly when both hold, so one register per staged row serves any KH, KW <= 16 (a 64-bit mask per row
-// would take two and stop at 64 taps).  The existing kernel is left as it is: its instantiations' code does not change.
-// =================================================================================
-struct GatherArgs8K {
-    const unsigned char* src;      // e4m3 [B][SH][SW][SC]
-    const unsigned char* wgt;      // e4m3 [tap][DN][SC]
-    const float* bias;             // [DN] or nullptr
-    const float* s_w;              // [DN] filter scales
-    void* dst;                     // bf16 or fp32 [M][DN] (modes 0, 1, 3)
-    unsigned char* dst8;           // e4m3 [M][DN] (modes 2, 3)
-    float s_in, s_out;
-    int M, DH, DW, DN;
-    int SH, SW, SC;
-    int KH, KW, dil, pad_h, pad_w;
-    int mul, relu, mode, MT;
-};
-
-template <int WM, int WN, int TM, int TN, int NS>
-__global__ __launch_bounds__(64 * WM * WN) void conv_bigk_fwd_fp8_kernel(GatherArgs8K pp) {
-    const GatherArgs8K& p = pp;
-    constexpr int NTHR = 64 * WM * WN;
-    constexpr int RPP_S = NTHR / 4;                   // tile rows one staging pass covers (4 lanes per 64-byte row)
-    constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
-    constexpr int A_N = BM / RPP_S, B_N = BN / RPP_S; // DMA instructions per thread and tile
-    constexpr int STAGE = (BM + BN) * KB8;
-    constexpr int LDC = BN + 4;
-    static_assert(BM % RPP_S == 0 && BN % RPP_S == 0 && RPP_S % 16 == 0, "tile vs staging pass");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int wg = xcd_remap(blockIdx.x, gridDim.x);
-    // Pixel tiles fastest: consecutive workgroups (one XCD's share, conv_detail.h xcd_remap) walk the pixel tiles of ONE filter column,
-    // so the workgroups resident on an XCD stream the same filter rows through its L2 (launch_fwd8k: why not conv_fwd_fp8's order)
-    const int nt = wg / p.MT, mt = wg - nt * p.MT;
-    const int m0 = mt * BM, n0 = nt * BN;
-
-    // ---- staging: thread -> rows (tid >> 2) + RPP_S i, LDS slot tid & 3, global chunk slot ^ ((row >> 2) & 3)
-    const int a_ck = ((tid & 3) ^ ((tid >> 4) & 3)) * 16;
-    unsigned a_off[A_N], a_msk[A_N];
-#pragma unroll
-    for (int i = 0; i < A_N; ++i) {
-        const int m = m0 + (tid >> 2) + RPP_S * i;
-        const int mm = m < p.M ? m : 0;
-        const int ow = mm % p.DW;
-        const int t2 = mm / p.DW;
-        const int oh = t2 % p.DH;
-        const int b = t2 / p.DH;
-        const int rh = oh * p.mul, rw = ow * p.mul;
-        a_off[i] = (unsigned)((b * p.SH * p.SW + rh * p.SW + rw) * p.SC + a_ck);
-        unsigned mk = 0;
-        if (m < p.M) {
-            for (int kh = 0; kh < p.KH; ++kh)
-                if ((unsigned)(rh + kh * p.dil - p.pad_h) < (unsigned)p.SH) mk |= 1u << kh;
-            for (int kw = 0; kw < p.KW; ++kw)
-                if ((unsigned)(rw + kw * p.dil - p.pad_w) < (unsigned)p.SW) mk |= 0x10000u << kw;
-        }
-        a_msk[i] = mk;
-    }
-    unsigned b_off[B_N], b_ok[B_N];
-#pragma unroll
-    for (int i = 0; i < B_N; ++i) {
-        const int n = n0 + (tid >> 2) + RPP_S * i;
-        b_ok[i] = 0u - (unsigned)(n < p.DN);
-        b_off[i] = (unsigned)((n < p.DN ? n : 0) * p.SC + a_ck);
-    }
-    const __amdgpu_buffer_rsrc_t src_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<unsigned char*>(p.src), 0, (unsigned)((size_t)(p.M / (p.DH * p.DW)) * p.SH * p.SW * p.SC), 0x00020000);
-    const __amdgpu_buffer_rsrc_t wgt_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char*>(p.wgt), 0,
-                                                                              (unsigned)((size_t)p.KH * p.KW * p.DN * p.SC), 0x00020000);
-
-    const int nk = (p.SC / KB8) * p.KH * p.KW;      // SC is a multiple of 64 (host check): no channel-chunk mask
-
-    // tiles are issued in k order, taps inside a channel chunk: (i_cc, i_kh, i_kw) is the next one, wave-uniform
-    int i_cc = 0, i_kh = 0, i_kw = 0;
-    auto issue_next = [&](int stage) {
-        unsigned char* As = smem + stage * STAGE + wave * 1024;        // wave-uniform: 16 rows x 64 B per DMA
-        unsigned char* Bs = As + BM * KB8;
-        const unsigned toff = (unsigned)(((i_kh * p.dil - p.pad_h) * p.SW + (i_kw * p.dil - p.pad_w)) * p.SC + i_cc * KB8);
-        const unsigned sel = (1u << i_kh) | (0x10000u << i_kw);
-#pragma unroll
-        for (int i = 0; i < A_N; ++i) {
-            const unsigned m = 0u - (unsigned)((a_msk[i] & sel) == sel);
-            const unsigned off = ((a_off[i] + toff) & m) | (OOB8 & ~m);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(src_rsrc, LDS_PTR8(As + i * (RPP_S * KB8)), 16, off, 0, 0, 0);
-        }
-        const unsigned woff = (unsigned)((i_kh * p.KW + i_kw) * p.DN * p.SC + i_cc * KB8);
-#pragma unroll
-        for (int i = 0; i < B_N; ++i) {
-            const unsigned m = b_ok[i];
-            const unsigned off = ((b_off[i] + woff) & m) | (OOB8 & ~m);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(wgt_rsrc, LDS_PTR8(Bs + i * (RPP_S * KB8)), 16, off, 0, 0, 0);
-        }
-        if (++i_kw == p.KW) {
-            i_kw = 0;
-            if (++i_kh == p.KH) {
-                i_kh = 0;
-                ++i_cc;
-            }
-        }
-    };
-
-    // ---- accumulators: D rows = output channels (filter operand first), D cols = pixels, as in conv_fwd_fp8_kernel
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-    const int wm = wave / WN, wn = wave - wm * WN;
-    const int li = lane & 31, lh = lane >> 5;
-    const int q0 = ((2 * lh) ^ ((li >> 2) & 3)) * 16;
-    const int a_row = (wm * 32 * TM + li) * KB8 + q0;
-    const int b_row = BM * KB8 + (wn * 32 * TN + li) * KB8 + q0;
-
-    auto load_frag = [&](const unsigned char* S, int addr) -> i32x8 {
-        const i32x4 lo = *reinterpret_cast<const i32x4*>(S + addr);
-        const i32x4 hi = *reinterpret_cast<const i32x4*>(S + (addr ^ 16));
-        return i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    };
-    auto compute = [&](int stage) {
-        const unsigned char* S = smem + stage * STAGE;
-        i32x8 a[TM], b[TN];
-#pragma unroll
-        for (int mi = 0; mi < TM; ++mi) a[mi] = load_frag(S, a_row + mi * 32 * KB8);
-#pragma unroll
-        for (int ni = 0; ni < TN; ++ni) b[ni] = load_frag(S, b_row + ni * 32 * KB8);
-#pragma unroll
-        for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < TN; ++ni)
-                acc[mi][ni] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(b[ni], a[mi], acc[mi][ni], 0, 0, 0, SCALE_ONE, 0, SCALE_ONE);
-    };
-
-    // ---- main loop: NS stages; tiles k+1 .. k+NS-1 stream in while tile k is multiplied
-#pragma unroll
-    for (int t = 0; t < NS - 1; ++t)
-        if (t < nk) issue_next(t);
-    int st_c = 0, st_i = NS - 1;
-    for (int k = 0; k < nk; ++k) {
-        const int later = nk - 1 - k;
-        wait_tiles_and_sync8<A_N + B_N, (NS - 2 > 4 ? 4 : NS - 2)>(later < NS - 2 ? later : NS - 2);      // tile k visible; stage st_i is free
-        if (k + NS - 1 < nk) issue_next(st_i);
-        compute(st_c);
-        st_c = st_c + 1 == NS ? 0 : st_c + 1;
-        st_i = st_i + 1 == NS ? 0 : st_i + 1;
-    }
-    __syncthreads();
-
-    // ---- epilogue through an fp32 LDS tile [BM][BN + 4], as in conv_fwd_fp8_kernel
-    float* Cs = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < TN; ++ni)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int ml = wm * 32 * TM + mi * 32 + li;
-                const int nl = wn * 32 * TN + ni * 32 + 8 * g + 4 * lh;
-                const f32x16& c = acc[mi][ni];
-                *reinterpret_cast<f32x4*>(Cs + ml * LDC + nl) = f32x4{c[4 * g], c[4 * g + 1], c[4 * g + 2], c[4 * g + 3]};
-            }
-    __syncthreads();
-    constexpr int TPR = BN / 8;               // threads per row, 8 channels each
-    constexpr int RPP = NTHR / TPR;           // rows per pass
-    const int cg = tid % TPR, r0 = tid / TPR;
-    const int n = n0 + cg * 8;
-    if (n >= p.DN) return;
-    float sc[8], bv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        sc[e] = p.s_in * p.s_w[n + e];
-        bv[e] = p.bias ? p.bias[n + e] : 0.f;
-    }
-#pragma unroll
-    for (int ps = 0; ps < BM / RPP; ++ps) {
-        const int ml = r0 + ps * RPP;
-        const int m = m0 + ml;
-        if (m >= p.M) continue;
-        const size_t o = (size_t)m * p.DN + n;
-        const f32x4 c0 = *reinterpret_cast<const f32x4*>(Cs + ml * LDC + cg * 8);
-        const f32x4 c1 = *reinterpret_cast<const f32x4*>(Cs + ml * LDC + cg * 8 + 4);
-        float v[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            v[e] = v[e] * sc[e] + bv[e];
-            if (p.relu) v[e] = v[e] > 0.f ? v[e] : 0.f;
-        }
-        if (p.mode == FP8_OUT_F32) {
-            float* d = reinterpret_cast<float*>(p.dst) + o;
-            *reinterpret_cast<f32x4*>(d) = f32x4{v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<f32x4*>(d + 4) = f32x4{v[4], v[5], v[6], v[7]};
-        } else if (p.mode != FP8_OUT_E4M3) {
-            *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(p.dst) + o) =
-                u32x4{pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
-        }
-        if (p.mode == FP8_OUT_E4M3 || p.mode == FP8_OUT_BF16_E4M3) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = v[e] / p.s_out;
-            *reinterpret_cast<u32x2*>(p.dst8 + o) = u32x2{pack4_e4m3(v[0], v[1], v[2], v[3]), pack4_e4m3(v[4], v[5], v[6], v[7])};
-        }
-    }
-}
-
-template <int WM, int WN, int TM, int TN, int NS>
-static void launch_fwd8k(GatherArgs8K& a, const char* label, double flops, double bytes, hipStream_t s) {
-    constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
-    constexpr size_t stages = NS * (size_t)(BM + BN) * KB8, ctile = (size_t)BM * (BN + 4) * 4;
-    constexpr size_t lds = stages > ctile ? stages : ctile;
-    static_assert(lds <= 66 * 1024, "LDS: two workgroups per CU");
-    auto kern = conv_bigk_fwd_fp8_kernel<WM, WN, TM, TN, NS>;
-    static bool once = (set_lds(kern, lds), true);
-    (void)once;
-    // Workgroup order.  Consecutive workgroups share an XCD's L2 (xcd_remap).  With filter columns fastest (conv_fwd_fp8's order) the
-    // workgroups resident on an XCD cover every column, and each row of pixel tiles streams the whole filter image: MT x its bytes
-    // in all.  With pixel tiles fastest they share one column, and each column streams the input: NT x its bytes.  A column of a
-    // filter with more than 9 taps (taps x BN x Ci bytes) is always larger than a pixel tile's input (about BM x Ci), so this kernel
-    // takes pixel tiles fastest.  fc6 at batch 128 (102 MB of filter, 24 MB of input, MT 361, NT 32): 4.92 against 9.70 ms.
-    a.MT = cdiv(a.M, BM);
-    ProfScope prof(label, flops, bytes, s);
-    SSD_LAUNCH_STOP(kern, dim3(a.MT * cdiv(a.DN, BN)), dim3(64 * WM * WN), lds, s, a);
-    HIP_OK(hipGetLastError());
-}
-
-bool conv_bigk_fwd_fp8_supported(const ConvDesc& d, const char** why) {
-    const char* w = nullptr;
-    const long long taps = (long long)d.KH * d.KW;
-    if (d.KH < 1 || d.KW < 1 || d.KH > 11 || d.KW > 11 || taps < 10) w = "fp8 conv (more than 9 taps): KH and KW in 1 ... 11 with 10 ... 121 taps";
-    else if (d.Ci < 64 || d.Ci % 64 != 0) w = "fp8 conv (more than 9 taps): Ci must be a multiple of 64";
-    else if (d.Co < 8 || d.Co % 8 != 0) w = "fp8 conv (more than 9 taps): Co must be a multiple of 8";
-    else if (d.stride < 1 || d.dil < 1) w = "fp8 conv (more than 9 taps): stride and dilation must be positive";
-    else if (d.B < 1 || d.Ho < 1 || d.Wo < 1 || d.Hi < 1 || d.Wi < 1) w = "fp8 conv (more than 9 taps): empty tensor";
-    else if ((long long)d.B * d.Hi * d.Wi * d.Ci >= (1LL << 31) - 16 || (long long)d.B * d.Ho * d.Wo * d.Co >= (1LL << 31) - 16)
-        w = "fp8 conv (more than 9 taps): a tensor of this layer exceeds the 32-bit offsets: lower the batch";
-    else if (taps * d.Co * d.Ci >= (1LL << 31) - 16) w = "fp8 conv (more than 9 taps): the filter image exceeds the 32-bit offsets";
-    if (why) *why = w;
-    return w == nullptr;
-}
-
-// Where an fp8 handle uses this kernel: SSD_FP8_BIGK (read per handle) = 1 takes every supported layer with at least 256 input
+// ... and for more than 9 taps: SSD_FP8_BIGK (read per handle) = 1 takes every supported layer with at least 256 input
 // channels (the fc graph's mod_conv6), 0 leaves it on conv_bigk_fwd_bf16 with a quantise pass behind it.  Unset = 1: in interleaved
 // rounds at batch 128 (tools/infer_rate.py --a-trous false, profiles/fp8_fc_infer_rate.txt) the mod_conv6 row separated
 // from the bf16 kernel's in fp8's favour, and the whole handle from the handle under SSD_FP8_BIGK=0.
 constexpr int FP8_BIGK_DEFAULT = 1;
 bool conv_bigk_fwd_fp8_worthwhile(const ConvDesc& d) { return d.Ci >= 256 && env_int("SSD_FP8_BIGK", FP8_BIGK_DEFAULT) == 1; }
 
-// Tiles as in conv_fwd_fp8: 0 = 128 x 128 with four stages, 1 = 64 x 64 with six; SSD_TILE_FP8 forces one.
+static void run_fp8(bool bigk, const ConvDesc& d, const unsigned char* x8, const unsigned char* w8, float s_in, const float* s_w, const float* bias,
+                    void* y, unsigned char* y8, int out_mode, float s_out, bool relu, hipStream_t s) {
+    GatherArgs8 a{};
+    a.src = x8; a.wgt = w8; a.bias = bias; a.s_w = s_w; a.dst = y; a.dst8 = y8; a.s_in = s_in; a.s_out = s_out;
+    conv_fwd_e4m3<false>(bigk, d, a, out_mode, relu, s);
+}
+void conv_fwd_fp8(const ConvDesc& d, const unsigned char* x8, const unsigned char* w8, float s_in, const float* s_w, const float* bias,
+                  void* y, unsigned char* y8, int out_mode, float s_out, bool relu, hipStream_t s) {
+    run_fp8(false, d, x8, w8, s_in, s_w, bias, y, y8, out_mode, s_out, relu, s);
+}
 void conv_bigk_fwd_fp8(const ConvDesc& d, const unsigned char* x8, const unsigned char* w8, float s_in, const float* s_w, const float* bias,
                        void* y, unsigned char* y8, int out_mode, float s_out, bool relu, hipStream_t s) {
-    SSD_REQUIRE(d.KH * d.KW > 9, "fp8 conv: %dx%d taps: 9 taps or fewer run on conv_fwd_fp8 (ssd_op_conv2d_fwd_fp8)", d.KH, d.KW);
-    const char* why = nullptr;
-    SSD_REQUIRE(conv_bigk_fwd_fp8_supported(d, &why), "%s (got %dx%d taps, Ci %d, Co %d)", why, d.KH, d.KW, d.Ci, d.Co);
-    SSD_REQUIRE(out_mode >= FP8_OUT_BF16 && out_mode <= FP8_OUT_BF16_E4M3, "fp8 conv: unknown output mode %d", out_mode);
-    const bool wants8 = out_mode == FP8_OUT_E4M3 || out_mode == FP8_OUT_BF16_E4M3;
-    SSD_REQUIRE(!wants8 || (y8 != nullptr && s_out > 0.f), "fp8 conv: an e4m3 output needs its buffer and a positive scale");
-    SSD_REQUIRE(out_mode == FP8_OUT_E4M3 || y != nullptr, "fp8 conv: null output");
-    SSD_REQUIRE(x8 && w8 && s_w && s_in > 0.f, "fp8 conv: null operand or non-positive input scale");
-    GatherArgs8K a{};
-    a.src = x8; a.wgt = w8; a.bias = bias; a.s_w = s_w; a.dst = y; a.dst8 = y8; a.s_in = s_in; a.s_out = wants8 ? s_out : 1.f;
-    a.M = d.B * d.Ho * d.Wo; a.DH = d.Ho; a.DW = d.Wo; a.DN = d.Co;
-    a.SH = d.Hi; a.SW = d.Wi; a.SC = d.Ci;
-    a.KH = d.KH; a.KW = d.KW; a.dil = d.dil; a.pad_h = d.pad_h; a.pad_w = d.pad_w;
-    a.mul = d.stride; a.relu = relu; a.mode = out_mode;
-    const double fl = conv_flops(d);
-    const double by = (double)d.B * d.Hi * d.Wi * d.Ci + (double)d.KH * d.KW * d.Ci * d.Co +
-                      (double)d.B * d.Ho * d.Wo * d.Co * (out_mode == FP8_OUT_F32 ? 4 : out_mode == FP8_OUT_BF16 ? 2 : out_mode == FP8_OUT_E4M3 ? 1 : 3);
-    int cfg = env_int("SSD_TILE_FP8", -1);
-    if (cfg != 0 && cfg != 1) cfg = (long long)cdiv(a.M, 128) * cdiv(a.DN, 128) <= 256 ? 1 : 0;
-    if (cfg == 0) launch_fwd8k<2, 2, 2, 2, 4>(a, "conv_bigk_fwd_fp8_128x128", fl, by, s);
-    else launch_fwd8k<2, 2, 1, 1, 6>(a, "conv_bigk_fwd_fp8_64x64x6", fl, by, s);
+    run_fp8(true, d, x8, w8, s_in, s_w, bias, y, y8, out_mode, s_out, relu, s);
 }
 
 // =================================================================================
@@ -777,11 +268,6 @@ __global__ __launch_bounds__(256) void quantize_fp8_x8_kernel(const T* __restric
         for (int e = 0; e < 8; ++e) v[e] = v[e] / scale;
         *reinterpret_cast<u32x2*>(y + i * 8) = u32x2{pack4_e4m3(v[0], v[1], v[2], v[3]), pack4_e4m3(v[4], v[5], v[6], v[7])};
     }
-}
-
-static int grid8(size_t items, int per_block) {
-    const size_t g = (items + per_block - 1) / per_block;
-    return (int)std::min<size_t>(std::max<size_t>(g, 1), 256 * 32);
 }
 
 void quantize_fp8(const void* x, bool x_f32, size_t n, float scale, unsigned char* y8, hipStream_t s) {

@@ -109,8 +109,54 @@ def run_conv(x8, w8, s_in, s_w, bias, geom, mode, s_out, relu):
     return (None if y_ is None else y_.float().cpu().numpy()), (None if y8_ is None else y8_.cpu().numpy())
 
 
-LAYOUT_CASES = [('3x3 SAME 64->64 2x9x7', 2, 9, 7, 64, 64, 3, 1), ('1x1 128->64 1x5x5', 1, 5, 5, 128, 64, 1, 1),
-                ('3x3 dil6 128->64 1x19x19', 1, 19, 19, 128, 64, 3, 6)]
+def geom2(hi, wi, kh, kw, stride, dil, padding):
+    """gpu_util.conv_geom with kh and kw apart: (pad_h, pad_w, ho, wo)"""
+    if padding == 'SAME':
+        ph, ho = same_pad(hi, kh, stride, dil)
+        pw, wo = same_pad(wi, kw, stride, dil)
+        return ph, pw, ho, wo
+    return 0, 0, (hi - ((kh - 1) * dil + 1)) // stride + 1, (wi - ((kw - 1) * dil + 1)) // stride + 1
+
+
+# The last three are what the tap walk (counters over kernel rows and columns, a separable row / column validity mask) can get wrong
+# at few taps: a stride with SAME on an even and an odd side (leading pad 0 and 1), Co across the 64-wide tile and inside the 128-wide
+# one, M = 25; kh != kw with two channel chunks and the smallest Co; nine taps in one kernel row, wider than any 3x3.
+#               name                                  b  hi  wi  ci   co  kh kw stride dil padding
+LAYOUT_CASES = [('3x3 SAME 64->64 2x9x7',             2,  9,  7, 64,  64, 3, 3, 1, 1, 'SAME'),
+                ('1x1 128->64 1x5x5',                 1,  5,  5, 128, 64, 1, 1, 1, 1, 'SAME'),
+                ('3x3 dil6 128->64 1x19x19',          1, 19, 19, 128, 64, 3, 3, 1, 6, 'SAME'),
+                ('3x3 stride2 SAME 64->72 1x10x9',    1, 10,  9, 64,  72, 3, 3, 2, 1, 'SAME'),
+                ('2x3 VALID 128->8 1x6x7',            1,  6,  7, 128, 8,  2, 3, 1, 1, 'VALID'),
+                ('1x9 SAME 64->64 1x3x11',            1,  3, 11, 64,  64, 1, 9, 1, 1, 'SAME')]
+
+
+def layout_reference_input(a, case):
+    """The oracle pads SAME by the kernel's rows, for rows and columns alike.  For kh != kw: (a [B,H,W,C] with the zeros SAME adds,
+    'VALID'), the same sums; otherwise (a, padding).  The pads come from same_pad, like the pad_h / pad_w that geom2 hands to the
+    kernel: for these cases the sums and the output shape are the oracle's, the split of the padding is not checked against it (the
+    stride-2 SAME case, a square kernel, goes through the oracle's own SAME)."""
+    hi, wi, kh, kw, stride, dil, padding = case[2], case[3], *case[6:]
+    if padding != 'SAME' or kh == kw:
+        return a, padding
+    pads = []
+    for n, k in ((hi, kh), (wi, kw)):
+        lead, out = same_pad(n, k, stride, dil)
+        pads.append((lead, max((out - 1) * stride + (k - 1) * dil + 1 - n, 0) - lead))
+    return np.pad(a, ((0, 0), pads[0], pads[1], (0, 0))), 'VALID'
+
+
+def layout_operands(case):
+    """(x integers [B,H,W,Ci] in 0 ... 7, filter codes [tap][Co][Ci] of integers in -2 ... 2, bias, geom) of a layout case:
+    asymmetric in pixel, channel, tap and output channel"""
+    name, b, hi, wi, ci, co, kh, kw, stride, dil, padding = case
+    ph, pw, ho, wo = geom2(hi, wi, kh, kw, stride, dil, padding)
+    B, H, W, Cc = np.meshgrid(np.arange(b), np.arange(hi), np.arange(wi), np.arange(ci), indexing='ij')
+    iv = (3 * B + 5 * H + 7 * W + 11 * Cc + (H * W) % 3 + (Cc * W) % 5 + (Cc // 16)) % 8
+    KH, KW, CI, CO = np.meshgrid(np.arange(kh), np.arange(kw), np.arange(ci), np.arange(co), indexing='ij')
+    wv = (2 * KH + 3 * KW + CI + 7 * CO + (CI * CO) % 3 + (KH * CI) % 2 + (CI // 32)) % 5 - 2
+    w8 = np.ascontiguousarray(np.transpose(f8.encode(wv.astype(np.float64)).reshape(kh * kw, ci, co), (0, 2, 1)))
+    bias = ((np.arange(co) * 5) % 17 - 8).astype(np.float32)
+    return iv, w8, bias, (b, hi, wi, ci, ho, wo, co, kh, kw, stride, dil, ph, pw)
 
 
 @pytest.mark.parametrize('tile', ['0', '1'], ids=['128x128', '64x64'])
@@ -118,19 +164,14 @@ LAYOUT_CASES = [('3x3 SAME 64->64 2x9x7', 2, 9, 7, 64, 64, 3, 1), ('1x1 128->64 
 def test_conv_layout_exact(case, tile, monkeypatch):
     """small integers, asymmetric in pixel, channel, tap and output channel; all scales 1: every sum is an integer < 2^24"""
     monkeypatch.setenv('SSD_TILE_FP8', tile)
-    name, b, hi, wi, ci, co, k, dil = case
-    ph, pw, ho, wo = conv_geom(hi, wi, k, 1, dil, 'SAME')
-    B, H, W, Cc = np.meshgrid(np.arange(b), np.arange(hi), np.arange(wi), np.arange(ci), indexing='ij')
-    xv = (3 * B + 5 * H + 7 * W + 11 * Cc + (H * W) % 3 + (Cc * W) % 5 + (Cc // 16)) % 8
-    KH, KW, CI, CO = np.meshgrid(np.arange(k), np.arange(k), np.arange(ci), np.arange(co), indexing='ij')
-    wv = (2 * KH + 3 * KW + CI + 7 * CO + (CI * CO) % 3 + (KH * CI) % 2 + (CI // 32)) % 5 - 2
+    name, co, (kh, kw, stride, dil, padding) = case[0], case[5], case[6:]
+    xv, w8, bias, geom = layout_operands(case)
     x8 = f8.encode(xv.astype(np.float64))
-    w8 = np.ascontiguousarray(np.transpose(f8.encode(wv.astype(np.float64)).reshape(k * k, ci, co), (0, 2, 1)))
-    bias = ((np.arange(co) * 5) % 17 - 8).astype(np.float32)
-    acc, _ = f8.conv_codes(x8, w8, k, k, 1, dil, 'SAME')
+    x8_ref, padding_ref = layout_reference_input(x8, case)
+    acc, _ = f8.conv_codes(x8_ref, w8, kh, kw, stride, dil, padding_ref)
     want = acc + bias
+    assert want.shape == (geom[0], geom[4], geom[5], co)
     assert np.abs(want).max() < 2 ** 24 and len(np.unique(want)) > 50
-    geom = (b, hi, wi, ci, ho, wo, co, k, k, 1, dil, ph, pw)
     y, _ = run_conv(x8, w8, 1.0, np.ones(co), bias, geom, f8.OUT_F32, 0.0, False)
     assert np.array_equal(y, want.astype(np.float32)), f'{name}: {np.argwhere(y != want)[:4]}'
     y, y8 = run_conv(x8, w8, 1.0, np.ones(co), bias, geom, f8.OUT_BF16_E4M3, 1.0, True)

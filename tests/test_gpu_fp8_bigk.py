@@ -11,19 +11,13 @@ import torch
 import fc_ref
 import fp8_ref as f8
 import test_gpu_fp8 as t8
-from gpu_util import lib, check, dev, ptr, host, same_pad, rel_err
+from gpu_util import lib, check, dev, ptr, host, rel_err
 from ssd_tensorflow_amd._lib import last_error
 
 pytestmark = pytest.mark.gpu
 
 
-def geom2(hi, wi, kh, kw, stride, dil, padding):
-    """gpu_util.conv_geom with kh and kw apart: (pad_h, pad_w, ho, wo)"""
-    if padding == 'SAME':
-        ph, ho = same_pad(hi, kh, stride, dil)
-        pw, wo = same_pad(wi, kw, stride, dil)
-        return ph, pw, ho, wo
-    return 0, 0, (hi - ((kh - 1) * dil + 1)) // stride + 1, (wi - ((kw - 1) * dil + 1)) // stride + 1
+geom2 = t8.geom2      # gpu_util.conv_geom with kh and kw apart: (pad_h, pad_w, ho, wo)
 
 
 def run_conv_bigk(x8, w8, s_in, s_w, bias, geom, mode, s_out, relu):

@@ -15,7 +15,7 @@ import fp8_ref as f8
 import mxfp8_ref as mx
 from gpu_util import lib, check, dev, ptr, host, conv_geom, same_pad, rel_err
 from ssd_tensorflow_amd._lib import last_error
-from test_gpu_fp8 import LAYOUT_CASES, REAL_CASES, FOUR_MODES_CASE, FP8_LAYERS, FP8_SCALED, FP8_POOLS, bf16_round, u8, gpu_quantize_filter
+from test_gpu_fp8 import LAYOUT_CASES as FP8_LAYOUT_CASES, layout_operands, layout_reference_input, REAL_CASES, FOUR_MODES_CASE, FP8_LAYERS, FP8_SCALED, FP8_POOLS, bf16_round, u8, gpu_quantize_filter
 
 pytestmark = pytest.mark.gpu
 
@@ -81,32 +81,38 @@ def run_conv(x8, xs, w8, s_w, bias, geom, mode, relu):
     return (None if y_ is None else y_.float().cpu().numpy()), (y8_.cpu().numpy() if wants8 else None), (ys_.cpu().numpy() if wants8 else None)
 
 
+# test_gpu_fp8's cases.  An MX output needs Co % 32 == 0: a case with another Co checks the fp32 and the bf16 output, and the stride-2
+# case is there once more with Co = 96 (across the 64-wide tile, inside the 128-wide one) for the MX output
+STRIDE2 = next(c for c in FP8_LAYOUT_CASES if c[0] == '3x3 stride2 SAME 64->72 1x10x9')
+LAYOUT_CASES = FP8_LAYOUT_CASES + [('3x3 stride2 SAME 64->96 1x10x9',) + STRIDE2[1:5] + (96,) + STRIDE2[6:]]
+
+
 @pytest.mark.parametrize('tile', ['0', '1'], ids=['128x128', '64x64'])
 @pytest.mark.parametrize('case', LAYOUT_CASES, ids=[c[0] for c in LAYOUT_CASES])
 def test_conv_layout_exact(case, tile, monkeypatch):
     """activations i * 2^s with i in 0 ... 7 and s in -2 ... 2 varying with pixel and block, filter codes in -2 ... 2, asymmetric in
     pixel, channel, tap and output channel: every sum is a multiple of 1/4 below 2^22, exact in any order"""
     monkeypatch.setenv('SSD_TILE_FP8', tile)
-    name, b, hi, wi, ci, co, k, dil = case
-    ph, pw, ho, wo = conv_geom(hi, wi, k, 1, dil, 'SAME')
+    name, b, hi, wi, ci, co, kh, kw, stride, dil, padding = case
+    iv, w8, bias, geom = layout_operands(case)
     B, H, W, Cc = np.meshgrid(np.arange(b), np.arange(hi), np.arange(wi), np.arange(ci), indexing='ij')
-    iv = (3 * B + 5 * H + 7 * W + 11 * Cc + (H * W) % 3 + (Cc * W) % 5 + (Cc // 16)) % 8
     sv = (2 * B + 3 * H + W + 2 * (Cc // 32) + (H * (Cc // 32)) % 3) % 5 - 2
     xv = np.ldexp(iv.astype(np.float32), sv).astype(np.float32)
     x8, xs = mx.quantize(xv)
     assert np.array_equal(mx.dequantize(x8, xs), xv.astype(np.float64)) and len(np.unique(xs)) >= 5      # lossless; scales vary
-    KH, KW, CI, CO = np.meshgrid(np.arange(k), np.arange(k), np.arange(ci), np.arange(co), indexing='ij')
-    wv = (2 * KH + 3 * KW + CI + 7 * CO + (CI * CO) % 3 + (KH * CI) % 2 + (CI // 32)) % 5 - 2
-    w8 = np.ascontiguousarray(np.transpose(f8.encode(wv.astype(np.float64)).reshape(k * k, ci, co), (0, 2, 1)))
-    bias = ((np.arange(co) * 5) % 17 - 8).astype(np.float32)
-    acc, absacc = mx.conv_values(xv, w8, k, k, 1, dil, 'SAME')
+    xv_ref, padding_ref = layout_reference_input(xv, case)
+    acc, absacc = mx.conv_values(xv_ref, w8, kh, kw, stride, dil, padding_ref)
     want = acc + bias
+    assert want.shape == (geom[0], geom[4], geom[5], co)
     assert absacc.max() + 8 < 2 ** 22 and np.array_equal(want * 4, np.round(want * 4)) and len(np.unique(want)) > 50
-    geom = (b, hi, wi, ci, ho, wo, co, k, k, 1, dil, ph, pw)
     y, _, _ = run_conv(x8, xs, w8, np.ones(co), bias, geom, mx.OUT_F32, False)
     assert np.array_equal(y, want.astype(np.float32)), f'{name}: {np.argwhere(y != want)[:4]}'
-    y, y8, ys = run_conv(x8, xs, w8, np.ones(co), bias, geom, mx.OUT_BF16_MX, True)
     pos = np.maximum(want, 0).astype(np.float32)
+    if co % 32:
+        y, _, _ = run_conv(x8, xs, w8, np.ones(co), bias, geom, mx.OUT_BF16, True)
+        assert np.array_equal(y, bf16_round(pos))
+        return
+    y, y8, ys = run_conv(x8, xs, w8, np.ones(co), bias, geom, mx.OUT_BF16_MX, True)
     assert np.array_equal(y, bf16_round(pos))
     want8, wants = mx.quantize(pos)
     assert np.array_equal(ys, wants) and np.array_equal(y8, want8)
