@@ -186,6 +186,10 @@ SIGNATURES = {
     'ssd_op_conv2d_fwd_mxfp8': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32] + [i32] * 14 + [vp]),
     'ssd_op_conv2d_fwd_mxfp8_bigk': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32] + [i32] * 14 + [vp]),
     'ssd_op_maxpool_fwd_mxfp8': (i32, [vp, vp, vp, vp] + [i32] * 10 + [vp]),
+    'ssd_op_quantize_mxfp6': (i32, [vp, i32, sz, i32, vp, vp, vp]),
+    'ssd_op_quantize_filter_mxfp6': (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    'ssd_op_conv2d_fwd_mxfp6': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32] + [i32] * 14 + [vp]),
+    'ssd_op_maxpool_fwd_mxfp6': (i32, [vp, vp, vp, vp] + [i32] * 10 + [vp]),
     'ssd_op_maxpool_fwd': (i32, [vp, vp] + [i32] * 10 + [vp]),
     'ssd_op_maxpool_bwd': (i32, [vp, vp, vp, i32, i32] + [i32] * 10 + [vp]),
     'ssd_op_clock_monitor': (i32, [vp, i32, C.c_uint, vp]),

@@ -711,6 +711,7 @@ static int create_handle(const char* preset, int num_classes, int max_batch, int
     *out = nullptr;
     SSD_REQUIRE(!(dtype == SSD_DTYPE_FP8 && training), "SSD_DTYPE_FP8 is inference only: create the handle with training = 0");
     SSD_REQUIRE(!(dtype == SSD_DTYPE_MXFP8 && training), "SSD_DTYPE_MXFP8 is inference only: create the handle with training = 0");
+    SSD_REQUIRE(!(dtype == SSD_DTYPE_MXFP6 && training), "SSD_DTYPE_MXFP6 is inference only: create the handle with training = 0");
     DeviceGuard dev_guard_(device);
     auto n = std::make_unique<Net>(preset, num_classes, max_batch, device, training != 0, seed, ext_params_dev, ext_grads_dev,
                                    ext_momentum_dev, dtype, graph);
@@ -1350,6 +1351,36 @@ int ssd_op_maxpool_fwd_mxfp8(const void* x8, const void* xscales, void* y8, void
     API_BEGIN
     PoolDesc d{b, hi, wi, c, ho, wo, k, stride, pad_h, pad_w};
     maxpool_fwd_mxfp8(d, (const unsigned char*)x8, (const unsigned char*)xscales, (unsigned char*)y8, (unsigned char*)yscales, (hipStream_t)stream);
+    API_END
+}
+// mxfp6 inference kernels (conv_mxfp6.hip)
+int ssd_op_quantize_mxfp6(const void* x, int x_f32, size_t rows, int c, void* y6, void* yscales, void* stream) {
+    API_BEGIN
+    quantize_mxfp6(x, x_f32 != 0, rows, c, (unsigned char*)y6, (unsigned char*)yscales, (hipStream_t)stream);
+    API_END
+}
+int ssd_op_quantize_filter_mxfp6(const float* w, void* w6, void* wscales, int taps, int ci, int co, void* stream) {
+    API_BEGIN
+    SSD_REQUIRE(w && w6 && wscales && taps >= 1 && ci >= 1 && co >= 1, "quantize_filter_mxfp6: null argument or empty filter");
+    FilterQuantPlan plan;
+    plan.add(0, 0, 0, taps, ci, co);
+    quantize_filters_mxfp6(plan, w, (unsigned char*)w6, (unsigned char*)wscales, (hipStream_t)stream);
+    API_END
+}
+int ssd_op_conv2d_fwd_mxfp6(const void* x6, const void* xscales, const void* w6, const void* wscales, const float* bias, void* y, void* y6,
+                            void* yscales, int out_mode, int b, int hi, int wi, int ci, int ho, int wo, int co, int kh, int kw, int stride,
+                            int dil, int pad_h, int pad_w, int relu, void* stream) {
+    API_BEGIN
+    conv_fwd_mxfp6(mk(b, hi, wi, ci, ho, wo, co, kh, kw, stride, dil, pad_h, pad_w), (const unsigned char*)x6, (const unsigned char*)xscales,
+                   (const unsigned char*)w6, (const unsigned char*)wscales, bias, y, (unsigned char*)y6, (unsigned char*)yscales, out_mode, relu != 0,
+                   (hipStream_t)stream);
+    API_END
+}
+int ssd_op_maxpool_fwd_mxfp6(const void* x6, const void* xscales, void* y6, void* yscales, int b, int hi, int wi, int c, int ho, int wo, int k,
+                             int stride, int pad_h, int pad_w, void* stream) {
+    API_BEGIN
+    PoolDesc d{b, hi, wi, c, ho, wo, k, stride, pad_h, pad_w};
+    maxpool_fwd_mxfp6(d, (const unsigned char*)x6, (const unsigned char*)xscales, (unsigned char*)y6, (unsigned char*)yscales, (hipStream_t)stream);
     API_END
 }
 int ssd_op_maxpool_fwd(const float* x, float* y, int b, int hi, int wi, int c, int ho, int wo, int k, int stride, int pad_h,

@@ -268,4 +268,25 @@ void quantize_mxfp8(const void* x, bool x_f32, size_t rows, int C, unsigned char
 // max-pooling of MX tensors: the maximum of the dequantised cells per channel, quantised again per block; C a multiple of 32
 void maxpool_fwd_mxfp8(const PoolDesc& d, const unsigned char* x8, const unsigned char* xs, unsigned char* y8, unsigned char* ys, hipStream_t s);
 
+// ---- mxfp6 inference kernels (conv_mxfp6.hip): OCP MX FP6 E2M3 codes, 32 consecutive channels = one 24-byte string (code j
+// in bits 6 j ... 6 j + 5, little-endian) + one E8M0 scale byte: activations [B,H,W,C/32][24] + [B,H,W,C/32], filters with blocks along
+// Ci, w6 [tap][Co][Ci/32][24] + ws [tap][Co][Ci/32] and no per-channel scale ----
+// scale rule on the bits of the block's fp32 absmax: x = clamp(E - 2 + (mantissa > 0x700000), -127, 127), byte x + 127 (an all-zero
+// block: byte 0); codes = RNE(clamp(ldexp(v, -x), -7.5, 7.5)).  y = relu?(acc + bias[co]) in fp32.  Output modes: FP8_OUT_BF16, _F32,
+// _MX, _BF16_MX, "MX" meaning this format.
+// KH * KW <= 9, Ci a multiple of 64, Co a multiple of 8, any stride / dilation / leading padding, no empty tensor, every tensor and the
+// filter below the 32-bit offsets; why (optional) = the reason text, a string literal.  There is no kernel for more than 9 taps.
+bool conv_fwd_mxfp6_supported(const ConvDesc& d, const char** why);
+// An MX output needs Co % 32 == 0.  xs and ws are read in whole dwords: their allocations must be readable up to their sizes rounded
+// up to 4 bytes, and start at even addresses; the code buffers at multiples of 8.  Anything unsupported throws before a launch.
+void conv_fwd_mxfp6(const ConvDesc& d, const unsigned char* x6, const unsigned char* xs, const unsigned char* w6, const unsigned char* ws,
+                    const float* bias, void* y, unsigned char* y6, unsigned char* ys, int out_mode, bool relu, hipStream_t s);
+// bf16 or fp32 [rows][C] -> codes [rows][C / 32][24] + scales [rows][C / 32]; C a multiple of 32
+void quantize_mxfp6(const void* x, bool x_f32, size_t rows, int C, unsigned char* y6, unsigned char* ys, hipStream_t s);
+// One launch quantises every listed layer's fp32 filter [tap][Ci][Co] (element offset off in w) into its code image (byte offset off8 in
+// w6, a multiple of 8) and its scales (byte offset offs in ws); Ci a multiple of 32
+void quantize_filters_mxfp6(const FilterQuantPlan& plan, const float* w, unsigned char* w6, unsigned char* ws, hipStream_t s);
+// max-pooling of mxfp6 tensors: the maximum of the dequantised cells per channel, quantised again per block; C a multiple of 32
+void maxpool_fwd_mxfp6(const PoolDesc& d, const unsigned char* x6, const unsigned char* xs, unsigned char* y6, unsigned char* ys, hipStream_t s);
+
 }  // namespace ssd

@@ -65,6 +65,7 @@ struct Op {
     // layer's per-channel filter scales
     bool fp8 = false;
     size_t sw_off = 0;
+    size_t w6_off = 0;      // mxfp6 handle: byte offset of the layer's code image in w8_
     // Round 6 (fp32): the Winograd F(4x4, 3x3) form of this layer's passes (net.hip plan_winograd; conv.h wino_*): forward, data
     // gradient, weight gradient; the layer's filter transforms [36][Ci][Co] / [36][Co][Ci] and its input's transform [36][tiles][Ci]
     // (written by forward, read by the weight gradient)
@@ -98,7 +99,8 @@ public:
     // dtype 0: fp32 everywhere (BASELINE.json configs[1]); 1: bf16 activations / gradients / filter mirrors with fp32
     // master weights, fp32 accumulation and fp32 loss (configs[2]); 2: fp8, an inference-only bf16 handle whose eligible
     // trunk convolutions (conv3_2 ... mod_conv7) run on e4m3 operands (plan_fp8); 3: mxfp8, the same layers with E8M0 block scales
-    // chosen by each producer (conv_mxfp8.hip): no per-tensor scales, no calibration
+    // chosen by each producer (conv_mxfp8.hip): no per-tensor scales, no calibration; 4: mxfp6, the mxfp8 plan on e2m3 operands
+    // with block scales on activations and filters (conv_mxfp6.hip), layers with more than 9 taps on bf16
     Net(const char* preset, int num_classes, int max_batch, int device, bool training, unsigned long long seed,
         float* ext_params, float* ext_grads, float* ext_momentum, int dtype = 0, int graph = 0);
     ~Net();
@@ -158,7 +160,7 @@ public:
     int nvars() const { return C_ + 5; }
     int max_batch() const { return Bmax_; }
     bool training() const { return training_; }
-    int dtype() const { return mx_ ? 3 : fp8_ ? 2 : bf16_ ? 1 : 0; }
+    int dtype() const { return mx6_ ? 4 : mx_ ? 3 : fp8_ ? 2 : bf16_ ? 1 : 0; }
     // fp8 handle: one scale per tensor that a convolution writes as e4m3, in graph order
     void fp8_calibrate(const float* x_dev, int b, bool accumulate);      // the graph on the bf16 kernels; scale = max(absmax, tiny) / 448
     int fp8_num_scales() const;
@@ -195,6 +197,10 @@ private:
     // fp32 masters by every forward pass like the bf16 mirrors (one launch, behind cast_filters)
     bool fp8_ = false;
     bool mx_ = false;                      // an fp8 handle (fp8_ is set) of the mxfp8 kind: block scales in Tensor::scale8
+    // ... of the mxfp6 kind (mx_ is set too; conv_mxfp6.hip): data8 holds 24 bytes per 32 channels, the filter images lie in w8_ at
+    // Op::w6_off with their block scales in wsc6_ at Op::sw_off (bytes), and layers with more than 9 taps stay on bf16
+    bool mx6_ = false;
+    unsigned char* wsc6_ = nullptr;
     bool fp8_calibrated_ = false, fp8_as_bf16_ = false;      // fp8_as_bf16_: this pass is the calibration run
     unsigned char* w8_ = nullptr;
     float *sw8_ = nullptr, *absmax8_ = nullptr;

@@ -587,6 +587,8 @@ void Net::plan_winograd() {
 // e4m3 (data8).  A pool between two fp8 layers runs on the bytes and its output shares its input's scale.  Where the e4m3 form is
 // needed behind a bf16 producer (conv3_1's output in the a-trous graph) a quantise pass of its own makes it.  A tensor with any non-fp8 reader (conv4_3: the l2 norm; mod_conv7's output: its head and conv8_1) keeps its
 // bf16 form as well (wants16).  Runs before plan_pool_fusion, which leaves the fp8 layers' pools alone.
+// An mxfp6 handle (mx6_) takes the mxfp8 plan for up to 9 taps -- the same eligibility, on conv_fwd_mxfp6 -- and leaves a layer
+// with more on conv_bigk_fwd_bf16; its filter images and their block scales get arenas of their own (Op::w6_off, Op::sw_off in bytes).
 void Net::plan_fp8() {
     size_t nsw = 0;
     for (Tensor& t : tensors_) t.wants16 = false;
@@ -598,7 +600,9 @@ void Net::plan_fp8() {
         const ConvDesc d = conv_desc(op, Bmax_);
         // (mxfp8: the fc graph's fc6 stays on bf16 with a quantise pass behind it unless SSD_MXFP8_BIGK=1 -- conv_bigk_fwd_mxfp8_worthwhile;
         // asked with the most demanding output mode, so that whichever form the readers below take can be launched)
-        const bool kernel8 = !conv_bigk(d) ? conv_fwd_fp8_supported(d, nullptr) && conv_fwd_fp8_worthwhile(d)
+        // (mxfp6: the mxfp8 handle's layers up to 9 taps -- the same Ci % 64, Co % 8 contract -- and nothing above: no mxfp6 kernel for more)
+        const bool kernel8 = !conv_bigk(d) ? conv_fwd_fp8_supported(d, nullptr) && conv_fwd_fp8_worthwhile(d) && (!mx6_ || conv_fwd_mxfp6_supported(d, nullptr))
+                             : mx6_        ? false
                              : mx_         ? conv_bigk_fwd_mxfp8_supported(d, FP8_OUT_BF16_MX, nullptr) && conv_bigk_fwd_mxfp8_worthwhile(d)
                                            : conv_bigk_fwd_fp8_supported(d, nullptr) && conv_bigk_fwd_fp8_worthwhile(d);
         op.fp8 = op.head < 0 && i < tail_first_ && !tensors_[op.in].data_f32 && kernel8;
@@ -628,8 +632,18 @@ void Net::plan_fp8() {
         }
     }
     for (int t : head_t_) tensors_[t].wants16 = true;      // (fp32, read by the loss / result pass)
+    size_t nw6 = 0;      // mxfp6: bytes of code images so far; every image and scale table starts at a multiple of 16 bytes
     for (Op& op : ops_) {
-        if (op.kind == OP_CONV && op.fp8) {
+        if (op.kind == OP_CONV && op.fp8 && mx6_) {
+            const Tensor& in = tensors_[op.in];
+            const Tensor& out = tensors_[op.out];
+            const size_t blocks = (size_t)op.KH * op.KW * out.C * (in.C / 32);
+            op.sw_off = nsw;
+            op.w6_off = nw6;
+            quant_plan_.add(op.w_off, nw6, nsw, op.KH * op.KW, in.C, out.C);
+            nw6 += (blocks * 24 + 15) / 16 * 16;
+            nsw += (blocks + 15) / 16 * 16;
+        } else if (op.kind == OP_CONV && op.fp8) {
             const Tensor& in = tensors_[op.in];
             const Tensor& out = tensors_[op.out];
             op.sw_off = nsw;
@@ -642,12 +656,18 @@ void Net::plan_fp8() {
         if (!(op.kind == OP_POOL && op.fp8) && !mx_) fp8_scaled_.push_back(op.out);      // (mxfp8: no tensor owns a scale)
     }
     SSD_REQUIRE(quant_plan_.n > 0, "no layer of this graph is eligible for fp8");
+    if (mx6_) {      // (+ 8: conv_fwd_mxfp6 reads the scales in whole dwords)
+        w8_ = static_cast<unsigned char*>(hip_.mem(nw6));
+        wsc6_ = static_cast<unsigned char*>(hip_.mem(nsw + 8));
+        return;
+    }
     w8_ = static_cast<unsigned char*>(hip_.mem(nfilters_));
     sw8_ = static_cast<float*>(hip_.mem(nsw * sizeof(float)));
     if (!mx_) absmax8_ = static_cast<float*>(hip_.mem(fp8_scaled_.size() * sizeof(float)));
 }
 
 void Net::require_fp8() const {
+    SSD_REQUIRE(!mx6_, "an mxfp6 handle has no calibration scales (SSD_DTYPE_MXFP6): every producer chooses its block scales itself");
     SSD_REQUIRE(!mx_, "an mxfp8 handle has no calibration scales (SSD_DTYPE_MXFP8): every producer chooses its block scales itself");
     SSD_REQUIRE(fp8_, "not an fp8 handle (SSD_DTYPE_FP8)");
 }
@@ -869,10 +889,11 @@ void Net::init_weights(unsigned long long seed) {
 
 Net::Net(const char* preset, int num_classes, int max_batch, int device, bool training, unsigned long long seed,
          float* ext_params, float* ext_grads, float* ext_momentum, int dtype, int graph)
-    : preset_(&get_preset(preset)), C_(num_classes), Bmax_(max_batch), device_(device), training_(training), bf16_(dtype >= 1 && dtype <= 3),
-      fc_(graph == 1), fp8_(dtype == 2 || dtype == 3), mx_(dtype == 3), hip_(device) {
-    SSD_REQUIRE(dtype >= 0 && dtype <= 3, "dtype must be 0 (fp32), 1 (bf16), 2 (fp8) or 3 (mxfp8), got %d", dtype);
-    SSD_REQUIRE(!(fp8_ && training), "%s is inference only: create the handle with training = 0", mx_ ? "SSD_DTYPE_MXFP8" : "SSD_DTYPE_FP8");
+    : preset_(&get_preset(preset)), C_(num_classes), Bmax_(max_batch), device_(device), training_(training), bf16_(dtype >= 1 && dtype <= 4),
+      fc_(graph == 1), fp8_(dtype >= 2 && dtype <= 4), mx_(dtype == 3 || dtype == 4), mx6_(dtype == 4), hip_(device) {
+    SSD_REQUIRE(dtype >= 0 && dtype <= 4, "dtype must be 0 (fp32), 1 (bf16), 2 (fp8), 3 (mxfp8) or 4 (mxfp6), got %d", dtype);
+    SSD_REQUIRE(!(fp8_ && training), "%s is inference only: create the handle with training = 0",
+                mx6_ ? "SSD_DTYPE_MXFP6" : mx_ ? "SSD_DTYPE_MXFP8" : "SSD_DTYPE_FP8");
     SSD_REQUIRE(graph == 0 || graph == 1, "graph must be 0 (a-trous) or 1 (fc), got %d", graph);
     require_num_classes(num_classes);
     SSD_REQUIRE(max_batch >= 1, "max_batch must be >= 1");
@@ -968,7 +989,10 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
     };
     // the stand-alone quantise pass behind a bf16 producer: samples b0 ... b0 + nb of t's bf16 form (src) into its e4m3 form
     auto quantize8 = [&](const Tensor& t, const void* src, int b0, int nb, hipStream_t s) {
-        if (mx_)
+        if (mx6_)      // (24 code bytes per 32 channels)
+            quantize_mxfp6(src, false, (size_t)nb * t.H * t.W, t.C, t.data8 + (size_t)b0 * (t.per_image() / 32 * 24),
+                           t.scale8 + (size_t)b0 * (t.per_image() / 32), s);
+        else if (mx_)
             quantize_mxfp8(src, false, (size_t)nb * t.H * t.W, t.C, t.data8 + (size_t)b0 * t.per_image(), t.scale8 + (size_t)b0 * (t.per_image() / 32), s);
         else
             quantize_fp8(src, false, (size_t)nb * t.per_image(), t.scale, t.data8 + (size_t)b0 * t.per_image(), s);
@@ -1003,7 +1027,8 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
         prof_.layer = "filters";
         cast_filters(cast_plan_, params_, wq_io_, wq_oi_, side ? hstream_ : stream_);
         // ... and the e4m3 filter images with their per-channel scales, under the same rule (one more launch)
-        if (run8) quantize_filters_fp8(quant_plan_, params_, w8_, sw8_, side ? hstream_ : stream_);
+        if (run8 && mx6_) quantize_filters_mxfp6(quant_plan_, params_, w8_, wsc6_, side ? hstream_ : stream_);
+        else if (run8) quantize_filters_fp8(quant_plan_, params_, w8_, sw8_, side ? hstream_ : stream_);
         if (chain_first_ >= 0) pack_tail_filters(side ? hstream_ : stream_);
         if (side) {
             HIP_OK(hipEventRecord(ev_cast_, hstream_));
@@ -1165,6 +1190,12 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
                     conv_first_fwd_bf16(d, xin, params_ + op.w_off, params_ + op.b_off, static_cast<bf16_t*>(yout), op.relu, cs);
                 else if (in.data_f32)
                     conv_fwd_smallc_bf16out(d, xin, params_ + op.w_off, params_ + op.b_off, static_cast<bf16_t*>(yout), op.relu, cs);
+                else if (run8 && op.fp8 && mx6_)     // e2m3 operands, block scales on both; the output in the form(s) its readers take
+                    conv_fwd_mxfp6(d, in.data8 + (size_t)run_b0 * (in.per_image() / 32 * 24), in.scale8 + (size_t)run_b0 * (in.per_image() / 32),
+                                   w8_ + op.w6_off, wsc6_ + op.sw_off, params_ + op.b_off, yout,
+                                   out.data8 ? out.data8 + (size_t)run_b0 * (out.per_image() / 32 * 24) : nullptr,
+                                   out.data8 ? out.scale8 + (size_t)run_b0 * (out.per_image() / 32) : nullptr,
+                                   out.data8 ? (out.wants16 ? FP8_OUT_BF16_MX : FP8_OUT_MX) : FP8_OUT_BF16, op.relu, cs);
                 else if (run8 && op.fp8 && mx_)      // e4m3 operands with block scales; the output in the form(s) its readers take
                     (conv_bigk(d) ? conv_bigk_fwd_mxfp8 : conv_fwd_mxfp8)(      // (more than 9 taps: the fc graph's mod_conv6 under SSD_MXFP8_BIGK=1)
                         d, in.data8 + (size_t)run_b0 * in.per_image(), in.scale8 + (size_t)run_b0 * (in.per_image() / 32), w8_ + op.w_off,
@@ -1196,7 +1227,10 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
                     else maxpool_fwd_arg(d, reinterpret_cast<const float*>(at(in, ln.b0)), reinterpret_cast<float*>(at(out, ln.b0)), arg, ln.s);
                     pool_arg_op_ = op_index;
                 } else if (run8 && op.fp8) {      // on e4m3 bytes (the output shares the input's scale); bf16 as well where someone reads that
-                    if (mx_)                      // (mxfp8: on the dequantised cells, with block scales of its own)
+                    if (mx6_)
+                        maxpool_fwd_mxfp6(d, in.data8 + (size_t)ln.b0 * (in.per_image() / 32 * 24), in.scale8 + (size_t)ln.b0 * (in.per_image() / 32),
+                                          out.data8 + (size_t)ln.b0 * (out.per_image() / 32 * 24), out.scale8 + (size_t)ln.b0 * (out.per_image() / 32), ln.s);
+                    else if (mx_)                 // (mxfp8: on the dequantised cells, with block scales of its own)
                         maxpool_fwd_mxfp8(d, in.data8 + (size_t)ln.b0 * in.per_image(), in.scale8 + (size_t)ln.b0 * (in.per_image() / 32),
                                           out.data8 + (size_t)ln.b0 * out.per_image(), out.scale8 + (size_t)ln.b0 * (out.per_image() / 32), ln.s);
                     else
@@ -1705,6 +1739,20 @@ void Net::activation(const char* name, int b, float* out, size_t count) {
                     count);
         const void* src = want_grad ? t.grad : t.data;
         HIP_OK(hipStreamSynchronize(stream_));
+        if (t.data8 && !want_grad && !want_bf16 && mx6_) {      // an mxfp6 tensor: its codes (24 bytes per block) times their blocks' 2^x
+            std::vector<unsigned char> hc(count / 32 * 24), hs(count / 32);
+            HIP_OK(hipMemcpy(hc.data(), t.data8, hc.size(), hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(hs.data(), t.scale8, hs.size(), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < count; ++i) {
+                const unsigned char* blk = hc.data() + i / 32 * 24;
+                const int bit = 6 * (int)(i % 32);
+                const int c = ((blk[bit >> 3] | (bit + 6 > ((bit >> 3) + 1) * 8 ? blk[(bit >> 3) + 1] << 8 : 0)) >> (bit & 7)) & 63;
+                const int e = (c >> 3) & 3, m = c & 7;
+                const float v = e == 0 ? m / 8.f : ldexpf(1.f + m / 8.f, e - 1);
+                out[i] = ldexpf(c & 32 ? -v : v, (int)hs[i / 32] - 127);
+            }
+            return;
+        }
         if (t.data8 && !want_grad && !want_bf16) {      // an fp8 tensor: its codes times its scale (exact in fp32)
             std::vector<unsigned char> hc(count), hs;
             HIP_OK(hipMemcpy(hc.data(), t.data8, count, hipMemcpyDeviceToHost));

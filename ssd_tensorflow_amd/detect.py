@@ -24,10 +24,11 @@ def main(argv=None):
     parser.add_argument('--training-data', default='', help='unused: the checkpoint carries the preset and the class names')
     parser.add_argument('--output-dir', default='test-out', help='output directory')
     parser.add_argument('--batch-size', type=int, default=32, help='batch size')
-    parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16', 'fp8', 'mxfp8'],
+    parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16', 'fp8', 'mxfp8', 'mxfp6'],
                         help='f32, bf16 activations on the bf16 matrix cores, fp8: the bf16 net with conv3_2 ... mod_conv7 on e4m3 operands '
                              '(calibrated scales), or mxfp8: the same layers with block scales chosen from the data (no calibration; the fc graph\'s 7x7 fc6 joins '
-                             'them when the environment has SSD_MXFP8_BIGK=1)')
+                             'them when the environment has SSD_MXFP8_BIGK=1), or mxfp6: the mxfp8 layers on 6-bit e2m3 operands with block scales on '
+                             'activations and filters (no calibration; fc6 stays on bf16)')
     add_fp8_arguments(parser)
     parser.add_argument('--decoder', default='gpu', choices=['pillow', 'gpu'],
                         help='gpu: baseline JPEGs are decoded on the GPU, other files as with pillow (same pixels); pillow: every file is decoded on the host')

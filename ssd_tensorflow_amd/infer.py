@@ -110,9 +110,9 @@ def add_fp8_arguments(parser):
 
 
 def check_fp8_arguments(parser, args):
-    """--fp8-calibration with --dtype mxfp8 is an argument error: such a net has nothing to calibrate"""
-    if args.dtype == 'mxfp8' and args.fp8_calibration:
-        parser.error('--fp8-calibration does not apply to --dtype mxfp8: an mxfp8 net has no calibration scales')
+    """--fp8-calibration with --dtype mxfp8 or mxfp6 is an argument error: such a net has nothing to calibrate"""
+    if args.dtype in ('mxfp8', 'mxfp6') and args.fp8_calibration:
+        parser.error('--fp8-calibration does not apply to --dtype %s: an %s net has no calibration scales' % (args.dtype, args.dtype))
 
 
 def fp8_batches(net, batches, calibration_file=None, calibrate_images=32):
@@ -177,10 +177,11 @@ def main(argv=None):
     parser.add_argument('--preset', default=None, help='preset when no checkpoint is given (random weights)')
     parser.add_argument('--num-classes', type=int, default=20, help='class count when no checkpoint is given (1..127)')
     parser.add_argument('--a-trous', type=str2bool, default='True', help='graph when no checkpoint is given: a-trous (true) or fc (false); a checkpoint carries its own')
-    parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16', 'fp8', 'mxfp8'],
+    parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16', 'fp8', 'mxfp8', 'mxfp6'],
                         help='f32, bf16 activations on the bf16 matrix cores, fp8: the bf16 net with conv3_2 ... mod_conv7 on e4m3 operands '
                              '(calibrated scales), or mxfp8: the same layers with block scales chosen from the data (no calibration; the fc graph\'s 7x7 fc6 joins '
-                             'them when the environment has SSD_MXFP8_BIGK=1)')
+                             'them when the environment has SSD_MXFP8_BIGK=1), or mxfp6: the mxfp8 layers on 6-bit e2m3 operands with block scales on '
+                             'activations and filters (no calibration; fc6 stays on bf16)')
     add_fp8_arguments(parser)
     parser.add_argument('--decoder', default='gpu', choices=['pillow', 'gpu'],
                         help='gpu: baseline JPEGs are decoded on the GPU, other files as with pillow (same pixels); pillow: every file is decoded on the host')

@@ -22,6 +22,8 @@ from ._lib import lib, check, np_ptr
 from .ssdutils import get_preset_by_name, SSD_PRESETS, detect_batch
 
 LOSS_NAMES = ('total', 'localization', 'confidence', 'l2')      # ssdvgg.py:594-599
+# compute types of a handle (include/ssdvgg_hip.h SSD_DTYPE_*); 'fp8', 'mxfp8' and 'mxfp6' are inference only
+DTYPES = {'f32': 0, 'bf16': 1, 'fp8': 2, 'mxfp8': 3, 'mxfp6': 4}
 
 
 class _Token:
@@ -175,7 +177,9 @@ class SSDVGG:
         'fp8': the bf16 net with conv3_2 ... mod_conv7 (the fc graph's 7x7 fc6 included) on e4m3 operands; call calibrate_fp8 or set
         fp8_scales before infer; or 'mxfp8': the same layers with one E8M0 block scale per pixel and 32 channels, chosen by each
         producer from its own values -- no calibration, infer works at once and an image's result depends on that image alone
-        (the fc graph's 7x7 fc6 stays on bf16 unless the environment has SSD_MXFP8_BIGK=1 when the net is built).
+        (the fc graph's 7x7 fc6 stays on bf16 unless the environment has SSD_MXFP8_BIGK=1 when the net is built); or 'mxfp6': the
+        mxfp8 net's layers and pools on 6-bit e2m3 operands with E8M0 block scales on activations and filters, again without
+        calibration (the fc graph's 7x7 fc6 stays on bf16).
         a_trous=False builds the reference's other graph (ssdvgg.py:210-228): VGG-16's fc6 / fc7 as a 7x7 and a
         1x1 convolution, 4096 wide, variables fc6/* and fc7/*; its weights come from `<vgg_dir>/vgg16_ssd_fc.npz`."""
         self.num_classes = num_classes + 1
@@ -203,9 +207,9 @@ class SSDVGG:
 
     def _create(self, num_classes, max_batch, training, seed, dtype='f32', a_trous=True):
         import torch
-        if dtype not in ('f32', 'bf16', 'fp8', 'mxfp8'):
-            raise ValueError("dtype must be 'f32', 'bf16' or 'fp8' (with block scales: 'mxfp8'), got %r" % (dtype,))
-        if dtype in ('fp8', 'mxfp8') and training:
+        if dtype not in DTYPES:
+            raise ValueError("dtype must be 'f32', 'bf16' or 'fp8' (with block scales: 'mxfp8', 'mxfp6'), got %r" % (dtype,))
+        if dtype in ('fp8', 'mxfp8', 'mxfp6') and training:
             raise ValueError("dtype %r is inference only: build with training=False" % (dtype,))
         self.dtype = dtype
         dev = self.session.device if self.session is not None else 0
@@ -226,7 +230,7 @@ class SSDVGG:
                                    self.params_flat.data_ptr(),
                                    self.grads_flat.data_ptr() if training else None,
                                    self.momentum_flat.data_ptr() if training else None,
-                                   {'f32': 0, 'bf16': 1, 'fp8': 2, 'mxfp8': 3}[dtype], graph, C.byref(h)))
+                                   DTYPES[dtype], graph, C.byref(h)))
         self._h = h
         fl = C.c_size_t(); ff = C.c_size_t()
         check(lib.ssd_arenas(h, None, None, None, C.byref(fl), C.byref(ff)))

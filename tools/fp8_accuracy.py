@@ -20,6 +20,11 @@ fc6 on the bf16 kernel) and under SSD_FP8_BIGK=1 (fc6 on e4m3), and the allowanc
 operands); the allowance is applied to the last.
 
     python tools/fp8_accuracy.py --a-trous false --mxfp8 --out profiles/mxfp8_fc_accuracy.txt
+
+--mxfp6 (a-trous graph): rows for fp32, bf16, fp8, mxfp8 and mxfp6, the allowance applied to mxfp6, and the distance of
+every handle's result to the fp32 handle's on the fixture of DESIGN.md 18 (synthetic alive weights, two synthetic images).
+
+    python tools/fp8_accuracy.py --mxfp6 --out profiles/mxfp6_accuracy.txt
 """
 import argparse
 import contextlib
@@ -52,8 +57,13 @@ def main():
     ap.add_argument('--calibrate-images', type=int, default=32)
     ap.add_argument('--a-trous', default='true', choices=['true', 'false'], help='false: the fc graph, fp8 under SSD_FP8_BIGK 0 and 1')
     ap.add_argument('--mxfp8', action='store_true', help='further rows: the mxfp8 handle (no calibration); fc graph: under SSD_MXFP8_BIGK 0 and 1')
+    ap.add_argument('--mxfp6', action='store_true', help='a-trous graph: rows for fp8, mxfp8 and mxfp6, and the distance to fp32 on the synthetic fixture')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.mxfp6:
+        if args.a_trous == 'false':
+            ap.error('--mxfp6 evaluates the a-trous graph')
+        args.mxfp8 = True
     fc = args.a_trous == 'false'
     from ssd_tensorflow_amd import train
     from ssd_tensorflow_amd.average_precision import APCalculator, APs2mAP
@@ -101,7 +111,7 @@ def main():
             elif fc:
                 handles += [('fp8/bigk0', 'fp8', F8, '0'), ('fp8/bigk1', 'fp8', F8, '1')]
             else:
-                handles += [('fp8', 'fp8', None, None)] + ([('mxfp8', 'mxfp8', None, None)] if args.mxfp8 else [])
+                handles += [('fp8', 'fp8', None, None)] + ([('mxfp8', 'mxfp8', None, None)] if args.mxfp8 else []) + ([('mxfp6', 'mxfp6', None, None)] if args.mxfp6 else [])
             for name, dt, switch, bigk in handles:
                 saved = os.environ.get(switch) if switch else None
                 if switch:
@@ -139,6 +149,24 @@ def main():
         say('# one missed object per class changes mAP by %.4f; bf16 - %s = %+.4f: %s' % (allow, last, diff, 'within it' if diff <= allow else 'BELOW it'))
         if args.mxfp8:
             say('# bf16 - fp8 = %+.4f' % (results['bf16'][0] - results['fp8'][0]))
+        if args.mxfp6:
+            say('# bf16 - mxfp8 = %+.4f' % (results['bf16'][0] - results['mxfp8'][0]))
+            # the fixture of DESIGN.md 18: weights init_params(seed 42, alive), images synth_images(default_rng(99), 2)
+            from oracle import boxes as ob, ssdvgg_ref as ref
+            preset = ob.get_preset('vgg300')
+            w = ref.init_params(preset, 20, seed=42, alive=True)
+            x = ref.synth_images(np.random.default_rng(99), 2, preset)
+            res = {}
+            with Session(0) as sess:
+                for dt in ('f32', 'bf16', 'fp8', 'mxfp8', 'mxfp6'):
+                    net = SSDVGG(sess, 'vgg300')
+                    net.build_from_vgg(None, 20, max_batch=2, training=False, weights=w, dtype=dt)
+                    if dt == 'fp8':
+                        net.calibrate_fp8(x)
+                    res[dt] = net.infer(x).astype(np.float64)
+            dist = lambda a: float(np.linalg.norm(a - res['f32']) / np.linalg.norm(res['f32']))
+            say('# synthetic fixture (alive weights seed 42, 2 images): |result - result fp32| / |result fp32|: '
+                + ', '.join('%s %.4e' % (dt, dist(res[dt])) for dt in ('bf16', 'fp8', 'mxfp8', 'mxfp6')))
         say('# fp8 activation scales calibrated on the first %d training images' % args.calibrate_images + ('; mxfp8: nothing to calibrate' if args.mxfp8 else ''))
     if args.out:
         with open(args.out, 'w') as f:

@@ -25,6 +25,12 @@ same weights -- bf16, fp8 (SSD_FP8_BIGK=1, calibrated), mxfp8 under SSD_MXFP8_BI
 behind it) and, the handle under test, mxfp8 under SSD_MXFP8_BIGK=1.
 
     python tools/infer_rate.py --a-trous false --mxfp8 --out profiles/mxfp8_fc_infer_rate.txt
+
+--mxfp6 (a-trous graph) measures four handles from the same weights -- bf16, fp8, mxfp8 and, the handle under test, mxfp6 (DESIGN.md
+24): the ratios and verdicts are mxfp6 against each of the others, and the convolution kernels of conv4_2 and mod_conv6 are listed
+with their TF/s for every handle.
+
+    python tools/infer_rate.py --mxfp6 --out profiles/mxfp6_infer_rate.txt
 """
 import argparse
 import ctypes as C
@@ -83,8 +89,13 @@ def main():
     ap.add_argument('--a-trous', default='true', choices=['true', 'false'], help="false: the fc graph, three handles (SSD_FP8_BIGK 0 / 1)"
                     "; with --mxfp8 four (SSD_MXFP8_BIGK 0 / 1)")
     ap.add_argument('--mxfp8', action='store_true', help='a further handle, mxfp8, as the handle under test (fc graph: under SSD_MXFP8_BIGK=1)')
+    ap.add_argument('--mxfp6', action='store_true', help='a-trous graph: bf16, fp8, mxfp8 and mxfp6 handles, mxfp6 as the handle under test')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.mxfp6:
+        if args.a_trous == 'false':
+            ap.error('--mxfp6 measures the a-trous graph: the fc graph has no mxfp6 kernel for its 7x7 fc6')
+        args.mxfp8 = True
     import torch
     from oracle import boxes as ob, ssdvgg_ref as ref
     from ssd_tensorflow_amd._lib import lib, check
@@ -109,7 +120,7 @@ def main():
             handles = [('bf16', 'bf16', None, None), ('fp8/bigk0', 'fp8', 'SSD_FP8_BIGK', '0'), ('fp8/bigk1', 'fp8', 'SSD_FP8_BIGK', '1')]
     else:
         w = ref.init_params(preset, 20, seed=42, alive=True)
-        handles = [('bf16', 'bf16', None, None), ('fp8', 'fp8', None, None)] + ([('mxfp8', 'mxfp8', None, None)] if args.mxfp8 else [])
+        handles = [('bf16', 'bf16', None, None), ('fp8', 'fp8', None, None)] + ([('mxfp8', 'mxfp8', None, None)] if args.mxfp8 else []) + ([('mxfp6', 'mxfp6', None, None)] if args.mxfp6 else [])
     x = torch.from_numpy(ref.synth_images(np.random.default_rng(5), args.batch, preset)).cuda()
     with Session(0) as sess:
         nets = {}
@@ -173,9 +184,9 @@ def main():
             for dt in nets:
                 tot[dt] += statistics.median(cols[dt])
             a, f = cols['bf16'], cols[last]
-            tag = 'mxfp8' if args.mxfp8 else 'fp8'
+            tag = 'mxfp6' if args.mxfp6 else 'mxfp8' if args.mxfp8 else 'fp8'
             verdict = tag + ' faster' if max(f) < min(a) else (tag + ' SLOWER' if max(a) < min(f) else 'not separated')
-            for other in (['fp8'] + (['mxfp8/bigk0'] if fc else []) if args.mxfp8 else []):      # ... and against these handles' rows
+            for other in (['fp8'] + (['mxfp8/bigk0'] if fc else []) + (['mxfp8'] if args.mxfp6 else []) if args.mxfp8 else []):      # ... and against these handles' rows
                 g = cols[other]
                 verdict += '; against %s %.3f %s' % (other, statistics.median(g) / max(statistics.median(f), 1e-9),
                                                      'faster' if max(f) < min(g) else ('SLOWER' if max(g) < min(f) else 'not separated'))
@@ -187,6 +198,18 @@ def main():
                     tot[dt] += statistics.median(f)
                     say('  %-18s only in %s: %s' % (k, dt, mmm(f)) if fc or args.mxfp8 else '  %-18s %28s %s' % (k, '-', mmm(f)))
         say('# sum of the kernels per batch, one stream: ' + ', '.join('%s %.3f ms' % (dt, tot[dt]) for dt in nets))
+        if args.mxfp6:
+            # ---- the convolution kernels of conv4_2 and mod_conv6, with their rates from the executed FLOPs 2 * pixels * Ci * Co * 9
+            f38, f19 = preset['maps'][0][0], preset['maps'][1][0]
+            flops = {'conv4_2': 2.0 * args.batch * f38 * f38 * 512 * 512 * 9, 'mod_conv6': 2.0 * args.batch * f19 * f19 * 512 * 1024 * 9}
+            say('# convolution kernels of conv4_2 (%.1f GFLOP) and mod_conv6 (%.1f GFLOP), ms per batch and TF/s'
+                % (flops['conv4_2'] / 1e9, flops['mod_conv6'] / 1e9))
+            for dt in nets:
+                for label in lab[dt][0]:
+                    kern, _, layer = label.partition(':')
+                    if layer in flops and kern.startswith('conv'):
+                        v = [p.get(label, 0.0) for p in lab[dt]]
+                        say('  %-6s %-40s %s  %.0f TF/s' % (dt, label, mmm(v), flops[layer] / (statistics.median(v) * 1e-3) / 1e12))
         if fc:
             # ---- the kernels around fc6 one by one; fc6's rate from its executed FLOPs 2 * pixels * Ci * Co * taps
             fmap = preset['maps'][1][0]
