@@ -57,6 +57,15 @@ SIGNATURES = {
     'ssd_decode_nms_dev': (i32, [cstr, i32, vp, vp, i32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     'ssd_anchors_dev': (i32, [cstr, vp, vp, vp]),
     'ssd_average_precision': (i32, [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, C.c_double, vp, vp]),
+    'ssd_average_precision_ex': (i32, [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    'ssd_ap_create': (i32, [i32, i32, C.POINTER(vp)]),
+    'ssd_ap_destroy': (i32, [vp]),
+    'ssd_ap_clear': (i32, [vp]),
+    'ssd_ap_add_dev': (i32, [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+    'ssd_ap_add_host': (i32, [vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+    'ssd_ap_count': (i32, [vp, p_i64, p_i64]),
+    'ssd_ap_fetch': (i32, [vp, C.c_longlong, vp, vp, vp, vp, p_i64]),
+    'ssd_ap_compute': (i32, [vp, i32, i32, vp, vp, vp, p_i64, p_i64]),
     'ssd_arena_floats': (sz, [cstr, i32]),
     'ssd_augment_ws_bytes': (sz, [i32, i32, i32]),
     'ssd_augment_batch_dev': (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),

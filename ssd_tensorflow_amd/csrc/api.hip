@@ -411,18 +411,16 @@ int ssd_merge_tiles(int device, const ssd_tile* tiles, int n_tiles, int n_images
     API_END
 }
 
-int ssd_average_precision(int device, int n_det, const float* det_box, const float* det_conf, const int* det_cls,
-                          const int* det_sample, int n_gt, const double* gt_box, const int* gt_cls, const int* gt_sample,
-                          int num_classes, double minoverlap, double* ap_out, int* present_out) {
+int ssd_average_precision_ex(int device, int n_det, const float* det_box, const float* det_conf, const int* det_cls,
+                             const int* det_sample, int n_gt, const double* gt_box, const int* gt_cls, const int* gt_sample,
+                             const unsigned char* gt_flags, int num_classes, int protocol, int n_thr, const double* minoverlaps,
+                             double* ap_out, int* present_out) {
     API_BEGIN
     SSD_REQUIRE(num_classes >= 1 && n_det >= 0 && n_gt >= 0, "bad sizes");
     for (int g = 1; g < n_gt; ++g) SSD_REQUIRE(gt_sample[g] >= gt_sample[g - 1], "ground truth must be grouped by ascending sample id");
     DeviceGuard dev_guard_(device);
-    int n2 = 1;
-    while (n2 < n_det) n2 <<= 1;
     const size_t nd = n_det ? n_det : 1, ng = n_gt ? n_gt : 1;
-    DevBuf dbox(nd * 16), dconf(nd * 4), dcls(nd * 4), dsmp(nd * 4), gbox(ng * 32), gcls(ng * 4), gsmp(ng * 4);
-    DevBuf keys((size_t)num_classes * n2 * 8), matched(ng), ap((size_t)num_classes * 8), present((size_t)num_classes * 4);
+    DevBuf dbox(nd * 16), dconf(nd * 4), dcls(nd * 4), dsmp(nd * 4), gbox(ng * 32), gcls(ng * 4), gsmp(ng * 4), gflg(ng);
     if (n_det) {
         HIP_OK(hipMemcpy(dbox.p, det_box, nd * 16, hipMemcpyHostToDevice));
         HIP_OK(hipMemcpy(dconf.p, det_conf, nd * 4, hipMemcpyHostToDevice));
@@ -434,11 +432,80 @@ int ssd_average_precision(int device, int n_det, const float* det_box, const flo
         HIP_OK(hipMemcpy(gcls.p, gt_cls, ng * 4, hipMemcpyHostToDevice));
         HIP_OK(hipMemcpy(gsmp.p, gt_sample, ng * 4, hipMemcpyHostToDevice));
     }
-    average_precision_device(n_det, n_gt, num_classes, dbox.as<float>(), dconf.as<float>(), dcls.as<int>(), dsmp.as<int>(),
-                             gbox.as<double>(), gcls.as<int>(), gsmp.as<int>(), minoverlap, keys.as<unsigned long long>(), n2,
-                             matched.as<unsigned char>(), ap.as<double>(), present.as<int>(), nullptr);
-    HIP_OK(hipMemcpy(ap_out, ap.p, (size_t)num_classes * 8, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(present_out, present.p, (size_t)num_classes * 4, hipMemcpyDeviceToHost));
+    if (n_gt && gt_flags) HIP_OK(hipMemcpy(gflg.p, gt_flags, ng, hipMemcpyHostToDevice));
+    else HIP_OK(hipMemset(gflg.p, 0, ng));
+    APInput in{n_det, n_gt, num_classes, dbox.as<float>(), dconf.as<float>(), dcls.as<int>(), dsmp.as<int>(), gbox.as<double>(),
+               gcls.as<int>(), gsmp.as<int>(), gflg.as<unsigned char>()};
+    average_precision_run(in, protocol, n_thr, minoverlaps, ap_out, present_out, nullptr);
+    API_END
+}
+
+int ssd_average_precision(int device, int n_det, const float* det_box, const float* det_conf, const int* det_cls,
+                          const int* det_sample, int n_gt, const double* gt_box, const int* gt_cls, const int* gt_sample,
+                          int num_classes, double minoverlap, double* ap_out, int* present_out) {
+    return ssd_average_precision_ex(device, n_det, det_box, det_conf, det_cls, det_sample, n_gt, gt_box, gt_cls, gt_sample, nullptr,
+                                    num_classes, AP_REFERENCE, 1, &minoverlap, ap_out, present_out);
+}
+
+static_assert(SSD_AP_REFERENCE == AP_REFERENCE && SSD_AP_VOC07 == AP_VOC07 && SSD_AP_VOC12 == AP_VOC12, "protocol ids");
+
+static APAccumulator& ACC(ssd_ap_accumulator a) {
+    if (!a) fail("null accumulator");
+    return *reinterpret_cast<APAccumulator*>(a);
+}
+
+int ssd_ap_create(int device, int num_classes, ssd_ap_accumulator* acc) {
+    API_BEGIN
+    SSD_REQUIRE(acc, "ssd_ap_create: null argument");
+    *acc = reinterpret_cast<ssd_ap_accumulator>(new APAccumulator(device, num_classes));
+    API_END
+}
+
+int ssd_ap_destroy(ssd_ap_accumulator acc) {
+    API_BEGIN
+    delete reinterpret_cast<APAccumulator*>(acc);
+    API_END
+}
+
+int ssd_ap_clear(ssd_ap_accumulator acc) {
+    API_BEGIN
+    ACC(acc).clear();
+    API_END
+}
+
+int ssd_ap_add_dev(ssd_ap_accumulator acc, int b, int out_cap, const int* count_dev, const float* conf_dev, const int* cls_dev,
+                   const int* box_dev, int n_gt, const double* gt_box, const int* gt_cls, const int* gt_image,
+                   const unsigned char* gt_flags, void* stream) {
+    API_BEGIN
+    ACC(acc).add_dev(b, out_cap, count_dev, conf_dev, cls_dev, box_dev, n_gt, gt_box, gt_cls, gt_image, gt_flags, (hipStream_t)stream);
+    API_END
+}
+
+int ssd_ap_add_host(ssd_ap_accumulator acc, int n_det, const float* det_box, const float* det_conf, const int* det_cls,
+                    const int* det_sample, int n_samples, int n_gt, const double* gt_box, const int* gt_cls, const int* gt_sample,
+                    const unsigned char* gt_flags) {
+    API_BEGIN
+    ACC(acc).add_host(n_det, det_box, det_conf, det_cls, det_sample, n_samples, n_gt, gt_box, gt_cls, gt_sample, gt_flags);
+    API_END
+}
+
+int ssd_ap_count(ssd_ap_accumulator acc, long long* n_det, long long* n_dropped) {
+    API_BEGIN
+    ACC(acc).counts(n_det, n_dropped);
+    API_END
+}
+
+int ssd_ap_fetch(ssd_ap_accumulator acc, long long cap, float* det_box, float* det_conf, int* det_cls, int* det_sample,
+                 long long* n_det) {
+    API_BEGIN
+    ACC(acc).fetch(cap, det_box, det_conf, det_cls, det_sample, n_det);
+    API_END
+}
+
+int ssd_ap_compute(ssd_ap_accumulator acc, int protocol, int n_thr, const double* minoverlaps, double* ap_out, int* present_out,
+                   long long* n_det, long long* n_dropped) {
+    API_BEGIN
+    ACC(acc).compute(protocol, n_thr, minoverlaps, ap_out, present_out, n_det, n_dropped);
     API_END
 }
 

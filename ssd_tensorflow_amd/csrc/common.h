@@ -77,6 +77,14 @@ struct DevBuf {
     DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            if (p) (void)hipFree(p);
+            p = o.p;
+            o.p = nullptr;
+        }
+        return *this;
+    }
     ~DevBuf() { if (p) (void)hipFree(p); }
     template <typename T> T* as() { return (T*)p; }
 };
@@ -121,7 +129,11 @@ public:
         HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         return s;
     }
-    // give back early what pinned() / stream() handed out; anything else (a caller's stream) is left alone
+    // give back early what mem() / pinned() / stream() handed out; anything else (a caller's stream) is left alone
+    void free_mem(void* p) {      // (hipFree waits for the device)
+        auto it = std::find_if(mem_.begin(), mem_.end(), [p](const DevBuf& b) { return b.p == p; });
+        if (it != mem_.end()) mem_.erase(it);
+    }
     void free_pinned(void* h) {
         if (take(pinned_, h)) HIP_OK(hipHostFree(h));
     }

@@ -1,10 +1,64 @@
-// VOC07 11-point average precision on the GPU (metrics.hip).
+// Average precision on the GPU (metrics.hip): the reference's protocol, VOC07 with difficult objects, VOC12 all-point AP,
+// and the device-side accumulator that collects a run's detections behind each detection pass.
 #pragma once
 #include "common.h"
 
 namespace ssd {
-void average_precision_device(int n_det, int n_gt, int ncls, const float* det_box, const float* det_conf, const int* det_cls,
-                              const int* det_sample, const double* gt_box, const int* gt_cls, const int* gt_sample,
-                              double minoverlap, unsigned long long* keys, int n2, unsigned char* matched, double* ap,
-                              int* present, hipStream_t s);
-}
+
+constexpr int AP_MAX_THRESHOLDS = 10;
+enum { AP_REFERENCE = 0, AP_VOC07 = 1, AP_VOC12 = 2 };
+
+// Device-visible inputs of one AP computation.  Ground truth rows are grouped by ascending sample id.
+struct APInput {
+    int n_det, n_gt, ncls;
+    const float* det_box;      // [n_det][4] xmin,xmax,ymin,ymax (the reference casts them to float32)
+    const float* det_conf;
+    const int* det_cls;
+    const int* det_sample;
+    const double* gt_box;      // [n_gt][4]
+    const int* gt_cls;
+    const int* gt_sample;
+    const unsigned char* gt_flags;      // [n_gt]: 1 = difficult
+};
+
+// Runs the count / sort / walk kernels on `s`, waits for it and copies ap [n_thr][ncls] and present [ncls] to the host.
+void average_precision_run(const APInput& in, int protocol, int n_thr, const double* minoverlaps, double* ap_out, int* present_out,
+                           hipStream_t s);
+
+// A run's detections in HBM.  Everything it takes from HIP is owned by `hip` and freed with it.
+class APAccumulator {
+public:
+    APAccumulator(int device, int num_classes);
+    int device() const { return device_; }
+    int num_classes() const { return ncls_; }
+    void clear();
+    void add_dev(int b, int out_cap, const int* count_dev, const float* conf_dev, const int* cls_dev, const int* box_dev, int n_gt,
+                 const double* gt_box, const int* gt_cls, const int* gt_image, const unsigned char* gt_flags, hipStream_t s);
+    void add_host(int n_det, const float* det_box, const float* det_conf, const int* det_cls, const int* det_sample, int n_samples,
+                  int n_gt, const double* gt_box, const int* gt_cls, const int* gt_sample, const unsigned char* gt_flags);
+    void counts(long long* n_det, long long* n_dropped);      // waits for the appends
+    void fetch(long long cap, float* det_box, float* det_conf, int* det_cls, int* det_sample, long long* n_det);
+    void compute(int protocol, int n_thr, const double* minoverlaps, double* ap_out, int* present_out, long long* n_det,
+                 long long* n_dropped);
+    long long samples() const { return samples_; }
+
+private:
+    struct Store { float* box = nullptr; float* conf = nullptr; int* cls = nullptr; int* sample = nullptr; };
+    void reserve(long long extra, hipStream_t s);
+    void sync();
+    void release_retired();
+    void push_gt(int n_gt, const double* gt_box, const int* gt_cls, const int* gt_sample, const unsigned char* gt_flags, int n_samples,
+                 const char* what);
+    HipOwner hip_;
+    int device_, ncls_;
+    Store st_;
+    long long cap_ = 0, bound_ = 0, samples_ = 0;      // bound_: the host's upper bound of the device-side end
+    int* words_ = nullptr;                             // device: [0] end, [1] dropped detections
+    std::vector<void*> retired_;                       // outgrown buffers, freed at the next wait
+    hipStream_t last_ = nullptr;
+    std::vector<double> gt_box_;
+    std::vector<int> gt_cls_, gt_sample_;
+    std::vector<unsigned char> gt_flags_;
+};
+
+}  // namespace ssd

@@ -1,30 +1,65 @@
-// VOC07 11-point average precision per class (average_precision.py:84-176) on gfx950.
-// One workgroup per class: compact the class's detections, sort them by confidence (bitonic, L2
-// resident), then ONE lane walks them in order -- the greedy matching of a detection against the
-// still-unmatched ground truth of its image is inherently sequential -- keeping the running maximum
-// precision for each of the 11 recall thresholds.  All arithmetic in IEEE f64: bit-exact with numpy.
+// Average precision per class on gfx950: the reference's VOC07 11-point form (average_precision.py:84-176), the devkit's VOC07
+// with difficult objects, and the VOC2010+ all-point area; and the accumulator that keeps a run's detections in HBM.
+// Three kernels per computation:
+//   count  one workgroup per class: its detections, its ground truth, its unflagged ground truth (npos).  The host turns the
+//          counts into offsets: the sort keys of class k take pow2(n_k) slots, not pow2(n_det).
+//   sort   one workgroup per class: compact the class's detections into keys, bitonic sort by confidence (L2 resident).
+//   walk   one wave per (class, IoU threshold): ONE lane walks the sorted detections -- the greedy matching of a detection
+//          against the still-unmatched ground truth of its image is inherently sequential -- with matched bytes of its own, so
+//          the walks of a threshold list run side by side.
+// All arithmetic in IEEE f64 with explicit round-to-nearest operations: bit-exact with numpy.
 #include "metrics.h"
+#include "boxmath.h"
 #include <climits>
+#include <numeric>
 
 namespace ssd {
 
 typedef unsigned long long u64;
 
 struct APArgs {
-    int n_det, n_gt, ncls, n2;
-    const float* det_box;      // [n_det][4] xmin,xmax,ymin,ymax (the reference casts them to float32)
-    const float* det_conf;
-    const int* det_cls;
-    const int* det_sample;
-    const double* gt_box;      // [n_gt][4], rows grouped by sample id (ascending)
-    const int* gt_cls;
-    const int* gt_sample;
-    double minoverlap;
-    u64* keys;                 // [ncls][n2]
-    unsigned char* matched;    // [n_gt], zeroed
-    double* ap;                // [ncls]
-    int* present;              // [ncls]: 1 if the class has ground truth
+    APInput in;
+    int protocol, n_thr;
+    double minoverlap[AP_MAX_THRESHOLDS];
+    int* counts;               // [3][ncls]: detections, ground truth, unflagged ground truth
+    const long long* koff;     // [ncls] first key of the class
+    const long long* toff;     // [ncls] first true-positive slot of the class (VOC12)
+    long long tp_stride;       // true-positive slots per threshold
+    u64* keys;
+    unsigned char* matched;    // [n_thr][n_gt], zeroed
+    double* tp_prec;           // [n_thr][tp_stride] (VOC12)
+    double* ap;                // [n_thr][ncls]
+    int* present;              // [ncls]: 1 if the class is part of the mAP
 };
+
+__device__ static int block_sum(int c, int* s_w) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    __syncthreads();
+    if (lane == 0) s_w[wv] = c;
+    __syncthreads();
+    return s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+__global__ __launch_bounds__(256) void ap_count_kernel(APArgs p) {
+    __shared__ int s_w[4];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    int nd = 0, ng = 0, np = 0;
+    for (int d = tid; d < p.in.n_det; d += 256) nd += p.in.det_cls[d] == k;
+    for (int g = tid; g < p.in.n_gt; g += 256) {
+        const bool mine = p.in.gt_cls[g] == k;
+        ng += mine;
+        np += mine && !p.in.gt_flags[g];
+    }
+    nd = block_sum(nd, s_w);
+    ng = block_sum(ng, s_w);
+    np = block_sum(np, s_w);
+    if (tid == 0) {
+        p.counts[k] = nd;
+        p.counts[p.in.ncls + k] = ng;
+        p.counts[2 * p.in.ncls + k] = np;
+    }
+}
 
 __device__ static void bitonic_desc_u64(u64* keys, int n2) {
     for (int k = 2; k <= n2; k <<= 1)
@@ -41,34 +76,26 @@ __device__ static void bitonic_desc_u64(u64* keys, int n2) {
         }
 }
 
-__global__ __launch_bounds__(256) void ap_class_kernel(APArgs p) {
-    __shared__ int s_w[4], s_cnt;
+// the class's denominator: every ground-truth box for the reference's protocol, the unflagged ones for the devkit's
+__device__ static int ap_denominator(const APArgs& p, int k) { return p.counts[(p.protocol == AP_REFERENCE ? 1 : 2) * p.in.ncls + k]; }
+
+__global__ __launch_bounds__(256) void ap_sort_kernel(APArgs p) {
+    __shared__ int s_w[4];
     const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    u64* keys = p.keys + (size_t)k * p.n2;
-    // ---- ground-truth count of this class -----------------------------------------------------
-    int c = 0;
-    for (int g = tid; g < p.n_gt; g += 256) c += p.gt_cls[g] == k;
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if (lane == 0) s_w[wv] = c;
-    __syncthreads();
-    const int count = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    __syncthreads();
-    if (count == 0) {
-        if (tid == 0) { p.present[k] = 0; p.ap[k] = 0.0; }
-        return;
-    }
+    if (ap_denominator(p, k) == 0) return;
+    u64* keys = p.keys + p.koff[k];
     // ---- this class's detections: key = order-preserving confidence bits << 32 | ~index --------
     int n = 0;
-    for (int d0 = 0; d0 < p.n_det; d0 += 256) {
+    for (int d0 = 0; d0 < p.in.n_det; d0 += 256) {
         const int d = d0 + tid;
-        const bool mine = d < p.n_det && p.det_cls[d] == k;
+        const bool mine = d < p.in.n_det && p.in.det_cls[d] == k;
         const u64 bal = __ballot(mine);
         if (lane == 0) s_w[wv] = __popcll(bal);
         __syncthreads();
         int base = n, tot = 0;
         for (int i = 0; i < 4; ++i) { if (i < wv) base += s_w[i]; tot += s_w[i]; }
         if (mine) {
-            unsigned u = __float_as_uint(p.det_conf[d]);
+            unsigned u = __float_as_uint(p.in.det_conf[d]);
             u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
             keys[base + __popcll(bal & ((1ull << lane) - 1ull))] = ((u64)u << 32) | (u64)(0xFFFFFFFFu - (unsigned)d);
         }
@@ -80,23 +107,39 @@ __global__ __launch_bounds__(256) void ap_class_kernel(APArgs p) {
     for (int i = n + tid; i < n2; i += 256) keys[i] = 0ull;
     __syncthreads();
     bitonic_desc_u64(keys, n2);
-    if (tid != 0) return;
-    // ---- greedy matching in confidence order (average_precision.py:130-161) -----------------------
+}
+
+__global__ __launch_bounds__(64) void ap_walk_kernel(APArgs p) {
+    if (threadIdx.x != 0) return;
+    const int k = blockIdx.x, t = blockIdx.y, ncls = p.in.ncls, n_gt = p.in.n_gt;
+    const int count = ap_denominator(p, k);
+    if (t == 0) p.present[k] = count > 0;
+    if (count == 0) { p.ap[t * ncls + k] = 0.0; return; }
+    const int n = p.counts[k];
+    const u64* keys = p.keys + p.koff[k];
+    const bool devkit = p.protocol != AP_REFERENCE, area = p.protocol == AP_VOC12;
+    const double minoverlap = p.minoverlap[t];
+    unsigned char* matched = p.matched + (size_t)t * (n_gt > 0 ? n_gt : 1);
+    double* tp_prec = area ? p.tp_prec + (size_t)t * p.tp_stride + p.toff[k] : nullptr;
+    const float* det_box = p.in.det_box;
+    const double* gt_box = p.in.gt_box;
+    // ---- greedy matching in confidence order (average_precision.py:130-161; VOCevaldet.m with difficult objects) ----------
     double tp = 0.0, fp = 0.0, best[11];
     bool any[11];
+    int ntp = 0;
     for (int j = 0; j < 11; ++j) { best[j] = 0.0; any[j] = false; }
     for (int i = 0; i < n; ++i) {
         const int d = (int)(0xFFFFFFFFu - (unsigned)(keys[i] & 0xFFFFFFFFull));
-        const int s = p.det_sample[d];
-        int lo = 0, hi = p.n_gt;                       // first ground-truth row of sample s
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if (p.gt_sample[mid] < s) lo = mid + 1; else hi = mid; }
-        const double b0 = p.det_box[d * 4], b1 = p.det_box[d * 4 + 1], b2 = p.det_box[d * 4 + 2], b3 = p.det_box[d * 4 + 3];
+        const int s = p.in.det_sample[d];
+        int lo = 0, hi = n_gt;                       // first ground-truth row of sample s
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (p.in.gt_sample[mid] < s) lo = mid + 1; else hi = mid; }
+        const double b0 = det_box[(size_t)d * 4], b1 = det_box[(size_t)d * 4 + 1], b2 = det_box[(size_t)d * 4 + 2], b3 = det_box[(size_t)d * 4 + 3];
         const double areab = __dmul_rn(__dadd_rn(__dsub_rn(b1, b0), 1.0), __dadd_rn(__dsub_rn(b3, b2), 1.0));
         int arg = -1;
         double iou_max = 0.0;
-        for (int g = lo; g < p.n_gt && p.gt_sample[g] == s; ++g) {
-            if (p.gt_cls[g] != k) continue;
-            const double a0 = p.gt_box[g * 4], a1 = p.gt_box[g * 4 + 1], a2 = p.gt_box[g * 4 + 2], a3 = p.gt_box[g * 4 + 3];
+        for (int g = lo; g < n_gt && p.in.gt_sample[g] == s; ++g) {
+            if (p.in.gt_cls[g] != k) continue;
+            const double a0 = gt_box[(size_t)g * 4], a1 = gt_box[(size_t)g * 4 + 1], a2 = gt_box[(size_t)g * 4 + 2], a3 = gt_box[(size_t)g * 4 + 3];
             const double areaa = __dmul_rn(__dadd_rn(__dsub_rn(a1, a0), 1.0), __dadd_rn(__dsub_rn(a3, a2), 1.0));
             const double w = fmax(0.0, __dadd_rn(__dsub_rn(fmin(b1, a1), fmax(b0, a0)), 1.0));
             const double h = fmax(0.0, __dadd_rn(__dsub_rn(fmin(b3, a3), fmax(b2, a2)), 1.0));
@@ -104,10 +147,20 @@ __global__ __launch_bounds__(256) void ap_class_kernel(APArgs p) {
             const double iou = __ddiv_rn(inter, __dsub_rn(__dadd_rn(areab, areaa), inter));
             if (arg < 0 || iou > iou_max) { iou_max = iou; arg = g; }    // np.argmax: first maximum
         }
-        if (arg < 0 || iou_max < p.minoverlap || p.matched[arg]) fp += 1.0;
-        else { tp += 1.0; p.matched[arg] = 1; }
+        bool hit = false;
+        if (arg < 0 || iou_max < minoverlap) fp += 1.0;
+        else if (devkit && p.in.gt_flags[arg]) continue;                 // a difficult object: the detection counts neither way
+        else if (matched[arg]) fp += 1.0;
+        else { tp += 1.0; matched[arg] = 1; hit = true; }
         const double recall = __ddiv_rn(tp, (double)count);
         const double prec = __ddiv_rn(tp, __dadd_rn(tp, fp));
+        if (area) {
+            // Only true positives are kept: recall moves only there, and a false positive's precision never exceeds that of
+            // the counted point before it (same tp, larger tp + fp; a correctly rounded quotient is monotonic), so the
+            // devkit's maximum over all later points is the maximum over the later true positives.
+            if (hit) tp_prec[ntp++] = prec;
+            continue;
+        }
         for (int j = 0; j < 11; ++j)
             if (recall >= __dmul_rn((double)j, 0.1)) {                     // np.arange(0, 1.1, 0.1)[j]
                 if (!any[j] || prec > best[j]) best[j] = prec;
@@ -115,20 +168,288 @@ __global__ __launch_bounds__(256) void ap_class_kernel(APArgs p) {
             }
     }
     double ap = 0.0;
-    for (int j = 0; j < 11; ++j)
-        if (any[j]) ap = __dadd_rn(ap, best[j]);
-    p.ap[k] = __ddiv_rn(ap, 11.0);
-    p.present[k] = 1;
+    if (area) {
+        // VOCevaldet.m / voc_eval: mrec = [0, recall, 1], mpre = [0, precision, 0], mpre made non-increasing from the back, then the
+        // sum over ascending i with mrec[i+1] != mrec[i] of (mrec[i+1] - mrec[i]) * mpre[i+1].  The closing term is (1 - r) * 0.
+        double m = 0.0;
+        for (int i = ntp - 1; i >= 0; --i) {
+            if (tp_prec[i] > m) m = tp_prec[i];
+            tp_prec[i] = m;
+        }
+        double prev = 0.0;
+        for (int i = 0; i < ntp; ++i) {
+            const double rec = __ddiv_rn((double)(i + 1), (double)count);
+            ap = __dadd_rn(ap, __dmul_rn(__dsub_rn(rec, prev), tp_prec[i]));
+            prev = rec;
+        }
+    } else {
+        for (int j = 0; j < 11; ++j)
+            if (any[j]) ap = __dadd_rn(ap, best[j]);
+        ap = __ddiv_rn(ap, 11.0);
+    }
+    p.ap[t * ncls + k] = ap;
 }
 
-void average_precision_device(int n_det, int n_gt, int ncls, const float* det_box, const float* det_conf, const int* det_cls,
-                              const int* det_sample, const double* gt_box, const int* gt_cls, const int* gt_sample,
-                              double minoverlap, u64* keys, int n2, unsigned char* matched, double* ap, int* present,
-                              hipStream_t s) {
-    APArgs a{n_det, n_gt, ncls, n2, det_box, det_conf, det_cls, det_sample, gt_box, gt_cls, gt_sample, minoverlap, keys, matched, ap, present};
-    HIP_OK(hipMemsetAsync(matched, 0, n_gt > 0 ? n_gt : 1, s));
-    hipLaunchKernelGGL(ap_class_kernel, dim3(ncls), dim3(256), 0, s, a);
+static long long pow2_at_least(long long n) {
+    long long n2 = 1;
+    while (n2 < n) n2 <<= 1;
+    return n2;
+}
+
+void average_precision_run(const APInput& in, int protocol, int n_thr, const double* minoverlaps, double* ap_out, int* present_out,
+                           hipStream_t s) {
+    require_num_classes(in.ncls);
+    SSD_REQUIRE(protocol >= AP_REFERENCE && protocol <= AP_VOC12, "AP protocol must be 0 (reference), 1 (voc07) or 2 (voc12), got %d", protocol);
+    SSD_REQUIRE(n_thr >= 1 && n_thr <= AP_MAX_THRESHOLDS && minoverlaps, "1..%d IoU thresholds (got %d)", AP_MAX_THRESHOLDS, n_thr);
+    SSD_REQUIRE(in.n_det >= 0 && in.n_gt >= 0 && ap_out && present_out, "bad sizes");
+    const int ncls = in.ncls;
+    APArgs a{};
+    a.in = in;
+    a.protocol = protocol;
+    a.n_thr = n_thr;
+    for (int t = 0; t < n_thr; ++t) a.minoverlap[t] = minoverlaps[t];
+    const size_t ng = in.n_gt ? in.n_gt : 1;
+    DevBuf counts((size_t)ncls * 12), offs((size_t)ncls * 16), matched(ng * n_thr), ap((size_t)n_thr * ncls * 8), present((size_t)ncls * 4);
+    a.counts = counts.as<int>();
+    hipLaunchKernelGGL(ap_count_kernel, dim3(ncls), dim3(256), 0, s, a);
     HIP_OK(hipGetLastError());
+    std::vector<int> h_counts((size_t)ncls * 3);
+    HIP_OK(hipMemcpyAsync(h_counts.data(), counts.p, h_counts.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    std::vector<long long> h_offs((size_t)ncls * 2);
+    long long nkeys = 0, ntp = 0;
+    for (int k = 0; k < ncls; ++k) {
+        h_offs[k] = nkeys;
+        h_offs[ncls + k] = ntp;
+        nkeys += pow2_at_least(h_counts[k]);
+        ntp += h_counts[2 * ncls + k];
+    }
+    DevBuf keys((size_t)nkeys * 8), tp_prec(protocol == AP_VOC12 ? (size_t)ntp * n_thr * 8 : 0);
+    HIP_OK(hipMemcpyAsync(offs.p, h_offs.data(), h_offs.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemsetAsync(matched.p, 0, ng * n_thr, s));
+    a.koff = offs.as<long long>();
+    a.toff = offs.as<long long>() + ncls;
+    a.tp_stride = ntp;
+    a.keys = keys.as<u64>();
+    a.matched = matched.as<unsigned char>();
+    a.tp_prec = tp_prec.as<double>();
+    a.ap = ap.as<double>();
+    a.present = present.as<int>();
+    hipLaunchKernelGGL(ap_sort_kernel, dim3(ncls), dim3(256), 0, s, a);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(ap_walk_kernel, dim3(ncls, n_thr), dim3(64), 0, s, a);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(ap_out, ap.p, (size_t)n_thr * ncls * 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(present_out, present.p, (size_t)ncls * 4, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+}
+
+// ------------------------------------------------------------------------------------------------------------ accumulator
+struct APStore { float* box; float* conf; int* cls; int* sample; };
+
+// One workgroup appends a pass: min(count[i], out_cap) detections of image 0, then of image 1, ... behind the accumulator's end,
+// in the order the host lists hold them (ties between equal confidences are broken by that order).  The boxes take the host
+// path's round trip through the proportional form.  words[0] (the end) and words[1] (dropped class ids) are advanced with
+// ordinary vector stores: the stream orders one append behind the other.
+__global__ __launch_bounds__(256) void ap_append_kernel(int b, int out_cap, const int* __restrict__ count, const float* __restrict__ conf,
+                                                         const int* __restrict__ cls, const int* __restrict__ box, int ncls, int sample0,
+                                                         long long cap, APStore st, int* words) {
+    __shared__ int s_w[4], s_bad[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int base = words[0];
+    int total = 0, dropped = 0;
+    __syncthreads();
+    for (int i = 0; i < b; ++i) {
+        int n = count[i];
+        n = n < 0 ? 0 : (n > out_cap ? out_cap : n);
+        for (int j0 = 0; j0 < n; j0 += 256) {
+            const int j = j0 + tid;
+            const size_t e = (size_t)i * out_cap + j;
+            const int c = j < n ? cls[e] : -1;
+            const bool ok = j < n && c >= 0 && c < ncls;
+            const u64 bal = __ballot(ok), bad = __ballot(j < n && !ok);
+            if (lane == 0) { s_w[wv] = __popcll(bal); s_bad[wv] = __popcll(bad); }
+            __syncthreads();
+            int at = total;
+            for (int q = 0; q < 4; ++q) { if (q < wv) at += s_w[q]; total += s_w[q]; dropped += s_bad[q]; }
+            const long long pos = (long long)base + at + __popcll(bal & ((1ull << lane) - 1ull));
+            if (ok && pos < cap) {
+                const int* r = box + e * 4;      // (a slot's boxes are 4-byte aligned only)
+                int o[4];
+                rect_on_image(r[0], r[1], r[2], r[3], 1000, 1000, o);
+                *reinterpret_cast<float4*>(st.box + pos * 4) = make_float4((float)o[0], (float)o[1], (float)o[2], (float)o[3]);
+                st.conf[pos] = conf[e];
+                st.cls[pos] = c;
+                st.sample[pos] = sample0 + i;
+            }
+            __syncthreads();
+        }
+    }
+    if (tid == 0) {
+        const long long end = (long long)base + total;
+        words[0] = (int)(end < cap ? end : cap);
+        words[1] += dropped + (int)(end > cap ? end - cap : 0);
+    }
+}
+
+APAccumulator::APAccumulator(int device, int num_classes) : hip_(device), device_(device), ncls_(num_classes) {
+    require_num_classes(num_classes);
+    DeviceGuard g(device_);
+    words_ = (int*)hip_.mem(16);
+    HIP_OK(hipMemset(words_, 0, 16));
+}
+
+void APAccumulator::release_retired() {
+    for (void* p : retired_) hip_.free_mem(p);
+    retired_.clear();
+}
+
+void APAccumulator::sync() {
+    HIP_OK(hipStreamSynchronize(last_));
+    release_retired();
+}
+
+void APAccumulator::clear() {
+    DeviceGuard g(device_);
+    sync();
+    HIP_OK(hipMemset(words_, 0, 16));
+    bound_ = 0;
+    samples_ = 0;
+    gt_box_.clear(); gt_cls_.clear(); gt_sample_.clear(); gt_flags_.clear();
+}
+
+// Room for `extra` more detections behind the host's bound.  The old buffers are copied on `s`, behind the appends already
+// enqueued there, and freed at the next wait: growing never waits for the GPU.
+void APAccumulator::reserve(long long extra, hipStream_t s) {
+    const long long need = bound_ + extra;
+    SSD_REQUIRE(need < INT_MAX, "the accumulator holds at most 2^31 - 1 detections");
+    if (need <= cap_) return;
+    const long long cap = std::max<long long>(std::max<long long>(2 * cap_, need), 1024);
+    Store nw;
+    nw.box = (float*)hip_.mem((size_t)cap * 16);
+    nw.conf = (float*)hip_.mem((size_t)cap * 4);
+    nw.cls = (int*)hip_.mem((size_t)cap * 4);
+    nw.sample = (int*)hip_.mem((size_t)cap * 4);
+    if (bound_ > 0) {
+        HIP_OK(hipMemcpyAsync(nw.box, st_.box, (size_t)bound_ * 16, hipMemcpyDeviceToDevice, s));
+        HIP_OK(hipMemcpyAsync(nw.conf, st_.conf, (size_t)bound_ * 4, hipMemcpyDeviceToDevice, s));
+        HIP_OK(hipMemcpyAsync(nw.cls, st_.cls, (size_t)bound_ * 4, hipMemcpyDeviceToDevice, s));
+        HIP_OK(hipMemcpyAsync(nw.sample, st_.sample, (size_t)bound_ * 4, hipMemcpyDeviceToDevice, s));
+    }
+    if (st_.box) {
+        retired_.push_back(st_.box); retired_.push_back(st_.conf); retired_.push_back(st_.cls); retired_.push_back(st_.sample);
+    }
+    st_ = nw;
+    cap_ = cap;
+}
+
+void APAccumulator::push_gt(int n_gt, const double* gt_box, const int* gt_cls, const int* gt_sample, const unsigned char* gt_flags,
+                            int n_samples, const char* what) {
+    SSD_REQUIRE(n_gt >= 0 && (n_gt == 0 || (gt_box && gt_cls && gt_sample)), "%s: null ground truth", what);
+    SSD_REQUIRE(samples_ + n_samples < INT_MAX, "%s: too many samples", what);
+    for (int g = 0; g < n_gt; ++g) {
+        SSD_REQUIRE(gt_sample[g] >= 0 && gt_sample[g] < n_samples, "%s: ground truth %d belongs to image %d outside 0..%d", what, g, gt_sample[g], n_samples - 1);
+        SSD_REQUIRE(gt_cls[g] >= 0 && gt_cls[g] < ncls_, "%s: ground truth %d has class id %d outside 0..%d", what, g, gt_cls[g], ncls_ - 1);
+    }
+    std::vector<int> order(n_gt);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return gt_sample[x] < gt_sample[y]; });      // rows grouped by sample
+    for (int g : order) {
+        gt_box_.insert(gt_box_.end(), gt_box + (size_t)g * 4, gt_box + (size_t)g * 4 + 4);
+        gt_cls_.push_back(gt_cls[g]);
+        gt_sample_.push_back((int)samples_ + gt_sample[g]);
+        gt_flags_.push_back(gt_flags ? (gt_flags[g] ? 1 : 0) : 0);
+    }
+}
+
+void APAccumulator::add_dev(int b, int out_cap, const int* count_dev, const float* conf_dev, const int* cls_dev, const int* box_dev,
+                            int n_gt, const double* gt_box, const int* gt_cls, const int* gt_image, const unsigned char* gt_flags,
+                            hipStream_t s) {
+    SSD_REQUIRE(b >= 1 && out_cap >= 1 && (long long)b * out_cap < INT_MAX, "ssd_ap_add_dev: b >= 1, out_cap >= 1");
+    SSD_REQUIRE(count_dev && conf_dev && cls_dev && box_dev, "ssd_ap_add_dev: null detection array");
+    DeviceGuard g(device_);
+    reserve((long long)b * out_cap, s);
+    push_gt(n_gt, gt_box, gt_cls, gt_image, gt_flags, b, "ssd_ap_add_dev");
+    APStore st{st_.box, st_.conf, st_.cls, st_.sample};
+    hipLaunchKernelGGL(ap_append_kernel, dim3(1), dim3(256), 0, s, b, out_cap, count_dev, conf_dev, cls_dev, box_dev, ncls_, (int)samples_,
+                       cap_, st, words_);
+    HIP_OK(hipGetLastError());
+    bound_ += (long long)b * out_cap;
+    samples_ += b;
+    last_ = s;
+}
+
+void APAccumulator::counts(long long* n_det, long long* n_dropped) {
+    DeviceGuard g(device_);
+    sync();
+    int w[2];
+    HIP_OK(hipMemcpy(w, words_, 8, hipMemcpyDeviceToHost));
+    bound_ = w[0];      // (the exact end: the bound is tight again)
+    if (n_det) *n_det = w[0];
+    if (n_dropped) *n_dropped = w[1];
+}
+
+void APAccumulator::add_host(int n_det, const float* det_box, const float* det_conf, const int* det_cls, const int* det_sample,
+                             int n_samples, int n_gt, const double* gt_box, const int* gt_cls, const int* gt_sample,
+                             const unsigned char* gt_flags) {
+    SSD_REQUIRE(n_det >= 0 && n_samples >= 0 && (n_det == 0 || (det_box && det_conf && det_cls && det_sample)), "ssd_ap_add_host: bad detections");
+    DeviceGuard g(device_);
+    long long end, dropped;
+    counts(&end, &dropped);
+    std::vector<float> hb, hc;
+    std::vector<int> hk, hs;
+    for (int d = 0; d < n_det; ++d) {
+        SSD_REQUIRE(det_sample[d] >= 0 && det_sample[d] < n_samples, "ssd_ap_add_host: detection %d belongs to sample %d outside 0..%d", d, det_sample[d], n_samples - 1);
+        if (det_cls[d] < 0 || det_cls[d] >= ncls_) { ++dropped; continue; }
+        hb.insert(hb.end(), det_box + (size_t)d * 4, det_box + (size_t)d * 4 + 4);
+        hc.push_back(det_conf[d]); hk.push_back(det_cls[d]); hs.push_back((int)samples_ + det_sample[d]);
+    }
+    const long long n = (long long)hk.size();
+    push_gt(n_gt, gt_box, gt_cls, gt_sample, gt_flags, n_samples, "ssd_ap_add_host");
+    reserve(n, last_);
+    HIP_OK(hipStreamSynchronize(last_));
+    if (n) {
+        HIP_OK(hipMemcpy(st_.box + end * 4, hb.data(), (size_t)n * 16, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(st_.conf + end, hc.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(st_.cls + end, hk.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(st_.sample + end, hs.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+    const int w[2] = {(int)(end + n), (int)dropped};
+    HIP_OK(hipMemcpy(words_, w, 8, hipMemcpyHostToDevice));
+    bound_ = end + n;
+    samples_ += n_samples;
+}
+
+void APAccumulator::fetch(long long cap, float* det_box, float* det_conf, int* det_cls, int* det_sample, long long* n_det) {
+    DeviceGuard g(device_);
+    long long end;
+    counts(&end, nullptr);
+    if (n_det) *n_det = end;
+    SSD_REQUIRE(cap >= end, "ssd_ap_fetch: room for %lld detections, the accumulator holds %lld", cap, end);
+    if (end == 0) return;
+    if (det_box) HIP_OK(hipMemcpy(det_box, st_.box, (size_t)end * 16, hipMemcpyDeviceToHost));
+    if (det_conf) HIP_OK(hipMemcpy(det_conf, st_.conf, (size_t)end * 4, hipMemcpyDeviceToHost));
+    if (det_cls) HIP_OK(hipMemcpy(det_cls, st_.cls, (size_t)end * 4, hipMemcpyDeviceToHost));
+    if (det_sample) HIP_OK(hipMemcpy(det_sample, st_.sample, (size_t)end * 4, hipMemcpyDeviceToHost));
+}
+
+void APAccumulator::compute(int protocol, int n_thr, const double* minoverlaps, double* ap_out, int* present_out, long long* n_det,
+                            long long* n_dropped) {
+    DeviceGuard g(device_);
+    long long end;
+    counts(&end, n_dropped);
+    if (n_det) *n_det = end;
+    const size_t ng = gt_cls_.size();
+    DevBuf gbox(ng * 32), gcls(ng * 4), gsmp(ng * 4), gflg(ng);
+    if (ng) {
+        HIP_OK(hipMemcpy(gbox.p, gt_box_.data(), ng * 32, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(gcls.p, gt_cls_.data(), ng * 4, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(gsmp.p, gt_sample_.data(), ng * 4, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(gflg.p, gt_flags_.data(), ng, hipMemcpyHostToDevice));
+    }
+    APInput in{(int)end, (int)ng, ncls_, st_.box, st_.conf, st_.cls, st_.sample, gbox.as<double>(), gcls.as<int>(), gsmp.as<int>(),
+               gflg.as<unsigned char>()};
+    average_precision_run(in, protocol, n_thr, minoverlaps, ap_out, present_out, last_);
 }
 
 }  // namespace ssd

@@ -17,12 +17,12 @@ import sys
 
 import numpy as np
 
-from .average_precision import APCalculator, APs2mAP
+from .average_precision import APCalculator, DeviceAPCalculator, APs2mAP, add_ap_arguments
 from .ssdvgg import SSDVGG, Session
 from .ssdutils import get_preset_by_name, boxes_from_detection
 from .training_data import default_class_names
 from .pascal_summary import PascalSummary
-from .utils import Size, str2bool, load_data_source, default_colors
+from .utils import Size, Sample, Box, Point, str2bool, load_data_source, default_colors
 
 
 def _has_jpeg_candidates(files):
@@ -157,6 +157,21 @@ def resolve_class_names(num_classes, source_names=None, stored=None):
     return dict(enumerate(default_class_names(num_classes)))
 
 
+def synthetic_ground_truth(n, boxes_per_image, num_classes, lid2name, size):
+    """--synthetic-boxes: seeded ground truth for the --synthetic images, so that the AP path runs without a data set"""
+    rng = np.random.default_rng(2)
+    samples = []
+    for i in range(n):
+        boxes = []
+        for _ in range(boxes_per_image):
+            k = int(rng.integers(0, num_classes))
+            w, h = (float(v) for v in rng.uniform(0.1, 0.5, 2))
+            cx, cy = float(rng.uniform(w / 2, 1 - w / 2)), float(rng.uniform(h / 2, 1 - h / 2))
+            boxes.append(Box(lid2name.get(k, 'class_%d' % k), k, Point(cx, cy), Size(w, h)))
+        samples.append(Sample('%06d.npy' % i, boxes, size))
+    return samples
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description='SSD inference')
     parser.add_argument('files', type=str, nargs='*', help='image files (anything Pillow decodes, or .npy arrays)')
@@ -174,6 +189,7 @@ def main(argv=None):
     parser.add_argument('--threshold', type=float, default=0.5, help='confidence threshold')
     parser.add_argument('--pascal-summary', type=str2bool, default='False', help='dump the detections in Pascal VOC format')
     parser.add_argument('--synthetic', type=int, default=0, help='run on N synthetic images instead of files')
+    parser.add_argument('--synthetic-boxes', type=int, default=0, help='--synthetic: this many seeded ground-truth boxes per image, and the mAP stats over them')
     parser.add_argument('--preset', default=None, help='preset when no checkpoint is given (random weights)')
     parser.add_argument('--num-classes', type=int, default=20, help='class count when no checkpoint is given (1..127)')
     parser.add_argument('--a-trous', type=str2bool, default='True', help='graph when no checkpoint is given: a-trous (true) or fc (false); a checkpoint carries its own')
@@ -183,6 +199,7 @@ def main(argv=None):
                              'them when the environment has SSD_MXFP8_BIGK=1), or mxfp6: the mxfp8 layers on 6-bit e2m3 operands with block scales on '
                              'activations and filters (no calibration; fc6 stays on bf16)')
     add_fp8_arguments(parser)
+    add_ap_arguments(parser)
     parser.add_argument('--decoder', default='gpu', choices=['pillow', 'gpu'],
                         help='gpu: baseline JPEGs are decoded on the GPU, other files as with pillow (same pixels); pillow: every file is decoded on the host')
     parser.add_argument('--decoder-entropy', default='host', choices=['host', 'gpu'],
@@ -273,6 +290,9 @@ def main(argv=None):
         elif args.synthetic:
             rng = np.random.default_rng(1)
             files = [rng.integers(0, 256, (size.h, size.w, 3)).astype(np.float32) for _ in range(args.synthetic)]
+            if args.synthetic_boxes > 0:
+                samples = synthetic_ground_truth(args.synthetic, args.synthetic_boxes, num_classes, lid2name, size)
+                compute_stats = bool(args.compute_stats)
         else:
             files = list(args.files)
             if not files:
@@ -287,7 +307,14 @@ def main(argv=None):
         print('[i] Network checkpoint:', ckpt or '(random weights, --preset ' + str(args.preset) + ')')
         print('[i] Image size:        ', size)
         print('[i] Number of files:   ', len(files))
-        ap_calc = APCalculator() if compute_stats else None
+        ap_dev = compute_stats and args.ap_on == 'gpu'
+        if ap_dev:
+            ap_calc = DeviceAPCalculator(sess.device, num_classes, args.ap_protocol)
+        else:
+            ap_calc = APCalculator(protocol=args.ap_protocol) if compute_stats else None
+        if args.ap_protocol != 'reference' or args.ap_on != 'host':
+            print('[i] AP protocol:       ', args.ap_protocol)
+            print('[i] AP detections on:  ', args.ap_on)
         pascal_summary = PascalSummary() if args.pascal_summary else None                    # infer.py:208-209
         style = None
         if args.annotate:                                                                    # infer.py:242-247
@@ -311,11 +338,13 @@ def main(argv=None):
             elif drawn is not None:
                 for i, img in enumerate(drawn.get()):
                     write_image(os.path.join(args.output_dir, os.path.basename(name_of(idxs[i]))), img)
+            if ap_dev and pascal_summary is None:      # the accumulator has the detections: nothing needs them on the host
+                return
             for i, det in enumerate(ticket.get()):
                 # decode_boxes(enc, anchors, threshold, lid2name, None); suppress_overlaps(boxes)[:200]  (infer.py:233-235)
                 boxes = boxes_from_detection(det, lid2name)
                 total += len(boxes)
-                if compute_stats:                                                            # infer.py:259-260
+                if compute_stats and not ap_dev:                                             # infer.py:259-260
                     ap_calc.add_detections(samples[idxs[i]].boxes, boxes)
                 if pascal_summary is not None:                                               # infer.py:263-264
                     pascal_summary.add_detections(name_of(idxs[i]), boxes, img_size=sizes[i])
@@ -329,6 +358,8 @@ def main(argv=None):
                 if k == 0:
                     tiling.fp8_ready(detector, (packed, offs, shapes), args.fp8_calibration, args.fp8_calibrate_images)
                 ticket = detector.launch(packed, offs, shapes)
+                if ap_dev:
+                    ap_calc.add_pass(ticket, [samples[i].boxes for i in idxs])
                 if writer is not None:
                     drawn = writer.launch(detector, (packed, offs, shapes), style,
                                           [os.path.join(args.output_dir, os.path.basename(name_of(i))) for i in idxs])
@@ -342,6 +373,8 @@ def main(argv=None):
             x, idxs, sizes = batch[:3]
             net.infer_dev(x)                                                                 # infer.py:225-227
             ticket = net.detect_last_launch(x.shape[0], args.threshold, None, 200)
+            if ap_dev:
+                ap_calc.add_pass(ticket, [samples[i].boxes for i in idxs])
             if writer is not None:
                 drawn = writer.launch(net, batch[3], style, [os.path.join(args.output_dir, os.path.basename(name_of(i))) for i in idxs])
             else:
@@ -365,6 +398,9 @@ def main(argv=None):
             print('[i] mAP: {0:.3f}'.format(APs2mAP(aps)))
         if pascal_summary is not None:                                                       # infer.py:278-279
             pascal_summary.write_summary(args.output_dir)
+        if ap_dev:
+            total = ap_calc.num_detections()
+            ap_calc.close()
         print('[i] Processed {} images, {} detections'.format(len(files), total))
     print('[i] All done.')
     return 0

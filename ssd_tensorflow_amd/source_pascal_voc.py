@@ -8,7 +8,7 @@ import os
 import xml.etree.ElementTree as ET
 from glob import glob
 
-from .utils import Label, Box, Sample, Size, abs2prop
+from .utils import Label, Box, FlaggedBox, Sample, Size, abs2prop
 
 VOC_NAMES = ['aeroplane', 'bicycle', 'bird', 'boat', 'bottle', 'bus', 'car', 'cat', 'chair', 'cow', 'diningtable', 'dog',
              'horse', 'motorbike', 'person', 'pottedplant', 'sheep', 'sofa', 'train', 'tvmonitor']
@@ -53,7 +53,10 @@ class PascalVOCSource:
                 xmin = int(float(obj.findtext('bndbox/xmin'))); xmax = int(float(obj.findtext('bndbox/xmax')))
                 ymin = int(float(obj.findtext('bndbox/ymin'))); ymax = int(float(obj.findtext('bndbox/ymax')))
                 center, size = abs2prop(xmin, xmax, ymin, ymax, imgsize)
-                boxes.append(Box(label, self.lname2id[label], center, size))
+                # <difficult> (absent in the oldest sets: 0) rides on the box; only the devkit AP protocols read it
+                difficult = int(float(obj.findtext('difficult') or 0)) != 0
+                boxes.append(FlaggedBox(label, self.lname2id[label], center, size, True) if difficult
+                             else Box(label, self.lname2id[label], center, size))
             if boxes:
                 samples.append(Sample(filename, boxes, imgsize))
         return samples

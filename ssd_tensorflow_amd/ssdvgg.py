@@ -76,8 +76,16 @@ class _DetectionList:
 
 class _Detections:
     """Ticket of SSDVGG.detect_last_launch."""
-    def __init__(self, net, serial, b, out_cap):
+    def __init__(self, net, serial, b, out_cap, slots=None):
         self.net, self.serial, self.b, self.out_cap = net, serial, b, out_cap
+        self._slots = slots
+
+    def dev_slots(self):
+        """(count, conf, cls, box, b, out_cap, stream): the pass's device-visible output slots and the stream it runs on --
+        what a kernel enqueued behind the pass reads (average_precision.DeviceAPCalculator.add_pass)."""
+        if self.net._det_serial != self.serial:
+            raise RuntimeError('the slots of these detections belong to an earlier pass: use them right after the launch')
+        return (*self._slots, self.b, self.out_cap, getattr(self.net, '_stream_ptr', 0))
 
     def get(self):
         which = self.net._det_serial - self.serial
@@ -579,14 +587,14 @@ class SSDVGG:
         ticket whose get() yields what detect_last returns.  Two output slots alternate in the handle, so a
         caller may launch the next batch before it collects this one (infer.py:225-235, pipelined)."""
         cap, mo, out_cap = self._det_caps(detections_cap, max_out)
-        count_dev = C.c_void_p(); cls_dev = C.c_void_p(); box_dev = C.c_void_p()
+        count_dev = C.c_void_p(); conf_dev = C.c_void_p(); cls_dev = C.c_void_p(); box_dev = C.c_void_p()
         check(lib.ssd_detect_last_dev(self._h, b, float(confidence_threshold), cap, mo, out_cap, 1 if nms else 0,
-                                      C.byref(count_dev), None, C.byref(cls_dev), None, C.byref(box_dev)))
+                                      C.byref(count_dev), C.byref(conf_dev), C.byref(cls_dev), None, C.byref(box_dev)))
         self._det_serial = getattr(self, '_det_serial', 0) + 1
         self._det_dev = (self._det_serial, count_dev.value, cls_dev.value, box_dev.value, b, out_cap)      # (annotate_last_launch)
         if not hasattr(self, '_det_views'):
             self._det_views = {}
-        return _Detections(self, self._det_serial, b, out_cap)
+        return _Detections(self, self._det_serial, b, out_cap, (count_dev.value, conf_dev.value, cls_dev.value, box_dev.value))
 
     def annotate_last_launch(self, src, src_offs, src_shapes, style, dst_shapes=None, rgb_out=False, keep_device=False, to_host=True):
         """Enqueue, right behind the decode that detect_last_launch has just launched and on the same stream, the drawing of its

@@ -92,6 +92,13 @@ class _TileDetections:
         self.owner, self.serial, self._dev, self._host, self.done = owner, serial, dev, host, done
         self.b, self.out_cap, self.tiles = n_images, out_cap, tiles
         self.count_dev, self.cls_dev, self.box_dev = dev['count'].data_ptr(), dev['cls'].data_ptr(), dev['box'].data_ptr()
+        self.conf_dev = dev['conf'].data_ptr()
+
+    def dev_slots(self):
+        """(count, conf, cls, box, b, out_cap, stream) of the merged detections (average_precision.DeviceAPCalculator.add_pass)"""
+        if self.owner._serial != self.serial:
+            raise RuntimeError('the slots of these detections belong to an earlier pass: use them right after the launch')
+        return (self.count_dev, self.conf_dev, self.cls_dev, self.box_dev, self.b, self.out_cap, getattr(self.owner.net, '_stream_ptr', 0))
 
     def get(self):
         if self.owner._serial - self.serial not in (0, 1):

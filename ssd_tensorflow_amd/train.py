@@ -22,7 +22,7 @@ import sys
 import numpy as np
 
 from . import _lib, parallel
-from .average_precision import APCalculator, APs2mAP
+from .average_precision import APCalculator, DeviceAPCalculator, APs2mAP, add_ap_arguments
 from .ssdutils import boxes_from_detection
 from .ssdvgg import SSDVGG, Session, LearningRate
 from .summaries import SummaryWriter, LossSummary, PrecisionSummary, ImageSummary
@@ -72,6 +72,8 @@ class StepLoop:
             return
         if drawn is not None:
             image_samples.add(drawn.get())
+        if isinstance(calc, DeviceAPCalculator):      # (run_epoch has handed it the pass where it launched the decode)
+            return
         for gt, det in zip(gt_boxes, dets.get()):
             calc.add_detections(gt, boxes_from_detection(det, self.td.lid2name))
 
@@ -119,6 +121,8 @@ class StepLoop:
                 continue
             # decode + NMS of the batch just computed, on the GPU (train.py:275-277)
             launched = net.detect_last_launch(n, 0.5, 200, None)
+            if isinstance(ap_calc, DeviceAPCalculator):
+                ap_calc.add_pass(launched, gt_boxes)
             drawn = self.annotate_launch(x, n, image_samples)
             if pending_det:
                 self.collect(*pending_det, ap_calc, image_samples)
@@ -148,6 +152,7 @@ def main(argv=None):
     parser.add_argument('--cache-gb', type=float, default=0, help='--decoder gpu: keep up to this many GB of decoded pictures in HBM; a cached picture costs no file read, no decode and no upload from its second epoch on (0 = off)')
     parser.add_argument('--preset', default='vgg300')
     parser.add_argument('--data-source', default='pascal_voc', help='data source module for a real --data-dir')
+    add_ap_arguments(parser)
     parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='f32, or bf16 activations on the bf16 matrix cores (fp32 master weights, loss and optimizer)')
     parser.add_argument('--a-trous', type=str2bool, default='True', help='a fresh run: the a-trous graph (true) or the fc graph with the whole fc6 / fc7 (false; weights from <vgg-dir>/vgg16_ssd_fc.npz); --continue-training takes the checkpoint\'s')
     parser.add_argument('--synthetic-train', type=int, default=64, help='synthetic training samples per epoch')
@@ -242,8 +247,12 @@ def main(argv=None):
         net.set_stream(torch.cuda.current_stream().cuda_stream)
 
         writer = SummaryWriter(os.path.join(args.tensorboard_dir, os.path.basename(os.path.normpath(args.name)))) if rank == 0 else None
-        training_ap_calc = APCalculator()
-        validation_ap_calc = APCalculator()
+        if args.ap_on == 'gpu':       # the detections stay on the GPU between the decode and the AP kernels
+            training_ap_calc = DeviceAPCalculator(local, td.num_classes, args.ap_protocol)
+            validation_ap_calc = DeviceAPCalculator(local, td.num_classes, args.ap_protocol)
+        else:
+            training_ap_calc = APCalculator(protocol=args.ap_protocol)
+            validation_ap_calc = APCalculator(protocol=args.ap_protocol)
         labels = list(td.lname2id.keys())
         training_ap = PrecisionSummary(writer, 'training', labels)
         validation_ap = PrecisionSummary(writer, 'validation', labels)
@@ -263,7 +272,10 @@ def main(argv=None):
             torch.distributed.gather_object(calc.state(), states, dst=0)
             if rank != 0:
                 return {}
-            merged = APCalculator(calc.minoverlap)
+            if isinstance(calc, DeviceAPCalculator):
+                merged = DeviceAPCalculator(calc.device, calc.num_classes, calc.protocol, calc.minoverlap)
+            else:
+                merged = APCalculator(calc.minoverlap, calc.protocol)
             for st in states:
                 merged.merge(st)
             return merged.compute_aps()

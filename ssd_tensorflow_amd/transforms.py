@@ -39,7 +39,7 @@ import numpy as np
 from . import _lib
 from ._lib import lib, check
 from .ssdutils import encode_labels_batch
-from .utils import Size, Sample, Point, Box, abs2prop, prop2abs
+from .utils import Size, Sample, Point, Box, box_like, abs2prop, prop2abs
 
 MAX_EXTRA = 16       # ssd_augment_params.extra_kind / extra_val
 MAX_POST = 4         # ssd_augment_params.post_kind / post_val
@@ -334,7 +334,7 @@ def transform_box(box, orig_size, new_size, h_off, w_off):
     centre_y = y0 + int((y1 - y0) / 2)
     if not (0 <= centre_x < new_size.w and 0 <= centre_y < new_size.h):
         return None
-    return Box(box.label, box.labelid, *abs2prop(x0, x1, y0, y1, new_size))
+    return box_like(box, *abs2prop(x0, x1, y0, y1, new_size))
 
 
 def transform_gt(gt, new_size, h_off, w_off):
@@ -509,7 +509,7 @@ class HorizontalFlipTransform(Transform):
         boxes = []
         for box in gt.boxes:
             center = Point(1 - box.center.x, box.center.y)
-            boxes.append(Box(box.label, box.labelid, center, box.size))
+            boxes.append(box_like(box, center, box.size))
         return data, label, Sample(gt.filename, boxes, gt.imgsize)
 
 

@@ -13,6 +13,33 @@ Point = namedtuple('Point', ['x', 'y'])
 Sample = namedtuple('Sample', ['filename', 'boxes', 'imgsize'])
 Box = namedtuple('Box', ['label', 'labelid', 'center', 'size'])
 Score = namedtuple('Score', ['idx', 'score'])
+
+
+class FlaggedBox(Box):
+    """A Box that carries VOC's <difficult> flag.  It IS the reference's 4-field tuple -- it compares, hashes, unpacks and
+    indexes like Box, so every consumer of Box takes it -- with one attribute more, which pickling keeps."""
+
+    def __new__(cls, label, labelid, center, size, difficult=False):
+        self = super().__new__(cls, label, labelid, center, size)
+        self.difficult = bool(difficult)
+        return self
+
+    def __reduce__(self):
+        return FlaggedBox, (self.label, self.labelid, self.center, self.size, self.difficult)
+
+    def _replace(self, **kwargs):
+        difficult = kwargs.pop('difficult', self.difficult)
+        return FlaggedBox(*Box._replace(Box(*self), **kwargs), difficult=difficult)
+
+    def __repr__(self):
+        return Box.__repr__(self)[:-1] + ', difficult=%r)' % self.difficult
+
+
+def box_like(box, center, size):
+    """`box` with another centre and size: a transform's result keeps the label and the difficult flag."""
+    if getattr(box, 'difficult', False):
+        return FlaggedBox(box.label, box.labelid, center, size, True)
+    return Box(box.label, box.labelid, center, size)
 Overlap = namedtuple('Overlap', ['best', 'good'])
 
 
@@ -58,7 +85,7 @@ def normalize_box(box):
     ymin = max(ymin, 0); ymax = min(ymax, img.h - 1)
     xmin = min(xmin, xmax); ymin = min(ymin, ymax)
     center, size = abs2prop(xmin, xmax, ymin, ymax, img)
-    return Box(box.label, box.labelid, center, size)
+    return box_like(box, center, size)
 
 
 def load_data_source(data_source):
