@@ -558,7 +558,9 @@ void tail_chain_bf16(const TailStage* stages, int nstages, int nimg, const char*
         int ksplit = TAIL_WAVES / k.tiles;
         if (ksplit < 1) ksplit = 1;
         if (ksplit > 4) ksplit = 4;
-        while (ksplit > 1 && k.ngroups / ksplit < 1) --ksplit;
+        // every split must own a group: a task without one (9 groups over 4 splits of 3: the last starts at group 9) would still prime
+        // its filter stream, 4 KB past the end of the packed filter
+        while (ksplit > 1 && (ksplit - 1) * cdiv(k.ngroups, ksplit) >= k.ngroups) --ksplit;
         k.ksplit = ksplit;
         k.ntask = k.tiles * ksplit;
         SSD_REQUIRE(k.ntask <= TAIL_MAX_TASKS && (ksplit == 1 || k.ntask <= TAIL_WAVES), "tail chain: stage %d has too many tasks (%d)", i, k.ntask);
@@ -568,6 +570,7 @@ void tail_chain_bf16(const TailStage* stages, int nstages, int nimg, const char*
             const int mg = t2 / nblk_n, nb = t2 - mg * nblk_n;
             const int nmb = std::min(TAIL_MG, nblk_m - mg * TAIL_MG);
             const int g0 = std::min(ks * per, k.ngroups), g1 = std::min(k.ngroups, g0 + per);
+            SSD_REQUIRE(g0 < g1, "tail chain: stage %d, task %d has no k group", i, task);
             k.tasks[task][0] = (unsigned)nb | ((unsigned)mg << 8) | ((unsigned)ks << 16) | ((unsigned)nmb << 24);
             k.tasks[task][1] = (unsigned)g0 | ((unsigned)g1 << 16);
         }
