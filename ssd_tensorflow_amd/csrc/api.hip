@@ -1302,7 +1302,7 @@ int ssd_op_conv2d_wino_fwd(const float* x, const float* w, const float* bias, fl
         wino_filter(d, w, k.U, k.Uf, (hipStream_t)stream);
     }
     wino_fwd(d, x, k.U, bias, y, relu != 0, k.V, (size_t)wino_tiles(d) * d.Ci, k.Mx, y_pool, rec, (hipStream_t)stream, relu_bits,
-             (flags & 4) != 0);
+             (flags & 4) != 0, (flags & 8) != 0);
     API_END
 }
 int ssd_op_conv2d_wino_dgrad(const float* dy, const float* w, float* dx, const float* mask, const void* mask_bits, int accumulate,
@@ -1316,7 +1316,7 @@ int ssd_op_conv2d_wino_dgrad(const float* dy, const float* w, float* dx, const f
         HIP_OK(hipMemsetAsync(k.Uf, 0, (size_t)36 * d.Ci * wino_kpad(d.Co) * sizeof(float), (hipStream_t)stream));      // the pad rows
         wino_filter(d, w, k.U, k.Uf, (hipStream_t)stream);
     }
-    wino_bwd_transform(d, dy, k.Yt, nullptr, (hipStream_t)stream);
+    wino_bwd_transform(d, dy, k.Yt, nullptr, (hipStream_t)stream, (flags & 8) != 0);
     wino_dgrad(d, k.Yt, k.Uf, dx, mask, accumulate != 0, k.Mx, rec, uh, uw, (hipStream_t)stream, mask_bits, (flags & 4) != 0);
     API_END
 }
@@ -1331,10 +1331,10 @@ int ssd_op_conv2d_wino_wgrad(const float* x, const float* dy, float* dw, float* 
     if (!(flags & 2)) {      // the input's transform: through wino_fwd's first kernel would need a filter; use the dy transform's B^T form on x
         ConvDesc dx = d;
         dx.Co = d.Ci; dx.Ho = d.Hi; dx.Wo = d.Wi;
-        wino_bwd_transform(dx, x, k.V, nullptr, (hipStream_t)stream);
+        wino_bwd_transform(dx, x, k.V, nullptr, (hipStream_t)stream, (flags & 8) != 0);
     }
-    wino_bwd_transform(d, dy, nullptr, k.Ya, (hipStream_t)stream);
-    wino_wgrad(d, k.V, vps, k.Ya, dw, dbias, w, weight_decay, k.slabs, (hipStream_t)stream);
+    wino_bwd_transform(d, dy, nullptr, k.Ya, (hipStream_t)stream, (flags & 8) != 0);
+    wino_wgrad(d, k.V, vps, k.Ya, dw, dbias, w, weight_decay, k.slabs, (hipStream_t)stream, (flags & 8) != 0);
     API_END
 }
 size_t ssd_op_conv2d_wgrad_ws_floats(int b, int hi, int wi, int ci, int ho, int wo, int co, int kh, int kw, int stride,

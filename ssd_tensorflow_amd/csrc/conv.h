@@ -78,10 +78,13 @@ size_t wino_fwd_ws_floats(const ConvDesc& d);              // Mws: 36 * tiles * 
 // the fused 2x2 pool of conv_fwd_pool instead of y (same values, same record).
 // relu_bits (optional, tiles * Ci / 4 64-bit words): which of x's values are positive, per tile and 4 channels -- what wino_dgrad of the
 // SAME layer takes as mask_bits in place of a second read of x
+// ref_geom (here, wino_bwd_transform, wino_wgrad): the reference launch geometry of winograd.hip (raster-order input transform, the
+// one-thread-per-(ci, 4 co) reduce) -- the same bits, kept for the bit-identity test and same-box A/Bs; SSD_WINO_GEOMETRY=0 forces it
 void wino_fwd(const ConvDesc& d, const float* x, const float* U, const float* bias, float* y, bool relu, float* V, size_t v_ps,
-              float* Mws, float* y_pool, void* pool_rec, hipStream_t s, void* relu_bits = nullptr, bool two_launch = false);
+              float* Mws, float* y_pool, void* pool_rec, hipStream_t s, void* relu_bits = nullptr, bool two_launch = false,
+              bool ref_geom = false);
 // dy -> Yt (B^T dy B, the data gradient's operand) and / or Ya (A dy A^T, the weight gradient's), each [36][tiles][wino_kpad(Co)]; nullptr skips one
-void wino_bwd_transform(const ConvDesc& d, const float* dy, float* Yt, float* Ya, hipStream_t s);
+void wino_bwd_transform(const ConvDesc& d, const float* dy, float* Yt, float* Ya, hipStream_t s, bool ref_geom = false);
 size_t wino_dgrad_ws_floats(const ConvDesc& d);            // Xws: 36 * tiles * Ci
 // conv_dgrad's semantics (mask, accumulate) from the transformed dy; unpool_rec != nullptr: conv_dgrad_unpool's
 void wino_dgrad(const ConvDesc& d, const float* Yt, const float* Uflip, float* dx, const float* mask, bool accumulate, float* Xws,
@@ -89,7 +92,7 @@ void wino_dgrad(const ConvDesc& d, const float* Yt, const float* Uflip, float* d
 size_t wino_wgrad_ws_floats(const ConvDesc& d);
 // conv_wgrad's semantics from the forward's V and the transformed dy
 void wino_wgrad(const ConvDesc& d, const float* V, size_t v_ps, const float* Ya, float* dw, float* dbias, const float* w,
-                float weight_decay, float* ws, hipStream_t s);
+                float weight_decay, float* ws, hipStream_t s, bool ref_geom = false);
 
 // ---- convolutions with more than 9 taps (conv_bigk.hip): the fc graph's 7x7 fc6 -------------------------------------------------
 // Stride 1, dilation 1, SAME; channel counts multiples of 4 (fp32) / 8 (bf16).  conv_fwd / conv_dgrad / conv_wgrad and their bf16 forms

@@ -14,7 +14,7 @@
 //   weight grad.   dU_p = V_p^T . (A dy A^T)_p                 36 GEMMs [Ci x T] . [T x Co], split over T into slabs (wino_gemm_tn_kernel)
 //                  dg = G^T (sum of slabs, fixed order) G + weight_decay g;  dbias = column sums of dy = a weighted sum of the
 //                  column sums of (A dy A^T) at 16 positions (bias_axis_weight)
-//                  (wino_wgrad_reduce_kernel)
+//                  (wino_wgrad_reduce36_kernel; wino_wgrad_reduce_kernel is its reference)
 //
 // The same form serves the dilated layer (mod_conv6: every residue class of the dilation is an image of its own, wino_in_kernel) and the
 // multibox heads of the big maps (output channels in multiples of 4: the data gradient's k is padded to 32 with zeros).  The relu mask a
@@ -77,13 +77,22 @@ __device__ __forceinline__ float bias_axis_weight(int slot) {
 // ---- input transforms: one thread = 4 channels of one tile ---------------------------------------------------------------------
 // BT: V = B^T d B of the 6x6 patch at (4i - 1, 4j - 1), zero outside the image        (forward input; data gradient's dy)
 // AT: Va = A e A^T of the patch's inner 4x4 (rows 4i ... 4i + 3), zero outside         (weight gradient's dy)
+// Workgroup order (BT): a workgroup is a run of 256 / (Cp / 4) tiles of the raster, and a tile row shares two pixel rows (and the
+// corners) with the next one, whose workgroups come tw * (Cp / 4) / 256 ids later.  Dealt round-robin over the XCDs those land on another
+// L2 and the shared rows come over the fabric twice (6 rows fetched per 4 used).  xcd_remap gives every XCD one contiguous run of the
+// raster instead: the 64 workgroups an XCD holds at a time span 5 to 13 tile rows of every layer of the step, so the neighbour's rows
+// are mostly in that L2 (FETCH_SIZE per launch 1.6 -> 1.1 times the tensor, profiles/wino_geometry_pmc.txt; 2-D blocks of tiles per
+// workgroup fetched no less).  Only which thread takes which (tile, quad) changes; raster = true is the plain order (the reference
+// geometry of tests/test_gpu_winograd_geometry.py).  AT has no halo and keeps the plain order.
 template <bool BT, bool AT>
 __global__ __launch_bounds__(256) void wino_in_kernel(const float* __restrict__ x, float* __restrict__ V, float* __restrict__ Va,
                                                       int H, int W, int C, int Cp, int th, int tw, int T, unsigned x_bytes,
-                                                      size_t v_ps, size_t va_ps, int D, unsigned long long* __restrict__ bits) {
+                                                      size_t v_ps, size_t va_ps, int D, unsigned long long* __restrict__ bits,
+                                                      bool raster) {
     // Cp >= C: row length of V / Va (a GEMM's k must be a multiple of 32: the multibox heads' 104 / 152 channels are padded with zeros)
     const int c4n = Cp >> 2;
-    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const int wg = (BT && !raster) ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+    const int idx = wg * 256 + threadIdx.x;
     const int q = idx % c4n, t = idx / c4n;
     if (t >= T) return;
     const int j = t % tw, t2 = t / tw;
@@ -759,6 +768,8 @@ __device__ __forceinline__ void gt3(const f32x4 s0, const f32x4 s1, const f32x4 
     g[2] = (8.f / 27.f) * (c - a) + s5;
 }
 // dw[tap][ci][co] = (G^T (sum_s slab_s) G)_tap + wd * w ; dbias = sum_s slab_s' bias part.  One thread = (ci, 4 co); slabs added in order.
+// The reference geometry (wino_wgrad_reduce36_kernel below is what a step runs): a thread's 36 nsplit loads come in 6 dependent rounds
+// per 4 slabs, the bias threads' 16 nsplit one after the other, and conv1_2's grid is 5 workgroups.
 __global__ __launch_bounds__(256) void wino_wgrad_reduce_kernel(const float* __restrict__ ws, int nsplit, int Ci, int Co,
                                                                 float* __restrict__ dw, float* __restrict__ db,
                                                                 const float* __restrict__ w, float wd) {
@@ -820,6 +831,81 @@ __global__ __launch_bounds__(256) void wino_wgrad_reduce_kernel(const float* __r
     }
 }
 
+// The same sums with one thread per (position, ci, 4 co): every thread adds its position's slabs in index order, the 6 threads of a
+// column meet in LDS for gt3 down the column, the 6 columns for gt3 across, then + wd * w -- the expressions of the kernel above in
+// its order, so the same bits, with nsplit dependent loads per thread instead of 36 nsplit and 36 times the threads.  The first
+// cdiv(Co / 4, 32) workgroups are the bias gradient's: one thread per (slot, 4 co) adds the slabs, one per 4 co the 16 slots.
+constexpr int WR_E = 16;      // (ci, 4 co) elements of a workgroup: 256 contiguous bytes per position
+__global__ __launch_bounds__(36 * WR_E) void wino_wgrad_reduce36_kernel(const float* __restrict__ ws, int nsplit, int Ci, int Co,
+                                                                        float* __restrict__ dw, float* __restrict__ db,
+                                                                        const float* __restrict__ w, float wd) {
+    __shared__ f32x4 sm[36][WR_E];      // slab sums per position; the bias blocks use it as [16 slots][32 quads]
+    __shared__ f32x4 cm[18][WR_E];      // after gt3 down the columns: [a][l]
+    const int c4n = Co >> 2, tid = threadIdx.x;
+    const size_t cc = (size_t)Ci * Co, ucount = 36 * cc, stride = ucount + 16 * (size_t)Co;
+    const int bias_blocks = (c4n + 31) / 32;
+    if ((int)blockIdx.x < bias_blocks) {
+        const int q = blockIdx.x * 32 + (tid & 31), slot = tid >> 5;
+        if (!db) return;
+        if (slot < 16 && q < c4n) {
+            f32x4 t = {0.f, 0.f, 0.f, 0.f};
+            for (int k = 0; k < nsplit; ++k) t += *reinterpret_cast<const f32x4*>(ws + (size_t)k * stride + ucount + (size_t)slot * Co + q * 4);
+            (&sm[0][0])[slot * 32 + (tid & 31)] = t;
+        }
+        __syncthreads();
+        if (slot == 0 && q < c4n) {
+            f32x4 s = {0.f, 0.f, 0.f, 0.f};
+            for (int sl = 0; sl < 16; ++sl) {      // fixed order: position, then slab
+                const f32x4 t = (&sm[0][0])[sl * 32 + tid];
+                s += (bias_axis_weight(sl >> 2) * bias_axis_weight(sl & 3)) * t;
+            }
+            *reinterpret_cast<f32x4*>(db + q * 4) = s;
+        }
+        return;
+    }
+    const int el = tid % WR_E, p = tid / WR_E;
+    const int idx = (blockIdx.x - bias_blocks) * WR_E + el;      // = ci * (Co / 4) + q
+    const bool valid = idx < Ci * c4n;
+    const size_t e = (size_t)idx * 4;                             // = ci * Co + 4 q
+    // the three taps of row a = p this thread will finish: w on its way while the slabs are summed
+    f32x4 wv[3];
+    const bool last = p < 3 && valid;
+    if (last && wd != 0.f) {
+#pragma unroll
+        for (int b = 0; b < 3; ++b) wv[b] = *reinterpret_cast<const f32x4*>(w + (size_t)(p * 3 + b) * cc + e);
+    }
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    if (valid) {
+        for (int sp0 = 0; sp0 < nsplit; sp0 += 4) {
+            f32x4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(ws + (size_t)min(sp0 + u, nsplit - 1) * stride + (size_t)p * cc + e);
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (sp0 + u < nsplit) s += v[u];
+        }
+    }
+    sm[p][el] = s;      // p = k * 6 + l
+    __syncthreads();
+    if (p < 6) {        // column l = p
+        f32x4 g[3];
+        gt3(sm[p][el], sm[6 + p][el], sm[12 + p][el], sm[18 + p][el], sm[24 + p][el], sm[30 + p][el], g);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) cm[a * 6 + p][el] = g[a];
+    }
+    __syncthreads();
+    if (last) {         // row a = p
+        f32x4 g[3];
+        gt3(cm[p * 6][el], cm[p * 6 + 1][el], cm[p * 6 + 2][el], cm[p * 6 + 3][el], cm[p * 6 + 4][el], cm[p * 6 + 5][el], g);
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            f32x4 v = g[b];
+            if (wd != 0.f) v += wd * wv[b];
+            *reinterpret_cast<f32x4*>(dw + (size_t)(p * 3 + b) * cc + e) = v;
+        }
+    }
+}
+
 // =====================================================================================================================================
 // host side
 // =====================================================================================================================================
@@ -864,22 +950,31 @@ void wino_filter(const ConvDesc& d, const float* w, float* U, float* Uflip, hipS
 }
 
 // x [B][H][W][C] -> V (B^T d B) and / or Va (A e A^T), both [36][.][C] with v_ps / va_ps elements between positions
+// The reference geometry: wino_in_kernel's workgroups in raster order and the one-thread-per-(ci, 4 co) reduce, for a call that asks for
+// it (the C ABI's flags bit 3) or for the whole process (SSD_WINO_GEOMETRY=0).  The same bits either way (tests/test_gpu_winograd_geometry.py).
+// For A/Bs of one part alone: SSD_WINO_GEOMETRY=2 keeps only the transform's new order, 3 only the new reduce.
+enum { GEOM_IN = 0, GEOM_REDUCE = 1 };
+static bool ref_geometry(bool asked, int part) {
+    static const int on = env_int("SSD_WINO_GEOMETRY", 1);
+    return asked || on == 0 || (on == 2 && part != GEOM_IN) || (on == 3 && part != GEOM_REDUCE);
+}
+
 static void launch_in(const float* x, float* V, float* Va, int B, int H, int W, int C, int Cp, int D, size_t v_ps, size_t va_ps, hipStream_t s,
-                      unsigned long long* bits = nullptr) {
+                      unsigned long long* bits, bool raster) {
     const int th = tiles_1d(H, D), tw = tiles_1d(W, D), T = B * th * tw;
     const unsigned xb = (unsigned)((size_t)B * H * W * C * 4u);
     const int grid = cdiv((long long)T * (Cp / 4), 256);
     const double by = 4.0 * ((double)B * H * W * C + 36.0 * T * Cp * ((V ? 1 : 0) + (Va ? 1 : 0)));
     if (V && Va) {      // (one kernel for both was never measured faster than the data gradient's stream running its own: two launches)
-        launch_in(x, V, nullptr, B, H, W, C, Cp, D, v_ps, 0, s, bits);
-        launch_in(x, nullptr, Va, B, H, W, C, Cp, D, 0, va_ps, s);
+        launch_in(x, V, nullptr, B, H, W, C, Cp, D, v_ps, 0, s, bits, raster);
+        launch_in(x, nullptr, Va, B, H, W, C, Cp, D, 0, va_ps, s, nullptr, raster);
         return;
     } else if (V) {
         ProfScope prof("wino_in", 0, by, s);
-        hipLaunchKernelGGL((wino_in_kernel<true, false>), dim3(grid), dim3(256), 0, s, x, V, Va, H, W, C, Cp, th, tw, T, xb, v_ps, va_ps, D, bits);
+        hipLaunchKernelGGL((wino_in_kernel<true, false>), dim3(grid), dim3(256), 0, s, x, V, Va, H, W, C, Cp, th, tw, T, xb, v_ps, va_ps, D, bits, raster);
     } else {
         ProfScope prof("wino_in_wgrad", 0, by, s);
-        hipLaunchKernelGGL((wino_in_kernel<false, true>), dim3(grid), dim3(256), 0, s, x, V, Va, H, W, C, Cp, th, tw, T, xb, v_ps, va_ps, D, bits);
+        hipLaunchKernelGGL((wino_in_kernel<false, true>), dim3(grid), dim3(256), 0, s, x, V, Va, H, W, C, Cp, th, tw, T, xb, v_ps, va_ps, D, bits, raster);
     }
     HIP_OK(hipGetLastError());
 }
@@ -959,10 +1054,10 @@ static void launch_fused(const float* A, size_t a_ps, const float* Bm, int K, co
 size_t wino_fwd_ws_floats(const ConvDesc& d) { return (size_t)36 * wino_tiles(d) * d.Co; }
 
 void wino_fwd(const ConvDesc& d, const float* x, const float* U, const float* bias, float* y, bool relu, float* V, size_t v_ps,
-              float* Mws, float* y_pool, void* pool_rec, hipStream_t s, void* relu_bits, bool two_launch) {
+              float* Mws, float* y_pool, void* pool_rec, hipStream_t s, void* relu_bits, bool two_launch, bool ref_geom) {
     require(d);
     const int T = wino_tiles(d);
-    launch_in(x, V, nullptr, d.B, d.Hi, d.Wi, d.Ci, d.Ci, d.dil, v_ps, 0, s, static_cast<unsigned long long*>(relu_bits));
+    launch_in(x, V, nullptr, d.B, d.Hi, d.Wi, d.Ci, d.Ci, d.dil, v_ps, 0, s, static_cast<unsigned long long*>(relu_bits), ref_geometry(ref_geom, GEOM_IN));
     const bool fused = fuse_out(d, d.Co, d.Ci, two_launch);
     if (!fused) gemm_nn(V, v_ps, U, Mws, (size_t)T * d.Co, T, d.Co, d.Ci, s);
     WinoOutArgs a{};
@@ -985,10 +1080,10 @@ void wino_fwd(const ConvDesc& d, const float* x, const float* U, const float* bi
 
 size_t wino_dgrad_ws_floats(const ConvDesc& d) { return (size_t)36 * wino_tiles(d) * d.Ci; }
 
-void wino_bwd_transform(const ConvDesc& d, const float* dy, float* Yt, float* Ya, hipStream_t s) {
+void wino_bwd_transform(const ConvDesc& d, const float* dy, float* Yt, float* Ya, hipStream_t s, bool ref_geom) {
     require(d);
     const size_t ps = (size_t)wino_tiles(d) * wino_kpad(d.Co);
-    launch_in(dy, Yt, Ya, d.B, d.Ho, d.Wo, d.Co, wino_kpad(d.Co), d.dil, ps, ps, s);
+    launch_in(dy, Yt, Ya, d.B, d.Ho, d.Wo, d.Co, wino_kpad(d.Co), d.dil, ps, ps, s, nullptr, ref_geometry(ref_geom, GEOM_IN));
 }
 
 void wino_dgrad(const ConvDesc& d, const float* Yt, const float* Uflip, float* dx, const float* mask, bool accumulate, float* Xws,
@@ -1058,7 +1153,7 @@ static void launch_tn(WinoTnArgs& a, const char* label, double flops, double byt
 }
 
 void wino_wgrad(const ConvDesc& d, const float* V, size_t v_ps, const float* Ya, float* dw, float* dbias, const float* w,
-                float weight_decay, float* ws, hipStream_t s) {
+                float weight_decay, float* ws, hipStream_t s, bool ref_geom) {
     require(d);
     const int T = wino_tiles(d);
     WinoTnArgs a{};
@@ -1078,8 +1173,12 @@ void wino_wgrad(const ConvDesc& d, const float* V, size_t v_ps, const float* Ya,
     {
         const int n = d.Ci * (d.Co / 4) + d.Co / 4;
         ProfScope prof("wino_wgrad_reduce", 0, 4.0 * ((double)a.nsplit * 36 + 18) * d.Ci * d.Co, s);
-        hipLaunchKernelGGL(wino_wgrad_reduce_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, ws, a.nsplit, d.Ci, d.Co, dw, dbias, w,
-                           weight_decay);
+        if (ref_geometry(ref_geom, GEOM_REDUCE))
+            hipLaunchKernelGGL(wino_wgrad_reduce_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, ws, a.nsplit, d.Ci, d.Co, dw, dbias, w,
+                               weight_decay);
+        else
+            hipLaunchKernelGGL(wino_wgrad_reduce36_kernel, dim3(cdiv(d.Co / 4, 32) + cdiv(d.Ci * (d.Co / 4), WR_E)), dim3(36 * WR_E), 0, s, ws,
+                               a.nsplit, d.Ci, d.Co, dw, dbias, w, weight_decay);
         HIP_OK(hipGetLastError());
     }
 }
