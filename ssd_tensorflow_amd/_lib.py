@@ -66,6 +66,11 @@ SIGNATURES = {
     'ssd_ap_count': (i32, [vp, p_i64, p_i64]),
     'ssd_ap_fetch': (i32, [vp, C.c_longlong, vp, vp, vp, vp, p_i64]),
     'ssd_ap_compute': (i32, [vp, i32, i32, vp, vp, vp, p_i64, p_i64]),
+    'ssd_coco_eval': (i32, [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]),
+    'ssd_ap_add_dev_coco': (i32, [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    'ssd_ap_add_host_coco': (i32, [vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
+    'ssd_ap_compute_coco': (i32, [vp, i32, vp, vp, vp, vp, p_i64, p_i64]),
+    'ssd_ap_kernel_times': (i32, [i32, vp]),
     'ssd_arena_floats': (sz, [cstr, i32]),
     'ssd_augment_ws_bytes': (sz, [i32, i32, i32]),
     'ssd_augment_batch_dev': (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),

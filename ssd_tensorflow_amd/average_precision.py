@@ -28,9 +28,10 @@ def APs2mAP(aps):
 
 def add_ap_arguments(parser):
     """--ap-protocol / --ap-on of the drivers that compute AP (infer.py, train.py)"""
-    parser.add_argument('--ap-protocol', default='reference', choices=list(PROTOCOLS),
+    parser.add_argument('--ap-protocol', default='reference', choices=list(PROTOCOLS) + ['coco'],
                         help="reference: the reference's 11-point AP, every ground-truth box counts; voc07: the devkit's 11-point AP, "
-                             'difficult objects count neither way; voc12: the same matching, all-point AP (VOC2010 on)')
+                             'difficult objects count neither way; voc12: the same matching, all-point AP (VOC2010 on); coco: '
+                             "COCO's box AP / AR over IoU 0.50:0.95, area ranges and detection caps (coco_eval.py), twelve numbers")
     parser.add_argument('--ap-on', default='host', choices=['host', 'gpu'],
                         help='host: the detections are collected in Python lists; gpu: a kernel behind each detection pass appends them '
                              'to buffers on the GPU, they come to the host only where files or pictures need them (same AP)')

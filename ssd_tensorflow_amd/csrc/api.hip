@@ -509,6 +509,88 @@ int ssd_ap_compute(ssd_ap_accumulator acc, int protocol, int n_thr, const double
     API_END
 }
 
+int ssd_coco_eval(int device, int n_det, const float* det_box, const float* det_conf, const int* det_cls, const int* det_sample,
+                  int n_gt, const double* gt_box, const int* gt_cls, const int* gt_sample, const unsigned char* gt_flags,
+                  const double* gt_area, int n_samples, const double* sample_scale, int num_classes, int n_thr,
+                  const double* thresholds, double* ap_out, double* ar_out, int* present_out) {
+    API_BEGIN
+    SSD_REQUIRE(num_classes >= 1 && n_det >= 0 && n_gt >= 0 && n_samples >= 0, "ssd_coco_eval: bad sizes");
+    SSD_REQUIRE(n_thr >= 1 && n_thr <= AP_MAX_THRESHOLDS && thresholds, "ssd_coco_eval: 1..%d IoU thresholds (got %d)", AP_MAX_THRESHOLDS, n_thr);
+    SSD_REQUIRE(ap_out && ar_out && present_out, "ssd_coco_eval: null output array");
+    SSD_REQUIRE(n_det == 0 || (det_box && det_conf && det_cls && det_sample), "ssd_coco_eval: null detection array");
+    SSD_REQUIRE(n_gt == 0 || (gt_box && gt_cls && gt_sample && gt_area), "ssd_coco_eval: null ground-truth array");
+    SSD_REQUIRE(n_samples == 0 || sample_scale, "ssd_coco_eval: null sample_scale");
+    for (int i = 0; i < n_samples; ++i)
+        SSD_REQUIRE(sample_scale[i] > 0.0, "ssd_coco_eval: sample_scale[%d] = %g must be positive (W*H/1e6 of the image)", i, sample_scale[i]);
+    for (int g = 0; g < n_gt; ++g) {
+        SSD_REQUIRE(g == 0 || gt_sample[g] >= gt_sample[g - 1], "ssd_coco_eval: ground truth must be grouped by ascending sample id");
+        SSD_REQUIRE(gt_sample[g] >= 0 && gt_sample[g] < n_samples, "ssd_coco_eval: ground truth %d belongs to sample %d outside 0..%d", g, gt_sample[g], n_samples - 1);
+        SSD_REQUIRE(gt_cls[g] >= 0 && gt_cls[g] < num_classes, "ssd_coco_eval: ground truth %d has class id %d outside 0..%d", g, gt_cls[g], num_classes - 1);
+        SSD_REQUIRE(gt_area[g] >= 0.0, "ssd_coco_eval: gt_area[%d] = %g is negative", g, gt_area[g]);
+    }
+    for (int d = 0; d < n_det; ++d) {
+        SSD_REQUIRE(det_sample[d] >= 0 && det_sample[d] < n_samples, "ssd_coco_eval: detection %d belongs to sample %d outside 0..%d", d, det_sample[d], n_samples - 1);
+        SSD_REQUIRE(det_cls[d] >= 0 && det_cls[d] < num_classes, "ssd_coco_eval: detection %d has class id %d outside 0..%d", d, det_cls[d], num_classes - 1);
+    }
+    DeviceGuard dev_guard_(device);
+    const size_t nd = n_det ? n_det : 1, ng = n_gt ? n_gt : 1, ns = n_samples ? n_samples : 1;
+    DevBuf dbox(nd * 16), dconf(nd * 4), dcls(nd * 4), dsmp(nd * 4), gbox(ng * 32), gcls(ng * 4), gsmp(ng * 4), gflg(ng), garea(ng * 8),
+        scale(ns * 8);
+    if (n_det) {
+        HIP_OK(hipMemcpy(dbox.p, det_box, nd * 16, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(dconf.p, det_conf, nd * 4, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(dcls.p, det_cls, nd * 4, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(dsmp.p, det_sample, nd * 4, hipMemcpyHostToDevice));
+    }
+    if (n_gt) {
+        HIP_OK(hipMemcpy(gbox.p, gt_box, ng * 32, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(gcls.p, gt_cls, ng * 4, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(gsmp.p, gt_sample, ng * 4, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(garea.p, gt_area, ng * 8, hipMemcpyHostToDevice));
+    }
+    if (n_gt && gt_flags) HIP_OK(hipMemcpy(gflg.p, gt_flags, ng, hipMemcpyHostToDevice));
+    else HIP_OK(hipMemset(gflg.p, 0, ng));
+    if (n_samples) HIP_OK(hipMemcpy(scale.p, sample_scale, ns * 8, hipMemcpyHostToDevice));
+    COCOInput c{{n_det, n_gt, num_classes, dbox.as<float>(), dconf.as<float>(), dcls.as<int>(), dsmp.as<int>(), gbox.as<double>(),
+                 gcls.as<int>(), gsmp.as<int>(), gflg.as<unsigned char>()}, n_samples, garea.as<double>(), scale.as<double>(), nullptr};
+    coco_eval_run(c, gt_sample, n_thr, thresholds, ap_out, ar_out, present_out, nullptr);
+    API_END
+}
+
+int ssd_ap_add_dev_coco(ssd_ap_accumulator acc, int b, int out_cap, const int* count_dev, const float* conf_dev, const int* cls_dev,
+                        const int* box_dev, int n_gt, const double* gt_box, const int* gt_cls, const int* gt_image,
+                        const unsigned char* gt_flags, const double* gt_area, const double* sample_scale, void* stream) {
+    API_BEGIN
+    SSD_REQUIRE(sample_scale, "ssd_ap_add_dev_coco: null sample_scale");
+    ACC(acc).add_dev_coco(b, out_cap, count_dev, conf_dev, cls_dev, box_dev, n_gt, gt_box, gt_cls, gt_image, gt_flags, gt_area, sample_scale,
+                          (hipStream_t)stream);
+    API_END
+}
+
+int ssd_ap_add_host_coco(ssd_ap_accumulator acc, int n_det, const float* det_box, const float* det_conf, const int* det_cls,
+                         const int* det_sample, int n_samples, int n_gt, const double* gt_box, const int* gt_cls, const int* gt_sample,
+                         const unsigned char* gt_flags, const double* gt_area, const double* sample_scale) {
+    API_BEGIN
+    SSD_REQUIRE(sample_scale || n_samples == 0, "ssd_ap_add_host_coco: null sample_scale");
+    static const double none = 1.0;      // (no samples: the pass still counts as one with scales)
+    ACC(acc).add_host_coco(n_det, det_box, det_conf, det_cls, det_sample, n_samples, n_gt, gt_box, gt_cls, gt_sample, gt_flags, gt_area,
+                           sample_scale ? sample_scale : &none);
+    API_END
+}
+
+int ssd_ap_compute_coco(ssd_ap_accumulator acc, int n_thr, const double* thresholds, double* ap_out, double* ar_out, int* present_out,
+                        long long* n_det, long long* n_dropped) {
+    API_BEGIN
+    ACC(acc).compute_coco(n_thr, thresholds, ap_out, ar_out, present_out, n_det, n_dropped);
+    API_END
+}
+
+int ssd_ap_kernel_times(int enable, double* ms_out) {
+    API_BEGIN
+    ap_kernel_times(enable, ms_out);
+    API_END
+}
+
 // ------------------------------------------------------------------------------ model
 size_t ssd_arena_floats(const char* preset, int num_classes) {
     try {

@@ -7,6 +7,8 @@
 //   walk   one wave per (class, IoU threshold): ONE lane walks the sorted detections -- the greedy matching of a detection
 //          against the still-unmatched ground truth of its image is inherently sequential -- with matched bytes of its own, so
 //          the walks of a threshold list run side by side.
+// COCO's box evaluation (AP / AR over thresholds, area ranges and detection caps) reuses count and sort and has a walk of its
+// own, one wave per class with the combinations as lanes: see "COCO" below.
 // All arithmetic in IEEE f64 with explicit round-to-nearest operations: bit-exact with numpy.
 #include "metrics.h"
 #include "boxmath.h"
@@ -190,6 +192,36 @@ __global__ __launch_bounds__(64) void ap_walk_kernel(APArgs p) {
     p.ap[t * ncls + k] = ap;
 }
 
+// HIP events around the count, sort and walk stages of a computation, while ap_kernel_times has switched them on (measurements).
+// The switch and the last times are process-wide and unguarded: for a tool that computes from one thread.
+static bool g_stage_timing = false;
+static double g_stage_ms[3] = {0.0, 0.0, 0.0};
+
+struct StageTimer {
+    hipStream_t s;
+    bool on;
+    hipEvent_t ev[5] = {};
+    explicit StageTimer(hipStream_t stream) : s(stream), on(g_stage_timing) {
+        for (int i = 0; on && i < 5; ++i) HIP_OK(hipEventCreate(&ev[i]));
+    }
+    ~StageTimer() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    void mark(int i) { if (on) HIP_OK(hipEventRecord(ev[i], s)); }      // 0 | count | 1 ... 2 | sort | 3 | walk | 4
+    void finish() {                                                      // (after the stream has been waited for)
+        if (!on) return;
+        const int from[3] = {0, 2, 3};
+        for (int i = 0; i < 3; ++i) {
+            float ms = 0.f;
+            HIP_OK(hipEventElapsedTime(&ms, ev[from[i]], ev[from[i] + 1]));
+            g_stage_ms[i] = ms;
+        }
+    }
+};
+
+void ap_kernel_times(int enable, double* ms_out) {
+    if (ms_out) for (int i = 0; i < 3; ++i) ms_out[i] = g_stage_ms[i];
+    g_stage_timing = enable != 0;
+}
+
 static long long pow2_at_least(long long n) {
     long long n2 = 1;
     while (n2 < n) n2 <<= 1;
@@ -211,8 +243,11 @@ void average_precision_run(const APInput& in, int protocol, int n_thr, const dou
     const size_t ng = in.n_gt ? in.n_gt : 1;
     DevBuf counts((size_t)ncls * 12), offs((size_t)ncls * 16), matched(ng * n_thr), ap((size_t)n_thr * ncls * 8), present((size_t)ncls * 4);
     a.counts = counts.as<int>();
+    StageTimer timer(s);
+    timer.mark(0);
     hipLaunchKernelGGL(ap_count_kernel, dim3(ncls), dim3(256), 0, s, a);
     HIP_OK(hipGetLastError());
+    timer.mark(1);
     std::vector<int> h_counts((size_t)ncls * 3);
     HIP_OK(hipMemcpyAsync(h_counts.data(), counts.p, h_counts.size() * 4, hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
@@ -235,13 +270,264 @@ void average_precision_run(const APInput& in, int protocol, int n_thr, const dou
     a.tp_prec = tp_prec.as<double>();
     a.ap = ap.as<double>();
     a.present = present.as<int>();
+    timer.mark(2);
     hipLaunchKernelGGL(ap_sort_kernel, dim3(ncls), dim3(256), 0, s, a);
     HIP_OK(hipGetLastError());
+    timer.mark(3);
     hipLaunchKernelGGL(ap_walk_kernel, dim3(ncls, n_thr), dim3(64), 0, s, a);
     HIP_OK(hipGetLastError());
+    timer.mark(4);
     HIP_OK(hipMemcpyAsync(ap_out, ap.p, (size_t)n_thr * ncls * 8, hipMemcpyDeviceToHost, s));
     HIP_OK(hipMemcpyAsync(present_out, present.p, (size_t)ncls * 4, hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
+    timer.finish();
+}
+
+// ------------------------------------------------------------------------------------------------------------------- COCO
+// COCO's box evaluation (include/ssdvgg_hip.h, "COCO box evaluation").  ap_count_kernel and ap_sort_kernel as above; then
+//   npig   one workgroup per class: its unflagged ground truth inside each of the four area ranges.
+//   walk   one WAVE per class, one LANE per (IoU threshold, area range, maxDet) combination -- at most 10 x (4 + 2) = 60.  All
+//          combinations walk the same detections against the same boxes and differ only in their matched state, so the
+//          control flow is the wave's: the detection, its rank in its image (one counter per sample, kept by lane 0), its
+//          image's boxes of the class and their IoUs (each computed by ONE lane, shared through LDS) are common; a lane owns
+//          its matched bytes, its tp / fp counts and its true-positive precisions, and ends with the 101-point sampling.
+constexpr int COCO_MAX_DET = 100;
+
+struct COCOArgs {
+    COCOInput c;
+    int n_thr, n_combo;                // lanes in use: 6 * n_thr
+    double thr[AP_MAX_THRESHOLDS];     // min(t, 1 - 1e-10)
+    double tmin;                       // the smallest of them: a box below it matches in no lane
+    const int* counts;                 // ap_count_kernel's [3][ncls]
+    int* npig;                         // [4][ncls]
+    const long long* koff;             // [ncls] first key of the class
+    const long long* toff;             // [ncls] first true-positive row of the class (a row = 64 lanes)
+    const u64* keys;
+    unsigned char* matched;            // [n_gt][64], zeroed
+    unsigned char* rank;               // [ncls][n_samples], zeroed: detections of the (image, class) seen so far, up to 100
+    double* tp_prec;                   // [rows][64]
+    double* ap;                        // [4][n_thr][ncls]
+    double* ar;                        // [6][n_thr][ncls]
+    int* present;                      // [4][ncls]
+};
+
+__device__ static double coco_area_lo(int a) { return a == 2 ? 1024.0 : (a == 3 ? 9216.0 : 0.0); }
+__device__ static double coco_area_hi(int a) { return a == 1 ? 1024.0 : (a == 2 ? 9216.0 : 1e10); }
+
+__global__ __launch_bounds__(256) void coco_npig_kernel(COCOArgs p) {
+    __shared__ int s_w[4];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    int n[COCO_AREAS] = {0, 0, 0, 0};
+    for (int g = tid; g < p.c.in.n_gt; g += 256) {
+        if (p.c.in.gt_cls[g] != k || p.c.in.gt_flags[g]) continue;
+        const double area = p.c.gt_area[g];
+        for (int a = 0; a < COCO_AREAS; ++a) n[a] += !(area < coco_area_lo(a) || area > coco_area_hi(a));
+    }
+    for (int a = 0; a < COCO_AREAS; ++a) {
+        const int v = block_sum(n[a], s_w);
+        if (tid == 0) p.npig[a * p.c.in.ncls + k] = v;
+    }
+}
+
+__global__ __launch_bounds__(64) void coco_walk_kernel(COCOArgs p) {
+    __shared__ int s_g[64];                // the image's boxes of the class (a chunk of 64 rows of the image): row,
+    __shared__ double s_iou[64];           // IoU with the detection,
+    __shared__ unsigned char s_fl[64];     // bit a = ignored under area range a, bit 4 = crowd
+    const int k = blockIdx.x, lane = threadIdx.x, ncls = p.c.in.ncls;
+    const bool live = lane < p.n_combo;
+    const int grp = live ? lane / p.n_thr : 0, t = live ? lane % p.n_thr : 0;
+    const int a = grp < COCO_AREAS ? grp : 0, maxdet = grp == 4 ? 1 : (grp == 5 ? 10 : COCO_MAX_DET);
+    if (lane < COCO_AREAS) p.present[lane * ncls + k] = p.npig[lane * ncls + k] > 0;
+    const int npos = p.counts[2 * ncls + k], npig = p.npig[a * ncls + k];
+    double* ap_out = grp < COCO_AREAS ? p.ap + ((size_t)grp * p.n_thr + t) * ncls + k : nullptr;
+    double* ar_out = p.ar + ((size_t)grp * p.n_thr + t) * ncls + k;
+    if (npos == 0) {                       // (the wave's: no unflagged box, the class is present under no range; nothing was sorted)
+        if (live) { *ar_out = -1.0; if (ap_out) *ap_out = -1.0; }
+        return;
+    }
+    const int n = p.counts[k];
+    const u64* keys = p.keys + p.koff[k];
+    double* tpp = p.tp_prec + (size_t)p.toff[k] * 64 + lane;
+    unsigned char* rank = p.rank + (size_t)k * p.c.n_samples;
+    const float* det_box = p.c.in.det_box;
+    const double* gt_box = p.c.in.gt_box;
+    const double thr = p.thr[t], lo = coco_area_lo(a), hi = coco_area_hi(a);
+    double tp = 0.0, fp = 0.0;
+    int ntp = 0;
+    for (int i = 0; i < n; ++i) {
+        const int d = (int)(0xFFFFFFFFu - (unsigned)(keys[i] & 0xFFFFFFFFull));
+        const int s = p.c.in.det_sample[d];
+        int r = 0;
+        if (lane == 0) {                   // one lane reads and writes the counter: no cross-lane ordering is relied on
+            r = rank[s];
+            if (r < COCO_MAX_DET) rank[s] = (unsigned char)(r + 1);
+        }
+        r = __shfl(r, 0, 64);
+        if (r >= COCO_MAX_DET) continue;   // the 101st detection of an (image, class) takes no part
+        const double b0 = det_box[(size_t)d * 4], b1 = det_box[(size_t)d * 4 + 1], b2 = det_box[(size_t)d * 4 + 2], b3 = det_box[(size_t)d * 4 + 3];
+        const double aread = __dmul_rn(__dsub_rn(b1, b0), __dsub_rn(b3, b2));
+        const int g_lo = p.c.gt_first[s], g_hi = p.c.gt_first[s + 1];
+        const bool act = live && r < maxdet, single = g_hi - g_lo <= 64;
+        double best = thr;
+        int m = -1, cnt = 0;
+        bool m_ign = false;
+        // COCO walks the non-ignored boxes first, then the ignored ones (which boxes those are depends on the lane's area range):
+        // two passes over the boxes in arrival order, pass 1 skipped by a lane that holds a non-ignored match
+        for (int pass = 0; pass < 2; ++pass)
+            for (int c0 = g_lo; c0 < g_hi; c0 += 64) {
+                if (!(single && pass == 1)) {
+                    __syncthreads();
+                    const int g = c0 + lane;
+                    const bool mine = g < g_hi && p.c.in.gt_cls[g] == k;
+                    const u64 bal = __ballot(mine);
+                    cnt = __popcll(bal);
+                    if (mine) {
+                        const int pos = __popcll(bal & ((1ull << lane) - 1ull));
+                        const double a0 = gt_box[(size_t)g * 4], a1 = gt_box[(size_t)g * 4 + 1], a2 = gt_box[(size_t)g * 4 + 2], a3 = gt_box[(size_t)g * 4 + 3];
+                        const int fl = p.c.in.gt_flags[g];
+                        const double ga = p.c.gt_area[g];
+                        const double w = __dsub_rn(fmin(b1, a1), fmax(b0, a0)), h = __dsub_rn(fmin(b3, a3), fmax(b2, a2));
+                        double iou = 0.0;
+                        if (w > 0.0 && h > 0.0) {
+                            const double inter = __dmul_rn(w, h);
+                            const double uni = (fl & 2) ? aread
+                                                        : __dsub_rn(__dadd_rn(aread, __dmul_rn(__dsub_rn(a1, a0), __dsub_rn(a3, a2))), inter);
+                            iou = __ddiv_rn(inter, uni);
+                        }
+                        int bits = (fl & 2) ? 16 : 0;
+                        for (int q = 0; q < COCO_AREAS; ++q) bits |= (fl != 0 || ga < coco_area_lo(q) || ga > coco_area_hi(q)) ? (1 << q) : 0;
+                        s_g[pos] = g; s_iou[pos] = iou; s_fl[pos] = (unsigned char)bits;
+                    }
+                    __syncthreads();
+                }
+                for (int j = 0; j < cnt; ++j) {
+                    const double iou = s_iou[j];
+                    if (iou < p.tmin) continue;                           // (the wave's) below every lane's threshold
+                    const int gi = s_g[j], fl = s_fl[j];
+                    const bool ign = (fl >> a) & 1;
+                    if (!act || ign != (pass == 1) || (pass == 1 && m >= 0 && !m_ign)) continue;
+                    if (p.matched[(size_t)gi * 64 + lane] && !(fl & 16)) continue;      // taken, and not a crowd box
+                    if (iou < best) continue;
+                    best = iou; m = gi; m_ign = ign;                       // >=: among equal IoUs the last one wins
+                }
+            }
+        const double area = __dmul_rn(aread, p.c.sample_scale[s]);
+        // ignored: matched to an ignored box, or unmatched and outside the area range itself
+        const bool counted = act && !(m >= 0 ? m_ign : (area < lo || area > hi));
+        if (act && m >= 0) p.matched[(size_t)m * 64 + lane] = 1;
+        if (counted && m >= 0) {
+            tp += 1.0;
+            // only the true positives' precisions are kept (see ap_walk_kernel: the 2^-52 term keeps the quotient monotonic in fp)
+            if (ntp < npos) tpp[(size_t)ntp * 64] = __ddiv_rn(tp, __dadd_rn(__dadd_rn(fp, tp), 0x1p-52));
+            ++ntp;
+        } else if (counted) {
+            fp += 1.0;
+        }
+    }
+    if (!live) return;
+    if (npig == 0) { *ar_out = -1.0; if (ap_out) *ap_out = -1.0; return; }
+    *ar_out = __ddiv_rn(tp, (double)npig);
+    if (!ap_out) return;
+    if (ntp > npos) ntp = npos;
+    double mx = 0.0;
+    for (int i = ntp - 1; i >= 0; --i) {                                  // the precisions made non-increasing from the back
+        const double v = tpp[(size_t)i * 64];
+        if (v > mx) mx = v;
+        tpp[(size_t)i * 64] = mx;
+    }
+    // q_j: the precision at the first point with recall >= j * 0.01 -- the first true positive nn with nn / npig >= j * 0.01
+    double sum = 0.0;
+    int nn = 1;
+    for (int j = 0; j <= 100; ++j) {
+        const double rj = __dmul_rn((double)j, 0.01);
+        while (nn <= ntp && !(__ddiv_rn((double)nn, (double)npig) >= rj)) ++nn;
+        if (nn <= ntp) sum = __dadd_rn(sum, tpp[(size_t)(nn - 1) * 64]);
+    }
+    *ap_out = __ddiv_rn(sum, 101.0);
+}
+
+void coco_eval_run(const COCOInput& c, const int* gt_sample_host, int n_thr, const double* thresholds, double* ap_out, double* ar_out,
+                   int* present_out, hipStream_t s) {
+    const APInput& in = c.in;
+    require_num_classes(in.ncls);
+    SSD_REQUIRE(n_thr >= 1 && n_thr <= AP_MAX_THRESHOLDS && thresholds, "1..%d IoU thresholds (got %d)", AP_MAX_THRESHOLDS, n_thr);
+    SSD_REQUIRE(in.n_det >= 0 && in.n_gt >= 0 && c.n_samples >= 0, "bad sizes");
+    SSD_REQUIRE(ap_out && ar_out && present_out, "null output array");
+    SSD_REQUIRE(in.n_gt == 0 || gt_sample_host, "null ground truth");
+    const int ncls = in.ncls, ns = c.n_samples;
+    std::vector<int> first((size_t)ns + 1, 0);
+    for (int g = 0; g < in.n_gt; ++g) {
+        SSD_REQUIRE(gt_sample_host[g] >= 0 && gt_sample_host[g] < ns, "ground truth %d belongs to sample %d outside 0..%d", g, gt_sample_host[g], ns - 1);
+        SSD_REQUIRE(g == 0 || gt_sample_host[g] >= gt_sample_host[g - 1], "ground truth must be grouped by ascending sample id");
+        ++first[(size_t)gt_sample_host[g] + 1];
+    }
+    for (int i = 0; i < ns; ++i) first[i + 1] += first[i];
+    APArgs a{};
+    a.in = in;
+    a.protocol = AP_VOC07;                 // the sort's denominator: the unflagged boxes
+    COCOArgs q{};
+    q.c = c;
+    q.n_thr = n_thr;
+    q.n_combo = COCO_GROUPS * n_thr;
+    q.tmin = 1.0;
+    for (int t = 0; t < n_thr; ++t) {
+        q.thr[t] = std::min(thresholds[t], 1.0 - 1e-10);
+        q.tmin = std::min(q.tmin, q.thr[t]);
+    }
+    const size_t ng = in.n_gt ? in.n_gt : 1;
+    DevBuf counts((size_t)ncls * 12), npig((size_t)ncls * 16), offs((size_t)ncls * 16), gfirst(first.size() * 4), matched(ng * 64),
+        rank((size_t)ncls * ns), ap((size_t)COCO_AREAS * n_thr * ncls * 8), ar((size_t)COCO_GROUPS * n_thr * ncls * 8),
+        present((size_t)COCO_AREAS * ncls * 4);
+    HIP_OK(hipMemcpyAsync(gfirst.p, first.data(), first.size() * 4, hipMemcpyHostToDevice, s));
+    q.c.gt_first = gfirst.as<int>();
+    a.counts = counts.as<int>();
+    q.counts = a.counts;
+    q.npig = npig.as<int>();
+    StageTimer timer(s);
+    timer.mark(0);
+    hipLaunchKernelGGL(ap_count_kernel, dim3(ncls), dim3(256), 0, s, a);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(coco_npig_kernel, dim3(ncls), dim3(256), 0, s, q);
+    HIP_OK(hipGetLastError());
+    timer.mark(1);
+    std::vector<int> h_counts((size_t)ncls * 3);
+    HIP_OK(hipMemcpyAsync(h_counts.data(), counts.p, h_counts.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    std::vector<long long> h_offs((size_t)ncls * 2);
+    long long nkeys = 0, ntp = 0;
+    for (int k = 0; k < ncls; ++k) {
+        h_offs[k] = nkeys;
+        h_offs[ncls + k] = ntp;
+        nkeys += pow2_at_least(h_counts[k]);
+        ntp += h_counts[2 * ncls + k];      // a lane's true positives match distinct unflagged boxes of the class
+    }
+    DevBuf keys((size_t)nkeys * 8), tp_prec((size_t)ntp * 64 * 8);
+    HIP_OK(hipMemcpyAsync(offs.p, h_offs.data(), h_offs.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemsetAsync(matched.p, 0, ng * 64, s));
+    HIP_OK(hipMemsetAsync(rank.p, 0, (size_t)ncls * ns ? (size_t)ncls * ns : 1, s));
+    a.koff = offs.as<long long>();
+    a.keys = keys.as<u64>();
+    q.koff = a.koff;
+    q.toff = offs.as<long long>() + ncls;
+    q.keys = a.keys;
+    q.matched = matched.as<unsigned char>();
+    q.rank = rank.as<unsigned char>();
+    q.tp_prec = tp_prec.as<double>();
+    q.ap = ap.as<double>();
+    q.ar = ar.as<double>();
+    q.present = present.as<int>();
+    timer.mark(2);
+    hipLaunchKernelGGL(ap_sort_kernel, dim3(ncls), dim3(256), 0, s, a);
+    HIP_OK(hipGetLastError());
+    timer.mark(3);
+    hipLaunchKernelGGL(coco_walk_kernel, dim3(ncls), dim3(64), 0, s, q);
+    HIP_OK(hipGetLastError());
+    timer.mark(4);
+    HIP_OK(hipMemcpyAsync(ap_out, ap.p, (size_t)COCO_AREAS * n_thr * ncls * 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(ar_out, ar.p, (size_t)COCO_GROUPS * n_thr * ncls * 8, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(present_out, present.p, (size_t)COCO_AREAS * ncls * 4, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    timer.finish();
 }
 
 // ------------------------------------------------------------------------------------------------------------ accumulator
@@ -316,6 +602,8 @@ void APAccumulator::clear() {
     bound_ = 0;
     samples_ = 0;
     gt_box_.clear(); gt_cls_.clear(); gt_sample_.clear(); gt_flags_.clear();
+    gt_area_.clear(); sample_scale_.clear();
+    plain_samples_ = 0;
 }
 
 // Room for `extra` more detections behind the host's bound.  The old buffers are copied on `s`, behind the appends already
@@ -343,8 +631,15 @@ void APAccumulator::reserve(long long extra, hipStream_t s) {
     cap_ = cap;
 }
 
+// gt_area / sample_scale: of a _coco append (both or neither).  Such rows keep their flag byte (bit 1 = crowd; the VOC kernels
+// read nonzero as flagged); the rows of a plain append get area 0 and scale 1, which nothing reads: they bar compute_coco.
 void APAccumulator::push_gt(int n_gt, const double* gt_box, const int* gt_cls, const int* gt_sample, const unsigned char* gt_flags,
-                            int n_samples, const char* what) {
+                            int n_samples, const char* what, const double* gt_area, const double* sample_scale) {
+    const bool coco = sample_scale != nullptr;
+    SSD_REQUIRE(!coco || n_gt == 0 || gt_area, "%s: null gt_area", what);
+    for (int i = 0; coco && i < n_samples; ++i)
+        SSD_REQUIRE(sample_scale[i] > 0.0, "%s: sample_scale[%d] = %g must be positive (W*H/1e6 of the image)", what, i, sample_scale[i]);
+    for (int g = 0; coco && g < n_gt; ++g) SSD_REQUIRE(gt_area[g] >= 0.0, "%s: gt_area[%d] = %g is negative", what, g, gt_area[g]);
     SSD_REQUIRE(n_gt >= 0 && (n_gt == 0 || (gt_box && gt_cls && gt_sample)), "%s: null ground truth", what);
     SSD_REQUIRE(samples_ + n_samples < INT_MAX, "%s: too many samples", what);
     for (int g = 0; g < n_gt; ++g) {
@@ -358,18 +653,28 @@ void APAccumulator::push_gt(int n_gt, const double* gt_box, const int* gt_cls, c
         gt_box_.insert(gt_box_.end(), gt_box + (size_t)g * 4, gt_box + (size_t)g * 4 + 4);
         gt_cls_.push_back(gt_cls[g]);
         gt_sample_.push_back((int)samples_ + gt_sample[g]);
-        gt_flags_.push_back(gt_flags ? (gt_flags[g] ? 1 : 0) : 0);
+        gt_flags_.push_back(gt_flags ? (coco ? gt_flags[g] : (gt_flags[g] ? 1 : 0)) : 0);
+        gt_area_.push_back(coco ? gt_area[g] : 0.0);
     }
+    for (int i = 0; i < n_samples; ++i) sample_scale_.push_back(coco ? sample_scale[i] : 1.0);
+    if (!coco) plain_samples_ += n_samples;
 }
 
 void APAccumulator::add_dev(int b, int out_cap, const int* count_dev, const float* conf_dev, const int* cls_dev, const int* box_dev,
                             int n_gt, const double* gt_box, const int* gt_cls, const int* gt_image, const unsigned char* gt_flags,
                             hipStream_t s) {
-    SSD_REQUIRE(b >= 1 && out_cap >= 1 && (long long)b * out_cap < INT_MAX, "ssd_ap_add_dev: b >= 1, out_cap >= 1");
-    SSD_REQUIRE(count_dev && conf_dev && cls_dev && box_dev, "ssd_ap_add_dev: null detection array");
+    add_dev_coco(b, out_cap, count_dev, conf_dev, cls_dev, box_dev, n_gt, gt_box, gt_cls, gt_image, gt_flags, nullptr, nullptr, s);
+}
+
+void APAccumulator::add_dev_coco(int b, int out_cap, const int* count_dev, const float* conf_dev, const int* cls_dev, const int* box_dev,
+                                 int n_gt, const double* gt_box, const int* gt_cls, const int* gt_image, const unsigned char* gt_flags,
+                                 const double* gt_area, const double* sample_scale, hipStream_t s) {
+    const char* what = sample_scale ? "ssd_ap_add_dev_coco" : "ssd_ap_add_dev";
+    SSD_REQUIRE(b >= 1 && out_cap >= 1 && (long long)b * out_cap < INT_MAX, "%s: b >= 1, out_cap >= 1", what);
+    SSD_REQUIRE(count_dev && conf_dev && cls_dev && box_dev, "%s: null detection array", what);
     DeviceGuard g(device_);
-    reserve((long long)b * out_cap, s);
-    push_gt(n_gt, gt_box, gt_cls, gt_image, gt_flags, b, "ssd_ap_add_dev");
+    reserve((long long)b * out_cap, s);      // (before the ground truth is appended: a failed allocation leaves the accumulator as it was)
+    push_gt(n_gt, gt_box, gt_cls, gt_image, gt_flags, b, what, gt_area, sample_scale);
     APStore st{st_.box, st_.conf, st_.cls, st_.sample};
     hipLaunchKernelGGL(ap_append_kernel, dim3(1), dim3(256), 0, s, b, out_cap, count_dev, conf_dev, cls_dev, box_dev, ncls_, (int)samples_,
                        cap_, st, words_);
@@ -392,21 +697,28 @@ void APAccumulator::counts(long long* n_det, long long* n_dropped) {
 void APAccumulator::add_host(int n_det, const float* det_box, const float* det_conf, const int* det_cls, const int* det_sample,
                              int n_samples, int n_gt, const double* gt_box, const int* gt_cls, const int* gt_sample,
                              const unsigned char* gt_flags) {
-    SSD_REQUIRE(n_det >= 0 && n_samples >= 0 && (n_det == 0 || (det_box && det_conf && det_cls && det_sample)), "ssd_ap_add_host: bad detections");
+    add_host_coco(n_det, det_box, det_conf, det_cls, det_sample, n_samples, n_gt, gt_box, gt_cls, gt_sample, gt_flags, nullptr, nullptr);
+}
+
+void APAccumulator::add_host_coco(int n_det, const float* det_box, const float* det_conf, const int* det_cls, const int* det_sample,
+                                  int n_samples, int n_gt, const double* gt_box, const int* gt_cls, const int* gt_sample,
+                                  const unsigned char* gt_flags, const double* gt_area, const double* sample_scale) {
+    const char* what = sample_scale ? "ssd_ap_add_host_coco" : "ssd_ap_add_host";
+    SSD_REQUIRE(n_det >= 0 && n_samples >= 0 && (n_det == 0 || (det_box && det_conf && det_cls && det_sample)), "%s: bad detections", what);
     DeviceGuard g(device_);
     long long end, dropped;
     counts(&end, &dropped);
     std::vector<float> hb, hc;
     std::vector<int> hk, hs;
     for (int d = 0; d < n_det; ++d) {
-        SSD_REQUIRE(det_sample[d] >= 0 && det_sample[d] < n_samples, "ssd_ap_add_host: detection %d belongs to sample %d outside 0..%d", d, det_sample[d], n_samples - 1);
+        SSD_REQUIRE(det_sample[d] >= 0 && det_sample[d] < n_samples, "%s: detection %d belongs to sample %d outside 0..%d", what, d, det_sample[d], n_samples - 1);
         if (det_cls[d] < 0 || det_cls[d] >= ncls_) { ++dropped; continue; }
         hb.insert(hb.end(), det_box + (size_t)d * 4, det_box + (size_t)d * 4 + 4);
         hc.push_back(det_conf[d]); hk.push_back(det_cls[d]); hs.push_back((int)samples_ + det_sample[d]);
     }
     const long long n = (long long)hk.size();
-    push_gt(n_gt, gt_box, gt_cls, gt_sample, gt_flags, n_samples, "ssd_ap_add_host");
-    reserve(n, last_);
+    reserve(n, last_);      // (before the ground truth is appended, as in add_dev_coco)
+    push_gt(n_gt, gt_box, gt_cls, gt_sample, gt_flags, n_samples, what, gt_area, sample_scale);
     HIP_OK(hipStreamSynchronize(last_));
     if (n) {
         HIP_OK(hipMemcpy(st_.box + end * 4, hb.data(), (size_t)n * 16, hipMemcpyHostToDevice));
@@ -450,6 +762,31 @@ void APAccumulator::compute(int protocol, int n_thr, const double* minoverlaps, 
     APInput in{(int)end, (int)ng, ncls_, st_.box, st_.conf, st_.cls, st_.sample, gbox.as<double>(), gcls.as<int>(), gsmp.as<int>(),
                gflg.as<unsigned char>()};
     average_precision_run(in, protocol, n_thr, minoverlaps, ap_out, present_out, last_);
+}
+
+void APAccumulator::compute_coco(int n_thr, const double* thresholds, double* ap_out, double* ar_out, int* present_out, long long* n_det,
+                                 long long* n_dropped) {
+    SSD_REQUIRE(plain_samples_ == 0, "ssd_ap_compute_coco: %lld of the accumulator's %lld samples were added without areas and image "
+                "scales (ssd_ap_add_dev / ssd_ap_add_host); use the _coco calls for every pass", plain_samples_, samples_);
+    SSD_REQUIRE(n_thr >= 1 && n_thr <= AP_MAX_THRESHOLDS && thresholds, "1..%d IoU thresholds (got %d)", AP_MAX_THRESHOLDS, n_thr);
+    SSD_REQUIRE(ap_out && ar_out && present_out, "ssd_ap_compute_coco: null output array");
+    DeviceGuard g(device_);
+    long long end;
+    counts(&end, n_dropped);
+    if (n_det) *n_det = end;
+    const size_t ng = gt_cls_.size(), ns = sample_scale_.size();
+    DevBuf gbox(ng * 32), gcls(ng * 4), gsmp(ng * 4), gflg(ng), garea(ng * 8), scale(ns * 8);
+    if (ng) {
+        HIP_OK(hipMemcpy(gbox.p, gt_box_.data(), ng * 32, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(gcls.p, gt_cls_.data(), ng * 4, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(gsmp.p, gt_sample_.data(), ng * 4, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(gflg.p, gt_flags_.data(), ng, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(garea.p, gt_area_.data(), ng * 8, hipMemcpyHostToDevice));
+    }
+    if (ns) HIP_OK(hipMemcpy(scale.p, sample_scale_.data(), ns * 8, hipMemcpyHostToDevice));
+    COCOInput c{{(int)end, (int)ng, ncls_, st_.box, st_.conf, st_.cls, st_.sample, gbox.as<double>(), gcls.as<int>(), gsmp.as<int>(),
+                 gflg.as<unsigned char>()}, (int)ns, garea.as<double>(), scale.as<double>(), nullptr};
+    coco_eval_run(c, gt_sample_.data(), n_thr, thresholds, ap_out, ar_out, present_out, last_);
 }
 
 }  // namespace ssd

@@ -12,17 +12,19 @@ detections on the original-size image on the GPU, from the source bytes the resi
 device-visible output (annotate.py), and writes it to <output-dir>/<basename>.
 """
 import argparse
+import json
 import os
 import sys
 
 import numpy as np
 
 from .average_precision import APCalculator, DeviceAPCalculator, APs2mAP, add_ap_arguments
+from .coco_eval import COCOEvaluator, DeviceCOCOEvaluator, aps_of, format_summary, summarize
 from .ssdvgg import SSDVGG, Session
 from .ssdutils import get_preset_by_name, boxes_from_detection
 from .training_data import default_class_names
 from .pascal_summary import PascalSummary
-from .utils import Size, Sample, Box, Point, str2bool, load_data_source, default_colors
+from .utils import Size, Sample, Box, Point, str2bool, load_data_source, default_colors, prop2abs
 
 
 def _has_jpeg_candidates(files):
@@ -172,6 +174,30 @@ def synthetic_ground_truth(n, boxes_per_image, num_classes, lid2name, size):
     return samples
 
 
+def coco_image_id(source, filename):
+    """source.image_ids is keyed by the annotation's file_name: usually the path's last component, but it may carry a directory"""
+    name = os.path.basename(filename)
+    if name in source.image_ids:
+        return source.image_ids[name]
+    path = filename.replace(os.sep, '/')
+    for key, image_id in source.image_ids.items():
+        if path.endswith('/' + key):
+            return image_id
+    raise RuntimeError('--coco-results: the data source has no image id for ' + filename)
+
+
+def coco_result_records(source, sample, boxes):
+    """The records of one image's detections in COCO's results format: bbox [x, y, w, h] in pixels from the 1000-grid box."""
+    image_id = coco_image_id(source, sample.filename)
+    sx, sy = sample.imgsize.w / 1000.0, sample.imgsize.h / 1000.0
+    out = []
+    for conf, box in boxes:
+        xmin, xmax, ymin, ymax = prop2abs(box.center, box.size, Size(1000, 1000))
+        out.append(dict(image_id=image_id, category_id=source.category_ids[box.labelid],
+                        bbox=[xmin * sx, ymin * sy, (xmax - xmin) * sx, (ymax - ymin) * sy], score=float(conf)))
+    return out
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description='SSD inference')
     parser.add_argument('files', type=str, nargs='*', help='image files (anything Pillow decodes, or .npy arrays)')
@@ -200,6 +226,9 @@ def main(argv=None):
                              'activations and filters (no calibration; fc6 stays on bf16)')
     add_fp8_arguments(parser)
     add_ap_arguments(parser)
+    parser.add_argument('--coco-results', default=None, metavar='FILE',
+                        help="write the run's detections as a COCO results JSON (image_id, category_id, bbox [x, y, w, h] in pixels, score); "
+                             'needs a data source that keeps the annotation file\'s ids (coco)')
     parser.add_argument('--decoder', default='gpu', choices=['pillow', 'gpu'],
                         help='gpu: baseline JPEGs are decoded on the GPU, other files as with pillow (same pixels); pillow: every file is decoded on the host')
     parser.add_argument('--decoder-entropy', default='host', choices=['host', 'gpu'],
@@ -265,6 +294,8 @@ def main(argv=None):
         except (ImportError, AttributeError, RuntimeError, OSError) as e:
             print('[!] Unable to load data source:', str(e)); return 1
         compute_stats = bool(args.compute_stats)
+    if args.coco_results and not (hasattr(source, 'image_ids') and hasattr(source, 'category_ids')):
+        print('[!] --coco-results needs a data source with image_ids and category_ids (--data-source coco)'); return 1
 
     with Session(0) as sess:
         print('[i] Creating the model...')
@@ -308,10 +339,14 @@ def main(argv=None):
         print('[i] Image size:        ', size)
         print('[i] Number of files:   ', len(files))
         ap_dev = compute_stats and args.ap_on == 'gpu'
+        coco = args.ap_protocol == 'coco'      # COCO's box AP / AR: classes of their own, the image sizes go along
         if ap_dev:
-            ap_calc = DeviceAPCalculator(sess.device, num_classes, args.ap_protocol)
+            ap_calc = DeviceCOCOEvaluator(sess.device, num_classes) if coco else DeviceAPCalculator(sess.device, num_classes, args.ap_protocol)
+        elif compute_stats:
+            ap_calc = COCOEvaluator(num_classes=num_classes) if coco else APCalculator(protocol=args.ap_protocol)
         else:
-            ap_calc = APCalculator(protocol=args.ap_protocol) if compute_stats else None
+            ap_calc = None
+        coco_records = [] if args.coco_results else None
         if args.ap_protocol != 'reference' or args.ap_on != 'host':
             print('[i] AP protocol:       ', args.ap_protocol)
             print('[i] AP detections on:  ', args.ap_on)
@@ -338,16 +373,29 @@ def main(argv=None):
             elif drawn is not None:
                 for i, img in enumerate(drawn.get()):
                     write_image(os.path.join(args.output_dir, os.path.basename(name_of(idxs[i]))), img)
-            if ap_dev and pascal_summary is None:      # the accumulator has the detections: nothing needs them on the host
+            if ap_dev and pascal_summary is None and coco_records is None:      # the accumulator has the detections: nothing needs them on the host
                 return
             for i, det in enumerate(ticket.get()):
                 # decode_boxes(enc, anchors, threshold, lid2name, None); suppress_overlaps(boxes)[:200]  (infer.py:233-235)
                 boxes = boxes_from_detection(det, lid2name)
                 total += len(boxes)
                 if compute_stats and not ap_dev:                                             # infer.py:259-260
-                    ap_calc.add_detections(samples[idxs[i]].boxes, boxes)
+                    if coco:
+                        ap_calc.add_detections(samples[idxs[i]].boxes, boxes, samples[idxs[i]].imgsize)
+                    else:
+                        ap_calc.add_detections(samples[idxs[i]].boxes, boxes)
+                if coco_records is not None:
+                    coco_records.extend(coco_result_records(source, samples[idxs[i]], boxes))
                 if pascal_summary is not None:                                               # infer.py:263-264
                     pascal_summary.add_detections(name_of(idxs[i]), boxes, img_size=sizes[i])
+
+        def add_pass(ticket, idxs):
+            """--ap-on gpu: the pass just launched goes to the accumulator; COCO's evaluator takes the image sizes too"""
+            gts = [samples[i].boxes for i in idxs]
+            if coco:
+                ap_calc.add_pass(ticket, gts, [samples[i].imgsize for i in idxs])
+            else:
+                ap_calc.add_pass(ticket, gts)
 
         pending = None
         if args.tile:       # (DESIGN.md 22) windows of the source picture through the net, their boxes merged on the GPU
@@ -359,7 +407,7 @@ def main(argv=None):
                     tiling.fp8_ready(detector, (packed, offs, shapes), args.fp8_calibration, args.fp8_calibrate_images)
                 ticket = detector.launch(packed, offs, shapes)
                 if ap_dev:
-                    ap_calc.add_pass(ticket, [samples[i].boxes for i in idxs])
+                    add_pass(ticket, idxs)
                 if writer is not None:
                     drawn = writer.launch(detector, (packed, offs, shapes), style,
                                           [os.path.join(args.output_dir, os.path.basename(name_of(i))) for i in idxs])
@@ -374,7 +422,7 @@ def main(argv=None):
             net.infer_dev(x)                                                                 # infer.py:225-227
             ticket = net.detect_last_launch(x.shape[0], args.threshold, None, 200)
             if ap_dev:
-                ap_calc.add_pass(ticket, [samples[i].boxes for i in idxs])
+                add_pass(ticket, idxs)
             if writer is not None:
                 drawn = writer.launch(net, batch[3], style, [os.path.join(args.output_dir, os.path.basename(name_of(i))) for i in idxs])
             else:
@@ -392,10 +440,20 @@ def main(argv=None):
             style.close()
 
         if compute_stats:                                                                    # infer.py:269-273
-            aps = ap_calc.compute_aps()
+            if coco:      # (one evaluation for the table and the twelve numbers)
+                result = ap_calc.compute()
+                aps, summary = aps_of(result), summarize(result)
+            else:
+                aps = ap_calc.compute_aps()
             for k, v in aps.items():
                 print('[i] AP [{0}]: {1:.3f}'.format(k, v))
             print('[i] mAP: {0:.3f}'.format(APs2mAP(aps)))
+            if coco:
+                print(format_summary(summary, ap_calc.thresholds))
+        if coco_records is not None:
+            with open(args.coco_results, 'w') as f:
+                json.dump(coco_records, f)
+            print('[i] COCO results:      ', args.coco_results, '(%d detections)' % len(coco_records))
         if pascal_summary is not None:                                                       # infer.py:278-279
             pascal_summary.write_summary(args.output_dir)
         if ap_dev:

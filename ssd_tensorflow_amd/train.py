@@ -23,6 +23,7 @@ import numpy as np
 
 from . import _lib, parallel
 from .average_precision import APCalculator, DeviceAPCalculator, APs2mAP, add_ap_arguments
+from .coco_eval import COCOEvaluator, DeviceCOCOEvaluator, aps_of, format_summary, summarize
 from .ssdutils import boxes_from_detection
 from .ssdvgg import SSDVGG, Session, LearningRate
 from .summaries import SummaryWriter, LossSummary, PrecisionSummary, ImageSummary
@@ -72,10 +73,19 @@ class StepLoop:
             return
         if drawn is not None:
             image_samples.add(drawn.get())
-        if isinstance(calc, DeviceAPCalculator):      # (run_epoch has handed it the pass where it launched the decode)
+        if isinstance(calc, (DeviceAPCalculator, DeviceCOCOEvaluator)):      # (run_epoch has handed it the pass where it launched the decode)
             return
         for gt, det in zip(gt_boxes, dets.get()):
-            calc.add_detections(gt, boxes_from_detection(det, self.td.lid2name))
+            if isinstance(calc, COCOEvaluator):
+                calc.add_detections(self.coco_gt([gt])[0], boxes_from_detection(det, self.td.lid2name), self.net.preset.image_size)
+            else:
+                calc.add_detections(gt, boxes_from_detection(det, self.td.lid2name))
+
+    @staticmethod
+    def coco_gt(gt_boxes):
+        """--ap-protocol coco: the epochs are evaluated on the resized network input, so every image has the network's size and a
+        box's area is its own w*h there, not the annotation's (which is in the source picture's pixels)"""
+        return [[b._replace(area=None) if getattr(b, 'area', None) is not None else b for b in gt] for gt in gt_boxes]
 
     def annotate_launch(self, x, n, image_samples):
         """train.py:273-281, 298-306: the first three samples of the epoch that have a decode, drawn on the GPU behind that
@@ -123,6 +133,8 @@ class StepLoop:
             launched = net.detect_last_launch(n, 0.5, 200, None)
             if isinstance(ap_calc, DeviceAPCalculator):
                 ap_calc.add_pass(launched, gt_boxes)
+            elif isinstance(ap_calc, DeviceCOCOEvaluator):
+                ap_calc.add_pass(launched, self.coco_gt(gt_boxes), [net.preset.image_size] * n)
             drawn = self.annotate_launch(x, n, image_samples)
             if pending_det:
                 self.collect(*pending_det, ap_calc, image_samples)
@@ -247,7 +259,12 @@ def main(argv=None):
         net.set_stream(torch.cuda.current_stream().cuda_stream)
 
         writer = SummaryWriter(os.path.join(args.tensorboard_dir, os.path.basename(os.path.normpath(args.name)))) if rank == 0 else None
-        if args.ap_on == 'gpu':       # the detections stay on the GPU between the decode and the AP kernels
+        if args.ap_protocol == 'coco':      # COCO's box AP / AR; the per-class values are AP averaged over 0.50:0.95
+            if args.ap_on == 'gpu':
+                training_ap_calc, validation_ap_calc = DeviceCOCOEvaluator(local, td.num_classes), DeviceCOCOEvaluator(local, td.num_classes)
+            else:
+                training_ap_calc, validation_ap_calc = COCOEvaluator(num_classes=td.num_classes), COCOEvaluator(num_classes=td.num_classes)
+        elif args.ap_on == 'gpu':       # the detections stay on the GPU between the decode and the AP kernels
             training_ap_calc = DeviceAPCalculator(local, td.num_classes, args.ap_protocol)
             validation_ap_calc = DeviceAPCalculator(local, td.num_classes, args.ap_protocol)
         else:
@@ -263,22 +280,34 @@ def main(argv=None):
 
         loop = StepLoop(net, sess, td, args.batch_size, args.num_workers, world, rank, bucket, args.allreduce_dtype)
 
-        def gathered_aps(calc):
+        def gathered_aps(calc, with_summary=False):
             """{label: AP} over the WHOLE sample (train.py:317-323): data parallel, every rank's detections and ground
             truth are gathered to rank 0, which computes; the other ranks get {}."""
+            def aps(c):
+                if not isinstance(c, (COCOEvaluator, DeviceCOCOEvaluator)):
+                    return c.compute_aps()
+                result = c.compute()      # one evaluation for the per-class values and the twelve numbers
+                if with_summary:
+                    say(format_summary(summarize(result), c.thresholds))
+                return aps_of(result)
+
             if world <= 1:
-                return calc.compute_aps()
+                return aps(calc)
             states = [None] * world if rank == 0 else None
             torch.distributed.gather_object(calc.state(), states, dst=0)
             if rank != 0:
                 return {}
-            if isinstance(calc, DeviceAPCalculator):
+            if isinstance(calc, DeviceCOCOEvaluator):
+                merged = DeviceCOCOEvaluator(calc.device, calc.num_classes, calc.thresholds)
+            elif isinstance(calc, COCOEvaluator):
+                merged = COCOEvaluator(calc.thresholds, calc.num_classes)
+            elif isinstance(calc, DeviceAPCalculator):
                 merged = DeviceAPCalculator(calc.device, calc.num_classes, calc.protocol, calc.minoverlap)
             else:
                 merged = APCalculator(calc.minoverlap, calc.protocol)
             for st in states:
                 merged.merge(st)
-            return merged.compute_aps()
+            return aps(merged)
 
         say('[i] Training...')
         for e in range(start_epoch, args.epochs):
@@ -295,7 +324,7 @@ def main(argv=None):
             # VOC07 11-point AP on the GPU, over all ranks' samples
             APs = gathered_aps(training_ap_calc); mAP = APs2mAP(APs)
             training_ap.push(e + 1, mAP, APs)
-            vAPs = gathered_aps(validation_ap_calc); vmAP = APs2mAP(vAPs)
+            vAPs = gathered_aps(validation_ap_calc, e > 0); vmAP = APs2mAP(vAPs)      # (coco: the validation's twelve numbers too)
             validation_ap.push(e + 1, vmAP, vAPs)
             if e > 0:
                 say('[i] mAP  {:>2}/{}  training {:.4f}  validation {:.4f}'.format(e + 1, args.epochs, mAP, vmAP))

@@ -16,27 +16,43 @@ Score = namedtuple('Score', ['idx', 'score'])
 
 
 class FlaggedBox(Box):
-    """A Box that carries VOC's <difficult> flag.  It IS the reference's 4-field tuple -- it compares, hashes, unpacks and
-    indexes like Box, so every consumer of Box takes it -- with one attribute more, which pickling keeps."""
+    """A Box that carries VOC's <difficult> flag, and COCO's `iscrowd` and annotation `area` (pixels^2; None: the box's own
+    w*h).  It IS the reference's 4-field tuple -- it compares, hashes, unpacks and indexes like Box, so every consumer of Box
+    takes it -- with attributes more, which pickling keeps.  A crowd box is difficult as well: the VOC protocols ignore it."""
 
-    def __new__(cls, label, labelid, center, size, difficult=False):
+    def __new__(cls, label, labelid, center, size, difficult=False, *, crowd=False, area=None):
         self = super().__new__(cls, label, labelid, center, size)
-        self.difficult = bool(difficult)
+        self.crowd = bool(crowd)
+        self.difficult = bool(difficult) or self.crowd
+        self.area = None if area is None else float(area)
         return self
 
     def __reduce__(self):
-        return FlaggedBox, (self.label, self.labelid, self.center, self.size, self.difficult)
+        if not self.crowd and self.area is None:
+            return FlaggedBox, (self.label, self.labelid, self.center, self.size, self.difficult)
+        return _flagged_box, (self.label, self.labelid, self.center, self.size, self.difficult, self.crowd, self.area)
 
     def _replace(self, **kwargs):
         difficult = kwargs.pop('difficult', self.difficult)
-        return FlaggedBox(*Box._replace(Box(*self), **kwargs), difficult=difficult)
+        crowd = kwargs.pop('crowd', self.crowd)
+        area = kwargs.pop('area', self.area)
+        return FlaggedBox(*Box._replace(Box(*self), **kwargs), difficult=difficult, crowd=crowd, area=area)
 
     def __repr__(self):
-        return Box.__repr__(self)[:-1] + ', difficult=%r)' % self.difficult
+        more = (', crowd=%r' % self.crowd if self.crowd else '') + (', area=%r' % self.area if self.area is not None else '')
+        return Box.__repr__(self)[:-1] + ', difficult=%r%s)' % (self.difficult, more)
+
+
+def _flagged_box(label, labelid, center, size, difficult, crowd, area):
+    """(pickle's constructor of a FlaggedBox with keyword attributes)"""
+    return FlaggedBox(label, labelid, center, size, difficult, crowd=crowd, area=area)
 
 
 def box_like(box, center, size):
-    """`box` with another centre and size: a transform's result keeps the label and the difficult flag."""
+    """`box` with another centre and size: a transform's result keeps the label, the flags and the annotation's area."""
+    crowd, area = getattr(box, 'crowd', False), getattr(box, 'area', None)
+    if crowd or area is not None:
+        return FlaggedBox(box.label, box.labelid, center, size, box.difficult, crowd=crowd, area=area)
     if getattr(box, 'difficult', False):
         return FlaggedBox(box.label, box.labelid, center, size, True)
     return Box(box.label, box.labelid, center, size)
