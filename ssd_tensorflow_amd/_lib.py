@@ -55,6 +55,9 @@ SIGNATURES = {
     'ssd_decode_nms': (i32, [cstr, i32, i32, vp, i32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     'ssd_decode_nms_ws_bytes': (sz, [cstr, i32]),
     'ssd_decode_nms_dev': (i32, [cstr, i32, vp, vp, i32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    'ssd_detection_output_ws_bytes': (sz, [cstr, i32, i32, i32]),
+    'ssd_detection_output_dev': (i32, [cstr, i32, vp, vp, i32, f32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'ssd_detection_output': (i32, [cstr, i32, i32, vp, i32, f32, i32, i32, i32, vp, vp, vp, vp, vp]),
     'ssd_anchors_dev': (i32, [cstr, vp, vp, vp]),
     'ssd_average_precision': (i32, [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, C.c_double, vp, vp]),
     'ssd_average_precision_ex': (i32, [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
@@ -143,6 +146,7 @@ SIGNATURES = {
     'ssd_arenas': (i32, [handle, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]),
     'ssd_detect_last': (i32, [handle, i32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     'ssd_detect_last_dev': (i32, [handle, i32, f32, i32, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    'ssd_detect_last_all_dev': (i32, [handle, i32, f32, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
     'ssd_detect_fetch': (i32, [handle, i32, vp, vp, vp, vp, vp]),
     'ssd_detect_host': (i32, [handle, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), p_i32, p_i32]),
     'ssd_nms_boxes': (i32, [i32, i32, vp, vp, vp, C.c_double, vp, p_i32]),

@@ -314,6 +314,55 @@ int ssd_decode_nms(const char* preset, int num_classes, int device, const float*
     API_END
 }
 
+size_t ssd_detection_output_ws_bytes(const char* preset, int num_classes, int b, int nms_top_k) {
+    try {
+        detection_output_check(get_preset(preset).num_anchors, num_classes, b, 0.f, nms_top_k, 1, 1);
+        return detection_output_ws_bytes(b, num_classes, nms_top_k);
+    } catch (const std::exception& e) {
+        ssd::set_error("%s", e.what());
+        return 0;
+    }
+}
+
+int ssd_detection_output_dev(const char* preset, int num_classes, const double* anchors_dev, const float* pred_dev, int b,
+                             float conf_thr, int nms_top_k, int keep_top_k, int out_cap, int* count_dev, float* conf_dev,
+                             int* cls_dev, int* idx_dev, int* box_dev, void* ws_dev, size_t ws_bytes, void* stream) {
+    API_BEGIN
+    const Preset& p = get_preset(preset);
+    DetectOut o{count_dev, conf_dev, cls_dev, idx_dev, box_dev};
+    detection_output(p.num_anchors, num_classes, anchors_dev, pred_dev, b, conf_thr, nms_top_k, keep_top_k, out_cap, o, ws_dev,
+                     ws_bytes, (hipStream_t)stream);
+    API_END
+}
+
+int ssd_detection_output(const char* preset, int num_classes, int device, const float* pred, int b, float conf_thr,
+                         int nms_top_k, int keep_top_k, int out_cap, int* count, float* conf, int* cls, int* idx, int* box) {
+    API_BEGIN
+    const Preset& p = get_preset(preset);
+    detection_output_check(p.num_anchors, num_classes, b, conf_thr, nms_top_k, keep_top_k, out_cap);
+    SSD_REQUIRE(pred && count && conf && cls && idx && box, "null argument");
+    DeviceGuard dev_guard_(device);
+    const size_t A = p.num_anchors, nv = num_classes + 5, n = (size_t)b * out_cap;
+    const size_t wsb = detection_output_ws_bytes(b, num_classes, nms_top_k);
+    DevBuf anc(A * 4 * sizeof(double)), dpred((size_t)b * A * nv * sizeof(float)), ws(wsb);
+    DevBuf dcount((size_t)b * 4), dconf(n * 4), dcls(n * 4), didx(n * 4), dbox(n * 16);
+    anchors_device(p, anc.as<double>(), nullptr, nullptr);
+    HIP_OK(hipMemcpy(dpred.p, pred, (size_t)b * A * nv * sizeof(float), hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(dconf.p, 0, n * 4));       // rows past an image's count read as zero
+    HIP_OK(hipMemset(dcls.p, 0, n * 4));
+    HIP_OK(hipMemset(didx.p, 0, n * 4));
+    HIP_OK(hipMemset(dbox.p, 0, n * 16));
+    DetectOut o{dcount.as<int>(), dconf.as<float>(), dcls.as<int>(), didx.as<int>(), dbox.as<int>()};
+    detection_output((int)A, num_classes, anc.as<double>(), dpred.as<float>(), b, conf_thr, nms_top_k, keep_top_k, out_cap, o, ws.p, wsb,
+                     nullptr);
+    HIP_OK(hipMemcpy(count, dcount.p, (size_t)b * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(conf, dconf.p, n * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(cls, dcls.p, n * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(idx, didx.p, n * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(box, dbox.p, n * 16, hipMemcpyDeviceToHost));
+    API_END
+}
+
 int ssd_nms_boxes(int device, int n, const int* box_abs, const float* conf, const int* group, double iou_thr, int* keep_out,
                   int* n_keep) {
     API_BEGIN
@@ -1151,6 +1200,19 @@ int ssd_detect_last_dev(ssd_handle h, int b, float conf_thr, int cap, int max_ou
     API_BEGIN_NET(h)
     DetectOut d{};
     n.detect_last_dev(b, conf_thr, cap, max_out, out_cap, nms != 0, &d);
+    if (count_dev) *count_dev = d.count;
+    if (conf_dev) *conf_dev = d.conf;
+    if (cls_dev) *cls_dev = d.cls;
+    if (idx_dev) *idx_dev = d.idx;
+    if (box_dev) *box_dev = d.box;
+    API_END
+}
+
+int ssd_detect_last_all_dev(ssd_handle h, int b, float conf_thr, int nms_top_k, int keep_top_k, int out_cap, int** count_dev,
+                            float** conf_dev, int** cls_dev, int** idx_dev, int** box_dev) {
+    API_BEGIN_NET(h)
+    DetectOut d{};
+    n.detect_last_all_dev(b, conf_thr, nms_top_k, keep_top_k, out_cap, &d);
     if (count_dev) *count_dev = d.count;
     if (conf_dev) *conf_dev = d.conf;
     if (cls_dev) *cls_dev = d.cls;

@@ -53,6 +53,19 @@ size_t detect_ws_bytes(int B, int A);
 void detect(int A, int num_classes, const double* anchors, const float* pred, int B, float conf_thr, int cap,
             int max_out, int out_cap, bool nms, const DetectOut& out, void* ws, hipStream_t s);
 
+// DetectionOutput: every (anchor, foreground class) pair with !(conf < conf_thr) is a candidate; per class the
+// best nms_top_k (confidence descending, ties by lower anchor), greedy NMS per class at the reference's 0.45, then the best
+// keep_top_k of the image by (confidence descending, anchor ascending, class ascending), written in THAT order (global
+// confidence order, not detect()'s class groups).  out.count may exceed out_cap; rows past out_cap are clipped.
+// nms_top_k, keep_top_k in 1..1024; conf_thr finite and >= 0.  Negative zero and NaN in the class columns are outside the
+// contract (inputs are softmax outputs).  pred is not modified.  Asynchronous on s, no host wait, deterministic; every limit
+// (and ws_bytes) is checked before anything is enqueued.
+//   ws bytes = align256(4 b C) + align256(8 b C nms_top_k) + 16 b C nms_top_k
+size_t detection_output_ws_bytes(int B, int num_classes, int nms_top_k);
+void detection_output_check(int A, int num_classes, int B, float conf_thr, int nms_top_k, int keep_top_k, int out_cap);      // the limits alone
+void detection_output(int A, int num_classes, const double* anchors, const float* pred, int B, float conf_thr, int nms_top_k,
+                      int keep_top_k, int out_cap, const DetectOut& out, void* ws, size_t ws_bytes, hipStream_t s);
+
 // non_maximum_suppression / suppress_overlaps on an arbitrary list: boxes [n][4] i32 (xmin,xmax,ymin,ymax),
 // conf [n], group [n] (0..ngroups-1); keep [n+1]: keep[0] = count, then the selected input indices in output order.
 size_t nms_boxes_ws_bytes(int n, int ngroups);

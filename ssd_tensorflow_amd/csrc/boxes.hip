@@ -1459,4 +1459,286 @@ void nms_boxes_device(int n, int ngroups, const int* boxes, const float* conf, c
     HIP_OK(hipGetLastError());
 }
 
+// =================================================================================
+// DetectionOutput: every (anchor, class) pair that reaches the threshold is a candidate
+// =================================================================================
+// The SSD paper's decode: per class the best nms_top_k candidates, greedy suppression per class, then the best keep_top_k of the
+// image across classes.  Two launches, no atomics on memory, no host wait:
+//   detout_class_kernel   one workgroup per (image, class), the classes of an image adjacent in launch order (their rows stay
+//                         in L2).  The class' column of `pred` is read ONCE into registers (PER values per thread, thread t
+//                         holding anchors t*PER .. t*PER+PER-1), so the b*A*C list of keys is never materialised.  With more than
+//                         nms_top_k candidates the bit pattern of the k-th largest confidence is found by a bitwise search
+//                         over the registers (32 workgroup-wide counts); everything above it and the first (by anchor) k - n_above
+//                         values equal to it are compacted by one prefix scan, sorted in LDS (bitonic_desc), decoded (decode_box)
+//                         and suppressed (nms_segment).  The survivors go to the class' [nms_top_k] slot of the workspace.
+//   detout_merge_kernel   one workgroup per image: the keep_top_k largest keys of its C sorted survivor lists.  The key
+//                           conf bits << 32 | (32767 - anchor) << 8 | (127 - class)
+//                         is unique in the image and orders by (confidence desc, anchor asc, class asc); the k-th largest key is
+//                         found by a bitwise search in which every list answers "how many of my keys are >= t" by bisection.
+// Candidates satisfy !(conf < thr) with thr >= 0: confidences are non-negative floats, whose bit patterns order as their
+// values.  Negative zero and NaN in the class columns are outside the contract (inputs are softmax outputs); they cannot make
+// the kernels leave their bounds.
+constexpr int DOUT_MAX_K = 1024;           // nms_top_k and keep_top_k: one LDS slot each
+
+struct DetOutArgs {
+    int A, nv, C, B;
+    const double* anchors;
+    const float* pred;
+    float thr;
+    int nms_top_k, keep_top_k, out_cap;
+    int* cls_count;     // [B][C] survivors of every class
+    u64* cls_keys;      // [B][C][nms_top_k] their keys, descending
+    int4* cls_box;      // [B][C][nms_top_k] their boxes
+    DetectOut out;
+};
+
+// sum of v over the workgroup (WAVES waves), the same value in every thread; two barriers
+template <int WAVES>
+__device__ __forceinline__ int dout_block_sum(int v, int* s_red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int t = 0;
+#pragma unroll
+    for (int i = 0; i < WAVES; ++i) t += s_red[i];
+    __syncthreads();
+    return __builtin_amdgcn_readfirstlane(t);
+}
+
+template <int DOUT_THREADS, int PER>
+__global__ __launch_bounds__(DOUT_THREADS) void detout_class_kernel(DetOutArgs p) {
+    constexpr int DOUT_WAVES = DOUT_THREADS / 64;
+    __shared__ __attribute__((aligned(16))) u64 skey[DOUT_MAX_K];
+    __shared__ int4 sbox[DOUT_MAX_K], snbox[DOUT_MAX_K];
+    __shared__ unsigned char alive[DOUT_MAX_K];
+    __shared__ int s_red[DOUT_WAVES], s_sc[2][DOUT_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x / p.C, c = blockIdx.x - b * p.C;
+    const int k = p.nms_top_k;
+    const float* col = p.pred + (size_t)b * p.A * p.nv + c;
+    const int a0 = tid * PER;
+    // the column, all loads in flight together (indices clamped, not predicated); u = 0: no candidate, else conf bits + 1
+    float v[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j)           // (a 32-bit byte offset from a uniform base: A * nv * 4 < 2^25)
+        v[j] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(col) + (unsigned)min(a0 + j, p.A - 1) * (unsigned)p.nv * 4u);
+    const int nvalid = p.A - a0;             // this thread's anchors are j < nvalid
+    // (the empty asm statements of this kernel pin a value in its register: without them the compiler keeps the lane mask
+    // of every comparison of one unrolled loop alive for the next loop that asks the same question -- 2 scalar registers per
+    // value, which it then has to park in vector lanes)
+    unsigned u[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const bool cand = j < nvalid && !(v[j] < p.thr);         // the argmax path's comparison
+        u[j] = cand ? min(__float_as_uint(v[j]), 0xFFFFFFFEu) + 1u : 0u;
+        asm volatile("" : "+v"(u[j]));
+    }
+    int mine = 0;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) mine += u[j] != 0u ? 1 : 0;
+    const int n = dout_block_sum<DOUT_WAVES>(mine, s_red);
+    // more than k: T = the k-th largest u, the largest t with count(u >= t) >= k, built from the top bit down
+    unsigned T = 0u;
+    int need_eq = 0;
+    if (n > k) {
+        for (int bit = 31; bit >= 0; --bit) {
+            const unsigned trial = T | (1u << bit);
+            int cnt = 0;
+#pragma unroll
+            for (int j = 0; j < PER; ++j) cnt += u[j] >= trial ? 1 : 0;
+            if (dout_block_sum<DOUT_WAVES>(cnt, s_red) >= k) T = trial;
+        }
+        int above = 0;
+#pragma unroll
+        for (int j = 0; j < PER; ++j) above += u[j] > T ? 1 : 0;
+        need_eq = k - dout_block_sum<DOUT_WAVES>(above, s_red);       // >= 1
+    }
+    // compaction: everything above T from slot 0 on, then the first need_eq values equal to T in anchor order (= thread order)
+    int g = 0, e = 0;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        g += u[j] > T ? 1 : 0;
+        e += (need_eq > 0 && u[j] == T) ? 1 : 0;
+    }
+    int gi = g, ei = e;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int tg = __shfl_up(gi, o, 64), te = __shfl_up(ei, o, 64);
+        if (lane >= o) { gi += tg; ei += te; }
+    }
+    if (lane == 63) { s_sc[0][wave] = gi; s_sc[1][wave] = ei; }
+    __syncthreads();
+    int gbase = 0, ebase = 0, n_above = 0;
+#pragma unroll
+    for (int w = 0; w < DOUT_WAVES; ++w) {
+        if (w < wave) { gbase += s_sc[0][w]; ebase += s_sc[1][w]; }
+        n_above += s_sc[0][w];
+    }
+    const int m = min(n, k);                 // n_above + min(need_eq, equals) == m
+    asm volatile("" : "+s"(T));
+    int gpos = gbase + gi - g, epos = n_above + ebase + ei - e;
+    const u64 low = (u64)(127 - c);
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const u64 key = ((u64)(u[j] - 1u) << 32) | ((u64)(32767 - (a0 + j)) << 8) | low;
+        const bool isg = u[j] > T, ise = need_eq > 0 && u[j] == T;
+        const int pos = isg ? gpos : epos;
+        if ((isg || ise) && pos < m) skey[pos] = key;      // (an equal past the first need_eq has pos >= m)
+        gpos += isg ? 1 : 0;
+        epos += ise ? 1 : 0;
+    }
+    const int m2 = next_pow2(m > 1 ? m : 1);
+    for (int i = m + tid; i < m2; i += DOUT_THREADS) skey[i] = 0ull;
+    __syncthreads();
+    bitonic_desc(skey, m2);
+    for (int q = tid; q < m; q += DOUT_THREADS) {
+        const int a = min(32767 - (int)((skey[q] >> 8) & 0xFFFFull), p.A - 1);
+        int bx[4], nb[4];
+        decode_box(p.pred + ((size_t)b * p.A + a) * p.nv + (p.nv - 4), p.anchors + (size_t)a * 4, bx);
+        nms_roundtrip(bx, nb);
+        sbox[q] = make_int4(bx[0], bx[1], bx[2], bx[3]);
+        snbox[q] = make_int4(nb[0], nb[1], nb[2], nb[3]);
+        alive[q] = 1;
+    }
+    __syncthreads();
+    if (wave == 0) nms_segment(snbox, alive, 0, m, lane);
+    __syncthreads();
+    // survivors, in order, into the class' slot
+    const size_t slot = (size_t)blockIdx.x * k;
+    int total = 0;
+    for (int q0 = 0; q0 < m; q0 += DOUT_THREADS) {
+        const int q = q0 + tid;
+        const bool keep = q < m && alive[q];
+        const u64 bal = __ballot(keep);
+        if (lane == 0) s_red[wave] = __popcll(bal);
+        __syncthreads();
+        int wbase = total, tot = 0;
+#pragma unroll
+        for (int i = 0; i < DOUT_WAVES; ++i) {
+            if (i < wave) wbase += s_red[i];
+            tot += s_red[i];
+        }
+        if (keep) {
+            const int o = wbase + __popcll(bal & ((1ull << lane) - 1ull));
+            p.cls_keys[slot + o] = skey[q];
+            p.cls_box[slot + o] = sbox[q];
+        }
+        total += tot;
+        __syncthreads();
+    }
+    if (tid == 0) p.cls_count[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(MRG_THREADS) void detout_merge_kernel(DetOutArgs p) {
+    __shared__ __attribute__((aligned(16))) u64 lkeys[DOUT_MAX_K];
+    __shared__ unsigned lvals[DOUT_MAX_K];
+    __shared__ int s_off[MRG_NCLS + 1], s_red[MRG_WAVES];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int C = p.C, k = p.nms_top_k, K = p.keep_top_k;
+    const size_t img = (size_t)b * C * k;
+    const u64* kc = p.cls_keys + img + (size_t)min(tid, C - 1) * k;       // thread c < C: the list of class c
+    const int cnt = tid < C ? min(max(p.cls_count[b * C + tid], 0), k) : 0;
+    const int N = dout_block_sum<MRG_WAVES>(cnt, s_red);
+    // more than K survivors: T = the K-th largest key.  The number of this list's keys >= T stays inside [lo, hi]: an accepted
+    // trial lowers hi, a rejected one (every later trial is smaller) raises lo.
+    int lo = 0, hi = cnt;
+    if (N > K) {
+        u64 T = 0ull;
+        for (int bit = 63; bit >= 0; --bit) {
+            const u64 trial = T | (1ull << bit);
+            int l = lo, h = hi;
+            while (l < h) {
+                const int mid = (l + h) >> 1;
+                if (kc[mid] >= trial) l = mid + 1; else h = mid;
+            }
+            if (dout_block_sum<MRG_WAVES>(l, s_red) >= K) { T = trial; hi = l; }
+            else lo = l;
+        }
+    }
+    const int sel = hi;                       // this list's share of the output
+    if (tid < MRG_NCLS) s_off[tid + 1] = sel;
+    if (tid == 0) s_off[0] = 0;
+    __syncthreads();
+    if (tid == 0)
+        for (int i = 1; i <= MRG_NCLS; ++i) s_off[i] += s_off[i - 1];
+    __syncthreads();
+    const int total = min(s_off[MRG_NCLS], K);      // (== s_off[MRG_NCLS]: the keys are unique)
+    const int n2 = next_pow2(total > 1 ? total : 1);
+    for (int f = tid; f < n2; f += MRG_THREADS) {
+        u64 key = 0ull;
+        unsigned src = 0u;
+        if (f < total) {
+            int l = 0, h = MRG_NCLS - 1;      // the list that holds the f-th selected record
+            while (l < h) {
+                const int mid = (l + h + 1) >> 1;
+                if (s_off[mid] <= f) l = mid; else h = mid - 1;
+            }
+            src = (unsigned)(l * k + (f - s_off[l]));
+            key = p.cls_keys[img + src];
+        }
+        lkeys[f] = key;
+        lvals[f] = src;
+    }
+    __syncthreads();
+    merge_sort_desc(lkeys, lvals, n2);
+    for (int f = tid; f < total && f < p.out_cap; f += MRG_THREADS) {
+        const u64 key = lkeys[f];
+        const size_t dst = (size_t)b * p.out_cap + f;
+        p.out.conf[dst] = __uint_as_float((unsigned)(key >> 32));
+        p.out.cls[dst] = 127 - (int)(key & 127ull);
+        p.out.idx[dst] = 32767 - (int)((key >> 8) & 0xFFFFull);
+        const int4 bx = p.cls_box[img + lvals[f]];
+        int* ob = p.out.box + dst * 4;      // (four stores: with out_cap = keep_top_k the caller's rows need not be 16-byte aligned)
+        ob[0] = bx.x; ob[1] = bx.y; ob[2] = bx.z; ob[3] = bx.w;
+    }
+    if (tid == 0) p.out.count[b] = total;
+}
+
+static size_t align256(size_t n) { return (n + 255) / 256 * 256; }
+
+void detection_output_check(int A, int num_classes, int B, float conf_thr, int nms_top_k, int keep_top_k, int out_cap) {
+    SSD_REQUIRE(A >= 1 && A <= 32767, "detection_output: at most 32767 anchors (got %d)", A);
+    require_num_classes(num_classes);
+    SSD_REQUIRE(B >= 1 && B <= DET_MAX_BATCH, "detection_output: 1..%d images per pass (got %d)", DET_MAX_BATCH, B);
+    SSD_REQUIRE(std::isfinite(conf_thr) && conf_thr >= 0.f, "detection_output: the confidence threshold must be finite and >= 0");
+    SSD_REQUIRE(nms_top_k >= 1 && nms_top_k <= DOUT_MAX_K, "detection_output: nms_top_k must be in 1..%d (got %d)", DOUT_MAX_K, nms_top_k);
+    SSD_REQUIRE(keep_top_k >= 1 && keep_top_k <= DOUT_MAX_K, "detection_output: keep_top_k must be in 1..%d (got %d)", DOUT_MAX_K, keep_top_k);
+    SSD_REQUIRE(out_cap >= 1, "detection_output: out_cap must be >= 1");
+}
+
+size_t detection_output_ws_bytes(int B, int num_classes, int nms_top_k) {
+    const size_t lists = (size_t)B * num_classes;
+    return align256(lists * 4) + align256(lists * nms_top_k * 8) + lists * nms_top_k * 16;
+}
+
+void detection_output(int A, int num_classes, const double* anchors, const float* pred, int B, float conf_thr, int nms_top_k,
+                      int keep_top_k, int out_cap, const DetectOut& out, void* ws, size_t ws_bytes, hipStream_t s) {
+    detection_output_check(A, num_classes, B, conf_thr, nms_top_k, keep_top_k, out_cap);
+    SSD_REQUIRE(anchors && pred && ws && out.count && out.conf && out.cls && out.idx && out.box, "detection_output: null argument");
+    const size_t need = detection_output_ws_bytes(B, num_classes, nms_top_k);
+    SSD_REQUIRE(ws_bytes >= need, "detection_output: the workspace holds %zu bytes, %zu are needed", ws_bytes, need);
+    const size_t lists = (size_t)B * num_classes;
+    DetOutArgs a{};
+    a.A = A; a.nv = num_classes + 5; a.C = num_classes; a.B = B; a.anchors = anchors; a.pred = pred; a.thr = conf_thr;
+    a.nms_top_k = nms_top_k; a.keep_top_k = keep_top_k; a.out_cap = out_cap; a.out = out;
+    char* base = (char*)ws;
+    a.cls_count = (int*)base; base += align256(lists * 4);
+    a.cls_keys = (u64*)base; base += align256(lists * nms_top_k * 8);
+    a.cls_box = (int4*)base;
+    {
+        ProfScope prof("detout_class", 0.0, (double)B * A * a.nv * 4.0, s);
+        const dim3 grid((unsigned)lists);
+        if (A <= 256 * 35) hipLaunchKernelGGL((detout_class_kernel<256, 35>), grid, dim3(256), 0, s, a);            // vgg300: 8732
+        else if (A <= 512 * 48) hipLaunchKernelGGL((detout_class_kernel<512, 48>), grid, dim3(512), 0, s, a);       // vgg512: 24564
+        else hipLaunchKernelGGL((detout_class_kernel<512, 64>), grid, dim3(512), 0, s, a);
+    }
+    {
+        ProfScope prof("detout_merge", 0.0, 0.0, s);
+        hipLaunchKernelGGL(detout_merge_kernel, dim3(B), dim3(MRG_THREADS), 0, s, a);
+    }
+    HIP_OK(hipGetLastError());
+}
+
 }  // namespace ssd

@@ -150,6 +150,8 @@ public:
     void detect_last(int b, float thr, int cap, int max_out, int out_cap, bool nms, int* count, float* conf, int* cls, int* idx, int* box);
     // asynchronous form: the kernels enqueued; dev_out (optional) = the device's view of the slot's arrays
     const DetectSlot& detect_last_dev(int b, float thr, int cap, int max_out, int out_cap, bool nms, DetectOut* dev_out);
+    // the DetectionOutput pass (boxes.h detection_output) on the last result, into the same two alternating slots
+    const DetectSlot& detect_last_all_dev(int b, float thr, int nms_top_k, int keep_top_k, int out_cap, DetectOut* dev_out);
     // host copy of the latest (which = 0) or the previous (which = 1) pass; waits for that slot's pass only
     void detect_fetch(int which, int* count, float* conf, int* cls, int* idx, int* box);
     // the pinned host memory of that slot itself (valid until the second-next pass); waits for the slot's pass only
@@ -291,6 +293,9 @@ private:
     double* anchors_dev_ = nullptr;
     int* anchors_abs_dev_ = nullptr;
     void* detect_ws_ = nullptr;
+    void* detout_ws_ = nullptr;     // DetectionOutput's workspace: grown on first use, freed with the handle
+    size_t detout_ws_bytes_ = 0;
+    DetectSlot& detect_slot_next(int b, int out_cap);      // the other slot, free for a new pass of b x out_cap
     DetectSlot det_slot_[2];
     int det_cur_ = 0;
     void detect_slot_carve(const DetectSlot& sl, DetectOut& d, char* base) const;

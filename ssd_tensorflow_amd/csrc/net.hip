@@ -1800,13 +1800,7 @@ void Net::detect_slot_carve(const DetectSlot& sl, DetectOut& d, char* base) cons
     d.box = d.idx + n;
 }
 
-const DetectSlot& Net::detect_last_dev(int b, float thr, int cap, int max_out, int out_cap, bool nms, DetectOut* dev_out) {
-    SSD_REQUIRE(b >= 1 && b <= Bmax_, "batch %d outside 1..%d", b, Bmax_);
-    SSD_REQUIRE(out_cap >= 1, "out_cap must be >= 1");
-    const int A = preset_->num_anchors;
-    if (!detect_ws_) {
-        detect_ws_ = hip_.mem(detect_ws_bytes(Bmax_, A));
-    }
+DetectSlot& Net::detect_slot_next(int b, int out_cap) {
     det_cur_ ^= 1;
     DetectSlot& sl = det_slot_[det_cur_];
     if (!sl.ready) {
@@ -1830,11 +1824,45 @@ const DetectSlot& Net::detect_last_dev(int b, float thr, int cap, int max_out, i
         sl.bytes = grow;
     }
     sl.b = b; sl.out_cap = out_cap; sl.used = need;
+    return sl;
+}
+
+const DetectSlot& Net::detect_last_dev(int b, float thr, int cap, int max_out, int out_cap, bool nms, DetectOut* dev_out) {
+    SSD_REQUIRE(b >= 1 && b <= Bmax_, "batch %d outside 1..%d", b, Bmax_);
+    SSD_REQUIRE(out_cap >= 1, "out_cap must be >= 1");
+    const int A = preset_->num_anchors;
+    if (!detect_ws_) {
+        detect_ws_ = hip_.mem(detect_ws_bytes(Bmax_, A));
+    }
+    DetectSlot& sl = detect_slot_next(b, out_cap);
     g_prof = &prof_;
     prof_.layer = "detect";
     DetectOut d;
     detect_slot_carve(sl, d, sl.dev);
     detect(A, C_, anchors_dev_, result_, b, thr, cap, max_out, out_cap, nms, d, detect_ws_, stream_);
+    HIP_OK(hipEventRecord(sl.ready, stream_));
+    if (dev_out) *dev_out = d;
+    return sl;
+}
+
+const DetectSlot& Net::detect_last_all_dev(int b, float thr, int nms_top_k, int keep_top_k, int out_cap, DetectOut* dev_out) {
+    SSD_REQUIRE(b >= 1 && b <= Bmax_, "batch %d outside 1..%d", b, Bmax_);
+    const int A = preset_->num_anchors;
+    detection_output_check(A, C_, b, thr, nms_top_k, keep_top_k, out_cap);      // before a slot is taken
+    const size_t need = detection_output_ws_bytes(Bmax_, C_, nms_top_k);
+    if (need > detout_ws_bytes_) {
+        if (detout_ws_) hip_.free_mem(detout_ws_);      // (waits for the device)
+        detout_ws_ = nullptr;
+        detout_ws_bytes_ = 0;
+        detout_ws_ = hip_.mem(need);
+        detout_ws_bytes_ = need;
+    }
+    DetectSlot& sl = detect_slot_next(b, out_cap);
+    g_prof = &prof_;
+    prof_.layer = "detect";
+    DetectOut d;
+    detect_slot_carve(sl, d, sl.dev);
+    detection_output(A, C_, anchors_dev_, result_, b, thr, nms_top_k, keep_top_k, out_cap, d, detout_ws_, detout_ws_bytes_, stream_);
     HIP_OK(hipEventRecord(sl.ready, stream_));
     if (dev_out) *dev_out = d;
     return sl;

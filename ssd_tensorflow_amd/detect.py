@@ -11,7 +11,8 @@ import sys
 import numpy as np
 
 from .annotate import Style, write_image, GpuJpegWriter
-from .infer import sample_generator, resolve_class_names, add_fp8_arguments, check_fp8_arguments, fp8_batches
+from .infer import (sample_generator, resolve_class_names, add_fp8_arguments, check_fp8_arguments, fp8_batches, add_decode_arguments,
+                    check_decode_arguments, decode_keywords)
 from .ssdvgg import SSDVGG, Session
 from .ssdutils import get_preset_by_name, boxes_from_detection
 from .utils import default_colors
@@ -41,8 +42,10 @@ def main(argv=None):
                         help='--encoder gpu: host: Huffman coding on host threads; gpu: on the GPU as well, only the files come back (same bytes)')
     from .tiling import add_arguments as add_tile_arguments
     add_tile_arguments(parser)
+    add_decode_arguments(parser)
     args = parser.parse_args(argv)
     check_fp8_arguments(parser, args)
+    check_decode_arguments(parser, args)
 
     print('[i] Model:         ', args.model)
     print('[i] Training data: ', args.training_data)
@@ -101,7 +104,10 @@ def main(argv=None):
                                                                           decoder=args.decoder, decoder_entropy=args.decoder_entropy),
                                                    args.fp8_calibration, args.fp8_calibrate_images):
             net.infer_dev(x)
-            ticket = net.detect_last_launch(x.shape[0], 0.5, None, 200)                      # detect.py:111-112
+            if args.decode == 'all':
+                ticket = net.detect_last_launch(x.shape[0], 0.5, **decode_keywords(args))
+            else:
+                ticket = net.detect_last_launch(x.shape[0], 0.5, None, 200)                  # detect.py:111-112
             if writer is not None:
                 drawn = writer.launch(net, sources, style, [os.path.join(args.output_dir, os.path.basename(files[i])) for i in idxs])
             else:

@@ -149,6 +149,32 @@ def fp8_batches(net, batches, calibration_file=None, calibrate_images=32):
     yield from batches
 
 
+def add_decode_arguments(parser):
+    """--decode / --nms-top-k / --keep-top-k of the deployment tools"""
+    parser.add_argument('--decode', default='argmax', choices=['argmax', 'all'],
+                        help="argmax: the reference's decode, one candidate per anchor (its best class); all: the SSD paper's DetectionOutput, "
+                             'every class of an anchor above the threshold is a candidate, the best --nms-top-k per class go through NMS and '
+                             'the best --keep-top-k of the image are kept, in confidence order')
+    parser.add_argument('--nms-top-k', type=int, default=400, help='--decode all: candidates per class that enter NMS (1..1024)')
+    parser.add_argument('--keep-top-k', type=int, default=200, help='--decode all: detections kept per image (1..1024)')
+
+
+def check_decode_arguments(parser, args):
+    """--decode all with --tile is an argument error: the tile merge takes one record per anchor"""
+    if args.decode == 'all' and args.tile:
+        parser.error('--decode all does not apply to --tile: the tile merge takes one record per anchor (use --decode argmax)')
+    for name in ('nms_top_k', 'keep_top_k'):
+        if args.decode == 'all' and not 1 <= getattr(args, name) <= 1024:
+            parser.error('--%s must be in 1..1024' % name.replace('_', '-'))
+
+
+def decode_keywords(args):
+    """the decode keywords of SSDVGG.detect_last_launch for these arguments"""
+    if args.decode == 'all':
+        return dict(decode='all', nms_top_k=args.nms_top_k, keep_top_k=args.keep_top_k)
+    return {}
+
+
 def resolve_class_names(num_classes, source_names=None, stored=None):
     """{class id: name}: the data source's names, else the checkpoint's __class_names__, else (a checkpoint written before
     names were stored, or no checkpoint) the VOC names for 20 classes and 'class_<id>' otherwise."""
@@ -240,8 +266,10 @@ def main(argv=None):
                         help='--encoder gpu: host: Huffman coding on host threads; gpu: on the GPU as well, only the files come back (same bytes)')
     from .tiling import add_arguments as add_tile_arguments
     add_tile_arguments(parser)
+    add_decode_arguments(parser)
     args = parser.parse_args(argv)
     check_fp8_arguments(parser, args)
+    check_decode_arguments(parser, args)
     if args.tile and args.dump_predictions:
         parser.error('--dump-predictions does not apply to --tile: a tiled picture has one prediction tensor per window')
     if args.tile and args.synthetic:
@@ -257,6 +285,8 @@ def main(argv=None):
     print('[i] Threshold:         ', args.threshold)
     print('[i] Pascal summary:    ', args.pascal_summary)
     print('[i] Annotate:          ', args.annotate)
+    if args.decode != 'argmax':
+        print('[i] Decode:            ', '%s (nms top k %d, keep top k %d)' % (args.decode, args.nms_top_k, args.keep_top_k))
 
     # ---- checkpoint lookup (infer.py:111-126) --------------------------------------------------
     ckpt = None
@@ -420,7 +450,10 @@ def main(argv=None):
                                                        decoder_entropy=args.decoder_entropy), args.fp8_calibration, args.fp8_calibrate_images):
             x, idxs, sizes = batch[:3]
             net.infer_dev(x)                                                                 # infer.py:225-227
-            ticket = net.detect_last_launch(x.shape[0], args.threshold, None, 200)
+            if args.decode == 'all':
+                ticket = net.detect_last_launch(x.shape[0], args.threshold, **decode_keywords(args))
+            else:
+                ticket = net.detect_last_launch(x.shape[0], args.threshold, None, 200)
             if ap_dev:
                 add_pass(ticket, idxs)
             if writer is not None:

@@ -181,6 +181,49 @@ def detect_tiles(pred, preset, tiles, thr, tile_cap=200, max_out=200, edge_margi
     return merge_tile_lists(tiles, count, conf, cls, idx, box, tile_cap, max_out, edge_margin)
 
 
+def detection_output_batch(pred, preset, confidence_threshold=0.01, nms_top_k=400, keep_top_k=200, out_cap=None):
+    """The SSD paper's DetectionOutput for pred [b, A, C+5] on the GPU (ssd_detection_output): every (anchor,
+    class) pair that reaches the threshold is a candidate, the best nms_top_k per class, NMS per class, the best keep_top_k
+    of the image.  Returns what detect_batch returns, in global confidence order (ties: lower anchor, then lower class); an
+    anchor may appear under several classes."""
+    pred = np.ascontiguousarray(pred, np.float32)
+    if pred.ndim == 2:
+        pred = pred[None]
+    b, A, nv = pred.shape
+    p = _preset_for(A) if preset is None else preset
+    if p.num_anchors != A:
+        raise ValueError(f'pred has {A} anchors, preset {p.name} has {p.num_anchors}')
+    keep_top_k = int(keep_top_k)
+    out_cap = max(keep_top_k, 1) if out_cap is None else int(out_cap)
+    n = max(out_cap, 1)
+    count = np.zeros(b, np.int32)
+    conf = np.zeros((b, n), np.float32)
+    cls = np.zeros((b, n), np.int32)
+    idx = np.zeros((b, n), np.int32)
+    box = np.zeros((b, n, 4), np.int32)
+    check(lib.ssd_detection_output(_pname(p), nv - 5, _lib.device(), np_ptr(pred), b, float(confidence_threshold), int(nms_top_k),
+                                   keep_top_k, out_cap, np_ptr(count), np_ptr(conf), np_ptr(cls), np_ptr(idx), np_ptr(box)))
+    out = []
+    for i in range(b):
+        m = min(int(count[i]), out_cap)
+        out.append(dict(conf=conf[i, :m], cls=cls[i, :m], idx=idx[i, :m], box=box[i, :m]))
+    return out
+
+
+def detection_output(pred, anchors_or_preset, confidence_threshold=0.01, lid2name={}, nms_top_k=400, keep_top_k=200):
+    """DetectionOutput for one image: the list of (confidence, Box) that decode_boxes + suppress_overlaps return, decoded the
+    way the SSD paper does (every class of an anchor, not its argmax class alone).  `anchors_or_preset`: a preset, its name, or
+    the anchor list (only its length is used)."""
+    if isinstance(anchors_or_preset, str):
+        p = get_preset_by_name(anchors_or_preset)
+    elif isinstance(anchors_or_preset, SSDPreset):
+        p = anchors_or_preset
+    else:
+        p = _preset_for(len(anchors_or_preset))
+    det = detection_output_batch(np.asarray(pred, np.float32), p, confidence_threshold, nms_top_k, keep_top_k)[0]
+    return boxes_from_detection(det, lid2name)
+
+
 def boxes_from_detection(det, lid2name={}):
     """dict from detect_batch -> the reference's list of (confidence, Box)."""
     res = []

@@ -582,14 +582,28 @@ class SSDVGG:
             out_cap = max(min(out_cap, mo), 1)
         return cap, mo, out_cap
 
-    def detect_last_launch(self, b, confidence_threshold=0.5, detections_cap=200, max_out=None, nms=True):
+    def detect_last_launch(self, b, confidence_threshold=0.5, detections_cap=200, max_out=None, nms=True, decode='argmax',
+                           nms_top_k=400, keep_top_k=200):
         """Enqueue decode + NMS of the last step's result and the copy of its (small) output; returns a
         ticket whose get() yields what detect_last returns.  Two output slots alternate in the handle, so a
-        caller may launch the next batch before it collects this one (infer.py:225-235, pipelined)."""
-        cap, mo, out_cap = self._det_caps(detections_cap, max_out)
+        caller may launch the next batch before it collects this one (infer.py:225-235, pipelined).
+        decode='argmax': the reference's decode_boxes + suppress_overlaps (one candidate per anchor).  decode='all': the SSD
+        paper's DetectionOutput (ssd_detect_last_all_dev) -- every class of an anchor is a candidate, the best
+        nms_top_k per class, NMS per class, the best keep_top_k of the image in global confidence order; detections_cap,
+        max_out and nms do not apply and must be left at their defaults."""
         count_dev = C.c_void_p(); conf_dev = C.c_void_p(); cls_dev = C.c_void_p(); box_dev = C.c_void_p()
-        check(lib.ssd_detect_last_dev(self._h, b, float(confidence_threshold), cap, mo, out_cap, 1 if nms else 0,
-                                      C.byref(count_dev), C.byref(conf_dev), C.byref(cls_dev), None, C.byref(box_dev)))
+        if decode == 'all':
+            if detections_cap != 200 or max_out is not None or nms is not True:
+                raise ValueError("decode='all' takes nms_top_k and keep_top_k; detections_cap, max_out and nms do not apply")
+            out_cap = max(int(keep_top_k), 1)
+            check(lib.ssd_detect_last_all_dev(self._h, b, float(confidence_threshold), int(nms_top_k), int(keep_top_k), out_cap,
+                                              C.byref(count_dev), C.byref(conf_dev), C.byref(cls_dev), None, C.byref(box_dev)))
+        elif decode == 'argmax':
+            cap, mo, out_cap = self._det_caps(detections_cap, max_out)
+            check(lib.ssd_detect_last_dev(self._h, b, float(confidence_threshold), cap, mo, out_cap, 1 if nms else 0,
+                                          C.byref(count_dev), C.byref(conf_dev), C.byref(cls_dev), None, C.byref(box_dev)))
+        else:
+            raise ValueError("decode must be 'argmax' or 'all' (got %r)" % (decode,))
         self._det_serial = getattr(self, '_det_serial', 0) + 1
         self._det_dev = (self._det_serial, count_dev.value, cls_dev.value, box_dev.value, b, out_cap)      # (annotate_last_launch)
         if not hasattr(self, '_det_views'):
@@ -625,10 +639,13 @@ class SSDVGG:
             done.record(stream)
         return _Annotated(host, done, offs, shapes, dst if keep_device else None, stream if keep_device else None)
 
-    def detect_last(self, b, confidence_threshold=0.5, detections_cap=200, max_out=None, nms=True):
-        """decode + NMS of the last step's result without leaving the GPU (train.py:275-277)."""
+    def detect_last(self, b, confidence_threshold=0.5, detections_cap=200, max_out=None, nms=True, decode='argmax', nms_top_k=400,
+                    keep_top_k=200):
+        """decode + NMS of the last step's result without leaving the GPU (train.py:275-277); decode='all': see
+        detect_last_launch."""
         # (copies: a caller of this synchronous form may keep the result across any number of later passes)
-        return [{k: v.copy() for k, v in d.items()} for d in self.detect_last_launch(b, confidence_threshold, detections_cap, max_out, nms).get()]
+        return [{k: v.copy() for k, v in d.items()}
+                for d in self.detect_last_launch(b, confidence_threshold, detections_cap, max_out, nms, decode, nms_top_k, keep_top_k).get()]
 
     # ------------------------------------------------------------------ Session.run routing
     def _run(self, fetches, feed):
