@@ -154,6 +154,10 @@ SIGNATURES = {
     'ssd_merge_tiles_ws_bytes': (sz, [i32, i32]),
     'ssd_merge_tiles_dev': (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     'ssd_merge_tiles': (i32, [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    'ssd_detout_tiles_ws_bytes': (sz, [cstr, i32, i32, i32, i32]),
+    'ssd_detout_tiles_add_dev': (i32, [cstr, i32, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp, sz, vp]),
+    'ssd_detout_tiles_merge_dev': (i32, [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    'ssd_detout_tiles': (i32, [cstr, i32, i32, vp, vp, i32, i32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     'ssd_set_overlap': (i32, [handle, i32]),
     'ssd_profile_enable': (i32, [handle, i32]),
     'ssd_profile_report': (i32, [handle, C.c_char_p, sz]),

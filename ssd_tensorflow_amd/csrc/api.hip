@@ -460,6 +460,73 @@ int ssd_merge_tiles(int device, const ssd_tile* tiles, int n_tiles, int n_images
     API_END
 }
 
+size_t ssd_detout_tiles_ws_bytes(const char* preset, int num_classes, int n_tiles, int n_images, int nms_top_k) {
+    try {
+        return detout_tiles_ws_bytes(get_preset(preset).num_anchors, num_classes, n_tiles, n_images, nms_top_k);
+    } catch (const std::exception& e) {
+        ssd::set_error("%s", e.what());
+        return 0;
+    }
+}
+
+int ssd_detout_tiles_add_dev(const char* preset, int num_classes, const double* anchors_dev, const float* pred_dev,
+                             const ssd_tile* tiles, int n_tiles, int first, int b, float conf_thr, int nms_top_k, int edge_margin,
+                             void* ws_dev, size_t ws_bytes, void* stream) {
+    API_BEGIN
+    detout_tiles_add("ssd_detout_tiles_add_dev", get_preset(preset).num_anchors, num_classes, anchors_dev, pred_dev,
+                     reinterpret_cast<const MergeTile*>(tiles), n_tiles, first, b, conf_thr, nms_top_k, edge_margin, ws_dev, ws_bytes,
+                     (hipStream_t)stream);
+    API_END
+}
+
+int ssd_detout_tiles_merge_dev(int num_classes, const ssd_tile* tiles, int n_tiles, int n_images, int nms_top_k, int keep_top_k,
+                               int out_cap, int* count_out, float* conf_out, int* cls_out, int* idx_out, int* tile_out, int* box_out,
+                               void* ws_dev, size_t ws_bytes, void* stream) {
+    API_BEGIN
+    detout_tiles_merge("ssd_detout_tiles_merge_dev", num_classes, reinterpret_cast<const MergeTile*>(tiles), n_tiles, n_images, nms_top_k,
+                       keep_top_k, out_cap, count_out, conf_out, cls_out, idx_out, tile_out, box_out, ws_dev, ws_bytes,
+                       (hipStream_t)stream);
+    API_END
+}
+
+int ssd_detout_tiles(const char* preset, int num_classes, int device, const float* pred, const ssd_tile* tiles, int n_tiles,
+                     int n_images, float conf_thr, int nms_top_k, int keep_top_k, int edge_margin, int out_cap, int* count_out,
+                     float* conf_out, int* cls_out, int* idx_out, int* tile_out, int* box_out) {
+    API_BEGIN
+    const char* who = "ssd_detout_tiles";
+    const Preset& p = get_preset(preset);
+    const MergeTile* mt = reinterpret_cast<const MergeTile*>(tiles);
+    {      // every limit before anything is allocated
+        std::vector<int> head;
+        detout_tiles_add_check(who, p.num_anchors, num_classes, mt, n_tiles, 0, n_tiles, conf_thr, nms_top_k, head);
+        detout_tiles_merge_check(who, num_classes, mt, n_tiles, n_images, nms_top_k, keep_top_k, out_cap, head);
+    }
+    SSD_REQUIRE(pred && count_out && cls_out && box_out, "%s: null argument", who);
+    DeviceGuard dev_guard_(device);
+    const size_t A = p.num_anchors, nv = num_classes + 5, nout = (size_t)n_images * out_cap;
+    const size_t wsb = detout_tiles_ws_bytes((int)A, num_classes, n_tiles, n_images, nms_top_k);
+    DevBuf anc(A * 4 * sizeof(double)), dpred((size_t)n_tiles * A * nv * sizeof(float)), ws(wsb);
+    DevBuf ocount((size_t)n_images * 4), oconf(nout * 4), ocls(nout * 4), oidx(nout * 4), otile(nout * 4), obox(nout * 16);
+    anchors_device(p, anc.as<double>(), nullptr, nullptr);
+    HIP_OK(hipMemcpy(dpred.p, pred, (size_t)n_tiles * A * nv * sizeof(float), hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(oconf.p, 0, nout * 4));      // rows past a picture's count read as zero
+    HIP_OK(hipMemset(ocls.p, 0, nout * 4));
+    HIP_OK(hipMemset(oidx.p, 0, nout * 4));
+    HIP_OK(hipMemset(otile.p, 0, nout * 4));
+    HIP_OK(hipMemset(obox.p, 0, nout * 16));
+    detout_tiles_add(who, (int)A, num_classes, anc.as<double>(), dpred.as<float>(), mt, n_tiles, 0, n_tiles, conf_thr, nms_top_k,
+                     edge_margin, ws.p, wsb, nullptr);
+    detout_tiles_merge(who, num_classes, mt, n_tiles, n_images, nms_top_k, keep_top_k, out_cap, ocount.as<int>(), oconf.as<float>(),
+                       ocls.as<int>(), oidx.as<int>(), otile.as<int>(), obox.as<int>(), ws.p, wsb, nullptr);
+    HIP_OK(hipMemcpy(count_out, ocount.p, (size_t)n_images * 4, hipMemcpyDeviceToHost));
+    if (conf_out) HIP_OK(hipMemcpy(conf_out, oconf.p, nout * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(cls_out, ocls.p, nout * 4, hipMemcpyDeviceToHost));
+    if (idx_out) HIP_OK(hipMemcpy(idx_out, oidx.p, nout * 4, hipMemcpyDeviceToHost));
+    if (tile_out) HIP_OK(hipMemcpy(tile_out, otile.p, nout * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(box_out, obox.p, nout * 16, hipMemcpyDeviceToHost));
+    API_END
+}
+
 int ssd_average_precision_ex(int device, int n_det, const float* det_box, const float* det_conf, const int* det_cls,
                              const int* det_sample, int n_gt, const double* gt_box, const int* gt_cls, const int* gt_sample,
                              const unsigned char* gt_flags, int num_classes, int protocol, int n_thr, const double* minoverlaps,

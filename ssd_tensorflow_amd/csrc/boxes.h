@@ -90,4 +90,26 @@ void merge_tiles(const MergeTile* tiles, int n_tiles, int n_images, int tile_cap
                  const int* idx, const int* box, int edge_margin, int max_out, int out_cap, int* count_out, float* conf_out,
                  int* cls_out, int* idx_out, int* tile_out, int* box_out, void* ws, hipStream_t s);
 
+// Tiled DetectionOutput: every tile decoded as detection_output decodes an image (per class the best nms_top_k
+// candidates, NO suppression inside a tile), edge drop, the picture's grid, then per class the best nms_top_k of the PICTURE
+// through one greedy NMS, and the best keep_top_k of the picture across classes, in the order of the unique key
+//   conf bits << 32 | (255 - tile) << 24 | (32767 - anchor) << 8 | (127 - class)      (descending).
+// detout_tiles_add decodes the b network inputs pred [b][A][C+5] = tiles first .. first + b - 1 of the table into the
+// workspace (once per network batch); detout_tiles_merge turns the workspace into the merged-detection layout of merge_tiles
+// (conf_out, idx_out, tile_out may be null).  tiles: HOST array of ALL n_tiles, as for merge_tiles.  Asynchronous on s, no
+// atomics on memory; every limit is checked before anything is enqueued, and `who` (the entry point) starts every message.
+//   ws bytes = align256(4 (8 n_tiles + n_images + 1)) + sum over L in {n_tiles C, n_images C} of
+//              align256(4 L) + align256(8 L nms_top_k) + align256(16 L nms_top_k)
+size_t detout_tiles_ws_bytes(int A, int num_classes, int n_tiles, int n_images, int nms_top_k);
+void detout_tiles_add_check(const char* who, int A, int num_classes, const MergeTile* tiles, int n_tiles, int first, int b, float conf_thr,
+                            int nms_top_k, std::vector<int>& head);                                           // the limits alone
+void detout_tiles_merge_check(const char* who, int num_classes, const MergeTile* tiles, int n_tiles, int n_images, int nms_top_k,
+                              int keep_top_k, int out_cap, std::vector<int>& head);                          // the limits alone
+void detout_tiles_add(const char* who, int A, int num_classes, const double* anchors, const float* pred, const MergeTile* tiles,
+                      int n_tiles, int first, int b, float conf_thr, int nms_top_k, int edge_margin, void* ws, size_t ws_bytes,
+                      hipStream_t s);
+void detout_tiles_merge(const char* who, int num_classes, const MergeTile* tiles, int n_tiles, int n_images, int nms_top_k, int keep_top_k,
+                        int out_cap, int* count_out, float* conf_out, int* cls_out, int* idx_out, int* tile_out, int* box_out, void* ws,
+                        size_t ws_bytes, hipStream_t s);
+
 }  // namespace ssd

@@ -1506,8 +1506,18 @@ __device__ __forceinline__ int dout_block_sum(int v, int* s_red) {
     return __builtin_amdgcn_readfirstlane(t);
 }
 
-template <int DOUT_THREADS, int PER>
-__global__ __launch_bounds__(DOUT_THREADS) void detout_class_kernel(DetOutArgs p) {
+// The tile stage of tiled DetectionOutput is this kernel with TILE = true: image = the b-th network input of
+// the call = tile tp.first + b of the table, the lists are the tiles' [C][nms_top_k] slots (p.cls_* point at tile tp.first), the
+// survivor predicate is "not cut by an interior edge" instead of "survived NMS", and a record leaves with its box on the
+// picture's 1000 grid and its tile (index inside the picture) in bits 24..31 of the key.
+struct DetTileArgs {
+    const MergeTile* tiles;     // [n_tiles] the whole table
+    const int* img_first;       // [n_images + 1] first tile of every picture
+    int first, edge_margin;
+};
+
+template <int DOUT_THREADS, int PER, bool TILE>
+__device__ __forceinline__ void detout_class_body(DetOutArgs p, DetTileArgs tp) {
     constexpr int DOUT_WAVES = DOUT_THREADS / 64;
     __shared__ __attribute__((aligned(16))) u64 skey[DOUT_MAX_K];
     __shared__ int4 sbox[DOUT_MAX_K], snbox[DOUT_MAX_K];
@@ -1597,14 +1607,31 @@ __global__ __launch_bounds__(DOUT_THREADS) void detout_class_kernel(DetOutArgs p
         const int a = min(32767 - (int)((skey[q] >> 8) & 0xFFFFull), p.A - 1);
         int bx[4], nb[4];
         decode_box(p.pred + ((size_t)b * p.A + a) * p.nv + (p.nv - 4), p.anchors + (size_t)a * 4, bx);
-        nms_roundtrip(bx, nb);
-        sbox[q] = make_int4(bx[0], bx[1], bx[2], bx[3]);
-        snbox[q] = make_int4(nb[0], nb[1], nb[2], nb[3]);
-        alive[q] = 1;
+        if constexpr (TILE) {
+            const MergeTile tl = tp.tiles[tp.first + b];
+            const int in = tl.interior, mg = tp.edge_margin;      // merge_tiles_kernel's rule, on the tile-grid box
+            const bool cut = mg >= 0 && (((in & 1) && bx[0] <= mg) || ((in & 2) && bx[1] >= 999 - mg) || ((in & 4) && bx[2] <= mg) ||
+                                         ((in & 8) && bx[3] >= 999 - mg));
+            sbox[q] = make_int4(merge_map(bx[0], tl.x0, tl.w, tl.img_w), merge_map(bx[1], tl.x0, tl.w, tl.img_w),
+                                merge_map(bx[2], tl.y0, tl.h, tl.img_h), merge_map(bx[3], tl.y0, tl.h, tl.img_h));
+            alive[q] = cut ? 0 : 1;
+        } else {
+            nms_roundtrip(bx, nb);
+            sbox[q] = make_int4(bx[0], bx[1], bx[2], bx[3]);
+            snbox[q] = make_int4(nb[0], nb[1], nb[2], nb[3]);
+            alive[q] = 1;
+        }
     }
     __syncthreads();
-    if (wave == 0) nms_segment(snbox, alive, 0, m, lane);
-    __syncthreads();
+    if constexpr (!TILE) {
+        if (wave == 0) nms_segment(snbox, alive, 0, m, lane);
+        __syncthreads();
+    }
+    u64 tile_bits = 0ull;
+    if constexpr (TILE) {
+        const int g = tp.first + b;
+        tile_bits = (u64)(255 - (g - tp.img_first[tp.tiles[g].image])) << 24;
+    }
     // survivors, in order, into the class' slot
     const size_t slot = (size_t)blockIdx.x * k;
     int total = 0;
@@ -1622,7 +1649,8 @@ __global__ __launch_bounds__(DOUT_THREADS) void detout_class_kernel(DetOutArgs p
         }
         if (keep) {
             const int o = wbase + __popcll(bal & ((1ull << lane) - 1ull));
-            p.cls_keys[slot + o] = skey[q];
+            if constexpr (TILE) p.cls_keys[slot + o] = skey[q] | tile_bits;
+            else p.cls_keys[slot + o] = skey[q];
             p.cls_box[slot + o] = sbox[q];
         }
         total += tot;
@@ -1631,7 +1659,20 @@ __global__ __launch_bounds__(DOUT_THREADS) void detout_class_kernel(DetOutArgs p
     if (tid == 0) p.cls_count[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(MRG_THREADS) void detout_merge_kernel(DetOutArgs p) {
+template <int DOUT_THREADS, int PER>
+__global__ __launch_bounds__(DOUT_THREADS) void detout_class_kernel(DetOutArgs p) {
+    detout_class_body<DOUT_THREADS, PER, false>(p, DetTileArgs{});
+}
+
+template <int DOUT_THREADS, int PER>
+__global__ __launch_bounds__(DOUT_THREADS) void detout_tile_kernel(DetOutArgs p, DetTileArgs tp) {
+    detout_class_body<DOUT_THREADS, PER, true>(p, tp);
+}
+
+// TILE = true is the picture merge of tiled DetectionOutput: the lists are a picture's classes, the key carries the tile in bits
+// 24..31 (so the anchor field is read with 15 bits), `tile_out` receives it, and conf / idx / tile_out may be null.
+template <bool TILE>
+__device__ __forceinline__ void detout_merge_body(DetOutArgs p, int* tile_out) {
     __shared__ __attribute__((aligned(16))) u64 lkeys[DOUT_MAX_K];
     __shared__ unsigned lvals[DOUT_MAX_K];
     __shared__ int s_off[MRG_NCLS + 1], s_red[MRG_WAVES];
@@ -1686,14 +1727,142 @@ __global__ __launch_bounds__(MRG_THREADS) void detout_merge_kernel(DetOutArgs p)
     for (int f = tid; f < total && f < p.out_cap; f += MRG_THREADS) {
         const u64 key = lkeys[f];
         const size_t dst = (size_t)b * p.out_cap + f;
-        p.out.conf[dst] = __uint_as_float((unsigned)(key >> 32));
-        p.out.cls[dst] = 127 - (int)(key & 127ull);
-        p.out.idx[dst] = 32767 - (int)((key >> 8) & 0xFFFFull);
+        if constexpr (TILE) {
+            if (p.out.conf) p.out.conf[dst] = __uint_as_float((unsigned)(key >> 32));
+            p.out.cls[dst] = 127 - (int)(key & 127ull);
+            if (p.out.idx) p.out.idx[dst] = 32767 - (int)((key >> 8) & 0x7FFFull);
+            if (tile_out) tile_out[dst] = 255 - (int)((key >> 24) & 0xFFull);
+        } else {
+            p.out.conf[dst] = __uint_as_float((unsigned)(key >> 32));
+            p.out.cls[dst] = 127 - (int)(key & 127ull);
+            p.out.idx[dst] = 32767 - (int)((key >> 8) & 0xFFFFull);
+        }
         const int4 bx = p.cls_box[img + lvals[f]];
         int* ob = p.out.box + dst * 4;      // (four stores: with out_cap = keep_top_k the caller's rows need not be 16-byte aligned)
         ob[0] = bx.x; ob[1] = bx.y; ob[2] = bx.z; ob[3] = bx.w;
     }
     if (tid == 0) p.out.count[b] = total;
+}
+
+__global__ __launch_bounds__(MRG_THREADS) void detout_merge_kernel(DetOutArgs p) { detout_merge_body<false>(p, nullptr); }
+
+__global__ __launch_bounds__(MRG_THREADS) void detout_tile_picture_kernel(DetOutArgs p, int* tile_out) {
+    detout_merge_body<true>(p, tile_out);
+}
+
+// Class merge of tiled DetectionOutput: one workgroup per (picture, class).  Thread t owns the sorted list that tile t of the
+// picture wrote for the class; the nms_top_k-th largest key of their union is found as detout_merge_kernel finds its cut (a
+// bitwise search over the key, every list answering "how many of my keys are >= trial" by bisection), so the up to
+// 256 * nms_top_k records of the picture are never sorted.  The <= nms_top_k selected records are gathered into LDS, sorted,
+// suppressed (nms_segment on the picture-grid boxes) and written, in order, to the picture's [C][nms_top_k] slot.
+struct DetTileMergeArgs {
+    const int* img_first;       // [n_images + 1]
+    int C, k;
+    const int* tcount; const u64* tkeys; const int4* tbox;      // [n_tiles][C] and [n_tiles][C][k]: the tile stage's lists
+    int* pcount; u64* pkeys; int4* pbox;                        // [n_images][C] and [n_images][C][k]
+};
+
+__global__ __launch_bounds__(MRG_THREADS) void detout_tile_class_kernel(DetTileMergeArgs p) {
+    __shared__ __attribute__((aligned(16))) u64 lkeys[DOUT_MAX_K];
+    __shared__ unsigned lvals[DOUT_MAX_K];
+    __shared__ int4 sbox[DOUT_MAX_K], snbox[DOUT_MAX_K];
+    __shared__ unsigned char alive[DOUT_MAX_K];
+    __shared__ int s_off[MERGE_MAX_TILES + 1], s_red[MRG_WAVES];
+    static_assert(MERGE_MAX_TILES <= MRG_THREADS && DOUT_MAX_K <= 1024, "a thread per list; 10 bits of the payload for the record");
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int C = p.C, k = p.k;
+    const int img = blockIdx.x / C, c = blockIdx.x - img * C;
+    const int T0 = p.img_first[img], nt = p.img_first[img + 1] - T0;      // 1..MERGE_MAX_TILES (checked on the host)
+    const size_t mylist = (size_t)(T0 + min(tid, nt - 1)) * C + c;
+    const u64* kc = p.tkeys + mylist * k;
+    const int cnt = tid < nt ? min(max(p.tcount[mylist], 0), k) : 0;
+    const int N = dout_block_sum<MRG_WAVES>(cnt, s_red);
+    int lo = 0, hi = cnt;                     // (as in detout_merge_body)
+    if (N > k) {
+        u64 T = 0ull;
+        for (int bit = 63; bit >= 0; --bit) {
+            const u64 trial = T | (1ull << bit);
+            int l = lo, h = hi;
+            while (l < h) {
+                const int mid = (l + h) >> 1;
+                if (kc[mid] >= trial) l = mid + 1; else h = mid;
+            }
+            if (dout_block_sum<MRG_WAVES>(l, s_red) >= k) { T = trial; hi = l; }
+            else lo = l;
+        }
+    }
+    // exclusive prefix of the lists' shares
+    int inc = hi;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    if (lane == 63) s_red[wave] = inc;
+    __syncthreads();
+    int wbase0 = 0;
+#pragma unroll
+    for (int w = 0; w < MRG_WAVES; ++w)
+        if (w < wave) wbase0 += s_red[w];
+    if (tid < MERGE_MAX_TILES) s_off[tid + 1] = wbase0 + inc;
+    if (tid == 0) s_off[0] = 0;
+    __syncthreads();
+    const int total = min(s_off[MERGE_MAX_TILES], k);      // (== s_off[MERGE_MAX_TILES]: the keys are unique)
+    const int n2 = next_pow2(total > 1 ? total : 1);
+    for (int f = tid; f < n2; f += MRG_THREADS) {
+        u64 key = 0ull;
+        unsigned src = 0u;
+        if (f < total) {
+            int l = 0, h = MERGE_MAX_TILES - 1;      // the list that holds the f-th selected record
+            while (l < h) {
+                const int mid = (l + h + 1) >> 1;
+                if (s_off[mid] <= f) l = mid; else h = mid - 1;
+            }
+            const int j = f - s_off[l];
+            src = ((unsigned)l << 10) | (unsigned)j;
+            key = p.tkeys[((size_t)(T0 + l) * C + c) * k + j];
+        }
+        lkeys[f] = key;
+        lvals[f] = src;
+    }
+    __syncthreads();
+    merge_sort_desc(lkeys, lvals, n2);
+    for (int q = tid; q < total; q += MRG_THREADS) {
+        const unsigned src = lvals[q];
+        const int4 bx = p.tbox[((size_t)(T0 + (int)(src >> 10)) * C + c) * k + (src & 1023u)];
+        int o[4] = {bx.x, bx.y, bx.z, bx.w}, nb[4];
+        nms_roundtrip(o, nb);
+        sbox[q] = bx;
+        snbox[q] = make_int4(nb[0], nb[1], nb[2], nb[3]);
+        alive[q] = 1;
+    }
+    __syncthreads();
+    if (wave == 0) nms_segment(snbox, alive, 0, total, lane);
+    __syncthreads();
+    const size_t slot = (size_t)blockIdx.x * k;
+    int kept = 0;
+    for (int q0 = 0; q0 < total; q0 += MRG_THREADS) {
+        const int q = q0 + tid;
+        const bool keep = q < total && alive[q];
+        const u64 bal = __ballot(keep);
+        if (lane == 0) s_red[wave] = __popcll(bal);
+        __syncthreads();
+        int wbase = kept, tot = 0;
+#pragma unroll
+        for (int i = 0; i < MRG_WAVES; ++i) {
+            if (i < wave) wbase += s_red[i];
+            tot += s_red[i];
+        }
+        if (keep) {
+            const int o = wbase + __popcll(bal & ((1ull << lane) - 1ull));
+            p.pkeys[slot + o] = lkeys[q];
+            p.pbox[slot + o] = sbox[q];
+        }
+        kept += tot;
+        __syncthreads();
+    }
+    if (tid == 0) p.pcount[blockIdx.x] = kept;
 }
 
 static size_t align256(size_t n) { return (n + 255) / 256 * 256; }
@@ -1737,6 +1906,159 @@ void detection_output(int A, int num_classes, const double* anchors, const float
     {
         ProfScope prof("detout_merge", 0.0, 0.0, s);
         hipLaunchKernelGGL(detout_merge_kernel, dim3(B), dim3(MRG_THREADS), 0, s, a);
+    }
+    HIP_OK(hipGetLastError());
+}
+
+// =================================================================================
+// tiled DetectionOutput: every tile decoded per class, one NMS per class over the picture's tiles
+// =================================================================================
+// workspace: the tile table and img_first, then the tile lists (count, key, box per (tile, class)) and the picture lists
+// (the same per (picture, class)); detout_tiles_add and detout_tiles_merge carve it alike from (n_tiles, n_images, C, k).
+struct DetTilesWs {
+    MergeTile* tiles; int* img_first;
+    int* tcount; u64* tkeys; int4* tbox;
+    int* pcount; u64* pkeys; int4* pbox;
+    size_t head_ints, bytes;
+};
+
+static DetTilesWs detout_tiles_carve(void* ws, int n_tiles, int n_images, int C, int k) {
+    DetTilesWs w{};
+    char* base = (char*)ws;
+    const size_t tl = (size_t)n_tiles * C, pl = (size_t)n_images * C;
+    w.head_ints = (size_t)n_tiles * 8 + (size_t)n_images + 1;
+    w.tiles = (MergeTile*)base; w.img_first = (int*)base + (size_t)n_tiles * 8; base += align256(w.head_ints * 4);
+    w.tcount = (int*)base; base += align256(tl * 4);
+    w.tkeys = (u64*)base; base += align256(tl * k * 8);
+    w.tbox = (int4*)base; base += align256(tl * k * 16);
+    w.pcount = (int*)base; base += align256(pl * 4);
+    w.pkeys = (u64*)base; base += align256(pl * k * 8);
+    w.pbox = (int4*)base; base += align256(pl * k * 16);
+    w.bytes = (size_t)(base - (char*)ws);
+    return w;
+}
+
+// every limit of the tile table; fills the head that goes to the device: the tiles, then img_first [n_images + 1]
+static void detout_tiles_plan(const char* who, const MergeTile* tiles, int n_tiles, int n_images, std::vector<int>& head) {
+    SSD_REQUIRE(tiles != nullptr, "%s: null argument", who);
+    SSD_REQUIRE(n_tiles >= 1 && n_tiles <= DET_MAX_BATCH, "%s: 1..%d tiles (got %d)", who, DET_MAX_BATCH, n_tiles);
+    SSD_REQUIRE(n_images >= 1 && n_images <= n_tiles, "%s: 1..n_tiles pictures (got %d for %d tiles)", who, n_images, n_tiles);
+    SSD_REQUIRE(tiles[0].image == 0 && tiles[n_tiles - 1].image == n_images - 1,
+                "%s: image indices must ascend from 0 to n_images - 1 = %d (first %d, last %d)", who, n_images - 1, tiles[0].image,
+                tiles[n_tiles - 1].image);
+    head.assign((size_t)n_tiles * 8 + (size_t)n_images + 1, 0);
+    MergeTile* ht = reinterpret_cast<MergeTile*>(head.data());
+    int* first = head.data() + (size_t)n_tiles * 8;
+    for (int t = 0, img = -1; t < n_tiles; ++t) {
+        const MergeTile& tl = tiles[t];
+        const int im = tl.image;
+        SSD_REQUIRE(im == img || im == img + 1, "%s: image indices must ascend without gaps (tile %d: image %d after %d)", who, t, im, img);
+        SSD_REQUIRE(tl.img_w >= 1 && tl.img_h >= 1 && tl.img_w <= MERGE_MAX_SIDE && tl.img_h <= MERGE_MAX_SIDE,
+                    "%s: tile %d: picture of %d x %d outside 1..%d", who, t, tl.img_w, tl.img_h, MERGE_MAX_SIDE);
+        SSD_REQUIRE(tl.x0 >= 0 && tl.y0 >= 0 && tl.w >= 1 && tl.h >= 1 && tl.x0 <= tl.img_w - tl.w && tl.y0 <= tl.img_h - tl.h,
+                    "%s: tile %d (%d, %d, %d x %d) leaves its %d x %d picture", who, t, tl.x0, tl.y0, tl.w, tl.h, tl.img_w, tl.img_h);
+        SSD_REQUIRE(tl.interior >= 0 && tl.interior <= 15, "%s: tile %d: interior = %d outside 0..15", who, t, tl.interior);
+        if (im != img) {
+            img = im;
+            first[img] = t;
+        } else {
+            SSD_REQUIRE(tl.img_w == tiles[t - 1].img_w && tl.img_h == tiles[t - 1].img_h,
+                        "%s: tile %d: the tiles of picture %d disagree about its size", who, t, im);
+        }
+        ht[t] = tl;
+    }
+    first[n_images] = n_tiles;
+    for (int i = 0; i < n_images; ++i)
+        SSD_REQUIRE(first[i + 1] - first[i] <= MERGE_MAX_TILES, "%s: picture %d has %d tiles, at most %d", who, i, first[i + 1] - first[i],
+                    MERGE_MAX_TILES);
+}
+
+static void detout_tiles_sizes(const char* who, int A, int num_classes, int nms_top_k) {
+    SSD_REQUIRE(A >= 1 && A <= 32767, "%s: at most 32767 anchors (got %d)", who, A);
+    SSD_REQUIRE(num_classes >= 1 && num_classes <= MAX_CLASSES, "%s: num_classes must be in 1..%d (got %d)", who, MAX_CLASSES, num_classes);
+    SSD_REQUIRE(nms_top_k >= 1 && nms_top_k <= DOUT_MAX_K, "%s: nms_top_k must be in 1..%d (got %d)", who, DOUT_MAX_K, nms_top_k);
+}
+
+size_t detout_tiles_ws_bytes(int A, int num_classes, int n_tiles, int n_images, int nms_top_k) {
+    const char* who = "detout_tiles_ws_bytes";
+    detout_tiles_sizes(who, A, num_classes, nms_top_k);
+    SSD_REQUIRE(n_tiles >= 1 && n_tiles <= DET_MAX_BATCH, "%s: 1..%d tiles (got %d)", who, DET_MAX_BATCH, n_tiles);
+    SSD_REQUIRE(n_images >= 1 && n_images <= n_tiles, "%s: 1..n_tiles pictures (got %d for %d tiles)", who, n_images, n_tiles);
+    return detout_tiles_carve(nullptr, n_tiles, n_images, num_classes, nms_top_k).bytes;
+}
+
+void detout_tiles_add_check(const char* who, int A, int num_classes, const MergeTile* tiles, int n_tiles, int first, int b, float conf_thr,
+                            int nms_top_k, std::vector<int>& head) {
+    detout_tiles_sizes(who, A, num_classes, nms_top_k);
+    SSD_REQUIRE(std::isfinite(conf_thr) && conf_thr >= 0.f, "%s: the confidence threshold must be finite and >= 0", who);
+    SSD_REQUIRE(tiles != nullptr && n_tiles >= 1, "%s: at least one tile", who);
+    detout_tiles_plan(who, tiles, n_tiles, tiles[n_tiles - 1].image + 1, head);
+    SSD_REQUIRE(first >= 0 && b >= 1 && b <= n_tiles - first, "%s: tiles %d .. %d + %d outside the %d tiles of the table", who, first, first, b,
+                n_tiles);
+}
+
+void detout_tiles_merge_check(const char* who, int num_classes, const MergeTile* tiles, int n_tiles, int n_images, int nms_top_k,
+                              int keep_top_k, int out_cap, std::vector<int>& head) {
+    detout_tiles_sizes(who, 1, num_classes, nms_top_k);
+    SSD_REQUIRE(keep_top_k >= 1 && keep_top_k <= DOUT_MAX_K, "%s: keep_top_k must be in 1..%d (got %d)", who, DOUT_MAX_K, keep_top_k);
+    SSD_REQUIRE(out_cap >= 1, "%s: out_cap must be >= 1 (got %d)", who, out_cap);
+    detout_tiles_plan(who, tiles, n_tiles, n_images, head);
+}
+
+static void detout_tiles_ws_check(const char* who, const void* ws, size_t ws_bytes, size_t need) {
+    SSD_REQUIRE(ws != nullptr && ((uintptr_t)ws & 15) == 0, "%s: the workspace must be a 16-byte aligned device pointer", who);
+    SSD_REQUIRE(ws_bytes >= need, "%s: the workspace holds %zu bytes, %zu are needed", who, ws_bytes, need);
+}
+
+void detout_tiles_add(const char* who, int A, int num_classes, const double* anchors, const float* pred, const MergeTile* tiles,
+                      int n_tiles, int first, int b, float conf_thr, int nms_top_k, int edge_margin, void* ws, size_t ws_bytes,
+                      hipStream_t s) {
+    std::vector<int> head;
+    detout_tiles_add_check(who, A, num_classes, tiles, n_tiles, first, b, conf_thr, nms_top_k, head);
+    SSD_REQUIRE(anchors && pred, "%s: null argument", who);
+    const int n_images = tiles[n_tiles - 1].image + 1;
+    const DetTilesWs w = detout_tiles_carve(ws, n_tiles, n_images, num_classes, nms_top_k);
+    detout_tiles_ws_check(who, ws, ws_bytes, w.bytes);
+    HIP_OK(hipMemcpyAsync(ws, head.data(), head.size() * sizeof(int), hipMemcpyHostToDevice, s));      // (pageable: copied by the call)
+    const size_t l0 = (size_t)first * num_classes;
+    DetOutArgs a{};
+    a.A = A; a.nv = num_classes + 5; a.C = num_classes; a.B = b; a.anchors = anchors; a.pred = pred; a.thr = conf_thr;
+    a.nms_top_k = nms_top_k;
+    a.cls_count = w.tcount + l0; a.cls_keys = w.tkeys + l0 * nms_top_k; a.cls_box = w.tbox + l0 * nms_top_k;
+    DetTileArgs t{w.tiles, w.img_first, first, edge_margin};
+    {
+        ProfScope prof("detout_tile", 0.0, (double)b * A * a.nv * 4.0, s);
+        const dim3 grid((unsigned)((size_t)b * num_classes));
+        if (A <= 256 * 35) hipLaunchKernelGGL((detout_tile_kernel<256, 35>), grid, dim3(256), 0, s, a, t);
+        else if (A <= 512 * 48) hipLaunchKernelGGL((detout_tile_kernel<512, 48>), grid, dim3(512), 0, s, a, t);
+        else hipLaunchKernelGGL((detout_tile_kernel<512, 64>), grid, dim3(512), 0, s, a, t);
+    }
+    HIP_OK(hipGetLastError());
+}
+
+void detout_tiles_merge(const char* who, int num_classes, const MergeTile* tiles, int n_tiles, int n_images, int nms_top_k, int keep_top_k,
+                        int out_cap, int* count_out, float* conf_out, int* cls_out, int* idx_out, int* tile_out, int* box_out, void* ws,
+                        size_t ws_bytes, hipStream_t s) {
+    std::vector<int> head;
+    detout_tiles_merge_check(who, num_classes, tiles, n_tiles, n_images, nms_top_k, keep_top_k, out_cap, head);
+    SSD_REQUIRE(count_out && cls_out && box_out, "%s: null argument", who);
+    const DetTilesWs w = detout_tiles_carve(ws, n_tiles, n_images, num_classes, nms_top_k);
+    detout_tiles_ws_check(who, ws, ws_bytes, w.bytes);
+    HIP_OK(hipMemcpyAsync(ws, head.data(), head.size() * sizeof(int), hipMemcpyHostToDevice, s));      // (pageable: copied by the call)
+    DetTileMergeArgs m{};
+    m.img_first = w.img_first; m.C = num_classes; m.k = nms_top_k;
+    m.tcount = w.tcount; m.tkeys = w.tkeys; m.tbox = w.tbox; m.pcount = w.pcount; m.pkeys = w.pkeys; m.pbox = w.pbox;
+    {
+        ProfScope prof("detout_tile_class", 0.0, 0.0, s);
+        hipLaunchKernelGGL(detout_tile_class_kernel, dim3((unsigned)((size_t)n_images * num_classes)), dim3(MRG_THREADS), 0, s, m);
+    }
+    DetOutArgs a{};
+    a.C = num_classes; a.B = n_images; a.nms_top_k = nms_top_k; a.keep_top_k = keep_top_k; a.out_cap = out_cap;
+    a.cls_count = w.pcount; a.cls_keys = w.pkeys; a.cls_box = w.pbox;
+    a.out = DetectOut{count_out, conf_out, cls_out, idx_out, box_out};
+    {
+        ProfScope prof("detout_tile_picture", 0.0, 0.0, s);
+        hipLaunchKernelGGL(detout_tile_picture_kernel, dim3(n_images), dim3(MRG_THREADS), 0, s, a, tile_out);
     }
     HIP_OK(hipGetLastError());
 }

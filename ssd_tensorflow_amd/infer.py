@@ -264,12 +264,13 @@ def main(argv=None):
     parser.add_argument('--jpeg-quality', type=int, default=95, help='--encoder gpu: JPEG quality 1..100 (95 = cv2.imwrite)')
     parser.add_argument('--jpeg-entropy', default='host', choices=['host', 'gpu'],
                         help='--encoder gpu: host: Huffman coding on host threads; gpu: on the GPU as well, only the files come back (same bytes)')
-    from .tiling import add_arguments as add_tile_arguments
+    from .tiling import add_arguments as add_tile_arguments, check_arguments as check_tile_arguments
     add_tile_arguments(parser)
     add_decode_arguments(parser)
     args = parser.parse_args(argv)
     check_fp8_arguments(parser, args)
     check_decode_arguments(parser, args)
+    check_tile_arguments(parser, args)
     if args.tile and args.dump_predictions:
         parser.error('--dump-predictions does not apply to --tile: a tiled picture has one prediction tensor per window')
     if args.tile and args.synthetic:
@@ -285,6 +286,8 @@ def main(argv=None):
     print('[i] Threshold:         ', args.threshold)
     print('[i] Pascal summary:    ', args.pascal_summary)
     print('[i] Annotate:          ', args.annotate)
+    if args.tile_decode != 'argmax':
+        print('[i] Tile decode:       ', '%s (nms top k %d, keep top k %d)' % (args.tile_decode, args.nms_top_k, args.keep_top_k))
     if args.decode != 'argmax':
         print('[i] Decode:            ', '%s (nms top k %d, keep top k %d)' % (args.decode, args.nms_top_k, args.keep_top_k))
 
@@ -430,7 +433,8 @@ def main(argv=None):
         pending = None
         if args.tile:       #  windows of the source picture through the net, their boxes merged on the GPU
             from . import tiling
-            detector = tiling.TiledDetector(net, args.tile, args.tile_overlap, args.tile_whole, args.tile_edge_margin, args.threshold, 200, 200)
+            detector = tiling.TiledDetector(net, args.tile, args.tile_overlap, args.tile_whole, args.tile_edge_margin, args.threshold, 200, 200,
+                                            **tiling.decode_keywords(args))
             for k, (packed, offs, shapes, idxs) in enumerate(tiling.source_batches(files, args.batch_size, sess.device, args.decoder,
                                                                                   args.decoder_entropy)):
                 if k == 0:

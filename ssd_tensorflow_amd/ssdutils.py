@@ -127,11 +127,18 @@ def detect_batch(pred, preset, confidence_threshold=0.01, detections_cap=200, ma
     return out
 
 
-def merge_tile_lists(tiles, count, conf, cls, idx, box, tile_cap, max_out=200, edge_margin=2, out_cap=None):
+def merge_tile_lists(tiles, count, conf, cls, idx, box, tile_cap, max_out=200, edge_margin=2, out_cap=None, decode='argmax'):
     """ssd_merge_tiles on host arrays: tiles = [(image, Tile, (W, H))] with the images ascending from 0; count [n_tiles], conf /
     cls / idx [n_tiles, tile_cap], box [n_tiles, tile_cap, 4] as detect_batch(nms=False) lays a tile's records out.  Returns one
-    dict per picture: conf, cls, idx, tile, box (the detections of tiling.TiledDetector, for tests and notebooks)."""
+    dict per picture: conf, cls, idx, tile, box (the detections of tiling.TiledDetector, for tests and notebooks).
+    These lists hold one record per anchor, i.e. the argmax decode: decode='all' has no host lists to merge (its per-class
+    candidates never leave the device) and is refused here; detect_tiles(decode='all') takes the predictions."""
     from .tiling import tile_structs
+    if decode not in ('argmax', 'all'):
+        raise ValueError("decode must be 'argmax' or 'all' (got %r)" % (decode,))
+    if decode == 'all':
+        raise ValueError("merge_tile_lists merges one record per anchor (decode='argmax'); decode='all' starts from the predictions: "
+                         'use detect_tiles(decode=\'all\')')
     n_tiles, tile_cap = len(tiles), int(tile_cap)
     n_images = (max(t[0] for t in tiles) + 1) if tiles else 0
     count = np.ascontiguousarray(count, np.int32).reshape(n_tiles)
@@ -158,11 +165,55 @@ def merge_tile_lists(tiles, count, conf, cls, idx, box, tile_cap, max_out=200, e
     return out
 
 
-def detect_tiles(pred, preset, tiles, thr, tile_cap=200, max_out=200, edge_margin=2):
+def check_tile_decode(decode, tile_cap=200, max_out=200):
+    """decode = 'argmax' | 'all' of the tiled path; tile_cap and max_out belong to 'argmax' and keep their defaults under 'all'"""
+    if decode not in ('argmax', 'all'):
+        raise ValueError("decode must be 'argmax' or 'all' (got %r)" % (decode,))
+    if decode == 'all' and (tile_cap != 200 or max_out != 200):
+        raise ValueError("decode='all' is bounded by nms_top_k and keep_top_k: tile_cap and max_out do not apply")
+    return decode
+
+
+def detection_output_tiles(pred, preset, tiles, thr, nms_top_k=400, keep_top_k=200, edge_margin=2, out_cap=None):
+    """ssd_detout_tiles on host predictions: pred [n_tiles, A, C+5], tiles = [(image, Tile, (W, H))] with the images
+    ascending from 0.  Every (anchor, class) pair of every tile is a candidate; per class one NMS over the picture's tiles, the
+    best keep_top_k of the picture.  Returns one dict per picture (conf, cls, idx, tile, box) in global confidence order (ties:
+    lower tile, lower anchor, lower class)."""
+    from .tiling import tile_structs
+    pred = np.ascontiguousarray(pred, np.float32)
+    if pred.ndim != 3 or pred.shape[0] != len(tiles):
+        raise ValueError('pred must be [n_tiles, A, C+5] with one entry per tile')
+    n_tiles, A, nv = pred.shape
+    p = _preset_for(A) if preset is None else preset
+    if p.num_anchors != A:
+        raise ValueError(f'pred has {A} anchors, preset {p.name} has {p.num_anchors}')
+    n_images = (max(t[0] for t in tiles) + 1) if tiles else 0
+    keep_top_k = int(keep_top_k)
+    out_cap = max(keep_top_k, 1) if out_cap is None else int(out_cap)
+    g, n = max(n_images, 1), max(out_cap, 1)
+    ocount = np.zeros(g, np.int32)
+    oconf = np.zeros((g, n), np.float32)
+    ocls, oidx, otile = (np.zeros((g, n), np.int32) for _ in range(3))
+    obox = np.zeros((g, n, 4), np.int32)
+    check(lib.ssd_detout_tiles(_pname(p), nv - 5, _lib.device(), np_ptr(pred), C.cast(tile_structs(tiles), C.c_void_p), n_tiles, n_images,
+                               float(thr), int(nms_top_k), keep_top_k, int(edge_margin), out_cap, np_ptr(ocount), np_ptr(oconf),
+                               np_ptr(ocls), np_ptr(oidx), np_ptr(otile), np_ptr(obox)))
+    out = []
+    for i in range(n_images):
+        m = min(int(ocount[i]), out_cap)
+        out.append(dict(conf=oconf[i, :m], cls=ocls[i, :m], idx=oidx[i, :m], tile=otile[i, :m], box=obox[i, :m]))
+    return out
+
+
+def detect_tiles(pred, preset, tiles, thr, tile_cap=200, max_out=200, edge_margin=2, decode='argmax', nms_top_k=400, keep_top_k=200):
     """Tiled detection on host predictions: pred [n_tiles, A, C+5], one row of anchors per tile; tiles = [(image, Tile, (W, H))]
     (tiling.plan_tiles), the images ascending from 0.  Every tile is decoded (decode_boxes, the first tile_cap records), the
     records of a picture are merged on the GPU (ssd_merge_tiles: edge drop, the picture's 1000 grid, one NMS over all tiles).
-    The mirror of detect_batch; returns one dict per picture: conf, cls, idx, tile, box."""
+    The mirror of detect_batch; returns one dict per picture: conf, cls, idx, tile, box.
+    decode='all': every class of an anchor is a candidate (detection_output_tiles with nms_top_k / keep_top_k; tile_cap and
+    max_out do not apply)."""
+    if check_tile_decode(decode, tile_cap, max_out) == 'all':
+        return detection_output_tiles(pred, preset, tiles, thr, nms_top_k, keep_top_k, edge_margin)
     pred = np.ascontiguousarray(pred, np.float32)
     if pred.ndim != 3 or pred.shape[0] != len(tiles):
         raise ValueError('pred must be [n_tiles, A, C+5] with one entry per tile')

@@ -118,10 +118,17 @@ class TiledDetector:
     handle's max_batch (a picture's tiles may span batches), decodes every batch's result with ssd_decode_nms_dev(nms = 0) into
     the tile lists and merges them with ONE ssd_merge_tiles_dev; everything is enqueued on the net's stream and nothing waits for
     the GPU between the batches.  Two output sets alternate, as in the handle: a caller may launch the next pictures before it
-    collects these."""
+    collects these.
+    decode='all' (DESIGN.md 28): every class of an anchor is a candidate.  ssd_detout_tiles_add_dev follows every infer_dev and one
+    ssd_detout_tiles_merge_dev ends the pass: the same ticket and output sets, out_cap = keep_top_k, the detections in global
+    confidence order.  tile_cap and max_out belong to 'argmax': other values than their defaults raise."""
 
-    def __init__(self, net, tile, overlap=0.25, whole=True, edge_margin=2, threshold=0.5, tile_cap=200, max_out=200):
+    def __init__(self, net, tile, overlap=0.25, whole=True, edge_margin=2, threshold=0.5, tile_cap=200, max_out=200, decode='argmax',
+                 nms_top_k=400, keep_top_k=200):
+        from .ssdutils import check_tile_decode
         plan_tiles(tile, tile, tile, overlap, whole)         # (validates tile and overlap)
+        self.decode = check_tile_decode(decode, tile_cap, max_out)
+        self.nms_top_k, self.keep_top_k = int(nms_top_k), int(keep_top_k)
         self.net, self.tile, self.overlap, self.whole = net, int(tile), float(overlap), bool(whole)
         self.edge_margin, self.threshold = int(edge_margin), float(threshold)
         self.tile_cap = int(tile_cap)
@@ -133,6 +140,7 @@ class TiledDetector:
         self._lists = None
         self._anchors = None
         self._det_ws = None
+        self._all_ws = None
         self._last = None
 
     # ---- planning ---------------------------------------------------------------------------------------
@@ -171,8 +179,17 @@ class TiledDetector:
         if self._anchors is None:
             self._anchors = torch.empty((net.preset.num_anchors, 4), dtype=torch.float64, device=dev)
             check(lib.ssd_anchors_dev(net.preset.name.encode(), self._anchors.data_ptr(), None, ptr or None))
+        if self._det_ws is None and self.decode == 'argmax':
             self._det_ws = torch.empty(max(int(lib.ssd_decode_nms_ws_bytes(net.preset.name.encode(), net.max_batch)), 16), dtype=torch.uint8,
                                        device=dev)
+        if self.decode == 'all':
+            # the per-class lists of every tile and picture live in one workspace, written and read in stream order
+            ws_bytes = int(lib.ssd_detout_tiles_ws_bytes(net.preset.name.encode(), net.num_vars - 5, n_tiles, n_images, self.nms_top_k))
+            if ws_bytes == 0:
+                raise RuntimeError(_lib.last_error())
+            if self._all_ws is None or self._all_ws.numel() < ws_bytes:
+                self._all_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            return self._out_set(n_images, out_cap, dev)
         # the tile lists are written and read in stream order: one set serves every launch
         if self._lists is None or self._lists['count'].shape[0] < n_tiles:
             self._lists = dict(count=torch.zeros(n_tiles, **i32), conf=torch.zeros((n_tiles, cap), dtype=torch.float32, device=dev),
@@ -183,6 +200,10 @@ class TiledDetector:
             raise RuntimeError(_lib.last_error())
         if self._lists['ws'] is None or self._lists['ws'].numel() < ws_bytes:
             self._lists['ws'] = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        return self._out_set(n_images, out_cap, dev)
+
+    def _out_set(self, n_images, out_cap, dev):
+        import torch
         which = self._serial & 1
         s = self._sets[which]
         if s is None or s[0]['count'].shape[0] != n_images or s[0]['cls'].shape[1] != out_cap:
@@ -205,6 +226,8 @@ class TiledDetector:
         per_image = max(sum(1 for t in tiles if t[0] == i) for i in range(n_images))
         mo = -1 if self.max_out is None else self.max_out
         out_cap = max(mo, 1) if mo >= 0 else per_image * cap
+        if self.decode == 'all':
+            out_cap = max(self.keep_top_k, 1)
         dev = packed.device
         ptr, stream = self._stream(dev)
         pname = net.preset.name.encode()
@@ -215,18 +238,32 @@ class TiledDetector:
             L = self._lists
             result = C.c_void_p()
             k = 0
+            structs = C.cast(tile_structs(tiles), C.c_void_p)
             for x in self.batches(packed, offs, shapes, tiles):
                 b = x.shape[0]
                 net.infer_dev(x)
                 check(lib.ssd_result_dev(net._h, C.byref(result)))
+                if self.decode == 'all':
+                    # the handle's result buffer is reused by the next batch: its tiles are decoded now
+                    check(lib.ssd_detout_tiles_add_dev(pname, nfg, self._anchors.data_ptr(), result.value, structs, n_tiles, k, b,
+                                                       self.threshold, self.nms_top_k, self.edge_margin, self._all_ws.data_ptr(),
+                                                       self._all_ws.numel(), ptr or None))
+                    k += b
+                    continue
                 check(lib.ssd_decode_nms_dev(pname, nfg, self._anchors.data_ptr(), result.value, b, self.threshold, cap, -1, cap, 0,
                                              L['count'][k:].data_ptr(), L['conf'][k:].data_ptr(), L['cls'][k:].data_ptr(),
                                              L['idx'][k:].data_ptr(), L['box'][k:].data_ptr(), self._det_ws.data_ptr(), ptr or None))
                 k += b
-            check(lib.ssd_merge_tiles_dev(C.cast(tile_structs(tiles), C.c_void_p), n_tiles, n_images, cap, L['count'].data_ptr(),
-                                          L['conf'].data_ptr(), L['cls'].data_ptr(), L['idx'].data_ptr(), L['box'].data_ptr(),
-                                          self.edge_margin, mo, out_cap, d['count'].data_ptr(), d['conf'].data_ptr(), d['cls'].data_ptr(),
-                                          d['idx'].data_ptr(), d['tile'].data_ptr(), d['box'].data_ptr(), L['ws'].data_ptr(), ptr or None))
+            if self.decode == 'all':
+                check(lib.ssd_detout_tiles_merge_dev(nfg, structs, n_tiles, n_images, self.nms_top_k, self.keep_top_k, out_cap,
+                                                     d['count'].data_ptr(), d['conf'].data_ptr(), d['cls'].data_ptr(), d['idx'].data_ptr(),
+                                                     d['tile'].data_ptr(), d['box'].data_ptr(), self._all_ws.data_ptr(),
+                                                     self._all_ws.numel(), ptr or None))
+            else:
+                check(lib.ssd_merge_tiles_dev(structs, n_tiles, n_images, cap, L['count'].data_ptr(),
+                                              L['conf'].data_ptr(), L['cls'].data_ptr(), L['idx'].data_ptr(), L['box'].data_ptr(),
+                                              self.edge_margin, mo, out_cap, d['count'].data_ptr(), d['conf'].data_ptr(), d['cls'].data_ptr(),
+                                              d['idx'].data_ptr(), d['tile'].data_ptr(), d['box'].data_ptr(), L['ws'].data_ptr(), ptr or None))
             for key in d:
                 h[key].copy_(d[key], non_blocking=True)
             done = torch.cuda.Event()
@@ -279,6 +316,28 @@ def add_arguments(parser):
     parser.add_argument('--tile-whole', type=str2bool, default='True', help='--tile: also detect on the whole shrunk picture (keeps the large objects)')
     parser.add_argument('--tile-edge-margin', type=int, default=2,
                         help='--tile: drop a box within this many thousandths of an interior window edge (the window cut it); -1 keeps all')
+    parser.add_argument('--tile-decode', default='argmax', choices=['argmax', 'all'],
+                        help="--tile: the decode of the windows (--decode names the untiled pass's decode and does not apply to --tile). "
+                             "argmax: one candidate per anchor of a window; all: the SSD paper's DetectionOutput across the windows, every class "
+                             'of an anchor above the threshold is a candidate, per class the best --nms-top-k of the picture go through one NMS '
+                             'over all windows and the best --keep-top-k of the picture are kept, in confidence order (DESIGN.md 28)')
+
+
+def check_arguments(parser, args):
+    """--tile-decode all needs --tile and --nms-top-k / --keep-top-k in range"""
+    if args.tile_decode == 'all':
+        if not args.tile:
+            parser.error('--tile-decode all needs --tile N (the untiled pass takes --decode all)')
+        for name in ('nms_top_k', 'keep_top_k'):
+            if not 1 <= getattr(args, name) <= 1024:
+                parser.error('--%s must be in 1..1024' % name.replace('_', '-'))
+
+
+def decode_keywords(args):
+    """the decode keywords of TiledDetector for these arguments"""
+    if args.tile_decode == 'all':
+        return dict(decode='all', nms_top_k=args.nms_top_k, keep_top_k=args.keep_top_k)
+    return {}
 
 
 def source_batches(files, batch_size, device=0, decoder='pillow', decoder_entropy='host'):

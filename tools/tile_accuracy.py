@@ -4,8 +4,11 @@ schedule of tools/fp8_accuracy.py), pastes the 128 held-out 300 x 300 pictures i
 shifted and scaled) and evaluates VOC07 mAP (threshold 0.5, NMS, 200 boxes) of the untiled pass -- the mosaic shrunk to 300 x 300
 in one piece -- and of --tile 400 --tile-overlap 0.25 with and without the edge drop, on one f32 handle.  Next to the result:
 what ONE missed object per class changes in mAP.  No number is fixed in advance.
+--tile-decodes evaluates --tile under both tile decodes instead -- argmax (tile_cap 200, 200 boxes) and all (nms_top_k
+400, keep_top_k 200) -- at thresholds 0.5 and 0.01, edge drop 2, with the whole view.
 
     python tools/tile_accuracy.py [--epochs 40] [--checkpoint final.npz] [--out profiles/tile_accuracy.txt]
+    python tools/tile_accuracy.py --tile-decodes [--out profiles/tile_detout_accuracy.txt]
 """
 import argparse
 import contextlib
@@ -30,6 +33,7 @@ def main():
     ap.add_argument('--checkpoint', default='', help='evaluate this checkpoint instead of training one')
     ap.add_argument('--tile', type=int, default=400)
     ap.add_argument('--tile-overlap', type=float, default=0.25)
+    ap.add_argument('--tile-decodes', action='store_true', help='compare the two tile decodes at thresholds 0.5 and 0.01')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     import torch
@@ -112,8 +116,15 @@ def main():
                 plans.append(plan)
             net.infer_dev(T.augment_batch(plans, side, side, device=sess.device))
             results['untiled'] = score(net.detect_last_launch(len(plans), 0.5, 200, None).get())
-            for name, margin, whole in (('tile %d, edge drop 2' % args.tile, 2, True), ('tile %d, no edge drop' % args.tile, -1, True),
-                                        ('tile %d, edge drop 2, no whole view' % args.tile, 2, False)):
+            decodes = {}
+            for thr in (0.5, 0.01) if args.tile_decodes else ():
+                for decode in ('argmax', 'all'):
+                    det = tiling.TiledDetector(net, args.tile, args.tile_overlap, True, 2, thr, 200, 200, decode=decode)
+                    ticket = det.launch(packed, offs, shapes)
+                    decodes['tile %d, threshold %.2f, tile decode %s' % (args.tile, thr, decode)] = score(ticket.get()) + (len(ticket.tiles) // len(mosaics),)
+            for name, margin, whole in () if args.tile_decodes else (
+                    ('tile %d, edge drop 2' % args.tile, 2, True), ('tile %d, no edge drop' % args.tile, -1, True),
+                    ('tile %d, edge drop 2, no whole view' % args.tile, 2, False)):
                 det = tiling.TiledDetector(net, args.tile, args.tile_overlap, whole, margin, 0.5, 200, 200)
                 ticket = det.launch(packed, offs, shapes)
                 results[name] = score(ticket.get()) + (len(ticket.tiles) // len(mosaics),)
@@ -122,6 +133,15 @@ def main():
         for name, r in results.items():
             say('  %-36s mAP %.4f   %s   (%d detections%s)' % (name, r[0], '  '.join('%s %.4f' % (k, v) for k, v in sorted(r[1].items())), r[2],
                                                              ', %d tiles per mosaic' % r[3] if len(r) > 3 else ''))
+        if decodes:
+            say('# the two tile decodes (DESIGN.md 28): argmax = tile_cap 200, 200 boxes; all = nms_top_k 400, keep_top_k 200; edge drop 2, whole view')
+            for name, r in decodes.items():
+                say('  %-44s mAP %.4f   %s   (%d detections, %d tiles per mosaic)'
+                    % (name, r[0], '  '.join('%s %.4f' % (k, v) for k, v in sorted(r[1].items())), r[2], r[3]))
+            for thr in ('0.50', '0.01'):
+                a, b = (decodes['tile %d, threshold %s, tile decode %s' % (args.tile, thr, d)][0] for d in ('all', 'argmax'))
+                say('# threshold %s: all - argmax = %+.4f' % (thr, a - b))
+            say('# VOC / COCO AP under the two tile decodes is NOT measured: there is no such data set here, only these mosaics of synthetic shapes')
         allow = one_miss_allowance(counts)
         base = results['untiled'][0]
         for name, r in results.items():
