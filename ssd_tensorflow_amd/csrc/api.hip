@@ -190,8 +190,11 @@ static EncodeCache::Anchors& encode_anchors(EncodeCache& ec, const Preset& p, in
     return an;
 }
 
+// match_dev / match_host: where the [b*A] winning-box indices go (at most one of the two; both null: not wanted)
 static void encode_labels_impl(const char* preset, int num_classes, int device, const double* gt, const int* cls,
-                               const int* offsets, int b, float* vec_dev, float* vec_host, hipStream_t s) {
+                               const int* offsets, int b, float* vec_dev, float* vec_host, hipStream_t s,
+                               int match = MATCH_REFERENCE, int* match_dev = nullptr, int* match_host = nullptr) {
+    require_match(match);                // before any HIP call
     const Preset& p = get_preset(preset);
     SSD_REQUIRE(b >= 1, "batch must be >= 1");
     require_num_classes(num_classes);
@@ -208,8 +211,9 @@ static void encode_labels_impl(const char* preset, int num_classes, int device, 
     const size_t n = (size_t)b * A * (num_classes + 5);
     auto up = [](size_t v) { return (v + 255) / 256 * 256; };
     const size_t o_gt = 0, o_cls = o_gt + up(nt * 4 * sizeof(double)), o_off = o_cls + up(nt * sizeof(int)),
-                 o_ws = o_off + up((size_t)(b + 1) * sizeof(int)), o_tmp = o_ws + up(encode_labels_ws_bytes(ntot)),
-                 need = o_tmp + (vec_dev ? 0 : n * sizeof(float));
+                 o_ws = o_off + up((size_t)(b + 1) * sizeof(int)), o_tmp = o_ws + up(encode_labels_ws_bytes_ex(ntot, b, match)),
+                 o_match = o_tmp + up(vec_dev ? 0 : n * sizeof(float)),
+                 need = o_match + (match_host ? (size_t)b * A * sizeof(int) : 0);
     EncodeCache::Scratch& sc = ec.scratch[device];
     if (need > sc.bytes) {
         if (sc.p) HIP_OK(hipFree(sc.p));
@@ -221,14 +225,16 @@ static void encode_labels_impl(const char* preset, int num_classes, int device, 
     int* dcls = (int*)(sc.p + o_cls);
     int* doff = (int*)(sc.p + o_off);
     float* out = vec_dev ? vec_dev : (float*)(sc.p + o_tmp);
+    int* mout = match_host ? (int*)(sc.p + o_match) : match_dev;
     try {
         if (ntot) {
             HIP_OK(hipMemcpyAsync(dgt, gt, (size_t)ntot * 4 * sizeof(double), hipMemcpyHostToDevice, s));
             HIP_OK(hipMemcpyAsync(dcls, cls, (size_t)ntot * sizeof(int), hipMemcpyHostToDevice, s));
         }
         HIP_OK(hipMemcpyAsync(doff, offsets, (size_t)(b + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-        encode_labels(p, num_classes, an.anc, an.aabs, dgt, dcls, doff, b, ntot, out, sc.p + o_ws, s);
+        encode_labels_ex(p, num_classes, an.anc, an.aabs, dgt, dcls, doff, b, ntot, out, mout, match, sc.p + o_ws, s);
         if (vec_host) HIP_OK(hipMemcpyAsync(vec_host, out, n * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (match_host) HIP_OK(hipMemcpyAsync(match_host, mout, (size_t)b * A * sizeof(int), hipMemcpyDeviceToHost, s));
     } catch (...) {
         (void)hipStreamSynchronize(s);   // nothing of this call may still be using the shared scratch when the lock is released
         throw;
@@ -250,11 +256,43 @@ int ssd_encode_labels_dev(const char* preset, int num_classes, int device, const
     API_END
 }
 
+int ssd_encode_labels_ex(const char* preset, int num_classes, int device, const double* gt_boxes, const int* gt_cls,
+                         const int* gt_offsets, int b, float* vec_out, int match, int* match_out) {
+    API_BEGIN
+    encode_labels_impl(preset, num_classes, device, gt_boxes, gt_cls, gt_offsets, b, nullptr, vec_out, nullptr, match, nullptr, match_out);
+    API_END
+}
+
+int ssd_encode_labels_dev_ex(const char* preset, int num_classes, int device, const double* gt_boxes, const int* gt_cls,
+                             const int* gt_offsets, int b, float* vec_out_dev, void* stream, int match, int* match_out_dev) {
+    API_BEGIN
+    encode_labels_impl(preset, num_classes, device, gt_boxes, gt_cls, gt_offsets, b, vec_out_dev, nullptr, (hipStream_t)stream, match,
+                       match_out_dev, nullptr);
+    API_END
+}
+
 size_t ssd_encode_labels_ws_bytes(int ntot) { return (encode_labels_ws_bytes(ntot) + 255) / 256 * 256; }
+
+size_t ssd_encode_labels_ws_bytes_ex(int ntot, int b, int match) {
+    try {
+        return (encode_labels_ws_bytes_ex(ntot, b, match) + 255) / 256 * 256;
+    } catch (const std::exception& e) {
+        ssd::set_error("%s", e.what());
+        return 0;
+    }
+}
 
 int ssd_encode_labels_resident(const char* preset, int num_classes, int device, const double* gt_boxes_dev, const int* gt_cls_dev,
                                const int* gt_offsets_dev, int b, int ntot, float* vec_out_dev, void* ws_dev, void* stream) {
+    return ssd_encode_labels_resident_ex(preset, num_classes, device, gt_boxes_dev, gt_cls_dev, gt_offsets_dev, b, ntot, vec_out_dev,
+                                         ws_dev, stream, SSD_MATCH_REFERENCE, nullptr);
+}
+
+int ssd_encode_labels_resident_ex(const char* preset, int num_classes, int device, const double* gt_boxes_dev, const int* gt_cls_dev,
+                                  const int* gt_offsets_dev, int b, int ntot, float* vec_out_dev, void* ws_dev, void* stream,
+                                  int match, int* match_out_dev) {
     API_BEGIN
+    require_match(match);                // before any HIP call
     const Preset& p = get_preset(preset);
     SSD_REQUIRE(b >= 1 && ntot >= 0, "batch must be >= 1 and ntot >= 0");
     require_num_classes(num_classes);
@@ -268,7 +306,8 @@ int ssd_encode_labels_resident(const char* preset, int num_classes, int device, 
         EncodeCache::Anchors& an = encode_anchors(ec, p, device);
         anc = an.anc; aabs = an.aabs;
     }
-    encode_labels(p, num_classes, anc, aabs, gt_boxes_dev, gt_cls_dev, gt_offsets_dev, b, ntot, vec_out_dev, ws_dev, (hipStream_t)stream);
+    encode_labels_ex(p, num_classes, anc, aabs, gt_boxes_dev, gt_cls_dev, gt_offsets_dev, b, ntot, vec_out_dev, match_out_dev, match, ws_dev,
+                     (hipStream_t)stream);
     API_END
 }
 

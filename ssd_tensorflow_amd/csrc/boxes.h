@@ -39,6 +39,17 @@ void jaccard_device(const double* box, const double* arr, int n, double* iou, hi
 size_t encode_labels_ws_bytes(int ntot);
 void encode_labels(const Preset& p, int num_classes, const double* anchors, const int* anchors_abs, const double* gt,
                    const int* cls, const int* offsets, int B, int ntot, float* vec, void* ws, hipStream_t s);
+// The same with a matching rule.  MATCH_REFERENCE: the encoder above, kernel for kernel.  MATCH_PAPER: first
+// every box is matched one-to-one to the free anchor it overlaps best, whatever the IoU (greedy by IoU; ties: lower
+// anchor, then lower box), then the remaining anchors take their best box above 0.5.  match_out [B][A] (device, may be
+// null): the winning box's index within its image, -1 for a background row; filled under both rules.
+// ws: encode_labels_ws_bytes_ex(ntot, B, match) bytes.  Any other `match` fails (require_match) before anything is enqueued.
+constexpr int MATCH_REFERENCE = 0, MATCH_PAPER = 1;
+void require_match(int match);
+size_t encode_labels_ws_bytes_ex(int ntot, int B, int match);
+void encode_labels_ex(const Preset& p, int num_classes, const double* anchors, const int* anchors_abs, const double* gt,
+                      const int* cls, const int* offsets, int B, int ntot, float* vec, int* match_out, int match, void* ws,
+                      hipStream_t s);
 
 // decode_boxes + suppress_overlaps (+ the caller's [:max_out]) for a batch.
 struct DetectOut {

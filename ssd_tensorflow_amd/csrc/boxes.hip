@@ -169,12 +169,14 @@ __global__ __launch_bounds__(256) void gt_best_kernel(int A, const int* __restri
 
 // one thread per (image, anchor): the winning GT box (pass 1: every 'good' overlap, higher IoU
 // wins, earlier box keeps a tie; pass 2: 'best' matches override, same rule among them) and
-// the encoded row (ssdutils.py:173-179, transforms.py:47-55).
+// the encoded row (ssdutils.py:173-179, transforms.py:47-55).  match_out (may be null): the winner's index within its image, -1: none.
+// Behind match_bipartite_kernel (match = paper) best_a holds at most one box per anchor: pass 1 is the per-anchor stage, pass 2
+// keeps the bipartite matches on top.
 __global__ __launch_bounds__(256) void label_rows_kernel(int A, int C, int B, const double* __restrict__ anchors,
                                                          const int* __restrict__ aabs, const double* __restrict__ gt,
                                                          const int* __restrict__ cls, const int* __restrict__ offsets,
                                                          const int* __restrict__ gabs, const int* __restrict__ best_a,
-                                                         float* __restrict__ vec) {
+                                                         float* __restrict__ vec, int* __restrict__ match_out) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= B * A) return;
     const int b = idx / A, a = idx - b * A;
@@ -194,6 +196,7 @@ __global__ __launch_bounds__(256) void label_rows_kernel(int A, int C, int B, co
         }
     }
     const int win = w2 >= 0 ? w2 : w1;
+    if (match_out) match_out[idx] = win >= 0 ? win - offsets[b] : -1;      // the box's index within its image
     float* row = vec + (size_t)idx * (C + 5);
     for (int c = 0; c < C + 5; ++c) row[c] = 0.f;
     if (win < 0) {
@@ -229,19 +232,177 @@ void jaccard_device(const double* box, const double* arr, int n, double* iou, hi
     HIP_OK(hipGetLastError());
 }
 
+// ---------------------------------------------------------------------------------
+// match = paper: the bipartite stage of the SSD paper's matching.  Greedy and one-to-one: among all pairs
+// (box not yet matched, anchor not yet taken) that intersect, the pair of greatest IoU is matched, exact ties going to
+// the lower anchor and then to the lower box; repeated until every box is matched or no pair is left.
+// One workgroup per image.  Every live box caches its best free anchor (greatest IoU, lowest anchor on a tie): the
+// pair to match is then the best of the cached ones under (IoU, lower anchor, lower box), and a box looks at the A
+// anchors again only when the anchor it cached has been taken.  A rescan is one wave's work (the 16 waves rescan 16
+// boxes side by side); box j of a chunk of 1024 belongs to lane j / 16 of wave j % 16, so neighbouring boxes -- the
+// ones that compete for the same anchors -- spread over the waves.  The first MATCH_LDS_BOXES boxes of the image keep
+// their state in LDS, the rest in the workspace: no limit on the boxes of an image.  The taken anchors are a bitmap
+// in LDS.  No atomics; the result does not depend on any execution order.
+// It leaves gabs and best_a (the anchor a box won, -1: none) as gt_best_kernel does: label_rows_kernel's pass 1 is the
+// per-anchor stage, and its pass 2 -- now at most one box per anchor -- keeps the bipartite matches on top.
+constexpr int MATCH_THREADS = 1024;
+constexpr int MATCH_WAVES = MATCH_THREADS / 64;
+constexpr int MATCH_LDS_BOXES = 32;
+constexpr int MATCH_MAX_ANCHORS = 24576;      // bitmap capacity (vgg512: 24564)
+constexpr int MATCH_BATCH = 8;                // anchor rows a lane has in flight during a rescan
+constexpr int MATCH_STALE = -2, MATCH_NONE = -1;
+
+// is (i1 / u1, a1, g1) ahead of (i2 / u2, a2, g2): greater IoU, then lower anchor, then lower box
+__device__ __forceinline__ bool match_ahead(long long i1, long long u1, int a1, int g1, long long i2, long long u2, int a2, int g2) {
+    const long long l = i1 * u2, r = i2 * u1;
+    return l > r || (l == r && (a1 < a2 || (a1 == a2 && g1 < g2)));
+}
+
+__global__ __launch_bounds__(MATCH_THREADS) void match_bipartite_kernel(int A, const int* __restrict__ aabs, const double* __restrict__ gt,
+                                                                        const int* __restrict__ offsets, int* __restrict__ gabs,
+                                                                        int* best_a, int* c_in, int* c_un, int* c_a) {
+    __shared__ unsigned taken[MATCH_MAX_ANCHORS / 32];
+    __shared__ int l_box[MATCH_LDS_BOXES][4], l_in[MATCH_LDS_BOXES], l_un[MATCH_LDS_BOXES], l_a[MATCH_LDS_BOXES], l_best[MATCH_LDS_BOXES];
+    __shared__ long long r_i[MATCH_WAVES], r_u[MATCH_WAVES];
+    __shared__ int r_a[MATCH_WAVES], r_g[MATCH_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g0 = offsets[blockIdx.x], n = offsets[blockIdx.x + 1] - g0;
+    if (n <= 0) return;                                  // workgroup uniform
+    for (int i = tid; i < MATCH_MAX_ANCHORS / 32; i += MATCH_THREADS) taken[i] = 0u;
+    for (int j = tid; j < n; j += MATCH_THREADS) {
+        const int g = g0 + j;
+        int o[4];
+        prop2abs_f64(gt[g * 4 + 0], gt[g * 4 + 1], gt[g * 4 + 2], gt[g * 4 + 3], o);
+        for (int e = 0; e < 4; ++e) gabs[g * 4 + e] = o[e];
+        best_a[g] = -1;
+        if (j < MATCH_LDS_BOXES) {
+            for (int e = 0; e < 4; ++e) l_box[j][e] = o[e];
+            l_best[j] = -1; l_a[j] = MATCH_STALE;
+        } else {
+            c_a[g] = MATCH_STALE;
+        }
+    }
+    __syncthreads();
+    const int nchunk = (n + MATCH_THREADS - 1) / MATCH_THREADS;
+    for (int round = 0; round < n; ++round) {
+        long long bi = -1, bu = 1;                       // this thread's best cached pair; (-1, 1): none, behind every real one
+        int ba = INT_MAX, bg = INT_MAX;
+        for (int c = 0; c < nchunk; ++c) {
+            const int j = c * MATCH_THREADS + lane * MATCH_WAVES + wave;
+            const bool lds = j < MATCH_LDS_BOXES;
+            bool live = false;
+            int ca = MATCH_NONE, ci = 0, cu = 1;
+            if (j < n) {
+                live = (lds ? l_best[j] : best_a[g0 + j]) < 0;
+                if (live) {
+                    ca = lds ? l_a[j] : c_a[g0 + j];
+                    if (ca >= 0) { ci = lds ? l_in[j] : c_in[g0 + j]; cu = lds ? l_un[j] : c_un[g0 + j]; }
+                }
+            }
+            const bool stale = live && (ca == MATCH_STALE || (ca >= 0 && ((taken[ca >> 5] >> (ca & 31)) & 1u)));
+            u64 todo = __ballot(stale);
+            while (todo) {                               // wave uniform: one rescan per stale box of this wave
+                const int l = __builtin_ctzll(todo);
+                todo &= todo - 1ull;
+                const int jj = c * MATCH_THREADS + l * MATCH_WAVES + wave;
+                int box[4];
+                for (int e = 0; e < 4; ++e) box[e] = jj < MATCH_LDS_BOXES ? l_box[jj][e] : gabs[(g0 + jj) * 4 + e];
+                const long long areab = (long long)(box[1] - box[0] + 1) * (box[3] - box[2] + 1);
+                long long si = 0, su = 1;                // (0, 1): only an anchor with a positive intersection gets ahead
+                int sa = INT_MAX;
+                // MATCH_BATCH rows of the table (L2) are in flight before the first is used (index clamped, not predicated);
+                // iou_terms' 64-bit products only for the anchors that touch the box.  What is left is instruction issue:
+                // A / 64 passes of ~40 instructions, ~2.3 us of the CU per rescan for vgg300 (profiles/label_match_rate.txt).
+                for (int a0 = lane; a0 < A; a0 += 64 * MATCH_BATCH) {
+                    int4 an[MATCH_BATCH];
+#pragma unroll
+                    for (int k = 0; k < MATCH_BATCH; ++k)      // (tables come from hipMalloc: 16-byte aligned)
+                        an[k] = *reinterpret_cast<const int4*>(aabs + (size_t)min(a0 + 64 * k, A - 1) * 4);
+#pragma unroll
+                    for (int k = 0; k < MATCH_BATCH; ++k) {
+                        const int a = a0 + 64 * k;
+                        const int w = min(box[1], an[k].y) - max(box[0], an[k].x) + 1;
+                        const int h = min(box[3], an[k].w) - max(box[2], an[k].z) + 1;
+                        if (a < A && w > 0 && h > 0 && !((taken[a >> 5] >> (a & 31)) & 1u)) {
+                            const long long in = (long long)w * h;
+                            const long long un = areab + (long long)(an[k].y - an[k].x + 1) * (an[k].w - an[k].z + 1) - in;
+                            if (in * su > si * un) { si = in; su = un; sa = a; }         // strict: the lower anchor keeps a tie
+                        }
+                    }
+                }
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    const long long oi = __shfl_xor(si, o, 64), ou = __shfl_xor(su, o, 64);
+                    const int oa = __shfl_xor(sa, o, 64);
+                    if (match_ahead(oi, ou, oa, 0, si, su, sa, 0)) { si = oi; su = ou; sa = oa; }
+                }
+                if (lane == l) { ca = sa == INT_MAX ? MATCH_NONE : sa; ci = (int)si; cu = (int)su; }
+            }
+            if (stale) {
+                if (lds) { l_a[j] = ca; l_in[j] = ci; l_un[j] = cu; }
+                else { c_a[g0 + j] = ca; c_in[g0 + j] = ci; c_un[g0 + j] = cu; }
+            }
+            if (live && ca >= 0 && match_ahead(ci, cu, ca, j, bi, bu, ba, bg)) { bi = ci; bu = cu; ba = ca; bg = j; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const long long oi = __shfl_xor(bi, o, 64), ou = __shfl_xor(bu, o, 64);
+            const int oa = __shfl_xor(ba, o, 64), og = __shfl_xor(bg, o, 64);
+            if (match_ahead(oi, ou, oa, og, bi, bu, ba, bg)) { bi = oi; bu = ou; ba = oa; bg = og; }
+        }
+        if (lane == 0) { r_i[wave] = bi; r_u[wave] = bu; r_a[wave] = ba; r_g[wave] = bg; }
+        __syncthreads();
+        bi = r_i[0]; bu = r_u[0]; ba = r_a[0]; bg = r_g[0];
+        for (int w = 1; w < MATCH_WAVES; ++w)
+            if (match_ahead(r_i[w], r_u[w], r_a[w], r_g[w], bi, bu, ba, bg)) { bi = r_i[w]; bu = r_u[w]; ba = r_a[w]; bg = r_g[w]; }
+        if (ba == INT_MAX) break;                        // workgroup uniform: no pair with a positive intersection is left
+        if (tid == 0) {
+            taken[ba >> 5] |= 1u << (ba & 31);
+            best_a[g0 + bg] = ba;
+            if (bg < MATCH_LDS_BOXES) l_best[bg] = ba;
+        }
+        __syncthreads();                                 // also: every thread has read r_* before the next round writes them
+    }
+}
+
 size_t encode_labels_ws_bytes(int ntot) { return (size_t)(ntot > 0 ? ntot : 1) * 7 * sizeof(int) + 64; }
 
 void encode_labels(const Preset& p, int num_classes, const double* anchors, const int* anchors_abs, const double* gt,
                    const int* cls, const int* offsets, int B, int ntot, float* vec, void* ws, hipStream_t s) {
+    encode_labels_ex(p, num_classes, anchors, anchors_abs, gt, cls, offsets, B, ntot, vec, nullptr, MATCH_REFERENCE, ws, s);
+}
+
+void require_match(int match) {
+    if (match != MATCH_REFERENCE && match != MATCH_PAPER) fail("match must be 0 (reference) or 1 (paper), got %d", match);
+}
+
+size_t encode_labels_ws_bytes_ex(int ntot, int B, int match) {
+    require_match(match);
+    (void)B;                                             // the bipartite stage keeps nothing per image outside LDS
+    return (size_t)(ntot > 0 ? ntot : 1) * (match == MATCH_PAPER ? 8 : 7) * sizeof(int) + 64;
+}
+
+void encode_labels_ex(const Preset& p, int num_classes, const double* anchors, const int* anchors_abs, const double* gt,
+                      const int* cls, const int* offsets, int B, int ntot, float* vec, int* match_out, int match, void* ws,
+                      hipStream_t s) {
+    require_match(match);
+    const size_t nt = ntot > 0 ? ntot : 1;
     int* gabs = (int*)ws;
-    int* best_a = gabs + (size_t)(ntot > 0 ? ntot : 1) * 4;
-    int* best_i = best_a + (ntot > 0 ? ntot : 1);
-    int* best_u = best_i + (ntot > 0 ? ntot : 1);
+    int* best_a = gabs + nt * 4;
+    int* best_i = best_a + nt;
+    int* best_u = best_i + nt;
     const int A = p.num_anchors;
-    if (ntot > 0)
+    if (match == MATCH_PAPER) {
+        if (A > MATCH_MAX_ANCHORS) fail("match = paper: %d anchors exceed the kernel's bitmap of %d", A, MATCH_MAX_ANCHORS);
+        if (ntot > 0)
+            hipLaunchKernelGGL(match_bipartite_kernel, dim3(B), dim3(MATCH_THREADS), 0, s, A, anchors_abs, gt, offsets, gabs, best_a,
+                               best_i, best_u, best_u + nt);
+    } else if (ntot > 0) {
         hipLaunchKernelGGL(gt_best_kernel, dim3(ntot), dim3(256), 0, s, A, anchors_abs, gt, ntot, gabs, best_a, best_i, best_u);
+    }
     hipLaunchKernelGGL(label_rows_kernel, dim3((B * A + 255) / 256), dim3(256), 0, s, A, num_classes, B, anchors, anchors_abs,
-                       gt, cls, offsets, gabs, best_a, vec);
+                       gt, cls, offsets, gabs, best_a, vec, match_out);
     HIP_OK(hipGetLastError());
 }
 

@@ -405,12 +405,25 @@ def prime_anchor_table(preset, table=None):
     return _ANCHORS_ABS[key]
 
 
-def has_positive_anchor(preset, boxes):
+MATCH_RULES = {'reference': 0, 'paper': 1}      # SSD_MATCH_REFERENCE, SSD_MATCH_PAPER (include/ssdvgg_hip.h)
+
+
+def match_id(match):
+    """The library's number of a matching rule name; anything else is a ValueError (raised before the GPU is touched)."""
+    if not isinstance(match, str) or match not in MATCH_RULES:
+        raise ValueError("match must be 'reference' or 'paper' (got %r)" % (match,))
+    return MATCH_RULES[match]
+
+
+def has_positive_anchor(preset, boxes, match='reference'):
     """Would LabelCreatorTransform mark at least one anchor positive for these Box records?  That is the only
     thing the reference's redraw loop looks at (training_data.py:92-95: num_bg < rows), and an anchor turns
     positive iff its IoU (+1 pixel, 1000-pixel grid) with some box exceeds 0.5 (transforms.py:76-107,
-    ssdutils.py:152-169).  A handful of boxes against the cached integer anchor table, on the host."""
+    ssdutils.py:152-169).  A handful of boxes against the cached integer anchor table, on the host.
+    match='paper': iff some box has a positive intersection with some anchor -- the bipartite stage then matches it
+    (DESIGN.md 29), and without one no anchor reaches 0.5 either."""
     from .utils import prop2abs, Size
+    paper = match_id(match) == MATCH_RULES['paper']
     an = prime_anchor_table(preset)
     area_a = (an[:, 1] - an[:, 0] + 1) * (an[:, 3] - an[:, 2] + 1)
     grid = Size(1000, 1000)
@@ -419,6 +432,10 @@ def has_positive_anchor(preset, boxes):
         w = np.maximum(0, np.minimum(xmax, an[:, 1]) - np.maximum(xmin, an[:, 0]) + 1)
         h = np.maximum(0, np.minimum(ymax, an[:, 3]) - np.maximum(ymin, an[:, 2]) + 1)
         inter = w * h
+        if paper:
+            if (inter > 0).any():
+                return True
+            continue
         iou = inter / ((xmax - xmin + 1) * (ymax - ymin + 1) + area_a - inter)
         if (iou > 0.5).any():
             return True
@@ -435,25 +452,41 @@ def _pack_gt(gt_boxes_list, gt_cls_list):
     return np.ascontiguousarray(gt, np.float64), np.ascontiguousarray(cls, np.int32), offs
 
 
-def encode_labels_batch(preset, num_classes, gt_boxes_list, gt_cls_list):
+def encode_labels_batch(preset, num_classes, gt_boxes_list, gt_cls_list, match='reference', return_match=False):
     """LabelCreatorTransform for a batch on the GPU: lists (one per image) of [n,4] float64
-    proportional (cx, cy, w, h) and [n] class ids -> [b, A, num_classes+5] float32 (host)."""
+    proportional (cx, cy, w, h) and [n] class ids -> [b, A, num_classes+5] float32 (host).
+    match: 'reference' or 'paper' (DESIGN.md 29).  return_match=True: also the [b, A] int32 array of each anchor's
+    winning box (its index within the image, -1: background)."""
+    mid = match_id(match)
     b = len(gt_boxes_list)
     gt, cls, offs = _pack_gt(gt_boxes_list, gt_cls_list)
     vec = np.empty((b, preset.num_anchors, num_classes + 5), np.float32)
-    check(lib.ssd_encode_labels(_pname(preset), int(num_classes), _lib.device(), np_ptr(gt), np_ptr(cls), np_ptr(offs), b, np_ptr(vec)))
-    return vec
+    if mid == 0 and not return_match:
+        check(lib.ssd_encode_labels(_pname(preset), int(num_classes), _lib.device(), np_ptr(gt), np_ptr(cls), np_ptr(offs), b, np_ptr(vec)))
+        return vec
+    mt = np.empty((b, preset.num_anchors), np.int32) if return_match else None
+    check(lib.ssd_encode_labels_ex(_pname(preset), int(num_classes), _lib.device(), np_ptr(gt), np_ptr(cls), np_ptr(offs), b, np_ptr(vec),
+                                   mid, np_ptr(mt)))
+    return (vec, mt) if return_match else vec
 
 
-def encode_labels_batch_dev(preset, num_classes, gt_boxes_list, gt_cls_list, device=None, out=None):
+def encode_labels_batch_dev(preset, num_classes, gt_boxes_list, gt_cls_list, device=None, out=None, match='reference', return_match=False):
     """The same, left in HBM: a float32 CUDA tensor [b, A, num_classes+5] on `device` (default: this module's
-    device).  The few ground-truth boxes go up, 873 KB per image never come down (ssd_encode_labels_dev)."""
+    device).  The few ground-truth boxes go up, 873 KB per image never come down (ssd_encode_labels_dev).
+    return_match=True: also the [b, A] int32 CUDA tensor of the winning boxes."""
+    mid = match_id(match)
     import torch
     device = _lib.device() if device is None else int(device)
     b = len(gt_boxes_list)
     gt, cls, offs = _pack_gt(gt_boxes_list, gt_cls_list)
     if out is None:
         out = torch.empty((b, preset.num_anchors, num_classes + 5), dtype=torch.float32, device=torch.device('cuda', device))
-    check(lib.ssd_encode_labels_dev(_pname(preset), int(num_classes), device, np_ptr(gt), np_ptr(cls), np_ptr(offs), b,
-                                    out.data_ptr(), torch.cuda.current_stream(device).cuda_stream))
-    return out
+    stream = torch.cuda.current_stream(device).cuda_stream
+    if mid == 0 and not return_match:
+        check(lib.ssd_encode_labels_dev(_pname(preset), int(num_classes), device, np_ptr(gt), np_ptr(cls), np_ptr(offs), b,
+                                        out.data_ptr(), stream))
+        return out
+    mt = torch.empty((b, preset.num_anchors), dtype=torch.int32, device=out.device) if return_match else None
+    check(lib.ssd_encode_labels_dev_ex(_pname(preset), int(num_classes), device, np_ptr(gt), np_ptr(cls), np_ptr(offs), b,
+                                       out.data_ptr(), stream, mid, mt.data_ptr() if return_match else None))
+    return (out, mt) if return_match else out

@@ -352,10 +352,13 @@ class SSDVGG:
         check(lib.ssd_get_global_step(self._h, C.byref(s)))
         return s.value
 
-    def save_checkpoint(self, path, lr=None, momentum=0.9, weight_decay=0.0005, class_names=None):
+    def save_checkpoint(self, path, lr=None, momentum=0.9, weight_decay=0.0005, class_names=None, match='reference'):
         """tf.train.Saver.save counterpart (train.py:336-343): one .npz, reference variable names.  `class_names`
-        (one per class id; default: training_data.default_class_names) is stored as a unicode array, no pickle."""
+        (one per class id; default: training_data.default_class_names) is stored as a unicode array, no pickle; `match`, the
+        matching rule the labels of the run were encoded with, as a string under __match__."""
         from .training_data import default_class_names
+        from .ssdutils import match_id
+        match_id(match)
         names = list(class_names) if class_names is not None else default_class_names(self._n_classes)
         if len(names) != self._n_classes:
             raise ValueError(f'{len(names)} class names for {self._n_classes} classes')
@@ -367,7 +370,7 @@ class SSDVGG:
                  __global_step__=np.array(self.global_step), __lr_values__=np.array(lr.values, np.float64),
                  __lr_boundaries__=np.array(lr.boundaries, np.int64), __momentum__=np.array(momentum),
                  __weight_decay__=np.array(weight_decay), __class_names__=np.array([str(n) for n in names], dtype=np.str_),
-                 __a_trous__=np.array(int(self.a_trous)))
+                 __a_trous__=np.array(int(self.a_trous)), __match__=np.array(str(match)))
         np.savez(path, **d)
 
     # ------------------------------------------------------------------ steps

@@ -145,6 +145,12 @@ class StepLoop:
             self.collect(*pending_det, ap_calc, image_samples)
 
 
+def checkpoint_match(path):
+    """The matching rule a checkpoint's run encoded its labels with (checkpoints from before the option: 'reference')."""
+    with np.load(path, allow_pickle=False) as ck:
+        return str(ck['__match__']) if '__match__' in ck.files else 'reference'
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description='Train the SSD')
     parser.add_argument('--name', default='test', help='project name')
@@ -167,6 +173,8 @@ def main(argv=None):
     add_ap_arguments(parser)
     parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='f32, or bf16 activations on the bf16 matrix cores (fp32 master weights, loss and optimizer)')
     parser.add_argument('--a-trous', type=str2bool, default='True', help='a fresh run: the a-trous graph (true) or the fc graph with the whole fc6 / fc7 (false; weights from <vgg-dir>/vgg16_ssd_fc.npz); --continue-training takes the checkpoint\'s')
+    parser.add_argument('--match', default='reference', choices=['reference', 'paper'], help="which ground-truth boxes get positive anchors: reference = only boxes some anchor overlaps with IoU > 0.5; paper = the SSD paper's matching, every box first gets the anchor it overlaps best (DESIGN.md 29); --continue-training takes the checkpoint's")
+    parser.add_argument('--shapes-size', default='0.2;0.5', help="--data-dir shapes: smallest and largest side of a rectangle, as fractions of the frame")
     parser.add_argument('--synthetic-train', type=int, default=64, help='synthetic training samples per epoch')
     parser.add_argument('--synthetic-valid', type=int, default=16)
     parser.add_argument('--synthetic-classes', type=int, default=20, help='class count of the synthetic data sets (1..127)')
@@ -214,19 +222,25 @@ def main(argv=None):
         start_epoch = max(int(f[1:-4]) for f in cands)
         ckpt = os.path.join(args.name, f'e{start_epoch}.npz')
         say('[i] Last checkpoint:      ', ckpt)
+        ck_match = checkpoint_match(ckpt)
+        if ck_match != args.match:
+            say("[i] --match %s disagrees with the checkpoint: continuing with its rule, '%s'" % (args.match, ck_match))
+            args.match = ck_match
     elif rank == 0:
         try:
             os.makedirs(args.name, exist_ok=True)
         except OSError as e:
             print('[!] Cannot create directory {}: {}'.format(args.name, e)); return 1      # train.py:143-145
 
+    say('[i] Matching rule:        ', args.match)
     if args.cache_gb < 0 or (args.cache_gb and args.decoder != 'gpu'):
         print('[!] --cache-gb keeps pictures decoded on the GPU: it needs --decoder gpu and a size >= 0'); return 1
     try:
         td = TrainingData(args.data_dir, args.preset, args.synthetic_train, args.synthetic_valid, rank=rank, world=world,
                           augment=args.augment, device=local, data_source=args.data_source,
-                          synthetic_classes=args.synthetic_classes, decoder=args.decoder, cache_bytes=int(args.cache_gb * 1e9))
-    except RuntimeError as e:
+                          synthetic_classes=args.synthetic_classes, decoder=args.decoder, cache_bytes=int(args.cache_gb * 1e9), match=args.match,
+                          shapes_size=[float(v) for v in args.shapes_size.split(';')])
+    except (RuntimeError, ValueError) as e:
         print('[!] Unable to load training data:', str(e)); return 1                       # train.py:155-161
     say('[i] # training samples:   ', td.num_train)
     say('[i] # validation samples: ', td.num_valid)
@@ -337,11 +351,11 @@ def main(argv=None):
             # ---- checkpoint (train.py:336-343) -------------------------------------------------
             if (e + 1) % args.checkpoint_interval == 0 and rank == 0:
                 path = '{}/e{}.npz'.format(args.name, e + 1)
-                net.save_checkpoint(path, lr, args.momentum, args.weight_decay, class_names=class_names)
+                net.save_checkpoint(path, lr, args.momentum, args.weight_decay, class_names=class_names, match=args.match)
                 print('[i] Checkpoint saved:', path)
         if rank == 0:
             path = '{}/final.npz'.format(args.name)
-            net.save_checkpoint(path, lr, args.momentum, args.weight_decay, class_names=class_names)
+            net.save_checkpoint(path, lr, args.momentum, args.weight_decay, class_names=class_names, match=args.match)
             print('[i] Checkpoint saved:', path)
         if writer is not None:
             writer.close()

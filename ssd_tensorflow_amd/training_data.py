@@ -54,7 +54,7 @@ import numpy as np
 
 from .data_queue import DataQueue, WorkerError
 from .parallel import ShardSampler
-from .ssdutils import (encode_labels_batch, encode_labels_batch_dev, get_preset_by_name, has_positive_anchor,
+from .ssdutils import (encode_labels_batch, encode_labels_batch_dev, get_preset_by_name, has_positive_anchor, match_id,
                        prime_anchor_table)
 from .utils import Box, Point, Size, Sample, load_data_source
 
@@ -136,7 +136,7 @@ class _Recipe:
                 # redrawn (<= 50 times) until at least one anchor is positive (training_data.py:92-98)
                 for tries in range(50):
                     img, gt = td._sample(int(i) + 7919 * tries, self.salt)
-                    if has_positive_anchor(td.preset, gt):
+                    if has_positive_anchor(td.preset, gt, td.match):
                         break
                 imgs.append(img); gts.append(gt)
             return dict({'images': np.stack(imgs)}, **_gt_packed(gts, td.num_classes)), gts
@@ -164,7 +164,7 @@ class _Recipe:
                     args = (None, None, sample)
                     for t in host_tfs:
                         args = t(*args)
-                    if has_positive_anchor(td.preset, args[2].boxes):
+                    if has_positive_anchor(td.preset, args[2].boxes, td.match):
                         break
                 plans.append(args[0]); gts.append(args[2].boxes)
         finally:
@@ -493,7 +493,14 @@ class TrainingData:
 
     def __init__(self, data_dir=None, preset='vgg300', num_train=64, num_valid=16, seed=1234, rank=0, world=1,
                  augment=False, sampler_trials=50, expand_prob=0.5, device=0, device_tensors=True,
-                 data_source='pascal_voc', valid_fraction=0.025, images=None, synthetic_classes=20, decoder='pillow', cache_bytes=0):
+                 data_source='pascal_voc', valid_fraction=0.025, images=None, synthetic_classes=20, decoder='pillow', cache_bytes=0,
+                 match='reference', shapes_size=(0.2, 0.5)):
+        match_id(match)                        # 'reference' or 'paper' (DESIGN.md 29); anything else: ValueError
+        self.match = match
+        lo, hi = (float(v) for v in shapes_size)   # 'shapes': the rectangles' sides, as fractions of the frame
+        if not 0 < lo <= hi <= 1:
+            raise ValueError('shapes_size must be (lo, hi) with 0 < lo <= hi <= 1 (got %r)' % (shapes_size,))
+        self.shapes_size = (lo, hi)
         if decoder not in DECODERS:
             raise ValueError("decoder must be 'pillow' or 'gpu' (got %r)" % (decoder,))
         if int(cache_bytes) < 0 or (cache_bytes and decoder != 'gpu'):
@@ -530,8 +537,8 @@ class TrainingData:
             self.train_samples, self.valid_samples = list(source.train_samples), list(source.valid_samples)
             self.num_train, self.num_valid = len(self.train_samples), len(self.valid_samples)
             self.augment = True
-            self.train_transforms = T.build_train_transforms(self.preset, self.num_classes, sampler_trials, expand_prob, images, decoder)
-            self.valid_transforms = T.build_valid_transforms(self.preset, self.num_classes, images, decoder)
+            self.train_transforms = T.build_train_transforms(self.preset, self.num_classes, sampler_trials, expand_prob, images, decoder, match)
+            self.valid_transforms = T.build_valid_transforms(self.preset, self.num_classes, images, decoder, match)
             self._max_image_bytes = max([s.imgsize.w * s.imgsize.h * 3 for s in self.train_samples + self.valid_samples] + [1])
             if decoder == 'gpu':
                 # int16 coefficients: at most 6 bytes per pixel of the MCU-padded frame (4:4:4; an MCU is at most 16 x 16)
@@ -552,8 +559,8 @@ class TrainingData:
             self.num_train, self.num_valid = num_train, num_valid
             self.augment = bool(augment)
             if self.augment:
-                self.train_transforms = T.build_train_transforms(self.preset, self.num_classes, sampler_trials, expand_prob)
-                self.valid_transforms = T.build_valid_transforms(self.preset, self.num_classes)
+                self.train_transforms = T.build_train_transforms(self.preset, self.num_classes, sampler_trials, expand_prob, match=match)
+                self.valid_transforms = T.build_valid_transforms(self.preset, self.num_classes, match=match)
                 self.train_samples = [self._dataset_sample(i, 0)[1] for i in range(num_train)]
                 self.valid_samples = [self._dataset_sample(i, 1 << 20)[1] for i in range(num_valid)]
                 self._max_image_bytes = 640 * 640 * 3
@@ -601,14 +608,14 @@ class TrainingData:
     def _labels(self, gts, out=None):
         bxs, cls = _gt_arrays(gts)
         if self.device_tensors:
-            return encode_labels_batch_dev(self.preset, self.num_classes, bxs, cls, self.device, out=out)
-        return encode_labels_batch(self.preset, self.num_classes, bxs, cls)
+            return encode_labels_batch_dev(self.preset, self.num_classes, bxs, cls, self.device, out=out, match=self.match)
+        return encode_labels_batch(self.preset, self.num_classes, bxs, cls, match=self.match)
 
     # ---- the learnable synthetic set ('shapes') --------------------------------------------------------------------
     SHAPE_CLASSES = 4      # textures, booked under the first four class ids (the net keeps the benchmark's shape)
 
     def _shapes_canvas(self, rng, W, H):
-        """uint8 BGR image [H, W, 3] + boxes: 1..3 non-overlapping rectangles of 20..50 % of the frame on low-contrast
+        """uint8 BGR image [H, W, 3] + boxes: 1..3 non-overlapping rectangles of 20..50 % of the frame (shapes_size) on low-contrast
         noise, each filled with a two-colour texture that IS its class -- 0 horizontal stripes, 1 vertical stripes,
         2 checkerboard, 3 diagonal stripes (either direction: a horizontal flip keeps every class).  Texture, not colour,
         because the reference's training recipe permutes channels and shifts hue / saturation / contrast
@@ -618,7 +625,7 @@ class TrainingData:
         placed = []
         for _ in range(n):
             for _try in range(20):
-                w, h = rng.uniform(0.2, 0.5, 2)
+                w, h = rng.uniform(self.shapes_size[0], self.shapes_size[1], 2)
                 cx, cy = rng.uniform(w / 2, 1 - w / 2), rng.uniform(h / 2, 1 - h / 2)
                 if all(abs(cx - q[0]) >= (w + q[2]) / 2 or abs(cy - q[1]) >= (h + q[3]) / 2 for q in placed):
                     placed.append((float(cx), float(cy), float(w), float(h)))
@@ -872,12 +879,15 @@ class TrainingData:
             check(lib.ssd_augment_batch_dev(sp + offs['packed'], C.c_void_p(arrays['params'].ctypes.data), b, W, H, images.data_ptr(),
                                             ring['ws'][dslot].data_ptr(), stream))
         ntot = int(arrays['gcls'].shape[0])
-        ws_need = lib.ssd_encode_labels_ws_bytes(ntot)
+        mid = match_id(self.match)
+        ws_need = lib.ssd_encode_labels_ws_bytes_ex(ntot, b, mid)
         if ring['enc_ws'][dslot] is None or ring['enc_ws'][dslot].numel() < ws_need:
-            ring['enc_ws'][dslot] = torch.empty((max(ws_need, lib.ssd_encode_labels_ws_bytes(ring['batch'] * 16)),), dtype=torch.uint8, device=dev)
+            ring['enc_ws'][dslot] = torch.empty((max(ws_need, lib.ssd_encode_labels_ws_bytes_ex(ring['batch'] * 16, ring['batch'], mid)),),
+                                                dtype=torch.uint8, device=dev)
         labels = ring['labels'][dslot][:b]
-        check(lib.ssd_encode_labels_resident(self.preset.name.encode(), self.num_classes, self.device, sp + offs['gt'], sp + offs['gcls'],
-                                             sp + offs['goff'], b, ntot, labels.data_ptr(), ring['enc_ws'][dslot].data_ptr(), stream))
+        check(lib.ssd_encode_labels_resident_ex(self.preset.name.encode(), self.num_classes, self.device, sp + offs['gt'], sp + offs['gcls'],
+                                                sp + offs['goff'], b, ntot, labels.data_ptr(), ring['enc_ws'][dslot].data_ptr(), stream,
+                                                mid, None))
         return images, labels
 
     # ---- the generators ----------------------------------------------------------------------------------------------

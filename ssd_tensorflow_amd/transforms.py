@@ -38,7 +38,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import lib, check
-from .ssdutils import encode_labels_batch
+from .ssdutils import encode_labels_batch, match_id
 from .utils import Size, Sample, Point, Box, box_like, abs2prop, prop2abs
 
 MAX_EXTRA = 16       # ssd_augment_params.extra_kind / extra_val
@@ -226,11 +226,15 @@ class ImageLoaderTransform(Transform):
 
 
 class LabelCreatorTransform(Transform):
-    """Parameters: preset, num_classes"""
+    """Parameters: preset, num_classes, match ('reference', the default, or 'paper': ssdutils.MATCH_RULES)"""
+    def __init__(self, preset=None, num_classes=None, match='reference', **kwargs):
+        match_id(match)                 # an unknown rule is refused here, not at the first sample
+        super().__init__(preset=preset, num_classes=num_classes, match=match, **kwargs)
+
     def __call__(self, data, label, gt):
         boxes = np.array([[b.center.x, b.center.y, b.size.w, b.size.h] for b in gt.boxes], np.float64).reshape(-1, 4)
         cls = np.array([b.labelid for b in gt.boxes], np.int32)
-        vec = encode_labels_batch(self.preset, self.num_classes, [boxes], [cls])[0]
+        vec = encode_labels_batch(self.preset, self.num_classes, [boxes], [cls], match=self.match)[0]
         return data, vec, gt
 
 
@@ -642,7 +646,7 @@ def build_sampler(overlap, trials):
                             min_jaccard_overlap=overlap, max_trials=trials)
 
 
-def build_train_transforms(preset, num_classes, sampler_trials, expand_prob, images=None, decoder='pillow'):
+def build_train_transforms(preset, num_classes, sampler_trials, expand_prob, images=None, decoder='pillow', match='reference'):
     """process_dataset.py:66-140"""
     if decoder not in DECODERS:
         raise ValueError("decoder must be 'pillow' or 'gpu' (got %r)" % (decoder,))
@@ -661,12 +665,12 @@ def build_train_transforms(preset, num_classes, sampler_trials, expand_prob, ima
     tf_sample_picker = SamplePickerTransform(samplers=samplers)
     tf_rnd_flip = RandomTransform(prob=0.5, transform=HorizontalFlipTransform())
     return [ImageLoaderTransform(images=images, decoder=decoder), tf_rnd_brightness, tf_distort, tf_rnd_reorder_channels, tf_rnd_expand,
-            tf_sample_picker, tf_rnd_flip, LabelCreatorTransform(preset=preset, num_classes=num_classes), tf_resize]
+            tf_sample_picker, tf_rnd_flip, LabelCreatorTransform(preset=preset, num_classes=num_classes, match=match), tf_resize]
 
 
-def build_valid_transforms(preset, num_classes, images=None, decoder='pillow'):
+def build_valid_transforms(preset, num_classes, images=None, decoder='pillow', match='reference'):
     """process_dataset.py:143-153"""
     if decoder not in DECODERS:
         raise ValueError("decoder must be 'pillow' or 'gpu' (got %r)" % (decoder,))
-    return [ImageLoaderTransform(images=images, decoder=decoder), LabelCreatorTransform(preset=preset, num_classes=num_classes),
+    return [ImageLoaderTransform(images=images, decoder=decoder), LabelCreatorTransform(preset=preset, num_classes=num_classes, match=match),
             ResizeTransform(width=preset.image_size.w, height=preset.image_size.h, algorithms=[INTER_LINEAR])]
