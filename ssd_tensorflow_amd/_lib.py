@@ -139,6 +139,8 @@ SIGNATURES = {
     'ssd_set_wgrad_stream': (i32, [handle, vp]),
     'ssd_set_loss_normalizer': (i32, [handle, f32]),
     'ssd_null_gradients_dev': (i32, [handle]),
+    'ssd_set_loss': (i32, [handle, vp]),
+    'ssd_get_loss': (i32, [handle, vp]),
     'ssd_train_step_dev': (i32, [handle, vp, vp, i32]),
     'ssd_eval_step_dev': (i32, [handle, vp, vp, i32]),
     'ssd_infer_dev': (i32, [handle, vp, i32]),
@@ -227,6 +229,8 @@ SIGNATURES = {
     'ssd_op_multibox_loss_ws_bytes': (sz, [i32, p_i32, p_i32, i32, C.POINTER(sz), p_i32]),
     'ssd_op_multibox_loss': (i32, [i32, p_i32, p_i32, i32, C.POINTER(vp), vp, vp, vp, i32, i32, i32, f32, vp, sz, f32, vp]),
     'ssd_op_multibox_loss_grad': (i32, [i32, p_i32, p_i32, i32, C.POINTER(vp), i32, vp, vp, vp, i32, i32, i32, vp]),
+    'ssd_op_multibox_loss_ex': (i32, [i32, p_i32, p_i32, i32, C.POINTER(vp), vp, vp, vp, i32, i32, i32, f32, vp, sz, f32, vp, vp]),
+    'ssd_op_multibox_loss_grad_ex': (i32, [i32, p_i32, p_i32, i32, C.POINTER(vp), i32, vp, vp, vp, i32, i32, i32, vp, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1176,6 +1176,31 @@ int ssd_set_loss_normalizer(ssd_handle h, float batch) {
     n.set_loss_normalizer(batch);
     API_END
 }
+// a loss configuration as the ABI takes it: refused here, on the host, before any HIP call (NULL means mining)
+static void check_loss_config(const ssd_loss_config* cfg) {
+    if (!cfg) return;
+    SSD_REQUIRE(cfg->kind == SSD_LOSS_MINING || cfg->kind == SSD_LOSS_FOCAL, "loss: kind %d is neither SSD_LOSS_MINING nor SSD_LOSS_FOCAL",
+                cfg->kind);
+    if (cfg->kind != SSD_LOSS_FOCAL) return;
+    SSD_REQUIRE(cfg->focal_gamma >= 0.f && cfg->focal_gamma <= 5.f, "loss: focal gamma %g outside [0, 5]", (double)cfg->focal_gamma);
+    SSD_REQUIRE(cfg->focal_alpha > 0.f && cfg->focal_alpha < 1.f, "loss: focal alpha %g outside (0, 1)", (double)cfg->focal_alpha);
+}
+int ssd_set_loss(ssd_handle h, const ssd_loss_config* cfg) {
+    API_BEGIN
+    SSD_REQUIRE(cfg != nullptr, "loss: null configuration");
+    check_loss_config(cfg);
+    Net& n = N(h);
+    SSD_REQUIRE(n.training(), "loss: the handle was created with training = 0");
+    if (cfg->kind == SSD_LOSS_FOCAL) n.set_loss(cfg->kind, cfg->focal_gamma, cfg->focal_alpha);
+    else n.set_loss(SSD_LOSS_MINING, 2.f, 0.25f);
+    API_END
+}
+int ssd_get_loss(ssd_handle h, ssd_loss_config* cfg) {
+    API_BEGIN
+    SSD_REQUIRE(cfg != nullptr, "loss: null configuration");
+    N(h).get_loss(&cfg->kind, &cfg->focal_gamma, &cfg->focal_alpha);
+    API_END
+}
 int ssd_null_gradients_dev(ssd_handle h) {
     API_BEGIN_NET(h)
     n.null_gradients_step();
@@ -1861,6 +1886,46 @@ int ssd_op_multibox_loss(int nmaps, const int* hw, const int* nj, int num_classe
     loss_work_carve(w, ws, b_total, L.A);
     if (filters) l2_partials(filters, nfilters, w, (hipStream_t)stream);
     multibox_loss(L, b, b_off, b_total, result, labels, w, weight_decay, bnorm, (hipStream_t)stream);
+    API_END
+}
+int ssd_op_multibox_loss_ex(int nmaps, const int* hw, const int* nj, int num_classes, void* const* heads, const float* labels,
+                            float* result, void* ws, int b, int b_off, int b_total, float bnorm, const float* filters,
+                            size_t nfilters, float weight_decay, const ssd_loss_config* cfg, void* stream) {
+    if (!cfg || cfg->kind == SSD_LOSS_MINING)
+        return ssd_op_multibox_loss(nmaps, hw, nj, num_classes, heads, labels, result, ws, b, b_off, b_total, bnorm, filters, nfilters,
+                                    weight_decay, stream);
+    API_BEGIN
+    check_loss_config(cfg);
+    HeadLayout L = loss_op_layout(nmaps, hw, nj, num_classes, b, b_off, b_total);
+    SSD_REQUIRE(heads && labels && result && ws, "null buffer");
+    for (int i = 0; i < nmaps; ++i) {
+        SSD_REQUIRE(heads[i], "null head buffer %d", i);
+        L.buf[i] = static_cast<float*>(heads[i]);
+    }
+    LossWork w;
+    loss_work_carve(w, ws, b_total, L.A);
+    if (filters) l2_partials(filters, nfilters, w, (hipStream_t)stream);
+    multibox_focal_loss(L, b, b_off, b_total, result, labels, w, weight_decay, bnorm, cfg->focal_gamma, cfg->focal_alpha,
+                        (hipStream_t)stream);
+    API_END
+}
+int ssd_op_multibox_loss_grad_ex(int nmaps, const int* hw, const int* nj, int num_classes, void* const* grads, int grads_bf16,
+                                 const float* labels, const float* result, void* ws, int b, int b_off, int b_total,
+                                 const ssd_loss_config* cfg, void* stream) {
+    if (!cfg || cfg->kind == SSD_LOSS_MINING)
+        return ssd_op_multibox_loss_grad(nmaps, hw, nj, num_classes, grads, grads_bf16, labels, result, ws, b, b_off, b_total, stream);
+    API_BEGIN
+    check_loss_config(cfg);
+    HeadLayout L = loss_op_layout(nmaps, hw, nj, num_classes, b, b_off, b_total);
+    SSD_REQUIRE(grads && labels && result && ws, "null buffer");
+    for (int i = 0; i < nmaps; ++i) {
+        SSD_REQUIRE(grads[i], "null gradient buffer %d", i);
+        L.dbuf[i] = grads[i];
+    }
+    L.grad_bf16 = grads_bf16 ? 1 : 0;
+    LossWork w;
+    loss_work_carve(w, ws, b_total, L.A);
+    multibox_focal_loss_grad(L, b, b_off, result, labels, w, cfg->focal_gamma, cfg->focal_alpha, (hipStream_t)stream);
     API_END
 }
 int ssd_op_multibox_loss_grad(int nmaps, const int* hw, const int* nj, int num_classes, void* const* grads, int grads_bf16,

@@ -125,6 +125,9 @@ public:
     void apply_gradients(float grad_scale);
     void backward_apply(int b, const float* y, float grad_scale);      // backward + update, the optimizer overlapped with backward's tail
     void set_loss_normalizer(float bnorm) { loss_bnorm_ = bnorm; }      // <= 0: every step's own batch size
+    // which loss the steps compute from the next forward on: 0 mining (the default), 1 focal with (gamma, alpha)
+    void set_loss(int kind, float gamma, float alpha) { loss_kind_ = kind; focal_gamma_ = gamma; focal_alpha_ = alpha; }
+    void get_loss(int* kind, float* gamma, float* alpha) const { *kind = loss_kind_; *gamma = focal_gamma_; *alpha = focal_alpha_; }
     void null_gradients_step();                                         // gradient arena of a step without samples
     void set_optimizer(const float* lr_values, const long long* bounds, int n, float momentum, float wd);
 
@@ -304,6 +307,9 @@ private:
     std::vector<long long> lr_bounds_;
     float momentum_ = 0.9f, wd_ = 0.0005f;
     float loss_bnorm_ = 0.f;
+    int loss_kind_ = 0;                     // SSD_LOSS_MINING / SSD_LOSS_FOCAL
+    int bw_loss_kind_ = 0;                  // the kind the last training forward computed: its backward takes the same
+    float focal_gamma_ = 2.f, focal_alpha_ = 0.25f, bw_gamma_ = 2.f, bw_alpha_ = 0.25f;
     Profiler prof_;
     int bw_pos_ = 0, bw_b_ = 0;          // next entry of bwd_order_
     size_t bw_done_off_ = 0;

@@ -98,6 +98,14 @@ void l2_partials(const float* filters, size_t nfilters, LossWork& w, hipStream_t
 void multibox_loss_grad(const HeadLayout& L, int B, int b_off, const float* result, const float* labels, const LossWork& w,
                         hipStream_t s);
 
+// The focal loss (softmax form) on the same buffers, lanes and workspace: heads_kernel<true> as above, then
+// focal_sample_kernel / focal_grad_kernel.  Every anchor contributes alpha_t * (1 - p_t)^gamma * ce, a sample is normalised
+// by max(pos_n, 1), sel is all ones; the gradient is dense.  gamma in [0, 5], alpha in (0, 1): checked by the callers.
+void multibox_focal_loss(const HeadLayout& L, int B, int b_off, int B_total, const float* result, const float* labels, LossWork& w,
+                         float weight_decay, float bnorm, float gamma, float alpha, hipStream_t s);
+void multibox_focal_loss_grad(const HeadLayout& L, int B, int b_off, const float* result, const float* labels, const LossWork& w,
+                              float gamma, float alpha, hipStream_t s);
+
 // ---- MomentumOptimizer without Nesterov (ssdvgg.py:586-588): acc = m*acc + g; w -= lr*acc
 void momentum_update(float* w, float* acc, const float* g, size_t n, float lr, float momentum, float gscale,
                      hipStream_t s);

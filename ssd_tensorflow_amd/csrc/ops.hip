@@ -1503,6 +1503,239 @@ void multibox_loss_grad(const HeadLayout& L, int B, int b_off, const float* resu
     HIP_OK(hipGetLastError());
 }
 
+// ---- focal loss (Lin et al. 2017), softmax form, on what the head kernels store per anchor -------------------------
+// With ce = -log p_t from heads_kernel<true>:  p_t = exp(-ce),  q = 1 - p_t = -expm1(-ce)  (never 1 - exp(-ce): the small
+// cross entropies of easy anchors would lose every digit),  alpha_t = alpha (positive) or 1 - alpha (background),
+//   fl    = alpha_t * q^gamma * ce                                  exactly 0 at ce == 0 for every gamma, 0 included
+//   kappa = alpha_t * q^gamma * (1 + gamma * p_t * ce / q)          d fl / d logit_c = kappa * (softmax_c - label_c)
+// kappa is alpha_t * (q^gamma + gamma * p_t * ce * q^(gamma-1)) with q^gamma factored out: ce / q -> 1 as q -> 0, so no
+// factor grows without bound for 0 < gamma < 1; q == 0 (ce == 0) is decided apart: alpha_t at gamma == 0, else 0.
+// Every anchor contributes, nothing is selected; a sample is normalised by n_b = max(pos_n, 1), so a sample without
+// positives still trains its background anchors (under mining it contributes exactly 0).
+// gmode: gamma when it is 0, 1 or 2 (no powf on those), -1 otherwise.
+__device__ __forceinline__ float focal_qpow(float q, float gamma, int gmode) {
+    if (gmode == 0) return 1.f;
+    if (gmode == 1) return q;
+    if (gmode == 2) return q * q;
+    return powf(q, gamma);
+}
+__device__ __forceinline__ float focal_term(float ce, bool pos, float gamma, float alpha, int gmode) {
+    if (ce == 0.f) return 0.f;
+    const float q = -expm1f(-ce);
+    return (pos ? alpha : 1.f - alpha) * focal_qpow(q, gamma, gmode) * ce;
+}
+__device__ __forceinline__ float focal_kappa(float ce, bool pos, float gamma, float alpha, int gmode) {
+    const float at = pos ? alpha : 1.f - alpha;
+    const float q = -expm1f(-ce);
+    if (!(q > 0.f)) return gmode == 0 ? at : 0.f;
+    return at * focal_qpow(q, gamma, gmode) * (1.f + gamma * expf(-ce) * (ce / q));
+}
+
+// One workgroup per sample, the lanes and the completion ticket of loss_sample_kernel: three block sums (positives, focal
+// terms, smooth-L1), sel = 1 on every valid anchor, sample = (sum fl / n_b, sum sl1 / n_b, 1 / (n_b * bnorm), pos_n).
+template <int PT>
+__global__ __launch_bounds__(LS_THREADS) void focal_sample_kernel(int B, int b_off, int A, float bnorm, float gamma, float alpha,
+                                                                  int gmode, const float* __restrict__ ce,
+                                                                  const float* __restrict__ sl1,
+                                                                  const unsigned char* __restrict__ pos,
+                                                                  unsigned char* __restrict__ sel, float* __restrict__ sample,
+                                                                  const float* __restrict__ partial, int npartial, float wd,
+                                                                  float* __restrict__ losses, unsigned* __restrict__ ticket) {
+    __shared__ double dred[LS_WAVES];
+    __shared__ unsigned sh_last;
+    __shared__ float red[3 * LS_WAVES];
+    const int tid = threadIdx.x, b = (int)blockIdx.x + b_off;
+    const float* cb = ce + (size_t)b * A;
+    const float* lb = sl1 + (size_t)b * A;
+    const unsigned char* pb = pos + (size_t)b * A;
+    unsigned char* sb = sel + (size_t)b * A;
+    float npos = 0.f, fsum = 0.f, lsum = 0.f;
+    // Pass 1 issues every load, pass 2 consumes (loss_sample_body).  PT = 32 (A > 24576, no preset) takes two such rounds of 16:
+    // its 96 values in flight at once would need more of the 128 registers that 1024 threads leave than the consumers spare,
+    // and spill.  The per-thread order of every sum is the same either way.
+    constexpr int ROUNDS = PT > 24 ? 2 : 1, PR = PT / ROUNDS;
+#pragma unroll
+    for (int r0 = 0; r0 < PT; r0 += PR) {
+        float cv[PR], lv[PR];
+        unsigned char pv[PR];
+#pragma unroll
+        for (int r = 0; r < PR; ++r) {
+            const int a = tid + LS_THREADS * (r0 + r);
+            const int ac = a < A ? a : 0;           // unconditional loads from a clamped index, masked in pass 2
+            cv[r] = cb[ac];
+            lv[r] = lb[ac];
+            pv[r] = pb[ac];
+        }
+#pragma unroll
+        for (int r = 0; r < PR; ++r) {
+            const int a = tid + LS_THREADS * (r0 + r);
+            if (a < A) {
+                const bool p = pv[r] != 0;
+                npos += p ? 1.f : 0.f;
+                lsum += lv[r];                      // stored as 0 off the positives
+                fsum += focal_term(cv[r], p, gamma, alpha, gmode);
+                sb[a] = 1;
+            }
+        }
+        if (ROUNDS > 1) __builtin_amdgcn_sched_barrier(0);      // (keeps the next round's loads behind this round's consumers)
+    }
+    block_sum3_1024(npos, fsum, lsum, red);
+    if (tid == 0) {
+        const float nb = fmaxf(npos, 1.f);
+        sample[b * 4 + 0] = fsum / nb;
+        sample[b * 4 + 1] = lsum / nb;
+        sample[b * 4 + 2] = 1.f / (nb * bnorm);
+        sample[b * 4 + 3] = npos;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();                                   // this sample's results before the ticket
+        const unsigned t = atomicAdd(ticket, 1u);
+        sh_last = t == (unsigned)B - 1u ? 1u : 0u;
+        if (sh_last) *ticket = 0u;
+    }
+    __syncthreads();
+    if (!sh_last) return;
+    __threadfence();
+    loss_final_block(B, bnorm, sample, partial, npartial, wd, losses, dred);
+}
+
+static int focal_gmode(float gamma) { return gamma == 0.f ? 0 : gamma == 1.f ? 1 : gamma == 2.f ? 2 : -1; }
+
+void multibox_focal_loss(const HeadLayout& L, int B, int b_off, int B_total, const float* result, const float* labels, LossWork& w,
+                         float weight_decay, float bnorm, float gamma, float alpha, hipStream_t s) {
+    SSD_REQUIRE(L.A <= 32 * LS_THREADS, "loss: at most %d anchors", 32 * LS_THREADS);
+    SSD_REQUIRE(B_total <= LS_THREADS / 2, "loss: at most %d images per step", LS_THREADS / 2);
+    const int total = B * L.A;
+    const HeadGrid G = head_grid(L, B);
+    if (!(bnorm > 0.f)) bnorm = (float)B_total;
+    const size_t o = (size_t)b_off * L.A;
+    const int gm = focal_gmode(gamma);
+    ProfScope prof("multibox_focal_loss", 0.0, 12.0 * total * L.nvars, s);
+    launch_heads<true>(L, G, B, const_cast<float*>(result), labels, w.ce + o, w.sl1 + o, w.pos + o, s);
+    const int pt = (L.A + LS_THREADS - 1) / LS_THREADS;
+    if (pt <= 9)
+        hipLaunchKernelGGL(focal_sample_kernel<9>, dim3(B), dim3(LS_THREADS), 0, s, B_total, b_off, L.A, bnorm, gamma, alpha, gm, w.ce,
+                           w.sl1, w.pos, w.sel, w.sample, w.partial, SUMSQ_BLOCKS, weight_decay, w.losses, w.ticket);
+    else if (pt <= 24)
+        hipLaunchKernelGGL(focal_sample_kernel<24>, dim3(B), dim3(LS_THREADS), 0, s, B_total, b_off, L.A, bnorm, gamma, alpha, gm, w.ce,
+                           w.sl1, w.pos, w.sel, w.sample, w.partial, SUMSQ_BLOCKS, weight_decay, w.losses, w.ticket);
+    else
+        hipLaunchKernelGGL(focal_sample_kernel<32>, dim3(B), dim3(LS_THREADS), 0, s, B_total, b_off, L.A, bnorm, gamma, alpha, gm, w.ce,
+                           w.sl1, w.pos, w.sel, w.sample, w.partial, SUMSQ_BLOCKS, weight_decay, w.losses, w.ticket);
+    HIP_OK(hipGetLastError());
+}
+
+// d/d(logits) = w_b * kappa * (softmax - labels) ; d/d(loc) = pos * clip(loc - gt, -1, 1) * w_b: every anchor has a gradient,
+// so the kernel is dense and HBM-bound -- it reads the result and labels records and writes the head-shaped tile, the bytes
+// heads_kernel<true> moves.  Tile geometry of head_block.  result and labels share one record layout, so per box type the
+// two contiguous runs of [nv] records are read with dword loads at the same flat index i (heads_kernel's label reads),
+// subtracted element by element and scaled by the factor of anchor i / nv, which one thread per anchor left in LDS from ce,
+// pos and the sample weight.  The tile is built in LDS at pitch ld, pad columns zero, and leaves as one run of 16-byte
+// stores.  WIDE (rows of more than MAXV values, G.hch < HCH): the runs are strided over the workgroup in a loop instead of
+// held in registers.  No atomics: bitwise reproducible.
+template <typename T, bool WIDE>
+__global__ __launch_bounds__(HTHREADS) void focal_grad_kernel(HeadLayout L, HeadGrid G, int B, int b_off, float gamma, float alpha,
+                                                              int gmode, const float* __restrict__ result,
+                                                              const float* __restrict__ labels, const float* __restrict__ ce,
+                                                              const unsigned char* __restrict__ pos,
+                                                              const float* __restrict__ sample) {
+    extern __shared__ __attribute__((aligned(16))) float gsm[];      // [G.hch][ld] tile, then [HSLOTS * G.hch] x 2 anchor factors
+    const HeadBlock k = head_block(L, G);
+    const int hch = G.hch;
+    const int nv = L.nvars, nc = nv - 4;
+    const int ld = L.ld[k.map], nj = L.nj[k.map], hw = L.hw[k.map];
+    float* fk = gsm + hch * (G.ldp_max - 1);      // w_b * kappa per (type, cell)
+    float* fp = fk + HSLOTS * hch;                // w_b on positives, else 0
+    const size_t a0 = (size_t)k.b * L.A + L.off[k.map] + k.cell0;      // anchor of (type 0, first cell), local to this launch
+    const int nrec = k.ncell * nv;
+    const float rnv = 1.f / (float)nv;
+    // ---- per-anchor loads first, then the records: nothing is consumed before every load is issued (narrow rows)
+    const int acell = threadIdx.x & (hch - 1), aj = threadIdx.x >> G.lg_hch;
+    const bool ahave = aj < nj && acell < k.ncell;        // aj >= HSLOTS >= nj for the threads beyond the anchors
+    const size_t aidx = a0 + (size_t)(ahave ? aj : 0) * hw + (ahave ? acell : 0);
+    const float ace = ce[aidx];
+    const bool apos = pos[aidx] != 0;
+    const float wb = sample[(k.b + b_off) * 4 + 2];
+    constexpr int RU = WIDE ? 1 : HCH * MAXV / HTHREADS;
+    float rv[WIDE ? 1 : HSLOTS][RU], yv[WIDE ? 1 : HSLOTS][RU];
+    if constexpr (!WIDE) {
+#pragma unroll
+        for (int j = 0; j < HSLOTS; ++j) {
+            const float* rrun = result + (a0 + (size_t)j * hw) * nv;
+            const float* yrun = labels + (a0 + (size_t)j * hw) * nv;
+#pragma unroll
+            for (int u = 0; u < RU; ++u) {
+                const int i = threadIdx.x + HTHREADS * u;
+                const bool in = j < nj && i < nrec;
+                rv[j][u] = in ? rrun[i] : 0.f;
+                yv[j][u] = in ? yrun[i] : 0.f;
+            }
+        }
+    }
+    if (ahave) {
+        fk[aj * hch + acell] = wb * focal_kappa(ace, apos, gamma, alpha, gmode);
+        fp[aj * hch + acell] = apos ? wb : 0.f;
+    }
+    const int npad = ld - nj * nv;
+    for (int i = threadIdx.x; i < k.ncell * npad; i += HTHREADS) {
+        const int row = i / npad;
+        gsm[row * ld + nj * nv + (i - row * npad)] = 0.f;
+    }
+    __syncthreads();
+    if constexpr (!WIDE) {
+#pragma unroll
+        for (int j = 0; j < HSLOTS; ++j)
+#pragma unroll
+            for (int u = 0; u < RU; ++u) {
+                const int i = threadIdx.x + HTHREADS * u;
+                if (j < nj && i < nrec) {
+                    const int cell = (int)(((float)i + 0.5f) * rnv), c = i - cell * nv;      // i < 1024: exact
+                    const float d = rv[j][u] - yv[j][u];
+                    gsm[cell * ld + j * nv + c] = c < nc ? d * fk[j * hch + cell] : fminf(fmaxf(d, -1.f), 1.f) * fp[j * hch + cell];
+                }
+            }
+    } else {
+        for (int j = 0; j < nj; ++j) {
+            const float* rrun = result + (a0 + (size_t)j * hw) * nv;
+            const float* yrun = labels + (a0 + (size_t)j * hw) * nv;
+#pragma unroll 4
+            for (int i = threadIdx.x; i < nrec; i += HTHREADS) {
+                const int cell = (int)(((float)i + 0.5f) * rnv), c = i - cell * nv;          // i < 16 * 132: exact
+                const float d = rrun[i] - yrun[i];
+                gsm[cell * ld + j * nv + c] = c < nc ? d * fk[j * hch + cell] : fminf(fmaxf(d, -1.f), 1.f) * fp[j * hch + cell];
+            }
+        }
+    }
+    __syncthreads();
+    const int n4 = (k.ncell * ld) >> 2;
+    T* out = static_cast<T*>(L.dbuf[k.map]) + ((size_t)k.b * hw + k.cell0) * ld;
+    for (int i = threadIdx.x; i < n4; i += HTHREADS) st4t(out + 4 * i, *reinterpret_cast<const f32x4*>(gsm + 4 * i));
+}
+
+void multibox_focal_loss_grad(const HeadLayout& L, int B, int b_off, const float* result, const float* labels, const LossWork& w,
+                              float gamma, float alpha, hipStream_t s) {
+    const int total = B * L.A;
+    const HeadGrid G = head_grid(L, B);
+    const size_t lds = ((size_t)G.hch * (G.ldp_max - 1) + 2 * (size_t)HSLOTS * G.hch) * sizeof(float);
+    const size_t o = (size_t)b_off * L.A;
+    const int gm = focal_gmode(gamma);
+    const dim3 grid(G.blk_off[MAX_MAPS]), block(HTHREADS);
+    ProfScope prof("multibox_focal_loss_grad", 0.0, (L.grad_bf16 ? 10.0 : 12.0) * total * L.nvars, s);
+#define SSD_FOCAL_GRAD(T, WIDE)                                                                                                      \
+    hipLaunchKernelGGL((focal_grad_kernel<T, WIDE>), grid, block, lds, s, L, G, B, b_off, gamma, alpha, gm, result, labels, w.ce + o, \
+                       w.pos + o, w.sample)
+    if (L.nvars <= MAXV) {
+        if (L.grad_bf16) SSD_FOCAL_GRAD(bf16_t, false);
+        else SSD_FOCAL_GRAD(float, false);
+    } else {
+        if (L.grad_bf16) SSD_FOCAL_GRAD(bf16_t, true);
+        else SSD_FOCAL_GRAD(float, true);
+    }
+#undef SSD_FOCAL_GRAD
+    HIP_OK(hipGetLastError());
+}
+
 // =================================================================================
 // optimizer
 // =================================================================================

@@ -24,6 +24,30 @@ from .ssdutils import get_preset_by_name, SSD_PRESETS, detect_batch
 LOSS_NAMES = ('total', 'localization', 'confidence', 'l2')      # ssdvgg.py:594-599
 # compute types of a handle (include/ssdvgg_hip.h SSD_DTYPE_*); 'fp8', 'mxfp8' and 'mxfp6' are inference only
 DTYPES = {'f32': 0, 'bf16': 1, 'fp8': 2, 'mxfp8': 3, 'mxfp6': 4}
+# losses of a training handle (include/ssdvgg_hip.h SSD_LOSS_*): the reference's hard-negative mining, or the focal loss
+LOSS_KINDS = {'mining': 0, 'focal': 1}
+
+
+class LossConfig(C.Structure):
+    """ssd_loss_config of the C ABI"""
+    _fields_ = [('kind', C.c_int), ('focal_gamma', C.c_float), ('focal_alpha', C.c_float)]
+
+
+def loss_config(loss='mining', focal_gamma=2.0, focal_alpha=0.25):
+    """The ABI's configuration of a loss given by name; a bad name, gamma outside [0, 5] or alpha outside (0, 1): ValueError."""
+    if loss not in LOSS_KINDS:
+        raise ValueError('loss must be one of %s, got %r' % (sorted(LOSS_KINDS), loss))
+    g, a = float(focal_gamma), float(focal_alpha)
+    if loss == 'focal' and not (0.0 <= g <= 5.0 and 0.0 < a < 1.0):
+        raise ValueError('focal loss takes gamma in [0, 5] and alpha in (0, 1), got gamma %r, alpha %r' % (focal_gamma, focal_alpha))
+    return LossConfig(LOSS_KINDS[loss], g, a)
+
+
+def checkpoint_loss(ck):
+    """(loss name, gamma, alpha) of an opened checkpoint; one from before the option is 'mining'."""
+    if '__loss__' not in ck.files:
+        return 'mining', 2.0, 0.25
+    return str(ck['__loss__']), float(ck['__focal_gamma__']), float(ck['__focal_alpha__'])
 
 
 class _Token:
@@ -177,7 +201,7 @@ class SSDVGG:
 
     # ------------------------------------------------------------------ construction
     def build_from_vgg(self, vgg_dir, num_classes, a_trous=True, progress_hook='tqdm', max_batch=32,
-                       training=True, seed=42, weights=None, dtype='f32'):
+                       training=True, seed=42, weights=None, dtype='f32', background_prior=None):
         """ssdvgg.py:96-118.  There is no vgg.zip offline: the VGG-16 trunk starts from
         Xavier-uniform synthetic weights (seed) unless `weights` ({tf_name: array}) or
         `<vgg_dir>/vgg16_ssd.npz` supplies them.  dtype 'f32' (default) or 'bf16' (bf16 activations and
@@ -189,7 +213,12 @@ class SSDVGG:
         mxfp8 net's layers and pools on 6-bit e2m3 operands with E8M0 block scales on activations and filters, again without
         calibration (the fc graph's 7x7 fc6 stays on bf16).
         a_trous=False builds the reference's other graph (ssdvgg.py:210-228): VGG-16's fc6 / fc7 as a 7x7 and a
-        1x1 convolution, 4096 wide, variables fc6/* and fc7/*; its weights come from `<vgg_dir>/vgg16_ssd_fc.npz`."""
+        1x1 convolution, 4096 wide, variables fc6/* and fc7/*; its weights come from `<vgg_dir>/vgg16_ssd_fc.npz`.
+        background_prior=P (0 < P < 1; the focal loss's start): after everything else, every classifier's biases are
+        set so that an untrained anchor gives each of the C object classes the probability P / C: the background entry
+        log(C * (1 - P) / P), the other class entries 0 (the four offset entries keep their values)."""
+        if background_prior is not None and not 0.0 < float(background_prior) < 1.0:
+            raise ValueError('background_prior must lie in (0, 1), got %r' % (background_prior,))
         self.num_classes = num_classes + 1
         self.num_vars = num_classes + 5
         self._create(num_classes, max_batch, training, seed, dtype, a_trous)
@@ -198,6 +227,14 @@ class SSDVGG:
             weights = dict(np.load(path))
         if weights:
             self.load_variables(weights)
+        if background_prior is not None:
+            p = float(background_prior)
+            names = [n for n, _ in self.variables() if n.startswith('classifiers/') and n.endswith('/biases')]
+            biases = self.save_variables(names)
+            for a in biases.values():
+                a[:num_classes] = 0.0
+                a[num_classes] = np.log(num_classes * (1.0 - p) / p)
+            self.load_variables(biases)
         self.__built = True
 
     def build_from_metagraph(self, metagraph_file, checkpoint_file, max_batch=32, training=False, dtype='f32'):
@@ -273,10 +310,14 @@ class SSDVGG:
             pass
 
     # ------------------------------------------------------------------ optimizer
-    def build_optimizer(self, learning_rate=0.001, weight_decay=0.0005, momentum=0.9, global_step=None):
-        """ssdvgg.py:375-599.  learning_rate: float or LearningRate (train.py:43-47)."""
+    def build_optimizer(self, learning_rate=0.001, weight_decay=0.0005, momentum=0.9, global_step=None, loss='mining',
+                        focal_gamma=2.0, focal_alpha=0.25):
+        """ssdvgg.py:375-599.  learning_rate: float or LearningRate (train.py:43-47).  loss: 'mining' (the reference's 3:1
+        hard-negative mining) or 'focal' (every anchor, damped by (1 - p_t)^focal_gamma and weighted focal_alpha on positives,
+        1 - focal_alpha on background; a sample without positives still trains its background anchors)."""
         if not self.training:
             raise RuntimeError('build_from_* was called with training=False')
+        self.set_loss(loss, focal_gamma, focal_alpha)
         lr = learning_rate if isinstance(learning_rate, LearningRate) else LearningRate([learning_rate], [])
         vals = np.array(lr.values, np.float32)
         bnds = np.array(lr.boundaries + [0], np.int64)
@@ -296,7 +337,9 @@ class SSDVGG:
         if ck is None:
             raise RuntimeError('build_from_metagraph first')
         lr = LearningRate(list(ck['__lr_values__']), list(ck['__lr_boundaries__']))
-        self.build_optimizer(lr, float(ck['__weight_decay__']), float(ck['__momentum__']), int(ck['__global_step__']))
+        loss, gamma, alpha = checkpoint_loss(ck)
+        self.build_optimizer(lr, float(ck['__weight_decay__']), float(ck['__momentum__']), int(ck['__global_step__']),
+                             loss=loss, focal_gamma=gamma, focal_alpha=alpha)
         for k in ck.files:
             if k.startswith('__momentum__/'):
                 a = np.ascontiguousarray(ck[k], np.float32)
@@ -371,6 +414,9 @@ class SSDVGG:
                  __lr_boundaries__=np.array(lr.boundaries, np.int64), __momentum__=np.array(momentum),
                  __weight_decay__=np.array(weight_decay), __class_names__=np.array([str(n) for n in names], dtype=np.str_),
                  __a_trous__=np.array(int(self.a_trous)), __match__=np.array(str(match)))
+        if self.training:
+            loss, gamma, alpha = self.get_loss()
+            d.update(__loss__=np.array(loss), __focal_gamma__=np.array(gamma), __focal_alpha__=np.array(alpha))
         np.savez(path, **d)
 
     # ------------------------------------------------------------------ steps
@@ -544,6 +590,17 @@ class SSDVGG:
         """reduce_mean over `batch` samples instead of the step's own b (<= 0 restores the default): data
         parallel shards of unequal size pass global_samples / world (parallel.train_step_dp)."""
         check(lib.ssd_set_loss_normalizer(self._h, float(batch)))
+
+    def set_loss(self, loss='mining', focal_gamma=2.0, focal_alpha=0.25):
+        """The loss of the steps from the next one on (ssd_set_loss): 'mining' or 'focal' (build_optimizer)."""
+        cfg = loss_config(loss, focal_gamma, focal_alpha)
+        check(lib.ssd_set_loss(self._h, C.byref(cfg)))
+
+    def get_loss(self):
+        """(name, focal_gamma, focal_alpha) of the handle's loss"""
+        cfg = LossConfig()
+        check(lib.ssd_get_loss(self._h, C.byref(cfg)))
+        return [k for k, v in LOSS_KINDS.items() if v == cfg.kind][0], float(cfg.focal_gamma), float(cfg.focal_alpha)
 
     def null_gradients_dev(self):
         """The gradient arena of a step without samples: weight_decay * filters, zero elsewhere."""

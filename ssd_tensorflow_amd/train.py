@@ -151,6 +151,13 @@ def checkpoint_match(path):
         return str(ck['__match__']) if '__match__' in ck.files else 'reference'
 
 
+def checkpoint_loss(path):
+    """(loss, gamma, alpha) a checkpoint's run trained with (checkpoints from before the option: 'mining')."""
+    from .ssdvgg import checkpoint_loss as of
+    with np.load(path, allow_pickle=False) as ck:
+        return of(ck)
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description='Train the SSD')
     parser.add_argument('--name', default='test', help='project name')
@@ -174,6 +181,10 @@ def main(argv=None):
     parser.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help='f32, or bf16 activations on the bf16 matrix cores (fp32 master weights, loss and optimizer)')
     parser.add_argument('--a-trous', type=str2bool, default='True', help='a fresh run: the a-trous graph (true) or the fc graph with the whole fc6 / fc7 (false; weights from <vgg-dir>/vgg16_ssd_fc.npz); --continue-training takes the checkpoint\'s')
     parser.add_argument('--match', default='reference', choices=['reference', 'paper'], help="which ground-truth boxes get positive anchors: reference = only boxes some anchor overlaps with IoU > 0.5; paper = the SSD paper's matching, every box first gets the anchor it overlaps best (DESIGN.md 29); --continue-training takes the checkpoint's")
+    parser.add_argument('--loss', default='mining', choices=['mining', 'focal'], help="mining = the reference's softmax cross entropy over the positives and 3x as many hard negatives; focal = the focal loss, every anchor contributes, damped by (1 - p_t)^gamma (DESIGN.md 30); --continue-training takes the checkpoint's")
+    parser.add_argument('--focal-gamma', type=float, default=2.0, help='--loss focal: the focusing exponent, 0..5')
+    parser.add_argument('--focal-alpha', type=float, default=0.25, help='--loss focal: the weight of a positive anchor (background: 1 - alpha), inside (0, 1)')
+    parser.add_argument('--focal-prior', type=float, default=0.01, help='a fresh --loss focal run: the classifier biases start at a total object probability of this per anchor')
     parser.add_argument('--shapes-size', default='0.2;0.5', help="--data-dir shapes: smallest and largest side of a rectangle, as fractions of the frame")
     parser.add_argument('--synthetic-train', type=int, default=64, help='synthetic training samples per epoch')
     parser.add_argument('--synthetic-valid', type=int, default=16)
@@ -226,6 +237,11 @@ def main(argv=None):
         if ck_match != args.match:
             say("[i] --match %s disagrees with the checkpoint: continuing with its rule, '%s'" % (args.match, ck_match))
             args.match = ck_match
+        ck_loss = checkpoint_loss(ckpt)
+        asked = (args.loss, args.focal_gamma, args.focal_alpha) if args.loss == 'focal' else (args.loss,)
+        if asked != ck_loss[:len(asked)]:
+            say("[i] --loss %s disagrees with the checkpoint: continuing with its loss, '%s'" % (args.loss, ck_loss[0]))
+        args.loss, args.focal_gamma, args.focal_alpha = ck_loss
     elif rank == 0:
         try:
             os.makedirs(args.name, exist_ok=True)
@@ -233,6 +249,14 @@ def main(argv=None):
             print('[!] Cannot create directory {}: {}'.format(args.name, e)); return 1      # train.py:143-145
 
     say('[i] Matching rule:        ', args.match)
+    try:
+        from .ssdvgg import loss_config
+        loss_config(args.loss, args.focal_gamma, args.focal_alpha)
+        if args.loss == 'focal' and not 0.0 < args.focal_prior < 1.0:
+            raise ValueError('--focal-prior must lie in (0, 1)')
+    except ValueError as e:
+        print('[!] Bad loss:', str(e)); return 1
+    say('[i] Loss:                 ', args.loss if args.loss != 'focal' else 'focal (gamma %g, alpha %g)' % (args.focal_gamma, args.focal_alpha))
     if args.cache_gb < 0 or (args.cache_gb and args.decoder != 'gpu'):
         print('[!] --cache-gb keeps pictures decoded on the GPU: it needs --decoder gpu and a size >= 0'); return 1
     try:
@@ -266,8 +290,10 @@ def main(argv=None):
             net.build_from_metagraph(None, ckpt, max_batch=args.batch_size, training=True, dtype=args.dtype)
             net.build_optimizer_from_metagraph()
         else:
-            net.build_from_vgg(args.vgg_dir, td.num_classes, a_trous=args.a_trous, max_batch=args.batch_size, dtype=args.dtype)
-            net.build_optimizer(learning_rate=lr, weight_decay=args.weight_decay, momentum=args.momentum)
+            net.build_from_vgg(args.vgg_dir, td.num_classes, a_trous=args.a_trous, max_batch=args.batch_size, dtype=args.dtype,
+                               background_prior=args.focal_prior if args.loss == 'focal' else None)
+            net.build_optimizer(learning_rate=lr, weight_decay=args.weight_decay, momentum=args.momentum, loss=args.loss,
+                                focal_gamma=args.focal_gamma, focal_alpha=args.focal_alpha)
         if world > 1:
             torch.distributed.broadcast(net.params_flat, 0)
         net.set_stream(torch.cuda.current_stream().cuda_stream)
