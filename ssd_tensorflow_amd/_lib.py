@@ -141,6 +141,8 @@ SIGNATURES = {
     'ssd_null_gradients_dev': (i32, [handle]),
     'ssd_set_loss': (i32, [handle, vp]),
     'ssd_get_loss': (i32, [handle, vp]),
+    'ssd_set_loc_loss': (i32, [handle, vp]),
+    'ssd_get_loc_loss': (i32, [handle, vp]),
     'ssd_train_step_dev': (i32, [handle, vp, vp, i32]),
     'ssd_eval_step_dev': (i32, [handle, vp, vp, i32]),
     'ssd_infer_dev': (i32, [handle, vp, i32]),
@@ -231,6 +233,8 @@ SIGNATURES = {
     'ssd_op_multibox_loss_grad': (i32, [i32, p_i32, p_i32, i32, C.POINTER(vp), i32, vp, vp, vp, i32, i32, i32, vp]),
     'ssd_op_multibox_loss_ex': (i32, [i32, p_i32, p_i32, i32, C.POINTER(vp), vp, vp, vp, i32, i32, i32, f32, vp, sz, f32, vp, vp]),
     'ssd_op_multibox_loss_grad_ex': (i32, [i32, p_i32, p_i32, i32, C.POINTER(vp), i32, vp, vp, vp, i32, i32, i32, vp, vp]),
+    'ssd_op_multibox_loss_ex2': (i32, [i32, p_i32, p_i32, i32, C.POINTER(vp), vp, vp, vp, i32, i32, i32, f32, vp, sz, f32, vp, vp, vp]),
+    'ssd_op_multibox_loss_grad_ex2': (i32, [i32, p_i32, p_i32, i32, C.POINTER(vp), i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

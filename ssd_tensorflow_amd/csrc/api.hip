@@ -1201,6 +1201,31 @@ int ssd_get_loss(ssd_handle h, ssd_loss_config* cfg) {
     N(h).get_loss(&cfg->kind, &cfg->focal_gamma, &cfg->focal_alpha);
     API_END
 }
+// ... and a localization loss configuration (NULL means smooth-L1)
+static void check_loc_loss_config(const ssd_loc_loss_config* cfg) {
+    if (!cfg) return;
+    SSD_REQUIRE(cfg->kind == SSD_LOC_SMOOTH_L1 || cfg->kind == SSD_LOC_GIOU,
+                "localization loss: kind %d is neither SSD_LOC_SMOOTH_L1 nor SSD_LOC_GIOU", cfg->kind);
+    if (cfg->kind != SSD_LOC_GIOU) return;
+    SSD_REQUIRE(std::isfinite(cfg->weight) && cfg->weight > 0.f, "localization loss: weight %g is not a finite number > 0",
+                (double)cfg->weight);
+}
+int ssd_set_loc_loss(ssd_handle h, const ssd_loc_loss_config* cfg) {
+    API_BEGIN
+    SSD_REQUIRE(cfg != nullptr, "localization loss: null configuration");
+    check_loc_loss_config(cfg);
+    Net& n = N(h);
+    SSD_REQUIRE(n.training(), "localization loss: the handle was created with training = 0");
+    if (cfg->kind == SSD_LOC_GIOU) n.set_loc_loss(cfg->kind, cfg->weight);
+    else n.set_loc_loss(SSD_LOC_SMOOTH_L1, 1.f);
+    API_END
+}
+int ssd_get_loc_loss(ssd_handle h, ssd_loc_loss_config* cfg) {
+    API_BEGIN
+    SSD_REQUIRE(cfg != nullptr, "localization loss: null configuration");
+    N(h).get_loc_loss(&cfg->kind, &cfg->weight);
+    API_END
+}
 int ssd_null_gradients_dev(ssd_handle h) {
     API_BEGIN_NET(h)
     n.null_gradients_step();
@@ -1926,6 +1951,58 @@ int ssd_op_multibox_loss_grad_ex(int nmaps, const int* hw, const int* nj, int nu
     LossWork w;
     loss_work_carve(w, ws, b_total, L.A);
     multibox_focal_loss_grad(L, b, b_off, result, labels, w, cfg->focal_gamma, cfg->focal_alpha, (hipStream_t)stream);
+    API_END
+}
+int ssd_op_multibox_loss_ex2(int nmaps, const int* hw, const int* nj, int num_classes, void* const* heads, const float* labels,
+                             float* result, void* ws, int b, int b_off, int b_total, float bnorm, const float* filters,
+                             size_t nfilters, float weight_decay, const ssd_loss_config* cfg, const ssd_loc_loss_config* loc,
+                             void* stream) {
+    if (!loc || loc->kind == SSD_LOC_SMOOTH_L1)
+        return ssd_op_multibox_loss_ex(nmaps, hw, nj, num_classes, heads, labels, result, ws, b, b_off, b_total, bnorm, filters, nfilters,
+                                       weight_decay, cfg, stream);
+    API_BEGIN
+    check_loss_config(cfg);
+    check_loc_loss_config(loc);
+    HeadLayout L = loss_op_layout(nmaps, hw, nj, num_classes, b, b_off, b_total);
+    SSD_REQUIRE(heads && labels && result && ws, "null buffer");
+    for (int i = 0; i < nmaps; ++i) {
+        SSD_REQUIRE(heads[i], "null head buffer %d", i);
+        L.buf[i] = static_cast<float*>(heads[i]);
+    }
+    LossWork w;
+    loss_work_carve(w, ws, b_total, L.A);
+    if (filters) l2_partials(filters, nfilters, w, (hipStream_t)stream);
+    const LocLoss ll{loc->kind, loc->weight};
+    if (cfg && cfg->kind == SSD_LOSS_FOCAL)
+        multibox_focal_loss(L, b, b_off, b_total, result, labels, w, weight_decay, bnorm, cfg->focal_gamma, cfg->focal_alpha,
+                            (hipStream_t)stream, ll);
+    else
+        multibox_loss(L, b, b_off, b_total, result, labels, w, weight_decay, bnorm, (hipStream_t)stream, ll);
+    API_END
+}
+int ssd_op_multibox_loss_grad_ex2(int nmaps, const int* hw, const int* nj, int num_classes, void* const* grads, int grads_bf16,
+                                  const float* labels, const float* result, void* ws, int b, int b_off, int b_total,
+                                  const ssd_loss_config* cfg, const ssd_loc_loss_config* loc, void* stream) {
+    if (!loc || loc->kind == SSD_LOC_SMOOTH_L1)
+        return ssd_op_multibox_loss_grad_ex(nmaps, hw, nj, num_classes, grads, grads_bf16, labels, result, ws, b, b_off, b_total, cfg,
+                                            stream);
+    API_BEGIN
+    check_loss_config(cfg);
+    check_loc_loss_config(loc);
+    HeadLayout L = loss_op_layout(nmaps, hw, nj, num_classes, b, b_off, b_total);
+    SSD_REQUIRE(grads && labels && result && ws, "null buffer");
+    for (int i = 0; i < nmaps; ++i) {
+        SSD_REQUIRE(grads[i], "null gradient buffer %d", i);
+        L.dbuf[i] = grads[i];
+    }
+    L.grad_bf16 = grads_bf16 ? 1 : 0;
+    LossWork w;
+    loss_work_carve(w, ws, b_total, L.A);
+    const LocLoss ll{loc->kind, loc->weight};
+    if (cfg && cfg->kind == SSD_LOSS_FOCAL)
+        multibox_focal_loss_grad(L, b, b_off, result, labels, w, cfg->focal_gamma, cfg->focal_alpha, (hipStream_t)stream, ll);
+    else
+        multibox_loss_grad(L, b, b_off, result, labels, w, (hipStream_t)stream, ll);
     API_END
 }
 int ssd_op_multibox_loss_grad(int nmaps, const int* hw, const int* nj, int num_classes, void* const* grads, int grads_bf16,

@@ -128,6 +128,9 @@ public:
     // which loss the steps compute from the next forward on: 0 mining (the default), 1 focal with (gamma, alpha)
     void set_loss(int kind, float gamma, float alpha) { loss_kind_ = kind; focal_gamma_ = gamma; focal_alpha_ = alpha; }
     void get_loss(int* kind, float* gamma, float* alpha) const { *kind = loss_kind_; *gamma = focal_gamma_; *alpha = focal_alpha_; }
+    // ... and which localization loss: 0 smooth-L1 (the default; weight 1), 1 GIoU with its weight
+    void set_loc_loss(int kind, float weight) { loc_.kind = kind; loc_.weight = weight; }
+    void get_loc_loss(int* kind, float* weight) const { *kind = loc_.kind; *weight = loc_.weight; }
     void null_gradients_step();                                         // gradient arena of a step without samples
     void set_optimizer(const float* lr_values, const long long* bounds, int n, float momentum, float wd);
 
@@ -310,6 +313,7 @@ private:
     int loss_kind_ = 0;                     // SSD_LOSS_MINING / SSD_LOSS_FOCAL
     int bw_loss_kind_ = 0;                  // the kind the last training forward computed: its backward takes the same
     float focal_gamma_ = 2.f, focal_alpha_ = 0.25f, bw_gamma_ = 2.f, bw_alpha_ = 0.25f;
+    LocLoss loc_{}, bw_loc_{};              // SSD_LOC_SMOOTH_L1 / SSD_LOC_GIOU and its weight; bw_: of the last training forward
     Profiler prof_;
     int bw_pos_ = 0, bw_b_ = 0;          // next entry of bwd_order_
     size_t bw_done_off_ = 0;

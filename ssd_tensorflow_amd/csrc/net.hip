@@ -1254,7 +1254,7 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
     }
     prof_.layer = "loss";
     const int A = preset_->num_anchors, nv = C_ + 5;
-    if (train_mode) { bw_loss_kind_ = loss_kind_; bw_gamma_ = focal_gamma_; bw_alpha_ = focal_alpha_; }      // the step's loss: backward follows it
+    if (train_mode) { bw_loss_kind_ = loss_kind_; bw_gamma_ = focal_gamma_; bw_alpha_ = focal_alpha_; bw_loc_ = loc_; }      // the step's loss: backward follows it
     const bool focal = train_mode && bw_loss_kind_ == 1;
     // The lanes' loss launches share a self-resetting completion ticket (ops.hip): if a launch fails after another
     // lane's has been enqueued, the count never reaches the step's total and the ticket would stay non-zero for the life
@@ -1265,8 +1265,8 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
         HIP_OK(hipStreamWaitEvent(stream_, ev_h_, 0));
         HIP_OK(hipEventRecord(ev_join_, s2_));
         HIP_OK(hipStreamWaitEvent(stream_, ev_join_, 0));
-        if (focal) multibox_focal_loss(heads_, b, 0, b, result_, y, lw_, wd_, loss_bnorm_, bw_gamma_, bw_alpha_, stream_);
-        else if (train_mode) multibox_loss(heads_, b, 0, b, result_, y, lw_, wd_, loss_bnorm_, stream_);
+        if (focal) multibox_focal_loss(heads_, b, 0, b, result_, y, lw_, wd_, loss_bnorm_, bw_gamma_, bw_alpha_, stream_, bw_loc_);
+        else if (train_mode) multibox_loss(heads_, b, 0, b, result_, y, lw_, wd_, loss_bnorm_, stream_, bw_loc_);
         else heads_result(heads_, b, result_, stream_);
     }
     for (int li = 0; li < nl && !heads_full; ++li) {
@@ -1280,8 +1280,8 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
         float* res = result_ + (size_t)ln.b0 * A * nv;
         if (train_mode) {
             if (li == 1) HIP_OK(hipStreamWaitEvent(ln.s, ev_l2_, 0));      // the final reduction may fall to this lane
-            if (focal) multibox_focal_loss(hl, ln.nb, ln.b0, b, res, y + (size_t)ln.b0 * A * nv, lw_, wd_, loss_bnorm_, bw_gamma_, bw_alpha_, ln.s);
-            else multibox_loss(hl, ln.nb, ln.b0, b, res, y + (size_t)ln.b0 * A * nv, lw_, wd_, loss_bnorm_, ln.s);
+            if (focal) multibox_focal_loss(hl, ln.nb, ln.b0, b, res, y + (size_t)ln.b0 * A * nv, lw_, wd_, loss_bnorm_, bw_gamma_, bw_alpha_, ln.s, bw_loc_);
+            else multibox_loss(hl, ln.nb, ln.b0, b, res, y + (size_t)ln.b0 * A * nv, lw_, wd_, loss_bnorm_, ln.s, bw_loc_);
         } else {
             heads_result(hl, ln.nb, res, ln.s);
         }
@@ -1347,8 +1347,8 @@ void Net::backward_begin(int b, const float* y) {
         HIP_OK(hipStreamWaitEvent(stream_, ev_wino_flip_, 0));
         wino_flip_pending_ = false;
     }
-    if (bw_loss_kind_ == 1) multibox_focal_loss_grad(heads_, b, 0, result_, y, lw_, bw_gamma_, bw_alpha_, stream_);
-    else multibox_loss_grad(heads_, b, 0, result_, y, lw_, stream_);
+    if (bw_loss_kind_ == 1) multibox_focal_loss_grad(heads_, b, 0, result_, y, lw_, bw_gamma_, bw_alpha_, stream_, bw_loc_);
+    else multibox_loss_grad(heads_, b, 0, result_, y, lw_, stream_, bw_loc_);
     for (int t : head_t_) bw_wrote(0, tensors_[t]);      // the loss gradient, on the main stream
     if (side) bw_sync(1, 0);      // the side stream starts behind it (the small maps' head data gradients: backward_step)
     bw_conv_done_.assign(ops_.size(), 0);

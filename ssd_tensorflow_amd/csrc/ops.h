@@ -73,13 +73,21 @@ void heads_result(const HeadLayout& L, int B, float* result, hipStream_t s);
 
 struct LossWork {                    // per-step scratch, all device
     float* ce;                       // [B][A] cross entropy
-    float* sl1;                      // [B][A] smooth-L1 summed over the 4 offsets
+    float* sl1;                      // [B][A] localization term: smooth-L1 summed over the 4 offsets, or weight * (1 - GIoU)
     unsigned char* pos;              // [B][A] 1 = positive anchor
     unsigned char* sel;              // [B][A] 1 = contributes to the confidence loss
     float* sample;                   // [B][4]: conf_b, loc_b, weight_b (1/(pos_n*B) or 0), pos_n
     float* partial;                  // [1024] sum-of-squares partials
     float* losses;                   // [4] total, localization, confidence, l2 (the executor points this at mapped host memory)
     unsigned* ticket;                // completion ticket of the per-sample workgroups (zero between launches)
+};
+// The localization half of the multibox loss: kind 0 = smooth-L1 on the four encoded offsets (the reference's, the default; weight
+// unused), 1 = weight * (1 - GIoU) of the box the offsets describe against the box the label offsets describe, both in units of
+// their anchor.  The per-anchor term takes the place of the smooth-L1 sum in LossWork::sl1; everything after the
+// head kernels is shared.  weight finite and > 0: checked by the callers.
+struct LocLoss {
+    int kind = 0;
+    float weight = 1.f;
 };
 size_t loss_work_bytes(int B, int A);
 void loss_work_carve(LossWork& w, void* base, int B, int A);
@@ -89,22 +97,22 @@ void loss_work_carve(LossWork& w, void* base, int B, int A);
 // A step may compute its loss in several launches over disjoint sample ranges (forward lanes): L.buf, result and labels
 // point at the range's first sample, B = samples of this launch, b_off = index of its first sample, B_total = the step's.
 void multibox_loss(const HeadLayout& L, int B, int b_off, int B_total, const float* result, const float* labels, LossWork& w,
-                   float weight_decay, float bnorm, hipStream_t s);
+                   float weight_decay, float bnorm, hipStream_t s, LocLoss loc = {});
 // sum of squares of the filter region into w.partial (the l2 term of multibox_loss, which must follow it in stream
 // order): 4 bytes per parameter, independent of the forward pass, so the step runs it beside the first layers
 void l2_partials(const float* filters, size_t nfilters, LossWork& w, hipStream_t s);
 // d(loss)/d(head outputs) written into L.dbuf (pad columns stay zero).
 // (lane form like multibox_loss: L.dbuf, result and labels point at sample b_off, B samples)
 void multibox_loss_grad(const HeadLayout& L, int B, int b_off, const float* result, const float* labels, const LossWork& w,
-                        hipStream_t s);
+                        hipStream_t s, LocLoss loc = {});
 
 // The focal loss (softmax form) on the same buffers, lanes and workspace: heads_kernel<true> as above, then
 // focal_sample_kernel / focal_grad_kernel.  Every anchor contributes alpha_t * (1 - p_t)^gamma * ce, a sample is normalised
 // by max(pos_n, 1), sel is all ones; the gradient is dense.  gamma in [0, 5], alpha in (0, 1): checked by the callers.
 void multibox_focal_loss(const HeadLayout& L, int B, int b_off, int B_total, const float* result, const float* labels, LossWork& w,
-                         float weight_decay, float bnorm, float gamma, float alpha, hipStream_t s);
+                         float weight_decay, float bnorm, float gamma, float alpha, hipStream_t s, LocLoss loc = {});
 void multibox_focal_loss_grad(const HeadLayout& L, int B, int b_off, const float* result, const float* labels, const LossWork& w,
-                              float gamma, float alpha, hipStream_t s);
+                              float gamma, float alpha, hipStream_t s, LocLoss loc = {});
 
 // ---- MomentumOptimizer without Nesterov (ssdvgg.py:586-588): acc = m*acc + g; w -= lr*acc
 void momentum_update(float* w, float* acc, const float* g, size_t n, float lr, float momentum, float gscale,

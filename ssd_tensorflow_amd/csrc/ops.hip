@@ -932,10 +932,65 @@ __device__ __forceinline__ void lds_to_run(float* __restrict__ dst, const float*
     for (int i = pre + 4 * n4 + threadIdx.x; i < n; i += HTHREADS) dst[i] = src[i];
 }
 
-template <bool TRAIN>
+// ---- generalized IoU box regression (Rezatofighi et al. 2019) on the encoded offsets -------------------------------------------------
+// IoU and GIoU are ratios of areas, unchanged under a separate scaling and shift per axis, so the box of the offsets t is taken in
+// units of its own anchor (centre (t0, t1) / 10, size exp((t2, t3) / 5)) and the ground truth of the same anchor from the label
+// offsets g likewise: no anchor table.  Offsets are clamped to +-100 (no product overflows: exp(20)^2 ~ 2e17), so every width is
+// >= exp(-20) > 0, U > 0 and C > 0, and no epsilon is added.  L = 1 - GIoU = (1 - I / U) + (1 - U / C), in [0, 2).
+// Evaluated in the ground-truth box's frame (centre difference first: the one subtraction that cancels is then exact or rounds
+// relative to its own result, not to |t|), with the rounding of t / 5 carried into the exponential (exp(q) * (1 + (t - 5 q) / 5),
+// t - 5 q exact by fma), so every width is good to ~4 * 2^-24 relative instead of 20 * 2^-24.  No contraction: the order written
+// here is the order evaluated, and the tie cases of the tests (unit boxes at multiples of 1/2) are exact ties.
+// At a tie of a max / min the derivative goes to the predicted coordinate; boxes that only touch are not live.
+// dt (GRAD): dL / dt, 0 on a clamped component.
+constexpr int LOC_SMOOTH_L1 = 0, LOC_GIOU = 1;
+__device__ __forceinline__ float giou_size(float t) {
+    const float q = t / 5.f;
+    const float e = expf(q);
+    return fmaf(e, fmaf(-5.f, q, t) / 5.f, e);
+}
+template <bool GRAD>
+__device__ __forceinline__ float giou_eval(const float* t, const float* g, float* dt) {
+#pragma clang fp contract(off)
+    float tc[4], gc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        tc[i] = fminf(fmaxf(t[i], -100.f), 100.f);
+        gc[i] = fminf(fmaxf(g[i], -100.f), 100.f);
+    }
+    const float dx = (tc[0] - gc[0]) / 10.f, dy = (tc[1] - gc[1]) / 10.f;
+    const float wp = giou_size(tc[2]), hp = giou_size(tc[3]), wg = giou_size(gc[2]), hg = giou_size(gc[3]);
+    const float x0p = dx - 0.5f * wp, x1p = dx + 0.5f * wp, x0g = -0.5f * wg, x1g = 0.5f * wg;
+    const float y0p = dy - 0.5f * hp, y1p = dy + 0.5f * hp, y0g = -0.5f * hg, y1g = 0.5f * hg;
+    const float iw = fmaxf(fminf(x1p, x1g) - fmaxf(x0p, x0g), 0.f), ih = fmaxf(fminf(y1p, y1g) - fmaxf(y0p, y0g), 0.f);
+    const float cw = fmaxf(x1p, x1g) - fminf(x0p, x0g), ch = fmaxf(y1p, y1g) - fminf(y0p, y0g);
+    const float I = iw * ih, U = wp * hp + wg * hg - I, C = cw * ch;
+    const float iou = I / U, uc = U / C;
+    if constexpr (GRAD) {
+        const float kA = iou / U - 1.f / C, kI = -1.f / U - kA, kC = uc / C;
+        const bool live = iw > 0.f && ih > 0.f;
+        const float gx0 = kI * ((live && x0p >= x0g) ? -ih : 0.f) - kA * hp + kC * (x0p <= x0g ? -ch : 0.f);
+        const float gx1 = kI * ((live && x1p <= x1g) ? ih : 0.f) + kA * hp + kC * (x1p >= x1g ? ch : 0.f);
+        const float gy0 = kI * ((live && y0p >= y0g) ? -iw : 0.f) - kA * wp + kC * (y0p <= y0g ? -cw : 0.f);
+        const float gy1 = kI * ((live && y1p <= y1g) ? iw : 0.f) + kA * wp + kC * (y1p >= y1g ? cw : 0.f);
+        dt[0] = fabsf(t[0]) > 100.f ? 0.f : (gx0 + gx1) / 10.f;
+        dt[1] = fabsf(t[1]) > 100.f ? 0.f : (gy0 + gy1) / 10.f;
+        dt[2] = fabsf(t[2]) > 100.f ? 0.f : (gx1 - gx0) * wp / 10.f;
+        dt[3] = fabsf(t[3]) > 100.f ? 0.f : (gy1 - gy0) * hp / 10.f;
+    }
+    return fmaxf((1.f - iou) + (1.f - uc), 0.f);
+}
+// the localization weight of a kernel instantiation: the smooth-L1 ones take no such argument
+__device__ __forceinline__ float loc_weight_arg() { return 1.f; }
+__device__ __forceinline__ float loc_weight_arg(float w) { return w; }
+
+
+// LOC (training): the localization term left in sl1_out, smooth-L1 (no further argument: the kernel and its arguments as they
+// always were) or loc_weight * (1 - GIoU) (one more argument, the weight); only a positive anchor takes the GIoU branch.
+template <bool TRAIN, int LOC = LOC_SMOOTH_L1, typename... LW>
 __global__ __launch_bounds__(HTHREADS) void heads_kernel(HeadLayout L, HeadGrid G, int B, float* __restrict__ result,
                                                          const float* __restrict__ labels, float* __restrict__ ce_out,
-                                                         float* __restrict__ sl1_out, unsigned char* __restrict__ pos_out) {
+                                                         float* __restrict__ sl1_out, unsigned char* __restrict__ pos_out, LW... loc_w) {
     extern __shared__ __attribute__((aligned(16))) float hsm[];
     const HeadBlock k = head_block(L, G);
     const int nv = L.nvars, nc = nv - 4;
@@ -1021,10 +1076,21 @@ __global__ __launch_bounds__(HTHREADS) void heads_kernel(HeadLayout L, HeadGrid 
             for (int c = 0; c < MAXV; ++c) {
                 if (c < nc) {
                     if (y[c] != 0.f) ce += y[c] * (lse - z[c]);
-                } else if (c < nv) {
+                } else if (LOC == LOC_SMOOTH_L1 && c < nv) {
                     const float d = z[c] - y[c];
                     const float ad = fabsf(d);
                     sl += ad < 1.f ? 0.5f * d * d : ad - 0.5f;
+                }
+            }
+            if constexpr (LOC == LOC_GIOU) {
+                if (pos) {
+                    float gt[4];
+#pragma unroll
+                    for (int c = 1; c < MAXV; ++c)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (c == nc + i) gt[i] = y[c];
+                    sl = loc_weight_arg(loc_w...) * giou_eval<false>(zsrc + nc, gt, nullptr);
                 }
             }
             const size_t idx = a0 + (size_t)j * hw + cell;
@@ -1050,10 +1116,11 @@ __global__ __launch_bounds__(HTHREADS) void heads_kernel(HeadLayout L, HeadGrid 
 // G.hch (16, 8 or 4) cells per workgroup and a group of gl = HTHREADS / (HSLOTS * hch) lanes per anchor.  The lanes of a
 // group stride the anchor's values in LDS (no per-value register arrays, so no spills at any width); max, sum of
 // exponentials, cross-entropy and smooth-L1 meet by xor-shuffles inside the group (one wave holds whole groups).
-template <bool TRAIN>
+template <bool TRAIN, int LOC = LOC_SMOOTH_L1, typename... LW>
 __global__ __launch_bounds__(HTHREADS) void heads_wide_kernel(HeadLayout L, HeadGrid G, int B, float* __restrict__ result,
                                                               const float* __restrict__ labels, float* __restrict__ ce_out,
-                                                              float* __restrict__ sl1_out, unsigned char* __restrict__ pos_out) {
+                                                              float* __restrict__ sl1_out, unsigned char* __restrict__ pos_out,
+                                                              LW... loc_w) {
     extern __shared__ __attribute__((aligned(16))) float hsm[];
     const HeadBlock k = head_block(L, G);
     const int hch = G.hch;
@@ -1100,9 +1167,17 @@ __global__ __launch_bounds__(HTHREADS) void heads_wide_kernel(HeadLayout L, Head
             }
             r[c] = __expf(zc - m) * inv;
         }
+        if constexpr (LOC == LOC_GIOU) {          // every lane of a positive's group, from the record before the loop below overwrites it
+            if (pos) {
+                float gt[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) gt[i] = r[nc + i];
+                sl = loc_weight_arg(loc_w...) * giou_eval<false>(z + nc, gt, nullptr);
+            }
+        }
         for (int c = nc + lane; c < nv; c += gl) {
             const float zc = z[c];
-            if constexpr (TRAIN) {
+            if constexpr (TRAIN && LOC == LOC_SMOOTH_L1) {
                 const float d = zc - r[c];
                 const float ad = fabsf(d);
                 sl += ad < 1.f ? 0.5f * d * d : ad - 0.5f;
@@ -1112,7 +1187,7 @@ __global__ __launch_bounds__(HTHREADS) void heads_wide_kernel(HeadLayout L, Head
         if constexpr (TRAIN) {
             for (int o = gl >> 1; o > 0; o >>= 1) {
                 ce += __shfl_xor(ce, o, 64);
-                sl += __shfl_xor(sl, o, 64);
+                if constexpr (LOC == LOC_SMOOTH_L1) sl += __shfl_xor(sl, o, 64);
             }
             if (lane == 0) {
                 const size_t idx = a0 + (size_t)j * hw + cell;
@@ -1134,7 +1209,18 @@ static size_t heads_lds_bytes(const HeadLayout& L, const HeadGrid& G) {
 // wider rows, whose register arrays would spill, take heads_wide_kernel.  Chosen by L.nvars, fixed for a handle.
 template <bool TRAIN>
 static void launch_heads(const HeadLayout& L, const HeadGrid& G, int B, float* result, const float* labels, float* ce, float* sl1,
-                         unsigned char* pos, hipStream_t s) {
+                         unsigned char* pos, hipStream_t s, LocLoss loc = {}) {
+    if constexpr (TRAIN) {
+        if (loc.kind == LOC_GIOU) {
+            if (L.nvars <= MAXV)
+                hipLaunchKernelGGL((heads_kernel<true, LOC_GIOU, float>), dim3(G.blk_off[MAX_MAPS]), dim3(HTHREADS), heads_lds_bytes(L, G), s,
+                                   L, G, B, result, labels, ce, sl1, pos, loc.weight);
+            else
+                hipLaunchKernelGGL((heads_wide_kernel<true, LOC_GIOU, float>), dim3(G.blk_off[MAX_MAPS]), dim3(HTHREADS),
+                                   heads_lds_bytes(L, G), s, L, G, B, result, labels, ce, sl1, pos, loc.weight);
+            return;
+        }
+    }
     if (L.nvars <= MAXV)
         hipLaunchKernelGGL(heads_kernel<TRAIN>, dim3(G.blk_off[MAX_MAPS]), dim3(HTHREADS), heads_lds_bytes(L, G), s, L, G, B, result,
                            labels, ce, sl1, pos);
@@ -1424,7 +1510,7 @@ void l2_partials(const float* filters, size_t nfilters, LossWork& w, hipStream_t
 }
 
 void multibox_loss(const HeadLayout& L, int B, int b_off, int B_total, const float* result, const float* labels, LossWork& w,
-                   float weight_decay, float bnorm, hipStream_t s) {
+                   float weight_decay, float bnorm, hipStream_t s, LocLoss loc) {
     SSD_REQUIRE(L.A <= 32 * LS_THREADS, "loss: at most %d anchors", 32 * LS_THREADS);
     SSD_REQUIRE(B_total <= LS_THREADS / 2, "loss: at most %d images per step", LS_THREADS / 2);
     const int total = B * L.A;
@@ -1432,7 +1518,7 @@ void multibox_loss(const HeadLayout& L, int B, int b_off, int B_total, const flo
     if (!(bnorm > 0.f)) bnorm = (float)B_total;          // reduce_mean over this step's own batch (ssdvgg.py:520,559)
     const size_t o = (size_t)b_off * L.A;                // this launch's slice of the per-anchor work arrays
     ProfScope prof("multibox_loss", 0.0, 12.0 * total * L.nvars, s);
-    launch_heads<true>(L, G, B, const_cast<float*>(result), labels, w.ce + o, w.sl1 + o, w.pos + o, s);
+    launch_heads<true>(L, G, B, const_cast<float*>(result), labels, w.ce + o, w.sl1 + o, w.pos + o, s, loc);
     const int pt = (L.A + LS_THREADS - 1) / LS_THREADS;
     if (pt <= 9)
         hipLaunchKernelGGL(loss_sample_kernel<9>, dim3(B), dim3(LS_THREADS), 0, s, B_total, b_off, L.A, bnorm, w.ce, w.sl1, w.pos, w.sel, w.sample,
@@ -1451,12 +1537,14 @@ void multibox_loss(const HeadLayout& L, int B, int b_off, int B_total, const flo
 // All but a few hundred anchors per image are neither selected nor positive: a workgroup zero-fills its
 // [HCH][ld] tile of the gradient buffer in LDS, the few flagged anchors fetch their result / label records and
 // fill their columns, and the tile leaves as one contiguous run of 16-byte stores (pad columns included).
-template <typename T>
+// LOC_GIOU (one more argument, the weight): d/d(loc) = pos * loc_weight * w_b * dL/dt, the four derivatives of an anchor from
+// all four offsets of its result and label records: lane 0 of the anchor's group computes and stores them.
+template <typename T, int LOC = LOC_SMOOTH_L1, typename... LW>
 __global__ __launch_bounds__(HTHREADS) void loss_grad_kernel(HeadLayout L, HeadGrid G, int B, int b_off, const float* __restrict__ result,
                                                              const float* __restrict__ labels,
                                                              const unsigned char* __restrict__ pos,
                                                              const unsigned char* __restrict__ sel,
-                                                             const float* __restrict__ sample) {
+                                                             const float* __restrict__ sample, LW... loc_w) {
     extern __shared__ __attribute__((aligned(16))) float gsm[];      // [G.hch][ld]
     const HeadBlock k = head_block(L, G);
     const int nv = L.nvars, nc = nv - 4;
@@ -1478,7 +1566,17 @@ __global__ __launch_bounds__(HTHREADS) void loss_grad_kernel(HeadLayout L, HeadG
             float* dst = gsm + cell * ld + j * nv;
             if (isel)
                 for (int c = lane; c < nc; c += gl) dst[c] = (r[c] - y[c]) * wb;
-            if (ipos)
+            if constexpr (LOC == LOC_GIOU) {
+                if (ipos && lane == 0) {
+                    float rt[4], gt[4], dt[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) { rt[i] = r[nc + i]; gt[i] = y[nc + i]; }
+                    giou_eval<true>(rt, gt, dt);
+                    const float lw = loc_weight_arg(loc_w...) * wb;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) dst[nc + i] = lw * dt[i];
+                }
+            } else if (ipos)
                 for (int c = nc + lane; c < nv; c += gl) dst[c] = fminf(fmaxf(r[c] - y[c], -1.f), 1.f) * wb;
         }
     }
@@ -1488,13 +1586,20 @@ __global__ __launch_bounds__(HTHREADS) void loss_grad_kernel(HeadLayout L, HeadG
 }
 
 void multibox_loss_grad(const HeadLayout& L, int B, int b_off, const float* result, const float* labels, const LossWork& w,
-                        hipStream_t s) {
+                        hipStream_t s, LocLoss loc) {
     const int total = B * L.A;
     const HeadGrid G = head_grid(L, B);
     const size_t lds = (size_t)G.hch * (G.ldp_max - 1) * sizeof(float);
     const size_t o = (size_t)b_off * L.A;
     ProfScope prof("multibox_loss_grad", 0.0, (L.grad_bf16 ? 10.0 : 12.0) * total * L.nvars, s);
-    if (L.grad_bf16)
+    if (loc.kind == LOC_GIOU) {
+        if (L.grad_bf16)
+            hipLaunchKernelGGL((loss_grad_kernel<bf16_t, LOC_GIOU, float>), dim3(G.blk_off[MAX_MAPS]), dim3(HTHREADS), lds, s, L, G, B, b_off,
+                               result, labels, w.pos + o, w.sel + o, w.sample, loc.weight);
+        else
+            hipLaunchKernelGGL((loss_grad_kernel<float, LOC_GIOU, float>), dim3(G.blk_off[MAX_MAPS]), dim3(HTHREADS), lds, s, L, G, B, b_off,
+                               result, labels, w.pos + o, w.sel + o, w.sample, loc.weight);
+    } else if (L.grad_bf16)
         hipLaunchKernelGGL(loss_grad_kernel<bf16_t>, dim3(G.blk_off[MAX_MAPS]), dim3(HTHREADS), lds, s, L, G, B, b_off, result, labels,
                            w.pos + o, w.sel + o, w.sample);
     else
@@ -1603,7 +1708,7 @@ __global__ __launch_bounds__(LS_THREADS) void focal_sample_kernel(int B, int b_o
 static int focal_gmode(float gamma) { return gamma == 0.f ? 0 : gamma == 1.f ? 1 : gamma == 2.f ? 2 : -1; }
 
 void multibox_focal_loss(const HeadLayout& L, int B, int b_off, int B_total, const float* result, const float* labels, LossWork& w,
-                         float weight_decay, float bnorm, float gamma, float alpha, hipStream_t s) {
+                         float weight_decay, float bnorm, float gamma, float alpha, hipStream_t s, LocLoss loc) {
     SSD_REQUIRE(L.A <= 32 * LS_THREADS, "loss: at most %d anchors", 32 * LS_THREADS);
     SSD_REQUIRE(B_total <= LS_THREADS / 2, "loss: at most %d images per step", LS_THREADS / 2);
     const int total = B * L.A;
@@ -1612,7 +1717,7 @@ void multibox_focal_loss(const HeadLayout& L, int B, int b_off, int B_total, con
     const size_t o = (size_t)b_off * L.A;
     const int gm = focal_gmode(gamma);
     ProfScope prof("multibox_focal_loss", 0.0, 12.0 * total * L.nvars, s);
-    launch_heads<true>(L, G, B, const_cast<float*>(result), labels, w.ce + o, w.sl1 + o, w.pos + o, s);
+    launch_heads<true>(L, G, B, const_cast<float*>(result), labels, w.ce + o, w.sl1 + o, w.pos + o, s, loc);
     const int pt = (L.A + LS_THREADS - 1) / LS_THREADS;
     if (pt <= 9)
         hipLaunchKernelGGL(focal_sample_kernel<9>, dim3(B), dim3(LS_THREADS), 0, s, B_total, b_off, L.A, bnorm, gamma, alpha, gm, w.ce,
@@ -1634,19 +1739,22 @@ void multibox_focal_loss(const HeadLayout& L, int B, int b_off, int B_total, con
 // pos and the sample weight.  The tile is built in LDS at pitch ld, pad columns zero, and leaves as one run of 16-byte
 // stores.  WIDE (rows of more than MAXV values, G.hch < HCH): the runs are strided over the workgroup in a loop instead of
 // held in registers.  No atomics: bitwise reproducible.
-template <typename T, bool WIDE>
+// LOC_GIOU (one more argument, the weight; four more anchor factors in LDS): the anchor's thread, on a positive, fetches the four
+// offsets of its result and label records and leaves pos * loc_weight * w_b * dL/dt there for the element-wise stage.
+template <typename T, bool WIDE, int LOC = LOC_SMOOTH_L1, typename... LW>
 __global__ __launch_bounds__(HTHREADS) void focal_grad_kernel(HeadLayout L, HeadGrid G, int B, int b_off, float gamma, float alpha,
                                                               int gmode, const float* __restrict__ result,
                                                               const float* __restrict__ labels, const float* __restrict__ ce,
                                                               const unsigned char* __restrict__ pos,
-                                                              const float* __restrict__ sample) {
-    extern __shared__ __attribute__((aligned(16))) float gsm[];      // [G.hch][ld] tile, then [HSLOTS * G.hch] x 2 anchor factors
+                                                              const float* __restrict__ sample, LW... loc_w) {
+    extern __shared__ __attribute__((aligned(16))) float gsm[];      // [G.hch][ld] tile, then [HSLOTS * G.hch] x 2 (GIoU: x 6) anchor factors
     const HeadBlock k = head_block(L, G);
     const int hch = G.hch;
     const int nv = L.nvars, nc = nv - 4;
     const int ld = L.ld[k.map], nj = L.nj[k.map], hw = L.hw[k.map];
     float* fk = gsm + hch * (G.ldp_max - 1);      // w_b * kappa per (type, cell)
     float* fp = fk + HSLOTS * hch;                // w_b on positives, else 0
+    float* fg = fp + HSLOTS * hch;                // LOC_GIOU: [4][HSLOTS * hch] gradients of the four offsets, 0 off the positives
     const size_t a0 = (size_t)k.b * L.A + L.off[k.map] + k.cell0;      // anchor of (type 0, first cell), local to this launch
     const int nrec = k.ncell * nv;
     const float rnv = 1.f / (float)nv;
@@ -1676,6 +1784,18 @@ __global__ __launch_bounds__(HTHREADS) void focal_grad_kernel(HeadLayout L, Head
     if (ahave) {
         fk[aj * hch + acell] = wb * focal_kappa(ace, apos, gamma, alpha, gmode);
         fp[aj * hch + acell] = apos ? wb : 0.f;
+        if constexpr (LOC == LOC_GIOU) {
+            float dt[4] = {0.f, 0.f, 0.f, 0.f};
+            if (apos) {
+                float rt[4], gt[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { rt[i] = result[aidx * nv + nc + i]; gt[i] = labels[aidx * nv + nc + i]; }
+                giou_eval<true>(rt, gt, dt);
+            }
+            const float lw = loc_weight_arg(loc_w...) * wb;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) fg[i * HSLOTS * hch + aj * hch + acell] = lw * dt[i];
+        }
     }
     const int npad = ld - nj * nv;
     for (int i = threadIdx.x; i < k.ncell * npad; i += HTHREADS) {
@@ -1692,18 +1812,37 @@ __global__ __launch_bounds__(HTHREADS) void focal_grad_kernel(HeadLayout L, Head
                 if (j < nj && i < nrec) {
                     const int cell = (int)(((float)i + 0.5f) * rnv), c = i - cell * nv;      // i < 1024: exact
                     const float d = rv[j][u] - yv[j][u];
-                    gsm[cell * ld + j * nv + c] = c < nc ? d * fk[j * hch + cell] : fminf(fmaxf(d, -1.f), 1.f) * fp[j * hch + cell];
+                    if constexpr (LOC == LOC_GIOU)
+                        gsm[cell * ld + j * nv + c] = c < nc ? d * fk[j * hch + cell] : fg[(c - nc) * HSLOTS * hch + j * hch + cell];
+                    else
+                        gsm[cell * ld + j * nv + c] = c < nc ? d * fk[j * hch + cell] : fminf(fmaxf(d, -1.f), 1.f) * fp[j * hch + cell];
                 }
             }
     } else {
         for (int j = 0; j < nj; ++j) {
             const float* rrun = result + (a0 + (size_t)j * hw) * nv;
             const float* yrun = labels + (a0 + (size_t)j * hw) * nv;
+            if constexpr (LOC == LOC_GIOU) {
+                // the class columns alone are read (a record difference that only the columns c < nc use makes the compiler sink its
+                // two loads under that condition, and the unrolled loop then waits for every pair of loads in turn); the loc columns
+                // come from LDS
+                const float rnc = 1.f / (float)nc;
+                const int ncls = k.ncell * nc;
 #pragma unroll 4
-            for (int i = threadIdx.x; i < nrec; i += HTHREADS) {
-                const int cell = (int)(((float)i + 0.5f) * rnv), c = i - cell * nv;          // i < 16 * 132: exact
-                const float d = rrun[i] - yrun[i];
-                gsm[cell * ld + j * nv + c] = c < nc ? d * fk[j * hch + cell] : fminf(fmaxf(d, -1.f), 1.f) * fp[j * hch + cell];
+                for (int e = threadIdx.x; e < ncls; e += HTHREADS) {
+                    const int cell = (int)(((float)e + 0.5f) * rnc), c = e - cell * nc;      // e < 16 * 128: exact
+                    const int i = cell * nv + c;
+                    gsm[cell * ld + j * nv + c] = (rrun[i] - yrun[i]) * fk[j * hch + cell];
+                }
+                for (int e = threadIdx.x; e < 4 * k.ncell; e += HTHREADS)
+                    gsm[(e >> 2) * ld + j * nv + nc + (e & 3)] = fg[(e & 3) * HSLOTS * hch + j * hch + (e >> 2)];
+            } else {
+#pragma unroll 4
+                for (int i = threadIdx.x; i < nrec; i += HTHREADS) {
+                    const int cell = (int)(((float)i + 0.5f) * rnv), c = i - cell * nv;          // i < 16 * 132: exact
+                    const float d = rrun[i] - yrun[i];
+                    gsm[cell * ld + j * nv + c] = c < nc ? d * fk[j * hch + cell] : fminf(fmaxf(d, -1.f), 1.f) * fp[j * hch + cell];
+                }
             }
         }
     }
@@ -1714,10 +1853,11 @@ __global__ __launch_bounds__(HTHREADS) void focal_grad_kernel(HeadLayout L, Head
 }
 
 void multibox_focal_loss_grad(const HeadLayout& L, int B, int b_off, const float* result, const float* labels, const LossWork& w,
-                              float gamma, float alpha, hipStream_t s) {
+                              float gamma, float alpha, hipStream_t s, LocLoss loc) {
     const int total = B * L.A;
     const HeadGrid G = head_grid(L, B);
-    const size_t lds = ((size_t)G.hch * (G.ldp_max - 1) + 2 * (size_t)HSLOTS * G.hch) * sizeof(float);
+    const bool giou = loc.kind == LOC_GIOU;
+    const size_t lds = ((size_t)G.hch * (G.ldp_max - 1) + (giou ? 6 : 2) * (size_t)HSLOTS * G.hch) * sizeof(float);
     const size_t o = (size_t)b_off * L.A;
     const int gm = focal_gmode(gamma);
     const dim3 grid(G.blk_off[MAX_MAPS]), block(HTHREADS);
@@ -1725,7 +1865,18 @@ void multibox_focal_loss_grad(const HeadLayout& L, int B, int b_off, const float
 #define SSD_FOCAL_GRAD(T, WIDE)                                                                                                      \
     hipLaunchKernelGGL((focal_grad_kernel<T, WIDE>), grid, block, lds, s, L, G, B, b_off, gamma, alpha, gm, result, labels, w.ce + o, \
                        w.pos + o, w.sample)
-    if (L.nvars <= MAXV) {
+#define SSD_FOCAL_GRAD_GIOU(T, WIDE)                                                                                                  \
+    hipLaunchKernelGGL((focal_grad_kernel<T, WIDE, LOC_GIOU, float>), grid, block, lds, s, L, G, B, b_off, gamma, alpha, gm, result, \
+                       labels, w.ce + o, w.pos + o, w.sample, loc.weight)
+    if (giou) {
+        if (L.nvars <= MAXV) {
+            if (L.grad_bf16) SSD_FOCAL_GRAD_GIOU(bf16_t, false);
+            else SSD_FOCAL_GRAD_GIOU(float, false);
+        } else {
+            if (L.grad_bf16) SSD_FOCAL_GRAD_GIOU(bf16_t, true);
+            else SSD_FOCAL_GRAD_GIOU(float, true);
+        }
+    } else if (L.nvars <= MAXV) {
         if (L.grad_bf16) SSD_FOCAL_GRAD(bf16_t, false);
         else SSD_FOCAL_GRAD(float, false);
     } else {
@@ -1733,6 +1884,7 @@ void multibox_focal_loss_grad(const HeadLayout& L, int B, int b_off, const float
         else SSD_FOCAL_GRAD(float, true);
     }
 #undef SSD_FOCAL_GRAD
+#undef SSD_FOCAL_GRAD_GIOU
     HIP_OK(hipGetLastError());
 }
 

@@ -50,6 +50,35 @@ def checkpoint_loss(ck):
     return str(ck['__loss__']), float(ck['__focal_gamma__']), float(ck['__focal_alpha__'])
 
 
+# localization losses of a training handle (include/ssdvgg_hip.h SSD_LOC_*): the reference's smooth-L1, or GIoU
+LOC_LOSS_KINDS = {'smooth_l1': 0, 'giou': 1}
+
+
+class LocLossConfig(C.Structure):
+    """ssd_loc_loss_config of the C ABI"""
+    _fields_ = [('kind', C.c_int), ('weight', C.c_float)]
+
+
+def loc_loss_config(loc_loss='smooth_l1', loc_weight=1.0):
+    """The ABI's configuration of a localization loss given by name; a bad name, or a weight that is not a finite number > 0:
+    ValueError.  Under 'smooth_l1' the weight is ignored and stored as 1."""
+    if loc_loss not in LOC_LOSS_KINDS:
+        raise ValueError('localization loss must be one of %s, got %r' % (sorted(LOC_LOSS_KINDS), loc_loss))
+    w = float(loc_weight)
+    if loc_loss == 'smooth_l1':
+        return LocLossConfig(LOC_LOSS_KINDS[loc_loss], 1.0)
+    if not (np.isfinite(w) and w > 0.0):
+        raise ValueError('localization loss %r takes a finite weight > 0, got %r' % (loc_loss, loc_weight))
+    return LocLossConfig(LOC_LOSS_KINDS[loc_loss], w)
+
+
+def checkpoint_loc_loss(ck):
+    """(localization loss name, weight) of an opened checkpoint; one from before the option is 'smooth_l1'."""
+    if '__loc_loss__' not in ck.files:
+        return 'smooth_l1', 1.0
+    return str(ck['__loc_loss__']), float(ck['__loc_weight__'])
+
+
 class _Token:
     """An opaque stand-in for a TF tensor/op handle; only identity matters."""
     def __init__(self, name):
@@ -311,13 +340,16 @@ class SSDVGG:
 
     # ------------------------------------------------------------------ optimizer
     def build_optimizer(self, learning_rate=0.001, weight_decay=0.0005, momentum=0.9, global_step=None, loss='mining',
-                        focal_gamma=2.0, focal_alpha=0.25):
+                        focal_gamma=2.0, focal_alpha=0.25, loc_loss='smooth_l1', loc_weight=1.0):
         """ssdvgg.py:375-599.  learning_rate: float or LearningRate (train.py:43-47).  loss: 'mining' (the reference's 3:1
         hard-negative mining) or 'focal' (every anchor, damped by (1 - p_t)^focal_gamma and weighted focal_alpha on positives,
-        1 - focal_alpha on background; a sample without positives still trains its background anchors)."""
+        1 - focal_alpha on background; a sample without positives still trains its background anchors).
+        loc_loss: 'smooth_l1' (the reference's, on the four encoded offsets) or 'giou' (loc_weight * (1 - GIoU) of the predicted
+        against the ground-truth box of every positive anchor); either goes with either `loss`."""
         if not self.training:
             raise RuntimeError('build_from_* was called with training=False')
         self.set_loss(loss, focal_gamma, focal_alpha)
+        self.set_loc_loss(loc_loss, loc_weight)
         lr = learning_rate if isinstance(learning_rate, LearningRate) else LearningRate([learning_rate], [])
         vals = np.array(lr.values, np.float32)
         bnds = np.array(lr.boundaries + [0], np.int64)
@@ -338,8 +370,9 @@ class SSDVGG:
             raise RuntimeError('build_from_metagraph first')
         lr = LearningRate(list(ck['__lr_values__']), list(ck['__lr_boundaries__']))
         loss, gamma, alpha = checkpoint_loss(ck)
+        loc_loss, loc_weight = checkpoint_loc_loss(ck)
         self.build_optimizer(lr, float(ck['__weight_decay__']), float(ck['__momentum__']), int(ck['__global_step__']),
-                             loss=loss, focal_gamma=gamma, focal_alpha=alpha)
+                             loss=loss, focal_gamma=gamma, focal_alpha=alpha, loc_loss=loc_loss, loc_weight=loc_weight)
         for k in ck.files:
             if k.startswith('__momentum__/'):
                 a = np.ascontiguousarray(ck[k], np.float32)
@@ -417,6 +450,8 @@ class SSDVGG:
         if self.training:
             loss, gamma, alpha = self.get_loss()
             d.update(__loss__=np.array(loss), __focal_gamma__=np.array(gamma), __focal_alpha__=np.array(alpha))
+            loc_loss, loc_weight = self.get_loc_loss()
+            d.update(__loc_loss__=np.array(loc_loss), __loc_weight__=np.array(loc_weight))
         np.savez(path, **d)
 
     # ------------------------------------------------------------------ steps
@@ -595,6 +630,17 @@ class SSDVGG:
         """The loss of the steps from the next one on (ssd_set_loss): 'mining' or 'focal' (build_optimizer)."""
         cfg = loss_config(loss, focal_gamma, focal_alpha)
         check(lib.ssd_set_loss(self._h, C.byref(cfg)))
+
+    def set_loc_loss(self, loc_loss='smooth_l1', loc_weight=1.0):
+        """The localization loss of the steps from the next one on (ssd_set_loc_loss): 'smooth_l1' or 'giou' (build_optimizer)."""
+        cfg = loc_loss_config(loc_loss, loc_weight)
+        check(lib.ssd_set_loc_loss(self._h, C.byref(cfg)))
+
+    def get_loc_loss(self):
+        """(name, weight) of the handle's localization loss"""
+        cfg = LocLossConfig()
+        check(lib.ssd_get_loc_loss(self._h, C.byref(cfg)))
+        return [k for k, v in LOC_LOSS_KINDS.items() if v == cfg.kind][0], float(cfg.weight)
 
     def get_loss(self):
         """(name, focal_gamma, focal_alpha) of the handle's loss"""

@@ -158,6 +158,13 @@ def checkpoint_loss(path):
         return of(ck)
 
 
+def checkpoint_loc_loss(path):
+    """(localization loss, weight) a checkpoint's run trained with (checkpoints from before the option: 'smooth_l1')."""
+    from .ssdvgg import checkpoint_loc_loss as of
+    with np.load(path, allow_pickle=False) as ck:
+        return of(ck)
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description='Train the SSD')
     parser.add_argument('--name', default='test', help='project name')
@@ -184,6 +191,8 @@ def main(argv=None):
     parser.add_argument('--loss', default='mining', choices=['mining', 'focal'], help="mining = the reference's softmax cross entropy over the positives and 3x as many hard negatives; focal = the focal loss, every anchor contributes, damped by (1 - p_t)^gamma (DESIGN.md 30); --continue-training takes the checkpoint's")
     parser.add_argument('--focal-gamma', type=float, default=2.0, help='--loss focal: the focusing exponent, 0..5')
     parser.add_argument('--focal-alpha', type=float, default=0.25, help='--loss focal: the weight of a positive anchor (background: 1 - alpha), inside (0, 1)')
+    parser.add_argument('--loc-loss', default='smooth_l1', choices=['smooth_l1', 'giou'], help="the box regression half of the loss: smooth_l1 = the reference's, on the four encoded offsets; giou = 1 - generalized IoU of the predicted against the ground-truth box of every positive anchor (DESIGN.md 31); goes with either --loss; --continue-training takes the checkpoint's")
+    parser.add_argument('--loc-weight', type=float, default=1.0, help='--loc-loss giou: the factor on the localization term, a finite number > 0')
     parser.add_argument('--focal-prior', type=float, default=0.01, help='a fresh --loss focal run: the classifier biases start at a total object probability of this per anchor')
     parser.add_argument('--shapes-size', default='0.2;0.5', help="--data-dir shapes: smallest and largest side of a rectangle, as fractions of the frame")
     parser.add_argument('--synthetic-train', type=int, default=64, help='synthetic training samples per epoch')
@@ -242,6 +251,11 @@ def main(argv=None):
         if asked != ck_loss[:len(asked)]:
             say("[i] --loss %s disagrees with the checkpoint: continuing with its loss, '%s'" % (args.loss, ck_loss[0]))
         args.loss, args.focal_gamma, args.focal_alpha = ck_loss
+        ck_loc = checkpoint_loc_loss(ckpt)
+        asked = (args.loc_loss, args.loc_weight) if args.loc_loss != 'smooth_l1' else (args.loc_loss,)
+        if asked != ck_loc[:len(asked)]:
+            say("[i] --loc-loss %s disagrees with the checkpoint: continuing with its localization loss, '%s'" % (args.loc_loss, ck_loc[0]))
+        args.loc_loss, args.loc_weight = ck_loc
     elif rank == 0:
         try:
             os.makedirs(args.name, exist_ok=True)
@@ -250,13 +264,15 @@ def main(argv=None):
 
     say('[i] Matching rule:        ', args.match)
     try:
-        from .ssdvgg import loss_config
+        from .ssdvgg import loss_config, loc_loss_config
         loss_config(args.loss, args.focal_gamma, args.focal_alpha)
+        loc_loss_config(args.loc_loss, args.loc_weight)
         if args.loss == 'focal' and not 0.0 < args.focal_prior < 1.0:
             raise ValueError('--focal-prior must lie in (0, 1)')
     except ValueError as e:
         print('[!] Bad loss:', str(e)); return 1
     say('[i] Loss:                 ', args.loss if args.loss != 'focal' else 'focal (gamma %g, alpha %g)' % (args.focal_gamma, args.focal_alpha))
+    say('[i] Localization loss:    ', args.loc_loss if args.loc_loss == 'smooth_l1' else '%s (weight %g)' % (args.loc_loss, args.loc_weight))
     if args.cache_gb < 0 or (args.cache_gb and args.decoder != 'gpu'):
         print('[!] --cache-gb keeps pictures decoded on the GPU: it needs --decoder gpu and a size >= 0'); return 1
     try:
@@ -293,7 +309,8 @@ def main(argv=None):
             net.build_from_vgg(args.vgg_dir, td.num_classes, a_trous=args.a_trous, max_batch=args.batch_size, dtype=args.dtype,
                                background_prior=args.focal_prior if args.loss == 'focal' else None)
             net.build_optimizer(learning_rate=lr, weight_decay=args.weight_decay, momentum=args.momentum, loss=args.loss,
-                                focal_gamma=args.focal_gamma, focal_alpha=args.focal_alpha)
+                                focal_gamma=args.focal_gamma, focal_alpha=args.focal_alpha, loc_loss=args.loc_loss,
+                                loc_weight=args.loc_weight)
         if world > 1:
             torch.distributed.broadcast(net.params_flat, 0)
         net.set_stream(torch.cuda.current_stream().cuda_stream)
