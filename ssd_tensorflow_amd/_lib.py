@@ -222,12 +222,18 @@ SIGNATURES = {
     'ssd_op_maxpool_fwd_mxfp6': (i32, [vp, vp, vp, vp] + [i32] * 10 + [vp]),
     'ssd_op_maxpool_fwd': (i32, [vp, vp] + [i32] * 10 + [vp]),
     'ssd_op_maxpool_bwd': (i32, [vp, vp, vp, i32, i32] + [i32] * 10 + [vp]),
+    'ssd_op_maxpool_fwd_bf16': (i32, [vp, vp] + [i32] * 10 + [vp]),
+    'ssd_op_maxpool_bwd_bf16': (i32, [vp, vp, vp, i32, i32] + [i32] * 10 + [vp]),
+    'ssd_op_maxpool_arg_fwd': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    'ssd_op_maxpool_arg_bwd': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     'ssd_op_clock_monitor': (i32, [vp, i32, C.c_uint, vp]),
     'ssd_grads_to_bf16': (i32, [i32, vp, vp, sz, vp]),
     'ssd_grads_from_bf16': (i32, [i32, vp, vp, sz, vp]),
     'ssd_op_l2norm_fwd': (i32, [vp, vp, vp, i32, i32, vp]),
     'ssd_op_l2norm_bwd_ws_floats': (sz, [i32, i32]),
     'ssd_op_l2norm_bwd': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    'ssd_op_l2norm_fwd_bf16': (i32, [vp, vp, vp, i32, i32, vp]),
+    'ssd_op_l2norm_bwd_bf16': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     'ssd_op_multibox_loss_ws_bytes': (sz, [i32, p_i32, p_i32, i32, C.POINTER(sz), p_i32]),
     'ssd_op_multibox_loss': (i32, [i32, p_i32, p_i32, i32, C.POINTER(vp), vp, vp, vp, i32, i32, i32, f32, vp, sz, f32, vp]),
     'ssd_op_multibox_loss_grad': (i32, [i32, p_i32, p_i32, i32, C.POINTER(vp), i32, vp, vp, vp, i32, i32, i32, vp]),

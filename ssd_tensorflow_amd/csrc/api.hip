@@ -1766,6 +1766,42 @@ int ssd_op_maxpool_bwd(const float* x, const float* dy, float* dx, int accumulat
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));     // the scratch dies here
     API_END
 }
+// the bf16 storage forms of the two entry points above: the same dispatch (ops.hip maxpool_fwd_t / maxpool_bwd_t) on bf16_t
+int ssd_op_maxpool_fwd_bf16(const void* x, void* y, int b, int hi, int wi, int c, int ho, int wo, int k, int stride, int pad_h,
+                            int pad_w, void* stream) {
+    API_BEGIN
+    PoolDesc d{b, hi, wi, c, ho, wo, k, stride, pad_h, pad_w};
+    maxpool_fwd(d, (const bf16_t*)x, (bf16_t*)y, (hipStream_t)stream);
+    API_END
+}
+int ssd_op_maxpool_bwd_bf16(const void* x, const void* dy, void* dx, int accumulate, int relu_mask, int b, int hi, int wi, int c,
+                            int ho, int wo, int k, int stride, int pad_h, int pad_w, void* stream) {
+    API_BEGIN
+    PoolDesc d{b, hi, wi, c, ho, wo, k, stride, pad_h, pad_w};
+    DevBuf ws(maxpool_bwd_ws_bytes(d));
+    maxpool_bwd(d, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, accumulate != 0, relu_mask != 0, maxpool_bwd_ws_bytes(d) ? ws.p : nullptr,
+                (hipStream_t)stream);
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));     // the scratch dies here
+    API_END
+}
+// 3x3 stride-1 SAME pooling (mod_pool5) as the training step runs it: the forward pass writes every window's first-maximum tap
+// (arg: one uint32 per window and 4 channels), the backward pass reads it (ops.h maxpool_fwd_arg / maxpool_bwd_arg)
+int ssd_op_maxpool_arg_fwd(const void* x, void* y, void* arg, int bf16, int b, int hi, int wi, int c, void* stream) {
+    API_BEGIN
+    PoolDesc d{b, hi, wi, c, hi, wi, 3, 1, 1, 1};
+    if (bf16) maxpool_fwd_arg(d, (const bf16_t*)x, (bf16_t*)y, arg, (hipStream_t)stream);
+    else maxpool_fwd_arg(d, (const float*)x, (float*)y, arg, (hipStream_t)stream);
+    API_END
+}
+int ssd_op_maxpool_arg_bwd(const void* x, const void* arg, const void* dy, void* dx, int accumulate, int relu_mask, int bf16, int b,
+                           int hi, int wi, int c, void* stream) {
+    API_BEGIN
+    PoolDesc d{b, hi, wi, c, hi, wi, 3, 1, 1, 1};
+    if (bf16)
+        maxpool_bwd_arg(d, (const bf16_t*)x, arg, (const bf16_t*)dy, (bf16_t*)dx, accumulate != 0, relu_mask != 0, (hipStream_t)stream);
+    else maxpool_bwd_arg(d, (const float*)x, arg, (const float*)dy, (float*)dx, accumulate != 0, relu_mask != 0, (hipStream_t)stream);
+    API_END
+}
 // 2x2 stride-2 pooling with the forward-written record (ops.h), fp32 (bf16 = 0) or bf16 storage: the unfused form of the
 // fused-pool entry points below (tests compare the two bit for bit)
 int ssd_op_maxpool_rec_fwd(const void* x, void* y, void* rec, int bf16, int b, int hi, int wi, int c, void* stream) {
@@ -1870,6 +1906,18 @@ int ssd_op_l2norm_bwd(const float* x, const float* scale, const float* dy, float
                       int c, void* stream) {
     API_BEGIN
     l2norm_bwd(npix, c, x, scale, dy, dx, dscale, ws, (hipStream_t)stream);
+    API_END
+}
+// bf16 storage of x / y / dy / dx; scale, dscale and ws stay fp32
+int ssd_op_l2norm_fwd_bf16(const void* x, const float* scale, void* y, int npix, int c, void* stream) {
+    API_BEGIN
+    l2norm_fwd(npix, c, (const bf16_t*)x, scale, (bf16_t*)y, (hipStream_t)stream);
+    API_END
+}
+int ssd_op_l2norm_bwd_bf16(const void* x, const float* scale, const void* dy, void* dx, float* dscale, float* ws, int npix, int c,
+                           void* stream) {
+    API_BEGIN
+    l2norm_bwd(npix, c, (const bf16_t*)x, scale, (const bf16_t*)dy, (bf16_t*)dx, dscale, ws, (hipStream_t)stream);
     API_END
 }
 

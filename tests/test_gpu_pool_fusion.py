@@ -1,8 +1,9 @@
 """-m gpu: the 2x2 stride-2 max-pools fused into their neighbour convolutions (round 5; reference: tf.nn.max_pool between two
 convolutions of the VGG trunk, ssdvgg.py:195-207, TF SAME 75 -> 38: ssdutils.py:40).
 
-The separate passes -- conv, maxpool_fwd_rec, conv data gradient, maxpool_bwd_rec -- are checked against the oracle elsewhere
-(test_gpu_kernels.py, test_gpu_bf16.py, the layer-local tests on SSD_POOL_FUSE=0 handles).  Here the fused kernels must
+The separate passes are checked elsewhere: the convolutions and their data gradients against the oracle in test_gpu_kernels.py,
+test_gpu_bf16.py and the layer-local tests on SSD_POOL_FUSE=0 handles; maxpool_fwd_rec / maxpool_bwd_rec (pooled tensor, record
+and un-pooled gradient, value for value and bit for bit) against a float64 reference in test_gpu_pool_l2_exact.py.  Here the fused kernels must
 reproduce them BIT FOR BIT: pooled tensor, 12-bit record, un-pooled gradient; then whole training steps of a fused and an
 unfused handle, at small and at the benchmarked batch sizes, in both dtypes: result, losses, every gradient identical."""
 import os
