@@ -7,6 +7,7 @@
 #include "ops.h"
 #include "boxes.h"
 #include "bf16.h"
+#include "quant_layout.h"
 #include <string>
 #include <vector>
 #include <map>
@@ -27,11 +28,11 @@ struct Tensor {
     bool grad_f32 = true;    // storage of grad
     void* data = nullptr;
     void* grad = nullptr;
-    // fp8 handle (net.hip plan_fp8): the tensor's e4m3 image for its fp8 readers and its scale; wants16: it also has a reader
-    // that takes the bf16 form
+    // quantised handle (net.hip plan_fp8): the tensor's code image for its quantised readers, in the handle's format (quant_layout.h;
+    // a sample of it: Net::q_at), and its scale (fp8); wants16: it also has a reader that takes the bf16 form
     unsigned char* data8 = nullptr;
     float scale = 0.f;
-    // mxfp8 handle: the E8M0 block scales of data8, one byte per pixel and 32 channels, written by the tensor's producer
+    // MX kinds: the E8M0 block scales of data8, written by the tensor's producer
     unsigned char* scale8 = nullptr;
     bool wants16 = true;
     size_t per_image() const { return (size_t)H * W * C; }
@@ -65,7 +66,7 @@ struct Op {
     // layer's per-channel filter scales
     bool fp8 = false;
     size_t sw_off = 0;
-    size_t w6_off = 0;      // mxfp6 handle: byte offset of the layer's code image in w8_
+    size_t w8_off = 0;      // byte offset of the layer's code image in w8_ (fp8, mxfp8: its arena offset w_off; mxfp6: packed, three quarters the size)
     // Round 6 (fp32): the Winograd F(4x4, 3x3) form of this layer's passes (net.hip plan_winograd; conv.h wino_*): forward, data
     // gradient, weight gradient; the layer's filter transforms [36][Ci][Co] / [36][Co][Ci] and its input's transform [36][tiles][Ci]
     // (written by forward, read by the weight gradient)
@@ -168,7 +169,7 @@ public:
     int nvars() const { return C_ + 5; }
     int max_batch() const { return Bmax_; }
     bool training() const { return training_; }
-    int dtype() const { return mx6_ ? 4 : mx_ ? 3 : fp8_ ? 2 : bf16_ ? 1 : 0; }
+    int dtype() const { return quant_ == Quant::fp8 ? 2 : quant_ == Quant::mxfp8 ? 3 : quant_ == Quant::mxfp6 ? 4 : bf16_ ? 1 : 0; }
     // fp8 handle: one scale per tensor that a convolution writes as e4m3, in graph order
     void fp8_calibrate(const float* x_dev, int b, bool accumulate);      // the graph on the bf16 kernels; scale = max(absmax, tiny) / 448
     int fp8_num_scales() const;
@@ -201,14 +202,13 @@ private:
     bool training_;
     bool bf16_ = false;
     bool fc_ = false;                      // the fc graph (arena_floats)
-    // fp8 handle: e4m3 filter images [tap][Co][Ci] at the filters' arena offsets + per-channel scales, refreshed from the
-    // fp32 masters by every forward pass like the bf16 mirrors (one launch, behind cast_filters)
-    bool fp8_ = false;
-    bool mx_ = false;                      // an fp8 handle (fp8_ is set) of the mxfp8 kind: block scales in Tensor::scale8
-    // ... of the mxfp6 kind (mx_ is set too; conv_mxfp6.hip): data8 holds 24 bytes per 32 channels, the filter images lie in w8_ at
-    // Op::w6_off with their block scales in wsc6_ at Op::sw_off (bytes), and layers with more than 9 taps stay on bf16
-    bool mx6_ = false;
+    // The quantised format of an inference handle's eligible layers (dtype 2 ... 4; bf16_ is set too), quant_layout.h.  fp8 and mxfp8:
+    // e4m3 filter images [tap][Co][Ci] in w8_ at the filters' arena offsets + per-channel scales in sw8_, refreshed from the fp32
+    // masters by every forward pass like the bf16 mirrors (one launch, behind cast_filters).  mxfp6 (conv_mxfp6.hip): the filter
+    // images lie in w8_ at Op::w8_off with their block scales in wsc6_ at Op::sw_off (bytes), and layers with more than 9 taps stay on bf16
+    Quant quant_ = Quant::none;
     unsigned char* wsc6_ = nullptr;
+    QView q_at(const Tensor& t, int b0) const;      // sample b0 of t's quantised form
     bool fp8_calibrated_ = false, fp8_as_bf16_ = false;      // fp8_as_bf16_: this pass is the calibration run
     unsigned char* w8_ = nullptr;
     float *sw8_ = nullptr, *absmax8_ = nullptr;
@@ -230,7 +230,24 @@ private:
     // Issue orders (net.hip build_orders): forward walks fwd_order_ (every multibox head right behind its feature map), backward
     // walks bwd_order_ (reverse graph order)
     std::vector<int> fwd_order_, bwd_order_;
-    std::vector<char> bw_conv_done_;     // backward: conv ops processed so far (indexed like ops_)
+    // Which filter ranges have their final gradient.  backward_step retires every convolution it has issued, backward_ranges walks
+    // bwd_order_ with an instance of its own and launches nothing: both report their stages from the same loop condition (next)
+    // and the same chain rule (retire).
+    struct BwProgress {
+        const Net* net = nullptr;
+        std::vector<char> done;          // conv ops retired so far (indexed like ops_)
+        bool chain_done = false;         // the tail chain's members (all but chain_first_) are retired: they finish together
+        int pos = 0;                     // next entry of bwd_order_
+        size_t hi = 0, lo = 0;           // the current stage's range so far: [lo, hi)
+        void begin(const Net* n);
+        int next(size_t min_floats);     // the stage's next op, -1 once it has gathered min_floats or the order is exhausted
+        bool finished() const;
+        size_t retire(int op_index);     // -> lo; a chain member met first retires the chain with it
+        void retire_chain();             // launch_tail_backward, behind the chain's grouped weight-gradient launch
+        std::pair<size_t, size_t> end_stage();      // (offset, count) of the stage; the next one starts below it
+    private:
+        size_t final_lo() const;         // lowest arena offset such that every filter at or above it has its final gradient
+    } bw_;
     // backward stream classes: 0 = a lane's main stream, 1 = its side stream.  bw_issued_[c] counts the kernels class c has been
     // given that write a gradient, bw_seen_[x][y] is the count of class y that class x has already been made to wait for
     long bw_issued_[2] = {0, 0}, bw_seen_[2][2] = {{0, 0}, {0, 0}};
@@ -240,6 +257,8 @@ private:
     bool bw_first_fused_ = false;        // ... and this backward pass took it
     int fused_first_out_ = -1;           // the tensor whose gradient that pass did not materialise (conv1_1's output)
     void launch_wgrad(int op_index, int b, hipStream_t ws);
+    // the data gradient of one convolution into dst (= in, or the input of the pool `up` it un-pools), on ds
+    void launch_dgrad(const Op& op, const ConvDesc& d, const Op* up, Tensor& dst, bool mask, int cls, hipStream_t ds);
     // Round 6 (bf16): the latency-bound tail as one launch per direction (conv.h TailStage; net.hip plan_tail_chain).  chain_first_ =
     // op index of the first 1x1 layer below the 10x10 map (vgg300: conv9_1, vgg512: conv10_1), -1: off; in_chain_[op] marks the
     // extra layers from there on and the multibox heads that read them.
@@ -249,7 +268,6 @@ private:
     std::vector<long long> tail_fwd_off_, tail_bwd_off_; // ... element offsets per op of the forward / data-gradient form (-1: none)
     void pack_tail_filters(hipStream_t s);               // from the fresh bf16 mirrors, one launch (forward, behind cast_filters)
     bool chain_fwd_ = false, chain_bwd_ = false;      // SSD_TAIL_FUSE bit 0 / bit 1: the chain in forward / in backward
-    bool bw_chain_done_ = false;         // this backward pass has issued the chain's data gradients and grouped weight gradients
     void plan_tail_chain();
     // Round 6 (fp32): Winograd layers.  Scratch shared by every such layer: the GEMM results of a forward lane (wino_m_), the
     // transformed dy / dx of the data gradient (main stream: wino_yt_, wino_xw_), the transformed dy and the slabs of the weight
@@ -261,6 +279,34 @@ private:
     bool wino_any_f_ = false, wino_any_d_ = false;
     float *wino_m_[3] = {nullptr, nullptr, nullptr}, *wino_vs_[3] = {nullptr, nullptr, nullptr}, *wino_yt_ = nullptr, *wino_xw_ = nullptr, *wino_ya_ = nullptr, *wino_slab_ = nullptr;
     hipEvent_t ev_wino_ = nullptr, ev_wino_first_ = nullptr, ev_wino_flip_ = nullptr;
+    // A forward pass (net.hip, "steps"): forward builds the lanes, walks fwd_order_ and joins; the members below do the rest.
+    struct Lane {
+        hipStream_t s, h;
+        hipEvent_t* ev_fmap;
+        hipEvent_t ev_h;
+        int b0, nb;
+        bool heads_on_side, cast_pending;
+        int wino_pending;                 // filter-transform events this lane has still to wait for: 2 = the first layer's, then 1 = the rest
+        bool fmap_carried[MAX_MAPS];      // the feature map's producer carried ev_fmap[head] itself (g_stop_event)
+    };
+    struct FwdPass {                      // the state of one pass, on forward's stack
+        Lane lane[2];
+        int nl, nl_cur;                   // lanes of the pass / of the current op (they merge at conv8_1)
+        bool heads_full;                  // with two lanes the multibox heads run as full-batch launches (forward_conv)
+        int small_heads;
+        int b;
+        bool train_mode, run8, side;      // run8: the quantised layers run on their codes (the calibration pass does not)
+    };
+    struct LossSlotGuard;
+    struct ConvRun;
+    void forward_filters(FwdPass& p, LossSlotGuard& guard);
+    void forward_conv(FwdPass& p, int li, int op_index);
+    bool conv_stream(FwdPass& p, int li, const Op& op, ConvRun& r);
+    void conv_wino_scratch(const FwdPass& p, int li, int op_index, const ConvDesc& d, ConvRun& r);
+    void launch_conv_fwd(const FwdPass& p, const Op& op, const ConvDesc& d, const ConvRun& r);
+    void forward_pool(FwdPass& p, int li, int op_index);
+    void forward_l2norm(FwdPass& p, int li, int op_index);
+    void forward_loss(FwdPass& p, const float* y, LossSlotGuard& guard);
     void launch_tail_forward(int b0, int nb, hipStream_t s);
     void launch_tail_backward(int b, bool* side_used);
     void build_orders();
@@ -269,7 +315,6 @@ private:
     void bw_sync(int x, int y);          // class x waits for everything class y has been given so far
     void bw_need(int x, const Tensor& t);
     void bw_wrote(int x, Tensor& t, bool carried = false);
-    size_t bw_final_lo() const;          // lowest arena offset such that every filter at or above it has its final gradient
     bool overlap_ = true;
 
     std::vector<Tensor> tensors_;
@@ -315,8 +360,7 @@ private:
     float focal_gamma_ = 2.f, focal_alpha_ = 0.25f, bw_gamma_ = 2.f, bw_alpha_ = 0.25f;
     LocLoss loc_{}, bw_loc_{};              // SSD_LOC_SMOOTH_L1 / SSD_LOC_GIOU and its weight; bw_: of the last training forward
     Profiler prof_;
-    int bw_pos_ = 0, bw_b_ = 0;          // next entry of bwd_order_
-    size_t bw_done_off_ = 0;
+    int bw_b_ = 0;
     // Every buffer, pinned page, event and stream above that the handle made itself.  Declared after every member that holds its
     // handles, so it is destroyed before them: the device is synchronised before the members above (prof_'s events) go.
     HipOwner hip_;

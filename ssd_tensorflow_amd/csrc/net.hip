@@ -234,7 +234,7 @@ static int env_i(const char* name, int dflt) {
 //  * Backward: reverse graph order, in bf16 with the big heads behind the chain (below).  (Round 4 built and measured another
 //    alternative -- head 0 + l2-norm deferred beside mod_conv6 on the side stream: chain 450 -> 264 us, step 7.22 -> 7.37 ms,
 //    profiles/r04_g_ab_schedule_bf16.txt; re-measured in round 5: 6.864 -> 6.885 ms.  The bookkeeping (bw_need / bw_sync /
-//    bw_final_lo) serves any valid order.)
+//    BwProgress) serves any valid order.)
 void Net::build_orders() {
     const int n = (int)ops_.size();
     fwd_order_.clear();
@@ -299,14 +299,56 @@ void Net::bw_wrote(int x, Tensor& t, bool carried) {
     }
 }
 
-size_t Net::bw_final_lo() const {
-    size_t lo = nfilters_;
-    for (int i = (int)ops_.size() - 1; i >= 0; --i) {
-        if (ops_[i].kind != OP_CONV) continue;
-        if (!bw_conv_done_[i]) break;
-        lo = ops_[i].w_off;      // conv ops own descending, adjacent filter ranges
+void Net::BwProgress::begin(const Net* n) {
+    net = n;
+    done.assign(n->ops_.size(), 0);
+    chain_done = false;
+    pos = 0;
+    hi = lo = n->nfilters_;
+}
+
+// (min_floats = 0 counts as 1: a stage that asked for nothing would run no op, and a caller that loops until the order is exhausted --
+// backward_ranges, every staged backward -- would never return)
+int Net::BwProgress::next(size_t min_floats) {
+    return !finished() && hi - lo < std::max<size_t>(min_floats, 1) ? net->bwd_order_[pos++] : -1;
+}
+
+bool Net::BwProgress::finished() const { return pos >= (int)net->bwd_order_.size(); }
+
+size_t Net::BwProgress::final_lo() const {
+    size_t f = net->nfilters_;
+    for (int i = (int)net->ops_.size() - 1; i >= 0; --i) {
+        if (net->ops_[i].kind != OP_CONV) continue;
+        if (!done[i]) break;
+        f = net->ops_[i].w_off;      // conv ops own descending, adjacent filter ranges
     }
-    return lo;
+    return f;
+}
+
+// The chain rule (plan_tail_chain): the chain's weight gradients are one grouped launch, issued when backward meets the chain's first
+// member in its order -- all of them but chain_first_'s, which keeps its own launch and retires when its turn comes.
+void Net::BwProgress::retire_chain() {
+    for (size_t j = 0; j < net->ops_.size(); ++j)
+        if (net->in_chain_[j] && (int)j != net->chain_first_) done[j] = 1;
+    chain_done = true;
+    lo = final_lo();
+}
+
+size_t Net::BwProgress::retire(int op_index) {
+    const Op& op = net->ops_[op_index];
+    if (op.kind != OP_CONV) return lo;
+    if (net->chain_bwd_ && net->in_chain_[op_index] && !op_ablated(op.name, op.kind, op.head, op.k)) {
+        if (!chain_done) retire_chain();
+        if (op_index != net->chain_first_) return lo;
+    }
+    done[op_index] = 1;
+    return lo = final_lo();
+}
+
+std::pair<size_t, size_t> Net::BwProgress::end_stage() {
+    const std::pair<size_t, size_t> r(lo, hi - lo);
+    hi = lo;
+    return r;
 }
 
 // Pool fusion (round 5).  A 2x2 stride-2 pool whose input has no other consumer (pool1-3: conv4_3 also feeds the l2-norm) is
@@ -503,13 +545,13 @@ void Net::launch_tail_backward(int b, bool* side_used) {
         const Tensor& out = tensors_[op.out];
         WgradGroupItem it{};
         it.d = conv_desc(op, b);
-        if (oi == chain_first_) continue;      // (whatever the batch: backward_ranges, which knows no batch, mirrors this)
+        if (oi == chain_first_) continue;      // (whatever the batch: BwProgress::retire_chain, which knows no batch, leaves it out too)
         it.x = in.h(); it.dy = out.gh();
         it.dw = grads_ + op.w_off; it.dbias = grads_ + op.b_off; it.w = params_ + op.w_off;
         items.push_back(it);
-        bw_conv_done_[oi] = 1;
     }
     conv_wgrad_group_bf16(items.data(), (int)items.size(), wd_, ws);
+    bw_.retire_chain();
     if (wside) *side_used = true;
 }
 
@@ -587,8 +629,8 @@ void Net::plan_winograd() {
 // e4m3 (data8).  A pool between two fp8 layers runs on the bytes and its output shares its input's scale.  Where the e4m3 form is
 // needed behind a bf16 producer (conv3_1's output in the a-trous graph) a quantise pass of its own makes it.  A tensor with any non-fp8 reader (conv4_3: the l2 norm; mod_conv7's output: its head and conv8_1) keeps its
 // bf16 form as well (wants16).  Runs before plan_pool_fusion, which leaves the fp8 layers' pools alone.
-// An mxfp6 handle (mx6_) takes the mxfp8 plan for up to 9 taps -- the same eligibility, on conv_fwd_mxfp6 -- and leaves a layer
-// with more on conv_bigk_fwd_bf16; its filter images and their block scales get arenas of their own (Op::w6_off, Op::sw_off in bytes).
+// An mxfp6 handle (Quant::mxfp6) takes the mxfp8 plan for up to 9 taps -- the same eligibility, on conv_fwd_mxfp6 -- and leaves a layer
+// with more on conv_bigk_fwd_bf16; its filter images and their block scales get arenas of their own (Op::w8_off, Op::sw_off in bytes).
 void Net::plan_fp8() {
     size_t nsw = 0;
     for (Tensor& t : tensors_) t.wants16 = false;
@@ -601,16 +643,19 @@ void Net::plan_fp8() {
         // (mxfp8: the fc graph's fc6 stays on bf16 with a quantise pass behind it unless SSD_MXFP8_BIGK=1 -- conv_bigk_fwd_mxfp8_worthwhile;
         // asked with the most demanding output mode, so that whichever form the readers below take can be launched)
         // (mxfp6: the mxfp8 handle's layers up to 9 taps -- the same Ci % 64, Co % 8 contract -- and nothing above: no mxfp6 kernel for more)
-        const bool kernel8 = !conv_bigk(d) ? conv_fwd_fp8_supported(d, nullptr) && conv_fwd_fp8_worthwhile(d) && (!mx6_ || conv_fwd_mxfp6_supported(d, nullptr))
-                             : mx6_        ? false
-                             : mx_         ? conv_bigk_fwd_mxfp8_supported(d, FP8_OUT_BF16_MX, nullptr) && conv_bigk_fwd_mxfp8_worthwhile(d)
-                                           : conv_bigk_fwd_fp8_supported(d, nullptr) && conv_bigk_fwd_fp8_worthwhile(d);
+        const bool kernel8 = !conv_bigk(d) ? conv_fwd_fp8_supported(d, nullptr) && conv_fwd_fp8_worthwhile(d) && (quant_ != Quant::mxfp6 || conv_fwd_mxfp6_supported(d, nullptr))
+                             : quant_ == Quant::mxfp6 ? false
+                             : quant_ == Quant::mxfp8 ? conv_bigk_fwd_mxfp8_supported(d, FP8_OUT_BF16_MX, nullptr) && conv_bigk_fwd_mxfp8_worthwhile(d)
+                                                      : conv_bigk_fwd_fp8_supported(d, nullptr) && conv_bigk_fwd_fp8_worthwhile(d);
         op.fp8 = op.head < 0 && i < tail_first_ && !tensors_[op.in].data_f32 && kernel8;
     }
     auto need8 = [&](Tensor& t) {
+        // One byte per element, whatever the kind: an mxfp6 tensor takes quant_code_bytes() of it, three quarters.  The size is kept:
+        // which bytes past a format's nominal end its kernels touch has not been checked on a GPU.
         if (!t.data8) t.data8 = static_cast<unsigned char*>(hip_.mem(t.per_image() * Bmax_));
-        // (+ 8: conv_fwd_mxfp8 reads the scales in whole dwords)
-        if (mx_ && !t.scale8) t.scale8 = static_cast<unsigned char*>(hip_.mem(t.per_image() / 32 * Bmax_ + 8));
+        // (+ 8: conv_fwd_mxfp8 and conv_fwd_mxfp6 read the scales in whole dwords)
+        if (quant_block_scales(quant_) && !t.scale8)
+            t.scale8 = static_cast<unsigned char*>(hip_.mem(quant_scale_bytes(quant_, t.per_image()) * Bmax_ + 8));
     };
     for (int i = (int)ops_.size() - 1; i >= 0; --i) {      // readers before their producers: a pool learns from its consumer
         Op& op = ops_[i];
@@ -634,42 +679,48 @@ void Net::plan_fp8() {
     for (int t : head_t_) tensors_[t].wants16 = true;      // (fp32, read by the loss / result pass)
     size_t nw6 = 0;      // mxfp6: bytes of code images so far; every image and scale table starts at a multiple of 16 bytes
     for (Op& op : ops_) {
-        if (op.kind == OP_CONV && op.fp8 && mx6_) {
+        if (op.kind == OP_CONV && op.fp8 && quant_ == Quant::mxfp6) {
             const Tensor& in = tensors_[op.in];
             const Tensor& out = tensors_[op.out];
-            const size_t blocks = (size_t)op.KH * op.KW * out.C * (in.C / 32);
+            const size_t n = (size_t)op.KH * op.KW * out.C * in.C;      // (blocks along Ci, a multiple of 64)
             op.sw_off = nsw;
-            op.w6_off = nw6;
+            op.w8_off = nw6;
             quant_plan_.add(op.w_off, nw6, nsw, op.KH * op.KW, in.C, out.C);
-            nw6 += (blocks * 24 + 15) / 16 * 16;
-            nsw += (blocks + 15) / 16 * 16;
+            nw6 += (quant_code_bytes(quant_, n) + 15) / 16 * 16;
+            nsw += (quant_scale_bytes(quant_, n) + 15) / 16 * 16;
         } else if (op.kind == OP_CONV && op.fp8) {
             const Tensor& in = tensors_[op.in];
             const Tensor& out = tensors_[op.out];
             op.sw_off = nsw;
-            quant_plan_.add(op.w_off, op.w_off, nsw, op.KH * op.KW, in.C, out.C);
+            op.w8_off = op.w_off;
+            quant_plan_.add(op.w_off, op.w8_off, nsw, op.KH * op.KW, in.C, out.C);
             nsw += out.C;
         }
         Tensor& out = tensors_[op.out];
         if (!out.data8) continue;
         if (!op.fp8) out.wants16 = true;      // a bf16 op writes bf16; the quantise pass behind it makes the e4m3 form
-        if (!(op.kind == OP_POOL && op.fp8) && !mx_) fp8_scaled_.push_back(op.out);      // (mxfp8: no tensor owns a scale)
+        if (!(op.kind == OP_POOL && op.fp8) && quant_tensor_scale(quant_)) fp8_scaled_.push_back(op.out);      // (MX kinds: no tensor owns a scale)
     }
     SSD_REQUIRE(quant_plan_.n > 0, "no layer of this graph is eligible for fp8");
-    if (mx6_) {      // (+ 8: conv_fwd_mxfp6 reads the scales in whole dwords)
+    if (quant_ == Quant::mxfp6) {      // (+ 8: conv_fwd_mxfp6 reads the scales in whole dwords)
         w8_ = static_cast<unsigned char*>(hip_.mem(nw6));
         wsc6_ = static_cast<unsigned char*>(hip_.mem(nsw + 8));
         return;
     }
     w8_ = static_cast<unsigned char*>(hip_.mem(nfilters_));
     sw8_ = static_cast<float*>(hip_.mem(nsw * sizeof(float)));
-    if (!mx_) absmax8_ = static_cast<float*>(hip_.mem(fp8_scaled_.size() * sizeof(float)));
+    if (quant_tensor_scale(quant_)) absmax8_ = static_cast<float*>(hip_.mem(fp8_scaled_.size() * sizeof(float)));
+}
+
+QView Net::q_at(const Tensor& t, int b0) const {
+    return QView{t.data8 ? t.data8 + (size_t)b0 * quant_code_bytes(quant_, t.per_image()) : nullptr,
+                 t.scale8 ? t.scale8 + (size_t)b0 * quant_scale_bytes(quant_, t.per_image()) : nullptr, t.scale};
 }
 
 void Net::require_fp8() const {
-    SSD_REQUIRE(!mx6_, "an mxfp6 handle has no calibration scales (SSD_DTYPE_MXFP6): every producer chooses its block scales itself");
-    SSD_REQUIRE(!mx_, "an mxfp8 handle has no calibration scales (SSD_DTYPE_MXFP8): every producer chooses its block scales itself");
-    SSD_REQUIRE(fp8_, "not an fp8 handle (SSD_DTYPE_FP8)");
+    SSD_REQUIRE(quant_ != Quant::mxfp6, "an mxfp6 handle has no calibration scales (SSD_DTYPE_MXFP6): every producer chooses its block scales itself");
+    SSD_REQUIRE(quant_ != Quant::mxfp8, "an mxfp8 handle has no calibration scales (SSD_DTYPE_MXFP8): every producer chooses its block scales itself");
+    SSD_REQUIRE(quant_ == Quant::fp8, "not an fp8 handle (SSD_DTYPE_FP8)");
 }
 
 void Net::fp8_share_pool_scales() {
@@ -890,10 +941,10 @@ void Net::init_weights(unsigned long long seed) {
 Net::Net(const char* preset, int num_classes, int max_batch, int device, bool training, unsigned long long seed,
          float* ext_params, float* ext_grads, float* ext_momentum, int dtype, int graph)
     : preset_(&get_preset(preset)), C_(num_classes), Bmax_(max_batch), device_(device), training_(training), bf16_(dtype >= 1 && dtype <= 4),
-      fc_(graph == 1), fp8_(dtype >= 2 && dtype <= 4), mx_(dtype == 3 || dtype == 4), mx6_(dtype == 4), hip_(device) {
+      fc_(graph == 1), quant_(dtype == 2 ? Quant::fp8 : dtype == 3 ? Quant::mxfp8 : dtype == 4 ? Quant::mxfp6 : Quant::none), hip_(device) {
     SSD_REQUIRE(dtype >= 0 && dtype <= 4, "dtype must be 0 (fp32), 1 (bf16), 2 (fp8), 3 (mxfp8) or 4 (mxfp6), got %d", dtype);
-    SSD_REQUIRE(!(fp8_ && training), "%s is inference only: create the handle with training = 0",
-                mx6_ ? "SSD_DTYPE_MXFP6" : mx_ ? "SSD_DTYPE_MXFP8" : "SSD_DTYPE_FP8");
+    SSD_REQUIRE(!(quant_ != Quant::none && training), "%s is inference only: create the handle with training = 0",
+                quant_ == Quant::mxfp6 ? "SSD_DTYPE_MXFP6" : quant_ == Quant::mxfp8 ? "SSD_DTYPE_MXFP8" : "SSD_DTYPE_FP8");
     SSD_REQUIRE(graph == 0 || graph == 1, "graph must be 0 (a-trous) or 1 (fc), got %d", graph);
     require_num_classes(num_classes);
     SSD_REQUIRE(max_batch >= 1, "max_batch must be >= 1");
@@ -928,7 +979,7 @@ Net::Net(const char* preset, int num_classes, int max_batch, int device, bool tr
     // streams beside the caller's measure the same as four (bf16 4142 vs 4081 images/s, r02_w) and leave the fourth queue to
     // a data-parallel caller's collective stream.
     s2_ = training_ ? wstream_ : hip_.stream();
-    if (fp8_) plan_fp8();
+    if (quant_ != Quant::none) plan_fp8();
     plan_pool_fusion();
     plan_tail_chain();
     plan_winograd();
@@ -939,6 +990,7 @@ Net::Net(const char* preset, int num_classes, int max_batch, int device, bool tr
         for (const Op& op : ops_)
             if (op.in != input_t_ && !tensors_[op.in].gev)
                 tensors_[op.in].gev = hip_.event();
+    bw_.begin(this);
 }
 
 Net::~Net() {
@@ -948,6 +1000,78 @@ Net::~Net() {
 // ---------------------------------------------------------------------------------
 // steps
 // ---------------------------------------------------------------------------------
+static char* at(const Tensor& t, int b0, bool grad = false) {      // first element of sample b0
+    return static_cast<char*>(grad ? t.grad : t.data) + (size_t)b0 * t.per_image() * ((grad ? t.grad_f32 : t.data_f32) ? 4 : 2);
+}
+
+// ---- The quantised kinds: one dispatcher per operation, each on views of its operands (Net::q_at), each the launcher of the format.
+// the stand-alone quantise pass behind a bf16 producer: nb samples of t's bf16 form (src) into its quantised form from dst on
+static void quantize_q(Quant q, const Tensor& t, const void* src, int nb, QView dst, hipStream_t s) {
+    switch (q) {
+    case Quant::mxfp6: quantize_mxfp6(src, false, (size_t)nb * t.H * t.W, t.C, dst.codes, dst.scales, s); break;
+    case Quant::mxfp8: quantize_mxfp8(src, false, (size_t)nb * t.H * t.W, t.C, dst.codes, dst.scales, s); break;
+    case Quant::fp8: quantize_fp8(src, false, (size_t)nb * t.per_image(), dst.scale, dst.codes, s); break;
+    case Quant::none: fail("quantize: the handle has no quantised format");
+    }
+}
+
+// the filter images with their per-channel scales (sw8) or their block scales (wsc6), fresh from the fp32 masters: one launch
+static void quantize_filters_q(Quant q, const FilterQuantPlan& plan, const float* w, unsigned char* w8, float* sw8, unsigned char* wsc6, hipStream_t s) {
+    if (q == Quant::mxfp6) quantize_filters_mxfp6(plan, w, w8, wsc6, s);
+    else quantize_filters_fp8(plan, w, w8, sw8, s);
+}
+
+// The convolution on quantised operands; the output in the form(s) its readers take: codes where it has a quantised form (y8), bf16 (y)
+// where it has no such form or a reader wants that as well (wants16).  sw / wsc: the layer's per-channel / block filter scales.
+static void conv_fwd_q(Quant q, const ConvDesc& d, QView x, const unsigned char* w, const float* sw, const unsigned char* wsc, const float* bias,
+                       void* y, QView y8, bool wants16, bool relu, hipStream_t s) {
+    const int mx_mode = y8.codes ? (wants16 ? FP8_OUT_BF16_MX : FP8_OUT_MX) : FP8_OUT_BF16;
+    switch (q) {
+    case Quant::mxfp6:      // e2m3 operands, block scales on both
+        conv_fwd_mxfp6(d, x.codes, x.scales, w, wsc, bias, y, y8.codes, y8.scales, mx_mode, relu, s);
+        break;
+    case Quant::mxfp8:      // e4m3 operands with block scales (more than 9 taps: the fc graph's mod_conv6 under SSD_MXFP8_BIGK=1)
+        (conv_bigk(d) ? conv_bigk_fwd_mxfp8 : conv_fwd_mxfp8)(d, x.codes, x.scales, w, sw, bias, y, y8.codes, y8.scales, mx_mode, relu, s);
+        break;
+    case Quant::fp8:        // e4m3 operands (more than 9 taps: the fc graph's mod_conv6)
+        (conv_bigk(d) ? conv_bigk_fwd_fp8 : conv_fwd_fp8)(d, x.codes, w, x.scale, sw, bias, y, y8.codes,
+                                                          y8.codes ? (wants16 ? FP8_OUT_BF16_E4M3 : FP8_OUT_E4M3) : FP8_OUT_BF16, y8.scale, relu, s);
+        break;
+    case Quant::none: fail("convolution: the handle has no quantised format");
+    }
+}
+
+// max-pooling on the codes: fp8 on the bytes (the output shares the input's scale), the MX kinds on the dequantised cells, with block
+// scales of the output's own
+static void maxpool_fwd_q(Quant q, const PoolDesc& d, QView x, QView y, hipStream_t s) {
+    switch (q) {
+    case Quant::mxfp6: maxpool_fwd_mxfp6(d, x.codes, x.scales, y.codes, y.scales, s); break;
+    case Quant::mxfp8: maxpool_fwd_mxfp8(d, x.codes, x.scales, y.codes, y.scales, s); break;
+    case Quant::fp8: maxpool_fwd_fp8(d, x.codes, y.codes, s); break;
+    case Quant::none: fail("max-pool: the handle has no quantised format");
+    }
+}
+
+// A forward pass that fails after it has taken a slot of the loss ring gives the slot back: its event was never
+// recorded, and a reader one step late (get_losses_step) would otherwise be handed a slot of four passes ago.
+struct Net::LossSlotGuard {
+    long long& seq;
+    bool armed = false;
+    bool done = false;
+    explicit LossSlotGuard(long long& s) : seq(s) {}
+    void failed() { if (armed && !done) { --seq; armed = false; } }
+    ~LossSlotGuard() { if (armed && !done) --seq; }
+};
+
+// where one forward convolution launch runs and on which samples; wino_M set: in the Winograd form, on this scratch
+struct Net::ConvRun {
+    hipStream_t cs;
+    int b0, nb;
+    float *wino_M = nullptr, *wino_V = nullptr;
+    size_t wino_vps = 0;
+    void* wino_bits = nullptr;
+};
+
 // Forward runs the op list on up to two LANES: the batch is cut in two halves that walk the network side by side (lane 0
 // on the caller's stream + the side stream for its heads, lane 1 with its heads on s2_, which is the
 // weight-gradient stream: see the constructor), so that the tail of one half's kernel (its last, partial round of workgroups) is filled by the other half's
@@ -956,9 +1080,8 @@ Net::~Net() {
 // reduction, which the last per-sample workgroup of either lane performs (ops.hip).
 void Net::forward(const float* x, int b, bool train_mode, const float* y) {
     SSD_REQUIRE(b >= 1 && b <= Bmax_, "batch %d outside 1..%d (max_batch)", b, Bmax_);
-    SSD_REQUIRE(!fp8_ || mx_ || fp8_as_bf16_ || fp8_calibrated_,
+    SSD_REQUIRE(quant_ != Quant::fp8 || fp8_as_bf16_ || fp8_calibrated_,
                 "the fp8 handle has no activation scales yet: call ssd_fp8_calibrate_dev or ssd_fp8_set_scales before inference");
-    const bool run8 = fp8_ && !fp8_as_bf16_;      // this pass runs the fp8 layers on e4m3 operands (the calibration pass does not)
     g_prof = &prof_;
     tensors_[input_t_].data = const_cast<float*>(x);
     pool_arg_op_ = -1;
@@ -967,42 +1090,65 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
     static const int lanes_env = [] { const char* v = getenv("SSD_FWD_LANES"); return v ? atoi(v) : 0; }();
     const int want_lanes = lanes_env > 0 ? lanes_env : 2;
     const int nl = (want_lanes >= 2 && side && s2_ && b >= 8) ? 2 : 1;
-    const bool heads_full = nl == 2;      // with two lanes the multibox heads run as full-batch launches (see the head ops below)
-    struct Lane {
-        hipStream_t s, h;
-        hipEvent_t* ev_fmap;
-        hipEvent_t ev_h;
-        int b0, nb;
-        bool heads_on_side, cast_pending;
-        int wino_pending;                 // filter-transform events this lane has still to wait for: 2 = the first layer's, then 1 = the rest
-        bool fmap_carried[MAX_MAPS];      // the feature map's producer carried ev_fmap[head] itself (g_stop_event)
-    } lane[2] = {{stream_, hstream_, ev_fmap_, ev_h_, 0, nl == 2 ? (b + 1) / 2 : b, false, false, 0, {}},
-                 {s2_, s2_, ev2_fmap_, ev2_h_, (b + 1) / 2, b - (b + 1) / 2, false, false, 0, {}}};
-    // feature map tensor -> the head that reads it (-1: none), for the carried events
-    auto head_of = [&](int tensor) {
-        for (const Op& o : ops_)
-            if (o.kind == OP_CONV && o.head >= 0 && o.in == tensor) return o.head;
-        return -1;
-    };
-    auto at = [](const Tensor& t, int b0, bool grad = false) -> char* {      // first element of sample b0
-        return static_cast<char*>(grad ? t.grad : t.data) + (size_t)b0 * t.per_image() * ((grad ? t.grad_f32 : t.data_f32) ? 4 : 2);
-    };
-    // the stand-alone quantise pass behind a bf16 producer: samples b0 ... b0 + nb of t's bf16 form (src) into its e4m3 form
-    auto quantize8 = [&](const Tensor& t, const void* src, int b0, int nb, hipStream_t s) {
-        if (mx6_)      // (24 code bytes per 32 channels)
-            quantize_mxfp6(src, false, (size_t)nb * t.H * t.W, t.C, t.data8 + (size_t)b0 * (t.per_image() / 32 * 24),
-                           t.scale8 + (size_t)b0 * (t.per_image() / 32), s);
-        else if (mx_)
-            quantize_mxfp8(src, false, (size_t)nb * t.H * t.W, t.C, t.data8 + (size_t)b0 * t.per_image(), t.scale8 + (size_t)b0 * (t.per_image() / 32), s);
-        else
-            quantize_fp8(src, false, (size_t)nb * t.per_image(), t.scale, t.data8 + (size_t)b0 * t.per_image(), s);
-    };
+    FwdPass p{{{stream_, hstream_, ev_fmap_, ev_h_, 0, nl == 2 ? (b + 1) / 2 : b, false, false, 0, {}},
+               {s2_, s2_, ev2_fmap_, ev2_h_, (b + 1) / 2, b - (b + 1) / 2, false, false, 0, {}}},
+              nl, nl, nl == 2, 0, b, train_mode, quant_ != Quant::none && !fp8_as_bf16_, side};
     if (side && (bf16_ || train_mode || nl == 2)) {
         HIP_OK(hipEventRecord(ev_fmap_[MAX_MAPS - 1], stream_));      // everything issued so far (the previous step's update)
         HIP_OK(hipStreamWaitEvent(hstream_, ev_fmap_[MAX_MAPS - 1], 0));
         if (nl == 2) HIP_OK(hipStreamWaitEvent(s2_, ev_fmap_[MAX_MAPS - 1], 0));
-        lane[0].heads_on_side = true;
+        p.lane[0].heads_on_side = true;
     }
+    LossSlotGuard fwd_guard(loss_seq_);
+    forward_filters(p, fwd_guard);
+    // Round 5: the lanes MERGE at conv8_1.  The extra layers behind it are a chain of sixteen dependent launches of a handful of
+    // workgroups each (conv8_1 ... conv11_2 on two lanes: 6-37 us per launch, every one of them latency- not work-bound): a
+    // timeline of the step (profiles/r05_j_timeline_bf16.txt) shows 285 us between mod_conv7 and the loss with a nearly empty chip.
+    // One lane runs the eight layers once, at twice the rows per launch and the same latency; the second lane's stream -- idle
+    // from here on -- takes every other small head, which used to queue behind each other on the one side stream.
+    // (Round 4 merged at the 19x19 maps, i.e. incl. conv5_x / mod_conv6, where two lanes fill each other's partial rounds: slower.)
+    for (const int op_index : fwd_order_) {
+        const Op& op = ops_[op_index];
+        prof_.layer = op.name.c_str();
+        if (op_ablated(op.name, op.kind, op.head, op.k)) continue;
+        if (chain_fwd_ && in_chain_[op_index]) {      // Round 6 (plan_tail_chain): the chain's layers and heads run as ONE launch per lane, issued at its first op
+            if (op_index == chain_first_)
+                for (int li = 0; li < p.nl_cur; ++li) {
+                    Lane& ln = p.lane[li];
+                    if (ln.cast_pending) {
+                        HIP_OK(hipStreamWaitEvent(ln.s, ev_cast_, 0));
+                        ln.cast_pending = false;
+                    }
+                    launch_tail_forward(ln.b0, ln.nb, ln.s);
+                }
+            continue;
+        }
+        if (p.nl_cur == 2 && p.heads_full && op_index == tail_first_) {
+            HIP_OK(hipEventRecord(ev_join_, s2_));
+            HIP_OK(hipStreamWaitEvent(stream_, ev_join_, 0));
+            p.lane[0].nb = b;
+            p.nl_cur = 1;
+        }
+        for (int li = 0; li < p.nl_cur; ++li)
+            switch (op.kind) {
+            case OP_CONV: forward_conv(p, li, op_index); break;
+            case OP_POOL: forward_pool(p, li, op_index); break;
+            case OP_L2NORM: forward_l2norm(p, li, op_index); break;
+            }
+    }
+    forward_loss(p, y, fwd_guard);
+    if (nl == 2) {
+        HIP_OK(hipEventRecord(ev_join_, s2_));
+        HIP_OK(hipStreamWaitEvent(stream_, ev_join_, 0));
+    }
+    if (train_mode) HIP_OK(hipEventRecord(ev_loss_[loss_seq_ % LOSS_RING], stream_));
+    fwd_guard.done = true;
+}
+
+// Everything that reads the fp32 masters in front of the walk, on the side stream beside the first layers: the filters' Winograd
+// transforms, bf16 mirrors, quantised images and chain packing, and -- training -- the loss's l2 term; with the events the lanes wait for.
+void Net::forward_filters(FwdPass& p, LossSlotGuard& guard) {
+    const bool side = p.side;
     if (wino_plan_.n + wino_plan_first_.n > 0) {
         // Winograd layers (plan_winograd): the filters' transforms, fresh from the fp32 masters like the bf16 mirrors below, on the side
         // stream beside conv1_1: the first such layer's own (a launch of microseconds: what the lanes wait for), the other layers', and --
@@ -1013,12 +1159,12 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
         if (side) HIP_OK(hipEventRecord(ev_wino_first_, fs));
         wino_filter_plan(wino_plan_, true, false, fs);
         if (side) HIP_OK(hipEventRecord(ev_wino_, fs));
-        if (train_mode && wino_plan_flip_.n > 0) {
+        if (p.train_mode && wino_plan_flip_.n > 0) {
             wino_filter_plan(wino_plan_flip_, false, true, fs);
             if (side) HIP_OK(hipEventRecord(ev_wino_flip_, fs));
             wino_flip_pending_ = side;
         }
-        if (side) lane[0].wino_pending = lane[1].wino_pending = 2;
+        if (side) p.lane[0].wino_pending = p.lane[1].wino_pending = 2;
     }
     if (bf16_) {
         // the fp32 masters may have been updated by the optimizer, a variable load or the caller (external
@@ -1026,232 +1172,204 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
         // the fp32 master itself); the first layer that reads a mirror waits for it
         prof_.layer = "filters";
         cast_filters(cast_plan_, params_, wq_io_, wq_oi_, side ? hstream_ : stream_);
-        // ... and the e4m3 filter images with their per-channel scales, under the same rule (one more launch)
-        if (run8 && mx6_) quantize_filters_mxfp6(quant_plan_, params_, w8_, wsc6_, side ? hstream_ : stream_);
-        else if (run8) quantize_filters_fp8(quant_plan_, params_, w8_, sw8_, side ? hstream_ : stream_);
+        // ... and the quantised filter images with their scales, under the same rule (one more launch)
+        if (p.run8) quantize_filters_q(quant_, quant_plan_, params_, w8_, sw8_, wsc6_, side ? hstream_ : stream_);
         if (chain_first_ >= 0) pack_tail_filters(side ? hstream_ : stream_);
         if (side) {
             HIP_OK(hipEventRecord(ev_cast_, hstream_));
-            lane[0].cast_pending = lane[1].cast_pending = true;
+            p.lane[0].cast_pending = p.lane[1].cast_pending = true;
         }
     }
-    // A forward pass that fails after it has taken a slot of the loss ring gives the slot back: its event was never
-    // recorded, and a reader one step late (get_losses_step) would otherwise be handed a slot of four passes ago.
-    struct LossSlotGuard {
-        long long& seq;
-        bool armed = false;
-        bool done = false;
-        explicit LossSlotGuard(long long& s) : seq(s) {}
-        void failed() { if (armed && !done) { --seq; armed = false; } }
-        ~LossSlotGuard() { if (armed && !done) --seq; }
-    } fwd_guard(loss_seq_);
-    if (train_mode) {
+    if (p.train_mode) {
         begin_loss_slot();
-        fwd_guard.armed = true;
+        guard.armed = true;
         // the l2 term reads every filter once (105 MB): on the side stream beside the first (matrix-bound) layers
         prof_.layer = "loss";
         l2_partials(params_, nfilters_, lw_, side ? hstream_ : stream_);
-        if (nl == 2) HIP_OK(hipEventRecord(ev_l2_, hstream_));
+        if (p.nl == 2) HIP_OK(hipEventRecord(ev_l2_, hstream_));
     }
-    // Round 5: the lanes MERGE at conv8_1.  The extra layers behind it are a chain of sixteen dependent launches of a handful of
-    // workgroups each (conv8_1 ... conv11_2 on two lanes: 6-37 us per launch, every one of them latency- not work-bound): a
-    // timeline of the step (profiles/r05_j_timeline_bf16.txt) shows 285 us between mod_conv7 and the loss with a nearly empty chip.
-    // One lane runs the eight layers once, at twice the rows per launch and the same latency; the second lane's stream -- idle
-    // from here on -- takes every other small head, which used to queue behind each other on the one side stream.
-    // (Round 4 merged at the 19x19 maps, i.e. incl. conv5_x / mod_conv6, where two lanes fill each other's partial rounds: slower.)
-    int nl_cur = nl;
-    int small_heads = 0;
-    for (const int op_index : fwd_order_) {
-        const Op& op = ops_[op_index];
-        const Tensor& in = tensors_[op.in];
-        const Tensor& out = tensors_[op.out];
-        prof_.layer = op.name.c_str();
-        if (op_ablated(op.name, op.kind, op.head, op.k)) continue;
-        if (chain_fwd_ && in_chain_[op_index]) {      // Round 6 (plan_tail_chain): the chain's layers and heads run as ONE launch per lane, issued at its first op
-            if (op_index == chain_first_)
-                for (int li = 0; li < nl_cur; ++li) {
-                    Lane& ln = lane[li];
-                    if (ln.cast_pending) {
-                        HIP_OK(hipStreamWaitEvent(ln.s, ev_cast_, 0));
-                        ln.cast_pending = false;
-                    }
-                    launch_tail_forward(ln.b0, ln.nb, ln.s);
-                }
-            continue;
-        }
-        if (nl_cur == 2 && heads_full && op_index == tail_first_) {
-            HIP_OK(hipEventRecord(ev_join_, s2_));
-            HIP_OK(hipStreamWaitEvent(stream_, ev_join_, 0));
-            lane[0].nb = b;
-            nl_cur = 1;
-        }
-        for (int li = 0; li < nl_cur; ++li) {
-            Lane& ln = lane[li];
-            const int nb = ln.nb;
-            switch (op.kind) {
-            case OP_CONV: {
-                hipStream_t cs = ln.s;
-                int run_nb = nb, run_b0 = ln.b0;
-                if (op.head >= 0 && side) {
-                    // the multibox heads hang off the trunk: they run on a side stream behind their feature
-                    // map and fill the CUs the trunk's kernels leave idle between waves of workgroups
-                    if (!ln.fmap_carried[op.head]) HIP_OK(hipEventRecord(ln.ev_fmap[op.head], ln.s));
-                    ln.fmap_carried[op.head] = false;
-                    if (heads_full) {
-                        // ONE launch over the whole batch on lane 0's side stream, behind both lanes' feature maps: half the
-                        // launches, twice the workgroups each, and lane 1's trunk (whose own "side" stream is its main
-                        // stream) does not queue behind its heads
-                        if (li < nl_cur - 1) break;
-                        // (after the merge: the small maps' heads alternate between the side stream and the idle second lane's)
-                        cs = (nl_cur == 1 && op.head >= 2 && (small_heads++ & 1)) ? s2_ : hstream_;
-                        for (int l = 0; l < nl_cur; ++l) HIP_OK(hipStreamWaitEvent(cs, lane[l].ev_fmap[op.head], 0));
-                        run_nb = b; run_b0 = 0;
-                        lane[0].heads_on_side = true;
-                    } else {
-                        HIP_OK(hipStreamWaitEvent(ln.h, ln.ev_fmap[op.head], 0));
-                        cs = ln.h;
-                        ln.heads_on_side = true;
-                    }
-                }
-                const ConvDesc d = conv_desc(op, run_nb);
-                struct LanesScope {      // (tile choice of the bf16 kernel-row gather: the lanes share the chip's workgroup slots)
-                    LanesScope(int n) { g_conv_lanes = n; }
-                    ~LanesScope() { g_conv_lanes = 1; }
-                } lanes_scope(run_nb == nb ? nl_cur : 1);
-                if (ln.cast_pending && !in.data_f32) {
-                    HIP_OK(hipStreamWaitEvent(ln.s, ev_cast_, 0));
-                    ln.cast_pending = false;
-                }
-                const float* xin = reinterpret_cast<const float*>(at(in, run_b0));
-                void* yout = at(out, run_b0);
-                // Round 6: the Winograd form (plan_winograd).  A lane owns the tile rows of its images in the layer's full-batch
-                // transform V (which the weight gradient reads) and its own GEMM-result scratch.
-                // (GEMM-result scratch: one per stream that runs such layers -- the lanes' main streams and the side stream of the heads)
-                float* const wino_M = cs == ln.s ? wino_m_[li] : cs == hstream_ ? wino_m_[2] : nullptr;
-                const bool wino = op.wino_f && wino_M;
-                float* wino_V = nullptr;
-                void* wino_bits = nullptr;
-                size_t wino_vps = 0;
-                if (wino) {
-                    if (cs == ln.s && ln.wino_pending) {      // (the side stream ran the filter transforms itself)
-                        // (waiting for ALL transforms incl. the flipped ones before the first layer: 24.00 against 23.69 ms median,
-                        // profiles/r06_bc_ab_filter_split_f32.txt)
-                        HIP_OK(hipStreamWaitEvent(ln.s, ln.wino_pending == 2 ? ev_wino_first_ : ev_wino_, 0));
-                        --ln.wino_pending;
-                    }
-                    const size_t tpi = (size_t)wino_tiles(d) / d.B;
-                    if (op.wino_V) {      // a training handle: this launch's rows of the layer's full-batch transform
-                        wino_V = op.wino_V + (size_t)run_b0 * tpi * d.Ci;
-                        wino_vps = (size_t)b * tpi * d.Ci;
-                        if (train_mode) ops_[op_index].wino_v_step = fwd_serial_;
-                    } else {              // an inference handle: the stream's own scratch
-                        wino_V = wino_vs_[cs == ln.s ? li : 2];
-                        wino_vps = (size_t)run_nb * tpi * d.Ci;
-                    }
-                    // training: the input transform notes the relu mask of this layer's input for its own data gradient (conv.h)
-                    if (train_mode && op.wino_bits) {
-                        wino_bits = static_cast<char*>(op.wino_bits) + (size_t)run_b0 * tpi * (d.Ci / 4) * 8;
-                        ops_[op_index].wino_bits_step = fwd_serial_;
-                    }
-                }
-                if (op.pool_after >= 0) {
-                    // Pool fusion (round 5): this conv's epilogue takes the 2x2 maxima itself and writes the POOLED tensor (+ the
-                    // pool's 12-bit record in training); its own output has no other reader -- forward or backward -- and is
-                    // never written (plan_pool_fusion)
-                    const Op& pl = ops_[op.pool_after];
-                    const Tensor& pt = tensors_[pl.out];
-                    void* rec = (pl.pool_rec && train_mode)
-                                    ? static_cast<char*>(pl.pool_rec) + (size_t)run_b0 * pt.H * pt.W * (pt.C / 4) * sizeof(unsigned short) : nullptr;
-                    if (wino)
-                        wino_fwd(d, xin, op.wino_U, params_ + op.b_off, nullptr, true, wino_V, wino_vps, wino_M,
-                                 reinterpret_cast<float*>(at(pt, run_b0)), rec, cs, wino_bits);
-                    else if (!bf16_)
-                        conv_fwd_pool(d, xin, params_ + op.w_off, params_ + op.b_off, reinterpret_cast<float*>(at(pt, run_b0)), rec, cs);
-                    else
-                        conv_fwd_pool_bf16(d, reinterpret_cast<const bf16_t*>(xin), wq_oi_ + op.w_off, params_ + op.b_off,
-                                           reinterpret_cast<bf16_t*>(at(pt, run_b0)), rec, cs);
-                    if (run8 && pt.data8)      // the pooled tensor feeds an fp8 layer: the boundary's quantise pass
-                        quantize8(pt, at(pt, run_b0), run_b0, run_nb, cs);
-                    break;
-                }
-                // a feature map's producer carries the event its head waits for (common.h g_stop_event; backward_step does the same)
-                const int fh = (side && op.head < 0 && cs == ln.s) ? head_of(op.out) : -1;
-                if (fh >= 0) g_stop_event = ln.ev_fmap[fh];
-                struct CarryScope {
-                    bool* flag;
-                    ~CarryScope() { if (flag) *flag = g_stop_event == nullptr; g_stop_event = nullptr; }
-                } carry_scope{fh >= 0 ? &ln.fmap_carried[fh] : nullptr};
-                if (wino)
-                    wino_fwd(d, xin, op.wino_U, params_ + op.b_off, static_cast<float*>(yout), op.relu, wino_V, wino_vps, wino_M,
-                             nullptr, nullptr, cs, wino_bits);
-                else if (!bf16_)
-                    conv_fwd(d, xin, params_ + op.w_off, params_ + op.b_off, static_cast<float*>(yout), op.relu, cs);
-                else if (in.data_f32 && first_layer_kernel(d))      // conv1_1: fp32 image and master filter in, bf16 out
-                    conv_first_fwd_bf16(d, xin, params_ + op.w_off, params_ + op.b_off, static_cast<bf16_t*>(yout), op.relu, cs);
-                else if (in.data_f32)
-                    conv_fwd_smallc_bf16out(d, xin, params_ + op.w_off, params_ + op.b_off, static_cast<bf16_t*>(yout), op.relu, cs);
-                else if (run8 && op.fp8 && mx6_)     // e2m3 operands, block scales on both; the output in the form(s) its readers take
-                    conv_fwd_mxfp6(d, in.data8 + (size_t)run_b0 * (in.per_image() / 32 * 24), in.scale8 + (size_t)run_b0 * (in.per_image() / 32),
-                                   w8_ + op.w6_off, wsc6_ + op.sw_off, params_ + op.b_off, yout,
-                                   out.data8 ? out.data8 + (size_t)run_b0 * (out.per_image() / 32 * 24) : nullptr,
-                                   out.data8 ? out.scale8 + (size_t)run_b0 * (out.per_image() / 32) : nullptr,
-                                   out.data8 ? (out.wants16 ? FP8_OUT_BF16_MX : FP8_OUT_MX) : FP8_OUT_BF16, op.relu, cs);
-                else if (run8 && op.fp8 && mx_)      // e4m3 operands with block scales; the output in the form(s) its readers take
-                    (conv_bigk(d) ? conv_bigk_fwd_mxfp8 : conv_fwd_mxfp8)(      // (more than 9 taps: the fc graph's mod_conv6 under SSD_MXFP8_BIGK=1)
-                        d, in.data8 + (size_t)run_b0 * in.per_image(), in.scale8 + (size_t)run_b0 * (in.per_image() / 32), w8_ + op.w_off,
-                        sw8_ + op.sw_off, params_ + op.b_off, yout, out.data8 ? out.data8 + (size_t)run_b0 * out.per_image() : nullptr,
-                        out.data8 ? out.scale8 + (size_t)run_b0 * (out.per_image() / 32) : nullptr,
-                        out.data8 ? (out.wants16 ? FP8_OUT_BF16_MX : FP8_OUT_MX) : FP8_OUT_BF16, op.relu, cs);
-                else if (run8 && op.fp8)      // e4m3 operands; the output in the form(s) its readers take
-                    (conv_bigk(d) ? conv_bigk_fwd_fp8 : conv_fwd_fp8)(      // (more than 9 taps: the fc graph's mod_conv6)
-                        d, in.data8 + (size_t)run_b0 * in.per_image(), w8_ + op.w_off, in.scale, sw8_ + op.sw_off, params_ + op.b_off, yout,
-                        out.data8 ? out.data8 + (size_t)run_b0 * out.per_image() : nullptr,
-                        out.data8 ? (out.wants16 ? FP8_OUT_BF16_E4M3 : FP8_OUT_E4M3) : FP8_OUT_BF16, out.scale, op.relu, cs);
-                else
-                    conv_fwd_bf16(d, reinterpret_cast<const bf16_t*>(xin), wq_oi_ + op.w_off, params_ + op.b_off, yout, out.data_f32, op.relu, cs);
-                // a bf16 layer in front of an fp8 one: a boundary with a quantise pass of its own
-                if (run8 && out.data8 && !op.fp8) quantize8(out, yout, run_b0, run_nb, cs);
-                break;
-            }
-            case OP_POOL: {
-                if (op.fused_fwd) break;      // written by its producer's epilogue
-                PoolDesc d{nb, in.H, in.W, in.C, out.H, out.W, op.k, op.stride, op.pad_h, op.pad_w};
-                if (op.pool_rec && train_mode) {
-                    void* rec = static_cast<char*>(op.pool_rec) + (size_t)ln.b0 * out.H * out.W * (in.C / 4) * sizeof(unsigned short);
-                    if (bf16_) maxpool_fwd_rec(d, reinterpret_cast<const bf16_t*>(at(in, ln.b0)), reinterpret_cast<bf16_t*>(at(out, ln.b0)), rec, ln.s);
-                    else maxpool_fwd_rec(d, reinterpret_cast<const float*>(at(in, ln.b0)), reinterpret_cast<float*>(at(out, ln.b0)), rec, ln.s);
-                } else if (train_mode && pool_ws_ && maxpool_arg_applicable(d)) {
-                    // mod_pool5: the windows' first-maximum taps stay in pool_ws_ (this pool is its only user) for backward
-                    void* arg = static_cast<char*>(pool_ws_) + (size_t)ln.b0 * out.H * out.W * (in.C / 4) * sizeof(unsigned);
-                    if (bf16_) maxpool_fwd_arg(d, reinterpret_cast<const bf16_t*>(at(in, ln.b0)), reinterpret_cast<bf16_t*>(at(out, ln.b0)), arg, ln.s);
-                    else maxpool_fwd_arg(d, reinterpret_cast<const float*>(at(in, ln.b0)), reinterpret_cast<float*>(at(out, ln.b0)), arg, ln.s);
-                    pool_arg_op_ = op_index;
-                } else if (run8 && op.fp8) {      // on e4m3 bytes (the output shares the input's scale); bf16 as well where someone reads that
-                    if (mx6_)
-                        maxpool_fwd_mxfp6(d, in.data8 + (size_t)ln.b0 * (in.per_image() / 32 * 24), in.scale8 + (size_t)ln.b0 * (in.per_image() / 32),
-                                          out.data8 + (size_t)ln.b0 * (out.per_image() / 32 * 24), out.scale8 + (size_t)ln.b0 * (out.per_image() / 32), ln.s);
-                    else if (mx_)                 // (mxfp8: on the dequantised cells, with block scales of its own)
-                        maxpool_fwd_mxfp8(d, in.data8 + (size_t)ln.b0 * in.per_image(), in.scale8 + (size_t)ln.b0 * (in.per_image() / 32),
-                                          out.data8 + (size_t)ln.b0 * out.per_image(), out.scale8 + (size_t)ln.b0 * (out.per_image() / 32), ln.s);
-                    else
-                        maxpool_fwd_fp8(d, in.data8 + (size_t)ln.b0 * in.per_image(), out.data8 + (size_t)ln.b0 * out.per_image(), ln.s);
-                    if (out.wants16) maxpool_fwd(d, reinterpret_cast<const bf16_t*>(at(in, ln.b0)), reinterpret_cast<bf16_t*>(at(out, ln.b0)), ln.s);
-                } else if (bf16_) {
-                    maxpool_fwd(d, reinterpret_cast<const bf16_t*>(at(in, ln.b0)), reinterpret_cast<bf16_t*>(at(out, ln.b0)), ln.s);
-                    if (run8 && out.data8)      // a bf16 pool in front of an fp8 layer
-                        quantize8(out, at(out, ln.b0), ln.b0, nb, ln.s);
-                } else maxpool_fwd(d, reinterpret_cast<const float*>(at(in, ln.b0)), reinterpret_cast<float*>(at(out, ln.b0)), ln.s);
-                break;
-            }
-            case OP_L2NORM:
-                if (bf16_) l2norm_fwd(nb * in.H * in.W, in.C, reinterpret_cast<const bf16_t*>(at(in, ln.b0)), params_ + scale_off_,
-                                      reinterpret_cast<bf16_t*>(at(out, ln.b0)), ln.s);
-                else l2norm_fwd(nb * in.H * in.W, in.C, reinterpret_cast<const float*>(at(in, ln.b0)), params_ + scale_off_,
-                                reinterpret_cast<float*>(at(out, ln.b0)), ln.s);
-                break;
-            }
-        }
+}
+
+// Step 1 of a forward convolution: its stream, batch range and the events in front of it.  A trunk layer runs on its lane's stream.  A
+// multibox head hangs off the trunk: false = this lane issues nothing (a full-batch head belongs to the last lane).
+bool Net::conv_stream(FwdPass& p, int li, const Op& op, ConvRun& r) {
+    Lane& ln = p.lane[li];
+    if (!(op.head >= 0 && p.side)) return true;
+    // the multibox heads hang off the trunk: they run on a side stream behind their feature
+    // map and fill the CUs the trunk's kernels leave idle between waves of workgroups
+    if (!ln.fmap_carried[op.head]) HIP_OK(hipEventRecord(ln.ev_fmap[op.head], ln.s));
+    ln.fmap_carried[op.head] = false;
+    if (p.heads_full) {
+        // ONE launch over the whole batch on lane 0's side stream, behind both lanes' feature maps: half the
+        // launches, twice the workgroups each, and lane 1's trunk (whose own "side" stream is its main
+        // stream) does not queue behind its heads
+        if (li < p.nl_cur - 1) return false;
+        // (after the merge: the small maps' heads alternate between the side stream and the idle second lane's)
+        r.cs = (p.nl_cur == 1 && op.head >= 2 && (p.small_heads++ & 1)) ? s2_ : hstream_;
+        for (int l = 0; l < p.nl_cur; ++l) HIP_OK(hipStreamWaitEvent(r.cs, p.lane[l].ev_fmap[op.head], 0));
+        r.nb = p.b; r.b0 = 0;
+        p.lane[0].heads_on_side = true;
+    } else {
+        HIP_OK(hipStreamWaitEvent(ln.h, ln.ev_fmap[op.head], 0));
+        r.cs = ln.h;
+        ln.heads_on_side = true;
     }
+    return true;
+}
+
+// Step 2: Round 6: the Winograd form (plan_winograd).  A lane owns the tile rows of its images in the layer's full-batch
+// transform V (which the weight gradient reads) and its own GEMM-result scratch.
+void Net::conv_wino_scratch(const FwdPass& p, int li, int op_index, const ConvDesc& d, ConvRun& r) {
+    Op& op = ops_[op_index];
+    const bool own = r.cs == p.lane[li].s;
+    const size_t tpi = (size_t)wino_tiles(d) / d.B;
+    if (op.wino_V) {      // a training handle: this launch's rows of the layer's full-batch transform
+        r.wino_V = op.wino_V + (size_t)r.b0 * tpi * d.Ci;
+        r.wino_vps = (size_t)p.b * tpi * d.Ci;
+        if (p.train_mode) op.wino_v_step = fwd_serial_;
+    } else {              // an inference handle: the stream's own scratch
+        r.wino_V = wino_vs_[own ? li : 2];
+        r.wino_vps = (size_t)r.nb * tpi * d.Ci;
+    }
+    // training: the input transform notes the relu mask of this layer's input for its own data gradient (conv.h)
+    if (p.train_mode && op.wino_bits) {
+        r.wino_bits = static_cast<char*>(op.wino_bits) + (size_t)r.b0 * tpi * (d.Ci / 4) * 8;
+        op.wino_bits_step = fwd_serial_;
+    }
+}
+
+// Step 3: the kernel, by the handle's compute type and the layer's place in the graph.
+void Net::launch_conv_fwd(const FwdPass& p, const Op& op, const ConvDesc& d, const ConvRun& r) {
+    const Tensor& in = tensors_[op.in];
+    const Tensor& out = tensors_[op.out];
+    hipStream_t cs = r.cs;
+    const float* xin = reinterpret_cast<const float*>(at(in, r.b0));
+    void* yout = at(out, r.b0);
+    if (op.pool_after >= 0) {
+        // Pool fusion (round 5): this conv's epilogue takes the 2x2 maxima itself and writes the POOLED tensor (+ the
+        // pool's 12-bit record in training); its own output has no other reader -- forward or backward -- and is
+        // never written (plan_pool_fusion)
+        const Op& pl = ops_[op.pool_after];
+        const Tensor& pt = tensors_[pl.out];
+        void* rec = (pl.pool_rec && p.train_mode)
+                        ? static_cast<char*>(pl.pool_rec) + (size_t)r.b0 * pt.H * pt.W * (pt.C / 4) * sizeof(unsigned short) : nullptr;
+        if (r.wino_M)
+            wino_fwd(d, xin, op.wino_U, params_ + op.b_off, nullptr, true, r.wino_V, r.wino_vps, r.wino_M,
+                     reinterpret_cast<float*>(at(pt, r.b0)), rec, cs, r.wino_bits);
+        else if (!bf16_)
+            conv_fwd_pool(d, xin, params_ + op.w_off, params_ + op.b_off, reinterpret_cast<float*>(at(pt, r.b0)), rec, cs);
+        else
+            conv_fwd_pool_bf16(d, reinterpret_cast<const bf16_t*>(xin), wq_oi_ + op.w_off, params_ + op.b_off,
+                               reinterpret_cast<bf16_t*>(at(pt, r.b0)), rec, cs);
+        if (p.run8 && pt.data8)      // the pooled tensor feeds a quantised layer: the boundary's quantise pass
+            quantize_q(quant_, pt, at(pt, r.b0), r.nb, q_at(pt, r.b0), cs);
+        return;
+    }
+    if (r.wino_M)
+        wino_fwd(d, xin, op.wino_U, params_ + op.b_off, static_cast<float*>(yout), op.relu, r.wino_V, r.wino_vps, r.wino_M,
+                 nullptr, nullptr, cs, r.wino_bits);
+    else if (!bf16_)
+        conv_fwd(d, xin, params_ + op.w_off, params_ + op.b_off, static_cast<float*>(yout), op.relu, cs);
+    else if (in.data_f32 && first_layer_kernel(d))      // conv1_1: fp32 image and master filter in, bf16 out
+        conv_first_fwd_bf16(d, xin, params_ + op.w_off, params_ + op.b_off, static_cast<bf16_t*>(yout), op.relu, cs);
+    else if (in.data_f32)
+        conv_fwd_smallc_bf16out(d, xin, params_ + op.w_off, params_ + op.b_off, static_cast<bf16_t*>(yout), op.relu, cs);
+    else if (p.run8 && op.fp8)
+        conv_fwd_q(quant_, d, q_at(in, r.b0), w8_ + op.w8_off, sw8_ ? sw8_ + op.sw_off : nullptr, wsc6_ ? wsc6_ + op.sw_off : nullptr,
+                   params_ + op.b_off, yout, q_at(out, r.b0), out.wants16, op.relu, cs);
+    else
+        conv_fwd_bf16(d, reinterpret_cast<const bf16_t*>(xin), wq_oi_ + op.w_off, params_ + op.b_off, yout, out.data_f32, op.relu, cs);
+    // a bf16 layer in front of a quantised one: a boundary with a quantise pass of its own
+    if (p.run8 && out.data8 && !op.fp8) quantize_q(quant_, out, yout, r.nb, q_at(out, r.b0), cs);
+}
+
+// One convolution on one lane.
+void Net::forward_conv(FwdPass& p, int li, int op_index) {
+    const Op& op = ops_[op_index];
+    const Tensor& in = tensors_[op.in];
+    Lane& ln = p.lane[li];
+    // ---- 1. stream and events
+    ConvRun r{ln.s, ln.b0, ln.nb};
+    if (!conv_stream(p, li, op, r)) return;
+    const ConvDesc d = conv_desc(op, r.nb);
+    struct LanesScope {      // (tile choice of the bf16 kernel-row gather: the lanes share the chip's workgroup slots)
+        LanesScope(int n) { g_conv_lanes = n; }
+        ~LanesScope() { g_conv_lanes = 1; }
+    } lanes_scope(r.nb == ln.nb ? p.nl_cur : 1);
+    if (ln.cast_pending && !in.data_f32) {
+        HIP_OK(hipStreamWaitEvent(ln.s, ev_cast_, 0));
+        ln.cast_pending = false;
+    }
+    // (GEMM-result scratch: one per stream that runs such layers -- the lanes' main streams and the side stream of the heads)
+    r.wino_M = !op.wino_f ? nullptr : r.cs == ln.s ? wino_m_[li] : r.cs == hstream_ ? wino_m_[2] : nullptr;
+    if (r.wino_M && r.cs == ln.s && ln.wino_pending) {      // (the side stream ran the filter transforms itself)
+        // (waiting for ALL transforms incl. the flipped ones before the first layer: 24.00 against 23.69 ms median,
+        // profiles/r06_bc_ab_filter_split_f32.txt)
+        HIP_OK(hipStreamWaitEvent(ln.s, ln.wino_pending == 2 ? ev_wino_first_ : ev_wino_, 0));
+        --ln.wino_pending;
+    }
+    // ---- 2. Winograd scratch
+    if (r.wino_M) conv_wino_scratch(p, li, op_index, d, r);
+    // ---- 3. the kernel
+    if (op.pool_after >= 0) {
+        launch_conv_fwd(p, op, d, r);
+        return;
+    }
+    // a feature map's producer carries the event its head waits for (common.h g_stop_event; backward_step does the same)
+    int fh = -1;      // the head that reads this op's output
+    if (p.side && op.head < 0 && r.cs == ln.s)
+        for (const Op& o : ops_)
+            if (o.kind == OP_CONV && o.head >= 0 && o.in == op.out) { fh = o.head; break; }
+    if (fh >= 0) g_stop_event = ln.ev_fmap[fh];
+    struct CarryScope {
+        bool* flag;
+        ~CarryScope() { if (flag) *flag = g_stop_event == nullptr; g_stop_event = nullptr; }
+    } carry_scope{fh >= 0 ? &ln.fmap_carried[fh] : nullptr};
+    launch_conv_fwd(p, op, d, r);
+}
+
+void Net::forward_pool(FwdPass& p, int li, int op_index) {
+    const Op& op = ops_[op_index];
+    const Tensor& in = tensors_[op.in];
+    const Tensor& out = tensors_[op.out];
+    const Lane& ln = p.lane[li];
+    if (op.fused_fwd) return;      // written by its producer's epilogue
+    PoolDesc d{ln.nb, in.H, in.W, in.C, out.H, out.W, op.k, op.stride, op.pad_h, op.pad_w};
+    if (op.pool_rec && p.train_mode) {
+        void* rec = static_cast<char*>(op.pool_rec) + (size_t)ln.b0 * out.H * out.W * (in.C / 4) * sizeof(unsigned short);
+        if (bf16_) maxpool_fwd_rec(d, reinterpret_cast<const bf16_t*>(at(in, ln.b0)), reinterpret_cast<bf16_t*>(at(out, ln.b0)), rec, ln.s);
+        else maxpool_fwd_rec(d, reinterpret_cast<const float*>(at(in, ln.b0)), reinterpret_cast<float*>(at(out, ln.b0)), rec, ln.s);
+    } else if (p.train_mode && pool_ws_ && maxpool_arg_applicable(d)) {
+        // mod_pool5: the windows' first-maximum taps stay in pool_ws_ (this pool is its only user) for backward
+        void* arg = static_cast<char*>(pool_ws_) + (size_t)ln.b0 * out.H * out.W * (in.C / 4) * sizeof(unsigned);
+        if (bf16_) maxpool_fwd_arg(d, reinterpret_cast<const bf16_t*>(at(in, ln.b0)), reinterpret_cast<bf16_t*>(at(out, ln.b0)), arg, ln.s);
+        else maxpool_fwd_arg(d, reinterpret_cast<const float*>(at(in, ln.b0)), reinterpret_cast<float*>(at(out, ln.b0)), arg, ln.s);
+        pool_arg_op_ = op_index;
+    } else if (p.run8 && op.fp8) {      // on the codes; bf16 as well where someone reads that
+        maxpool_fwd_q(quant_, d, q_at(in, ln.b0), q_at(out, ln.b0), ln.s);
+        if (out.wants16) maxpool_fwd(d, reinterpret_cast<const bf16_t*>(at(in, ln.b0)), reinterpret_cast<bf16_t*>(at(out, ln.b0)), ln.s);
+    } else if (bf16_) {
+        maxpool_fwd(d, reinterpret_cast<const bf16_t*>(at(in, ln.b0)), reinterpret_cast<bf16_t*>(at(out, ln.b0)), ln.s);
+        if (p.run8 && out.data8)      // a bf16 pool in front of a quantised layer
+            quantize_q(quant_, out, at(out, ln.b0), ln.nb, q_at(out, ln.b0), ln.s);
+    } else maxpool_fwd(d, reinterpret_cast<const float*>(at(in, ln.b0)), reinterpret_cast<float*>(at(out, ln.b0)), ln.s);
+}
+
+void Net::forward_l2norm(FwdPass& p, int li, int op_index) {
+    const Op& op = ops_[op_index];
+    const Tensor& in = tensors_[op.in];
+    const Tensor& out = tensors_[op.out];
+    const Lane& ln = p.lane[li];
+    if (bf16_) l2norm_fwd(ln.nb * in.H * in.W, in.C, reinterpret_cast<const bf16_t*>(at(in, ln.b0)), params_ + scale_off_,
+                          reinterpret_cast<bf16_t*>(at(out, ln.b0)), ln.s);
+    else l2norm_fwd(ln.nb * in.H * in.W, in.C, reinterpret_cast<const float*>(at(in, ln.b0)), params_ + scale_off_,
+                    reinterpret_cast<float*>(at(out, ln.b0)), ln.s);
+}
+
+// The loss (training) or result pass behind the heads: one full-batch launch, or one per lane.
+void Net::forward_loss(FwdPass& p, const float* y, LossSlotGuard& guard) {
+    const int b = p.b;
+    const bool train_mode = p.train_mode;
     prof_.layer = "loss";
     const int A = preset_->num_anchors, nv = C_ + 5;
     if (train_mode) { bw_loss_kind_ = loss_kind_; bw_gamma_ = focal_gamma_; bw_alpha_ = focal_alpha_; bw_loc_ = loc_; }      // the step's loss: backward follows it
@@ -1260,7 +1378,7 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
     // lane's has been enqueued, the count never reaches the step's total and the ticket would stay non-zero for the life
     // of the handle -- drain the device and clear it before the error leaves.
     try {
-    if (heads_full) {      // full-batch heads: one loss / result launch on the main stream behind the side stream and lane 1
+    if (p.heads_full) {      // full-batch heads: one loss / result launch on the main stream behind the side stream and lane 1
         HIP_OK(hipEventRecord(ev_h_, hstream_));
         HIP_OK(hipStreamWaitEvent(stream_, ev_h_, 0));
         HIP_OK(hipEventRecord(ev_join_, s2_));
@@ -1269,8 +1387,8 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
         else if (train_mode) multibox_loss(heads_, b, 0, b, result_, y, lw_, wd_, loss_bnorm_, stream_, bw_loc_);
         else heads_result(heads_, b, result_, stream_);
     }
-    for (int li = 0; li < nl && !heads_full; ++li) {
-        Lane& ln = lane[li];
+    for (int li = 0; li < p.nl && !p.heads_full; ++li) {
+        Lane& ln = p.lane[li];
         if (ln.heads_on_side) {
             HIP_OK(hipEventRecord(ln.ev_h, ln.h));
             HIP_OK(hipStreamWaitEvent(ln.s, ln.ev_h, 0));
@@ -1291,15 +1409,9 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
             (void)hipDeviceSynchronize();
             (void)hipMemset(lw_.ticket, 0, sizeof(unsigned));
         }
-        fwd_guard.failed();
+        guard.failed();
         throw;
     }
-    if (nl == 2) {
-        HIP_OK(hipEventRecord(ev_join_, s2_));
-        HIP_OK(hipStreamWaitEvent(stream_, ev_join_, 0));
-    }
-    if (train_mode) HIP_OK(hipEventRecord(ev_loss_[loss_seq_ % LOSS_RING], stream_));
-    fwd_guard.done = true;
 }
 
 // Backward runs the op list in reverse.  It can be driven in stages so a data-parallel caller can
@@ -1335,6 +1447,25 @@ void Net::launch_wgrad(int op_index, int b, hipStream_t ws) {
     }
 }
 
+// The data gradient of one convolution: into its input's gradient, or -- un-pooling (up) -- through the pool's record into the pool's
+// input gradient (dst); mask: with the relu mask of the input's producer.
+void Net::launch_dgrad(const Op& op, const ConvDesc& d, const Op* up, Tensor& dst, bool mask, int cls, hipStream_t ds) {
+    const Tensor& in = tensors_[op.in];
+    const Tensor& out = tensors_[op.out];
+    if (op.wino_d && cls == 0) {      // Round 6: the Winograd form (its scratch belongs to the main stream)
+        wino_bwd_transform(d, out.gf(), wino_yt_, nullptr, ds);
+        wino_dgrad(d, wino_yt_, op.wino_Uf, up ? dst.gf() : in.gf(), mask ? in.f() : nullptr, !up && in.done > 0, wino_xw_,
+                   up ? up->pool_rec : nullptr, dst.H, dst.W, ds,
+                   op.wino_bits && op.wino_bits_step == fwd_serial_ ? op.wino_bits : nullptr);      // (the forward of THIS step wrote them)
+    } else if (!bf16_) {
+        if (up) conv_dgrad_unpool(d, out.gf(), params_ + op.w_off, dst.gf(), up->pool_rec, dst.H, dst.W, ds);
+        else conv_dgrad(d, out.gf(), params_ + op.w_off, in.gf(), mask ? in.f() : nullptr, in.done > 0, ds);
+    } else {
+        if (up) conv_dgrad_unpool_bf16(d, out.gh(), wq_io_ + op.w_off, dst.gh(), up->pool_rec, dst.H, dst.W, ds);
+        else conv_dgrad_bf16(d, out.gh(), wq_io_ + op.w_off, in.gh(), mask ? in.h() : nullptr, in.done > 0, ds);
+    }
+}
+
 void Net::backward_begin(int b, const float* y) {
     SSD_REQUIRE(training_, "handle was created with training = 0");
     g_prof = &prof_;
@@ -1351,23 +1482,16 @@ void Net::backward_begin(int b, const float* y) {
     else multibox_loss_grad(heads_, b, 0, result_, y, lw_, stream_, bw_loc_);
     for (int t : head_t_) bw_wrote(0, tensors_[t]);      // the loss gradient, on the main stream
     if (side) bw_sync(1, 0);      // the side stream starts behind it (the small maps' head data gradients: backward_step)
-    bw_conv_done_.assign(ops_.size(), 0);
+    bw_.begin(this);
     bw_first_on_main_ = false;
     bw_first_fused_ = false;
-    bw_chain_done_ = false;
-    bw_pos_ = 0;
     bw_b_ = b;
-    bw_done_off_ = nfilters_;
 }
 
 bool Net::backward_step(size_t min_floats, size_t* off, size_t* count, bool sync_main) {
     const int b = bw_b_;
-    const size_t hi = bw_done_off_;
-    size_t lo = hi;
     bool side_used = false;
-    const int n_order = (int)bwd_order_.size();
-    while (bw_pos_ < n_order && hi - lo < min_floats) {
-        const int op_index = bwd_order_[bw_pos_++];
+    for (int op_index; (op_index = bw_.next(min_floats)) >= 0;) {
         const Op& op = ops_[op_index];
         Tensor& in = tensors_[op.in];
         const Tensor& out = tensors_[op.out];
@@ -1383,16 +1507,14 @@ bool Net::backward_step(size_t min_floats, size_t* off, size_t* count, bool sync
             // Round 6 (plan_tail_chain): the first chain op met issues the chain's data gradients (one launch) and every chain layer's
             // weight gradient (one grouped launch); the other members are skipped when their turn comes -- all but the chain's first
             // layer, whose data and weight gradients are ordinary launches below (launch_tail_backward leaves it out of the group)
-            if (!bw_chain_done_) {
-                launch_tail_backward(b, &side_used);
-                bw_chain_done_ = true;
-                lo = bw_final_lo();
+            if (!bw_.chain_done) {
+                launch_tail_backward(b, &side_used);      // (retires them)
                 prof_.layer = op.name.c_str();
             }
             if (op_index != chain_first_) continue;
         }
         if (op_ablated(op.name, op.kind, op.head, op.k)) {
-            if (op.kind == OP_CONV) { bw_conv_done_[op_index] = 1; lo = bw_final_lo(); }
+            bw_.retire(op_index);
             in.done++;
             continue;
         }
@@ -1451,29 +1573,16 @@ bool Net::backward_step(size_t min_floats, size_t* off, size_t* count, bool sync
                     bw_first_fused_ = true;
                     fused_first_out_ = op.in;
                     bw_wrote(cls, in);
-                    bw_conv_done_[op_index] = 1;
-                    lo = bw_final_lo();
+                    bw_.retire(op_index);
                     break;
                 }
                 g_stop_event = dst.gev;      // the launch carries dst's event (taken by the gather launchers)
                 struct Disarm { ~Disarm() { g_stop_event = nullptr; } } disarm;      // (also when the launch throws)
-                if (op.wino_d && cls == 0) {      // Round 6: the Winograd form (its scratch belongs to the main stream)
-                    wino_bwd_transform(d, out.gf(), wino_yt_, nullptr, ds);
-                    wino_dgrad(d, wino_yt_, op.wino_Uf, up ? dst.gf() : in.gf(), mask ? in.f() : nullptr, !up && in.done > 0, wino_xw_,
-                               up ? up->pool_rec : nullptr, dst.H, dst.W, ds,
-                               op.wino_bits && op.wino_bits_step == fwd_serial_ ? op.wino_bits : nullptr);      // (the forward of THIS step wrote them)
-                } else if (!bf16_) {
-                    if (up) conv_dgrad_unpool(d, out.gf(), params_ + op.w_off, dst.gf(), up->pool_rec, dst.H, dst.W, ds);
-                    else conv_dgrad(d, out.gf(), params_ + op.w_off, in.gf(), mask ? in.f() : nullptr, in.done > 0, ds);
-                } else {
-                    if (up) conv_dgrad_unpool_bf16(d, out.gh(), wq_io_ + op.w_off, dst.gh(), up->pool_rec, dst.H, dst.W, ds);
-                    else conv_dgrad_bf16(d, out.gh(), wq_io_ + op.w_off, in.gh(), mask ? in.h() : nullptr, in.done > 0, ds);
-                }
+                launch_dgrad(op, d, up, dst, mask, cls, ds);
                 const bool carried = dst.gev && g_stop_event == nullptr;
                 bw_wrote(cls, dst, carried);
             }
-            bw_conv_done_[op_index] = 1;
-            lo = bw_final_lo();
+            bw_.retire(op_index);
             break;
         }
         case OP_POOL: {
@@ -1508,7 +1617,7 @@ bool Net::backward_step(size_t min_floats, size_t* off, size_t* count, bool sync
         }
         in.done++;
     }
-    const bool finished = bw_pos_ >= n_order;
+    const bool finished = bw_.finished();
     if (finished && bw_issued_[1] > bw_seen_[0][1]) bw_sync(0, 1);      // (every side-stream result has a main-stream reader: a no-op)
     // The returned range is final in the weight-gradient stream's order.  Make it final in
     // main-stream order too unless the caller consumes it on the weight-gradient stream itself
@@ -1525,46 +1634,20 @@ bool Net::backward_step(size_t min_floats, size_t* off, size_t* count, bool sync
         HIP_OK(hipEventRecord(ev_dy_, stream_));
         HIP_OK(hipStreamWaitEvent(wstream_, ev_dy_, 0));
     }
-    bw_done_off_ = lo;
-    *off = lo;
-    *count = hi - lo;
+    const std::pair<size_t, size_t> range = bw_.end_stage();
+    *off = range.first;
+    *count = range.second;
     return !finished;
 }
 
 std::vector<std::pair<size_t, size_t>> Net::backward_ranges(size_t min_floats) const {
     std::vector<std::pair<size_t, size_t>> out;
-    std::vector<char> done(ops_.size(), 0);
-    auto final_lo = [&] {
-        size_t lo = nfilters_;
-        for (int i = (int)ops_.size() - 1; i >= 0; --i) {
-            if (ops_[i].kind != OP_CONV) continue;
-            if (!done[i]) break;
-            lo = ops_[i].w_off;
-        }
-        return lo;
-    };
-    size_t hi = nfilters_, pos = 0;
-    bool chain_seen = false;
-    while (pos < bwd_order_.size()) {
-        size_t lo = hi;
-        while (pos < bwd_order_.size() && hi - lo < min_floats) {      // exactly backward_step's loop
-            const int i = bwd_order_[pos++];
-            if (ops_[i].kind != OP_CONV) continue;
-            if (chain_bwd_ && in_chain_[i]) {      // the chain's layers finish together, when its first member is met (backward_step)
-                if (chain_seen && i != chain_first_) continue;
-                if (!chain_seen) {
-                    for (size_t j = 0; j < ops_.size(); ++j)
-                        if (in_chain_[j] && (int)j != chain_first_) done[j] = 1;
-                    chain_seen = true;
-                    lo = final_lo();
-                    if (i != chain_first_) continue;
-                }
-            }
-            done[i] = 1;
-            lo = final_lo();
-        }
-        if (hi > lo) out.emplace_back(lo, hi - lo);
-        hi = lo;
+    BwProgress p;
+    p.begin(this);
+    while (!p.finished()) {
+        for (int i; (i = p.next(min_floats)) >= 0;) p.retire(i);
+        const std::pair<size_t, size_t> range = p.end_stage();
+        if (range.second > 0) out.push_back(range);
     }
     return out;
 }
@@ -1733,7 +1816,8 @@ void Net::activation(const char* name, int b, float* out, size_t count) {
         }
         if (want_scale) {
             SSD_REQUIRE(t.scale8 != nullptr, "activation %s has no block scales (not an MX tensor of an mxfp8 handle)", name);
-            SSD_REQUIRE(count == t.per_image() / 32 * b, "scale:%s holds %zu floats for b=%d, got %zu", name, t.per_image() / 32 * b, b, count);
+            const size_t want = quant_scale_bytes(quant_, t.per_image()) * b;
+            SSD_REQUIRE(count == want, "scale:%s holds %zu floats for b=%d, got %zu", name, want, b, count);
             HIP_OK(hipStreamSynchronize(stream_));
             std::vector<unsigned char> hs(count);
             HIP_OK(hipMemcpy(hs.data(), t.scale8, count, hipMemcpyDeviceToHost));
@@ -1744,35 +1828,14 @@ void Net::activation(const char* name, int b, float* out, size_t count) {
                     count);
         const void* src = want_grad ? t.grad : t.data;
         HIP_OK(hipStreamSynchronize(stream_));
-        if (t.data8 && !want_grad && !want_bf16 && mx6_) {      // an mxfp6 tensor: its codes (24 bytes per block) times their blocks' 2^x
-            std::vector<unsigned char> hc(count / 32 * 24), hs(count / 32);
+        if (t.data8 && !want_grad && !want_bf16) {      // a quantised tensor: its dequantised codes
+            std::vector<unsigned char> hc(quant_code_bytes(quant_, count)), hs(quant_scale_bytes(quant_, count));
             HIP_OK(hipMemcpy(hc.data(), t.data8, hc.size(), hipMemcpyDeviceToHost));
-            HIP_OK(hipMemcpy(hs.data(), t.scale8, hs.size(), hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < count; ++i) {
-                const unsigned char* blk = hc.data() + i / 32 * 24;
-                const int bit = 6 * (int)(i % 32);
-                const int c = ((blk[bit >> 3] | (bit + 6 > ((bit >> 3) + 1) * 8 ? blk[(bit >> 3) + 1] << 8 : 0)) >> (bit & 7)) & 63;
-                const int e = (c >> 3) & 3, m = c & 7;
-                const float v = e == 0 ? m / 8.f : ldexpf(1.f + m / 8.f, e - 1);
-                out[i] = ldexpf(c & 32 ? -v : v, (int)hs[i / 32] - 127);
-            }
+            if (!hs.empty()) HIP_OK(hipMemcpy(hs.data(), t.scale8, hs.size(), hipMemcpyDeviceToHost));
+            dequantize_host(quant_, hc.data(), hs.empty() ? nullptr : hs.data(), t.scale, count, out);
             return;
         }
-        if (t.data8 && !want_grad && !want_bf16) {      // an fp8 tensor: its codes times its scale (exact in fp32)
-            std::vector<unsigned char> hc(count), hs;
-            HIP_OK(hipMemcpy(hc.data(), t.data8, count, hipMemcpyDeviceToHost));
-            if (t.scale8) {      // an MX tensor: its codes times their blocks' 2^x
-                hs.resize(count / 32);
-                HIP_OK(hipMemcpy(hs.data(), t.scale8, count / 32, hipMemcpyDeviceToHost));
-            }
-            for (size_t i = 0; i < count; ++i) {
-                const int c = hc[i], e = (c >> 3) & 15, m = c & 7;
-                const float v = (e == 15 && m == 7) ? NAN : e == 0 ? ldexpf((float)m, -9) : ldexpf(1.f + m / 8.f, e - 7);
-                out[i] = t.scale8 ? ldexpf(c & 0x80 ? -v : v, (int)hs[i / 32] - 127) : (c & 0x80 ? -v : v) * t.scale;
-            }
-            return;
-        }
-        SSD_REQUIRE(!(fp8_ && !want_grad && !t.wants16), "activation %s of the fp8 handle has no bf16 form", name);
+        SSD_REQUIRE(!(quant_ != Quant::none && !want_grad && !t.wants16), "activation %s of the fp8 handle has no bf16 form", name);
         if (want_grad ? t.grad_f32 : t.data_f32) {
             HIP_OK(hipMemcpy(out, src, count * sizeof(float), hipMemcpyDeviceToHost));
         } else {        // bf16 storage: widen on the host (exact)

@@ -98,6 +98,13 @@ def test_loss_normalizer_and_null_gradients(nccl_group):
     net.forward_dev(xt, yt)
     assert staged == list(net.backward_staged(yt, b, 4_000_000)) and len(staged) >= 4
     assert staged[0][0] + staged[0][1] == nf and staged[-1][0] == 0 and all(a[0] == c[0] + c[1] for a, c in zip(staged, staged[1:]))
+    # ... at every bucket size: one range per layer (1; 0 counts as 1), one range for everything (all the filters).  (m = 0 needs
+    # the shared walker, Net::BwProgress: before it, a stage that asked for nothing ran no op and both loops never ended)
+    for m in (0, 1, nf):
+        staged = list(net.backward_ranges(m))
+        net.forward_dev(xt, yt)
+        assert staged == list(net.backward_staged(yt, b, m)) and (len(staged) == 1 if m == nf else len(staged) > 20), (m, len(staged))
+        assert staged[0][0] + staged[0][1] == nf and staged[-1][0] == 0 and all(a[0] == c[0] + c[1] for a, c in zip(staged, staged[1:]))
     for bucket in (0, 4_000_000):
         p0 = net.params_flat.clone(); m0 = net.momentum_flat.clone(); step0 = net.global_step
         parallel.train_step_dp(net, None, None, 1, bucket_floats=bucket, force_collectives=True, global_count=0)
