@@ -213,7 +213,9 @@ void conv_wgrad_group_bf16(const WgradGroupItem* items, int n, float weight_deca
 
 // ---- fp8 inference kernels (conv_fp8.hip): OCP e4m3fn codes, one fp32 scale per activation tensor and per output channel ----
 // (The four e4m3 convolutions below -- fp8 and mxfp8, up to 9 taps and 10 ... 121 -- are one kernel, one shape check and one host path:
-// conv_fp8_detail.h.  The entry points differ in the format, the tap range they accept and the workgroup order.)
+// conv_fp8_detail.h.  The entry points differ in the format, the tap range they accept and the workgroup order.  The same header
+// holds what the mxfp6 convolution shares with them -- the shape check (conv_quant_refusal), the host prologue, the launcher -- and the table of the two filter quantisers; mx_block.h holds the two MX code formats as traits and, once
+// over them, the scale rule, the stand-alone quantiser, max-pooling and the pools' geometry check.  DESIGN.md 33.)
 // code = RNE(clamp(v / s, -448, 448)); y = relu?(acc * (s_in * s_w[co]) + bias[co]) in fp32, then one of the output forms.
 enum { FP8_OUT_BF16 = 0, FP8_OUT_F32 = 1, FP8_OUT_E4M3 = 2, FP8_OUT_BF16_E4M3 = 3 };
 // KH * KW <= 9, Ci a multiple of 64, Co a multiple of 8, any stride / dilation / leading padding, no empty tensor, every tensor and the
@@ -266,12 +268,13 @@ bool conv_bigk_fwd_mxfp8_supported(const ConvDesc& d, int out_mode, const char**
 bool conv_bigk_fwd_mxfp8_worthwhile(const ConvDesc& d);
 void conv_bigk_fwd_mxfp8(const ConvDesc& d, const unsigned char* x8, const unsigned char* xs, const unsigned char* w8, const float* s_w,
                          const float* bias, void* y, unsigned char* y8, unsigned char* ys, int out_mode, bool relu, hipStream_t s);
-// bf16 or fp32 [rows][C] -> codes [rows][C] + scales [rows][C / 32]; C a multiple of 32
+// bf16 or fp32 [rows][C] -> codes [rows][C] + scales [rows][C / 32]; C a multiple of 32 (mx_block.h: quantize_mx<MxE4M3>)
 void quantize_mxfp8(const void* x, bool x_f32, size_t rows, int C, unsigned char* y8, unsigned char* ys, hipStream_t s);
 // max-pooling of MX tensors: the maximum of the dequantised cells per channel, quantised again per block; C a multiple of 32
+// (mx_block.h: maxpool_fwd_mx<MxE4M3>)
 void maxpool_fwd_mxfp8(const PoolDesc& d, const unsigned char* x8, const unsigned char* xs, unsigned char* y8, unsigned char* ys, hipStream_t s);
 
-// ---- mxfp6 inference kernels (conv_mxfp6.hip): OCP MX FP6 E2M3 codes, 32 consecutive channels = one 24-byte string (code j
+// ---- mxfp6 inference kernels (conv_mxfp6.hip; the format: mx_block.h's MxE2M3): OCP MX FP6 E2M3 codes, 32 consecutive channels = one 24-byte string (code j
 // in bits 6 j ... 6 j + 5, little-endian) + one E8M0 scale byte: activations [B,H,W,C/32][24] + [B,H,W,C/32], filters with blocks along
 // Ci, w6 [tap][Co][Ci/32][24] + ws [tap][Co][Ci/32] and no per-channel scale ----
 // scale rule on the bits of the block's fp32 absmax: x = clamp(E - 2 + (mantissa > 0x700000), -127, 127), byte x + 127 (an all-zero
@@ -284,12 +287,13 @@ bool conv_fwd_mxfp6_supported(const ConvDesc& d, const char** why);
 // up to 4 bytes, and start at even addresses; the code buffers at multiples of 8.  Anything unsupported throws before a launch.
 void conv_fwd_mxfp6(const ConvDesc& d, const unsigned char* x6, const unsigned char* xs, const unsigned char* w6, const unsigned char* ws,
                     const float* bias, void* y, unsigned char* y6, unsigned char* ys, int out_mode, bool relu, hipStream_t s);
-// bf16 or fp32 [rows][C] -> codes [rows][C / 32][24] + scales [rows][C / 32]; C a multiple of 32
+// bf16 or fp32 [rows][C] -> codes [rows][C / 32][24] + scales [rows][C / 32]; C a multiple of 32 (mx_block.h: quantize_mx<MxE2M3>)
 void quantize_mxfp6(const void* x, bool x_f32, size_t rows, int C, unsigned char* y6, unsigned char* ys, hipStream_t s);
 // One launch quantises every listed layer's fp32 filter [tap][Ci][Co] (element offset off in w) into its code image (byte offset off8 in
 // w6, a multiple of 8) and its scales (byte offset offs in ws); Ci a multiple of 32
 void quantize_filters_mxfp6(const FilterQuantPlan& plan, const float* w, unsigned char* w6, unsigned char* ws, hipStream_t s);
 // max-pooling of mxfp6 tensors: the maximum of the dequantised cells per channel, quantised again per block; C a multiple of 32
+// (mx_block.h: maxpool_fwd_mx<MxE2M3>)
 void maxpool_fwd_mxfp6(const PoolDesc& d, const unsigned char* x6, const unsigned char* xs, unsigned char* y6, unsigned char* ys, hipStream_t s);
 
 }  // namespace ssd

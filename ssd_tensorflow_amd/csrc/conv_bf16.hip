@@ -68,38 +68,6 @@ struct GatherArgsH {
 };
 struct OutMap { int M, DH, DW, ph, pw, ODH, ODW; };      // parity class: virtual pixel (b, a, c) -> real pixel (b, 2 a + ph, 2 c + pw)
 
-// Pipeline step: wait until all but the `ahead` most recent tiles of this lane's LDS-DMA have landed
-// (L DMA instructions per tile; vmcnt retires loads in order), then the workgroup barrier publishes them.
-// A raw s_barrier, not __syncthreads(): the latter's fence drains vmcnt to 0 and with it the tiles that
-// are meant to stay in flight across the barrier.  Every ds_read of the previous tile has already been
-// consumed by an MFMA (lgkmcnt) when a wave arrives here, so the stage it frees can be refilled at once.
-template <int L, int MAXA = 2>
-__device__ __forceinline__ void wait_tiles_and_sync(int ahead) {
-    static_assert(2 * L <= 63 && MAXA * L <= 63, "vmcnt field");
-    // (deep rings of the small-layer configurations: up to MAXA tiles stay in flight; the branches are wave-uniform)
-    if constexpr (MAXA >= 4) {
-        if (ahead >= 4) {
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * L) : "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            return;
-        }
-    }
-    if constexpr (MAXA >= 3) {
-        if (ahead == 3) {
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * L) : "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            return;
-        }
-    }
-    if (ahead >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * L) : "memory");
-    else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(L) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
 // Epilogue of both gather kernels, through an fp32 LDS tile [BM][BN + 4]: full-line loads / stores, fused bias + relu
 // (forward) or accumulate + relu mask (data gradient), ONE rounding to bf16.  The caller has passed a barrier after its
 // last LDS read.

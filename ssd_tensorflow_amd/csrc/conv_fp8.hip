@@ -15,7 +15,7 @@
 namespace ssd {
 
 static bool supported_fp8(bool bigk, const ConvDesc& d, const char** why) {
-    const char* w = conv_e4m3_refusal(false, bigk, d, -1);
+    const char* w = conv_quant_refusal(FMT_FP8, bigk, d, -1);
     if (why) *why = w;
     return w == nullptr;
 }
@@ -55,16 +55,8 @@ void conv_bigk_fwd_fp8(const ConvDesc& d, const unsigned char* x8, const unsigne
 
 // =================================================================================
 // filter quantisation: fp32 [tap][Ci][Co] -> e4m3 [tap][Co][Ci] + one fp32 scale per output channel, all layers in one launch
+// (the table: conv_fp8_detail.h; one workgroup per 32 output channels)
 // =================================================================================
-struct QuantTable {
-    int n;
-    struct Seg {
-        unsigned long long off, off8, offs;      // element offsets: fp32 filter, e4m3 image, scales
-        int taps, ci, co;
-        int blk0;                                // first block of this layer (one block per 32 output channels)
-    } seg[FilterQuantPlan::MAX_LAYERS];
-};
-
 __global__ __launch_bounds__(1024) void quantize_filters_fp8_kernel(QuantTable t, const float* __restrict__ w, unsigned char* __restrict__ w8,
                                                                    float* __restrict__ s_w) {
     __shared__ float red[32][33];
@@ -194,18 +186,10 @@ void FilterQuantPlan::add(size_t off, size_t off8, size_t offs, int taps, int ci
 
 void quantize_filters_fp8(const FilterQuantPlan& plan, const float* w, unsigned char* w8, float* s_w, hipStream_t s) {
     QuantTable t{};
-    t.n = 0;      // (layers whose rows are split below are not in the table)
-    int blk = 0;
-    double elems = 0;
-    for (int i = 0; i < plan.n; ++i) {
-        elems += (double)plan.L[i].taps * plan.L[i].ci * plan.L[i].co;
-        if (quantize_rows_split(plan.L[i], w, w8)) continue;      // below
-        QuantTable::Seg& g = t.seg[t.n++];
-        g.off = plan.L[i].off; g.off8 = plan.L[i].off8; g.offs = plan.L[i].offs;
-        g.taps = plan.L[i].taps; g.ci = plan.L[i].ci; g.co = plan.L[i].co;
-        g.blk0 = blk;
-        blk += cdiv(plan.L[i].co, 32);
-    }
+    double elems;      // (layers whose rows are split below are not in the table)
+    const int blk = fill_quant_table(
+        t, plan, elems, [&](const FilterQuantPlan::Layer& L) { return !quantize_rows_split(L, w, w8); },
+        [](const FilterQuantPlan::Layer& L) { return cdiv(L.co, 32); });
     if (plan.n == 0) return;
     ProfScope prof("quantize_filters_fp8", 0.0, 9.0 * elems, s);
     if (blk > 0) hipLaunchKernelGGL(quantize_filters_fp8_kernel, dim3(blk), dim3(1024), 0, s, t, w, w8, s_w);
@@ -249,21 +233,7 @@ __global__ __launch_bounds__(256) void quantize_fp8_x8_kernel(const T* __restric
     const size_t stride = (size_t)gridDim.x * 256;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += stride) {
         float v[8];
-        if constexpr (sizeof(T) == 2) {
-            const u32x4 w = *reinterpret_cast<const u32x4*>(x + i * 8);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[2 * e] = lo2f(w[e]);
-                v[2 * e + 1] = hi2f(w[e]);
-            }
-        } else {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(x + i * 8), b = *reinterpret_cast<const f32x4*>(x + i * 8 + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = a[e];
-                v[4 + e] = b[e];
-            }
-        }
+        load8(x, i, v);
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = v[e] / scale;
         *reinterpret_cast<u32x2*>(y + i * 8) = u32x2{pack4_e4m3(v[0], v[1], v[2], v[3]), pack4_e4m3(v[4], v[5], v[6], v[7])};
@@ -360,10 +330,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_fp8_kernel(PoolDesc d, const 
 void maxpool_fwd_fp8(const PoolDesc& d, const unsigned char* x8, unsigned char* y8, hipStream_t s) {
     SSD_REQUIRE(x8 && y8, "maxpool_fwd_fp8: null argument");
     SSD_REQUIRE(d.C % 16 == 0 && d.C > 0, "maxpool_fwd_fp8: C must be a multiple of 16 (got %d)", d.C);
-    SSD_REQUIRE(d.k >= 1 && d.stride >= 1 && d.B > 0 && d.Ho > 0 && d.Wo > 0, "maxpool_fwd_fp8: bad geometry");
-    // every window must hold at least one cell of the image
-    SSD_REQUIRE((d.Ho - 1) * d.stride - d.pad_h < d.Hi && (d.Wo - 1) * d.stride - d.pad_w < d.Wi && d.pad_h < d.k && d.pad_w < d.k,
-                "maxpool_fwd_fp8: a window lies outside the image");
+    require_pool_geometry("maxpool_fwd_fp8", d);
     const size_t total = (size_t)d.B * d.Ho * d.Wo * (d.C / 16);
     ProfScope prof("maxpool_fwd_fp8", 0.0, (double)d.C * d.B * ((double)d.Hi * d.Wi + (double)d.Ho * d.Wo), s);
     hipLaunchKernelGGL(maxpool_fwd_fp8_kernel, dim3(grid8(total, 256)), dim3(256), 0, s, d, x8, y8);

@@ -1,12 +1,15 @@
 // The forward gather convolution on e4m3 operands for gfx950 (MI355X), once: the kernel, its launcher, the shape check and the host path
 // behind the four entry points of conv.h.  conv_fp8.hip instantiates it with MX = false (one fp32 scale per activation tensor, DESIGN.md
 // 18, 19), conv_mxfp8.hip with MX = true (one E8M0 scale byte per pixel and 32 channels); DESIGN.md 23 on the merge.
-// The host functions are `static` templates on purpose: each of the two object files gets the instantiations of its own format and
-// nothing of the other's, and no third file includes this header for them.
-// Also what the other e4m3 kernels of the two files share: operand types, the clamped converts, the MX scale rule.
+// The host functions are `static` templates on purpose: each object file gets the instantiations of its own format and nothing of the
+// others', and no further file includes this header for them.
+// Also what the e2m3 kernel of conv_mxfp6_detail.h shares with it: the shape check, the host prologue, the launcher and
+// the filter table.  The frame of the kernel body around the staging and the fragments (gather_pixel_of ... gather_epilogue) is this
+// kernel's alone: conv_mxfp6_detail.h says why the e2m3 kernel keeps its own.  The clamped converts and the MX scale rule are
+// mx_block.h's.
 #pragma once
 #include "conv_detail.h"
-#include "bf16.h"
+#include "mx_block.h"
 
 namespace ssd {
 
@@ -16,70 +19,6 @@ typedef int i32x8 __attribute__((ext_vector_type(8)));
 constexpr int KB8 = 64;                 // k per pipeline iteration = bytes per tile row
 constexpr unsigned OOB8 = 0xFFFFFFF0u;  // offset no buffer covers: the DMA writes zeros (code 0 = +0)
 constexpr int SCALE_ONE = 0x7F7F7F7F;   // E8M0 block scale 127 = 2^0 in every byte
-
-// four floats -> four e4m3 codes in one dword, clamped in fp32 first (the convert's own overflow behaviour is not relied on)
-__device__ __forceinline__ float clamp448(float v) { return fminf(fmaxf(v, -448.f), 448.f); }
-__device__ __forceinline__ unsigned pack4_e4m3(float a, float b, float c, float d) {
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp448(a), clamp448(b), 0, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp448(c), clamp448(d), w, true);
-    return (unsigned)w;
-}
-__device__ __forceinline__ unsigned char to_e4m3(float v) {
-    return (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(clamp448(v), 0.f, 0, false) & 0xFF);
-}
-
-// the MX scale rule: fp32 absmax (>= 0) -> x in -127 ... 127.  Non-finite input gives 120 / 121: no byte 255, no fault
-__device__ __forceinline__ int mx_exponent(float amax) {
-    const unsigned u = __float_as_uint(amax);
-    const int x = (int)(u >> 23) - 127 - 8 + ((u & 0x7FFFFFu) > 0x600000u ? 1 : 0);
-    return x < -127 ? -127 : x > 127 ? 127 : x;
-}
-// a thread's 8 values of a 32-channel block held by 4 adjacent lanes -> the block's exponent; every lane of the four gets it
-__device__ __forceinline__ int mx_block_exponent(const float (&v)[8]) {
-    float am = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) am = fmaxf(am, fabsf(v[e]));
-    am = fmaxf(am, __shfl_xor(am, 1, 64));
-    am = fmaxf(am, __shfl_xor(am, 2, 64));
-    return mx_exponent(am);
-}
-__device__ __forceinline__ u32x2 mx_pack8(const float (&v)[8], int x) {
-    return u32x2{pack4_e4m3(ldexpf(v[0], -x), ldexpf(v[1], -x), ldexpf(v[2], -x), ldexpf(v[3], -x)),
-                 pack4_e4m3(ldexpf(v[4], -x), ldexpf(v[5], -x), ldexpf(v[6], -x), ldexpf(v[7], -x))};
-}
-
-// blocks of a grid-stride kernel: enough for `items`, at most 32 per CU
-inline int grid8(size_t items, int per_block) {
-    const size_t g = (items + per_block - 1) / per_block;
-    return (int)std::min<size_t>(std::max<size_t>(g, 1), 256 * 32);
-}
-
-// conv_bf16.hip wait_tiles_and_sync: all but the `ahead` most recent tiles of this lane's DMA have landed, then the barrier
-template <int L, int MAXA>
-__device__ __forceinline__ void wait_tiles_and_sync8(int ahead) {
-    static_assert(MAXA * L <= 63, "vmcnt field");
-    if constexpr (MAXA >= 4) {
-        if (ahead >= 4) {
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * L) : "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            return;
-        }
-    }
-    if constexpr (MAXA >= 3) {
-        if (ahead == 3) {
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * L) : "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            return;
-        }
-    }
-    if (ahead >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * L) : "memory");
-    else if (ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(L) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
 
 // =================================================================================
 // The kernel: the forward gather convolution of conv_bf16.hip restated for e4m3 operands on the block-scaled matrix instruction
@@ -193,6 +132,117 @@ struct TapWalk8<true> {
     }
 };
 
+// ---- The frame of conv_fwd_e4m3_kernel's body, one function per step, so that the kernel itself reads as what differs with MX and
+// the tap walk: the staging, the fragment reads, the scale-byte shifts.
+// output row -> its pixel at tap (0, 0), in pixels of the source
+__device__ __forceinline__ int gather_pixel_of(const GatherArgs8& p, int m, int& rh, int& rw) {
+    const int ow = m % p.DW;
+    const int t2 = m / p.DW;
+    const int oh = t2 % p.DH;
+    const int b = t2 / p.DH;
+    rh = oh * p.mul;
+    rw = ow * p.mul;
+    return b * p.SH * p.SW + rh * p.SW + rw;
+}
+// accumulators: D rows = output channels (filter operand first), D cols = pixels, as in conv_bf16.hip
+template <int TM, int TN>
+__device__ __forceinline__ void gather_zero(f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+    for (int a = 0; a < TM; ++a)
+#pragma unroll
+        for (int b = 0; b < TN; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+}
+// the main loop: NS stages; tiles k+1 .. k+NS-1 stream in while tile k is multiplied.  L_N: DMA instructions per thread and stage
+template <int NS, int L_N, typename Issue, typename Compute>
+__device__ __forceinline__ void gather_ring(int nk, const Issue& issue_next, const Compute& compute) {
+#pragma unroll
+    for (int t = 0; t < NS - 1; ++t)
+        if (t < nk) issue_next(t);
+    int st_c = 0, st_i = NS - 1;
+    for (int k = 0; k < nk; ++k) {
+        const int later = nk - 1 - k;
+        wait_tiles_and_sync<L_N, (NS - 2 > 4 ? 4 : NS - 2)>(later < NS - 2 ? later : NS - 2);      // tile k visible; stage st_i is free
+        if (k + NS - 1 < nk) issue_next(st_i);
+        compute(st_c);
+        st_c = st_c + 1 == NS ? 0 : st_c + 1;
+        st_i = st_i + 1 == NS ? 0 : st_i + 1;
+    }
+    __syncthreads();
+}
+// the accumulators into the fp32 LDS tile Cs [32 TM WM][LDC] of the epilogue, LDC = BN + 4
+template <int TM, int TN, int LDC>
+__device__ __forceinline__ void gather_acc_to_tile(float* Cs, const f32x16 (&acc)[TM][TN], int wm, int wn, int li, int lh) {
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int ml = wm * 32 * TM + mi * 32 + li;
+                const int nl = wn * 32 * TN + ni * 32 + 8 * g + 4 * lh;
+                const f32x16& c = acc[mi][ni];
+                *reinterpret_cast<f32x4*>(Cs + ml * LDC + nl) = f32x4{c[4 * g], c[4 * g + 1], c[4 * g + 2], c[4 * g + 3]};
+            }
+    __syncthreads();
+}
+// The epilogue's row walk over that tile: y = relu?(acc * scale[co] + bias[co]) in fp32, scale = s_in * s_w (MX: s_w alone, the pixel
+// scales went through the instruction), then one rounding per output format.  The arguments come by value: through a reference the
+// output stores may alias them as far as the compiler knows, which costs the 64 x 64 instantiations two VGPRs.
+template <bool MX, int NTHR, int BM, int BN>
+__device__ __forceinline__ void gather_epilogue(const GatherArgs8 p, const float* Cs, int m0, int n0, int tid) {
+    constexpr int LDC = BN + 4;
+    constexpr int OUT8 = MX ? FP8_OUT_MX : FP8_OUT_E4M3, OUT16_8 = MX ? FP8_OUT_BF16_MX : FP8_OUT_BF16_E4M3;
+    constexpr int TPR = BN / 8;               // threads per row, 8 channels each: a 32-channel MX block is 4 adjacent lanes
+    constexpr int RPP = NTHR / TPR;           // rows per pass
+    static_assert(TPR % 4 == 0, "a block's four lanes share a row");
+    const int cg = tid % TPR, r0 = tid / TPR;
+    const int n = n0 + cg * 8;
+    if (n >= p.DN) return;                    // (an MX output has DN % 32 == 0: the four lanes of a block leave or stay together)
+    float sc[8], bv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        if constexpr (MX) sc[e] = p.s_w[n + e];
+        else sc[e] = p.s_in * p.s_w[n + e];
+        bv[e] = p.bias ? p.bias[n + e] : 0.f;
+    }
+#pragma unroll
+    for (int ps = 0; ps < BM / RPP; ++ps) {
+        const int ml = r0 + ps * RPP;
+        const int m = m0 + ml;
+        if (m >= p.M) continue;               // (the same m for the four lanes of a block)
+        const size_t o = (size_t)m * p.DN + n;
+        const f32x4 c0 = *reinterpret_cast<const f32x4*>(Cs + ml * LDC + cg * 8);
+        const f32x4 c1 = *reinterpret_cast<const f32x4*>(Cs + ml * LDC + cg * 8 + 4);
+        float v[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            v[e] = v[e] * sc[e] + bv[e];
+            if (p.relu) v[e] = v[e] > 0.f ? v[e] : 0.f;
+        }
+        if (p.mode == FP8_OUT_F32) {
+            float* d = reinterpret_cast<float*>(p.dst) + o;
+            *reinterpret_cast<f32x4*>(d) = f32x4{v[0], v[1], v[2], v[3]};
+            *reinterpret_cast<f32x4*>(d + 4) = f32x4{v[4], v[5], v[6], v[7]};
+        } else if (p.mode != OUT8) {
+            *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(p.dst) + o) =
+                u32x4{pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
+        }
+        if (p.mode == OUT8 || p.mode == OUT16_8) {
+            if constexpr (MX) {      // (a block's 32 bytes are its channels' bytes: the thread's 8 codes go to o)
+                const int x = mx_block_exponent<MxE4M3>(v);
+                *reinterpret_cast<u32x2*>(p.dst8 + o) = MxE4M3::pack8(v, x);
+                if ((cg & 3) == 0) p.dst_sc[(size_t)m * (p.DN >> 5) + (n >> 5)] = (unsigned char)(x + 127);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = v[e] / p.s_out;
+                *reinterpret_cast<u32x2*>(p.dst8 + o) = u32x2{pack4_e4m3(v[0], v[1], v[2], v[3]), pack4_e4m3(v[4], v[5], v[6], v[7])};
+            }
+        }
+    }
+}
+
 template <bool MX, bool TABLE, int WM, int WN, int TM, int TN, int NS>
 __global__ __launch_bounds__(64 * WM * WN) void conv_fwd_e4m3_kernel(GatherArgs8 pp) {
     const GatherArgs8& p = pp;
@@ -203,8 +253,6 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_fwd_e4m3_kernel(GatherArgs8
     constexpr int L_N = A_N + B_N + (MX ? 1 : 0);     // ... and per stage: what the wait in front of a stage counts
     constexpr int CODES = (BM + BN) * KB8;
     constexpr int STAGE = CODES + (MX ? NTHR * 4 : 0);      // + the scale dwords
-    constexpr int LDC = BN + 4;
-    constexpr int OUT8 = MX ? FP8_OUT_MX : FP8_OUT_E4M3, OUT16_8 = MX ? FP8_OUT_BF16_MX : FP8_OUT_BF16_E4M3;
     static_assert(BM % RPP_S == 0 && BN % RPP_S == 0 && RPP_S % 16 == 0 && (!MX || BM <= NTHR), "tile vs staging pass");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -216,16 +264,6 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_fwd_e4m3_kernel(GatherArgs8
     const int m0 = mt * BM, n0 = nt * BN;
     const int SB = p.SC >> 5;                         // MX: scale bytes per pixel (even: SC is a multiple of 64)
 
-    // output row -> its pixel at tap (0, 0), in pixels of the source
-    auto pixel_of = [&](int m, int& rh, int& rw) {
-        const int ow = m % p.DW;
-        const int t2 = m / p.DW;
-        const int oh = t2 % p.DH;
-        const int b = t2 / p.DH;
-        rh = oh * p.mul;
-        rw = ow * p.mul;
-        return b * p.SH * p.SW + rh * p.SW + rw;
-    };
     using Walk = TapWalk8<TABLE>;
 
     // ---- staging: thread -> rows (tid >> 2) + RPP_S i, LDS slot tid & 3, global chunk slot ^ ((row >> 2) & 3)
@@ -235,7 +273,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_fwd_e4m3_kernel(GatherArgs8
     for (int i = 0; i < A_N; ++i) {
         const int m = m0 + (tid >> 2) + RPP_S * i;
         int rh, rw;
-        const int pix = pixel_of(m < p.M ? m : 0, rh, rw);
+        const int pix = gather_pixel_of(p, m < p.M ? m : 0, rh, rw);
         a_off[i] = (unsigned)(pix * p.SC + a_ck);
         a_msk[i] = m < p.M ? Walk::mask(p, rh, rw) : 0u;
     }
@@ -251,7 +289,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_fwd_e4m3_kernel(GatherArgs8
     if constexpr (MX)
         if (tid < BM && m0 + tid < p.M) {
             int rh, rw;
-            s_off = (unsigned)(pixel_of(m0 + tid, rh, rw) * SB + p.sc_delta);
+            s_off = (unsigned)(gather_pixel_of(p, m0 + tid, rh, rw) * SB + p.sc_delta);
             s_msk = Walk::mask(p, rh, rw);
         }
     const size_t src_pixels = (size_t)(p.M / (p.DH * p.DW)) * p.SH * p.SW;
@@ -293,15 +331,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_fwd_e4m3_kernel(GatherArgs8
         iw.advance(p);
     };
 
-    // ---- accumulators: D rows = output channels (filter operand first), D cols = pixels, as in conv_bf16.hip
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
+    gather_zero(acc);
     const int wm = wave / WN, wn = wave - wm * WN;
     const int li = lane & 31, lh = lane >> 5;
     // fragment = two chunks of row li, a fixed distance apart (the chunk assignment: above the kernel)
@@ -316,7 +347,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_fwd_e4m3_kernel(GatherArgs8
         for (int mi = 0; mi < TM; ++mi) {
             const int m = m0 + wm * 32 * TM + mi * 32 + li;
             int rh, rw;
-            s_rb[mi] = (unsigned)(pixel_of(m < p.M ? m : 0, rh, rw) * SB + p.sc_delta);
+            s_rb[mi] = (unsigned)(gather_pixel_of(p, m < p.M ? m : 0, rh, rw) * SB + p.sc_delta);
         }
     }
 
@@ -348,96 +379,24 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_fwd_e4m3_kernel(GatherArgs8
         if constexpr (MX) cw.advance(p);
     };
 
-    // ---- main loop: NS stages; tiles k+1 .. k+NS-1 stream in while tile k is multiplied
-#pragma unroll
-    for (int t = 0; t < NS - 1; ++t)
-        if (t < nk) issue_next(t);
-    int st_c = 0, st_i = NS - 1;
-    for (int k = 0; k < nk; ++k) {
-        const int later = nk - 1 - k;
-        wait_tiles_and_sync8<L_N, (NS - 2 > 4 ? 4 : NS - 2)>(later < NS - 2 ? later : NS - 2);      // tile k visible; stage st_i is free
-        if (k + NS - 1 < nk) issue_next(st_i);
-        compute(st_c);
-        st_c = st_c + 1 == NS ? 0 : st_c + 1;
-        st_i = st_i + 1 == NS ? 0 : st_i + 1;
-    }
-    __syncthreads();
+    gather_ring<NS, L_N>(nk, issue_next, compute);
 
-    // ---- epilogue through an fp32 LDS tile [BM][BN + 4]: y = relu?(acc * scale[co] + bias[co]), scale = s_in * s_w (MX: s_w alone, the
-    // pixel scales went through the instruction), then one rounding per output format
+    // ---- epilogue through an fp32 LDS tile [BM][BN + 4]
     float* Cs = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < TN; ++ni)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int ml = wm * 32 * TM + mi * 32 + li;
-                const int nl = wn * 32 * TN + ni * 32 + 8 * g + 4 * lh;
-                const f32x16& c = acc[mi][ni];
-                *reinterpret_cast<f32x4*>(Cs + ml * LDC + nl) = f32x4{c[4 * g], c[4 * g + 1], c[4 * g + 2], c[4 * g + 3]};
-            }
-    __syncthreads();
-    constexpr int TPR = BN / 8;               // threads per row, 8 channels each: a 32-channel MX block is 4 adjacent lanes
-    constexpr int RPP = NTHR / TPR;           // rows per pass
-    static_assert(TPR % 4 == 0, "a block's four lanes share a row");
-    const int cg = tid % TPR, r0 = tid / TPR;
-    const int n = n0 + cg * 8;
-    if (n >= p.DN) return;                    // (an MX output has DN % 32 == 0: the four lanes of a block leave or stay together)
-    float sc[8], bv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        if constexpr (MX) sc[e] = p.s_w[n + e];
-        else sc[e] = p.s_in * p.s_w[n + e];
-        bv[e] = p.bias ? p.bias[n + e] : 0.f;
-    }
-#pragma unroll
-    for (int ps = 0; ps < BM / RPP; ++ps) {
-        const int ml = r0 + ps * RPP;
-        const int m = m0 + ml;
-        if (m >= p.M) continue;               // (the same m for the four lanes of a block)
-        const size_t o = (size_t)m * p.DN + n;
-        const f32x4 c0 = *reinterpret_cast<const f32x4*>(Cs + ml * LDC + cg * 8);
-        const f32x4 c1 = *reinterpret_cast<const f32x4*>(Cs + ml * LDC + cg * 8 + 4);
-        float v[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            v[e] = v[e] * sc[e] + bv[e];
-            if (p.relu) v[e] = v[e] > 0.f ? v[e] : 0.f;
-        }
-        if (p.mode == FP8_OUT_F32) {
-            float* d = reinterpret_cast<float*>(p.dst) + o;
-            *reinterpret_cast<f32x4*>(d) = f32x4{v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<f32x4*>(d + 4) = f32x4{v[4], v[5], v[6], v[7]};
-        } else if (p.mode != OUT8) {
-            *reinterpret_cast<u32x4*>(reinterpret_cast<bf16_t*>(p.dst) + o) =
-                u32x4{pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
-        }
-        if (p.mode == OUT8 || p.mode == OUT16_8) {
-            if constexpr (MX) {
-                const int x = mx_block_exponent(v);
-                *reinterpret_cast<u32x2*>(p.dst8 + o) = mx_pack8(v, x);
-                if ((cg & 3) == 0) p.dst_sc[(size_t)m * (p.DN >> 5) + (n >> 5)] = (unsigned char)(x + 127);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = v[e] / p.s_out;
-                *reinterpret_cast<u32x2*>(p.dst8 + o) = u32x2{pack4_e4m3(v[0], v[1], v[2], v[3]), pack4_e4m3(v[4], v[5], v[6], v[7])};
-            }
-        }
-    }
+    gather_acc_to_tile<TM, TN, BN + 4>(Cs, acc, wm, wn, li, lh);
+    gather_epilogue<MX, NTHR, BM, BN>(p, Cs, m0, n0, tid);
 }
 
 // =================================================================================
-// The host path.  An entry point of conv.h is a format (MX) and a tap range: 1 ... 9 taps, or 10 ... 121 (`bigk`: the fc graph's 7 x 7 fc6).
+// The host path.  An entry point of conv.h is a format and a tap range: 1 ... 9 taps, or 10 ... 121 (`bigk`: the fc graph's 7 x 7 fc6,
+// e4m3 only).
 // =================================================================================
-template <bool MX, bool TABLE, int WM, int WN, int TM, int TN, int NS>
-static void launch_fwd_e4m3(GatherArgs8& a, bool bigk, const char* label, double flops, double bytes, hipStream_t s) {
-    constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
-    constexpr size_t stages = NS * ((size_t)(BM + BN) * KB8 + (MX ? 64 * WM * WN * 4 : 0)), ctile = (size_t)BM * (BN + 4) * 4;
-    constexpr size_t lds = stages > ctile ? stages : ctile;
+// One launcher for the gather kernels: KERN with NTHR threads per BM x BN tile and STAGES bytes of LDS for its ring.
+template <auto KERN, int NTHR, int BM, int BN, size_t STAGES, typename Args>
+static void launch_gather(Args& a, bool m_fast, const char* label, double flops, double bytes, hipStream_t s) {
+    constexpr size_t ctile = (size_t)BM * (BN + 4) * 4, lds = STAGES > ctile ? STAGES : ctile;
     static_assert(lds <= 80 * 1024, "LDS: two workgroups per CU");
-    auto kern = conv_fwd_e4m3_kernel<MX, TABLE, WM, WN, TM, TN, NS>;
-    static bool once = (set_lds(kern, lds), true);
+    static bool once = (set_lds(KERN, lds), true);
     (void)once;
     // Workgroup order.  Consecutive workgroups share an XCD's L2 (xcd_remap).  With filter columns fastest the workgroups resident on an
     // XCD cover every column, and each row of pixel tiles streams the whole filter image: MT x its bytes in all.  With pixel tiles fastest
@@ -445,68 +404,101 @@ static void launch_fwd_e4m3(GatherArgs8& a, bool bigk, const char* label, double
     // Ci bytes) is always larger than a pixel tile's input (about BM x Ci), so those layers take pixel tiles fastest; up to 9 taps keep
     // filter columns fastest.  fc6 at batch 128 (102 MB of filter, 24 MB of input, MT 361, NT 32): 4.92 against 9.70 ms.
     const int MT = cdiv(a.M, BM), NT = cdiv(a.DN, BN);
-    a.m_fast = bigk;
-    a.fast_n = bigk ? MT : NT;
+    a.m_fast = m_fast;
+    a.fast_n = m_fast ? MT : NT;
     ProfScope prof(label, flops, bytes, s);
-    SSD_LAUNCH_STOP(kern, dim3(MT * NT), dim3(64 * WM * WN), lds, s, a);
+    SSD_LAUNCH_STOP(KERN, dim3(MT * NT), dim3(NTHR), lds, s, a);
     HIP_OK(hipGetLastError());
 }
+template <bool MX, bool TABLE, int WM, int WN, int TM, int TN, int NS>
+static void launch_fwd_e4m3(GatherArgs8& a, bool bigk, const char* label, double flops, double bytes, hipStream_t s) {
+    constexpr int NTHR = 64 * WM * WN, BM = 32 * TM * WM, BN = 32 * TN * WN;
+    launch_gather<conv_fwd_e4m3_kernel<MX, TABLE, WM, WN, TM, TN, NS>, NTHR, BM, BN, NS * ((size_t)(BM + BN) * KB8 + (MX ? NTHR * 4 : 0))>(
+        a, bigk, label, flops, bytes, s);
+}
 
-// Why an entry point refuses a layer, or nullptr: a string literal "<fmt> conv[ (more than 9 taps)]: reason" (fmt = "fp8" / "mxfp8").
-// out_mode < 0: the shape alone.  An MX output needs whole 32-channel blocks, and the scale tensors stay below the offset guard too.
-#define E4M3_WHY(text) \
-    (mx ? (bigk ? "mxfp8 conv (more than 9 taps): " text : "mxfp8 conv: " text) : (bigk ? "fp8 conv (more than 9 taps): " text : "fp8 conv: " text))
-inline const char* conv_e4m3_refusal(bool mx, bool bigk, const ConvDesc& d, int out_mode) {
+// Why an entry point refuses a layer, or nullptr: a string literal "<fmt> conv[ (more than 9 taps)]: reason" (fmt = "fp8" / "mxfp8" /
+// "mxfp6").  out_mode < 0: the shape alone.  An MX output needs whole 32-channel blocks, and the scale tensors of mxfp8 stay below the
+// offset guard too.  mxfp6 has no kernel for more than 9 taps, so no `bigk` and one text of its own for every tap count it cannot run.
+enum QuantFmt { FMT_FP8, FMT_MXFP8, FMT_MXFP6 };
+#define QUANT_WHY(text)                                                                                           \
+    (fmt == FMT_MXFP6 ? "mxfp6 conv: " text                                                                       \
+     : fmt == FMT_MXFP8 ? (bigk ? "mxfp8 conv (more than 9 taps): " text : "mxfp8 conv: " text)                   \
+                        : (bigk ? "fp8 conv (more than 9 taps): " text : "fp8 conv: " text))
+inline const char* conv_quant_refusal(QuantFmt fmt, bool bigk, const ConvDesc& d, int out_mode) {
     const long long taps = (long long)d.KH * d.KW;
+    const bool mx = fmt != FMT_FP8;
     const bool wants_mx = out_mode == FP8_OUT_MX || out_mode == FP8_OUT_BF16_MX;
     const bool mode_ok = out_mode == FP8_OUT_BF16 || out_mode == FP8_OUT_F32 ||
                          (mx ? wants_mx : out_mode == FP8_OUT_E4M3 || out_mode == FP8_OUT_BF16_E4M3);
-    if (d.KH < 1 || d.KW < 1 || d.KH > 11 || d.KW > 11) return E4M3_WHY("KH and KW must be in 1 ... 11");
-    if (bigk && taps <= 9)      // (a wrong tap count names the entry point that runs it)
-        return mx ? E4M3_WHY("9 taps or fewer run on conv_fwd_mxfp8 (ssd_op_conv2d_fwd_mxfp8)") : E4M3_WHY("9 taps or fewer run on conv_fwd_fp8 (ssd_op_conv2d_fwd_fp8)");
-    if (!bigk && taps > 9)
-        return mx ? E4M3_WHY("more than 9 taps run on conv_bigk_fwd_mxfp8 (ssd_op_conv2d_fwd_mxfp8_bigk)")
-                  : E4M3_WHY("more than 9 taps run on conv_bigk_fwd_fp8 (ssd_op_conv2d_fwd_fp8_bigk)");
-    if (d.Ci < 64 || d.Ci % 64 != 0) return E4M3_WHY("Ci must be a multiple of 64");
-    if (d.Co < 8 || d.Co % 8 != 0) return E4M3_WHY("Co must be a multiple of 8");
-    if (d.stride < 1 || d.dil < 1) return E4M3_WHY("stride and dilation must be positive");
-    if (d.B < 1 || d.Ho < 1 || d.Wo < 1 || d.Hi < 1 || d.Wi < 1) return E4M3_WHY("empty tensor");
+    if (fmt == FMT_MXFP6) {
+        if (d.KH < 1 || d.KW < 1 || taps > 9) return QUANT_WHY("at most 9 taps (a layer with more stays on its bf16 kernel: there is no mxfp6 kernel for it)");
+    } else {
+        if (d.KH < 1 || d.KW < 1 || d.KH > 11 || d.KW > 11) return QUANT_WHY("KH and KW must be in 1 ... 11");
+        if (bigk && taps <= 9)      // (a wrong tap count names the entry point that runs it)
+            return mx ? QUANT_WHY("9 taps or fewer run on conv_fwd_mxfp8 (ssd_op_conv2d_fwd_mxfp8)") : QUANT_WHY("9 taps or fewer run on conv_fwd_fp8 (ssd_op_conv2d_fwd_fp8)");
+        if (!bigk && taps > 9)
+            return mx ? QUANT_WHY("more than 9 taps run on conv_bigk_fwd_mxfp8 (ssd_op_conv2d_fwd_mxfp8_bigk)")
+                      : QUANT_WHY("more than 9 taps run on conv_bigk_fwd_fp8 (ssd_op_conv2d_fwd_fp8_bigk)");
+    }
+    if (d.Ci < 64 || d.Ci % 64 != 0) return QUANT_WHY("Ci must be a multiple of 64");
+    if (d.Co < 8 || d.Co % 8 != 0) return QUANT_WHY("Co must be a multiple of 8");
+    if (d.stride < 1 || d.dil < 1) return QUANT_WHY("stride and dilation must be positive");
+    if (d.B < 1 || d.Ho < 1 || d.Wo < 1 || d.Hi < 1 || d.Wi < 1) return QUANT_WHY("empty tensor");
     if ((long long)d.B * d.Hi * d.Wi * d.Ci >= (1LL << 31) - 16 || (long long)d.B * d.Ho * d.Wo * d.Co >= (1LL << 31) - 16)
-        return E4M3_WHY("a tensor of this layer exceeds the 32-bit offsets: lower the batch");
-    if (taps * d.Co * d.Ci >= (1LL << 31) - 16) return E4M3_WHY("the filter image exceeds the 32-bit offsets");
-    if (mx && ((long long)d.B * d.Hi * d.Wi * (d.Ci / 32) + 8 >= (1LL << 31) - 16 || (long long)d.B * d.Ho * d.Wo * (d.Co / 32) >= (1LL << 31) - 16))
-        return E4M3_WHY("a scale tensor of this layer exceeds the 32-bit offsets: lower the batch");
-    if (out_mode >= 0 && !mode_ok) return E4M3_WHY("unknown output mode");
-    if (out_mode >= 0 && wants_mx && d.Co % 32 != 0) return E4M3_WHY("an MX output needs Co to be a multiple of 32");
+        return QUANT_WHY("a tensor of this layer exceeds the 32-bit offsets: lower the batch");
+    if (taps * d.Co * d.Ci >= (1LL << 31) - 16) return QUANT_WHY("the filter image exceeds the 32-bit offsets");
+    if (fmt == FMT_MXFP8 && ((long long)d.B * d.Hi * d.Wi * (d.Ci / 32) + 8 >= (1LL << 31) - 16 || (long long)d.B * d.Ho * d.Wo * (d.Co / 32) >= (1LL << 31) - 16))
+        return QUANT_WHY("a scale tensor of this layer exceeds the 32-bit offsets: lower the batch");
+    if (out_mode >= 0 && !mode_ok) return QUANT_WHY("unknown output mode");
+    if (out_mode >= 0 && wants_mx && d.Co % 32 != 0) return QUANT_WHY("an MX output needs Co to be a multiple of 32");
     return nullptr;
 }
-#undef E4M3_WHY
+#undef QUANT_WHY
+
+// ---- the host prologue of every gather entry point: the refusal as an error, the geometry, the scale pointers, the tile
+inline void require_conv_quant(QuantFmt fmt, bool bigk, const ConvDesc& d, int out_mode) {
+    const char* why = conv_quant_refusal(fmt, bigk, d, out_mode);
+    SSD_REQUIRE(why == nullptr, "%s (got %dx%d taps, Ci %d, Co %d, output mode %d)", why, d.KH, d.KW, d.Ci, d.Co, out_mode);
+}
+inline void gather_geometry(GatherArgs8& a, const ConvDesc& d, int out_mode, bool relu) {
+    a.M = d.B * d.Ho * d.Wo; a.DH = d.Ho; a.DW = d.Wo; a.DN = d.Co;
+    a.SH = d.Hi; a.SW = d.Wi; a.SC = d.Ci;
+    a.KH = d.KH; a.KW = d.KW; a.dil = d.dil; a.pad_h = d.pad_h; a.pad_w = d.pad_w;
+    a.mul = d.stride; a.relu = relu; a.mode = out_mode;
+}
+// a scale tensor is fetched in aligned dwords, and a sample's scales inside a batch may start between two: the dword boundary in
+// front of `sc`, and in `delta` how far in front
+inline const unsigned char* dword_base(const unsigned char* sc, int& delta) {
+    delta = (int)(reinterpret_cast<uintptr_t>(sc) & 3);
+    return sc - delta;
+}
+// Tiles: 0 = 128 x 128 (the fp32 epilogue tile's 66 KB sets the allocation: two workgroups per CU); 1 = 64 x 64, six stages, where the
+// 128 x 128 tiling would leave CUs empty.  SSD_TILE_FP8 forces one (tests, tuning).
+inline int gather_tile(const GatherArgs8& a) {
+    const int cfg = env_int("SSD_TILE_FP8", -1);
+    return cfg == 0 || cfg == 1 ? cfg : (long long)cdiv(a.M, 128) * cdiv(a.DN, 128) <= 256 ? 1 : 0;
+}
 
 // What an entry point passes on: the operands in `a` (src, src_sc, wgt, bias, s_w, dst, dst8, dst_sc, s_in, s_out), the rest is filled
-// here.  Tiles: 0 = 128 x 128, four stages of 16 KB (the fp32 epilogue tile's 66 KB sets the allocation: two workgroups per CU); 1 = 64
-// x 64, six stages, where the 128 x 128 tiling would leave CUs empty.  SSD_TILE_FP8 forces one (tests, tuning).
+// here.  128 x 128 runs four stages of 16 KB.
 template <bool MX>
 static void conv_fwd_e4m3(bool bigk, const ConvDesc& d, GatherArgs8 a, int out_mode, bool relu, hipStream_t s) {
-    const char* why = conv_e4m3_refusal(MX, bigk, d, out_mode);
-    SSD_REQUIRE(why == nullptr, "%s (got %dx%d taps, Ci %d, Co %d, output mode %d)", why, d.KH, d.KW, d.Ci, d.Co, out_mode);
+    require_conv_quant(MX ? FMT_MXFP8 : FMT_FP8, bigk, d, out_mode);
     const bool wants8 = out_mode == (MX ? FP8_OUT_MX : FP8_OUT_E4M3) || out_mode == (MX ? FP8_OUT_BF16_MX : FP8_OUT_BF16_E4M3);
     if constexpr (MX) {
         SSD_REQUIRE(!wants8 || (a.dst8 != nullptr && a.dst_sc != nullptr), "mxfp8 conv: an MX output needs its code and scale buffers");
         SSD_REQUIRE(out_mode == FP8_OUT_MX || a.dst != nullptr, "mxfp8 conv: null output");
         SSD_REQUIRE(a.src && a.src_sc && a.wgt && a.s_w, "mxfp8 conv: null operand");
         SSD_REQUIRE(reinterpret_cast<uintptr_t>(a.src_sc) % 2 == 0, "mxfp8 conv: the scale buffer must start at an even address");
-        a.sc_delta = (int)(reinterpret_cast<uintptr_t>(a.src_sc) & 3);      // (a sample's scales inside a batch may start between two dwords)
-        a.src_sc -= a.sc_delta;
+        a.src_sc = dword_base(a.src_sc, a.sc_delta);
     } else {
         SSD_REQUIRE(!wants8 || (a.dst8 != nullptr && a.s_out > 0.f), "fp8 conv: an e4m3 output needs its buffer and a positive scale");
         SSD_REQUIRE(out_mode == FP8_OUT_E4M3 || a.dst != nullptr, "fp8 conv: null output");
         SSD_REQUIRE(a.src && a.wgt && a.s_w && a.s_in > 0.f, "fp8 conv: null operand or non-positive input scale");
         if (!wants8) a.s_out = 1.f;
     }
-    a.M = d.B * d.Ho * d.Wo; a.DH = d.Ho; a.DW = d.Wo; a.DN = d.Co;
-    a.SH = d.Hi; a.SW = d.Wi; a.SC = d.Ci;
-    a.KH = d.KH; a.KW = d.KW; a.dil = d.dil; a.pad_h = d.pad_h; a.pad_w = d.pad_w;
-    a.mul = d.stride; a.relu = relu; a.mode = out_mode;
+    gather_geometry(a, d, out_mode, relu);
     if (!bigk) {
         a.ntaps = d.KH * d.KW;
         for (int kh = 0; kh < d.KH; ++kh)
@@ -521,8 +513,7 @@ static void conv_fwd_e4m3(bool bigk, const ConvDesc& d, GatherArgs8 a, int out_m
     const double by = (double)d.B * d.Hi * d.Wi * d.Ci * (1.0 + sc_b) + (double)d.KH * d.KW * d.Ci * d.Co + (double)d.B * d.Ho * d.Wo * d.Co * out_b;
     static const char* const LABEL[2][2][2] = {{{"conv_fwd_fp8_128x128", "conv_fwd_fp8_64x64x6"}, {"conv_bigk_fwd_fp8_128x128", "conv_bigk_fwd_fp8_64x64x6"}},
                                                {{"conv_fwd_mxfp8_128x128", "conv_fwd_mxfp8_64x64x6"}, {"conv_bigk_fwd_mxfp8_128x128", "conv_bigk_fwd_mxfp8_64x64x6"}}};
-    int cfg = env_int("SSD_TILE_FP8", -1);
-    if (cfg != 0 && cfg != 1) cfg = (long long)cdiv(a.M, 128) * cdiv(a.DN, 128) <= 256 ? 1 : 0;
+    const int cfg = gather_tile(a);
     // the tap walk (TapWalk8): the table for MX = false up to 9 taps, the counters everywhere else
     if constexpr (!MX)
         if (!bigk) {
@@ -532,6 +523,37 @@ static void conv_fwd_e4m3(bool bigk, const ConvDesc& d, GatherArgs8 a, int out_m
         }
     if (cfg == 0) launch_fwd_e4m3<MX, false, 2, 2, 2, 2, 4>(a, bigk, LABEL[MX][bigk][0], fl, by, s);
     else launch_fwd_e4m3<MX, false, 2, 2, 1, 1, 6>(a, bigk, LABEL[MX][bigk][1], fl, by, s);
+}
+
+// =================================================================================
+// The table of a filter-quantisation launch that covers several layers (quantize_filters_fp8_kernel, quantize_filters_mxfp6_kernel): a
+// workgroup finds its layer by its number.
+// =================================================================================
+struct QuantTable {
+    int n;
+    struct Seg {
+        unsigned long long off, off8, offs;      // fp32 filter (elements), code image (bytes), scales (elements of their type)
+        int taps, ci, co;
+        int blk0;                                // first workgroup of this layer
+    } seg[FilterQuantPlan::MAX_LAYERS];
+};
+// the plan's layers that belong(L), at blocks(L) workgroups each; returns the grid.  elems: the elements of all layers of the plan
+template <typename Belongs, typename Blocks>
+static int fill_quant_table(QuantTable& t, const FilterQuantPlan& plan, double& elems, const Belongs& belongs, const Blocks& blocks) {
+    int blk = 0;
+    t.n = 0;
+    elems = 0;
+    for (int i = 0; i < plan.n; ++i) {
+        const FilterQuantPlan::Layer& L = plan.L[i];
+        elems += (double)L.taps * L.ci * L.co;
+        if (!belongs(L)) continue;
+        QuantTable::Seg& g = t.seg[t.n++];
+        g.off = L.off; g.off8 = L.off8; g.offs = L.offs;
+        g.taps = L.taps; g.ci = L.ci; g.co = L.co;
+        g.blk0 = blk;
+        blk += blocks(L);
+    }
+    return blk;
 }
 
 }  // namespace ssd

@@ -1,59 +1,14 @@
-// The forward gather convolution on e2m3 (OCP MX FP6) operands for gfx950 (MI355X), and what the mxfp6 kernels of conv_mxfp6.hip
-// share: the scale rule, the integer encoder, the 24-byte block store.  DESIGN.md 24.  Included by conv_mxfp6.hip alone; the tap walks,
-// the stage wait and the operand types are conv_fp8_detail.h's, by inclusion.
+// The forward gather convolution on e2m3 (OCP MX FP6) operands for gfx950 (MI355X): the staging of 48-byte rows, the fragments and the
+// scales on both operands.  DESIGN.md 24.  Included by conv_mxfp6.hip alone; the tap walks, the stage wait, the launcher and the
+// operand types are conv_fp8_detail.h's, the format (scale rule, encoder, 24-byte block store) is mx_block.h's MxE2M3.  The kernel's
+// body is written out here and does not use the gather_* frame of conv_fp8_detail.h: with the frame its 64 x 64 instantiation measured
+// 0.2 ... 0.4 us slower per launch at batch 1, with this text its instructions are the earlier kernel's one for one.
 #pragma once
 #include "conv_fp8_detail.h"
 
 namespace ssd {
 
 constexpr int KB6 = 48;      // bytes per tile row: 64 channels = two 24-byte blocks = three 16-byte LDS-DMA units
-
-// the MX scale rule for e2m3: fp32 absmax (>= 0) -> x in -127 ... 127, the smallest power of two with a / 2^x <= 7.5 = 1.875 * 2^2
-__device__ __forceinline__ int mx6_exponent(float amax) {
-    const unsigned u = __float_as_uint(amax);
-    const int x = (int)(u >> 23) - 127 - 2 + ((u & 0x7FFFFFu) > 0x700000u ? 1 : 0);
-    return x < -127 ? -127 : x > 127 ? 127 : x;
-}
-// a thread's 8 values of a 32-channel block held by 4 adjacent lanes -> the block's exponent; every lane of the four gets it
-__device__ __forceinline__ int mx6_block_exponent(const float (&v)[8]) {
-    float am = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) am = fmaxf(am, fabsf(v[e]));
-    am = fmaxf(am, __shfl_xor(am, 1, 64));
-    am = fmaxf(am, __shfl_xor(am, 2, 64));
-    return mx6_exponent(am);
-}
-// one value -> its e2m3 code in plain arithmetic: clamp to 7.5, round to nearest even on the grid (step 1/8 below 2, 1/4 below 4, 1/2
-// above; the subnormals share the first binade's step), the sign bit is the input's.  (tools/probes/mxfp6_probe.hip reports what
-// v_cvt_scalef32_2xpk16_fp6_f32 does; nothing here depends on it.)
-__device__ __forceinline__ unsigned enc_e2m3(float v) {
-    const float a = fminf(fabsf(v), 7.5f);
-    const unsigned c = a < 2.f ? (unsigned)rintf(a * 8.f) : a < 4.f ? 8u + (unsigned)rintf(a * 4.f) : 16u + (unsigned)rintf(a * 2.f);
-    return c | ((__float_as_uint(v) >> 31) << 5);
-}
-// a code's value, by the format's definition (exact)
-__device__ __forceinline__ float dec_e2m3(unsigned c) {
-    const unsigned e = (c >> 3) & 3u, m = c & 7u;
-    const float a = e ? __uint_as_float(((e + 126u) << 23) | (m << 20)) : (float)m * 0.125f;
-    return (c & 32u) ? -a : a;
-}
-// 8 values at block exponent x -> 8 codes = 48 bits, value e in bits 6 e ... 6 e + 5
-__device__ __forceinline__ unsigned long long mx6_pack8(const float (&v)[8], int x) {
-    unsigned long long w = 0;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) w |= (unsigned long long)enc_e2m3(ldexpf(v[e], -x)) << (6 * e);
-    return w;
-}
-// The block's four lanes q = 0 ... 3 (adjacent, all active) hold 48 bits each; the 24-byte string is written by lanes 0 ... 2 as three
-// 8-byte stores: lane q's store is bits 64 q ... 64 q + 63 = its own bits from 16 q on and the next lane's first 16 (q + 1) bits.
-__device__ __forceinline__ void mx6_store_block(unsigned char* blk, unsigned long long mine, int q) {
-    const unsigned nlo = (unsigned)__shfl_down((int)(unsigned)mine, 1, 64), nhi = (unsigned)__shfl_down((int)(unsigned)(mine >> 32), 1, 64);
-    const unsigned long long next = ((unsigned long long)nhi << 32) | nlo;
-    if (q < 3) {
-        const unsigned long long out = (mine >> (16 * q)) | (next << (48 - 16 * q));
-        *reinterpret_cast<u32x2*>(blk + 8 * q) = u32x2{(unsigned)out, (unsigned)(out >> 32)};
-    }
-}
 
 // =================================================================================
 // The kernel: conv_fp8_detail.h's gather convolution restated for e2m3 operands with E8M0 block scales on BOTH operands
@@ -273,7 +228,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_fwd_mxfp6_kernel(GatherArgs
     int st_c = 0, st_i = NS - 1;
     for (int k = 0; k < nk; ++k) {
         const int later = nk - 1 - k;
-        wait_tiles_and_sync8<L_N, (NS - 2 > 4 ? 4 : NS - 2)>(later < NS - 2 ? later : NS - 2);      // tile k visible; stage st_i is free
+        wait_tiles_and_sync<L_N, (NS - 2 > 4 ? 4 : NS - 2)>(later < NS - 2 ? later : NS - 2);      // tile k visible; stage st_i is free
         if (k + NS - 1 < nk) issue_next(st_i);
         compute(st_c);
         st_c = st_c + 1 == NS ? 0 : st_c + 1;
@@ -327,29 +282,20 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_fwd_mxfp6_kernel(GatherArgs
                 u32x4{pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
         }
         if (p.mode == FP8_OUT_MX || p.mode == FP8_OUT_BF16_MX) {
-            const int x = mx6_block_exponent(v);
+            const int x = mx_block_exponent<MxE2M3>(v);
             const size_t blk = (size_t)m * (p.DN >> 5) + (n >> 5);
-            mx6_store_block(p.dst8 + blk * 24, mx6_pack8(v, x), cg & 3);
+            MxE2M3::store8(p.dst8, blk, cg & 3, MxE2M3::pack8(v, x));
             if ((cg & 3) == 0) p.dst_sc[blk] = (unsigned char)(x + 127);
         }
     }
 }
 
+// filter columns fastest, as the e4m3 kernel does up to 9 taps (launch_gather)
 template <int WM, int WN, int TM, int TN, int NS>
 static void launch_fwd_mxfp6(GatherArgs6& a, const char* label, double flops, double bytes, hipStream_t s) {
     constexpr int NTHR = 64 * WM * WN, BM = 32 * TM * WM, BN = 32 * TN * WN;
-    constexpr size_t stages = NS * ((size_t)((3 * (BM + BN) + NTHR - 1) / NTHR) * NTHR * 16 + NTHR * 4), ctile = (size_t)BM * (BN + 4) * 4;
-    constexpr size_t lds = stages > ctile ? stages : ctile;
-    static_assert(lds <= 80 * 1024, "LDS: two workgroups per CU");
-    auto kern = conv_fwd_mxfp6_kernel<WM, WN, TM, TN, NS>;
-    static bool once = (set_lds(kern, lds), true);
-    (void)once;
-    const int MT = cdiv(a.M, BM), NT = cdiv(a.DN, BN);
-    a.m_fast = 0;      // filter columns fastest, as the e4m3 kernel does up to 9 taps (launch_fwd_e4m3)
-    a.fast_n = NT;
-    ProfScope prof(label, flops, bytes, s);
-    SSD_LAUNCH_STOP(kern, dim3(MT * NT), dim3(NTHR), lds, s, a);
-    HIP_OK(hipGetLastError());
+    launch_gather<conv_fwd_mxfp6_kernel<WM, WN, TM, TN, NS>, NTHR, BM, BN, NS * ((size_t)((3 * (BM + BN) + NTHR - 1) / NTHR) * NTHR * 16 + NTHR * 4)>(
+        a, false, label, flops, bytes, s);
 }
 
 }  // namespace ssd

@@ -59,6 +59,20 @@ def test_quantize_bit_exact(x_f32, c):
     assert f8.decode(got8).reshape(rows, c // 32, 32)[1:].__abs__().max(-1).min() >= 224.0      # every block uses its range
 
 
+def test_quantize_bit_exact_second_sweep():
+    """the grid is capped at 8192 workgroups of 256 threads: n8 = 2 097 280 is 128 threads' work past one sweep of the grid-stride
+    loop.  The last 1024 rows straddle the end of the first sweep at row 262 144."""
+    rng = np.random.default_rng(97)
+    rows, c = 262160, 64
+    assert rows * c // 8 == 8192 * 256 + 128
+    v = rng.standard_normal((rows, c), np.float32) * np.exp2(rng.integers(-20, 21, (rows, c // 32))).astype(np.float32).repeat(32, 1)
+    got8, gots = gpu_quantize(v, True)
+    for sl in (slice(0, 1024), slice(rows - 1024, rows)):
+        want8, wants = mx.quantize(v[sl])
+        assert np.array_equal(gots[sl], wants), np.argwhere(gots[sl] != wants)[:8]
+        assert np.array_equal(got8[sl], want8), np.argwhere(got8[sl] != want8)[:8]
+
+
 def test_quantize_refuses_c24():
     x_ = dev(np.ones((4, 24), np.float32))
     y_, s_ = u8((96,)), u8((8,))
