@@ -39,6 +39,32 @@ sz = C.c_size_t
 cstr = C.c_char_p
 handle = C.c_void_p
 
+
+
+class TailStage(C.Structure):
+    """ssd_tail_stage: one stage of a tail-chain launch"""
+    _fields_ = [(n, C.c_int) for n in ('hi', 'wi', 'ci', 'ho', 'wo', 'co', 'kh', 'kw', 'stride', 'dil', 'pad_h', 'pad_w',
+                                       'dgrad', 'relu', 'accum', 'out_f32')] + \
+               [(n, C.c_void_p) for n in ('src', 'wgt', 'bias', 'mask', 'dst')]
+
+
+TAIL_ZERO_BYTES, TAIL_LDS_MAX, TAIL_MAX_TASKS = 2560, 160 * 1024, 64      # SSD_TAIL_* of the header
+TF_RELU, TF_ACCUM, TF_OUT_F32, TF_LOAD_IN, TF_LOAD_OUT, TF_KTAIL = 1, 2, 4, 8, 16, 32
+
+
+class TailPlanStage(C.Structure):
+    """ssd_tail_plan_stage: what the host plans for one stage"""
+    _fields_ = [(n, C.c_int) for n in ('flags', 'ntask', 'tiles', 'ksplit', 'ngroups', 'gpt', 'in_off', 'in_bytes', 'out_off',
+                                       'out_bytes', 'scratch_off', 'scratch_bytes')] + \
+               [('tasks', (C.c_uint * 2) * TAIL_MAX_TASKS)]
+
+
+class WgradItem(C.Structure):
+    """ssd_wgrad_item: one layer of a grouped weight-gradient launch"""
+    _fields_ = [(n, C.c_int) for n in ('hi', 'wi', 'ci', 'ho', 'wo', 'co', 'kh', 'kw', 'stride', 'dil', 'pad_h', 'pad_w')] + \
+               [(n, C.c_void_p) for n in ('x', 'dy', 'dw', 'dbias', 'w')]
+
+
 # name -> (restype, argtypes); every symbol include/ssdvgg_hip.h declares
 SIGNATURES = {
     'ssd_last_error': (cstr, []),
@@ -186,6 +212,9 @@ SIGNATURES = {
     'ssd_op_conv2d_fwd_bf16_chain': (i32, [vp, vp, vp, vp, i32] + [i32] * 14 + [vp]),
     'ssd_op_conv2d_dgrad_bf16_chain': (i32, [vp, vp, vp, vp, i32] + [i32] * 13 + [vp]),
     'ssd_op_conv2d_wgrad_bf16_direct': (i32, [vp, vp, vp, vp, vp, f32] + [i32] * 13 + [vp]),
+    'ssd_op_tail_chain_plan': (i32, [C.POINTER(TailStage), i32, C.POINTER(TailPlanStage), p_i32]),
+    'ssd_op_tail_chain_bf16': (i32, [C.POINTER(TailStage), i32, i32, vp]),
+    'ssd_op_conv2d_wgrad_group_bf16': (i32, [C.POINTER(WgradItem), i32, f32, i32, vp]),
     'ssd_op_conv2d_wgrad_bf16_ws_floats': (sz, [i32] * 13),
     'ssd_op_conv2d_wgrad_bf16': (i32, [vp, vp, vp, vp, vp, f32, vp] + [i32] * 13 + [vp]),
     'ssd_op_conv2d_first_fwd_bf16': (i32, [vp, vp, vp, vp] + [i32] * 14 + [vp]),

@@ -1549,6 +1549,77 @@ int ssd_op_conv2d_wgrad_bf16_direct(const void* x, const void* dy, float* dw, fl
     conv_wgrad_group_bf16(&it, 1, weight_decay, (hipStream_t)stream);
     API_END
 }
+// several stages / layers per launch, as the step issues them (the plan alone: host only)
+static_assert(SSD_TAIL_ZERO_BYTES == TAIL_ZERO_BYTES && SSD_TAIL_LDS_MAX == TAIL_LDS_MAX && SSD_TAIL_MAX_TASKS == TAIL_PLAN_MAX_TASKS, "ssdvgg_hip.h");
+static_assert(SSD_TF_RELU == TF_RELU && SSD_TF_ACCUM == TF_ACCUM && SSD_TF_OUT_F32 == TF_OUT_F32 && SSD_TF_LOAD_IN == TF_LOAD_IN &&
+              SSD_TF_LOAD_OUT == TF_LOAD_OUT && SSD_TF_KTAIL == TF_KTAIL, "ssdvgg_hip.h");
+static_assert(sizeof(ssd_tail_plan_stage) == sizeof(TailPlanStage), "ssd_tail_plan_stage is TailPlanStage");
+static std::vector<TailStage> tail_stages_of(const ssd_tail_stage* stages, int nstages) {
+    SSD_REQUIRE(stages != nullptr && nstages >= 1 && nstages <= 4096, "tail chain: no stage list (%d stages)", nstages);
+    std::vector<TailStage> st(nstages);
+    for (int i = 0; i < nstages; ++i) {
+        const ssd_tail_stage& a = stages[i];
+        TailStage& t = st[i];
+        t = TailStage{};
+        t.d = mk(1, a.hi, a.wi, a.ci, a.ho, a.wo, a.co, a.kh, a.kw, a.stride, a.dil, a.pad_h, a.pad_w);
+        t.dgrad = a.dgrad != 0; t.src = a.src; t.wgt_packed = a.wgt; t.bias = a.bias; t.mask = a.mask; t.dst = a.dst;
+        t.relu = a.relu != 0; t.accum = a.accum != 0; t.out_f32 = a.out_f32 != 0;
+    }
+    return st;
+}
+int ssd_op_tail_chain_plan(const ssd_tail_stage* stages, int nstages, ssd_tail_plan_stage* plan_out, int* lds_total_out) {
+    API_BEGIN
+    SSD_REQUIRE(plan_out != nullptr && lds_total_out != nullptr, "tail chain plan: null output");
+    std::vector<TailStage> st = tail_stages_of(stages, nstages);
+    static const char key = 0;
+    for (TailStage& t : st)
+        if (!t.wgt_packed) t.wgt_packed = &key;      // (a filter is no key of the plan)
+    std::vector<TailPlanStage> plan(nstages);
+    tail_chain_plan(st.data(), nstages, plan.data(), lds_total_out);
+    memcpy(plan_out, plan.data(), (size_t)nstages * sizeof(TailPlanStage));
+    API_END
+}
+int ssd_op_tail_chain_bf16(const ssd_tail_stage* stages, int nstages, int b, void* stream) {
+    API_BEGIN
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<TailStage> st = tail_stages_of(stages, nstages);
+    for (int i = 0; i < nstages; ++i)
+        SSD_REQUIRE(st[i].wgt_packed != nullptr && st[i].src != nullptr && st[i].dst != nullptr, "tail chain: stage %d has a null tensor", i);
+    {   // a list the chain refuses is refused before the pack launch reads a filter by its shape
+        std::vector<TailPlanStage> plan(nstages);
+        int lds_total = 0;
+        tail_chain_plan(st.data(), nstages, plan.data(), &lds_total);
+    }
+    int device = 0;
+    HIP_OK(hipGetDevice(&device));
+    HipOwner tmp(device);
+    TailTables tables{tmp, {}};
+    std::vector<TailPackItem> items(nstages);
+    size_t total = 0;      // (one image of all packed filters, back to back: the step's wq_tail_)
+    for (int i = 0; i < nstages; ++i) total += tail_chain_packed_elems(st[i].d, st[i].dgrad);
+    char* store = static_cast<char*>(tmp.mem(total * 2));
+    for (int i = 0; i < nstages; ++i) {
+        items[i] = TailPackItem{st[i].d, st[i].dgrad, st[i].wgt_packed, store};
+        st[i].wgt_packed = store;
+        store += tail_chain_packed_elems(st[i].d, st[i].dgrad) * 2;
+    }
+    tail_chain_pack_filters(items.data(), nstages, s);
+    tail_chain_bf16(st.data(), nstages, b, st[0].dgrad ? "tail_dgrad_bf16" : "tail_fwd_bf16", s, tables);
+    HIP_OK(hipStreamSynchronize(s));
+    API_END
+}
+int ssd_op_conv2d_wgrad_group_bf16(const ssd_wgrad_item* items, int n, float weight_decay, int b, void* stream) {
+    API_BEGIN
+    SSD_REQUIRE(items != nullptr && n >= 1 && n <= 4096, "grouped weight gradient: no layer list (%d layers)", n);
+    std::vector<WgradGroupItem> v(n);
+    for (int i = 0; i < n; ++i) {
+        const ssd_wgrad_item& a = items[i];
+        v[i].d = mk(b, a.hi, a.wi, a.ci, a.ho, a.wo, a.co, a.kh, a.kw, a.stride, a.dil, a.pad_h, a.pad_w);
+        v[i].x = (const bf16_t*)a.x; v[i].dy = (const bf16_t*)a.dy; v[i].dw = a.dw; v[i].dbias = a.dbias; v[i].w = a.w;
+    }
+    conv_wgrad_group_bf16(v.data(), n, weight_decay, (hipStream_t)stream);
+    API_END
+}
 int ssd_op_conv2d_first_fwd_bf16(const float* x, const float* w, const float* bias, void* y, int b, int hi, int wi, int ci, int ho,
                                  int wo, int co, int kh, int kw, int stride, int dil, int pad_h, int pad_w, int relu,
                                  void* stream) {

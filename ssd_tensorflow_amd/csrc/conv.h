@@ -198,6 +198,22 @@ struct TailTables {
     std::vector<std::pair<std::vector<char>, const void*>> uploaded;
 };
 void tail_chain_bf16(const TailStage* stages, int nstages, int nimg, const char* label, hipStream_t s, TailTables& tables);
+// The plan tail_chain_bf16 launches, as the host computes it (no HIP call; the stages' pointers are only keys: which stage's output
+// is which stage's input).  All offsets and sizes are bytes of the workgroup's LDS: [0, TAIL_ZERO_BYTES) is the zero row, a feature
+// map's region holds its pixel rows at a pitch of channels * 2 + 16 plus 256 bytes.  Throws what tail_chain_bf16 would.
+constexpr int TAIL_ZERO_BYTES = 2560;        // the zero row: covers the widest pixel row (1024 channels) plus a group's immediates
+constexpr int TAIL_LDS_MAX = 160 * 1024;
+constexpr int TAIL_PLAN_MAX_TASKS = 64;
+enum { TF_RELU = 1, TF_ACCUM = 2, TF_OUT_F32 = 4, TF_LOAD_IN = 8, TF_LOAD_OUT = 16, TF_KTAIL = 32 };
+struct TailPlanStage {
+    int flags;                              // TF_*
+    int ntask, tiles, ksplit, ngroups, GPT; // ntask = tiles * ksplit; ngroups = taps * GPT groups of 4 k steps of 32 channels
+    int in_off, in_bytes;                   // the gathered tensor's region
+    int out_off, out_bytes;                 // the output's region (-1, 0: not kept in LDS)
+    int scratch_off, scratch_bytes;         // the k-split partial sums
+    unsigned tasks[TAIL_PLAN_MAX_TASKS][2]; // [0] = nb | mg << 8 | ks << 16 | nmb << 24,  [1] = g0 | g1 << 16
+};
+void tail_chain_plan(const TailStage* stages, int nstages, TailPlanStage* out, int* lds_total);
 // the weight gradients of several small layers in ONE launch, each with a single pixel split and the direct epilogue
 // (dw = x^T dy + weight_decay * w, dbias = column sums of dy): no slabs, no reduce launches
 struct WgradGroupItem {

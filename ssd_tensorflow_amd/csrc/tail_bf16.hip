@@ -23,7 +23,7 @@
 //   * The ACTIVATIONS never leave LDS between stages: a stage's input feature map (at most 100 pixels) sits in LDS with a padded
 //     pixel pitch (conflict-free ds_read_b128), its epilogue writes the output to global memory (backward and the tests read it)
 //     AND into the LDS region the next stage gathers from; a tap outside the image reads a zero row.  The host plans the regions
-//     by liveness (tail_chain_bf16).
+//     by liveness (plan_chain).
 //
 // Same arithmetic as the per-layer kernels: bf16 operands, fp32 accumulation, bias + relu (forward) or accumulate + relu mask
 // (data gradient) in fp32, ONE rounding to bf16 (heads: fp32 out).  The summation order differs from theirs (k in ascending
@@ -50,9 +50,8 @@ constexpr int TAIL_MAX_STAGES = 16;
 constexpr int TAIL_WAVES = 16, TAIL_THREADS = 64 * TAIL_WAVES;
 constexpr int TAIL_MG = 4;                   // blocks of 16 pixels per task
 constexpr int TAIL_MAX_TASKS = 64;           // tasks per stage (four rounds of the 16 waves)
-constexpr int TAIL_ZERO_BYTES = 2560;        // the zero row: covers the widest pixel row (1024 channels) plus a group's immediates
-constexpr int TAIL_LDS_MAX = 160 * 1024;
-enum { TF_RELU = 1, TF_ACCUM = 2, TF_OUT_F32 = 4, TF_LOAD_IN = 8, TF_LOAD_OUT = 16, TF_KTAIL = 32 };
+// (TAIL_ZERO_BYTES, TAIL_LDS_MAX and the TF_* flags: conv.h -- the plan is also handed to the tests)
+static_assert(TAIL_MAX_TASKS == TAIL_PLAN_MAX_TASKS, "conv.h TailPlanStage carries a stage's task words");
 
 // One stage of the chain as the kernel reads it: a table in DEVICE memory (read with scalar loads through a constant-address-space
 // pointer), built by tail_chain_bf16 and kept in the caller's TailTables.  Everything a wave would otherwise compute with integer divisions -- its task, its
@@ -507,12 +506,13 @@ bool tail_chain_stage_supported(const ConvDesc& d) {
            cdiv(d.Co, 16) * cdiv(cdiv(Mo, 16), TAIL_MG) <= TAIL_MAX_TASKS && cdiv(d.Ci, 16) * cdiv(cdiv(Mi, 16), TAIL_MG) <= TAIL_MAX_TASKS;
 }
 
-void tail_chain_bf16(const TailStage* stages, int nstages, int nimg, const char* label, hipStream_t s, TailTables& tables) {
+// The PLAN of a chain: per-stage geometry, tasks, the LDS regions and the k-split scratch.  Host only -- no HIP call; pointers are
+// read as keys (which stage's output is which stage's input) and copied into the table.  Fills tab (nstages entries, padding bytes zero) and
+// the launch's dynamic LDS size.  tail_chain_bf16 uploads and launches it; tail_chain_plan hands it to the tests.
+static void plan_chain(const TailStage* stages, int nstages, std::vector<TailStageK>& tab, int* lds_total_out) {
     SSD_REQUIRE(nstages >= 1 && nstages <= TAIL_MAX_STAGES, "tail chain: 1..%d stages (got %d)", TAIL_MAX_STAGES, nstages);
-    SSD_REQUIRE(nimg >= 1, "tail chain: no images");
-    std::vector<TailStageK> tab(nstages);
+    tab.resize(nstages);
     memset(tab.data(), 0, nstages * sizeof(TailStageK));
-    double flops = 0.0, bytes = 0.0;
     // ---- per-stage geometry
     for (int i = 0; i < nstages; ++i) {
         const TailStage& t = stages[i];
@@ -574,9 +574,6 @@ void tail_chain_bf16(const TailStage* stages, int nstages, int nimg, const char*
             k.tasks[task][0] = (unsigned)nb | ((unsigned)mg << 8) | ((unsigned)ks << 16) | ((unsigned)nmb << 24);
             k.tasks[task][1] = (unsigned)g0 | ((unsigned)g1 << 16);
         }
-        d.B = nimg;
-        flops += conv_flops(d);
-        bytes += 2.0 * conv_elems(d);
     }
     // ---- LDS plan.  A tensor (keyed by its pointer) lives in LDS from the stage that loads / produces it to the last stage that
     // gathers from it or accumulates into it; regions are placed first-fit above the zero row, a stage's k-split scratch above
@@ -639,6 +636,9 @@ void tail_chain_bf16(const TailStage* stages, int nstages, int nimg, const char*
         const Region* in = find(stages[i].src);
         k.in_off = in->off; k.in_pitch = k.SC * 2 + 16;
         const Region* out = stages[i].out_f32 ? nullptr : find(stages[i].dst);
+        // (a region found by pointer may be a DEAD one: a stage may write, in global memory only, over a tensor whose last reader has
+        // run -- the launch's own input, say -- and that region's bytes belong to another tensor by now)
+        if (out && !(out->first <= i && i <= out->last)) out = nullptr;
         k.out_off = out ? out->off : -1; k.out_pitch = k.DN * 2 + 16;
         int top = TAIL_ZERO_BYTES;
         for (const Region& r : regs)
@@ -648,6 +648,37 @@ void tail_chain_bf16(const TailStage* stages, int nstages, int nimg, const char*
         lds_total = std::max(lds_total, k.scratch_off + scratch);
     }
     SSD_REQUIRE(lds_total <= TAIL_LDS_MAX, "tail chain: the stages' feature maps need %d bytes of LDS (limit %d)", lds_total, TAIL_LDS_MAX);
+    *lds_total_out = lds_total;
+}
+
+void tail_chain_plan(const TailStage* stages, int nstages, TailPlanStage* out, int* lds_total) {
+    std::vector<TailStageK> tab;
+    plan_chain(stages, nstages, tab, lds_total);
+    for (int i = 0; i < nstages; ++i) {
+        const TailStageK& k = tab[i];
+        TailPlanStage& o = out[i];
+        memset(&o, 0, sizeof o);
+        o.flags = k.flags; o.ntask = k.ntask; o.tiles = k.tiles; o.ksplit = k.ksplit; o.ngroups = k.ngroups; o.GPT = k.GPT;
+        // (the extents as the planner reserves them: pixel rows at the padded pitch + 256 bytes for a group's immediates)
+        o.in_off = k.in_off; o.in_bytes = k.SH * k.SW * k.in_pitch + 256;
+        o.out_off = k.out_off; o.out_bytes = k.out_off >= 0 ? k.DH * k.DW * k.out_pitch + 256 : 0;
+        o.scratch_off = k.scratch_off; o.scratch_bytes = (k.ksplit - 1) * k.tiles * TAIL_MG * 256 * 4;
+        memcpy(o.tasks, k.tasks, sizeof o.tasks);
+    }
+}
+
+void tail_chain_bf16(const TailStage* stages, int nstages, int nimg, const char* label, hipStream_t s, TailTables& tables) {
+    SSD_REQUIRE(nimg >= 1, "tail chain: no images");
+    std::vector<TailStageK> tab;
+    int lds_total = 0;
+    plan_chain(stages, nstages, tab, &lds_total);
+    double flops = 0.0, bytes = 0.0;
+    for (int i = 0; i < nstages; ++i) {
+        ConvDesc d = stages[i].d;
+        d.B = nimg;
+        flops += conv_flops(d);
+        bytes += 2.0 * conv_elems(d);
+    }
     const TailStageK* tab_dev = upload_table(tables, tab);
     static bool once = (set_lds(tail_chain_bf16_kernel, TAIL_LDS_MAX), true);
     (void)once;

@@ -7,6 +7,9 @@ the maps they produce (ssdvgg.py:353-365).  Three things are checked:
   * the whole step with the chain (default) against the same handle configuration with SSD_TAIL_FUSE=0 (the per-layer launches):
     another summation order of the same bf16 products, so activations agree to a bf16 rounding and the fp32 results to 1e-3;
   * which launches the step makes (the profiler's labels): the chain's layers must not appear as launches of their own.
+The "-live" cases of the whole-step test run a batch whose boxes give every map a positive anchor: on the synthetic batches the 1x1
+and 3x3 maps often carry no gradient at all, and the deep end of the backward chain is then compared as 0 == 0 only.
+(Several stages per launch against the same stages one per launch, bit for bit: test_gpu_tail_chain.py.)
 The layer-local oracle tests of the step (test_gpu_bf16.py, test_gpu_bench_config.py) run with the chain on: it is the default."""
 import ctypes as C
 
@@ -18,6 +21,7 @@ from oracle import boxes as ob
 from oracle import ssdvgg_ref as ref
 from gpu_util import lib, check, max_rel, rel_err
 from test_gpu_bf16 import conv_case_check
+from tail_cases import live_boxes, positives_per_map
 from ssd_tensorflow_amd.ssdvgg import SSDVGG, Session
 
 pytestmark = pytest.mark.gpu
@@ -72,12 +76,27 @@ def _step(pname, b, fuse, monkeypatch, x, y, w):
     return out
 
 
-@pytest.mark.parametrize('pname,b', [('vgg300', 3), ('vgg512', 2), ('vgg300', 32)])
-def test_step_with_the_chain_agrees_with_the_per_layer_launches(pname, b, monkeypatch):
+def live_batch(rng, b, preset):
+    """a batch whose ground truth gives EVERY map a positive anchor (tail_cases.live_boxes: one box of each map's own scale), so that a
+    gradient flows back through every stage of the backward chain; the precondition is asserted on the label oracle's vectors"""
+    g, c = live_boxes(preset)
+    vec = ob.encode_labels(g, c, preset, 20)
+    pos = positives_per_map(vec, preset)
+    assert min(pos) >= 1, f'a map without a positive anchor: {pos}'
+    return ref.synth_images(rng, b, preset), np.stack([vec] * b)
+
+
+@pytest.mark.parametrize('pname,b,live', [pytest.param('vgg300', 3, False, id='vgg300-3'), pytest.param('vgg512', 2, False, id='vgg512-2'),
+                                          pytest.param('vgg300', 32, False, id='vgg300-32'), pytest.param('vgg300', 3, True, id='vgg300-3-live'),
+                                          pytest.param('vgg512', 2, True, id='vgg512-2-live')])
+def test_step_with_the_chain_agrees_with_the_per_layer_launches(pname, b, live, monkeypatch):
     preset = ob.get_preset(pname)
     w = ref.init_params(preset, 20, seed=42, alive=True)
     rng = np.random.default_rng(77)
-    x, y, _ = ref.synth_batch(rng, b, preset)
+    if live:
+        x, y = live_batch(rng, b, preset)
+    else:
+        x, y, _ = ref.synth_batch(rng, b, preset)
     plain = _step(pname, b, '0', monkeypatch, x, y, w)
     fused = _step(pname, b, '3', monkeypatch, x, y, w)
     # which launches: the chain's layers (vgg300: conv9_1 on, vgg512: conv10_1 on) are launches of their own only without it
@@ -104,6 +123,8 @@ def test_step_with_the_chain_agrees_with_the_per_layer_launches(pname, b, monkey
             worst_a = max(worst_a, e)
     print(f'    chain vs per-layer launches: activations max-rel {worst_a:.2e}, data gradients {worst_g:.2e}; without gradient: {dead}')
     assert len(dead) <= 4 and 'grad:conv9_1' not in dead and 'grad:conv10_1' not in dead
+    if live:
+        assert not dead, f'every map has a positive anchor, yet nothing flows back into {dead}'
     assert worst_a < 8e-3 and worst_g < 1.6e-2          # a bf16 rounding here and there that falls the other way (2^-8 of the value), carried through a layer or two
     assert max_rel(fused['result'], plain['result']) < 4e-3      # (softmax of head outputs computed from activations one bf16 rounding apart)
     for k in plain['losses']:
