@@ -193,6 +193,7 @@ SIGNATURES = {
     'ssd_detout_tiles_merge_dev': (i32, [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     'ssd_detout_tiles': (i32, [cstr, i32, i32, vp, vp, i32, i32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     'ssd_set_overlap': (i32, [handle, i32]),
+    'ssd_set_wino_dual': (i32, [handle, i32]),
     'ssd_profile_enable': (i32, [handle, i32]),
     'ssd_profile_report': (i32, [handle, C.c_char_p, sz]),
     'ssd_activation_shape': (i32, [handle, cstr, p_i32, p_i32, p_i32]),
@@ -206,6 +207,8 @@ SIGNATURES = {
     'ssd_op_conv2d_wino_fwd': (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32] + [i32] * 14 + [vp]),
     'ssd_op_conv2d_wino_dgrad': (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, i32] + [i32] * 13 + [vp]),
     'ssd_op_conv2d_wino_wgrad': (i32, [vp, vp, vp, vp, vp, f32, vp, i32] + [i32] * 13 + [vp]),
+    'ssd_op_wino_bwd_transform': (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    'ssd_op_wino_filter_flip_plan': (i32, [vp, vp, vp, vp, i32, i32, vp]),
     'ssd_op_cast_filter': (i32, [vp, vp, vp, i32, i32, i32, vp]),
     'ssd_op_conv2d_fwd_bf16': (i32, [vp, vp, vp, vp, i32] + [i32] * 14 + [vp]),
     'ssd_op_conv2d_dgrad_bf16': (i32, [vp, vp, vp, vp, i32] + [i32] * 13 + [vp]),

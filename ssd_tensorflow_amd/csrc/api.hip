@@ -1402,6 +1402,12 @@ int ssd_set_overlap(ssd_handle h, int on) {
     API_END
 }
 
+int ssd_set_wino_dual(ssd_handle h, int on) {
+    API_BEGIN_NET(h)
+    n.set_wino_dual(on);
+    API_END
+}
+
 int ssd_profile_enable(ssd_handle h, int on) {
     API_BEGIN_NET(h)
     n.profiler().on = on != 0;
@@ -1706,6 +1712,21 @@ int ssd_op_conv2d_wino_wgrad(const float* x, const float* dy, float* dw, float* 
     }
     wino_bwd_transform(d, dy, nullptr, k.Ya, (hipStream_t)stream, (flags & 8) != 0);
     wino_wgrad(d, k.V, vps, k.Ya, dw, dbias, w, weight_decay, k.slabs, (hipStream_t)stream, (flags & 8) != 0);
+    API_END
+}
+int ssd_op_wino_bwd_transform(const float* dy, float* Yt, float* Ya, int b, int h, int w, int co, int dil, int flags, void* stream) {
+    API_BEGIN
+    const ConvDesc d = mk(b, h, w, 32, h, w, co, 3, 3, 1, dil, dil, dil);      // (the transforms know nothing of the layer's input: any valid Ci)
+    SSD_REQUIRE(wino_applicable(d), "winograd: 3x3 / stride 1 / SAME layers (any dilation), Ci in multiples of 32, Co of 4");
+    SSD_REQUIRE(Yt && Ya, "ssd_op_wino_bwd_transform: both outputs are required");
+    wino_bwd_transform(d, dy, Yt, Ya, (hipStream_t)stream, (flags & 8) != 0, (flags & 16) != 0);
+    API_END
+}
+int ssd_op_wino_filter_flip_plan(const float* const* w, float* const* Uf, const int* ci, const int* co, int n, int flags, void* stream) {
+    API_BEGIN
+    WinoFilterPlan plan;
+    for (int i = 0; i < n; ++i) plan.add(w[i], nullptr, Uf[i], ci[i], co[i]);
+    wino_filter_plan(plan, false, true, (hipStream_t)stream, (flags & 1) != 0);
     API_END
 }
 size_t ssd_op_conv2d_wgrad_ws_floats(int b, int hi, int wi, int ci, int ho, int wo, int co, int kh, int kw, int stride,

@@ -67,12 +67,14 @@ struct WinoFilterPlan {
         const float* w;
         float *U, *Uf;
         int Ci, Co, Cop, blk0;
+        int tblk0;      // the flipped transform's first workgroup: one per 32 ci x 32 co tile
     } it[MAX];
-    int n = 0, blocks = 0;
+    int n = 0, blocks = 0, tblocks = 0;
     double elems = 0;
     void add(const float* w, float* U, float* Uf, int Ci, int Co);
 };
-void wino_filter_plan(const WinoFilterPlan& plan, bool forward, bool flipped, hipStream_t s);
+// flip_lanes_ci: the flipped transform as the kernel with lanes along ci and no LDS staging (the same bits; also SSD_WINO_FILTER_LDS=0)
+void wino_filter_plan(const WinoFilterPlan& plan, bool forward, bool flipped, hipStream_t s, bool flip_lanes_ci = false);
 size_t wino_fwd_ws_floats(const ConvDesc& d);              // Mws: 36 * tiles * Co
 // y = relu?(conv(x) + bias); V [36][.][Ci] receives the input's transform (kept by a training step for wino_wgrad).  y_pool != nullptr:
 // the fused 2x2 pool of conv_fwd_pool instead of y (same values, same record).
@@ -84,7 +86,8 @@ void wino_fwd(const ConvDesc& d, const float* x, const float* U, const float* bi
               float* Mws, float* y_pool, void* pool_rec, hipStream_t s, void* relu_bits = nullptr, bool two_launch = false,
               bool ref_geom = false);
 // dy -> Yt (B^T dy B, the data gradient's operand) and / or Ya (A dy A^T, the weight gradient's), each [36][tiles][wino_kpad(Co)]; nullptr skips one
-void wino_bwd_transform(const ConvDesc& d, const float* dy, float* Yt, float* Ya, hipStream_t s, bool ref_geom = false);
+// Both: one kernel that reads dy once (the same bits as the two single forms); two_launch or SSD_WINO_DUAL=0: the two single launches
+void wino_bwd_transform(const ConvDesc& d, const float* dy, float* Yt, float* Ya, hipStream_t s, bool ref_geom = false, bool two_launch = false);
 size_t wino_dgrad_ws_floats(const ConvDesc& d);            // Xws: 36 * tiles * Ci
 // conv_dgrad's semantics (mask, accumulate) from the transformed dy; unpool_rec != nullptr: conv_dgrad_unpool's
 void wino_dgrad(const ConvDesc& d, const float* Yt, const float* Uflip, float* dx, const float* mask, bool accumulate, float* Xws,

@@ -187,6 +187,7 @@ public:
     long long global_step = 0;
     Profiler& profiler() { return prof_; }
     void set_overlap(bool on) { overlap_ = on; }
+    void set_wino_dual(int mode) { wino_dual_ = mode; }      // backward transforms a Winograd layer's dy once for both gradients (backward_step)
 
 private:
     int add_tensor(const std::string& name, int H, int W, int C, bool relu_out);
@@ -256,9 +257,11 @@ private:
     bool fuse_first_wgrad_ = false;      // bf16: conv1_1's weight gradient inside conv1_2's data gradient where the kernel applies (plan_pool_fusion)
     bool bw_first_fused_ = false;        // ... and this backward pass took it
     int fused_first_out_ = -1;           // the tensor whose gradient that pass did not materialise (conv1_1's output)
-    void launch_wgrad(int op_index, int b, hipStream_t ws);
+    // ya: the layer's transformed dy where the main stream's dual transform has already written it (backward_step), else nullptr
+    void launch_wgrad(int op_index, int b, hipStream_t ws, const float* ya = nullptr);
     // the data gradient of one convolution into dst (= in, or the input of the pool `up` it un-pools), on ds
-    void launch_dgrad(const Op& op, const ConvDesc& d, const Op* up, Tensor& dst, bool mask, int cls, hipStream_t ds);
+    // (yt_done: wino_yt_ already holds this layer's transformed dy)
+    void launch_dgrad(const Op& op, const ConvDesc& d, const Op* up, Tensor& dst, bool mask, int cls, hipStream_t ds, bool yt_done = false);
     // Round 6 (bf16): the latency-bound tail as one launch per direction (conv.h TailStage; net.hip plan_tail_chain).  chain_first_ =
     // op index of the first 1x1 layer below the 10x10 map (vgg300: conv9_1, vgg512: conv10_1), -1: off; in_chain_[op] marks the
     // extra layers from there on and the multibox heads that read them.
@@ -271,7 +274,11 @@ private:
     void plan_tail_chain();
     // Round 6 (fp32): Winograd layers.  Scratch shared by every such layer: the GEMM results of a forward lane (wino_m_), the
     // transformed dy / dx of the data gradient (main stream: wino_yt_, wino_xw_), the transformed dy and the slabs of the weight
-    // gradient (weight-gradient stream: wino_ya_, wino_slab_).  One stream runs each kind in order, so one buffer per kind suffices.
+    // gradient (weight-gradient stream: wino_ya_, wino_slab_).  One stream runs each kind in order, so one buffer per kind suffices --
+    // but for the transformed dy of the weight gradient where the MAIN stream writes it (wino_dual_: one transform of dy for both
+    // gradients, backward_step): two buffers taken in turn (wino_ya_, wino_ya2_), so that the transform of one layer does not wait for
+    // the weight-gradient stream's GEMM of the layer before.  ev_ya_free_[k]: the last GEMM that read buffer k, recorded on the
+    // weight-gradient stream; the main stream waits for it before it writes the buffer again.
     void plan_winograd();
     long long fwd_serial_ = 0;           // forward passes so far
     WinoFilterPlan wino_plan_, wino_plan_first_, wino_plan_flip_;      // forward transforms of all layers but the first / of the first / flipped ones
@@ -279,6 +286,12 @@ private:
     bool wino_any_f_ = false, wino_any_d_ = false;
     float *wino_m_[3] = {nullptr, nullptr, nullptr}, *wino_vs_[3] = {nullptr, nullptr, nullptr}, *wino_yt_ = nullptr, *wino_xw_ = nullptr, *wino_ya_ = nullptr, *wino_slab_ = nullptr;
     hipEvent_t ev_wino_ = nullptr, ev_wino_first_ = nullptr, ev_wino_flip_ = nullptr;
+    float* wino_ya2_ = nullptr;
+    hipEvent_t ev_ya_free_[2] = {nullptr, nullptr};
+    bool ya_free_set_[2] = {false, false};
+    int ya_turn_ = 0;
+    int wino_dual_ = 1;                  // 0 off, 1 the layers of the shape rule (wino_dual_max_c_), 2 every layer with both gradients in this form
+    int wino_dual_max_c_ = 128;          // the rule: max(Ci, Co) <= this (SSD_WINO_DUAL_MAX_C): where the GEMMs beside the transform are HBM-bound themselves
     // A forward pass (net.hip, "steps"): forward builds the lanes, walks fwd_order_ and joins; the members below do the rest.
     struct Lane {
         hipStream_t s, h;

@@ -567,6 +567,7 @@ void Net::plan_winograd() {
     const int mode = env_i("SSD_WINOGRAD", 15), min_cc = env_i("SSD_WINO_MIN_CC", 4096), head_min_hw = env_i("SSD_WINO_HEAD_MIN_HW", 16);
     if (!(mode & 7)) return;
     size_t m_max = 0, v_max = 0, yt_max = 0, xw_max = 0, slab_max = 0;
+    bool dual_any = false;
     for (Op& op : ops_) {
         if (op.kind != OP_CONV) continue;
         const ConvDesc d = conv_desc(op, Bmax_);
@@ -605,6 +606,7 @@ void Net::plan_winograd() {
         if (op.wino_Uf) wino_plan_flip_.add(params_ + op.w_off, nullptr, op.wino_Uf, d.Ci, d.Co);
         wino_any_f_ |= op.wino_f;
         wino_any_d_ |= op.wino_d;
+        dual_any |= op.wino_d && op.wino_w;
     }
     if (wino_plan_.n + wino_plan_first_.n + wino_plan_flip_.n == 0) return;
     ev_wino_ = hip_.event();
@@ -617,6 +619,12 @@ void Net::plan_winograd() {
         wino_xw_ = (float*)hip_.mem(xw_max * sizeof(float));
         wino_ya_ = (float*)hip_.mem(yt_max * sizeof(float));
         wino_slab_ = (float*)hip_.mem(slab_max * sizeof(float));
+        // a layer with both gradients in this form: its dy is transformed once, on the main stream, into wino_ya_ / wino_ya2_ in turn
+        // (backward_step) -- the second buffer is yt_max floats more (1.66 GB at vgg300 batch 32)
+        if (dual_any) {
+            wino_ya2_ = (float*)hip_.mem(yt_max * sizeof(float));
+            for (hipEvent_t& e : ev_ya_free_) e = hip_.event();
+        }
     }
 }
 
@@ -955,6 +963,8 @@ Net::Net(const char* preset, int num_classes, int max_batch, int device, bool tr
     init_weights(seed);
     const char* ov = getenv("SSD_OVERLAP_WGRAD");
     overlap_ = !(ov && ov[0] == '0');
+    wino_dual_ = env_i("SSD_WINO_DUAL", 1);
+    wino_dual_max_c_ = env_i("SSD_WINO_DUAL_MAX_C", wino_dual_max_c_);
     hstream_ = hip_.stream();      // (a high-priority side stream was measured again in round 5: +-0)
     ev_h_ = hip_.event();
     ev_cast_ = hip_.event();
@@ -1421,7 +1431,7 @@ void Net::forward_loss(FwdPass& p, const float* y, LossSlotGuard& guard) {
 // The data-gradient chain is ONE lane (rounds 2-4 also carried a two-lane form, half batches on two sets of streams:
 // fp32 -0.3 %, bf16 -7 %, profiles/r02_l_ab_bwd_lanes_*.txt -- backward already has the weight-gradient stream filling the
 // data gradients' tails; removed in round 5).
-void Net::launch_wgrad(int op_index, int b, hipStream_t ws) {
+void Net::launch_wgrad(int op_index, int b, hipStream_t ws, const float* ya) {
     const Op& op = ops_[op_index];
     const Tensor& in = tensors_[op.in];
     const Tensor& out = tensors_[op.out];
@@ -1432,9 +1442,14 @@ void Net::launch_wgrad(int op_index, int b, hipStream_t ws) {
     // left that transform (a launch that ran on a stream without Winograd scratch took the direct kernel: the direct weight gradient then)
     if (op.wino_w && op.wino_v_step == fwd_serial_) {
         const size_t tpi = (size_t)wino_tiles(d) / d.B;
-        wino_bwd_transform(d, out.gf(), nullptr, wino_ya_, ws);
-        wino_wgrad(d, op.wino_V, (size_t)b * tpi * d.Ci, wino_ya_, grads_ + op.w_off, grads_ + op.b_off, params_ + op.w_off, wd_,
+        if (!ya) wino_bwd_transform(d, out.gf(), nullptr, wino_ya_, ws);      // (this stream's own transform: into buffer 0)
+        wino_wgrad(d, op.wino_V, (size_t)b * tpi * d.Ci, ya ? ya : wino_ya_, grads_ + op.w_off, grads_ + op.b_off, params_ + op.w_off, wd_,
                    wino_slab_, ws);
+        if (ws != stream_ && wino_ya2_) {      // the buffer is free again behind this GEMM: what the main stream's next write of it waits for
+            const int k = ya == wino_ya2_ ? 1 : 0;
+            HIP_OK(hipEventRecord(ev_ya_free_[k], ws));
+            ya_free_set_[k] = true;
+        }
     } else if (!bf16_) {
         conv_wgrad(d, in.f(), out.gf(), grads_ + op.w_off, grads_ + op.b_off, params_ + op.w_off, wd_, slab, ws);
     } else if (in.data_f32) {   // conv1_1
@@ -1449,11 +1464,11 @@ void Net::launch_wgrad(int op_index, int b, hipStream_t ws) {
 
 // The data gradient of one convolution: into its input's gradient, or -- un-pooling (up) -- through the pool's record into the pool's
 // input gradient (dst); mask: with the relu mask of the input's producer.
-void Net::launch_dgrad(const Op& op, const ConvDesc& d, const Op* up, Tensor& dst, bool mask, int cls, hipStream_t ds) {
+void Net::launch_dgrad(const Op& op, const ConvDesc& d, const Op* up, Tensor& dst, bool mask, int cls, hipStream_t ds, bool yt_done) {
     const Tensor& in = tensors_[op.in];
     const Tensor& out = tensors_[op.out];
     if (op.wino_d && cls == 0) {      // Round 6: the Winograd form (its scratch belongs to the main stream)
-        wino_bwd_transform(d, out.gf(), wino_yt_, nullptr, ds);
+        if (!yt_done) wino_bwd_transform(d, out.gf(), wino_yt_, nullptr, ds);
         wino_dgrad(d, wino_yt_, op.wino_Uf, up ? dst.gf() : in.gf(), mask ? in.f() : nullptr, !up && in.done > 0, wino_xw_,
                    up ? up->pool_rec : nullptr, dst.H, dst.W, ds,
                    op.wino_bits && op.wino_bits_step == fwd_serial_ ? op.wino_bits : nullptr);      // (the forward of THIS step wrote them)
@@ -1485,6 +1500,7 @@ void Net::backward_begin(int b, const float* y) {
     bw_.begin(this);
     bw_first_on_main_ = false;
     bw_first_fused_ = false;
+    ya_turn_ = 1;      // (the first dual transform of the step writes wino_ya2_: wino_ya_ may still be read by a layer that transforms on the weight-gradient stream)
     bw_b_ = b;
 }
 
@@ -1531,7 +1547,29 @@ bool Net::backward_step(size_t min_floats, size_t* off, size_t* count, bool sync
             const bool side = wstream_ && overlap_;
             const bool on_main = side && !need_dx;
             hipStream_t ws = (side && !on_main) ? wstream_ : stream_;
-            if (side && !on_main) {
+            // One transform of dy for both gradients (wino_bwd_transform's dual kernel: dy is read once): where the layer takes the
+            // Winograd form of both, on the main stream, which the data gradient runs on.  The weight-gradient stream then waits for
+            // the transform instead of dy's producer.  Which layers: by shape alone, max(Ci, Co) <= 128 (conv1_2, conv2_x) -- there the GEMMs
+            // that run beside the transform are HBM-bound themselves and the bytes saved shorten the step; on the wider layers the AT
+            // transform hides beside a compute-bound GEMM on the other stream, and moving its writes to the main stream measured
+            // slower (DESIGN.md 4.9 has the rows).  wino_dual_ == 2: every such layer (the bit-identity tests).
+            const bool dual = wino_dual_ && (wino_dual_ == 2 || std::max(d.Ci, d.Co) <= wino_dual_max_c_) && wino_ya2_ && need_dx && cls == 0 &&
+                              op.wino_d && op.wino_w && op.wino_v_step == fwd_serial_;
+            const float* ya = nullptr;
+            if (dual) {
+                bw_need(0, out);
+                float* buf = ya_turn_ ? wino_ya2_ : wino_ya_;
+                // (the GEMM that read this buffer last, two dual layers back on the weight-gradient stream: normally long done)
+                if (side && ya_free_set_[ya_turn_]) HIP_OK(hipStreamWaitEvent(stream_, ev_ya_free_[ya_turn_], 0));
+                wino_bwd_transform(d, out.gf(), wino_yt_, buf, stream_);
+                if (side) {
+                    HIP_OK(hipEventRecord(ev_dy_, stream_));
+                    HIP_OK(hipStreamWaitEvent(wstream_, ev_dy_, 0));
+                    side_used = true;
+                }
+                ya = buf;
+                ya_turn_ ^= 1;
+            } else if (side && !on_main) {
                 // (dy written on the main stream but already waited for by the side stream, and this op lives there: the
                 // side stream is the one that is less far ahead -- a small head's weight gradient need not wait for mod_conv7)
                 if (out.gev && out.gev_set) {
@@ -1547,9 +1585,9 @@ bool Net::backward_step(size_t min_floats, size_t* off, size_t* count, bool sync
                 if (on_main) bw_first_on_main_ = true;
             }
             if (!(bw_first_fused_ && !need_dx))      // (conv1_1's came out of conv1_2's data gradient: below)
-                launch_wgrad(op_index, b, ws);
+                launch_wgrad(op_index, b, ws, ya);
             if (need_dx) {
-                bw_need(cls, out);
+                if (!dual) bw_need(cls, out);
                 // Pool fusion (round 5): when this conv reads a recorded 2x2 pool's output, its data gradient routes every
                 // pooled pixel's dx through the record straight into the four cells of the POOL'S INPUT gradient (relu mask of
                 // that tensor's producer included, from the record's sign bit): the pooled tensor's own gradient is never
@@ -1578,7 +1616,7 @@ bool Net::backward_step(size_t min_floats, size_t* off, size_t* count, bool sync
                 }
                 g_stop_event = dst.gev;      // the launch carries dst's event (taken by the gather launchers)
                 struct Disarm { ~Disarm() { g_stop_event = nullptr; } } disarm;      // (also when the launch throws)
-                launch_dgrad(op, d, up, dst, mask, cls, ds);
+                launch_dgrad(op, d, up, dst, mask, cls, ds, dual);
                 const bool carried = dst.gev && g_stop_event == nullptr;
                 bw_wrote(cls, dst, carried);
             }

@@ -83,7 +83,8 @@ __device__ __forceinline__ float bias_axis_weight(int slot) {
 // raster instead: the 64 workgroups an XCD holds at a time span 5 to 13 tile rows of every layer of the step, so the neighbour's rows
 // are mostly in that L2 (FETCH_SIZE per launch 1.6 -> 1.1 times the tensor, profiles/wino_geometry_pmc.txt; 2-D blocks of tiles per
 // workgroup fetched no less).  Only which thread takes which (tile, quad) changes; raster = true is the plain order (the reference
-// geometry of tests/test_gpu_winograd_geometry.py).  AT has no halo and keeps the plain order.
+// geometry of tests/test_gpu_winograd_geometry.py).  AT alone has no halo and keeps the plain order; <true, true> (backward's dy, both
+// outputs from one read: launch_in) takes BT's.
 template <bool BT, bool AT>
 __global__ __launch_bounds__(256) void wino_in_kernel(const float* __restrict__ x, float* __restrict__ V, float* __restrict__ Va,
                                                       int H, int W, int C, int Cp, int th, int tw, int T, unsigned x_bytes,
@@ -349,6 +350,24 @@ __device__ __forceinline__ void g6(const float g0, const float g1, const float g
     u[4] = c - d;
     u[5] = g2;
 }
+// U[(k, l)][e] = (G g G^T)_(k, l), ps elements between positions: columns first
+__device__ __forceinline__ void wino_filter_store(const float (&g)[3][3], float* __restrict__ U, size_t ps, size_t e) {
+    float c[6][3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        float u[6];
+        g6(g[0][b], g[1][b], g[2][b], u);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) c[k][b] = u[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        float u[6];
+        g6(c[k][0], c[k][1], c[k][2], u);
+#pragma unroll
+        for (int l = 0; l < 6; ++l) U[(size_t)(k * 6 + l) * ps + e] = u[l];
+    }
+}
 // U[p][ci][co] = (G g G^T)_p of g = w[.][.][ci][co]; FLIP: U'[p][co][ci] of the filter rotated by 180 degrees (the data gradient's).
 // One launch transforms every layer of a plan (conv.h WinoFilterPlan): a block's layer is found by its first-block table.
 template <bool FLIP>
@@ -369,22 +388,47 @@ __global__ __launch_bounds__(256) void wino_filter_kernel(WinoFilterPlan plan) {
     for (int a = 0; a < 3; ++a)
 #pragma unroll
         for (int b = 0; b < 3; ++b) g[a][b] = w[((size_t)((FLIP ? 2 - a : a) * 3 + (FLIP ? 2 - b : b)) * Ci + ci) * Co + co];
-    float c[6][3];
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-        float u[6];
-        g6(g[0][b], g[1][b], g[2][b], u);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) c[k][b] = u[k];
-    }
     const size_t ps = FLIP ? (size_t)plan.it[li].Cop * Ci : (size_t)Ci * Co;      // (the flipped form has Cop >= Co rows; the pad rows stay zero)
     const size_t e = FLIP ? (size_t)co * Ci + ci : (size_t)ci * Co + co;
+    wino_filter_store(g, U, ps, e);
+}
+
+// The flipped form with whole lines on both sides.  Above, a lane's nine reads of w are 4 bytes of a 128-byte line each (its lanes run
+// along ci, w's rows along co): 2.9 TB/s where the unflipped launch moves the same bytes at 5.2.  Here a workgroup takes a 32 ci x 32 co
+// tile of the nine taps: read with lanes along co (a row of the tile = one line of w), through LDS (rows padded to 33 words: the
+// transposed read is conflict-free), written with lanes along ci (32 lanes = one line of U').  The same g6 arithmetic on the same
+// values: the same bits (tests/test_gpu_winograd_filter_flip.py).  Ci is a multiple of 32 (wino_applicable); Co's last tile is ragged.
+__global__ __launch_bounds__(256) void wino_filter_flip_lds_kernel(WinoFilterPlan plan) {
+    __shared__ float sw[9][32][33];
+    int li = 0;
+    for (int k = 1; k < plan.n; ++k)
+        if ((int)blockIdx.x >= plan.it[k].tblk0) li = k;
+    const float* __restrict__ w = plan.it[li].w;
+    float* __restrict__ U = plan.it[li].Uf;
+    if (!U) return;      // (the whole workgroup)
+    const int Ci = plan.it[li].Ci, Co = plan.it[li].Co;
+    const int tile = (int)blockIdx.x - plan.it[li].tblk0, nct = (Co + 31) / 32;
+    const int ci0 = (tile / nct) * 32, co0 = (tile % nct) * 32;
+    const int lane = threadIdx.x & 31, grp = threadIdx.x >> 5;
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        float u[6];
-        g6(c[k][0], c[k][1], c[k][2], u);
+    for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
-        for (int l = 0; l < 6; ++l) U[(size_t)(k * 6 + l) * ps + e] = u[l];
+        for (int k = 0; k < 4; ++k) {
+            const int r = grp + 8 * k;
+            sw[tap][r][lane] = co0 + lane < Co ? w[((size_t)tap * Ci + ci0 + r) * Co + co0 + lane] : 0.f;
+        }
+    __syncthreads();
+    const size_t ps = (size_t)plan.it[li].Cop * Ci;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = grp + 8 * k;
+        if (co0 + c >= Co) continue;
+        float g[3][3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) g[a][b] = sw[(2 - a) * 3 + (2 - b)][lane][c];
+        wino_filter_store(g, U, ps, (size_t)(co0 + c) * Ci + ci0 + lane);
     }
 }
 
@@ -924,12 +968,15 @@ static void require(const ConvDesc& d) { SSD_REQUIRE(wino_applicable(d), "winogr
 
 void WinoFilterPlan::add(const float* w, float* U, float* Uf, int Ci, int Co) {
     SSD_REQUIRE(n < MAX, "winograd: more than %d layers in one filter plan", MAX);
-    it[n] = Item{w, U, Uf, Ci, Co, wino_kpad(Co), blocks};
+    SSD_REQUIRE(!Uf || Ci % 32 == 0, "winograd: the flipped filter transform takes Ci in multiples of 32 (got %d)", Ci);
+    it[n] = Item{w, U, Uf, Ci, Co, wino_kpad(Co), blocks, tblocks};
     blocks += cdiv((long long)Ci * Co, 256);
+    tblocks += (Ci / 32) * cdiv(Co, 32);
     elems += (double)Ci * Co;
     ++n;
 }
-void wino_filter_plan(const WinoFilterPlan& plan, bool forward, bool flipped, hipStream_t s) {
+void wino_filter_plan(const WinoFilterPlan& plan, bool forward, bool flipped, hipStream_t s, bool flip_lanes_ci) {
+    static const int flip_lds = env_int("SSD_WINO_FILTER_LDS", 1);
     if (plan.n == 0) return;
     const double by = 4.0 * plan.elems * (9 + 36);
     if (forward) {
@@ -938,7 +985,8 @@ void wino_filter_plan(const WinoFilterPlan& plan, bool forward, bool flipped, hi
     }
     if (flipped) {
         ProfScope prof("wino_filter_flip", 0, by, s);
-        hipLaunchKernelGGL(wino_filter_kernel<true>, dim3(plan.blocks), dim3(256), 0, s, plan);
+        if (flip_lanes_ci || !flip_lds) hipLaunchKernelGGL(wino_filter_kernel<true>, dim3(plan.blocks), dim3(256), 0, s, plan);
+        else hipLaunchKernelGGL(wino_filter_flip_lds_kernel, dim3(plan.tblocks), dim3(256), 0, s, plan);
     }
     HIP_OK(hipGetLastError());
 }
@@ -959,16 +1007,28 @@ static bool ref_geometry(bool asked, int part) {
     return asked || on == 0 || (on == 2 && part != GEOM_IN) || (on == 3 && part != GEOM_REDUCE);
 }
 
+// Both outputs of one x (backward: dy -> Yt for the data gradient and Ya for the weight gradient): one launch of the <true, true> form,
+// which reads x once -- the AT patch is the inner 4x4 of the 6x6 patch the thread holds -- in the BT form's workgroup order, every value
+// the same expression as in the single forms (tests/test_gpu_winograd_dual.py: the same bits).  `two` asks for the two single launches
+// instead, as does SSD_WINO_DUAL=0 for the whole process.
+static bool dual_launch(bool two) {
+    static const int on = env_int("SSD_WINO_DUAL", 1);
+    return !two && on != 0;
+}
+
 static void launch_in(const float* x, float* V, float* Va, int B, int H, int W, int C, int Cp, int D, size_t v_ps, size_t va_ps, hipStream_t s,
-                      unsigned long long* bits, bool raster) {
+                      unsigned long long* bits, bool raster, bool two = false) {
     const int th = tiles_1d(H, D), tw = tiles_1d(W, D), T = B * th * tw;
     const unsigned xb = (unsigned)((size_t)B * H * W * C * 4u);
     const int grid = cdiv((long long)T * (Cp / 4), 256);
     const double by = 4.0 * ((double)B * H * W * C + 36.0 * T * Cp * ((V ? 1 : 0) + (Va ? 1 : 0)));
-    if (V && Va) {      // (one kernel for both was never measured faster than the data gradient's stream running its own: two launches)
+    if (V && Va && !dual_launch(two)) {
         launch_in(x, V, nullptr, B, H, W, C, Cp, D, v_ps, 0, s, bits, raster);
         launch_in(x, nullptr, Va, B, H, W, C, Cp, D, 0, va_ps, s, nullptr, raster);
         return;
+    } else if (V && Va) {
+        ProfScope prof("wino_in_dual", 0, by, s);
+        hipLaunchKernelGGL((wino_in_kernel<true, true>), dim3(grid), dim3(256), 0, s, x, V, Va, H, W, C, Cp, th, tw, T, xb, v_ps, va_ps, D, bits, raster);
     } else if (V) {
         ProfScope prof("wino_in", 0, by, s);
         hipLaunchKernelGGL((wino_in_kernel<true, false>), dim3(grid), dim3(256), 0, s, x, V, Va, H, W, C, Cp, th, tw, T, xb, v_ps, va_ps, D, bits, raster);
@@ -1080,10 +1140,10 @@ void wino_fwd(const ConvDesc& d, const float* x, const float* U, const float* bi
 
 size_t wino_dgrad_ws_floats(const ConvDesc& d) { return (size_t)36 * wino_tiles(d) * d.Ci; }
 
-void wino_bwd_transform(const ConvDesc& d, const float* dy, float* Yt, float* Ya, hipStream_t s, bool ref_geom) {
+void wino_bwd_transform(const ConvDesc& d, const float* dy, float* Yt, float* Ya, hipStream_t s, bool ref_geom, bool two_launch) {
     require(d);
     const size_t ps = (size_t)wino_tiles(d) * wino_kpad(d.Co);
-    launch_in(dy, Yt, Ya, d.B, d.Ho, d.Wo, d.Co, wino_kpad(d.Co), d.dil, ps, ps, s, nullptr, ref_geometry(ref_geom, GEOM_IN));
+    launch_in(dy, Yt, Ya, d.B, d.Ho, d.Wo, d.Co, wino_kpad(d.Co), d.dil, ps, ps, s, nullptr, ref_geometry(ref_geom, GEOM_IN), two_launch);
 }
 
 void wino_dgrad(const ConvDesc& d, const float* Yt, const float* Uflip, float* dx, const float* mask, bool accumulate, float* Xws,
