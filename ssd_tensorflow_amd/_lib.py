@@ -169,6 +169,11 @@ SIGNATURES = {
     'ssd_get_loss': (i32, [handle, vp]),
     'ssd_set_loc_loss': (i32, [handle, vp]),
     'ssd_get_loc_loss': (i32, [handle, vp]),
+    'ssd_set_grad_clip': (i32, [handle, vp]),
+    'ssd_get_grad_clip': (i32, [handle, vp]),
+    'ssd_get_grad_norm_step': (i32, [handle, i32, vp]),
+    'ssd_op_grad_norm_ws_bytes': (sz, [sz]),
+    'ssd_op_momentum_update_clipped': (i32, [vp, vp, vp, sz, f32, f32, f32, f32, vp, vp, vp]),
     'ssd_train_step_dev': (i32, [handle, vp, vp, i32]),
     'ssd_eval_step_dev': (i32, [handle, vp, vp, i32]),
     'ssd_infer_dev': (i32, [handle, vp, i32]),

@@ -1226,6 +1226,30 @@ int ssd_get_loc_loss(ssd_handle h, ssd_loc_loss_config* cfg) {
     N(h).get_loc_loss(&cfg->kind, &cfg->weight);
     API_END
 }
+// ... and a gradient clipping configuration: 0 off, a number > 0, or +inf (measure only)
+static void check_grad_clip(float max_norm) {
+    SSD_REQUIRE(max_norm >= 0.f, "gradient clipping: max_norm %g is neither 0 (off), a number > 0 nor +inf", (double)max_norm);
+}
+int ssd_set_grad_clip(ssd_handle h, const ssd_grad_clip_config* cfg) {
+    API_BEGIN
+    SSD_REQUIRE(cfg != nullptr, "gradient clipping: null configuration");
+    check_grad_clip(cfg->max_norm);
+    Net& n = N(h);
+    n.set_grad_clip(cfg->max_norm == 0.f ? 0.f : cfg->max_norm);      // (-0 is stored as 0)
+    API_END
+}
+int ssd_get_grad_clip(ssd_handle h, ssd_grad_clip_config* cfg) {
+    API_BEGIN
+    SSD_REQUIRE(cfg != nullptr, "gradient clipping: null configuration");
+    cfg->max_norm = N(h).grad_clip();
+    API_END
+}
+int ssd_get_grad_norm_step(ssd_handle h, int steps_back, float out[2]) {
+    API_BEGIN_NET(h)
+    SSD_REQUIRE(out != nullptr, "null argument");
+    n.get_grad_norm_step(steps_back, out);
+    API_END
+}
 int ssd_null_gradients_dev(ssd_handle h) {
     API_BEGIN_NET(h)
     n.null_gradients_step();
@@ -1980,6 +2004,15 @@ int ssd_grads_from_bf16(int device, const void* msg_dev, float* grads_dev, size_
     API_BEGIN
     DeviceGuard guard(device);
     grads_from_bf16(msg_dev, grads_dev, count, (hipStream_t)stream);
+    API_END
+}
+size_t ssd_op_grad_norm_ws_bytes(size_t n) { return grad_norm_ws_bytes(n); }
+int ssd_op_momentum_update_clipped(float* w, float* acc, const float* g, size_t n, float lr, float momentum, float grad_scale,
+                                   float max_norm, void* ws_dev, float* report_dev, void* stream) {
+    API_BEGIN
+    check_grad_clip(max_norm);
+    SSD_REQUIRE(w && acc && g && (max_norm == 0.f || ws_dev), "null buffer");
+    momentum_update_clipped(w, acc, g, n, lr, momentum, grad_scale, max_norm, ws_dev, report_dev, (hipStream_t)stream);
     API_END
 }
 int ssd_op_clock_monitor(unsigned* out_dev, int nsamples, unsigned period_ticks, void* stream) {

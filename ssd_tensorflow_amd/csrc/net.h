@@ -132,6 +132,12 @@ public:
     // ... and which localization loss: 0 smooth-L1 (the default; weight 1), 1 GIoU with its weight
     void set_loc_loss(int kind, float weight) { loc_.kind = kind; loc_.weight = weight; }
     void get_loc_loss(int* kind, float* weight) const { *kind = loc_.kind; *weight = loc_.weight; }
+    // clip the gradient by its global norm from the next update on: 0 off (the plain update's launch), > 0 the threshold,
+    // +inf measures and never clips (ops.h momentum_update_clipped); the caller has checked the value
+    void set_grad_clip(float max_norm);
+    float grad_clip() const { return clip_max_norm_; }
+    // {norm, factor} of the last clipped update (steps_back = 0) or of one of the LOSS_RING - 2 before it: waits for THAT update only
+    void get_grad_norm_step(int steps_back, float out[2]);
     void null_gradients_step();                                         // gradient arena of a step without samples
     void set_optimizer(const float* lr_values, const long long* bounds, int n, float momentum, float wd);
 
@@ -354,6 +360,14 @@ private:
     hipEvent_t ev_loss_[LOSS_RING] = {};  // recorded behind the forward pass that wrote the slot
     long long loss_seq_ = -1;             // forward passes with a loss so far - 1
     float* begin_loss_slot();             // next slot: waits until its previous use (LOSS_RING passes ago) has finished
+    // gradient clipping (apply_gradients): 0 off, > 0 the threshold, +inf measure only.  The norm and the factor of every clipped
+    // update land in a ring like the losses', keyed by the count of such updates, an event behind each update.
+    float clip_max_norm_ = 0.f;
+    void* clip_ws_ = nullptr;             // grad_norm_ws_bytes(nparams_): allocated with the arenas
+    float* clip_host_ = nullptr;          // pinned, device-mapped: LOSS_RING slots of 2 floats
+    float* clip_dev_ = nullptr;
+    hipEvent_t ev_clip_[LOSS_RING] = {};
+    long long clip_seq_ = -1;             // clipped (or measured) updates so far - 1
     double* anchors_dev_ = nullptr;
     int* anchors_abs_dev_ = nullptr;
     void* detect_ws_ = nullptr;

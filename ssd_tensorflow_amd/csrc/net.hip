@@ -917,6 +917,16 @@ void Net::alloc() {
     anchors_dev_ = (double*)hip_.mem((size_t)A * 4 * sizeof(double));
     anchors_abs_dev_ = (int*)hip_.mem((size_t)A * 4 * sizeof(int));
     anchors_device(*preset_, anchors_dev_, anchors_abs_dev_, nullptr);
+    // Gradient clipping (apply_gradients), after everything else so that every other buffer sits where it sat without it: the norm
+    // pass's partials with the update's scale, and a ring of {norm, factor} per clipped update that the finish kernel writes
+    // straight into mapped host memory, like the losses above.
+    if (training_) {
+        clip_ws_ = hip_.mem(grad_norm_ws_bytes(nparams_));
+        clip_host_ = static_cast<float*>(hip_.pinned(LOSS_RING * 2 * sizeof(float), &dp));
+        for (int i = 0; i < LOSS_RING * 2; ++i) clip_host_[i] = 0.f;
+        clip_dev_ = static_cast<float*>(dp);
+        for (int i = 0; i < LOSS_RING; ++i) ev_clip_[i] = hip_.event();
+    }
     HIP_OK(hipDeviceSynchronize());
 }
 
@@ -1713,8 +1723,34 @@ void Net::apply_gradients(float grad_scale) {
     SSD_REQUIRE(training_, "handle was created with training = 0");
     g_prof = &prof_;
     prof_.layer = "optimizer";
-    momentum_update(params_, mom_, grads_, nparams_, current_lr(), momentum_, grad_scale, stream_);
-    ++global_step;
+    if (clip_max_norm_ == 0.f) {
+        momentum_update(params_, mom_, grads_, nparams_, current_lr(), momentum_, grad_scale, stream_);
+    } else {
+        // the slot's previous update (LOSS_RING updates ago) has long finished; nothing here waits for this one
+        ++clip_seq_;
+        const int slot = (int)(clip_seq_ % LOSS_RING);
+        if (clip_seq_ >= LOSS_RING) HIP_OK(hipEventSynchronize(ev_clip_[slot]));
+        momentum_update_clipped(params_, mom_, grads_, nparams_, current_lr(), momentum_, grad_scale, clip_max_norm_, clip_ws_,
+                                clip_dev_ + 2 * slot, stream_);
+        HIP_OK(hipEventRecord(ev_clip_[slot], stream_));
+    }
+    ++global_step;      // a skipped update counts: the schedule is a function of the steps taken
+}
+
+void Net::set_grad_clip(float max_norm) {
+    SSD_REQUIRE(training_, "gradient clipping: the handle was created with training = 0");
+    clip_max_norm_ = max_norm;
+}
+
+void Net::get_grad_norm_step(int steps_back, float out[2]) {
+    SSD_REQUIRE(training_, "gradient clipping: the handle was created with training = 0");
+    SSD_REQUIRE(steps_back >= 0 && steps_back < LOSS_RING - 1, "steps_back must be in 0..%d", LOSS_RING - 2);
+    SSD_REQUIRE(clip_max_norm_ != 0.f, "gradient clipping is off: no update has measured a gradient norm (ssd_set_grad_clip)");
+    SSD_REQUIRE(clip_seq_ - steps_back >= 0, "gradient clipping: no clipped update has run %d update(s) back", steps_back);
+    const int slot = (int)((clip_seq_ - steps_back) % LOSS_RING);
+    HIP_OK(hipEventSynchronize(ev_clip_[slot]));
+    out[0] = clip_host_[2 * slot];
+    out[1] = clip_host_[2 * slot + 1];
 }
 
 // backward + update of a single-GPU step.  (Rounds 2-4 carried an "early update" of the finished arena suffix on the

@@ -117,6 +117,19 @@ void multibox_focal_loss_grad(const HeadLayout& L, int B, int b_off, const float
 // ---- MomentumOptimizer without Nesterov (ssdvgg.py:586-588): acc = m*acc + g; w -= lr*acc
 void momentum_update(float* w, float* acc, const float* g, size_t n, float lr, float momentum, float gscale,
                      hipStream_t s);
+// ... with the gradient clipped by its global norm (include/ssdvgg_hip.h "gradient clipping").  max_norm == 0: the
+// call above.  Otherwise three launches on s and no host wait: grad_norm_kernel (one fp64 partial sum of squares per block),
+// grad_norm_finish_kernel (one block: the partials in a fixed tree, then norm, factor and the update's scale into ws and, where
+// report != NULL, norm and factor into report[0..1] -- device or device-mapped host memory), momentum_clipped_kernel (momentum_kernel's
+// body with that scale; returns at once where the sum was not finite).  ws: grad_norm_ws_bytes(n) bytes, 16-byte aligned.
+// The grid of the norm pass is a function of n alone, so the summation tree is too: bit-reproducible.
+constexpr int GRAD_NORM_BLOCK = 256;              // threads of a block = 4-float groups of one block's pass
+constexpr int GRAD_NORM_GRID_CAP = 256 * 16;      // blocks: the update's own cap
+constexpr int GRAD_NORM_UNROLL = 4;                // passes of the grid whose loads a thread issues together: the main loop of the norm
+                                                  // kernel runs while GRAD_NORM_UNROLL whole passes remain, a one-pass loop takes the rest
+size_t grad_norm_ws_bytes(size_t n);
+void momentum_update_clipped(float* w, float* acc, const float* g, size_t n, float lr, float momentum, float gscale, float max_norm,
+                             void* ws, float* report, hipStream_t s);
 
 // gradients of a step without samples (a data-parallel rank whose shard of a short last batch is empty)
 void null_gradients(const float* w, float* g, size_t nfilters, size_t n, float wd, hipStream_t s);

@@ -1910,6 +1910,116 @@ void momentum_update(float* w, float* acc, const float* g, size_t n, float lr, f
     HIP_OK(hipGetLastError());
 }
 
+// ---- the same update with the gradient clipped by its global norm (ops.h; contract in include/ssdvgg_hip.h)
+// Head of the workspace: what the finish kernel leaves for the update; the per-block partials follow it.
+struct ClipState {
+    float gscale;       // grad_scale * factor
+    unsigned skip;      // the sum of squares was not finite: the update touches nothing
+    unsigned pad[2];
+};
+static_assert(sizeof(ClipState) == 16, "the partials behind it are read as aligned doubles");
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// the block's sum, valid in thread 0: lanes by the xor butterfly, the four waves through LDS in wave order
+__device__ __forceinline__ double block_sum_256(double v) {
+    __shared__ double red[4];
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// One read of the arena, 16 bytes per lane and trip: a float's square is exact in fp64 (48 bits of product), so the only
+// rounding is the additions', and four chains per thread keep the fp64 adds off each other's latency.
+__global__ __launch_bounds__(GRAD_NORM_BLOCK) void grad_norm_kernel(const float* __restrict__ g, size_t n4, double* __restrict__ partial) {
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+#define SSD_SQ_ACC(v)                   \
+    a0 += (double)v[0] * (double)v[0];  \
+    a1 += (double)v[1] * (double)v[1];  \
+    a2 += (double)v[2] * (double)v[2];  \
+    a3 += (double)v[3] * (double)v[3];
+    // GRAD_NORM_UNROLL loads in flight per lane (a wave alone would wait out HBM's latency on every trip); added in index order, so
+    // the sums are those of the plain loop below
+    for (; i + (GRAD_NORM_UNROLL - 1) * stride < n4; i += GRAD_NORM_UNROLL * stride) {
+        f32x4 v[GRAD_NORM_UNROLL];
+#pragma unroll
+        for (int u = 0; u < GRAD_NORM_UNROLL; ++u) v[u] = ld4(g + (i + u * stride) * 4);
+#pragma unroll
+        for (int u = 0; u < GRAD_NORM_UNROLL; ++u) { SSD_SQ_ACC(v[u]) }
+    }
+    for (; i < n4; i += stride) {
+        const f32x4 v = ld4(g + i * 4);
+        SSD_SQ_ACC(v)
+    }
+#undef SSD_SQ_ACC
+    const double s = block_sum_256((a0 + a1) + (a2 + a3));
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// One block: thread t takes partials t, t + 256, ... in index order, then the block's tree.  norm = |grad_scale| * sqrt(S) and
+// the factor in fp64, each rounded to float once.
+__global__ __launch_bounds__(GRAD_NORM_BLOCK) void grad_norm_finish_kernel(const double* __restrict__ partial, int nparts, float gscale,
+                                                                          float max_norm, ClipState* __restrict__ st,
+                                                                          float* __restrict__ report) {
+    double a = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += GRAD_NORM_BLOCK) a += partial[i];
+    const double S = block_sum_256(a);
+    if (threadIdx.x != 0) return;
+    const double norm = fabs((double)gscale) * sqrt(S);
+    const bool finite = __builtin_isfinite(S);
+    float f = 0.f;
+    if (finite) f = norm <= (double)max_norm ? 1.f : (float)((double)max_norm / norm);
+    st->gscale = gscale * f;
+    st->skip = finite ? 0u : 1u;
+    if (report) {
+        report[0] = (float)norm;
+        report[1] = f;
+    }
+}
+
+// momentum_kernel's body; the scale comes from the finish kernel (one scalar load per wave: the pointer is a kernel argument)
+__global__ __launch_bounds__(256) void momentum_clipped_kernel(float* __restrict__ w, float* __restrict__ acc,
+                                                               const float* __restrict__ g, size_t n4, float lr, float mom,
+                                                               const ClipState* __restrict__ st) {
+    if (st->skip) return;
+    const float gscale = st->gscale;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        const f32x4 a = mom * ld4(acc + i * 4) + gscale * ld4(g + i * 4);
+        st4(acc + i * 4, a);
+        st4(w + i * 4, ld4(w + i * 4) - lr * a);
+    }
+}
+
+static inline int grad_norm_grid(size_t n) { return grid_for(n / 4, GRAD_NORM_BLOCK, GRAD_NORM_GRID_CAP); }
+size_t grad_norm_ws_bytes(size_t n) { return sizeof(ClipState) + (size_t)grad_norm_grid(n) * sizeof(double); }
+
+void momentum_update_clipped(float* w, float* acc, const float* g, size_t n, float lr, float momentum, float gscale, float max_norm,
+                             void* ws, float* report, hipStream_t s) {
+    if (max_norm == 0.f) return momentum_update(w, acc, g, n, lr, momentum, gscale, s);
+    SSD_REQUIRE(max_norm > 0.f, "gradient clipping: max_norm %g is neither 0 (off), a number > 0 nor +inf", (double)max_norm);
+    SSD_REQUIRE(n % 4 == 0, "momentum: arena size must be a multiple of 4");
+    SSD_REQUIRE(ws != nullptr && (uintptr_t)ws % 16 == 0, "gradient clipping: the workspace must be 16-byte aligned");
+    ClipState* st = static_cast<ClipState*>(ws);
+    double* partial = reinterpret_cast<double*>(st + 1);
+    const int grid = grad_norm_grid(n);
+    {
+        ProfScope prof("grad_norm", 2.0 * n, 4.0 * n, s);
+        hipLaunchKernelGGL(grad_norm_kernel, dim3(grid), dim3(GRAD_NORM_BLOCK), 0, s, g, n / 4, partial);
+        hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(GRAD_NORM_BLOCK), 0, s, (const double*)partial, grid, gscale, max_norm,
+                           st, report);
+    }
+    ProfScope prof("momentum_update_clipped", 0.0, 20.0 * n, s);
+    hipLaunchKernelGGL(momentum_clipped_kernel, dim3(grid_for(n / 4, 256, 256 * 16)), dim3(256), 0, s, w, acc, g, n / 4, lr, momentum,
+                       (const ClipState*)st);
+    HIP_OK(hipGetLastError());
+}
+
 // Gradient range <-> bf16 message buffer of the data-parallel all-reduce (parallel.py, allreduce_dtype = 'bf16'): the payload
 // that crosses xGMI is halved; masters, momentum and the local gradient arena stay fp32.  Round-to-nearest-even like every other
 // bf16 store of the library; n need not be a multiple of anything.

@@ -79,6 +79,27 @@ def checkpoint_loc_loss(ck):
     return str(ck['__loc_loss__']), float(ck['__loc_weight__'])
 
 
+class GradClipConfig(C.Structure):
+    """ssd_grad_clip_config of the C ABI"""
+    _fields_ = [('max_norm', C.c_float)]
+
+
+def grad_clip_config(clip_norm=0.0):
+    """The ABI's configuration of gradient clipping by global norm (include/ssdvgg_hip.h): 0 off, a number > 0 the
+    threshold, inf measures the norm of every update and never clips.  A negative value or NaN: ValueError."""
+    v = float(clip_norm)
+    if not v >= 0.0:
+        raise ValueError('gradient clipping takes clip_norm 0 (off), a number > 0 or inf, got %r' % (clip_norm,))
+    return GradClipConfig(v)
+
+
+def checkpoint_clip_norm(ck):
+    """clip_norm of an opened checkpoint; one from before the option is 0.0 (off)."""
+    if '__clip_norm__' not in ck.files:
+        return 0.0
+    return float(ck['__clip_norm__'])
+
+
 class _Token:
     """An opaque stand-in for a TF tensor/op handle; only identity matters."""
     def __init__(self, name):
@@ -340,16 +361,18 @@ class SSDVGG:
 
     # ------------------------------------------------------------------ optimizer
     def build_optimizer(self, learning_rate=0.001, weight_decay=0.0005, momentum=0.9, global_step=None, loss='mining',
-                        focal_gamma=2.0, focal_alpha=0.25, loc_loss='smooth_l1', loc_weight=1.0):
+                        focal_gamma=2.0, focal_alpha=0.25, loc_loss='smooth_l1', loc_weight=1.0, clip_norm=0.0):
         """ssdvgg.py:375-599.  learning_rate: float or LearningRate (train.py:43-47).  loss: 'mining' (the reference's 3:1
         hard-negative mining) or 'focal' (every anchor, damped by (1 - p_t)^focal_gamma and weighted focal_alpha on positives,
         1 - focal_alpha on background; a sample without positives still trains its background anchors).
         loc_loss: 'smooth_l1' (the reference's, on the four encoded offsets) or 'giou' (loc_weight * (1 - GIoU) of the predicted
-        against the ground-truth box of every positive anchor); either goes with either `loss`."""
+        against the ground-truth box of every positive anchor); either goes with either `loss`.
+        clip_norm: clip the gradient by its global norm in the update (0, the default: off; inf: measure only)."""
         if not self.training:
             raise RuntimeError('build_from_* was called with training=False')
         self.set_loss(loss, focal_gamma, focal_alpha)
         self.set_loc_loss(loc_loss, loc_weight)
+        self.set_grad_clip(clip_norm)
         lr = learning_rate if isinstance(learning_rate, LearningRate) else LearningRate([learning_rate], [])
         vals = np.array(lr.values, np.float32)
         bnds = np.array(lr.boundaries + [0], np.int64)
@@ -372,7 +395,8 @@ class SSDVGG:
         loss, gamma, alpha = checkpoint_loss(ck)
         loc_loss, loc_weight = checkpoint_loc_loss(ck)
         self.build_optimizer(lr, float(ck['__weight_decay__']), float(ck['__momentum__']), int(ck['__global_step__']),
-                             loss=loss, focal_gamma=gamma, focal_alpha=alpha, loc_loss=loc_loss, loc_weight=loc_weight)
+                             loss=loss, focal_gamma=gamma, focal_alpha=alpha, loc_loss=loc_loss, loc_weight=loc_weight,
+                             clip_norm=checkpoint_clip_norm(ck))
         for k in ck.files:
             if k.startswith('__momentum__/'):
                 a = np.ascontiguousarray(ck[k], np.float32)
@@ -452,6 +476,7 @@ class SSDVGG:
             d.update(__loss__=np.array(loss), __focal_gamma__=np.array(gamma), __focal_alpha__=np.array(alpha))
             loc_loss, loc_weight = self.get_loc_loss()
             d.update(__loc_loss__=np.array(loc_loss), __loc_weight__=np.array(loc_weight))
+            d.update(__clip_norm__=np.array(self.get_grad_clip()))
         np.savez(path, **d)
 
     # ------------------------------------------------------------------ steps
@@ -641,6 +666,25 @@ class SSDVGG:
         cfg = LocLossConfig()
         check(lib.ssd_get_loc_loss(self._h, C.byref(cfg)))
         return [k for k, v in LOC_LOSS_KINDS.items() if v == cfg.kind][0], float(cfg.weight)
+
+    def set_grad_clip(self, clip_norm=0.0):
+        """Clip the gradient by its global norm from the next update on (ssd_set_grad_clip): 0 off, > 0 the threshold, inf
+        measures only (build_optimizer)."""
+        cfg = grad_clip_config(clip_norm)
+        check(lib.ssd_set_grad_clip(self._h, C.byref(cfg)))
+
+    def get_grad_clip(self):
+        """clip_norm of the handle"""
+        cfg = GradClipConfig()
+        check(lib.ssd_get_grad_clip(self._h, C.byref(cfg)))
+        return float(cfg.max_norm)
+
+    def get_grad_norm_step(self, steps_back=0):
+        """(norm, factor) of the last clipped or measured update (0) or of the one 1 / 2 before it, waiting only for THAT update
+        (ssd_get_grad_norm_step).  factor 1: not clipped; in (0, 1): clipped; 0: skipped, the gradient was not finite."""
+        out = np.zeros(2, np.float32)
+        check(lib.ssd_get_grad_norm_step(self._h, int(steps_back), np_ptr(out)))
+        return float(out[0]), float(out[1])
 
     def get_loss(self):
         """(name, focal_gamma, focal_alpha) of the handle's loss"""

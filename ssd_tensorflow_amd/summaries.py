@@ -52,6 +52,38 @@ class LossSummary:
         return means
 
 
+class GradNormSummary:
+    """The gradient's global norm at every update of an epoch (--clip-norm; no reference site): `grad_norm` per update, at the
+    update's number, and per epoch `grad_norm_median`, `grad_norm_max`, `grad_clipped` and `grad_skipped` (how many updates were
+    scaled down, and how many were skipped because their gradient was not finite)."""
+
+    def __init__(self, writer, updates=0):
+        self.writer = writer
+        self.values = []          # (norm, factor) per update since the last push
+        self.updates = updates    # updates before the first one booked here (a continued run: the checkpoint's global step)
+
+    def add(self, norm, factor):
+        self.updates += 1
+        self.values.append((float(norm), float(factor)))
+        if self.writer is not None and factor != 0.0:      # (a skipped update has no finite norm to plot; the epoch counts it)
+            self.writer.add_scalar('grad_norm', norm, self.updates)
+
+    def push(self, epoch):
+        """{median, max (over the finite norms), clipped, skipped, updates} of the epoch"""
+        finite = sorted(n for n, f in self.values if f != 0.0)
+        m = len(finite)
+        median = 0.0 if not m else finite[m // 2] if m % 2 else 0.5 * (finite[m // 2 - 1] + finite[m // 2])
+        out = dict(median=median, max=finite[-1] if m else 0.0, clipped=sum(1 for _, f in self.values if 0.0 < f < 1.0),
+                   skipped=sum(1 for _, f in self.values if f == 0.0), updates=len(self.values))
+        if self.writer is not None and self.values:
+            for k in ('median', 'max'):
+                self.writer.add_scalar('grad_norm_' + k, out[k], epoch)
+            self.writer.add_scalar('grad_clipped', out['clipped'], epoch)
+            self.writer.add_scalar('grad_skipped', out['skipped'], epoch)
+        self.values = []
+        return out
+
+
 class PrecisionSummary:
     """utils.py:151-199: `<sample_name>_mAP` and `<sample_name>_AP_<label>` per epoch; nothing when no
     AP could be computed."""

@@ -26,7 +26,7 @@ from .average_precision import APCalculator, DeviceAPCalculator, APs2mAP, add_ap
 from .coco_eval import COCOEvaluator, DeviceCOCOEvaluator, aps_of, format_summary, summarize
 from .ssdutils import boxes_from_detection
 from .ssdvgg import SSDVGG, Session, LearningRate
-from .summaries import SummaryWriter, LossSummary, PrecisionSummary, ImageSummary
+from .summaries import SummaryWriter, LossSummary, PrecisionSummary, ImageSummary, GradNormSummary
 from .training_data import TrainingData
 from .utils import str2bool
 
@@ -49,6 +49,7 @@ class StepLoop:
         self.world, self.rank, self.bucket = world, rank, bucket
         self.allreduce_dtype = allreduce_dtype
         self.steps = 0
+        self.grad_norms = None      # a summaries.GradNormSummary when the handle clips or measures (--clip-norm): booked like the losses
 
     def booked(self, loss_batch, count):
         """(values, weight) for LossSummary.add.  One GPU: the batch's losses, weighted by its samples
@@ -107,6 +108,7 @@ class StepLoop:
         net, sess, td, world = self.net, self.sess, self.td, self.world
         pending_det = None
         pending_loss = None                     # sample count of the launched step whose losses are not booked yet
+        pending_norm = False                    # the launched step ends in an update whose norm is not booked yet
         for x, y, gt_boxes in generator(self.batch_size, self.num_workers):
             n = len(gt_boxes)
             count = td.global_count if world > 1 else n
@@ -127,6 +129,10 @@ class StepLoop:
             if pending_loss is not None:
                 self.book(net.get_losses_step(1 if ran else 0), pending_loss, loss_summary)
             pending_loss = count if ran else None
+            if train and self.grad_norms is not None:
+                if pending_norm:
+                    self.grad_norms.add(*net.get_grad_norm_step(1 if ran else 0))
+                pending_norm = ran
             if not with_ap or n == 0:
                 continue
             # decode + NMS of the batch just computed, on the GPU (train.py:275-277)
@@ -141,6 +147,8 @@ class StepLoop:
             pending_det = (launched, gt_boxes, drawn)
         if pending_loss is not None:
             self.book(net.get_losses_step(0), pending_loss, loss_summary)
+        if pending_norm:
+            self.grad_norms.add(*net.get_grad_norm_step(0))
         if pending_det:
             self.collect(*pending_det, ap_calc, image_samples)
 
@@ -161,6 +169,13 @@ def checkpoint_loss(path):
 def checkpoint_loc_loss(path):
     """(localization loss, weight) a checkpoint's run trained with (checkpoints from before the option: 'smooth_l1')."""
     from .ssdvgg import checkpoint_loc_loss as of
+    with np.load(path, allow_pickle=False) as ck:
+        return of(ck)
+
+
+def checkpoint_clip_norm(path):
+    """--clip-norm of a checkpoint's run (checkpoints from before the option: 0, off)."""
+    from .ssdvgg import checkpoint_clip_norm as of
     with np.load(path, allow_pickle=False) as ck:
         return of(ck)
 
@@ -193,6 +208,7 @@ def main(argv=None):
     parser.add_argument('--focal-alpha', type=float, default=0.25, help='--loss focal: the weight of a positive anchor (background: 1 - alpha), inside (0, 1)')
     parser.add_argument('--loc-loss', default='smooth_l1', choices=['smooth_l1', 'giou'], help="the box regression half of the loss: smooth_l1 = the reference's, on the four encoded offsets; giou = 1 - generalized IoU of the predicted against the ground-truth box of every positive anchor (DESIGN.md 31); goes with either --loss; --continue-training takes the checkpoint's")
     parser.add_argument('--loc-weight', type=float, default=1.0, help='--loc-loss giou: the factor on the localization term, a finite number > 0')
+    parser.add_argument('--clip-norm', type=float, default=0.0, help="clip the gradient by its global norm in the update, on the GPU: 0 = off; X > 0 = scale an update whose gradient norm exceeds X down to X and skip one whose gradient is not finite; inf = measure the norm of every update and never clip (DESIGN.md 34); --continue-training takes the checkpoint's")
     parser.add_argument('--focal-prior', type=float, default=0.01, help='a fresh --loss focal run: the classifier biases start at a total object probability of this per anchor')
     parser.add_argument('--shapes-size', default='0.2;0.5', help="--data-dir shapes: smallest and largest side of a rectangle, as fractions of the frame")
     parser.add_argument('--synthetic-train', type=int, default=64, help='synthetic training samples per epoch')
@@ -256,6 +272,10 @@ def main(argv=None):
         if asked != ck_loc[:len(asked)]:
             say("[i] --loc-loss %s disagrees with the checkpoint: continuing with its localization loss, '%s'" % (args.loc_loss, ck_loc[0]))
         args.loc_loss, args.loc_weight = ck_loc
+        ck_clip = checkpoint_clip_norm(ckpt)
+        if args.clip_norm != 0.0 and args.clip_norm != ck_clip:
+            say("[i] --clip-norm %g disagrees with the checkpoint: continuing with its value, %g" % (args.clip_norm, ck_clip))
+        args.clip_norm = ck_clip
     elif rank == 0:
         try:
             os.makedirs(args.name, exist_ok=True)
@@ -264,15 +284,20 @@ def main(argv=None):
 
     say('[i] Matching rule:        ', args.match)
     try:
-        from .ssdvgg import loss_config, loc_loss_config
+        from .ssdvgg import loss_config, loc_loss_config, grad_clip_config
         loss_config(args.loss, args.focal_gamma, args.focal_alpha)
         loc_loss_config(args.loc_loss, args.loc_weight)
         if args.loss == 'focal' and not 0.0 < args.focal_prior < 1.0:
             raise ValueError('--focal-prior must lie in (0, 1)')
     except ValueError as e:
         print('[!] Bad loss:', str(e)); return 1
+    try:
+        grad_clip_config(args.clip_norm)
+    except ValueError as e:
+        print('[!] Bad --clip-norm:', str(e)); return 1
     say('[i] Loss:                 ', args.loss if args.loss != 'focal' else 'focal (gamma %g, alpha %g)' % (args.focal_gamma, args.focal_alpha))
     say('[i] Localization loss:    ', args.loc_loss if args.loc_loss == 'smooth_l1' else '%s (weight %g)' % (args.loc_loss, args.loc_weight))
+    say('[i] Gradient clipping:    ', 'off' if args.clip_norm == 0 else 'norm measured, never clipped' if math.isinf(args.clip_norm) else 'global norm <= %g' % args.clip_norm)
     if args.cache_gb < 0 or (args.cache_gb and args.decoder != 'gpu'):
         print('[!] --cache-gb keeps pictures decoded on the GPU: it needs --decoder gpu and a size >= 0'); return 1
     try:
@@ -310,7 +335,7 @@ def main(argv=None):
                                background_prior=args.focal_prior if args.loss == 'focal' else None)
             net.build_optimizer(learning_rate=lr, weight_decay=args.weight_decay, momentum=args.momentum, loss=args.loss,
                                 focal_gamma=args.focal_gamma, focal_alpha=args.focal_alpha, loc_loss=args.loc_loss,
-                                loc_weight=args.loc_weight)
+                                loc_weight=args.loc_weight, clip_norm=args.clip_norm)
         if world > 1:
             torch.distributed.broadcast(net.params_flat, 0)
         net.set_stream(torch.cuda.current_stream().cuda_stream)
@@ -336,6 +361,8 @@ def main(argv=None):
         validation_imgs = ImageSummary(writer, 'validation', td.label_colors, td.lid2name) if rank == 0 else None
 
         loop = StepLoop(net, sess, td, args.batch_size, args.num_workers, world, rank, bucket, args.allreduce_dtype)
+        if net.get_grad_clip() != 0.0:      # every rank holds the same arena: the same norms; rank 0 writes them
+            loop.grad_norms = GradNormSummary(writer, net.global_step)
 
         def gathered_aps(calc, with_summary=False):
             """{label: AP} over the WHOLE sample (train.py:317-323): data parallel, every rank's detections and ground
@@ -378,6 +405,10 @@ def main(argv=None):
                 e + 1, args.epochs, tl['total'], tl['localization'], tl['confidence'], tl['l2']))
             say('[i] Valid {:>2}/{}  total {:.4f}  localization {:.4f}  confidence {:.4f}  l2 {:.4f}'.format(
                 e + 1, args.epochs, vl['total'], vl['localization'], vl['confidence'], vl['l2']))
+            if loop.grad_norms is not None:
+                gn = loop.grad_norms.push(e + 1)
+                say('[i] Grad  {:>2}/{}  norm median {:.4g}  max {:.4g}  clipped {}  skipped {}  of {} updates'.format(
+                    e + 1, args.epochs, gn['median'], gn['max'], gn['clipped'], gn['skipped'], gn['updates']))
             # VOC07 11-point AP on the GPU, over all ranks' samples
             APs = gathered_aps(training_ap_calc); mAP = APs2mAP(APs)
             training_ap.push(e + 1, mAP, APs)
