@@ -174,6 +174,13 @@ SIGNATURES = {
     'ssd_get_grad_norm_step': (i32, [handle, i32, vp]),
     'ssd_op_grad_norm_ws_bytes': (sz, [sz]),
     'ssd_op_momentum_update_clipped': (i32, [vp, vp, vp, sz, f32, f32, f32, f32, vp, vp, vp]),
+    'ssd_set_update_rule': (i32, [handle, vp]),
+    'ssd_get_update_rule': (i32, [handle, vp]),
+    'ssd_get_adam_step': (i32, [handle, p_i64]),
+    'ssd_set_adam_step': (i32, [handle, C.c_longlong]),
+    'ssd_save_second_moment': (i32, [handle, cstr, vp, sz]),
+    'ssd_load_second_moment': (i32, [handle, cstr, vp, sz]),
+    'ssd_op_adamw_update': (i32, [vp, vp, vp, vp, sz, sz, f32, f32, f32, f32, f32, C.c_longlong, f32, f32, vp, vp, vp]),
     'ssd_train_step_dev': (i32, [handle, vp, vp, i32]),
     'ssd_eval_step_dev': (i32, [handle, vp, vp, i32]),
     'ssd_infer_dev': (i32, [handle, vp, i32]),

@@ -1250,6 +1250,46 @@ int ssd_get_grad_norm_step(ssd_handle h, int steps_back, float out[2]) {
     n.get_grad_norm_step(steps_back, out);
     API_END
 }
+// ... and an update rule: the hyper-parameters in the order beta1, beta2, eps, decay (ops.h adamw_check), then the kind
+static_assert(SSD_UPDATE_MOMENTUM == ssd::UPDATE_MOMENTUM && SSD_UPDATE_ADAMW == ssd::UPDATE_ADAMW, "ops.h mirrors the ABI's kinds");
+int ssd_set_update_rule(ssd_handle h, const ssd_update_rule_config* cfg) {
+    API_BEGIN
+    SSD_REQUIRE(cfg != nullptr, "update rule: null configuration");
+    adamw_check(cfg->beta1, cfg->beta2, cfg->eps, cfg->decay);
+    SSD_REQUIRE(cfg->kind == SSD_UPDATE_MOMENTUM || cfg->kind == SSD_UPDATE_ADAMW,
+                "update rule: kind %d is neither SSD_UPDATE_MOMENTUM nor SSD_UPDATE_ADAMW", cfg->kind);
+    Net& n = N(h);
+    DeviceGuard dev_guard_(n.device());
+    n.set_update_rule(cfg->kind, cfg->beta1, cfg->beta2, cfg->eps, cfg->decay == 0.f ? 0.f : cfg->decay);
+    API_END
+}
+int ssd_get_update_rule(ssd_handle h, ssd_update_rule_config* cfg) {
+    API_BEGIN
+    SSD_REQUIRE(cfg != nullptr, "update rule: null configuration");
+    N(h).get_update_rule(&cfg->kind, &cfg->beta1, &cfg->beta2, &cfg->eps, &cfg->decay);
+    API_END
+}
+int ssd_get_adam_step(ssd_handle h, long long* t) {
+    API_BEGIN_NET(h)
+    SSD_REQUIRE(t != nullptr, "null argument");
+    *t = n.adam_step();
+    API_END
+}
+int ssd_set_adam_step(ssd_handle h, long long t) {
+    API_BEGIN_NET(h)
+    n.set_adam_step(t);
+    API_END
+}
+int ssd_save_second_moment(ssd_handle h, const char* name, float* data, size_t count) {
+    API_BEGIN_NET(h)
+    n.save_variable(name, data, count, 3);
+    API_END
+}
+int ssd_load_second_moment(ssd_handle h, const char* name, const float* data, size_t count) {
+    API_BEGIN_NET(h)
+    n.load_variable(name, data, count, 3);
+    API_END
+}
 int ssd_null_gradients_dev(ssd_handle h) {
     API_BEGIN_NET(h)
     n.null_gradients_step();
@@ -2013,6 +2053,16 @@ int ssd_op_momentum_update_clipped(float* w, float* acc, const float* g, size_t 
     check_grad_clip(max_norm);
     SSD_REQUIRE(w && acc && g && (max_norm == 0.f || ws_dev), "null buffer");
     momentum_update_clipped(w, acc, g, n, lr, momentum, grad_scale, max_norm, ws_dev, report_dev, (hipStream_t)stream);
+    API_END
+}
+int ssd_op_adamw_update(float* w, float* m, float* v, const float* g, size_t n, size_t n_decay, float lr, float beta1, float beta2,
+                        float eps, float decay, long long t, float grad_scale, float max_norm, void* ws_dev, float* report_dev,
+                        void* stream) {
+    API_BEGIN
+    adamw_check(beta1, beta2, eps, decay);
+    check_grad_clip(max_norm);
+    SSD_REQUIRE(w && m && v && g && (max_norm == 0.f || ws_dev), "null buffer");
+    adamw_update(w, m, v, g, n, n_decay, lr, beta1, beta2, eps, decay, t, grad_scale, max_norm, ws_dev, report_dev, (hipStream_t)stream);
     API_END
 }
 int ssd_op_clock_monitor(unsigned* out_dev, int nsamples, unsigned period_ticks, void* stream) {

@@ -138,7 +138,14 @@ public:
     float grad_clip() const { return clip_max_norm_; }
     // {norm, factor} of the last clipped update (steps_back = 0) or of one of the LOSS_RING - 2 before it: waits for THAT update only
     void get_grad_norm_step(int steps_back, float out[2]);
-    void null_gradients_step();                                         // gradient arena of a step without samples
+    // which rule apply_gradients runs from the next update on: 0 momentum (the default), 1 AdamW with its four hyper-parameters
+    // (ops.h adamw_update); the caller has checked the values.  A DIFFERENT kind zeroes the accumulators and the count of AdamW
+    // updates on the handle's stream; the same kind keeps them.  The second moment is allocated on the first switch to AdamW.
+    void set_update_rule(int kind, float b1, float b2, float eps, float decay);
+    void get_update_rule(int* kind, float* b1, float* b2, float* eps, float* decay) const;
+    long long adam_step() const { return adam_t_; }      // AdamW updates enqueued since the state was zeroed (skipped ones count)
+    void set_adam_step(long long t);
+    void null_gradients_step();                                        // gradient arena of a step without samples
     void set_optimizer(const float* lr_values, const long long* bounds, int n, float momentum, float wd);
 
     // host-buffer conveniences
@@ -154,8 +161,8 @@ public:
     void set_result(const float* pred_dev, int b);
 
     const std::vector<Variable>& variables() const { return vars_; }
-    void load_variable(const char* name, const float* host, size_t count, int which);   // 0 params, 2 momentum
-    void save_variable(const char* name, float* host, size_t count, int which);         // 0 params, 1 grads, 2 momentum
+    void load_variable(const char* name, const float* host, size_t count, int which);   // 0 params, 2 momentum, 3 second moment
+    void save_variable(const char* name, float* host, size_t count, int which);         // 0 params, 1 grads, 2 momentum, 3 second moment
     void activation(const char* name, int b, float* out, size_t count);
     void activation_shape(const char* name, int* H, int* W, int* C) const;
     void pool_fusion(int* out, int cap, int* count) const;      // per 2x2 stride-2 pool in graph order: bit 0 fused forward, bit 1 fused backward
@@ -368,6 +375,11 @@ private:
     float* clip_dev_ = nullptr;
     hipEvent_t ev_clip_[LOSS_RING] = {};
     long long clip_seq_ = -1;             // clipped (or measured) updates so far - 1
+    // the update rule (apply_gradients): under AdamW mom_ is the first moment and adam_v_ the second
+    int rule_kind_ = 0;                   // UPDATE_MOMENTUM / UPDATE_ADAMW (ops.h)
+    float adam_b1_ = 0.9f, adam_b2_ = 0.999f, adam_eps_ = 1e-8f, adam_decay_ = 0.01f;
+    long long adam_t_ = 0;
+    float* adam_v_ = nullptr;             // nparams_ floats from hip_, null until the handle is first put under AdamW
     double* anchors_dev_ = nullptr;
     int* anchors_abs_dev_ = nullptr;
     void* detect_ws_ = nullptr;

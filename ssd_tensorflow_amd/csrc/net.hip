@@ -1723,7 +1723,21 @@ void Net::apply_gradients(float grad_scale) {
     SSD_REQUIRE(training_, "handle was created with training = 0");
     g_prof = &prof_;
     prof_.layer = "optimizer";
-    if (clip_max_norm_ == 0.f) {
+    if (rule_kind_ == UPDATE_ADAMW) {
+        // the momentum branches below with the other rule; t counts this update, skipped by the clipped kernel or not
+        ++adam_t_;
+        float* report = nullptr;
+        int slot = 0;
+        if (clip_max_norm_ != 0.f) {
+            ++clip_seq_;
+            slot = (int)(clip_seq_ % LOSS_RING);
+            if (clip_seq_ >= LOSS_RING) HIP_OK(hipEventSynchronize(ev_clip_[slot]));
+            report = clip_dev_ + 2 * slot;
+        }
+        adamw_update(params_, mom_, adam_v_, grads_, nparams_, nfilters_, current_lr(), adam_b1_, adam_b2_, adam_eps_, adam_decay_,
+                     adam_t_, grad_scale, clip_max_norm_, clip_ws_, report, stream_);
+        if (clip_max_norm_ != 0.f) HIP_OK(hipEventRecord(ev_clip_[slot], stream_));
+    } else if (clip_max_norm_ == 0.f) {
         momentum_update(params_, mom_, grads_, nparams_, current_lr(), momentum_, grad_scale, stream_);
     } else {
         // the slot's previous update (LOSS_RING updates ago) has long finished; nothing here waits for this one
@@ -1740,6 +1754,35 @@ void Net::apply_gradients(float grad_scale) {
 void Net::set_grad_clip(float max_norm) {
     SSD_REQUIRE(training_, "gradient clipping: the handle was created with training = 0");
     clip_max_norm_ = max_norm;
+}
+
+void Net::set_update_rule(int kind, float b1, float b2, float eps, float decay) {
+    SSD_REQUIRE(training_, "update rule: the handle was created with training = 0");
+    const size_t bytes = nparams_ * sizeof(float);
+    if (kind == UPDATE_ADAMW && !adam_v_) {
+        // on first use, so that a handle that stays under momentum holds the memory it held without the rule
+        adam_v_ = static_cast<float*>(hip_.mem(bytes));
+        HIP_OK(hipMemsetAsync(adam_v_, 0, bytes, stream_));
+    }
+    if (kind != rule_kind_) {
+        // the accumulators mean different things under the two rules
+        HIP_OK(hipMemsetAsync(mom_, 0, bytes, stream_));
+        if (adam_v_) HIP_OK(hipMemsetAsync(adam_v_, 0, bytes, stream_));
+        adam_t_ = 0;
+    }
+    rule_kind_ = kind;
+    adam_b1_ = b1; adam_b2_ = b2; adam_eps_ = eps; adam_decay_ = decay;
+}
+
+void Net::get_update_rule(int* kind, float* b1, float* b2, float* eps, float* decay) const {
+    *kind = rule_kind_;
+    *b1 = adam_b1_; *b2 = adam_b2_; *eps = adam_eps_; *decay = adam_decay_;
+}
+
+void Net::set_adam_step(long long t) {
+    SSD_REQUIRE(training_, "update rule: the handle was created with training = 0");
+    SSD_REQUIRE(t >= 0, "update rule: the count of AdamW updates must be >= 0, got %lld", t);
+    adam_t_ = t;
 }
 
 void Net::get_grad_norm_step(int steps_back, float out[2]) {
@@ -1836,7 +1879,8 @@ const Variable& Net::find_var(const char* name) const {
 void Net::load_variable(const char* name, const float* host, size_t count, int which) {
     const Variable& v = find_var(name);
     SSD_REQUIRE(count == v.count(), "variable %s holds %zu floats, got %zu", name, v.count(), count);
-    float* base = which == 0 ? params_ : mom_;
+    SSD_REQUIRE(which != 3 || adam_v_, "second moment of %s: the handle has never been under AdamW (ssd_set_update_rule)", name);
+    float* base = which == 0 ? params_ : which == 3 ? adam_v_ : mom_;
     SSD_REQUIRE(base != nullptr, "arena not allocated (training = 0?)");
     HIP_OK(hipStreamSynchronize(stream_));
     HIP_OK(hipMemcpy2D(base + v.off, v.pitch * sizeof(float), host, v.width * sizeof(float), v.width * sizeof(float), v.rows,
@@ -1846,7 +1890,8 @@ void Net::load_variable(const char* name, const float* host, size_t count, int w
 void Net::save_variable(const char* name, float* host, size_t count, int which) {
     const Variable& v = find_var(name);
     SSD_REQUIRE(count == v.count(), "variable %s holds %zu floats, got %zu", name, v.count(), count);
-    const float* base = which == 0 ? params_ : (which == 1 ? grads_ : mom_);
+    SSD_REQUIRE(which != 3 || adam_v_, "second moment of %s: the handle has never been under AdamW (ssd_set_update_rule)", name);
+    const float* base = which == 0 ? params_ : (which == 1 ? grads_ : which == 3 ? adam_v_ : mom_);
     SSD_REQUIRE(base != nullptr, "arena not allocated (training = 0?)");
     HIP_OK(hipStreamSynchronize(stream_));
     HIP_OK(hipMemcpy2D(host, v.width * sizeof(float), base + v.off, v.pitch * sizeof(float), v.width * sizeof(float), v.rows,

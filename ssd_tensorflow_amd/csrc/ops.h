@@ -130,6 +130,28 @@ constexpr int GRAD_NORM_UNROLL = 4;                // passes of the grid whose l
 size_t grad_norm_ws_bytes(size_t n);
 void momentum_update_clipped(float* w, float* acc, const float* g, size_t n, float lr, float momentum, float gscale, float max_norm,
                              void* ws, float* report, hipStream_t s);
+// the first two of those launches alone (ProfScope "grad_norm"): what they leave at the head of ws, for the update that follows
+struct ClipState {
+    float gscale;       // grad_scale * factor
+    unsigned skip;      // the sum of squares was not finite: the update touches nothing
+    unsigned pad[2];
+};
+static_assert(sizeof(ClipState) == 16, "the partials behind it are read as aligned doubles");
+void grad_norm_pass(const float* g, size_t n, float gscale, float max_norm, void* ws, float* report, hipStream_t s);
+
+// ---- AdamW (optim.hip, compiled without fused multiply-add; contract in include/ssdvgg_hip.h "update rule").
+// m: the momentum arena as first moment; v: the second moment; both n floats.  Decoupled decay on elements [0, n_decay), any
+// n_decay in 0..n.  t >= 1: the count of AdamW updates since the state was zeroed, this one included.  The host scalars (1 - beta,
+// the two bias corrections, lr * decay) are computed here in double and rounded to float once.  max_norm == 0: one launch,
+// adamw_kernel<false> (ProfScope "adamw_update").  Otherwise grad_norm_pass and adamw_kernel<true> ("adamw_update_clipped"), which
+// reads {scale, skip} from ws like momentum_clipped_kernel.  adamw_check refuses hyper-parameters outside their ranges
+// (beta1, beta2, eps, decay in that order).
+constexpr int UPDATE_MOMENTUM = 0, UPDATE_ADAMW = 1;      // SSD_UPDATE_* of the C ABI (api.hip asserts the match)
+constexpr int ADAMW_BLOCK = 256;                 // one pass of the grid is ADAMW_BLOCK * ADAMW_GRID_CAP * 4 floats
+constexpr int ADAMW_GRID_CAP = 256 * 16;
+void adamw_check(float b1, float b2, float eps, float decay);
+void adamw_update(float* w, float* m, float* v, const float* g, size_t n, size_t n_decay, float lr, float b1, float b2, float eps,
+                  float decay, long long t, float gscale, float max_norm, void* ws, float* report, hipStream_t s);
 
 // gradients of a step without samples (a data-parallel rank whose shard of a short last batch is empty)
 void null_gradients(const float* w, float* g, size_t nfilters, size_t n, float wd, hipStream_t s);

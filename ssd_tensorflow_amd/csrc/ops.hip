@@ -1911,13 +1911,7 @@ void momentum_update(float* w, float* acc, const float* g, size_t n, float lr, f
 }
 
 // ---- the same update with the gradient clipped by its global norm (ops.h; contract in include/ssdvgg_hip.h)
-// Head of the workspace: what the finish kernel leaves for the update; the per-block partials follow it.
-struct ClipState {
-    float gscale;       // grad_scale * factor
-    unsigned skip;      // the sum of squares was not finite: the update touches nothing
-    unsigned pad[2];
-};
-static_assert(sizeof(ClipState) == 16, "the partials behind it are read as aligned doubles");
+// Head of the workspace: ClipState (ops.h), what the finish kernel leaves for the update; the per-block partials follow it.
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -1999,24 +1993,26 @@ __global__ __launch_bounds__(256) void momentum_clipped_kernel(float* __restrict
 static inline int grad_norm_grid(size_t n) { return grid_for(n / 4, GRAD_NORM_BLOCK, GRAD_NORM_GRID_CAP); }
 size_t grad_norm_ws_bytes(size_t n) { return sizeof(ClipState) + (size_t)grad_norm_grid(n) * sizeof(double); }
 
-void momentum_update_clipped(float* w, float* acc, const float* g, size_t n, float lr, float momentum, float gscale, float max_norm,
-                             void* ws, float* report, hipStream_t s) {
-    if (max_norm == 0.f) return momentum_update(w, acc, g, n, lr, momentum, gscale, s);
+void grad_norm_pass(const float* g, size_t n, float gscale, float max_norm, void* ws, float* report, hipStream_t s) {
     SSD_REQUIRE(max_norm > 0.f, "gradient clipping: max_norm %g is neither 0 (off), a number > 0 nor +inf", (double)max_norm);
     SSD_REQUIRE(n % 4 == 0, "momentum: arena size must be a multiple of 4");
     SSD_REQUIRE(ws != nullptr && (uintptr_t)ws % 16 == 0, "gradient clipping: the workspace must be 16-byte aligned");
     ClipState* st = static_cast<ClipState*>(ws);
     double* partial = reinterpret_cast<double*>(st + 1);
     const int grid = grad_norm_grid(n);
-    {
-        ProfScope prof("grad_norm", 2.0 * n, 4.0 * n, s);
-        hipLaunchKernelGGL(grad_norm_kernel, dim3(grid), dim3(GRAD_NORM_BLOCK), 0, s, g, n / 4, partial);
-        hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(GRAD_NORM_BLOCK), 0, s, (const double*)partial, grid, gscale, max_norm,
-                           st, report);
-    }
+    ProfScope prof("grad_norm", 2.0 * n, 4.0 * n, s);
+    hipLaunchKernelGGL(grad_norm_kernel, dim3(grid), dim3(GRAD_NORM_BLOCK), 0, s, g, n / 4, partial);
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(GRAD_NORM_BLOCK), 0, s, (const double*)partial, grid, gscale, max_norm,
+                       st, report);
+}
+
+void momentum_update_clipped(float* w, float* acc, const float* g, size_t n, float lr, float momentum, float gscale, float max_norm,
+                             void* ws, float* report, hipStream_t s) {
+    if (max_norm == 0.f) return momentum_update(w, acc, g, n, lr, momentum, gscale, s);
+    grad_norm_pass(g, n, gscale, max_norm, ws, report, s);
     ProfScope prof("momentum_update_clipped", 0.0, 20.0 * n, s);
     hipLaunchKernelGGL(momentum_clipped_kernel, dim3(grid_for(n / 4, 256, 256 * 16)), dim3(256), 0, s, w, acc, g, n / 4, lr, momentum,
-                       (const ClipState*)st);
+                       (const ClipState*)ws);
     HIP_OK(hipGetLastError());
 }
 

@@ -100,6 +100,41 @@ def checkpoint_clip_norm(ck):
     return float(ck['__clip_norm__'])
 
 
+# update rules of a training handle (include/ssdvgg_hip.h SSD_UPDATE_*): the reference's momentum, or AdamW
+UPDATE_KINDS = {'momentum': 0, 'adamw': 1}
+ADAM_DEFAULTS = (0.9, 0.999, 1e-8, 0.01)      # beta1, beta2, eps, decay
+
+
+class UpdateRuleConfig(C.Structure):
+    """ssd_update_rule_config of the C ABI"""
+    _fields_ = [('kind', C.c_int), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float), ('decay', C.c_float)]
+
+
+def update_rule_config(optimizer='momentum', adam_beta1=0.9, adam_beta2=0.999, adam_eps=1e-8, adam_decay=0.01):
+    """The ABI's configuration of an update rule given by name (include/ssdvgg_hip.h).  beta1 or beta2 outside
+    [0, 1), an eps that is not a finite number > 0, a decay that is not a finite number >= 0 (as float32, what the library
+    gets), or a bad name, in that order: ValueError."""
+    b1, b2, eps, decay = (float(np.float32(x)) for x in (adam_beta1, adam_beta2, adam_eps, adam_decay))
+    for name, b in (('beta1', b1), ('beta2', b2)):
+        if not 0.0 <= b < 1.0:
+            raise ValueError('update rule: %s must lie in [0, 1), got %r' % (name, b))
+    if not (np.isfinite(eps) and eps > 0.0):
+        raise ValueError('update rule: eps must be a finite number > 0, got %r' % (adam_eps,))
+    if not (np.isfinite(decay) and decay >= 0.0):
+        raise ValueError('update rule: decay must be a finite number >= 0, got %r' % (adam_decay,))
+    if optimizer not in UPDATE_KINDS:
+        raise ValueError('update rule must be one of %s, got %r' % (sorted(UPDATE_KINDS), optimizer))
+    return UpdateRuleConfig(UPDATE_KINDS[optimizer], b1, b2, eps, decay)
+
+
+def checkpoint_update_rule(ck):
+    """(optimizer name, beta1, beta2, eps, decay) of an opened checkpoint; one without __optimizer__ is a momentum run's."""
+    if '__optimizer__' not in ck.files:
+        return ('momentum',) + ADAM_DEFAULTS
+    return (str(ck['__optimizer__']),) + tuple(float(np.float32(ck[k])) for k in
+                                               ('__adam_beta1__', '__adam_beta2__', '__adam_eps__', '__adam_decay__'))
+
+
 class _Token:
     """An opaque stand-in for a TF tensor/op handle; only identity matters."""
     def __init__(self, name):
@@ -361,18 +396,23 @@ class SSDVGG:
 
     # ------------------------------------------------------------------ optimizer
     def build_optimizer(self, learning_rate=0.001, weight_decay=0.0005, momentum=0.9, global_step=None, loss='mining',
-                        focal_gamma=2.0, focal_alpha=0.25, loc_loss='smooth_l1', loc_weight=1.0, clip_norm=0.0):
+                        focal_gamma=2.0, focal_alpha=0.25, loc_loss='smooth_l1', loc_weight=1.0, clip_norm=0.0, optimizer='momentum',
+                        adam_beta1=0.9, adam_beta2=0.999, adam_eps=1e-8, adam_decay=0.01):
         """ssdvgg.py:375-599.  learning_rate: float or LearningRate (train.py:43-47).  loss: 'mining' (the reference's 3:1
         hard-negative mining) or 'focal' (every anchor, damped by (1 - p_t)^focal_gamma and weighted focal_alpha on positives,
         1 - focal_alpha on background; a sample without positives still trains its background anchors).
         loc_loss: 'smooth_l1' (the reference's, on the four encoded offsets) or 'giou' (loc_weight * (1 - GIoU) of the predicted
         against the ground-truth box of every positive anchor); either goes with either `loss`.
-        clip_norm: clip the gradient by its global norm in the update (0, the default: off; inf: measure only)."""
+        clip_norm: clip the gradient by its global norm in the update (0, the default: off; inf: measure only).
+        optimizer: 'momentum' (the reference's rule, the default) or 'adamw'  with adam_beta1, adam_beta2, adam_eps
+        and the decoupled adam_decay on the filters; under 'adamw' `momentum` is ignored and `weight_decay` stays the L2 term of
+        the loss (0 gives pure AdamW).  Changing the rule zeroes the accumulators."""
         if not self.training:
             raise RuntimeError('build_from_* was called with training=False')
         self.set_loss(loss, focal_gamma, focal_alpha)
         self.set_loc_loss(loc_loss, loc_weight)
         self.set_grad_clip(clip_norm)
+        self.set_update_rule(optimizer, adam_beta1, adam_beta2, adam_eps, adam_decay)
         lr = learning_rate if isinstance(learning_rate, LearningRate) else LearningRate([learning_rate], [])
         vals = np.array(lr.values, np.float32)
         bnds = np.array(lr.boundaries + [0], np.int64)
@@ -394,13 +434,20 @@ class SSDVGG:
         lr = LearningRate(list(ck['__lr_values__']), list(ck['__lr_boundaries__']))
         loss, gamma, alpha = checkpoint_loss(ck)
         loc_loss, loc_weight = checkpoint_loc_loss(ck)
+        rule, b1, b2, eps, decay = checkpoint_update_rule(ck)
         self.build_optimizer(lr, float(ck['__weight_decay__']), float(ck['__momentum__']), int(ck['__global_step__']),
                              loss=loss, focal_gamma=gamma, focal_alpha=alpha, loc_loss=loc_loss, loc_weight=loc_weight,
-                             clip_norm=checkpoint_clip_norm(ck))
+                             clip_norm=checkpoint_clip_norm(ck), optimizer=rule, adam_beta1=b1, adam_beta2=b2, adam_eps=eps,
+                             adam_decay=decay)
         for k in ck.files:
             if k.startswith('__momentum__/'):
                 a = np.ascontiguousarray(ck[k], np.float32)
                 check(lib.ssd_load_momentum(self._h, k[len('__momentum__/'):].encode(), np_ptr(a), a.size))
+            elif k.startswith('__adam_v__/'):
+                a = np.ascontiguousarray(ck[k], np.float32)
+                check(lib.ssd_load_second_moment(self._h, k[len('__adam_v__/'):].encode(), np_ptr(a), a.size))
+        if rule == 'adamw':
+            check(lib.ssd_set_adam_step(self._h, int(ck['__adam_step__'])))
 
     def build_summaries(self, restore):
         """ssdvgg.py:625-649 builds TensorBoard histograms; observability is out of scope here."""
@@ -446,6 +493,17 @@ class SSDVGG:
     def save_momentum(self, names=None):
         return self._save(lib.ssd_save_momentum, names)
 
+    def save_second_moment(self, names=None):
+        """AdamW's second moment by variable name; an error while the handle has never been under AdamW"""
+        return self._save(lib.ssd_save_second_moment, names)
+
+    @property
+    def adam_step(self):
+        """AdamW updates since the accumulators were zeroed (the t of the bias corrections)"""
+        t = C.c_longlong()
+        check(lib.ssd_get_adam_step(self._h, C.byref(t)))
+        return t.value
+
     @property
     def global_step(self):
         s = C.c_longlong()
@@ -477,6 +535,12 @@ class SSDVGG:
             loc_loss, loc_weight = self.get_loc_loss()
             d.update(__loc_loss__=np.array(loc_loss), __loc_weight__=np.array(loc_weight))
             d.update(__clip_norm__=np.array(self.get_grad_clip()))
+            rule, b1, b2, eps, decay = self.get_update_rule()
+            if rule != 'momentum':      # (a momentum run's file holds the keys it held before the option)
+                d.update(__optimizer__=np.array(rule), __adam_beta1__=np.array(b1, np.float32), __adam_beta2__=np.array(b2, np.float32),
+                         __adam_eps__=np.array(eps, np.float32), __adam_decay__=np.array(decay, np.float32),
+                         __adam_step__=np.array(self.adam_step, np.int64))
+                d.update({'__adam_v__/' + k: v for k, v in self.save_second_moment().items()})
         np.savez(path, **d)
 
     # ------------------------------------------------------------------ steps
@@ -685,6 +749,19 @@ class SSDVGG:
         out = np.zeros(2, np.float32)
         check(lib.ssd_get_grad_norm_step(self._h, int(steps_back), np_ptr(out)))
         return float(out[0]), float(out[1])
+
+    def set_update_rule(self, optimizer='momentum', adam_beta1=0.9, adam_beta2=0.999, adam_eps=1e-8, adam_decay=0.01):
+        """The rule of the updates from the next one on (ssd_set_update_rule; build_optimizer).  Another rule than the handle's
+        zeroes the accumulators and the AdamW step count; the same rule with other hyper-parameters keeps them."""
+        cfg = update_rule_config(optimizer, adam_beta1, adam_beta2, adam_eps, adam_decay)
+        check(lib.ssd_set_update_rule(self._h, C.byref(cfg)))
+
+    def get_update_rule(self):
+        """(name, beta1, beta2, eps, decay) of the handle's update rule"""
+        cfg = UpdateRuleConfig()
+        check(lib.ssd_get_update_rule(self._h, C.byref(cfg)))
+        return ([k for k, v in UPDATE_KINDS.items() if v == cfg.kind][0], float(cfg.beta1), float(cfg.beta2), float(cfg.eps),
+                float(cfg.decay))
 
     def get_loss(self):
         """(name, focal_gamma, focal_alpha) of the handle's loss"""

@@ -180,6 +180,21 @@ def checkpoint_clip_norm(path):
         return of(ck)
 
 
+def checkpoint_update_rule(path):
+    """(--optimizer, beta1, beta2, eps, decay) of a checkpoint's run (a file without __optimizer__: a momentum run's)."""
+    from .ssdvgg import checkpoint_update_rule as of
+    with np.load(path, allow_pickle=False) as ck:
+        return of(ck)
+
+
+def resolved_weight_decay(weight_decay, optimizer):
+    """--weight-decay as the run uses it: the value given, else the reference's 0.0005 under momentum and 0 under adamw, whose
+    decay is the decoupled --adam-decay"""
+    if weight_decay is not None:
+        return weight_decay
+    return 0.0005 if optimizer == 'momentum' else 0.0
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser(description='Train the SSD')
     parser.add_argument('--name', default='test', help='project name')
@@ -192,7 +207,12 @@ def main(argv=None):
     parser.add_argument('--lr-values', type=str, default='0.00075;0.0001;0.00001', help='learning rate values')
     parser.add_argument('--lr-boundaries', type=str, default='320000;400000', help='learning rate chage boundaries (in batches)')
     parser.add_argument('--momentum', type=float, default=0.9, help='momentum for the optimizer')
-    parser.add_argument('--weight-decay', type=float, default=0.0005, help='L2 normalization factor')
+    parser.add_argument('--weight-decay', type=float, default=None, help='L2 normalization factor (the term in the loss and the gradient); default: 0.0005 under --optimizer momentum, 0 under adamw')
+    parser.add_argument('--optimizer', default='momentum', choices=['momentum', 'adamw'], help="the update rule: momentum = the reference's acc = m*acc + g; w -= lr*acc; adamw = AdamW on the GPU, exact in fp32, with a decoupled decay on the filters (DESIGN.md 35); composes with --clip-norm; --continue-training takes the checkpoint's")
+    parser.add_argument('--adam-beta1', type=float, default=0.9, help='--optimizer adamw: decay rate of the first moment, in [0, 1)')
+    parser.add_argument('--adam-beta2', type=float, default=0.999, help='--optimizer adamw: decay rate of the second moment, in [0, 1)')
+    parser.add_argument('--adam-eps', type=float, default=1e-8, help='--optimizer adamw: the term added to the root of the second moment, > 0')
+    parser.add_argument('--adam-decay', type=float, default=0.01, help='--optimizer adamw: the decoupled weight decay, w -= lr * decay * w on the filters, >= 0')
     parser.add_argument('--continue-training', type=str2bool, default='False', help='continue training from the latest checkpoint')
     parser.add_argument('--num-workers', type=int, default=0, help='number of parallel generators')
     parser.add_argument('--decoder', default='pillow', choices=['pillow', 'gpu'], help='a real --data-dir: pillow = the workers decode the files; gpu = they run the Huffman stage only and the GPU decodes in front of the augmentation kernel')
@@ -233,7 +253,6 @@ def main(argv=None):
     say('[i] Learning rate values: ', args.lr_values)
     say('[i] Learning rate boundaries: ', args.lr_boundaries)
     say('[i] Momentum:             ', args.momentum)
-    say('[i] Weight decay:         ', args.weight_decay)
     say('[i] Continue:             ', args.continue_training)
     say('[i] Number of workers:    ', args.num_workers)
     say('[i] Decoder:              ', args.decoder)
@@ -276,6 +295,11 @@ def main(argv=None):
         if args.clip_norm != 0.0 and args.clip_norm != ck_clip:
             say("[i] --clip-norm %g disagrees with the checkpoint: continuing with its value, %g" % (args.clip_norm, ck_clip))
         args.clip_norm = ck_clip
+        ck_rule = checkpoint_update_rule(ckpt)
+        asked = (args.optimizer,) + tuple(float(np.float32(x)) for x in (args.adam_beta1, args.adam_beta2, args.adam_eps, args.adam_decay))
+        if args.optimizer != 'momentum' and asked != ck_rule:
+            say("[i] --optimizer %s disagrees with the checkpoint: continuing with its rule, '%s'" % (args.optimizer, ck_rule[0]))
+        args.optimizer, args.adam_beta1, args.adam_beta2, args.adam_eps, args.adam_decay = ck_rule
     elif rank == 0:
         try:
             os.makedirs(args.name, exist_ok=True)
@@ -295,6 +319,16 @@ def main(argv=None):
         grad_clip_config(args.clip_norm)
     except ValueError as e:
         print('[!] Bad --clip-norm:', str(e)); return 1
+    try:
+        from .ssdvgg import update_rule_config
+        update_rule_config(args.optimizer, args.adam_beta1, args.adam_beta2, args.adam_eps, args.adam_decay)
+    except ValueError as e:
+        print('[!] Bad --optimizer:', str(e)); return 1
+    args.weight_decay = resolved_weight_decay(args.weight_decay, args.optimizer)
+    say('[i] Update rule:          ', args.optimizer if args.optimizer == 'momentum' else '%s (beta1 %g, beta2 %g, eps %g)' % (
+        args.optimizer, args.adam_beta1, args.adam_beta2, args.adam_eps))
+    say('[i] Weight decay:         ', args.weight_decay, '(L2 term of the loss)')
+    say('[i] Decoupled decay:      ', '%g' % args.adam_decay if args.optimizer == 'adamw' else 'none')
     say('[i] Loss:                 ', args.loss if args.loss != 'focal' else 'focal (gamma %g, alpha %g)' % (args.focal_gamma, args.focal_alpha))
     say('[i] Localization loss:    ', args.loc_loss if args.loc_loss == 'smooth_l1' else '%s (weight %g)' % (args.loc_loss, args.loc_weight))
     say('[i] Gradient clipping:    ', 'off' if args.clip_norm == 0 else 'norm measured, never clipped' if math.isinf(args.clip_norm) else 'global norm <= %g' % args.clip_norm)
@@ -335,7 +369,9 @@ def main(argv=None):
                                background_prior=args.focal_prior if args.loss == 'focal' else None)
             net.build_optimizer(learning_rate=lr, weight_decay=args.weight_decay, momentum=args.momentum, loss=args.loss,
                                 focal_gamma=args.focal_gamma, focal_alpha=args.focal_alpha, loc_loss=args.loc_loss,
-                                loc_weight=args.loc_weight, clip_norm=args.clip_norm)
+                                loc_weight=args.loc_weight, clip_norm=args.clip_norm, optimizer=args.optimizer,
+                                adam_beta1=args.adam_beta1, adam_beta2=args.adam_beta2, adam_eps=args.adam_eps,
+                                adam_decay=args.adam_decay)
         if world > 1:
             torch.distributed.broadcast(net.params_flat, 0)
         net.set_stream(torch.cuda.current_stream().cuda_stream)
