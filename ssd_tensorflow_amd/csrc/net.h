@@ -19,11 +19,8 @@ struct Tensor {
     int H = 0, W = 0, C = 0;
     bool relu_out = false;   // produced by conv+relu: gradients written into it get the relu mask
     int consumers = 0;       // ops reading it in forward
-    int done = 0;            // backward bookkeeping
-    int gstream = 0;         // backward: stream class (0 main, 1 side) of the last kernel that wrote grad ...
-    long gseq = 0;           // ... and its number in that class' issue order (net.hip bw_need)
     hipEvent_t gev = nullptr;    // optional: recorded behind every kernel that writes grad, so a reader on the other class waits for
-    bool gev_set = false;        // THAT kernel instead of everything its class has been given (the small heads' feature maps)
+                                 // THAT kernel instead of everything its class has been given (what a pass knows of it: Net::BwdPass)
     bool data_f32 = true;    // storage of data: fp32, or bf16 (bf16 configuration, every tensor but the image and the head outputs)
     bool grad_f32 = true;    // storage of grad
     void* data = nullptr;
@@ -200,7 +197,7 @@ public:
     long long global_step = 0;
     Profiler& profiler() { return prof_; }
     void set_overlap(bool on) { overlap_ = on; }
-    void set_wino_dual(int mode) { wino_dual_ = mode; }      // backward transforms a Winograd layer's dy once for both gradients (backward_step)
+    void set_wino_dual(int mode) { wino_dual_ = mode; }      // backward transforms a Winograd layer's dy once for both gradients (wgrad_handoff)
 
 private:
     int add_tensor(const std::string& name, int H, int W, int C, bool relu_out);
@@ -261,20 +258,49 @@ private:
         std::pair<size_t, size_t> end_stage();      // (offset, count) of the stage; the next one starts below it
     private:
         size_t final_lo() const;         // lowest arena offset such that every filter at or above it has its final gradient
-    } bw_;
-    // backward stream classes: 0 = a lane's main stream, 1 = its side stream.  bw_issued_[c] counts the kernels class c has been
-    // given that write a gradient, bw_seen_[x][y] is the count of class y that class x has already been made to wait for
-    long bw_issued_[2] = {0, 0}, bw_seen_[2][2] = {{0, 0}, {0, 0}};
+    };
+    // The state of one backward pass, the counterpart of FwdPass.  It lives in the handle because a pass spans backward_begin and
+    // several backward_step calls; backward_begin resets all of it (begin), nothing else does.
+    // Stream classes: 0 = the main stream, 1 = the side stream (bw_class).  issued[c] counts the kernels class c has been given that
+    // write a gradient, seen[x][y] is the count of class y that class x has already been made to wait for.
+    struct BwdPass {
+        struct Grad {                    // what the pass knows of one tensor's gradient
+            int done = 0;                // consumers whose data gradient has been issued
+            int gstream = 0;             // stream class of the last kernel that wrote it ...
+            long gseq = 0;               // ... and that kernel's number in the class' issue order (bw_need)
+            bool gev_set = false;        // Tensor::gev stands behind that kernel
+        };
+        int b = 0;
+        BwProgress progress;
+        long issued[2] = {0, 0}, seen[2][2] = {{0, 0}, {0, 0}};
+        bool first_on_main = false;      // the first layer's weight gradient was issued on the main stream (wgrad_handoff)
+        bool first_fused = false;        // it was computed inside the next layer's data gradient instead (dgrad_first_wgrad) ...
+        int fused_first_out = -1;        // ... and this tensor's gradient (conv1_1's output) was not materialised
+        int ya_turn = 1;                 // which of wino_ya_ / wino_ya2_ the next dual transform writes (wgrad_handoff)
+        bool side_used = false;          // the current stage gave the weight-gradient stream work (backward_join)
+        std::vector<Grad> t;             // indexed like tensors_
+        void begin(const Net* n, int batch);
+    } bwd_;
     hipEvent_t ev_m2s_ = nullptr;        // main -> side hand-off
-    bool bw_first_on_main_ = false;      // the first layer's weight gradient was issued on the main stream (backward_step)
     bool fuse_first_wgrad_ = false;      // bf16: conv1_1's weight gradient inside conv1_2's data gradient where the kernel applies (plan_pool_fusion)
-    bool bw_first_fused_ = false;        // ... and this backward pass took it
-    int fused_first_out_ = -1;           // the tensor whose gradient that pass did not materialise (conv1_1's output)
-    // ya: the layer's transformed dy where the main stream's dual transform has already written it (backward_step), else nullptr
+    int first_conv_ = -1;                // op index of the convolution that reads the image (plan_pool_fusion)
+    // ya: the layer's transformed dy where the main stream's dual transform has already written it (wgrad_handoff), else nullptr
     void launch_wgrad(int op_index, int b, hipStream_t ws, const float* ya = nullptr);
     // the data gradient of one convolution into dst (= in, or the input of the pool `up` it un-pools), on ds
     // (yt_done: wino_yt_ already holds this layer's transformed dy)
     void launch_dgrad(const Op& op, const ConvDesc& d, const Op* up, Tensor& dst, bool mask, int cls, hipStream_t ds, bool yt_done = false);
+    // A backward pass (net.hip, "Backward"): backward_step is the stage loop, the chain and ablation skips and backward_join; the
+    // members below do the rest.  Every cross-stream hand-off of backward goes through one of bw_sync / bw_need / bw_wrote,
+    // wgrad_handoff (and its primitive wgrad_wait), backward_join and launch_wgrad's release of a ya buffer.
+    struct WgradStream { hipStream_t ws; bool side, on_main; };
+    void backward_conv(int op_index);
+    WgradStream wgrad_stream_for(bool need_dx) const;
+    const float* wgrad_handoff(const Op& op, const ConvDesc& d, int cls, bool need_dx, const WgradStream& w);
+    void wgrad_wait(hipStream_t ws, hipEvent_t carried, hipStream_t from);
+    bool dgrad_first_wgrad(const Op& op, const ConvDesc& d, const Op* up, bool mask, int cls, hipStream_t ds);
+    void backward_pool(int op_index);
+    void backward_l2norm(int op_index);
+    void backward_join(bool finished, bool sync_main);
     // Round 6 (bf16): the latency-bound tail as one launch per direction (conv.h TailStage; net.hip plan_tail_chain).  chain_first_ =
     // op index of the first 1x1 layer below the 10x10 map (vgg300: conv9_1, vgg512: conv10_1), -1: off; in_chain_[op] marks the
     // extra layers from there on and the multibox heads that read them.
@@ -289,7 +315,7 @@ private:
     // transformed dy / dx of the data gradient (main stream: wino_yt_, wino_xw_), the transformed dy and the slabs of the weight
     // gradient (weight-gradient stream: wino_ya_, wino_slab_).  One stream runs each kind in order, so one buffer per kind suffices --
     // but for the transformed dy of the weight gradient where the MAIN stream writes it (wino_dual_: one transform of dy for both
-    // gradients, backward_step): two buffers taken in turn (wino_ya_, wino_ya2_), so that the transform of one layer does not wait for
+    // gradients, wgrad_handoff): two buffers taken in turn (wino_ya_, wino_ya2_), so that the transform of one layer does not wait for
     // the weight-gradient stream's GEMM of the layer before.  ev_ya_free_[k]: the last GEMM that read buffer k, recorded on the
     // weight-gradient stream; the main stream waits for it before it writes the buffer again.
     void plan_winograd();
@@ -302,7 +328,6 @@ private:
     float* wino_ya2_ = nullptr;
     hipEvent_t ev_ya_free_[2] = {nullptr, nullptr};
     bool ya_free_set_[2] = {false, false};
-    int ya_turn_ = 0;
     int wino_dual_ = 1;                  // 0 off, 1 the layers of the shape rule (wino_dual_max_c_), 2 every layer with both gradients in this form
     int wino_dual_max_c_ = 128;          // the rule: max(Ci, Co) <= this (SSD_WINO_DUAL_MAX_C): where the GEMMs beside the transform are HBM-bound themselves
     // A forward pass (net.hip, "steps"): forward builds the lanes, walks fwd_order_ and joins; the members below do the rest.
@@ -334,13 +359,13 @@ private:
     void forward_l2norm(FwdPass& p, int li, int op_index);
     void forward_loss(FwdPass& p, const float* y, LossSlotGuard& guard);
     void launch_tail_forward(int b0, int nb, hipStream_t s);
-    void launch_tail_backward(int b, bool* side_used);
+    void launch_tail_backward();
     void build_orders();
     void plan_pool_fusion();
     int bw_class(const Op& op, int op_index) const;
     void bw_sync(int x, int y);          // class x waits for everything class y has been given so far
-    void bw_need(int x, const Tensor& t);
-    void bw_wrote(int x, Tensor& t, bool carried = false);
+    void bw_need(int x, int ti);         // class x is about to read or accumulate into tensor ti's gradient
+    void bw_wrote(int x, int ti, bool carried = false);      // class x has been given the kernel that writes it
     bool overlap_ = true;
 
     std::vector<Tensor> tensors_;
@@ -375,6 +400,8 @@ private:
     float* clip_dev_ = nullptr;
     hipEvent_t ev_clip_[LOSS_RING] = {};
     long long clip_seq_ = -1;             // clipped (or measured) updates so far - 1
+    float* begin_clip_slot();             // next slot (the device's view): waits until its previous use (LOSS_RING updates ago) has finished
+    void end_clip_slot();                 // records the slot's event behind the update
     // the update rule (apply_gradients): under AdamW mom_ is the first moment and adam_v_ the second
     int rule_kind_ = 0;                   // UPDATE_MOMENTUM / UPDATE_ADAMW (ops.h)
     float adam_b1_ = 0.9f, adam_b2_ = 0.999f, adam_eps_ = 1e-8f, adam_decay_ = 0.01f;
@@ -399,7 +426,6 @@ private:
     float focal_gamma_ = 2.f, focal_alpha_ = 0.25f, bw_gamma_ = 2.f, bw_alpha_ = 0.25f;
     LocLoss loc_{}, bw_loc_{};              // SSD_LOC_SMOOTH_L1 / SSD_LOC_GIOU and its weight; bw_: of the last training forward
     Profiler prof_;
-    int bw_b_ = 0;
     // Every buffer, pinned page, event and stream above that the handle made itself.  Declared after every member that holds its
     // handles, so it is destroyed before them: the device is synchronised before the members above (prof_'s events) go.
     HipOwner hip_;

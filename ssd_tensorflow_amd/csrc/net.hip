@@ -281,22 +281,36 @@ void Net::bw_sync(int x, int y) {
     hipEvent_t ev = y == 1 ? ev_h_ : ev_m2s_;
     HIP_OK(hipEventRecord(ev, y == 1 ? hstream_ : stream_));
     HIP_OK(hipStreamWaitEvent(x == 1 ? hstream_ : stream_, ev, 0));
-    bw_seen_[x][y] = bw_issued_[y];
+    bwd_.seen[x][y] = bwd_.issued[y];
 }
 
-void Net::bw_need(int x, const Tensor& t) {
-    if (t.gstream == x || t.gseq <= bw_seen_[x][t.gstream]) return;
-    if (t.gev && t.gev_set) HIP_OK(hipStreamWaitEvent(x == 1 ? hstream_ : stream_, t.gev, 0));      // exactly the kernel that wrote it
-    else bw_sync(x, t.gstream);
+void Net::bw_need(int x, int ti) {
+    const BwdPass::Grad& g = bwd_.t[ti];
+    if (g.gstream == x || g.gseq <= bwd_.seen[x][g.gstream]) return;
+    if (g.gev_set) HIP_OK(hipStreamWaitEvent(x == 1 ? hstream_ : stream_, tensors_[ti].gev, 0));      // exactly the kernel that wrote it
+    else bw_sync(x, g.gstream);
 }
 
-void Net::bw_wrote(int x, Tensor& t, bool carried) {
-    t.gstream = x;
-    t.gseq = ++bw_issued_[x];
-    if (t.gev) {
-        if (!carried) HIP_OK(hipEventRecord(t.gev, x == 1 ? hstream_ : stream_));      // (carried: the kernel's own stop event, common.h)
-        t.gev_set = true;
+void Net::bw_wrote(int x, int ti, bool carried) {
+    BwdPass::Grad& g = bwd_.t[ti];
+    g.gstream = x;
+    g.gseq = ++bwd_.issued[x];
+    if (hipEvent_t gev = tensors_[ti].gev) {
+        if (!carried) HIP_OK(hipEventRecord(gev, x == 1 ? hstream_ : stream_));      // (carried: the kernel's own stop event, common.h)
+        g.gev_set = true;
     }
+}
+
+// A fresh record: every field at its default, so a field added to BwdPass is reset without a line here.  The two vectors keep their
+// storage (assign into a vector of that size already: no allocation from the second pass on).
+void Net::BwdPass::begin(const Net* n, int batch) {
+    BwdPass fresh;
+    fresh.b = batch;
+    fresh.progress.done = std::move(progress.done);
+    fresh.progress.begin(n);
+    fresh.t = std::move(t);
+    fresh.t.assign(n->tensors_.size(), Grad{});
+    *this = std::move(fresh);
 }
 
 void Net::BwProgress::begin(const Net* n) {
@@ -358,10 +372,13 @@ std::pair<size_t, size_t> Net::BwProgress::end_stage() {
 //    then never written -- nothing reads it in backward either (the record carries the argmax and the relu sign);
 //  * the CONSUMER's data gradient scatters through the record straight into the producer's output gradient.
 // SSD_POOL_FUSE: bit 0 forward, bit 1 backward, bit 2 (bf16) conv1_1's weight gradient inside conv1_2's data gradient
-// (backward_step); default 7; 0 = the separate kernels, for the A/B and the identity checks.
+// (dgrad_first_wgrad); default 7; 0 = the separate kernels, for the A/B and the identity checks.
 void Net::plan_pool_fusion() {
     const int mode = env_i("SSD_POOL_FUSE", 7);      // (read per handle: the tests build a fused and an unfused handle in one process)
     fuse_first_wgrad_ = (mode & 4) != 0 && bf16_ && training_;
+    first_conv_ = -1;      // the layer whose weight gradient that is: the convolution that reads the image (dgrad_first_wgrad)
+    for (int i = 0; i < (int)ops_.size(); ++i)
+        if (ops_[i].kind == OP_CONV && ops_[i].in == input_t_) first_conv_ = i;
     for (int i = 0; i < (int)ops_.size(); ++i) {
         Op& pl = ops_[i];
         if (pl.kind != OP_POOL) continue;
@@ -484,20 +501,22 @@ void Net::launch_tail_forward(int b0, int nb, hipStream_t s) {
 }
 
 // The chain's part of backward (see plan_tail_chain): called when backward_step meets the chain's first op in its order.
-void Net::launch_tail_backward(int b, bool* side_used) {
+void Net::launch_tail_backward() {
+    const int b = bwd_.b;
     const bool side = hstream_ && overlap_;
     const int cls = side ? 1 : 0;
     hipStream_t ds = cls == 1 ? hstream_ : stream_;
     std::vector<TailStage> st;
-    std::vector<Tensor*> written;
-    Tensor* first_out = &tensors_[ops_[chain_first_].out];      // the gradient the first layer's own data gradient (a launch) reads
+    std::vector<int> written;
+    const int first_out = ops_[chain_first_].out;      // the gradient the first layer's own data gradient (a launch) reads
     for (const int oi : bwd_order_) {
         if (!in_chain_[oi] || oi == chain_first_) continue;
         const Op& op = ops_[oi];
-        Tensor& in = tensors_[op.in];
+        const Tensor& in = tensors_[op.in];
         const Tensor& out = tensors_[op.out];
-        bw_need(cls, out);                                      // (the loss gradient of the heads: main stream)
-        const bool last = in.done + 1 == in.consumers;
+        int& done = bwd_.t[op.in].done;
+        bw_need(cls, op.out);                                   // (the loss gradient of the heads: main stream)
+        const bool last = done + 1 == in.consumers;
         TailStage t{};
         t.d = conv_desc(op, 1);
         t.dgrad = true;
@@ -505,35 +524,31 @@ void Net::launch_tail_backward(int b, bool* side_used) {
         t.wgt_packed = wq_tail_ + tail_bwd_off_[oi];
         t.mask = (last && in.relu_out) ? in.data : nullptr;
         t.dst = in.grad;
-        t.accum = in.done > 0;
+        t.accum = done > 0;
         st.push_back(t);
-        in.done++;
-        if (std::find(written.begin(), written.end(), &in) == written.end()) written.push_back(&in);
+        done++;
+        if (std::find(written.begin(), written.end(), op.in) == written.end()) written.push_back(op.in);
     }
     prof_.layer = "tail";
-    const bool carry = first_out->gev != nullptr;
-    g_stop_event = carry ? first_out->gev : nullptr;
+    const hipEvent_t carry = tensors_[first_out].gev;
+    g_stop_event = carry;
     {
         struct Disarm { ~Disarm() { g_stop_event = nullptr; } } disarm;
         tail_chain_bf16(st.data(), (int)st.size(), b, "tail_dgrad_bf16", ds, tail_tables_);
     }
-    for (Tensor* t : written) {      // one kernel wrote them all: the carried event (if any) stands for every one of them
-        t->gstream = cls;
-        t->gseq = ++bw_issued_[cls];
-        t->gev_set = false;
+    for (const int ti : written) {      // one kernel wrote them all: the carried event (if any) stands for every one of them
+        BwdPass::Grad& g = bwd_.t[ti];
+        g.gstream = cls;
+        g.gseq = ++bwd_.issued[cls];
+        g.gev_set = false;
     }
-    if (carry) first_out->gev_set = true;
+    if (carry) bwd_.t[first_out].gev_set = true;
     // ---- the weight gradients of every layer of the chain, one launch behind the data gradients
     const bool wside = wstream_ && overlap_;
     hipStream_t ws = wside ? wstream_ : stream_;
     if (wside || cls == 1) {
-        if (carry) {
-            HIP_OK(hipStreamWaitEvent(ws, first_out->gev, 0));
-        } else {
-            HIP_OK(hipEventRecord(ev_dy_, ds));
-            HIP_OK(hipStreamWaitEvent(ws, ev_dy_, 0));
-        }
-        if (!wside) bw_seen_[0][1] = bw_issued_[1];      // (the main stream has now waited for the side stream's chain)
+        wgrad_wait(ws, carry, ds);
+        if (!wside) bwd_.seen[0][1] = bwd_.issued[1];      // (the main stream has now waited for the side stream's chain)
     }
     // (the chain's first layer, on the 10x10 map -- 3200 pixels at batch 32 -- would be the group's straggler with its single pixel
     // split: 50 iterations on 8 workgroups; it keeps its own launch and slab reduce, issued when its turn comes)
@@ -551,8 +566,8 @@ void Net::launch_tail_backward(int b, bool* side_used) {
         items.push_back(it);
     }
     conv_wgrad_group_bf16(items.data(), (int)items.size(), wd_, ws);
-    bw_.retire_chain();
-    if (wside) *side_used = true;
+    bwd_.progress.retire_chain();
+    if (wside) bwd_.side_used = true;
 }
 
 // Round 6 (fp32): which layers take the Winograd form (conv.h wino_*).  SSD_WINOGRAD = bits 0 forward / 1 data gradient / 2 weight
@@ -620,7 +635,7 @@ void Net::plan_winograd() {
         wino_ya_ = (float*)hip_.mem(yt_max * sizeof(float));
         wino_slab_ = (float*)hip_.mem(slab_max * sizeof(float));
         // a layer with both gradients in this form: its dy is transformed once, on the main stream, into wino_ya_ / wino_ya2_ in turn
-        // (backward_step) -- the second buffer is yt_max floats more (1.66 GB at vgg300 batch 32)
+        // (wgrad_handoff) -- the second buffer is yt_max floats more (1.66 GB at vgg300 batch 32)
         if (dual_any) {
             wino_ya2_ = (float*)hip_.mem(yt_max * sizeof(float));
             for (hipEvent_t& e : ev_ya_free_) e = hip_.event();
@@ -1010,7 +1025,7 @@ Net::Net(const char* preset, int num_classes, int max_batch, int device, bool tr
         for (const Op& op : ops_)
             if (op.in != input_t_ && !tensors_[op.in].gev)
                 tensors_[op.in].gev = hip_.event();
-    bw_.begin(this);
+    bwd_.begin(this, 0);      // (the record's vectors get their size here)
 }
 
 Net::~Net() {
@@ -1335,7 +1350,7 @@ void Net::forward_conv(FwdPass& p, int li, int op_index) {
         launch_conv_fwd(p, op, d, r);
         return;
     }
-    // a feature map's producer carries the event its head waits for (common.h g_stop_event; backward_step does the same)
+    // a feature map's producer carries the event its head waits for (common.h g_stop_event; backward_conv does the same)
     int fh = -1;      // the head that reads this op's output
     if (p.side && op.head < 0 && r.cs == ln.s)
         for (const Op& o : ops_)
@@ -1477,17 +1492,56 @@ void Net::launch_wgrad(int op_index, int b, hipStream_t ws, const float* ya) {
 void Net::launch_dgrad(const Op& op, const ConvDesc& d, const Op* up, Tensor& dst, bool mask, int cls, hipStream_t ds, bool yt_done) {
     const Tensor& in = tensors_[op.in];
     const Tensor& out = tensors_[op.out];
+    const bool accum = bwd_.t[op.in].done > 0;
     if (op.wino_d && cls == 0) {      // Round 6: the Winograd form (its scratch belongs to the main stream)
         if (!yt_done) wino_bwd_transform(d, out.gf(), wino_yt_, nullptr, ds);
-        wino_dgrad(d, wino_yt_, op.wino_Uf, up ? dst.gf() : in.gf(), mask ? in.f() : nullptr, !up && in.done > 0, wino_xw_,
+        wino_dgrad(d, wino_yt_, op.wino_Uf, up ? dst.gf() : in.gf(), mask ? in.f() : nullptr, !up && accum, wino_xw_,
                    up ? up->pool_rec : nullptr, dst.H, dst.W, ds,
                    op.wino_bits && op.wino_bits_step == fwd_serial_ ? op.wino_bits : nullptr);      // (the forward of THIS step wrote them)
     } else if (!bf16_) {
         if (up) conv_dgrad_unpool(d, out.gf(), params_ + op.w_off, dst.gf(), up->pool_rec, dst.H, dst.W, ds);
-        else conv_dgrad(d, out.gf(), params_ + op.w_off, in.gf(), mask ? in.f() : nullptr, in.done > 0, ds);
+        else conv_dgrad(d, out.gf(), params_ + op.w_off, in.gf(), mask ? in.f() : nullptr, accum, ds);
     } else {
         if (up) conv_dgrad_unpool_bf16(d, out.gh(), wq_io_ + op.w_off, dst.gh(), up->pool_rec, dst.H, dst.W, ds);
-        else conv_dgrad_bf16(d, out.gh(), wq_io_ + op.w_off, in.gh(), mask ? in.h() : nullptr, in.done > 0, ds);
+        else conv_dgrad_bf16(d, out.gh(), wq_io_ + op.w_off, in.gh(), mask ? in.h() : nullptr, accum, ds);
+    }
+}
+
+// ---- Backward's cross-stream hand-offs, all of them.  M = stream_ (class 0: the data gradients of the trunk and the big heads, the
+// pools, the l2-norm), S = hstream_ (class 1: the last small head and the extra layers behind conv8_1, bw_class), W = wstream_ (the
+// weight gradients where overlap_ is on).  Events are recorded and waited for in host issue order; a wait takes the record that
+// precedes it.  No record / wait pair of backward is written anywhere but in the functions named here.
+//
+//   event           recorded by, on                              waited for by, on                      what it orders
+//   ev_m2s_         bw_sync(1, 0), M                             bw_sync(1, 0), S                       S reads or accumulates into a gradient M wrote
+//                                                                                                       (backward_begin: the loss gradient; bw_need)
+//   ev_h_           bw_sync(0, 1), S                             bw_sync(0, 1), M                       M reads or accumulates into a gradient S wrote
+//                                                                                                       (conv8_1 joins the chain; the end of the pass)
+//   Tensor::gev     bw_wrote, the writer's class -- or carried   bw_need, the other class               the same, for exactly the kernel that wrote it last
+//                   by the kernel itself (g_stop_event)          wgrad_handoff (b), W                   W's weight gradient reads dy
+//                                                                launch_tail_backward (wgrad_wait), W   the chain's grouped weight gradient reads the chain's dy
+//                                                                  -- or M when the weight gradients run there and the chain ran on S
+//   ev_dy_          wgrad_handoff (a), M behind the dual         wgrad_handoff (a), W                   W's GEMM reads the ya buffer the transform wrote
+//                     transform
+//                   wgrad_handoff (b), S or M (from_side)        wgrad_handoff (b), W                   W reads a dy that has no event of its own
+//                   launch_tail_backward (wgrad_wait), the       launch_tail_backward, W or M           as Tensor::gev above, where the chain's first
+//                     chain's stream                                                                    output has no event
+//                   backward_join, M                             backward_join, W                       a caller that consumes the range on W finds the weight
+//                                                                                                       gradients that ran on M (overlap off; conv1_1's)
+//   ev_w_           backward_join, W                             backward_join, M                       the range is final in M's order: the update, the caller
+//   ev_ya_free_[k]  launch_wgrad, W behind the GEMM that read    wgrad_handoff (a), M before the dual   the transform overwrites buffer k only behind its
+//                     ya buffer k                                  transform that writes buffer k       last reader (write after read; outlives a pass)
+//
+// (backward_begin's wait for ev_wino_flip_ is forward's hand-off: the filter transforms of the data gradients, issued by forward.)
+// Within a class everything is stream order.  W never writes what M or S read inside a pass: its results are the gradient arena.
+
+// ws waits for dy's producer: for the kernel that carried the event, or for everything `from` has been given so far
+void Net::wgrad_wait(hipStream_t ws, hipEvent_t carried, hipStream_t from) {
+    if (carried) {
+        HIP_OK(hipStreamWaitEvent(ws, carried, 0));
+    } else {
+        HIP_OK(hipEventRecord(ev_dy_, from));
+        HIP_OK(hipStreamWaitEvent(ws, ev_dy_, 0));
     }
 }
 
@@ -1496,193 +1550,208 @@ void Net::backward_begin(int b, const float* y) {
     g_prof = &prof_;
     prof_.layer = "loss";
     const bool side = hstream_ && overlap_;
-    for (Tensor& t : tensors_) { t.done = 0; t.gstream = 0; t.gseq = 0; t.gev_set = false; }
-    bw_issued_[0] = bw_issued_[1] = 0;
-    bw_seen_[0][0] = bw_seen_[0][1] = bw_seen_[1][0] = bw_seen_[1][1] = 0;
+    bwd_.begin(this, b);
     if (wino_flip_pending_) {      // the data gradients' filter transforms (side stream, issued by forward)
         HIP_OK(hipStreamWaitEvent(stream_, ev_wino_flip_, 0));
         wino_flip_pending_ = false;
     }
     if (bw_loss_kind_ == 1) multibox_focal_loss_grad(heads_, b, 0, result_, y, lw_, bw_gamma_, bw_alpha_, stream_, bw_loc_);
     else multibox_loss_grad(heads_, b, 0, result_, y, lw_, stream_, bw_loc_);
-    for (int t : head_t_) bw_wrote(0, tensors_[t]);      // the loss gradient, on the main stream
-    if (side) bw_sync(1, 0);      // the side stream starts behind it (the small maps' head data gradients: backward_step)
-    bw_.begin(this);
-    bw_first_on_main_ = false;
-    bw_first_fused_ = false;
-    ya_turn_ = 1;      // (the first dual transform of the step writes wino_ya2_: wino_ya_ may still be read by a layer that transforms on the weight-gradient stream)
-    bw_b_ = b;
+    for (int t : head_t_) bw_wrote(0, t);      // the loss gradient, on the main stream
+    if (side) bw_sync(1, 0);      // the side stream starts behind it (the small maps' head data gradients: bw_class)
 }
 
-bool Net::backward_step(size_t min_floats, size_t* off, size_t* count, bool sync_main) {
-    const int b = bw_b_;
-    bool side_used = false;
-    for (int op_index; (op_index = bw_.next(min_floats)) >= 0;) {
-        const Op& op = ops_[op_index];
-        Tensor& in = tensors_[op.in];
-        const Tensor& out = tensors_[op.out];
-        const bool need_dx = op.in != input_t_;
-        const bool last = in.done + 1 == in.consumers;
-        prof_.layer = op.name.c_str();
-        // Where this op's data gradient runs (bw_class): the small maps' heads and the chain of extra layers behind them on the
-        // side stream, everything else on the main stream.  Hand-offs between the two are events placed where a kernel reads
-        // or accumulates into a gradient that the other class wrote last (bw_need): conv8_1 joins the chain.
-        const int cls = bw_class(op, op_index);
-        hipStream_t ds = cls == 1 ? hstream_ : stream_;
-        if (chain_bwd_ && in_chain_[op_index] && !op_ablated(op.name, op.kind, op.head, op.k)) {
-            // Round 6 (plan_tail_chain): the first chain op met issues the chain's data gradients (one launch) and every chain layer's
-            // weight gradient (one grouped launch); the other members are skipped when their turn comes -- all but the chain's first
-            // layer, whose data and weight gradients are ordinary launches below (launch_tail_backward leaves it out of the group)
-            if (!bw_.chain_done) {
-                launch_tail_backward(b, &side_used);      // (retires them)
-                prof_.layer = op.name.c_str();
-            }
-            if (op_index != chain_first_) continue;
+// The weight gradient only feeds the optimizer; the data gradient is on the critical path.  They read the same dy and write disjoint
+// buffers, so the weight gradient goes to a side stream: its workgroups fill the CUs the data-gradient's last partial wave of
+// workgroups leaves idle (and vice versa).
+// The first layer's weight gradient (no data gradient behind it: the main stream has gone idle by then) runs on the MAIN stream
+// beside conv1_2's weight gradient instead of queueing behind it -- both are HBM-bound at half the achievable bandwidth
+// (profiles/r04_a_timeline_bf16.txt: 7013 .. 7391 us of the step ran one such kernel at a time)
+Net::WgradStream Net::wgrad_stream_for(bool need_dx) const {
+    const bool side = wstream_ && overlap_;
+    const bool on_main = side && !need_dx;
+    return WgradStream{(side && !on_main) ? wstream_ : stream_, side, on_main};
+}
+
+// Makes w.ws wait for what this layer's weight gradient reads.  Returns the buffer that holds the layer's transformed dy where the
+// main stream has written it (a), else nullptr.
+const float* Net::wgrad_handoff(const Op& op, const ConvDesc& d, int cls, bool need_dx, const WgradStream& w) {
+    // One transform of dy for both gradients (wino_bwd_transform's dual kernel: dy is read once): where the layer takes the
+    // Winograd form of both, on the main stream, which the data gradient runs on.  Which layers: by shape alone, max(Ci, Co) <= 128
+    // (conv1_2, conv2_x) -- there the GEMMs that run beside the transform are HBM-bound themselves and the bytes saved shorten the
+    // step; on the wider layers the AT transform hides beside a compute-bound GEMM on the other stream, and moving its writes to the
+    // main stream measured slower (DESIGN.md 4.9 has the rows).  wino_dual_ == 2: every such layer (the bit-identity tests).
+    const bool dual = wino_dual_ && (wino_dual_ == 2 || std::max(d.Ci, d.Co) <= wino_dual_max_c_) && wino_ya2_ && need_dx && cls == 0 &&
+                      op.wino_d && op.wino_w && op.wino_v_step == fwd_serial_;
+    const BwdPass::Grad& dy = bwd_.t[op.out];
+    if (dual) {
+        // (a) the dual transform on the main stream, then ev_dy_: the weight-gradient stream waits for the transform instead of
+        // dy's producer (which the main stream waits for here)
+        bw_need(0, op.out);
+        float* buf = bwd_.ya_turn ? wino_ya2_ : wino_ya_;
+        // (the GEMM that read this buffer last, two dual layers back on the weight-gradient stream: normally long done)
+        if (w.side && ya_free_set_[bwd_.ya_turn]) HIP_OK(hipStreamWaitEvent(stream_, ev_ya_free_[bwd_.ya_turn], 0));
+        wino_bwd_transform(d, tensors_[op.out].gf(), wino_yt_, buf, stream_);
+        if (w.side) {
+            wgrad_wait(wstream_, nullptr, stream_);
+            bwd_.side_used = true;
         }
-        if (op_ablated(op.name, op.kind, op.head, op.k)) {
-            bw_.retire(op_index);
-            in.done++;
-            continue;
-        }
-        switch (op.kind) {
-        case OP_CONV: {
-            const ConvDesc d = conv_desc(op, b);
-            // The weight gradient only feeds the optimizer; the data gradient is on the critical
-            // path.  They read the same dy and write disjoint buffers, so the weight gradient goes
-            // to a side stream: its workgroups fill the CUs the data-gradient's last partial wave
-            // of workgroups leaves idle (and vice versa).
-            // The first layer's weight gradient (no data gradient behind it: the main stream has gone idle by then) runs on the
-            // MAIN stream beside conv1_2's weight gradient instead of queueing behind it -- both are HBM-bound at half the
-            // achievable bandwidth (profiles/r04_a_timeline_bf16.txt: 7013 .. 7391 us of the step ran one such kernel at a time)
-            const bool side = wstream_ && overlap_;
-            const bool on_main = side && !need_dx;
-            hipStream_t ws = (side && !on_main) ? wstream_ : stream_;
-            // One transform of dy for both gradients (wino_bwd_transform's dual kernel: dy is read once): where the layer takes the
-            // Winograd form of both, on the main stream, which the data gradient runs on.  The weight-gradient stream then waits for
-            // the transform instead of dy's producer.  Which layers: by shape alone, max(Ci, Co) <= 128 (conv1_2, conv2_x) -- there the GEMMs
-            // that run beside the transform are HBM-bound themselves and the bytes saved shorten the step; on the wider layers the AT
-            // transform hides beside a compute-bound GEMM on the other stream, and moving its writes to the main stream measured
-            // slower (DESIGN.md 4.9 has the rows).  wino_dual_ == 2: every such layer (the bit-identity tests).
-            const bool dual = wino_dual_ && (wino_dual_ == 2 || std::max(d.Ci, d.Co) <= wino_dual_max_c_) && wino_ya2_ && need_dx && cls == 0 &&
-                              op.wino_d && op.wino_w && op.wino_v_step == fwd_serial_;
-            const float* ya = nullptr;
-            if (dual) {
-                bw_need(0, out);
-                float* buf = ya_turn_ ? wino_ya2_ : wino_ya_;
-                // (the GEMM that read this buffer last, two dual layers back on the weight-gradient stream: normally long done)
-                if (side && ya_free_set_[ya_turn_]) HIP_OK(hipStreamWaitEvent(stream_, ev_ya_free_[ya_turn_], 0));
-                wino_bwd_transform(d, out.gf(), wino_yt_, buf, stream_);
-                if (side) {
-                    HIP_OK(hipEventRecord(ev_dy_, stream_));
-                    HIP_OK(hipStreamWaitEvent(wstream_, ev_dy_, 0));
-                    side_used = true;
-                }
-                ya = buf;
-                ya_turn_ ^= 1;
-            } else if (side && !on_main) {
-                // (dy written on the main stream but already waited for by the side stream, and this op lives there: the
-                // side stream is the one that is less far ahead -- a small head's weight gradient need not wait for mod_conv7)
-                if (out.gev && out.gev_set) {
-                    HIP_OK(hipStreamWaitEvent(wstream_, out.gev, 0));      // the kernel that wrote dy last (it waited for the earlier writers)
-                } else {
-                    const bool from_side = out.gstream == 1 || (cls == 1 && bw_seen_[1][0] >= out.gseq);
-                    HIP_OK(hipEventRecord(ev_dy_, from_side ? hstream_ : stream_));
-                    HIP_OK(hipStreamWaitEvent(wstream_, ev_dy_, 0));
-                }
-                side_used = true;
-            } else {
-                bw_need(0, out);
-                if (on_main) bw_first_on_main_ = true;
-            }
-            if (!(bw_first_fused_ && !need_dx))      // (conv1_1's came out of conv1_2's data gradient: below)
-                launch_wgrad(op_index, b, ws, ya);
-            if (need_dx) {
-                if (!dual) bw_need(cls, out);
-                // Pool fusion (round 5): when this conv reads a recorded 2x2 pool's output, its data gradient routes every
-                // pooled pixel's dx through the record straight into the four cells of the POOL'S INPUT gradient (relu mask of
-                // that tensor's producer included, from the record's sign bit): the pooled tensor's own gradient is never
-                // written and the pool's backward pass is not launched.
-                const Op* up = op.unpool >= 0 ? &ops_[op.unpool] : nullptr;
-                Tensor& dst = up ? tensors_[up->in] : in;
-                if (!up && in.done > 0) bw_need(cls, in);      // accumulates into what the other class wrote
-                const bool mask = !up && last && in.relu_out;
-                // conv1_2 in bf16: the layer below is the first layer, whose only use for dx is its weight gradient -- computed
-                // here from the dx tiles while they are in LDS (conv.h conv_dgrad_first_wgrad_bf16); dx is never written and
-                // conv1_1's own weight-gradient kernel is skipped when its turn comes
-                int first = -1;
-                if (fuse_first_wgrad_ && !up && mask && in.done == 0)
-                    for (int j = 0; j < (int)ops_.size(); ++j)
-                        if (ops_[j].kind == OP_CONV && ops_[j].out == op.in && ops_[j].in == input_t_) first = j;
-                if (first >= 0 && cls == 0 && conv_dgrad_first_wgrad_bf16_applicable(d, conv_desc(ops_[first], b))) {
-                    const Op& f = ops_[first];
-                    prof_.layer = "conv1_2+conv1_1";
-                    conv_dgrad_first_wgrad_bf16(d, out.gh(), wq_io_ + op.w_off, in.h(), conv_desc(f, b), tensors_[input_t_].f(),
-                                                grads_ + f.w_off, grads_ + f.b_off, params_ + f.w_off, wd_, wgrad_ws_ + f.ws_off, ds);
-                    bw_first_fused_ = true;
-                    fused_first_out_ = op.in;
-                    bw_wrote(cls, in);
-                    bw_.retire(op_index);
-                    break;
-                }
-                g_stop_event = dst.gev;      // the launch carries dst's event (taken by the gather launchers)
-                struct Disarm { ~Disarm() { g_stop_event = nullptr; } } disarm;      // (also when the launch throws)
-                launch_dgrad(op, d, up, dst, mask, cls, ds, dual);
-                const bool carried = dst.gev && g_stop_event == nullptr;
-                bw_wrote(cls, dst, carried);
-            }
-            bw_.retire(op_index);
-            break;
-        }
-        case OP_POOL: {
-            if (op.fused_bwd) break;      // its consumer's data gradient has already written in.grad through the record
-            bw_need(0, out);
-            if (in.done > 0) bw_need(0, in);
-            PoolDesc d{b, in.H, in.W, in.C, out.H, out.W, op.k, op.stride, op.pad_h, op.pad_w};
-            void* pws = maxpool_bwd_ws_bytes(d) ? pool_ws_ : nullptr;
-            if (op.pool_rec && in.done == 0 && last) {      // single consumer: dx is overwritten from the forward record
-                if (bf16_) maxpool_bwd_rec(d, op.pool_rec, out.gh(), in.gh(), in.relu_out, stream_);
-                else maxpool_bwd_rec(d, op.pool_rec, out.gf(), in.gf(), in.relu_out, stream_);
-            } else if (pool_arg_op_ == op_index && pws && maxpool_arg_applicable(d)) {      // the forward pass of this step left the record
-                if (bf16_) maxpool_bwd_arg(d, in.h(), pws, out.gh(), in.gh(), in.done > 0, last && in.relu_out, stream_);
-                else maxpool_bwd_arg(d, in.f(), pws, out.gf(), in.gf(), in.done > 0, last && in.relu_out, stream_);
-            } else if (bf16_)
-                maxpool_bwd(d, in.h(), out.gh(), in.gh(), in.done > 0, last && in.relu_out, pws, stream_);
-            else
-                maxpool_bwd(d, in.f(), out.gf(), in.gf(), in.done > 0, last && in.relu_out, pws, stream_);
-            bw_wrote(0, in);
-            break;
-        }
-        case OP_L2NORM: {
-            SSD_REQUIRE(in.done == 0 && !last, "l2norm backward must be the first of several consumers");
-            bw_need(cls, out);
-            if (bf16_)
-                l2norm_bwd(b * in.H * in.W, in.C, in.h(), params_ + scale_off_, out.gh(), in.gh(), grads_ + scale_off_, l2_ws_, ds);
-            else
-                l2norm_bwd(b * in.H * in.W, in.C, in.f(), params_ + scale_off_, out.gf(), in.gf(), grads_ + scale_off_, l2_ws_, ds);
-            bw_wrote(cls, in);
-            break;
-        }
-        }
-        in.done++;
+        bwd_.ya_turn ^= 1;
+        return buf;
     }
-    const bool finished = bw_.finished();
-    if (finished && bw_issued_[1] > bw_seen_[0][1]) bw_sync(0, 1);      // (every side-stream result has a main-stream reader: a no-op)
+    if (w.side && !w.on_main) {
+        // (b) the weight-gradient stream waits for the kernel that wrote dy last (it waited for the earlier writers), or for the
+        // stream that holds dy.  (from_side: dy written on the main stream but already waited for by the side stream, and this op
+        // lives there: the side stream is the one that is less far ahead -- a small head's weight gradient need not wait for mod_conv7)
+        const bool from_side = dy.gstream == 1 || (cls == 1 && bwd_.seen[1][0] >= dy.gseq);
+        wgrad_wait(wstream_, dy.gev_set ? tensors_[op.out].gev : nullptr, from_side ? hstream_ : stream_);
+        bwd_.side_used = true;
+        return nullptr;
+    }
+    // (c) the weight gradient runs on the main stream (no overlap, or the first layer's): an ordinary reader of class 0
+    bw_need(0, op.out);
+    if (w.on_main) bwd_.first_on_main = true;
+    return nullptr;
+}
+
+// conv1_2 in bf16: the layer below is the first layer, whose only use for dx is its weight gradient -- computed here from the dx
+// tiles while they are in LDS (conv.h conv_dgrad_first_wgrad_bf16); dx is never written and conv1_1's own weight-gradient kernel is
+// skipped when its turn comes (backward_conv).  Returns whether the launch was taken.
+bool Net::dgrad_first_wgrad(const Op& op, const ConvDesc& d, const Op* up, bool mask, int cls, hipStream_t ds) {
+    if (!(fuse_first_wgrad_ && !up && mask && bwd_.t[op.in].done == 0 && cls == 0)) return false;
+    if (first_conv_ < 0 || ops_[first_conv_].out != op.in) return false;      // (this op reads the first layer's output)
+    const Op& f = ops_[first_conv_];
+    const ConvDesc df = conv_desc(f, bwd_.b);
+    if (!conv_dgrad_first_wgrad_bf16_applicable(d, df)) return false;
+    prof_.layer = "conv1_2+conv1_1";
+    conv_dgrad_first_wgrad_bf16(d, tensors_[op.out].gh(), wq_io_ + op.w_off, tensors_[op.in].h(), df, tensors_[input_t_].f(),
+                                grads_ + f.w_off, grads_ + f.b_off, params_ + f.w_off, wd_, wgrad_ws_ + f.ws_off, ds);
+    bwd_.first_fused = true;
+    bwd_.fused_first_out = op.in;
+    bw_wrote(cls, op.in);
+    return true;
+}
+
+// One convolution: the weight gradient's stream and hand-off, its launch, then the data gradient on the op's class (bw_class): the
+// small maps' heads and the chain of extra layers behind them on the side stream, everything else on the main stream.  Hand-offs
+// between the two are events placed where a kernel reads or accumulates into a gradient that the other class wrote last (bw_need):
+// conv8_1 joins the chain.
+void Net::backward_conv(int op_index) {
+    const Op& op = ops_[op_index];
+    const Tensor& in = tensors_[op.in];
+    const int b = bwd_.b;
+    const ConvDesc d = conv_desc(op, b);
+    const bool need_dx = op.in != input_t_;
+    const int cls = bw_class(op, op_index);
+    hipStream_t ds = cls == 1 ? hstream_ : stream_;
+    const WgradStream w = wgrad_stream_for(need_dx);
+    const float* ya = wgrad_handoff(op, d, cls, need_dx, w);
+    if (!(bwd_.first_fused && !need_dx))      // (conv1_1's came out of conv1_2's data gradient: dgrad_first_wgrad)
+        launch_wgrad(op_index, b, w.ws, ya);
+    if (need_dx) {
+        if (!ya) bw_need(cls, op.out);
+        // Pool fusion (round 5): when this conv reads a recorded 2x2 pool's output, its data gradient routes every
+        // pooled pixel's dx through the record straight into the four cells of the POOL'S INPUT gradient (relu mask of
+        // that tensor's producer included, from the record's sign bit): the pooled tensor's own gradient is never
+        // written and the pool's backward pass is not launched.
+        const Op* up = op.unpool >= 0 ? &ops_[op.unpool] : nullptr;
+        const int dst = up ? up->in : op.in;
+        const int done = bwd_.t[op.in].done;
+        if (!up && done > 0) bw_need(cls, op.in);      // accumulates into what the other class wrote
+        const bool mask = !up && done + 1 == in.consumers && in.relu_out;
+        if (!dgrad_first_wgrad(op, d, up, mask, cls, ds)) {
+            g_stop_event = tensors_[dst].gev;      // the launch carries dst's event (taken by the gather launchers)
+            struct Disarm { ~Disarm() { g_stop_event = nullptr; } } disarm;      // (also when the launch throws)
+            launch_dgrad(op, d, up, tensors_[dst], mask, cls, ds, ya != nullptr);
+            const bool carried = tensors_[dst].gev && g_stop_event == nullptr;
+            bw_wrote(cls, dst, carried);
+        }
+    }
+    bwd_.progress.retire(op_index);
+}
+
+void Net::backward_pool(int op_index) {
+    const Op& op = ops_[op_index];
+    if (op.fused_bwd) return;      // its consumer's data gradient has already written in.grad through the record
+    const Tensor& in = tensors_[op.in];
+    const Tensor& out = tensors_[op.out];
+    const int done = bwd_.t[op.in].done;
+    const bool last = done + 1 == in.consumers;
+    bw_need(0, op.out);
+    if (done > 0) bw_need(0, op.in);
+    PoolDesc d{bwd_.b, in.H, in.W, in.C, out.H, out.W, op.k, op.stride, op.pad_h, op.pad_w};
+    void* pws = maxpool_bwd_ws_bytes(d) ? pool_ws_ : nullptr;
+    if (op.pool_rec && done == 0 && last) {      // single consumer: dx is overwritten from the forward record
+        if (bf16_) maxpool_bwd_rec(d, op.pool_rec, out.gh(), in.gh(), in.relu_out, stream_);
+        else maxpool_bwd_rec(d, op.pool_rec, out.gf(), in.gf(), in.relu_out, stream_);
+    } else if (pool_arg_op_ == op_index && pws && maxpool_arg_applicable(d)) {      // the forward pass of this step left the record
+        if (bf16_) maxpool_bwd_arg(d, in.h(), pws, out.gh(), in.gh(), done > 0, last && in.relu_out, stream_);
+        else maxpool_bwd_arg(d, in.f(), pws, out.gf(), in.gf(), done > 0, last && in.relu_out, stream_);
+    } else if (bf16_)
+        maxpool_bwd(d, in.h(), out.gh(), in.gh(), done > 0, last && in.relu_out, pws, stream_);
+    else
+        maxpool_bwd(d, in.f(), out.gf(), in.gf(), done > 0, last && in.relu_out, pws, stream_);
+    bw_wrote(0, op.in);
+}
+
+void Net::backward_l2norm(int op_index) {
+    const Op& op = ops_[op_index];
+    const Tensor& in = tensors_[op.in];
+    const Tensor& out = tensors_[op.out];
+    const int b = bwd_.b, cls = bw_class(op, op_index);
+    hipStream_t ds = cls == 1 ? hstream_ : stream_;
+    SSD_REQUIRE(bwd_.t[op.in].done == 0 && in.consumers != 1, "l2norm backward must be the first of several consumers");
+    bw_need(cls, op.out);
+    if (bf16_)
+        l2norm_bwd(b * in.H * in.W, in.C, in.h(), params_ + scale_off_, out.gh(), in.gh(), grads_ + scale_off_, l2_ws_, ds);
+    else
+        l2norm_bwd(b * in.H * in.W, in.C, in.f(), params_ + scale_off_, out.gf(), in.gf(), grads_ + scale_off_, l2_ws_, ds);
+    bw_wrote(cls, op.in);
+}
+
+// The joins that close a stage.
+void Net::backward_join(bool finished, bool sync_main) {
+    if (finished && bwd_.issued[1] > bwd_.seen[0][1]) bw_sync(0, 1);      // (every side-stream result has a main-stream reader: a no-op)
     // The returned range is final in the weight-gradient stream's order.  Make it final in
     // main-stream order too unless the caller consumes it on the weight-gradient stream itself
     // (sync_main = false keeps the data gradients running ahead); the last stage always joins.
-    if (wstream_ && overlap_ && (side_used || finished) && (sync_main || finished)) {
+    if (wstream_ && overlap_ && (bwd_.side_used || finished) && (sync_main || finished)) {
         HIP_OK(hipEventRecord(ev_w_, wstream_));
         HIP_OK(hipStreamWaitEvent(stream_, ev_w_, 0));
     }
     // Overlap switched off (ssd_set_overlap(0) / SSD_OVERLAP_WGRAD=0): the weight gradients ran on the main
     // stream.  A caller that consumes the range on the weight-gradient stream (sync_main = false) must still
     // find it final there, so that stream waits for the main stream instead.  The same holds for the first layer's weight
-    // gradient, which is issued on the main stream (above).
-    if (wstream_ && !sync_main && (!overlap_ || (finished && bw_first_on_main_))) {
-        HIP_OK(hipEventRecord(ev_dy_, stream_));
-        HIP_OK(hipStreamWaitEvent(wstream_, ev_dy_, 0));
+    // gradient, which is issued on the main stream (wgrad_stream_for).
+    if (wstream_ && !sync_main && (!overlap_ || (finished && bwd_.first_on_main))) wgrad_wait(wstream_, nullptr, stream_);
+}
+
+// A stage: the reverse ops until the filter range that is newly final holds min_floats, then the joins.
+bool Net::backward_step(size_t min_floats, size_t* off, size_t* count, bool sync_main) {
+    bwd_.side_used = false;
+    for (int op_index; (op_index = bwd_.progress.next(min_floats)) >= 0;) {
+        const Op& op = ops_[op_index];
+        const bool ablated = op_ablated(op.name, op.kind, op.head, op.k);
+        prof_.layer = op.name.c_str();
+        if (chain_bwd_ && in_chain_[op_index] && !ablated) {
+            // Round 6 (plan_tail_chain): the first chain op met issues the chain's data gradients (one launch) and every chain layer's
+            // weight gradient (one grouped launch); the other members are skipped when their turn comes -- all but the chain's first
+            // layer, whose data and weight gradients are ordinary launches below (launch_tail_backward leaves it out of the group)
+            if (!bwd_.progress.chain_done) {
+                launch_tail_backward();      // (retires them)
+                prof_.layer = op.name.c_str();
+            }
+            if (op_index != chain_first_) continue;
+        }
+        if (ablated) bwd_.progress.retire(op_index);
+        else if (op.kind == OP_CONV) backward_conv(op_index);
+        else if (op.kind == OP_POOL) backward_pool(op_index);
+        else backward_l2norm(op_index);
+        bwd_.t[op.in].done++;
     }
-    const std::pair<size_t, size_t> range = bw_.end_stage();
+    const bool finished = bwd_.progress.finished();
+    backward_join(finished, sync_main);
+    const std::pair<size_t, size_t> range = bwd_.progress.end_stage();
     *off = range.first;
     *count = range.second;
     return !finished;
@@ -1723,31 +1792,16 @@ void Net::apply_gradients(float grad_scale) {
     SSD_REQUIRE(training_, "handle was created with training = 0");
     g_prof = &prof_;
     prof_.layer = "optimizer";
-    if (rule_kind_ == UPDATE_ADAMW) {
-        // the momentum branches below with the other rule; t counts this update, skipped by the clipped kernel or not
-        ++adam_t_;
-        float* report = nullptr;
-        int slot = 0;
-        if (clip_max_norm_ != 0.f) {
-            ++clip_seq_;
-            slot = (int)(clip_seq_ % LOSS_RING);
-            if (clip_seq_ >= LOSS_RING) HIP_OK(hipEventSynchronize(ev_clip_[slot]));
-            report = clip_dev_ + 2 * slot;
-        }
+    if (rule_kind_ == UPDATE_ADAMW) ++adam_t_;      // t counts this update, skipped by the clipped kernel or not
+    float* report = clip_max_norm_ != 0.f ? begin_clip_slot() : nullptr;      // where the update leaves {norm, factor}
+    if (rule_kind_ == UPDATE_ADAMW)
         adamw_update(params_, mom_, adam_v_, grads_, nparams_, nfilters_, current_lr(), adam_b1_, adam_b2_, adam_eps_, adam_decay_,
                      adam_t_, grad_scale, clip_max_norm_, clip_ws_, report, stream_);
-        if (clip_max_norm_ != 0.f) HIP_OK(hipEventRecord(ev_clip_[slot], stream_));
-    } else if (clip_max_norm_ == 0.f) {
+    else if (!report)
         momentum_update(params_, mom_, grads_, nparams_, current_lr(), momentum_, grad_scale, stream_);
-    } else {
-        // the slot's previous update (LOSS_RING updates ago) has long finished; nothing here waits for this one
-        ++clip_seq_;
-        const int slot = (int)(clip_seq_ % LOSS_RING);
-        if (clip_seq_ >= LOSS_RING) HIP_OK(hipEventSynchronize(ev_clip_[slot]));
-        momentum_update_clipped(params_, mom_, grads_, nparams_, current_lr(), momentum_, grad_scale, clip_max_norm_, clip_ws_,
-                                clip_dev_ + 2 * slot, stream_);
-        HIP_OK(hipEventRecord(ev_clip_[slot], stream_));
-    }
+    else
+        momentum_update_clipped(params_, mom_, grads_, nparams_, current_lr(), momentum_, grad_scale, clip_max_norm_, clip_ws_, report, stream_);
+    if (report) end_clip_slot();
     ++global_step;      // a skipped update counts: the schedule is a function of the steps taken
 }
 
@@ -1832,6 +1886,16 @@ void Net::upload_xy(const float* x, const float* y, int b) {
         HIP_OK(hipMemcpyAsync(y_stage_, y, ny * sizeof(float), hipMemcpyHostToDevice, stream_));
     }
 }
+
+// The clip ring, like the losses': the slot's previous update (LOSS_RING updates ago) has long finished; nothing here waits for this one
+float* Net::begin_clip_slot() {
+    ++clip_seq_;
+    const int slot = (int)(clip_seq_ % LOSS_RING);
+    if (clip_seq_ >= LOSS_RING) HIP_OK(hipEventSynchronize(ev_clip_[slot]));
+    return clip_dev_ + 2 * slot;
+}
+
+void Net::end_clip_slot() { HIP_OK(hipEventRecord(ev_clip_[clip_seq_ % LOSS_RING], stream_)); }
 
 float* Net::begin_loss_slot() {
     ++loss_seq_;
@@ -1925,7 +1989,7 @@ void Net::activation(const char* name, int b, float* out, size_t count) {
         const Tensor& t = tensors_[ti];
         if (t.name != name || !t.data) continue;
         SSD_REQUIRE(!want_grad || t.grad != nullptr, "no gradient storage (training = 0?)");
-        SSD_REQUIRE(!(want_grad && bw_first_fused_ && fused_first_out_ == (int)ti),
+        SSD_REQUIRE(!(want_grad && bwd_.first_fused && bwd_.fused_first_out == (int)ti),
                     "gradient of %s is not materialised: the first layer's weight gradient was computed inside the next layer's data gradient (SSD_POOL_FUSE=3 keeps it)", name);
         for (const Op& op : ops_) {
             SSD_REQUIRE(!(op.kind == OP_POOL && op.fused_fwd && op.in == (int)ti && !want_grad),

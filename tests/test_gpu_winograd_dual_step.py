@@ -1,4 +1,4 @@
-"""-m gpu: the fp32 training step with ONE transform of dy per Winograd layer in backward (csrc/net.hip backward_step: the main stream
+"""-m gpu: the fp32 training step with ONE transform of dy per Winograd layer in backward (csrc/net.hip wgrad_handoff: the main stream
 runs the dual kernel into wino_yt_ and one of two Ya buffers, the weight-gradient stream waits for it) against the step with one
 transform per gradient (ssd_set_wino_dual(h, 0)): mode 2 takes the one transform on EVERY layer with both Winograd gradients, mode 1 on
 the layers of the default shape rule.  Two vgg300 handles, the same weights and inputs, three steps.  Losses, result and
@@ -11,8 +11,7 @@ import pytest
 import torch
 
 from oracle import boxes as ob, ssdvgg_ref as ref
-from ssd_tensorflow_amd._lib import lib, check
-from ssd_tensorflow_amd.ssdvgg import SSDVGG, Session
+from step_state import make, state, assert_same
 
 pytestmark = pytest.mark.gpu
 B, STEPS = 3, 3
@@ -25,34 +24,6 @@ def data():
     rng = np.random.default_rng(23)
     batches = [ref.synth_batch(rng, B, preset)[:2] for _ in range(STEPS)]
     return w, [(torch.from_numpy(x).cuda(), torch.from_numpy(y).cuda()) for x, y in batches]
-
-
-def make(w, mode, overlap):
-    sess = Session(0)
-    net = SSDVGG(sess, 'vgg300')
-    net.build_from_vgg(None, 20, max_batch=B, weights=w)
-    net.build_optimizer(learning_rate=0.001, weight_decay=0.0005, momentum=0.9)
-    net.set_stream(torch.cuda.current_stream().cuda_stream)
-    check(lib.ssd_set_wino_dual(net._h, mode))
-    if not overlap:
-        check(lib.ssd_set_overlap(net._h, 0))
-    return sess, net
-
-
-def state(net):
-    torch.cuda.synchronize()
-    res = np.empty((B, net.preset.num_anchors, net.num_vars), np.float32)
-    check(lib.ssd_get_result(net._h, B, res.ctypes.data))
-    return dict(losses=net.get_losses(), result=res.view(np.uint32), grads=net.grads_flat.clone(), params=net.params_flat.clone(),
-                momentum=net.momentum_flat.clone())
-
-
-def assert_same(a, b, where):
-    assert a['losses'] == b['losses'], f'{where}: losses {a["losses"]} != {b["losses"]}'
-    assert np.array_equal(a['result'], b['result']), f'{where}: result differs'
-    for k in ('grads', 'params', 'momentum'):
-        assert torch.equal(a[k].view(torch.int32), b[k].view(torch.int32)), \
-            f'{where}: {k}_flat differs in {int((a[k].view(torch.int32) != b[k].view(torch.int32)).sum())} words'
 
 
 def step_plain(net, x, y):
