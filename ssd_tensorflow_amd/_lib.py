@@ -181,6 +181,14 @@ SIGNATURES = {
     'ssd_save_second_moment': (i32, [handle, cstr, vp, sz]),
     'ssd_load_second_moment': (i32, [handle, cstr, vp, sz]),
     'ssd_op_adamw_update': (i32, [vp, vp, vp, vp, sz, sz, f32, f32, f32, f32, f32, C.c_longlong, f32, f32, vp, vp, vp]),
+    'ssd_set_ema': (i32, [handle, f32]),
+    'ssd_get_ema': (i32, [handle, p_f32, p_i64, p_i32]),
+    'ssd_set_ema_step': (i32, [handle, C.c_longlong]),
+    'ssd_save_ema': (i32, [handle, cstr, vp, sz]),
+    'ssd_load_ema': (i32, [handle, cstr, vp, sz]),
+    'ssd_ema_swap': (i32, [handle]),
+    'ssd_op_ema_update': (i32, [vp, vp, sz, f32, C.c_longlong, vp]),
+    'ssd_op_ema_swap': (i32, [vp, vp, sz, vp]),
     'ssd_train_step_dev': (i32, [handle, vp, vp, i32]),
     'ssd_eval_step_dev': (i32, [handle, vp, vp, i32]),
     'ssd_infer_dev': (i32, [handle, vp, i32]),

@@ -1290,6 +1290,45 @@ int ssd_load_second_moment(ssd_handle h, const char* name, const float* data, si
     n.load_variable(name, data, count, 3);
     API_END
 }
+// ... and a weight EMA behind every update: the values are checked before the handle, like the rule's
+static void check_ema_step(long long t) { SSD_REQUIRE(t >= 0, "weight EMA: the count of EMA updates must be >= 0, got %lld", t); }
+int ssd_set_ema(ssd_handle h, float decay) {
+    API_BEGIN
+    if (decay != 0.f) ema_check(decay);
+    Net& n = N(h);
+    DeviceGuard dev_guard_(n.device());
+    n.set_ema(decay == 0.f ? 0.f : decay);      // (-0 is stored as 0)
+    API_END
+}
+int ssd_get_ema(ssd_handle h, float* decay, long long* t, int* swapped) {
+    API_BEGIN
+    Net& n = N(h);
+    if (decay) *decay = n.ema_decay();
+    if (t) *t = n.ema_step();
+    if (swapped) *swapped = n.ema_swapped() ? 1 : 0;
+    API_END
+}
+int ssd_set_ema_step(ssd_handle h, long long t) {
+    API_BEGIN
+    check_ema_step(t);
+    N(h).set_ema_step(t);
+    API_END
+}
+int ssd_save_ema(ssd_handle h, const char* name, float* data, size_t count) {
+    API_BEGIN_NET(h)
+    n.save_variable(name, data, count, 4);
+    API_END
+}
+int ssd_load_ema(ssd_handle h, const char* name, const float* data, size_t count) {
+    API_BEGIN_NET(h)
+    n.load_variable(name, data, count, 4);
+    API_END
+}
+int ssd_ema_swap(ssd_handle h) {
+    API_BEGIN_NET(h)
+    n.ema_swap_arenas();
+    API_END
+}
 int ssd_null_gradients_dev(ssd_handle h) {
     API_BEGIN_NET(h)
     n.null_gradients_step();
@@ -2063,6 +2102,22 @@ int ssd_op_adamw_update(float* w, float* m, float* v, const float* g, size_t n, 
     check_grad_clip(max_norm);
     SSD_REQUIRE(w && m && v && g && (max_norm == 0.f || ws_dev), "null buffer");
     adamw_update(w, m, v, g, n, n_decay, lr, beta1, beta2, eps, decay, t, grad_scale, max_norm, ws_dev, report_dev, (hipStream_t)stream);
+    API_END
+}
+int ssd_op_ema_update(float* e, const float* w, size_t n, float decay, long long t, void* stream) {
+    API_BEGIN
+    ema_check(decay);
+    check_ema_step(t);
+    SSD_REQUIRE(n % 4 == 0, "weight EMA: arena size must be a multiple of 4");
+    SSD_REQUIRE(e && w, "null buffer");
+    ema_update(e, w, n, decay, t, (hipStream_t)stream);
+    API_END
+}
+int ssd_op_ema_swap(float* a, float* b, size_t n, void* stream) {
+    API_BEGIN
+    SSD_REQUIRE(n % 4 == 0, "weight EMA: arena size must be a multiple of 4");
+    SSD_REQUIRE(a && b, "null buffer");
+    ema_swap(a, b, n, (hipStream_t)stream);
     API_END
 }
 int ssd_op_clock_monitor(unsigned* out_dev, int nsamples, unsigned period_ticks, void* stream) {

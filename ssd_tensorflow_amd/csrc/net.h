@@ -142,6 +142,17 @@ public:
     void get_update_rule(int* kind, float* b1, float* b2, float* eps, float* decay) const;
     long long adam_step() const { return adam_t_; }      // AdamW updates enqueued since the state was zeroed (skipped ones count)
     void set_adam_step(long long t);
+    // the weight EMA (include/ssdvgg_hip.h "weight EMA"; ops.h ema_update): decay in (0, 1) switches it on -- the arena allocated
+    // on the first enabling, filled with the parameters and t = 0 on every switch from off to on -- and 0 off; the caller has
+    // checked the value.  While it is on, one EMA update follows every update apply_gradients enqueues.
+    void set_ema(float decay);
+    float ema_decay() const { return ema_decay_; }
+    long long ema_step() const { return ema_t_; }        // EMA updates enqueued since the last enabling
+    void set_ema_step(long long t);
+    bool ema_swapped() const { return ema_swapped_; }
+    // the contents of the parameter arena and the EMA arena exchanged (one kernel on the handle's stream): the next forward derives
+    // every mirror and transform from the masters afresh.  While swapped, updates, backward and loads into either arena are refused.
+    void ema_swap_arenas();
     void null_gradients_step();                                        // gradient arena of a step without samples
     void set_optimizer(const float* lr_values, const long long* bounds, int n, float momentum, float wd);
 
@@ -158,8 +169,8 @@ public:
     void set_result(const float* pred_dev, int b);
 
     const std::vector<Variable>& variables() const { return vars_; }
-    void load_variable(const char* name, const float* host, size_t count, int which);   // 0 params, 2 momentum, 3 second moment
-    void save_variable(const char* name, float* host, size_t count, int which);         // 0 params, 1 grads, 2 momentum, 3 second moment
+    void load_variable(const char* name, const float* host, size_t count, int which);   // 0 params, 2 momentum, 3 second moment, 4 EMA
+    void save_variable(const char* name, float* host, size_t count, int which);         // 0 params, 1 grads, 2 momentum, 3 second moment, 4 EMA
     void activation(const char* name, int b, float* out, size_t count);
     void activation_shape(const char* name, int* H, int* W, int* C) const;
     void pool_fusion(int* out, int cap, int* count) const;      // per 2x2 stride-2 pool in graph order: bit 0 fused forward, bit 1 fused backward
@@ -407,6 +418,14 @@ private:
     float adam_b1_ = 0.9f, adam_b2_ = 0.999f, adam_eps_ = 1e-8f, adam_decay_ = 0.01f;
     long long adam_t_ = 0;
     float* adam_v_ = nullptr;             // nparams_ floats from hip_, null until the handle is first put under AdamW
+    // the weight EMA (apply_gradients, behind the update)
+    float* ema_ = nullptr;                // nparams_ floats from hip_, null until the EMA is first switched on
+    float ema_decay_ = 0.f;               // 0: off
+    long long ema_t_ = 0;
+    bool ema_swapped_ = false;            // the parameter arena holds the average and ema_ the raw weights (ema_swap_arenas)
+    bool fwd_swapped_ = false;            // ema_swapped_ at the last forward pass: what its mirrors and filter transforms were made from
+    hipEvent_t ev_ema_ = nullptr;         // behind every swap: the side streams wait for it (made with ema_)
+    void require_unswapped(const char* what) const;
     double* anchors_dev_ = nullptr;
     int* anchors_abs_dev_ = nullptr;
     void* detect_ws_ = nullptr;

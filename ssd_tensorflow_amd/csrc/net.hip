@@ -1121,6 +1121,7 @@ void Net::forward(const float* x, int b, bool train_mode, const float* y) {
     tensors_[input_t_].data = const_cast<float*>(x);
     pool_arg_op_ = -1;
     ++fwd_serial_;
+    fwd_swapped_ = ema_swapped_;
     const bool side = hstream_ && overlap_;
     static const int lanes_env = [] { const char* v = getenv("SSD_FWD_LANES"); return v ? atoi(v) : 0; }();
     const int want_lanes = lanes_env > 0 ? lanes_env : 2;
@@ -1547,6 +1548,10 @@ void Net::wgrad_wait(hipStream_t ws, hipEvent_t carried, hipStream_t from) {
 
 void Net::backward_begin(int b, const float* y) {
     SSD_REQUIRE(training_, "handle was created with training = 0");
+    require_unswapped("backward");
+    // (backward reads the flipped filter transforms and the bf16 mirrors that the LAST forward pass of any kind made from its masters)
+    SSD_REQUIRE(!fwd_swapped_, "weight EMA: backward is refused behind a forward pass that ran while the average was swapped in: "
+                               "run the training forward pass again");
     g_prof = &prof_;
     prof_.layer = "loss";
     const bool side = hstream_ && overlap_;
@@ -1728,6 +1733,7 @@ void Net::backward_join(bool finished, bool sync_main) {
 
 // A stage: the reverse ops until the filter range that is newly final holds min_floats, then the joins.
 bool Net::backward_step(size_t min_floats, size_t* off, size_t* count, bool sync_main) {
+    require_unswapped("backward");
     bwd_.side_used = false;
     for (int op_index; (op_index = bwd_.progress.next(min_floats)) >= 0;) {
         const Op& op = ops_[op_index];
@@ -1790,6 +1796,7 @@ float Net::current_lr() const {
 
 void Net::apply_gradients(float grad_scale) {
     SSD_REQUIRE(training_, "handle was created with training = 0");
+    require_unswapped("the update");
     g_prof = &prof_;
     prof_.layer = "optimizer";
     if (rule_kind_ == UPDATE_ADAMW) ++adam_t_;      // t counts this update, skipped by the clipped kernel or not
@@ -1802,7 +1809,64 @@ void Net::apply_gradients(float grad_scale) {
     else
         momentum_update_clipped(params_, mom_, grads_, nparams_, current_lr(), momentum_, grad_scale, clip_max_norm_, clip_ws_, report, stream_);
     if (report) end_clip_slot();
+    // the average follows every update enqueued, one that the clipped kernel skipped too: like global_step, t is a function of the
+    // updates taken
+    if (ema_decay_ != 0.f) {
+        ema_update(ema_, params_, nparams_, ema_decay_, ema_t_, stream_);
+        ++ema_t_;
+    }
     ++global_step;      // a skipped update counts: the schedule is a function of the steps taken
+}
+
+void Net::require_unswapped(const char* what) const {
+    SSD_REQUIRE(!ema_swapped_, "weight EMA: %s is refused while the average is swapped in (ssd_ema_swap)", what);
+}
+
+void Net::set_ema(float decay) {
+    SSD_REQUIRE(training_, "weight EMA: the handle was created with training = 0");
+    require_unswapped("ssd_set_ema");
+    if (decay != 0.f && ema_decay_ == 0.f) {
+        const size_t bytes = nparams_ * sizeof(float);
+        // on first use, so that a handle that never averages holds the memory it held without the option
+        if (!ema_) {
+            ema_ = static_cast<float*>(hip_.mem(bytes));
+            ev_ema_ = hip_.event();
+        }
+        HIP_OK(hipMemcpyAsync(ema_, params_, bytes, hipMemcpyDeviceToDevice, stream_));
+        // a rare call: the copy is finished when it returns, so a caller who gives the handle another stream afterwards
+        // (set_stream orders nothing) finds the first EMA update behind it
+        HIP_OK(hipStreamSynchronize(stream_));
+        ema_t_ = 0;
+    }
+    ema_decay_ = decay;
+}
+
+void Net::set_ema_step(long long t) {
+    SSD_REQUIRE(training_, "weight EMA: the handle was created with training = 0");
+    require_unswapped("ssd_set_ema_step");
+    SSD_REQUIRE(t >= 0, "weight EMA: the count of EMA updates must be >= 0, got %lld", t);
+    ema_t_ = t;
+}
+
+void Net::ema_swap_arenas() {
+    SSD_REQUIRE(training_, "weight EMA: the handle was created with training = 0");
+    SSD_REQUIRE(ema_decay_ != 0.f, "weight EMA: nothing to swap, the EMA is off (ssd_set_ema)");
+    g_prof = &prof_;
+    prof_.layer = "optimizer";
+    // Nothing else needs refreshing: what a pass reads besides the fp32 masters -- the Winograd filter transforms, the bf16 mirrors,
+    // the quantised images, the packed tail filters -- forward_filters derives from the masters at the head of every pass, and
+    // backward, which reads the flipped transforms and mirrors of the last forward pass, is refused until the weights are back and
+    // a forward pass has run on them (fwd_swapped_).
+    // Everything a pass reads from the masters on a side stream is waited for by its lanes, but for the flipped transforms of a
+    // training pass, which only backward waits for: the swap waits for them too (the wait stays pending for backward).
+    if (wino_flip_pending_) HIP_OK(hipStreamWaitEvent(stream_, ev_wino_flip_, 0));
+    ema_swap(params_, ema_, nparams_, stream_);
+    // The side streams read the masters at the head of a pass (forward_filters), and an fp32 inference pass of fewer than 8 samples
+    // does not make them wait for the main stream (forward: neither bf16_ nor train_mode nor two lanes): they wait for the swap here.
+    HIP_OK(hipEventRecord(ev_ema_, stream_));
+    if (hstream_) HIP_OK(hipStreamWaitEvent(hstream_, ev_ema_, 0));
+    if (s2_ && s2_ != hstream_) HIP_OK(hipStreamWaitEvent(s2_, ev_ema_, 0));
+    ema_swapped_ = !ema_swapped_;
 }
 
 void Net::set_grad_clip(float max_norm) {
@@ -1861,6 +1925,7 @@ void Net::backward_apply(int b, const float* y, float grad_scale) {
 
 void Net::null_gradients_step() {
     SSD_REQUIRE(training_, "handle was created with training = 0");
+    require_unswapped("a step without samples");      // (its gradient is the L2 term of the raw weights)
     null_gradients(params_, grads_, nfilters_, nparams_, wd_, stream_);
     // a step without samples has no loss kernel: its slot of the ring is written here, after the slot's previous user
     // (LOSS_RING passes ago) has finished -- no kernel in flight writes to it
@@ -1944,7 +2009,9 @@ void Net::load_variable(const char* name, const float* host, size_t count, int w
     const Variable& v = find_var(name);
     SSD_REQUIRE(count == v.count(), "variable %s holds %zu floats, got %zu", name, v.count(), count);
     SSD_REQUIRE(which != 3 || adam_v_, "second moment of %s: the handle has never been under AdamW (ssd_set_update_rule)", name);
-    float* base = which == 0 ? params_ : which == 3 ? adam_v_ : mom_;
+    SSD_REQUIRE(which != 4 || ema_, "weight EMA of %s: the handle has never been under a weight EMA (ssd_set_ema)", name);
+    if (which == 0 || which == 4) require_unswapped(which == 0 ? "ssd_load_variable" : "ssd_load_ema");
+    float* base = which == 0 ? params_ : which == 3 ? adam_v_ : which == 4 ? ema_ : mom_;
     SSD_REQUIRE(base != nullptr, "arena not allocated (training = 0?)");
     HIP_OK(hipStreamSynchronize(stream_));
     HIP_OK(hipMemcpy2D(base + v.off, v.pitch * sizeof(float), host, v.width * sizeof(float), v.width * sizeof(float), v.rows,
@@ -1955,7 +2022,8 @@ void Net::save_variable(const char* name, float* host, size_t count, int which) 
     const Variable& v = find_var(name);
     SSD_REQUIRE(count == v.count(), "variable %s holds %zu floats, got %zu", name, v.count(), count);
     SSD_REQUIRE(which != 3 || adam_v_, "second moment of %s: the handle has never been under AdamW (ssd_set_update_rule)", name);
-    const float* base = which == 0 ? params_ : (which == 1 ? grads_ : which == 3 ? adam_v_ : mom_);
+    SSD_REQUIRE(which != 4 || ema_, "weight EMA of %s: the handle has never been under a weight EMA (ssd_set_ema)", name);
+    const float* base = which == 0 ? params_ : (which == 1 ? grads_ : which == 3 ? adam_v_ : which == 4 ? ema_ : mom_);
     SSD_REQUIRE(base != nullptr, "arena not allocated (training = 0?)");
     HIP_OK(hipStreamSynchronize(stream_));
     HIP_OK(hipMemcpy2D(host, v.width * sizeof(float), base + v.off, v.pitch * sizeof(float), v.width * sizeof(float), v.rows,

@@ -152,6 +152,13 @@ constexpr int ADAMW_GRID_CAP = 256 * 16;
 void adamw_check(float b1, float b2, float eps, float decay);
 void adamw_update(float* w, float* m, float* v, const float* g, size_t n, size_t n_decay, float lr, float b1, float b2, float eps,
                   float decay, long long t, float gscale, float max_norm, void* ws, float* report, hipStream_t s);
+// ---- weight EMA (optim.hip; contract in include/ssdvgg_hip.h "weight EMA").  e, w (a, b): n floats, n a multiple
+// of 4.  t >= 0: the count of EMA updates before this one; the host computes omd = (float)(1 - min(decay, (1 + t) / (10 + t))) in
+// double.  ema_update: one launch of ema_kernel (ProfScope "ema_update"), e -= omd * (e - w), adamw_update's launch shape.
+// ema_swap: one launch of swap_kernel ("ema_swap"), the contents of a and b exchanged.  ema_check refuses a decay outside (0, 1).
+void ema_check(float decay);
+void ema_update(float* e, const float* w, size_t n, float decay, long long t, hipStream_t s);
+void ema_swap(float* a, float* b, size_t n, hipStream_t s);
 
 // gradients of a step without samples (a data-parallel rank whose shard of a short last batch is empty)
 void null_gradients(const float* w, float* g, size_t nfilters, size_t n, float wd, hipStream_t s);

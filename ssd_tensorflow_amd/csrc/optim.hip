@@ -1,10 +1,13 @@
-// AdamW update of the parameter arena for gfx950 (contract in include/ssdvgg_hip.h "update rule").
+// AdamW update of the parameter arena for gfx950 (contract in include/ssdvgg_hip.h "update rule"), and the weight EMA
+// behind every update with the kernel that swaps it in (same header, "weight EMA"; tests/ema_ref.py).
 // Every fp32 operation below is one rounding, in the order written: this file is compiled with -ffp-contract=off (Makefile,
 // EXTRA_optim) and must stay out of ops.hip, which is compiled with contraction on.  Division and square root are the
 // compiler's correctly rounded sequences, so a numpy float32 restatement of the loop has the same bits (tests/adamw_ref.py).
 #include "ops.h"
 #include "bf16.h"
+#include <algorithm>
 #include <cmath>
+#include <cstdint>
 
 #pragma clang fp contract(off)
 
@@ -100,6 +103,65 @@ void adamw_update(float* w, float* m, float* v, const float* g, size_t n, size_t
     grad_norm_pass(g, n, gscale, max_norm, ws, report, s);
     ProfScope prof("adamw_update_clipped", 0.0, 28.0 * n, s);
     hipLaunchKernelGGL(adamw_kernel<true>, grid, block, 0, s, w, m, v, g, n / 4, n_decay, a, gscale, (const ClipState*)ws);
+    HIP_OK(hipGetLastError());
+}
+
+// ---- weight EMA (contract in include/ssdvgg_hip.h "weight EMA"): e -= omd * (e - w), two roundings of their own and
+// the subtraction's, in that order.  HBM-bound: 12 bytes per parameter (e, w in; e out); adamw_kernel's shape, 16 bytes per lane and
+// trip with both loads in flight before the first use.  Padding floats of the arena are averaged like any other.
+__global__ __launch_bounds__(ADAMW_BLOCK) void ema_kernel(float* __restrict__ e, const float* __restrict__ w, size_t n4, float omd) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        f32x4 e4 = ld4(e + i * 4);
+        const f32x4 w4 = ld4(w + i * 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float diff = e4[k] - w4[k];
+            e4[k] = e4[k] - (omd * diff);
+        }
+        st4(e + i * 4, e4);
+    }
+}
+
+// The contents of two arenas exchanged: 16 bytes per parameter (a, b in; a, b out).  Every group of four is read and written by one
+// lane alone, so a and b need no order between lanes.  The two must not overlap (__restrict__): ema_buffers_check refuses that.
+__global__ __launch_bounds__(ADAMW_BLOCK) void swap_kernel(float* __restrict__ a, float* __restrict__ b, size_t n4) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+        const f32x4 a4 = ld4(a + i * 4);
+        const f32x4 b4 = ld4(b + i * 4);
+        st4(a + i * 4, b4);
+        st4(b + i * 4, a4);
+    }
+}
+
+void ema_check(float decay) {
+    // (a NaN fails both comparisons; 0.99999999 is 1.0 by the time it is a float)
+    SSD_REQUIRE(decay > 0.f && decay < 1.f, "weight EMA: decay %g is outside (0, 1)", (double)decay);
+}
+
+// what both kernels assume of their two buffers: n a multiple of 4, 16-byte aligned (they move f32x4), no overlap (__restrict__)
+static void ema_buffers_check(const float* a, const float* b, size_t n) {
+    SSD_REQUIRE(n % 4 == 0, "weight EMA: arena size must be a multiple of 4");
+    SSD_REQUIRE(((uintptr_t)a | (uintptr_t)b) % 16 == 0, "weight EMA: the buffers must be 16-byte aligned");
+    const uintptr_t lo = std::min((uintptr_t)a, (uintptr_t)b), hi = std::max((uintptr_t)a, (uintptr_t)b);
+    SSD_REQUIRE(n == 0 || hi - lo >= n * sizeof(float), "weight EMA: the two buffers overlap");
+}
+
+void ema_update(float* e, const float* w, size_t n, float decay, long long t, hipStream_t s) {
+    ema_check(decay);
+    SSD_REQUIRE(t >= 0, "weight EMA: the count of EMA updates must be >= 0, got %lld", t);
+    ema_buffers_check(e, w, n);
+    // TensorFlow's num_updates form: the average follows quickly at first
+    const double d = std::min((double)decay, (1.0 + (double)t) / (10.0 + (double)t));
+    const float omd = (float)(1.0 - d);
+    ProfScope prof("ema_update", 0.0, 12.0 * n, s);
+    hipLaunchKernelGGL(ema_kernel, dim3(adamw_grid(n / 4)), dim3(ADAMW_BLOCK), 0, s, e, w, n / 4, omd);
+    HIP_OK(hipGetLastError());
+}
+
+void ema_swap(float* a, float* b, size_t n, hipStream_t s) {
+    ema_buffers_check(a, b, n);
+    ProfScope prof("ema_swap", 0.0, 16.0 * n, s);
+    hipLaunchKernelGGL(swap_kernel, dim3(adamw_grid(n / 4)), dim3(ADAMW_BLOCK), 0, s, a, b, n / 4);
     HIP_OK(hipGetLastError());
 }
 

@@ -13,7 +13,7 @@ import numpy as np
 from .annotate import Style, write_image, GpuJpegWriter
 from .infer import (sample_generator, resolve_class_names, add_fp8_arguments, check_fp8_arguments, fp8_batches, add_decode_arguments,
                     check_decode_arguments, decode_keywords)
-from .ssdvgg import SSDVGG, Session
+from .ssdvgg import SSDVGG, Session, checkpoint_has_ema, NO_EMA_IN_FILE
 from .ssdutils import get_preset_by_name, boxes_from_detection
 from .utils import default_colors
 
@@ -30,6 +30,9 @@ def main(argv=None):
                              '(calibrated scales), or mxfp8: the same layers with block scales chosen from the data (no calibration; the fc graph\'s 7x7 fc6 joins '
                              'them when the environment has SSD_MXFP8_BIGK=1), or mxfp6: the mxfp8 layers on 6-bit e2m3 operands with block scales on '
                              'activations and filters (no calibration; fc6 stays on bf16)')
+    parser.add_argument('--weights', default='auto', choices=['auto', 'raw', 'ema'],
+                        help="a model file of a run with --ema-decay holds two sets of weights: raw = the last iterate; ema = the average (an error "
+                             "if the file has none); auto = the average where the file has one.  Every --dtype, and fp8's calibration, runs on the chosen set")
     add_fp8_arguments(parser)
     parser.add_argument('--decoder', default='gpu', choices=['pillow', 'gpu'],
                         help='gpu: baseline JPEGs are decoded on the GPU, other files as with pillow (same pixels); pillow: every file is decoded on the host')
@@ -61,8 +64,11 @@ def main(argv=None):
         with np.load(args.model, allow_pickle=False) as ck:
             pname, num_classes = str(ck['__preset__']), int(ck['__num_classes__'])
             stored = ck['__class_names__'] if '__class_names__' in ck.files else None
+            if args.weights == 'ema' and not checkpoint_has_ema(ck):
+                print('[!] Bad --weights:', NO_EMA_IN_FILE % (args.model,)); return 1
         net = SSDVGG(sess, get_preset_by_name(pname))
-        net.build_from_metagraph(None, args.model, max_batch=args.batch_size, dtype=args.dtype)
+        net.build_from_metagraph(None, args.model, max_batch=args.batch_size, dtype=args.dtype, weights=args.weights)
+        print('[i] Weights:       ', net.weights)
         lid2name = resolve_class_names(num_classes, None, stored)
         names = [str(lid2name[i]) for i in range(num_classes)]
         colors = default_colors(names)

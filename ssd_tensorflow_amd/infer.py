@@ -20,7 +20,7 @@ import numpy as np
 
 from .average_precision import APCalculator, DeviceAPCalculator, APs2mAP, add_ap_arguments
 from .coco_eval import COCOEvaluator, DeviceCOCOEvaluator, aps_of, format_summary, summarize
-from .ssdvgg import SSDVGG, Session
+from .ssdvgg import SSDVGG, Session, checkpoint_has_ema, NO_EMA_IN_FILE
 from .ssdutils import get_preset_by_name, boxes_from_detection
 from .training_data import default_class_names
 from .pascal_summary import PascalSummary
@@ -250,6 +250,9 @@ def main(argv=None):
                              '(calibrated scales), or mxfp8: the same layers with block scales chosen from the data (no calibration; the fc graph\'s 7x7 fc6 joins '
                              'them when the environment has SSD_MXFP8_BIGK=1), or mxfp6: the mxfp8 layers on 6-bit e2m3 operands with block scales on '
                              'activations and filters (no calibration; fc6 stays on bf16)')
+    parser.add_argument('--weights', default='auto', choices=['auto', 'raw', 'ema'],
+                        help="a checkpoint of a run with --ema-decay holds two sets of weights: raw = the last iterate; ema = the average (an error "
+                             "if the file has none); auto = the average where the file has one.  Every --dtype, and fp8's calibration, runs on the chosen set")
     add_fp8_arguments(parser)
     add_ap_arguments(parser)
     parser.add_argument('--coco-results', default=None, metavar='FILE',
@@ -338,8 +341,11 @@ def main(argv=None):
                 pname, num_classes = str(ck['__preset__']), int(ck['__num_classes__'])
                 if '__class_names__' in ck.files:
                     stored_names = ck['__class_names__']
+                if args.weights == 'ema' and not checkpoint_has_ema(ck):
+                    print('[!] Bad --weights:', NO_EMA_IN_FILE % (ckpt,)); return 1
             net = SSDVGG(sess, get_preset_by_name(pname))
-            net.build_from_metagraph(None, ckpt, max_batch=args.batch_size, dtype=args.dtype)
+            net.build_from_metagraph(None, ckpt, max_batch=args.batch_size, dtype=args.dtype, weights=args.weights)
+            print('[i] Weights:           ', net.weights)
         else:
             num_classes = args.num_classes
             net = SSDVGG(sess, get_preset_by_name(args.preset))

@@ -12,6 +12,7 @@ reference's train.py / infer.py loops read unchanged:
 PyTorch appears only as the allocator of the parameter / gradient / momentum arenas
 (so torch.distributed can all-reduce the gradient arena in place) and as stream owner.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -133,6 +134,34 @@ def checkpoint_update_rule(ck):
         return ('momentum',) + ADAM_DEFAULTS
     return (str(ck['__optimizer__']),) + tuple(float(np.float32(ck[k])) for k in
                                                ('__adam_beta1__', '__adam_beta2__', '__adam_eps__', '__adam_decay__'))
+
+
+# which set of a checkpoint with a weight EMA becomes an inference handle's parameters (build_from_metagraph)
+WEIGHT_SETS = ('auto', 'raw', 'ema')
+
+
+def ema_decay_config(ema_decay=0.0):
+    """The decay of the weight EMA as the library gets it, a float32 (include/ssdvgg_hip.h "weight EMA"; DESIGN.md 37): 0 is off;
+    anything else outside (0, 1) -- NaN, and 1.0 as a float32 too: ValueError."""
+    d = float(np.float32(ema_decay))
+    if d != 0.0 and not 0.0 < d < 1.0:
+        raise ValueError('weight EMA: decay must be 0 (off) or lie in (0, 1) as a float32, got %r' % (ema_decay,))
+    return abs(d) if d == 0.0 else d
+
+
+def checkpoint_ema(ck):
+    """The decay of the weight EMA of an opened checkpoint's run; a file without __ema_decay__ is a run's without one: 0.0."""
+    if '__ema_decay__' not in ck.files:
+        return 0.0
+    return float(np.float32(ck['__ema_decay__']))
+
+
+def checkpoint_has_ema(ck):
+    """whether an opened checkpoint holds the averaged weights (__ema__/<variable>) beside the raw ones"""
+    return any(k.startswith('__ema__/') for k in ck.files)
+
+
+NO_EMA_IN_FILE = "weights='ema': %s holds no weight EMA (its run had --ema-decay 0)"
 
 
 class _Token:
@@ -279,6 +308,7 @@ class SSDVGG:
         self.preset = get_preset_by_name(preset) if isinstance(preset, str) else preset
         self.session = session
         self._h = None
+        self.weights = 'raw'      # the set the parameters hold: 'ema' after build_from_metagraph took a checkpoint's average
         self.__built = False
         self.__build_names()
         if session is not None:
@@ -322,16 +352,29 @@ class SSDVGG:
             self.load_variables(biases)
         self.__built = True
 
-    def build_from_metagraph(self, metagraph_file, checkpoint_file, max_batch=32, training=False, dtype='f32'):
+    def build_from_metagraph(self, metagraph_file, checkpoint_file, max_batch=32, training=False, dtype='f32', weights='auto'):
         """ssdvgg.py:120-130: restore a trained net.  checkpoint_file is an .npz written by
-        save_checkpoint (variables under the reference's TF names + preset/num_classes)."""
+        save_checkpoint (variables under the reference's TF names + preset/num_classes).
+        weights: which set of a run with a weight EMA becomes the parameters.  'raw': the variables, the last
+        iterate; 'ema': the averages under __ema__/<name> in their place (an error if the file has none); 'auto' (the default):
+        'ema' for training=False when the file has them, else 'raw' -- so a file without them loads as before under every dtype.
+        With training=True the raw weights always go to the parameters (build_optimizer_from_metagraph restores the average)."""
+        if weights not in WEIGHT_SETS:
+            raise ValueError('weights must be one of %s, got %r' % (list(WEIGHT_SETS), weights))
         ck = np.load(checkpoint_file, allow_pickle=False)
         num_classes = int(ck['__num_classes__'])
         self.num_classes = num_classes + 1
         self.num_vars = num_classes + 5
         a_trous = bool(int(ck['__a_trous__'])) if '__a_trous__' in ck.files else True      # (older checkpoints: a-trous)
+        has_ema = checkpoint_has_ema(ck)
+        if weights == 'ema' and not has_ema:
+            raise ValueError(NO_EMA_IN_FILE % (checkpoint_file,))
         self._create(num_classes, max_batch, training, 0, dtype, a_trous)
-        self.load_variables({k: ck[k] for k in ck.files if not k.startswith('__')})
+        self.weights = 'ema' if has_ema and not training and weights != 'raw' else 'raw'      # the set the parameters hold
+        if self.weights == 'ema':      # (save_checkpoint writes an average for every variable)
+            self.load_variables({k[len('__ema__/'):]: ck[k] for k in ck.files if k.startswith('__ema__/')})
+        else:
+            self.load_variables({k: ck[k] for k in ck.files if not k.startswith('__')})
         self._ckpt = ck
         self.__built = True
 
@@ -397,7 +440,7 @@ class SSDVGG:
     # ------------------------------------------------------------------ optimizer
     def build_optimizer(self, learning_rate=0.001, weight_decay=0.0005, momentum=0.9, global_step=None, loss='mining',
                         focal_gamma=2.0, focal_alpha=0.25, loc_loss='smooth_l1', loc_weight=1.0, clip_norm=0.0, optimizer='momentum',
-                        adam_beta1=0.9, adam_beta2=0.999, adam_eps=1e-8, adam_decay=0.01):
+                        adam_beta1=0.9, adam_beta2=0.999, adam_eps=1e-8, adam_decay=0.01, ema_decay=0.0):
         """ssdvgg.py:375-599.  learning_rate: float or LearningRate (train.py:43-47).  loss: 'mining' (the reference's 3:1
         hard-negative mining) or 'focal' (every anchor, damped by (1 - p_t)^focal_gamma and weighted focal_alpha on positives,
         1 - focal_alpha on background; a sample without positives still trains its background anchors).
@@ -406,13 +449,16 @@ class SSDVGG:
         clip_norm: clip the gradient by its global norm in the update (0, the default: off; inf: measure only).
         optimizer: 'momentum' (the reference's rule, the default) or 'adamw'  with adam_beta1, adam_beta2, adam_eps
         and the decoupled adam_decay on the filters; under 'adamw' `momentum` is ignored and `weight_decay` stays the L2 term of
-        the loss (0 gives pure AdamW).  Changing the rule zeroes the accumulators."""
+        the loss (0 gives pure AdamW).  Changing the rule zeroes the accumulators.
+        ema_decay: keep an exponential moving average of the weights behind every update (0, the default: off; DESIGN.md 37);
+        averaged_weights() evaluates on it and save_checkpoint keeps both sets."""
         if not self.training:
             raise RuntimeError('build_from_* was called with training=False')
         self.set_loss(loss, focal_gamma, focal_alpha)
         self.set_loc_loss(loc_loss, loc_weight)
         self.set_grad_clip(clip_norm)
         self.set_update_rule(optimizer, adam_beta1, adam_beta2, adam_eps, adam_decay)
+        self.set_ema(ema_decay)
         lr = learning_rate if isinstance(learning_rate, LearningRate) else LearningRate([learning_rate], [])
         vals = np.array(lr.values, np.float32)
         bnds = np.array(lr.boundaries + [0], np.int64)
@@ -438,7 +484,7 @@ class SSDVGG:
         self.build_optimizer(lr, float(ck['__weight_decay__']), float(ck['__momentum__']), int(ck['__global_step__']),
                              loss=loss, focal_gamma=gamma, focal_alpha=alpha, loc_loss=loc_loss, loc_weight=loc_weight,
                              clip_norm=checkpoint_clip_norm(ck), optimizer=rule, adam_beta1=b1, adam_beta2=b2, adam_eps=eps,
-                             adam_decay=decay)
+                             adam_decay=decay, ema_decay=checkpoint_ema(ck))
         for k in ck.files:
             if k.startswith('__momentum__/'):
                 a = np.ascontiguousarray(ck[k], np.float32)
@@ -446,8 +492,13 @@ class SSDVGG:
             elif k.startswith('__adam_v__/'):
                 a = np.ascontiguousarray(ck[k], np.float32)
                 check(lib.ssd_load_second_moment(self._h, k[len('__adam_v__/'):].encode(), np_ptr(a), a.size))
+            elif k.startswith('__ema__/'):
+                a = np.ascontiguousarray(ck[k], np.float32)
+                check(lib.ssd_load_ema(self._h, k[len('__ema__/'):].encode(), np_ptr(a), a.size))
         if rule == 'adamw':
             check(lib.ssd_set_adam_step(self._h, int(ck['__adam_step__'])))
+        if checkpoint_ema(ck) != 0.0:
+            check(lib.ssd_set_ema_step(self._h, int(ck['__ema_step__'])))
 
     def build_summaries(self, restore):
         """ssdvgg.py:625-649 builds TensorBoard histograms; observability is out of scope here."""
@@ -497,6 +548,46 @@ class SSDVGG:
         """AdamW's second moment by variable name; an error while the handle has never been under AdamW"""
         return self._save(lib.ssd_save_second_moment, names)
 
+    # ------------------------------------------------------------------ weight EMA (DESIGN.md 37)
+    def set_ema(self, decay=0.0):
+        """Keep an exponential moving average of the weights behind every update from the next one on (ssd_set_ema): decay in
+        (0, 1), warmed up as min(decay, (1 + t) / (10 + t)).  Switching it on copies the current weights and counts from t = 0;
+        another decay while it is on keeps the average and t; 0 switches it off."""
+        check(lib.ssd_set_ema(self._h, ema_decay_config(decay)))
+
+    def get_ema(self):
+        """(decay, t, swapped): the decay (0.0: off), the count of EMA updates since it was switched on, and whether the average
+        is swapped in (swap_ema)"""
+        d = C.c_float(); t = C.c_longlong(); s = C.c_int()
+        check(lib.ssd_get_ema(self._h, C.byref(d), C.byref(t), C.byref(s)))
+        return float(d.value), t.value, bool(s.value)
+
+    def save_ema(self, names=None):
+        """The averaged weights by variable name (while swapped: the raw ones, and save_variables the averaged); an error while
+        the handle has never had the EMA on"""
+        return self._save(lib.ssd_save_ema, names)
+
+    def swap_ema(self):
+        """Exchange the contents of the parameters and the average on the GPU (ssd_ema_swap): forward, detect and
+        save_variables then run on the average until the next call; updates, backward and loads are refused meanwhile."""
+        check(lib.ssd_ema_swap(self._h))
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """`with net.averaged_weights():` -- the block runs on the averaged weights; the raw ones are back when it is left, by an
+        exception too.  With the EMA off (or inside another such block) it does nothing, so callers need no branch."""
+        on = False
+        if self.training:
+            decay, _, swapped = self.get_ema()
+            on = decay != 0.0 and not swapped
+        if on:
+            self.swap_ema()
+        try:
+            yield on
+        finally:
+            if on:
+                self.swap_ema()
+
     @property
     def adam_step(self):
         """AdamW updates since the accumulators were zeroed (the t of the bias corrections)"""
@@ -517,6 +608,8 @@ class SSDVGG:
         from .training_data import default_class_names
         from .ssdutils import match_id
         match_id(match)
+        if self.training and self.get_ema()[2]:
+            raise RuntimeError('weight EMA: save_checkpoint is refused while the average is swapped in (leave averaged_weights() first)')
         names = list(class_names) if class_names is not None else default_class_names(self._n_classes)
         if len(names) != self._n_classes:
             raise ValueError(f'{len(names)} class names for {self._n_classes} classes')
@@ -541,6 +634,10 @@ class SSDVGG:
                          __adam_eps__=np.array(eps, np.float32), __adam_decay__=np.array(decay, np.float32),
                          __adam_step__=np.array(self.adam_step, np.int64))
                 d.update({'__adam_v__/' + k: v for k, v in self.save_second_moment().items()})
+            ema_decay, ema_step, _ = self.get_ema()
+            if ema_decay != 0.0:        # (a run without the average writes the keys it wrote before the option)
+                d.update(__ema_decay__=np.array(ema_decay, np.float32), __ema_step__=np.array(ema_step, np.int64))
+                d.update({'__ema__/' + k: v for k, v in self.save_ema().items()})
         np.savez(path, **d)
 
     # ------------------------------------------------------------------ steps

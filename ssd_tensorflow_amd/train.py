@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Training driver: the counterpart of the reference's train.py loop (train.py:247-343) over
 the HIP library.  Same flags (train.py:55-80) plus --preset / --synthetic-train / --synthetic-valid /
---augment / --decoder / --cache-gb / --dtype / --allreduce-bucket-mb / --allreduce-dtype.  Scalar summaries go to <tensorboard-dir>/<name>/scalars.jsonl
+--augment / --decoder / --cache-gb / --dtype / --ema-decay / --allreduce-bucket-mb / --allreduce-dtype.  Scalar summaries go to <tensorboard-dir>/<name>/scalars.jsonl
 (summaries.py), the annotated image summaries as PNG files; TensorBoard event files are out of scope.
 
     python -m ssd_tensorflow_amd.train --name run1 --epochs 2 --batch-size 8
@@ -187,6 +187,13 @@ def checkpoint_update_rule(path):
         return of(ck)
 
 
+def checkpoint_ema(path):
+    """--ema-decay of a checkpoint's run (a file without __ema_decay__: 0, no average)."""
+    from .ssdvgg import checkpoint_ema as of
+    with np.load(path, allow_pickle=False) as ck:
+        return of(ck)
+
+
 def resolved_weight_decay(weight_decay, optimizer):
     """--weight-decay as the run uses it: the value given, else the reference's 0.0005 under momentum and 0 under adamw, whose
     decay is the decoupled --adam-decay"""
@@ -213,6 +220,7 @@ def main(argv=None):
     parser.add_argument('--adam-beta2', type=float, default=0.999, help='--optimizer adamw: decay rate of the second moment, in [0, 1)')
     parser.add_argument('--adam-eps', type=float, default=1e-8, help='--optimizer adamw: the term added to the root of the second moment, > 0')
     parser.add_argument('--adam-decay', type=float, default=0.01, help='--optimizer adamw: the decoupled weight decay, w -= lr * decay * w on the filters, >= 0')
+    parser.add_argument('--ema-decay', type=float, default=0.0, help='keep an exponential moving average of the weights on the GPU, updated behind every update with min(D, (1 + t) / (10 + t)): 0 = off; D in (0, 1), e.g. 0.999 = on -- validation, its AP and its annotated samples then run on the average and the checkpoints hold both sets (DESIGN.md 37); --continue-training takes the checkpoint\'s')
     parser.add_argument('--continue-training', type=str2bool, default='False', help='continue training from the latest checkpoint')
     parser.add_argument('--num-workers', type=int, default=0, help='number of parallel generators')
     parser.add_argument('--decoder', default='pillow', choices=['pillow', 'gpu'], help='a real --data-dir: pillow = the workers decode the files; gpu = they run the Huffman stage only and the GPU decodes in front of the augmentation kernel')
@@ -300,6 +308,10 @@ def main(argv=None):
         if args.optimizer != 'momentum' and asked != ck_rule:
             say("[i] --optimizer %s disagrees with the checkpoint: continuing with its rule, '%s'" % (args.optimizer, ck_rule[0]))
         args.optimizer, args.adam_beta1, args.adam_beta2, args.adam_eps, args.adam_decay = ck_rule
+        ck_ema = checkpoint_ema(ckpt)
+        if args.ema_decay != 0.0 and float(np.float32(args.ema_decay)) != ck_ema:
+            say("[i] --ema-decay %g disagrees with the checkpoint: continuing with its value, %g" % (args.ema_decay, ck_ema))
+        args.ema_decay = ck_ema
     elif rank == 0:
         try:
             os.makedirs(args.name, exist_ok=True)
@@ -324,6 +336,11 @@ def main(argv=None):
         update_rule_config(args.optimizer, args.adam_beta1, args.adam_beta2, args.adam_eps, args.adam_decay)
     except ValueError as e:
         print('[!] Bad --optimizer:', str(e)); return 1
+    try:
+        from .ssdvgg import ema_decay_config
+        args.ema_decay = ema_decay_config(args.ema_decay)
+    except ValueError as e:
+        print('[!] Bad --ema-decay:', str(e)); return 1
     args.weight_decay = resolved_weight_decay(args.weight_decay, args.optimizer)
     say('[i] Update rule:          ', args.optimizer if args.optimizer == 'momentum' else '%s (beta1 %g, beta2 %g, eps %g)' % (
         args.optimizer, args.adam_beta1, args.adam_beta2, args.adam_eps))
@@ -332,6 +349,7 @@ def main(argv=None):
     say('[i] Loss:                 ', args.loss if args.loss != 'focal' else 'focal (gamma %g, alpha %g)' % (args.focal_gamma, args.focal_alpha))
     say('[i] Localization loss:    ', args.loc_loss if args.loc_loss == 'smooth_l1' else '%s (weight %g)' % (args.loc_loss, args.loc_weight))
     say('[i] Gradient clipping:    ', 'off' if args.clip_norm == 0 else 'norm measured, never clipped' if math.isinf(args.clip_norm) else 'global norm <= %g' % args.clip_norm)
+    say('[i] Weight EMA:           ', 'off' if args.ema_decay == 0 else 'decay %g; validation and its AP run on the average' % args.ema_decay)
     if args.cache_gb < 0 or (args.cache_gb and args.decoder != 'gpu'):
         print('[!] --cache-gb keeps pictures decoded on the GPU: it needs --decoder gpu and a size >= 0'); return 1
     try:
@@ -375,6 +393,11 @@ def main(argv=None):
         if world > 1:
             torch.distributed.broadcast(net.params_flat, 0)
         net.set_stream(torch.cuda.current_stream().cuda_stream)
+        if not ckpt and args.ema_decay != 0.0:
+            # a fresh run's average starts here, one rank or many alike: from the weights every rank holds behind the broadcast, on
+            # the stream the steps will run on (a continued run's came from the file, build_optimizer_from_metagraph)
+            torch.cuda.synchronize()
+            net.set_ema(args.ema_decay)
 
         writer = SummaryWriter(os.path.join(args.tensorboard_dir, os.path.basename(os.path.normpath(args.name)))) if rank == 0 else None
         if args.ap_protocol == 'coco':      # COCO's box AP / AR; the per-class values are AP averaged over 0.50:0.95
@@ -389,12 +412,15 @@ def main(argv=None):
             training_ap_calc = APCalculator(protocol=args.ap_protocol)
             validation_ap_calc = APCalculator(protocol=args.ap_protocol)
         labels = list(td.lname2id.keys())
+        # with a weight EMA the validation epoch runs on the average (averaged_weights below) and its summaries say so; the training
+        # epoch's numbers are collected from the training steps, on the raw weights
+        valid_name = 'validation (averaged)' if net.get_ema()[0] != 0.0 else 'validation'
         training_ap = PrecisionSummary(writer, 'training', labels)
-        validation_ap = PrecisionSummary(writer, 'validation', labels)
+        validation_ap = PrecisionSummary(writer, valid_name, labels)
         training_loss = LossSummary(writer, 'training', td.num_train)
-        validation_loss = LossSummary(writer, 'validation', td.num_valid)
+        validation_loss = LossSummary(writer, valid_name, td.num_valid)
         training_imgs = ImageSummary(writer, 'training', td.label_colors, td.lid2name) if rank == 0 else None      # train.py:248-249
-        validation_imgs = ImageSummary(writer, 'validation', td.label_colors, td.lid2name) if rank == 0 else None
+        validation_imgs = ImageSummary(writer, valid_name, td.label_colors, td.lid2name) if rank == 0 else None
 
         loop = StepLoop(net, sess, td, args.batch_size, args.num_workers, world, rank, bucket, args.allreduce_dtype)
         if net.get_grad_clip() != 0.0:      # every rank holds the same arena: the same norms; rank 0 writes them
@@ -433,7 +459,8 @@ def main(argv=None):
         for e in range(start_epoch, args.epochs):
             td.epoch = e
             loop.run_epoch(td.train_generator, True, training_loss, training_ap_calc, e > 0, training_imgs)
-            loop.run_epoch(td.valid_generator, False, validation_loss, validation_ap_calc, e > 0, validation_imgs)
+            with net.averaged_weights():      # (nothing without --ema-decay)
+                loop.run_epoch(td.valid_generator, False, validation_loss, validation_ap_calc, e > 0, validation_imgs)
             # ---- summaries (train.py:311-331) -----------------------------------------------------
             tl = training_loss.push(e + 1, rank_sum)
             vl = validation_loss.push(e + 1, rank_sum)
@@ -451,7 +478,7 @@ def main(argv=None):
             vAPs = gathered_aps(validation_ap_calc, e > 0); vmAP = APs2mAP(vAPs)      # (coco: the validation's twelve numbers too)
             validation_ap.push(e + 1, vmAP, vAPs)
             if e > 0:
-                say('[i] mAP  {:>2}/{}  training {:.4f}  validation {:.4f}'.format(e + 1, args.epochs, mAP, vmAP))
+                say('[i] mAP  {:>2}/{}  training {:.4f}  {} {:.4f}'.format(e + 1, args.epochs, mAP, valid_name, vmAP))
             if rank == 0:                                                                       # train.py:328-329
                 training_imgs.push(e + 1)
                 validation_imgs.push(e + 1)
