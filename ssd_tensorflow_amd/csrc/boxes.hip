@@ -1544,7 +1544,11 @@ __global__ __launch_bounds__(NMSB_THREADS) void nms_boxes_kernel(int n, int n2, 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int i = tid; i < n2; i += NMSB_THREADS) {
         u64 k = 0ull;        // padding sorts last
-        if (i < n) k = ((u64)(65535 - group[i]) << 48) | ((u64)float_order_bits(conf[i]) << 16) | (u64)(65535 - i);
+        if (i < n) {
+            // -0.0 == +0.0 by value: both take +0.0's bits, so that the input index alone orders them (the earlier box first)
+            const float c = conf[i] == 0.f ? 0.f : conf[i];
+            k = ((u64)(65535 - group[i]) << 48) | ((u64)float_order_bits(c) << 16) | (u64)(65535 - i);
+        }
         keys[i] = k;
         if (i < n) alive[i] = 1;
     }
