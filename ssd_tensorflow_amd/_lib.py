@@ -88,6 +88,9 @@ SIGNATURES = {
     'ssd_detection_output_ws_bytes': (sz, [cstr, i32, i32, i32]),
     'ssd_detection_output_dev': (i32, [cstr, i32, vp, vp, i32, f32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     'ssd_detection_output': (i32, [cstr, i32, i32, vp, i32, f32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    'ssd_detection_output_soft_dev': (i32, [cstr, i32, vp, vp, i32, f32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
+    'ssd_detection_output_soft': (i32, [cstr, i32, i32, vp, i32, f32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    'ssd_soft_nms_boxes': (i32, [i32, i32, vp, vp, vp, vp, vp, p_i32]),
     'ssd_anchors_dev': (i32, [cstr, vp, vp, vp]),
     'ssd_average_precision': (i32, [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, C.c_double, vp, vp]),
     'ssd_average_precision_ex': (i32, [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
@@ -201,6 +204,7 @@ SIGNATURES = {
     'ssd_detect_last': (i32, [handle, i32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     'ssd_detect_last_dev': (i32, [handle, i32, f32, i32, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
     'ssd_detect_last_all_dev': (i32, [handle, i32, f32, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    'ssd_detect_last_all_soft_dev': (i32, [handle, i32, f32, i32, i32, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]),
     'ssd_detect_fetch': (i32, [handle, i32, vp, vp, vp, vp, vp]),
     'ssd_detect_host': (i32, [handle, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), p_i32, p_i32]),
     'ssd_nms_boxes': (i32, [i32, i32, vp, vp, vp, C.c_double, vp, p_i32]),
@@ -212,6 +216,8 @@ SIGNATURES = {
     'ssd_detout_tiles_add_dev': (i32, [cstr, i32, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp, sz, vp]),
     'ssd_detout_tiles_merge_dev': (i32, [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     'ssd_detout_tiles': (i32, [cstr, i32, i32, vp, vp, i32, i32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    'ssd_detout_tiles_merge_soft_dev': (i32, [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
+    'ssd_detout_tiles_soft': (i32, [cstr, i32, i32, vp, vp, i32, i32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
     'ssd_set_overlap': (i32, [handle, i32]),
     'ssd_set_wino_dual': (i32, [handle, i32]),
     'ssd_profile_enable': (i32, [handle, i32]),

@@ -402,6 +402,93 @@ int ssd_detection_output(const char* preset, int num_classes, int device, const 
     API_END
 }
 
+static_assert(sizeof(ssd_nms_params) == sizeof(NmsParams) && SSD_NMS_HARD == NMS_HARD && SSD_NMS_SOFT_LINEAR == NMS_SOFT_LINEAR &&
+                  SSD_NMS_SOFT_GAUSSIAN == NMS_SOFT_GAUSSIAN,
+              "ssd_nms_params is boxes.h's NmsParams");
+
+// the parameters of a *_soft entry point, refused before anything else is looked at
+static NmsParams soft_params(const char* who, const ssd_nms_params* nms) {
+    nms_params_check(who, reinterpret_cast<const NmsParams*>(nms));
+    return *reinterpret_cast<const NmsParams*>(nms);
+}
+
+int ssd_detection_output_soft_dev(const char* preset, int num_classes, const double* anchors_dev, const float* pred_dev, int b,
+                                  float conf_thr, int nms_top_k, int keep_top_k, int out_cap, int* count_dev, float* conf_dev,
+                                  int* cls_dev, int* idx_dev, int* box_dev, void* ws_dev, size_t ws_bytes, const ssd_nms_params* nms,
+                                  void* stream) {
+    API_BEGIN
+    const NmsParams np = soft_params("ssd_detection_output_soft_dev", nms);
+    const Preset& p = get_preset(preset);
+    DetectOut o{count_dev, conf_dev, cls_dev, idx_dev, box_dev};
+    detection_output(p.num_anchors, num_classes, anchors_dev, pred_dev, b, conf_thr, nms_top_k, keep_top_k, out_cap, o, ws_dev,
+                     ws_bytes, (hipStream_t)stream, np);
+    API_END
+}
+
+int ssd_detection_output_soft(const char* preset, int num_classes, int device, const float* pred, int b, float conf_thr,
+                              int nms_top_k, int keep_top_k, int out_cap, int* count, float* conf, int* cls, int* idx, int* box,
+                              const ssd_nms_params* nms) {
+    API_BEGIN
+    const NmsParams np = soft_params("ssd_detection_output_soft", nms);
+    const Preset& p = get_preset(preset);
+    detection_output_check(p.num_anchors, num_classes, b, conf_thr, nms_top_k, keep_top_k, out_cap);
+    SSD_REQUIRE(pred && count && conf && cls && idx && box, "null argument");
+    DeviceGuard dev_guard_(device);
+    const size_t A = p.num_anchors, nv = num_classes + 5, n = (size_t)b * out_cap;
+    const size_t wsb = detection_output_ws_bytes(b, num_classes, nms_top_k);
+    DevBuf anc(A * 4 * sizeof(double)), dpred((size_t)b * A * nv * sizeof(float)), ws(wsb);
+    DevBuf dcount((size_t)b * 4), dconf(n * 4), dcls(n * 4), didx(n * 4), dbox(n * 16);
+    anchors_device(p, anc.as<double>(), nullptr, nullptr);
+    HIP_OK(hipMemcpy(dpred.p, pred, (size_t)b * A * nv * sizeof(float), hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(dconf.p, 0, n * 4));       // rows past an image's count read as zero
+    HIP_OK(hipMemset(dcls.p, 0, n * 4));
+    HIP_OK(hipMemset(didx.p, 0, n * 4));
+    HIP_OK(hipMemset(dbox.p, 0, n * 16));
+    DetectOut o{dcount.as<int>(), dconf.as<float>(), dcls.as<int>(), didx.as<int>(), dbox.as<int>()};
+    detection_output((int)A, num_classes, anc.as<double>(), dpred.as<float>(), b, conf_thr, nms_top_k, keep_top_k, out_cap, o, ws.p, wsb,
+                     nullptr, np);
+    HIP_OK(hipMemcpy(count, dcount.p, (size_t)b * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(conf, dconf.p, n * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(cls, dcls.p, n * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(idx, didx.p, n * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(box, dbox.p, n * 16, hipMemcpyDeviceToHost));
+    API_END
+}
+
+int ssd_soft_nms_boxes(int device, int n, const int* box_abs, const float* conf, const ssd_nms_params* nms, int* order_out,
+                       float* conf_out, int* n_keep) {
+    API_BEGIN
+    const char* who = "ssd_soft_nms_boxes";
+    const NmsParams np = soft_params(who, nms);
+    SSD_REQUIRE(np.kind != NMS_HARD, "%s: nms kind must be 1 (soft, linear) or 2 (soft, gaussian): the hard rule on a list is ssd_nms_boxes", who);
+    SSD_REQUIRE(n >= 0 && n <= 1024, "%s: 0..1024 boxes (got %d)", who, n);
+    SSD_REQUIRE(n_keep != nullptr, "%s: n_keep is null", who);
+    *n_keep = 0;
+    if (n > 0) {
+        SSD_REQUIRE(box_abs && conf && order_out && conf_out, "%s: null argument", who);
+        for (int i = 0; i < n; ++i) {
+            const int* bx = box_abs + (size_t)i * 4;
+            SSD_REQUIRE(bx[0] >= 0 && bx[0] <= bx[1] && bx[1] <= 999 && bx[2] >= 0 && bx[2] <= bx[3] && bx[3] <= 999,
+                        "%s: box %d (%d, %d, %d, %d) is not xmin <= xmax, ymin <= ymax on the 1000 grid", who, i, bx[0], bx[1], bx[2], bx[3]);
+            SSD_REQUIRE(std::isfinite(conf[i]) && !std::signbit(conf[i]), "%s: conf[%d] must be finite and non-negative", who, i);
+        }
+        DeviceGuard dev_guard_(device);
+        DevBuf dbox((size_t)n * 16), dconf((size_t)n * 4), dorder((size_t)n * 4), dout((size_t)n * 4), dkeep(4);
+        HIP_OK(hipMemcpy(dbox.p, box_abs, (size_t)n * 16, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(dconf.p, conf, (size_t)n * 4, hipMemcpyHostToDevice));
+        soft_nms_boxes_device(n, dbox.as<int>(), dconf.as<float>(), np, dorder.as<int>(), dout.as<float>(), dkeep.as<int>(), nullptr);
+        int keep = 0;
+        HIP_OK(hipMemcpy(&keep, dkeep.p, 4, hipMemcpyDeviceToHost));
+        SSD_REQUIRE(keep >= 0 && keep <= n, "%s: the kernel reported %d picks of %d boxes", who, keep, n);
+        if (keep > 0) {
+            HIP_OK(hipMemcpy(order_out, dorder.p, (size_t)keep * 4, hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(conf_out, dout.p, (size_t)keep * 4, hipMemcpyDeviceToHost));
+        }
+        *n_keep = keep;
+    }
+    API_END
+}
+
 int ssd_nms_boxes(int device, int n, const int* box_abs, const float* conf, const int* group, double iou_thr, int* keep_out,
                   int* n_keep) {
     API_BEGIN
@@ -528,11 +615,46 @@ int ssd_detout_tiles_merge_dev(int num_classes, const ssd_tile* tiles, int n_til
     API_END
 }
 
+int ssd_detout_tiles_merge_soft_dev(int num_classes, const ssd_tile* tiles, int n_tiles, int n_images, int nms_top_k, int keep_top_k,
+                                    int out_cap, int* count_out, float* conf_out, int* cls_out, int* idx_out, int* tile_out,
+                                    int* box_out, void* ws_dev, size_t ws_bytes, const ssd_nms_params* nms, void* stream) {
+    API_BEGIN
+    const char* who = "ssd_detout_tiles_merge_soft_dev";
+    const NmsParams np = soft_params(who, nms);
+    detout_tiles_merge(who, num_classes, reinterpret_cast<const MergeTile*>(tiles), n_tiles, n_images, nms_top_k, keep_top_k, out_cap,
+                       count_out, conf_out, cls_out, idx_out, tile_out, box_out, ws_dev, ws_bytes, (hipStream_t)stream, np);
+    API_END
+}
+
+static int detout_tiles_host(const char* who, const NmsParams& np, const char* preset, int num_classes, int device, const float* pred,
+                             const ssd_tile* tiles, int n_tiles, int n_images, float conf_thr, int nms_top_k, int keep_top_k,
+                             int edge_margin, int out_cap, int* count_out, float* conf_out, int* cls_out, int* idx_out, int* tile_out,
+                             int* box_out);
+
+int ssd_detout_tiles_soft(const char* preset, int num_classes, int device, const float* pred, const ssd_tile* tiles, int n_tiles,
+                          int n_images, float conf_thr, int nms_top_k, int keep_top_k, int edge_margin, int out_cap, int* count_out,
+                          float* conf_out, int* cls_out, int* idx_out, int* tile_out, int* box_out, const ssd_nms_params* nms) {
+    API_BEGIN
+    const char* who = "ssd_detout_tiles_soft";
+    const NmsParams np = soft_params(who, nms);
+    return detout_tiles_host(who, np, preset, num_classes, device, pred, tiles, n_tiles, n_images, conf_thr, nms_top_k, keep_top_k,
+                             edge_margin, out_cap, count_out, conf_out, cls_out, idx_out, tile_out, box_out);
+    API_END
+}
+
 int ssd_detout_tiles(const char* preset, int num_classes, int device, const float* pred, const ssd_tile* tiles, int n_tiles,
                      int n_images, float conf_thr, int nms_top_k, int keep_top_k, int edge_margin, int out_cap, int* count_out,
                      float* conf_out, int* cls_out, int* idx_out, int* tile_out, int* box_out) {
+    return detout_tiles_host("ssd_detout_tiles", NmsParams{NMS_HARD, 0.f, 0.f, 0.f}, preset, num_classes, device, pred, tiles, n_tiles,
+                             n_images, conf_thr, nms_top_k, keep_top_k, edge_margin, out_cap, count_out, conf_out, cls_out, idx_out,
+                             tile_out, box_out);
+}
+
+static int detout_tiles_host(const char* who, const NmsParams& np, const char* preset, int num_classes, int device, const float* pred,
+                             const ssd_tile* tiles, int n_tiles, int n_images, float conf_thr, int nms_top_k, int keep_top_k,
+                             int edge_margin, int out_cap, int* count_out, float* conf_out, int* cls_out, int* idx_out, int* tile_out,
+                             int* box_out) {
     API_BEGIN
-    const char* who = "ssd_detout_tiles";
     const Preset& p = get_preset(preset);
     const MergeTile* mt = reinterpret_cast<const MergeTile*>(tiles);
     {      // every limit before anything is allocated
@@ -556,7 +678,7 @@ int ssd_detout_tiles(const char* preset, int num_classes, int device, const floa
     detout_tiles_add(who, (int)A, num_classes, anc.as<double>(), dpred.as<float>(), mt, n_tiles, 0, n_tiles, conf_thr, nms_top_k,
                      edge_margin, ws.p, wsb, nullptr);
     detout_tiles_merge(who, num_classes, mt, n_tiles, n_images, nms_top_k, keep_top_k, out_cap, ocount.as<int>(), oconf.as<float>(),
-                       ocls.as<int>(), oidx.as<int>(), otile.as<int>(), obox.as<int>(), ws.p, wsb, nullptr);
+                       ocls.as<int>(), oidx.as<int>(), otile.as<int>(), obox.as<int>(), ws.p, wsb, nullptr, np);
     HIP_OK(hipMemcpy(count_out, ocount.p, (size_t)n_images * 4, hipMemcpyDeviceToHost));
     if (conf_out) HIP_OK(hipMemcpy(conf_out, oconf.p, nout * 4, hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(cls_out, ocls.p, nout * 4, hipMemcpyDeviceToHost));
@@ -1472,6 +1594,20 @@ int ssd_detect_last_all_dev(ssd_handle h, int b, float conf_thr, int nms_top_k, 
     API_BEGIN_NET(h)
     DetectOut d{};
     n.detect_last_all_dev(b, conf_thr, nms_top_k, keep_top_k, out_cap, &d);
+    if (count_dev) *count_dev = d.count;
+    if (conf_dev) *conf_dev = d.conf;
+    if (cls_dev) *cls_dev = d.cls;
+    if (idx_dev) *idx_dev = d.idx;
+    if (box_dev) *box_dev = d.box;
+    API_END
+}
+
+int ssd_detect_last_all_soft_dev(ssd_handle h, int b, float conf_thr, int nms_top_k, int keep_top_k, int out_cap, int** count_dev,
+                                 float** conf_dev, int** cls_dev, int** idx_dev, int** box_dev, const ssd_nms_params* nms) {
+    API_BEGIN_NET(h)
+    const NmsParams np = soft_params("ssd_detect_last_all_soft_dev", nms);
+    DetectOut d{};
+    n.detect_last_all_dev(b, conf_thr, nms_top_k, keep_top_k, out_cap, &d, np);
     if (count_dev) *count_dev = d.count;
     if (conf_dev) *conf_dev = d.conf;
     if (cls_dev) *cls_dev = d.cls;

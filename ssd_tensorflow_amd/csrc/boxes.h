@@ -72,10 +72,20 @@ void detect(int A, int num_classes, const double* anchors, const float* pred, in
 // contract (inputs are softmax outputs).  pred is not modified.  Asynchronous on s, no host wait, deterministic; every limit
 // (and ws_bytes) is checked before anything is enqueued.
 //   ws bytes = align256(4 b C) + align256(8 b C nms_top_k) + 16 b C nms_top_k
+// `nms` replaces the greedy suppression by Soft-NMS: ssd_nms_params of the public header, whose comment is the
+// contract.  kind = NMS_HARD (the default argument) launches the kernels of the hard rule and reads no other field.
+struct NmsParams { int kind; float iou_thr, sigma, min_score; };
+constexpr int NMS_HARD = 0, NMS_SOFT_LINEAR = 1, NMS_SOFT_GAUSSIAN = 2;
+void nms_params_check(const char* who, const NmsParams* nms);      // kind, iou_thr (linear), sigma (gaussian), min_score: in this order
 size_t detection_output_ws_bytes(int B, int num_classes, int nms_top_k);
 void detection_output_check(int A, int num_classes, int B, float conf_thr, int nms_top_k, int keep_top_k, int out_cap);      // the limits alone
 void detection_output(int A, int num_classes, const double* anchors, const float* pred, int B, float conf_thr, int nms_top_k,
-                      int keep_top_k, int out_cap, const DetectOut& out, void* ws, size_t ws_bytes, hipStream_t s);
+                      int keep_top_k, int out_cap, const DetectOut& out, void* ws, size_t ws_bytes, hipStream_t s,
+                      const NmsParams& nms = NmsParams{NMS_HARD, 0.f, 0.f, 0.f});
+// Soft-NMS alone on one list of n <= 1024 boxes [n][4] i32 on the 1000 grid (device pointers): the picks' input indices and
+// decayed scores in pick order, *n_keep their number.
+void soft_nms_boxes_device(int n, const int* boxes, const float* conf, const NmsParams& nms, int* order_out, float* conf_out, int* n_keep,
+                           hipStream_t s);
 
 // non_maximum_suppression / suppress_overlaps on an arbitrary list: boxes [n][4] i32 (xmin,xmax,ymin,ymax),
 // conf [n], group [n] (0..ngroups-1); keep [n+1]: keep[0] = count, then the selected input indices in output order.
@@ -121,6 +131,6 @@ void detout_tiles_add(const char* who, int A, int num_classes, const double* anc
                       hipStream_t s);
 void detout_tiles_merge(const char* who, int num_classes, const MergeTile* tiles, int n_tiles, int n_images, int nms_top_k, int keep_top_k,
                         int out_cap, int* count_out, float* conf_out, int* cls_out, int* idx_out, int* tile_out, int* box_out, void* ws,
-                        size_t ws_bytes, hipStream_t s);
+                        size_t ws_bytes, hipStream_t s, const NmsParams& nms = NmsParams{NMS_HARD, 0.f, 0.f, 0.f});
 
 }  // namespace ssd

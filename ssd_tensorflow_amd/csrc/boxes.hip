@@ -720,6 +720,116 @@ __device__ __forceinline__ void nms_segment(const int4* nbox, unsigned char* al_
     }
 }
 
+// =================================================================================
+// Soft-NMS: a neighbour's score is decayed, the picks re-ranked after every decay
+// =================================================================================
+// exp(x) for x <= 0 as a fixed sequence of singly rounded fp32 operations (this file is compiled with -ffp-contract=off), so
+// that numpy float32 restates it bit for bit (tests/softnms_ref.py expw): Cody-Waite reduction by ln 2 in two parts, a degree-6
+// polynomial, the scale by an exact power of two.  x < -87 gives 0; the smallest other value, 2^-126 * y, is a normal number.
+__device__ __forceinline__ float soft_expw(float x) {
+    if (x < -87.f) return 0.f;
+    const float n = rintf(__fmul_rn(x, 1.44269504088896341f));
+    const float r = __fsub_rn(__fsub_rn(x, __fmul_rn(n, 0.693359375f)), __fmul_rn(n, -2.12194440e-4f));
+    float p = 1.9875691500e-4f;
+    p = __fadd_rn(__fmul_rn(p, r), 1.3981999507e-3f);
+    p = __fadd_rn(__fmul_rn(p, r), 8.3334519073e-3f);
+    p = __fadd_rn(__fmul_rn(p, r), 4.1665795894e-2f);
+    p = __fadd_rn(__fmul_rn(p, r), 1.6666665459e-1f);
+    p = __fadd_rn(__fmul_rn(p, r), 5.0000001201e-1f);
+    const float y = __fadd_rn(__fadd_rn(__fmul_rn(p, __fmul_rn(r, r)), r), 1.f);
+    return __fmul_rn(y, __uint_as_float((unsigned)((int)n + 127) << 23));
+}
+
+constexpr int SOFT_LINEAR = 1, SOFT_GAUSSIAN = 2;      // ssd_nms_params.kind (0 = hard: nms_segment)
+constexpr int SOFT_MAX = 1024;                         // candidates of one list
+constexpr int SOFT_PER = SOFT_MAX / 64;                // per lane
+
+struct SoftNmsArgs {
+    float iou_thr, sigma, min_score;
+    int max_picks;      // a class gives the image at most keep_top_k rows: the walk stops there
+};
+
+// Soft-NMS of one list of m <= 1024 candidates by one wave, where nms_segment runs for the hard rule.  keys[q] = score bits
+// << 32 | a unique low word that ranks equal scores (any order of q: the rule always takes the largest remaining key), nbox[q]
+// the round-tripped box.  Lane l owns candidates l, l + 64, ...: their keys live in registers (hi = score bits, lo = the low
+// word; 0 / 0 = picked or absent -- a live key is never 0, its anchor field is at least 1 << 8), their boxes are read from LDS
+// for every pivot.  Per pick: the lane's largest key, a 64-bit wave maximum (six __shfl_xor steps), the owner by ballot,
+// the pivot's slot and box made scalar with readfirstlane (see nms_segment about vector loop state), then every remaining
+// score times the weight of its overlap with the pivot.  Scores are non-negative floats, so their bit patterns order as their
+// values and a product that is a denormal stays one (the kernels run with fp32 denormals on).  Picks leave as newkey[i] (the
+// decayed key) and order[i] (the pivot's q), i < the returned count; the keys are strictly descending.  No atomics, no spin,
+// every loop bounded by m, LDS the only memory touched.
+template <int KIND>
+__device__ __forceinline__ int soft_nms_segment(const u64* keys, const int4* nbox, int m, int lane, SoftNmsArgs sp, u64* newkey,
+                                                unsigned short* order) {
+    m = __builtin_amdgcn_readfirstlane(m);
+    const int rows = (m + 63) >> 6;            // uniform: the slots any lane uses
+    unsigned hi[SOFT_PER], lo[SOFT_PER];
+#pragma unroll
+    for (int t = 0; t < SOFT_PER; ++t) {
+        const int q = lane + 64 * t;
+        const u64 key = q < m ? keys[q] : 0ull;
+        hi[t] = (unsigned)(key >> 32);
+        lo[t] = (unsigned)key;
+    }
+    const int limit = __builtin_amdgcn_readfirstlane(min(m, sp.max_picks));
+    int picks = 0;
+    for (; picks < limit; ++picks) {
+        // the lane's largest key and its slot
+        u64 best = 0ull;
+        int bt = 0;
+#pragma unroll
+        for (int t = 0; t < SOFT_PER; ++t) {
+            if (t < rows) {
+                const u64 key = ((u64)hi[t] << 32) | (u64)lo[t];
+                if (key > best) { best = key; bt = t; }
+            }
+        }
+        u64 top = best;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const u64 other = __shfl_xor(top, o, 64);
+            top = other > top ? other : top;
+        }
+        const unsigned top_hi = __builtin_amdgcn_readfirstlane((unsigned)(top >> 32));
+        const unsigned top_lo = __builtin_amdgcn_readfirstlane((unsigned)top);
+        if ((top_hi | top_lo) == 0u) break;                            // nothing remains (cannot happen before `limit`)
+        if (__uint_as_float(top_hi) < sp.min_score) break;             // the rest is below it too
+        const u64 own = __ballot(best == (((u64)top_hi << 32) | (u64)top_lo));      // exactly one lane: keys are unique
+        const int owner = __builtin_ctzll(own);
+        const int pt = __builtin_amdgcn_readlane(bt, owner);
+        const int pq = owner + 64 * pt;
+        if (lane == 0) {
+            newkey[picks] = ((u64)top_hi << 32) | (u64)top_lo;
+            order[picks] = (unsigned short)pq;
+        }
+#pragma unroll
+        for (int t = 0; t < SOFT_PER; ++t)
+            if (t == pt && lane == owner) { hi[t] = 0u; lo[t] = 0u; }
+        const int4 pv = nbox[pq];
+        const int x0 = __builtin_amdgcn_readfirstlane(pv.x), x1 = __builtin_amdgcn_readfirstlane(pv.y);
+        const int y0 = __builtin_amdgcn_readfirstlane(pv.z), y1 = __builtin_amdgcn_readfirstlane(pv.w);
+        const int area_i = (x1 - x0 + 1) * (y1 - y0 + 1);
+#pragma unroll
+        for (int t = 0; t < SOFT_PER; ++t) {
+            if (t < rows) {
+                const int q = min(lane + 64 * t, m - 1);               // (a clamped read; an absent slot's product stays 0)
+                const int4 bj = nbox[q];
+                const int w = max(0, min(x1, bj.y) - max(x0, bj.x) + 1);      // as overlaps45 computes them
+                const int h = max(0, min(y1, bj.w) - max(y0, bj.z) + 1);
+                const int inter = w * h;
+                const int uni = area_i + (bj.y - bj.x + 1) * (bj.w - bj.z + 1) - inter;
+                const float iou = uni > 0 ? __fdiv_rn((float)inter, (float)uni) : 0.f;
+                float wgt;
+                if constexpr (KIND == SOFT_LINEAR) wgt = iou > sp.iou_thr ? __fsub_rn(1.f, iou) : 1.f;
+                else wgt = soft_expw(-__fdiv_rn(__fmul_rn(iou, iou), sp.sigma));
+                hi[t] = __float_as_uint(__fmul_rn(__uint_as_float(hi[t]), wgt));
+            }
+        }
+    }
+    return picks;
+}
+
 constexpr int DET_THREADS = 512;
 constexpr int DET_WAVES = DET_THREADS / 64;
 constexpr int DET_FAST = 1024;           // up to this many candidates the whole image is handled in LDS
@@ -1681,8 +1791,11 @@ struct DetTileArgs {
     int first, edge_margin;
 };
 
-template <int DOUT_THREADS, int PER, bool TILE>
-__device__ __forceinline__ void detout_class_body(DetOutArgs p, DetTileArgs tp) {
+// NMS = SOFT_LINEAR / SOFT_GAUSSIAN (never with TILE): soft_nms_segment in the place of nms_segment; the picks
+// leave in pick order with their decayed keys.
+template <int DOUT_THREADS, int PER, bool TILE, int NMS = 0>
+__device__ __forceinline__ void detout_class_body(DetOutArgs p, DetTileArgs tp, SoftNmsArgs sp = SoftNmsArgs{}) {
+    static_assert(!(TILE && NMS != 0), "the tile stage suppresses nothing");
     constexpr int DOUT_WAVES = DOUT_THREADS / 64;
     __shared__ __attribute__((aligned(16))) u64 skey[DOUT_MAX_K];
     __shared__ int4 sbox[DOUT_MAX_K], snbox[DOUT_MAX_K];
@@ -1788,6 +1901,23 @@ __device__ __forceinline__ void detout_class_body(DetOutArgs p, DetTileArgs tp) 
         }
     }
     __syncthreads();
+    if constexpr (NMS != 0) {
+        __shared__ __attribute__((aligned(16))) u64 newkey[DOUT_MAX_K];
+        __shared__ unsigned short order[DOUT_MAX_K];
+        if (wave == 0) {
+            const int picks = soft_nms_segment<NMS>(skey, snbox, m, lane, sp, newkey, order);
+            if (lane == 0) s_red[0] = picks;
+        }
+        __syncthreads();
+        const int picks = s_red[0];
+        const size_t slot = (size_t)blockIdx.x * k;
+        for (int i = tid; i < picks; i += DOUT_THREADS) {
+            p.cls_keys[slot + i] = newkey[i];
+            p.cls_box[slot + i] = sbox[order[i]];
+        }
+        if (tid == 0) p.cls_count[blockIdx.x] = picks;
+        return;
+    }
     if constexpr (!TILE) {
         if (wave == 0) nms_segment(snbox, alive, 0, m, lane);
         __syncthreads();
@@ -1827,6 +1957,11 @@ __device__ __forceinline__ void detout_class_body(DetOutArgs p, DetTileArgs tp) 
 template <int DOUT_THREADS, int PER>
 __global__ __launch_bounds__(DOUT_THREADS) void detout_class_kernel(DetOutArgs p) {
     detout_class_body<DOUT_THREADS, PER, false>(p, DetTileArgs{});
+}
+
+template <int DOUT_THREADS, int PER, int NMS>
+__global__ __launch_bounds__(DOUT_THREADS) void detout_class_soft_kernel(DetOutArgs p, SoftNmsArgs sp) {
+    detout_class_body<DOUT_THREADS, PER, false, NMS>(p, DetTileArgs{}, sp);
 }
 
 template <int DOUT_THREADS, int PER>
@@ -1927,7 +2062,10 @@ struct DetTileMergeArgs {
     int* pcount; u64* pkeys; int4* pbox;                        // [n_images][C] and [n_images][C][k]
 };
 
-__global__ __launch_bounds__(MRG_THREADS) void detout_tile_class_kernel(DetTileMergeArgs p) {
+// NMS = SOFT_LINEAR / SOFT_GAUSSIAN: soft_nms_segment in the place of nms_segment.  The kernel itself is the
+// template (NMS = 0 never reads sp): behind a wrapper the compiler schedules the hard instantiation differently.
+template <int NMS>
+__global__ __launch_bounds__(MRG_THREADS) void detout_tile_class_kernel(DetTileMergeArgs p, SoftNmsArgs sp) {
     __shared__ __attribute__((aligned(16))) u64 lkeys[DOUT_MAX_K];
     __shared__ unsigned lvals[DOUT_MAX_K];
     __shared__ int4 sbox[DOUT_MAX_K], snbox[DOUT_MAX_K];
@@ -2003,6 +2141,23 @@ __global__ __launch_bounds__(MRG_THREADS) void detout_tile_class_kernel(DetTileM
         alive[q] = 1;
     }
     __syncthreads();
+    if constexpr (NMS != 0) {      //  the picks in pick order, their keys decayed
+        __shared__ __attribute__((aligned(16))) u64 newkey[DOUT_MAX_K];
+        __shared__ unsigned short order[DOUT_MAX_K];
+        if (wave == 0) {
+            const int picks = soft_nms_segment<NMS>(lkeys, snbox, total, lane, sp, newkey, order);
+            if (lane == 0) s_red[0] = picks;
+        }
+        __syncthreads();
+        const int picks = s_red[0];
+        const size_t slot = (size_t)blockIdx.x * k;
+        for (int i = tid; i < picks; i += MRG_THREADS) {
+            p.pkeys[slot + i] = newkey[i];
+            p.pbox[slot + i] = sbox[order[i]];
+        }
+        if (tid == 0) p.pcount[blockIdx.x] = picks;
+        return;
+    }
     if (wave == 0) nms_segment(snbox, alive, 0, total, lane);
     __syncthreads();
     const size_t slot = (size_t)blockIdx.x * k;
@@ -2030,6 +2185,42 @@ __global__ __launch_bounds__(MRG_THREADS) void detout_tile_class_kernel(DetTileM
     if (tid == 0) p.pcount[blockIdx.x] = kept;
 }
 
+// The rule alone on one list (ssd_soft_nms_boxes): boxes [n] on the 1000 grid, conf [n] non-negative; the key's anchor field
+// is the input index.  One workgroup; order_out / conf_out [n] receive the picks, *n_keep their number.
+constexpr int SOFTB_THREADS = 256;
+
+template <int NMS>
+__global__ __launch_bounds__(SOFTB_THREADS) void soft_nms_boxes_kernel(int n, const int4* __restrict__ boxes, const float* __restrict__ conf,
+                                                                       SoftNmsArgs sp, int* __restrict__ order_out,
+                                                                       float* __restrict__ conf_out, int* __restrict__ n_keep) {
+    __shared__ __attribute__((aligned(16))) u64 skey[SOFT_MAX], newkey[SOFT_MAX];
+    __shared__ int4 snbox[SOFT_MAX];
+    __shared__ unsigned short order[SOFT_MAX];
+    __shared__ int s_picks;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    n = min(n, SOFT_MAX);
+    for (int q = tid; q < n; q += SOFTB_THREADS) {
+        const int4 bx = boxes[q];
+        int o[4] = {bx.x, bx.y, bx.z, bx.w}, nb[4];
+        nms_roundtrip(o, nb);
+        snbox[q] = make_int4(nb[0], nb[1], nb[2], nb[3]);
+        skey[q] = ((u64)__float_as_uint(conf[q]) << 32) | ((u64)(32767 - q) << 8) | 127ull;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        const int picks = soft_nms_segment<NMS>(skey, snbox, n, lane, sp, newkey, order);
+        if (lane == 0) s_picks = picks;
+    }
+    __syncthreads();
+    const int picks = s_picks;
+    for (int i = tid; i < picks; i += SOFTB_THREADS) {
+        order_out[i] = (int)order[i];
+        conf_out[i] = __uint_as_float((unsigned)(newkey[i] >> 32));
+    }
+    if (tid == 0) *n_keep = picks;
+}
+
 static size_t align256(size_t n) { return (n + 255) / 256 * 256; }
 
 void detection_output_check(int A, int num_classes, int B, float conf_thr, int nms_top_k, int keep_top_k, int out_cap) {
@@ -2042,13 +2233,31 @@ void detection_output_check(int A, int num_classes, int B, float conf_thr, int n
     SSD_REQUIRE(out_cap >= 1, "detection_output: out_cap must be >= 1");
 }
 
+void nms_params_check(const char* who, const NmsParams* nms) {
+    SSD_REQUIRE(nms != nullptr, "%s: the nms parameters are null", who);
+    SSD_REQUIRE(nms->kind == NMS_HARD || nms->kind == NMS_SOFT_LINEAR || nms->kind == NMS_SOFT_GAUSSIAN,
+                "%s: nms kind must be 0 (hard), 1 (soft, linear) or 2 (soft, gaussian) (got %d)", who, nms->kind);
+    if (nms->kind == NMS_HARD) return;      // the other fields are not read
+    if (nms->kind == NMS_SOFT_LINEAR)
+        SSD_REQUIRE(std::isfinite(nms->iou_thr) && nms->iou_thr >= 0.f && nms->iou_thr <= 1.f, "%s: soft nms iou_thr must be finite and in [0, 1]",
+                    who);
+    if (nms->kind == NMS_SOFT_GAUSSIAN)
+        SSD_REQUIRE(std::isfinite(nms->sigma) && nms->sigma > 0.f, "%s: soft nms sigma must be finite and > 0", who);
+    SSD_REQUIRE(std::isfinite(nms->min_score) && nms->min_score >= 0.f, "%s: soft nms min_score must be finite and >= 0", who);
+}
+
+static SoftNmsArgs soft_args(const NmsParams& nms, int max_picks) {
+    return SoftNmsArgs{nms.iou_thr, nms.sigma, nms.min_score + 0.f, max_picks};      // (+ 0.f: a -0.0 min_score compares like +0.0 anyway)
+}
+
 size_t detection_output_ws_bytes(int B, int num_classes, int nms_top_k) {
     const size_t lists = (size_t)B * num_classes;
     return align256(lists * 4) + align256(lists * nms_top_k * 8) + lists * nms_top_k * 16;
 }
 
 void detection_output(int A, int num_classes, const double* anchors, const float* pred, int B, float conf_thr, int nms_top_k,
-                      int keep_top_k, int out_cap, const DetectOut& out, void* ws, size_t ws_bytes, hipStream_t s) {
+                      int keep_top_k, int out_cap, const DetectOut& out, void* ws, size_t ws_bytes, hipStream_t s, const NmsParams& nms) {
+    nms_params_check("detection_output", &nms);
     detection_output_check(A, num_classes, B, conf_thr, nms_top_k, keep_top_k, out_cap);
     SSD_REQUIRE(anchors && pred && ws && out.count && out.conf && out.cls && out.idx && out.box, "detection_output: null argument");
     const size_t need = detection_output_ws_bytes(B, num_classes, nms_top_k);
@@ -2062,9 +2271,18 @@ void detection_output(int A, int num_classes, const double* anchors, const float
     a.cls_keys = (u64*)base; base += align256(lists * nms_top_k * 8);
     a.cls_box = (int4*)base;
     {
-        ProfScope prof("detout_class", 0.0, (double)B * A * a.nv * 4.0, s);
+        ProfScope prof(nms.kind == NMS_HARD ? "detout_class" : "detout_class_soft", 0.0, (double)B * A * a.nv * 4.0, s);
         const dim3 grid((unsigned)lists);
-        if (A <= 256 * 35) hipLaunchKernelGGL((detout_class_kernel<256, 35>), grid, dim3(256), 0, s, a);            // vgg300: 8732
+        const SoftNmsArgs sp = soft_args(nms, keep_top_k);
+        if (nms.kind == NMS_SOFT_LINEAR) {
+            if (A <= 256 * 35) hipLaunchKernelGGL((detout_class_soft_kernel<256, 35, SOFT_LINEAR>), grid, dim3(256), 0, s, a, sp);
+            else if (A <= 512 * 48) hipLaunchKernelGGL((detout_class_soft_kernel<512, 48, SOFT_LINEAR>), grid, dim3(512), 0, s, a, sp);
+            else hipLaunchKernelGGL((detout_class_soft_kernel<512, 64, SOFT_LINEAR>), grid, dim3(512), 0, s, a, sp);
+        } else if (nms.kind == NMS_SOFT_GAUSSIAN) {
+            if (A <= 256 * 35) hipLaunchKernelGGL((detout_class_soft_kernel<256, 35, SOFT_GAUSSIAN>), grid, dim3(256), 0, s, a, sp);
+            else if (A <= 512 * 48) hipLaunchKernelGGL((detout_class_soft_kernel<512, 48, SOFT_GAUSSIAN>), grid, dim3(512), 0, s, a, sp);
+            else hipLaunchKernelGGL((detout_class_soft_kernel<512, 64, SOFT_GAUSSIAN>), grid, dim3(512), 0, s, a, sp);
+        } else if (A <= 256 * 35) hipLaunchKernelGGL((detout_class_kernel<256, 35>), grid, dim3(256), 0, s, a);     // vgg300: 8732
         else if (A <= 512 * 48) hipLaunchKernelGGL((detout_class_kernel<512, 48>), grid, dim3(512), 0, s, a);       // vgg512: 24564
         else hipLaunchKernelGGL((detout_class_kernel<512, 64>), grid, dim3(512), 0, s, a);
     }
@@ -2203,7 +2421,8 @@ void detout_tiles_add(const char* who, int A, int num_classes, const double* anc
 
 void detout_tiles_merge(const char* who, int num_classes, const MergeTile* tiles, int n_tiles, int n_images, int nms_top_k, int keep_top_k,
                         int out_cap, int* count_out, float* conf_out, int* cls_out, int* idx_out, int* tile_out, int* box_out, void* ws,
-                        size_t ws_bytes, hipStream_t s) {
+                        size_t ws_bytes, hipStream_t s, const NmsParams& nms) {
+    nms_params_check(who, &nms);
     std::vector<int> head;
     detout_tiles_merge_check(who, num_classes, tiles, n_tiles, n_images, nms_top_k, keep_top_k, out_cap, head);
     SSD_REQUIRE(count_out && cls_out && box_out, "%s: null argument", who);
@@ -2214,8 +2433,12 @@ void detout_tiles_merge(const char* who, int num_classes, const MergeTile* tiles
     m.img_first = w.img_first; m.C = num_classes; m.k = nms_top_k;
     m.tcount = w.tcount; m.tkeys = w.tkeys; m.tbox = w.tbox; m.pcount = w.pcount; m.pkeys = w.pkeys; m.pbox = w.pbox;
     {
-        ProfScope prof("detout_tile_class", 0.0, 0.0, s);
-        hipLaunchKernelGGL(detout_tile_class_kernel, dim3((unsigned)((size_t)n_images * num_classes)), dim3(MRG_THREADS), 0, s, m);
+        ProfScope prof(nms.kind == NMS_HARD ? "detout_tile_class" : "detout_tile_class_soft", 0.0, 0.0, s);
+        const dim3 grid((unsigned)((size_t)n_images * num_classes));
+        const SoftNmsArgs sp = soft_args(nms, keep_top_k);
+        if (nms.kind == NMS_SOFT_LINEAR) hipLaunchKernelGGL(detout_tile_class_kernel<SOFT_LINEAR>, grid, dim3(MRG_THREADS), 0, s, m, sp);
+        else if (nms.kind == NMS_SOFT_GAUSSIAN) hipLaunchKernelGGL(detout_tile_class_kernel<SOFT_GAUSSIAN>, grid, dim3(MRG_THREADS), 0, s, m, sp);
+        else hipLaunchKernelGGL(detout_tile_class_kernel<0>, grid, dim3(MRG_THREADS), 0, s, m, sp);
     }
     DetOutArgs a{};
     a.C = num_classes; a.B = n_images; a.nms_top_k = nms_top_k; a.keep_top_k = keep_top_k; a.out_cap = out_cap;
@@ -2225,6 +2448,20 @@ void detout_tiles_merge(const char* who, int num_classes, const MergeTile* tiles
         ProfScope prof("detout_tile_picture", 0.0, 0.0, s);
         hipLaunchKernelGGL(detout_tile_picture_kernel, dim3(n_images), dim3(MRG_THREADS), 0, s, a, tile_out);
     }
+    HIP_OK(hipGetLastError());
+}
+
+// one list through soft_nms_segment; every pointer in device memory, n in 1..1024, nms.kind soft (checked by the caller)
+void soft_nms_boxes_device(int n, const int* boxes, const float* conf, const NmsParams& nms, int* order_out, float* conf_out, int* n_keep,
+                           hipStream_t s) {
+    SSD_REQUIRE(n >= 1 && n <= SOFT_MAX, "soft_nms_boxes: 1..%d boxes (got %d)", SOFT_MAX, n);
+    SSD_REQUIRE(nms.kind == NMS_SOFT_LINEAR || nms.kind == NMS_SOFT_GAUSSIAN, "soft_nms_boxes: a soft nms kind (got %d)", nms.kind);
+    const SoftNmsArgs sp = soft_args(nms, n);
+    const int4* b4 = reinterpret_cast<const int4*>(boxes);
+    if (nms.kind == NMS_SOFT_LINEAR)
+        hipLaunchKernelGGL(soft_nms_boxes_kernel<SOFT_LINEAR>, dim3(1), dim3(SOFTB_THREADS), 0, s, n, b4, conf, sp, order_out, conf_out, n_keep);
+    else
+        hipLaunchKernelGGL(soft_nms_boxes_kernel<SOFT_GAUSSIAN>, dim3(1), dim3(SOFTB_THREADS), 0, s, n, b4, conf, sp, order_out, conf_out, n_keep);
     HIP_OK(hipGetLastError());
 }
 

@@ -179,7 +179,8 @@ public:
     // asynchronous form: the kernels enqueued; dev_out (optional) = the device's view of the slot's arrays
     const DetectSlot& detect_last_dev(int b, float thr, int cap, int max_out, int out_cap, bool nms, DetectOut* dev_out);
     // the DetectionOutput pass (boxes.h detection_output) on the last result, into the same two alternating slots
-    const DetectSlot& detect_last_all_dev(int b, float thr, int nms_top_k, int keep_top_k, int out_cap, DetectOut* dev_out);
+    const DetectSlot& detect_last_all_dev(int b, float thr, int nms_top_k, int keep_top_k, int out_cap, DetectOut* dev_out,
+                                          const NmsParams& nms = NmsParams{NMS_HARD, 0.f, 0.f, 0.f});
     // host copy of the latest (which = 0) or the previous (which = 1) pass; waits for that slot's pass only
     void detect_fetch(int which, int* count, float* conf, int* cls, int* idx, int* box);
     // the pinned host memory of that slot itself (valid until the second-next pass); waits for the slot's pass only

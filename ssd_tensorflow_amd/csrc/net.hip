@@ -2164,7 +2164,9 @@ const DetectSlot& Net::detect_last_dev(int b, float thr, int cap, int max_out, i
     return sl;
 }
 
-const DetectSlot& Net::detect_last_all_dev(int b, float thr, int nms_top_k, int keep_top_k, int out_cap, DetectOut* dev_out) {
+const DetectSlot& Net::detect_last_all_dev(int b, float thr, int nms_top_k, int keep_top_k, int out_cap, DetectOut* dev_out,
+                                           const NmsParams& nms) {
+    nms_params_check("detect_last_all", &nms);
     SSD_REQUIRE(b >= 1 && b <= Bmax_, "batch %d outside 1..%d", b, Bmax_);
     const int A = preset_->num_anchors;
     detection_output_check(A, C_, b, thr, nms_top_k, keep_top_k, out_cap);      // before a slot is taken
@@ -2181,7 +2183,8 @@ const DetectSlot& Net::detect_last_all_dev(int b, float thr, int nms_top_k, int 
     prof_.layer = "detect";
     DetectOut d;
     detect_slot_carve(sl, d, sl.dev);
-    detection_output(A, C_, anchors_dev_, result_, b, thr, nms_top_k, keep_top_k, out_cap, d, detout_ws_, detout_ws_bytes_, stream_);
+    detection_output(A, C_, anchors_dev_, result_, b, thr, nms_top_k, keep_top_k, out_cap, d, detout_ws_, detout_ws_bytes_, stream_,
+                     nms);
     HIP_OK(hipEventRecord(sl.ready, stream_));
     if (dev_out) *dev_out = d;
     return sl;

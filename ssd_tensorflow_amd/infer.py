@@ -157,10 +157,30 @@ def add_decode_arguments(parser):
                              'the best --keep-top-k of the image are kept, in confidence order')
     parser.add_argument('--nms-top-k', type=int, default=400, help='--decode all: candidates per class that enter NMS (1..1024)')
     parser.add_argument('--keep-top-k', type=int, default=200, help='--decode all: detections kept per image (1..1024)')
+    parser.add_argument('--soft-nms', default='off', choices=['off', 'linear', 'gaussian'],
+                        help='--decode all (with --tile: --tile-decode all): Soft-NMS in the place of the NMS per class. A box that overlaps a '
+                             'better one of its class keeps a lower confidence instead of being deleted: linear: times 1 - IoU above '
+                             '--soft-nms-iou; gaussian: times exp(-IoU^2 / --soft-nms-sigma). The picks are re-ranked after every decay and '
+                             'end below --soft-nms-min-score; the reported confidence is the decayed one (DESIGN.md 38)')
+    parser.add_argument('--soft-nms-iou', type=float, default=0.45, help='--soft-nms linear: overlaps above it decay the score (0..1)')
+    parser.add_argument('--soft-nms-sigma', type=float, default=0.5, help='--soft-nms gaussian: the width of the decay (> 0)')
+    parser.add_argument('--soft-nms-min-score', type=float, default=None,
+                        help='--soft-nms: a candidate whose decayed score falls below it is dropped (default: --threshold)')
 
 
 def check_decode_arguments(parser, args):
     """--decode all with --tile is an argument error: the tile merge takes one record per anchor"""
+    if args.soft_nms != 'off':
+        if args.tile and args.tile_decode != 'all':
+            parser.error('--soft-nms %s needs --tile-decode all with --tile: the argmax decode of the windows keeps the hard rule' % args.soft_nms)
+        if not args.tile and args.decode != 'all':
+            parser.error('--soft-nms %s needs --decode all: the argmax decode keeps the hard rule' % args.soft_nms)
+        if not 0.0 <= args.soft_nms_iou <= 1.0:
+            parser.error('--soft-nms-iou must be in 0..1')
+        if not (args.soft_nms_sigma > 0.0 and args.soft_nms_sigma < float('inf')):
+            parser.error('--soft-nms-sigma must be finite and > 0')
+        if args.soft_nms_min_score is not None and not 0.0 <= args.soft_nms_min_score < float('inf'):
+            parser.error('--soft-nms-min-score must be finite and >= 0')
     if args.decode == 'all' and args.tile:
         parser.error('--decode all does not apply to --tile: the tile merge takes one record per anchor (use --decode argmax)')
     for name in ('nms_top_k', 'keep_top_k'):
@@ -171,8 +191,26 @@ def check_decode_arguments(parser, args):
 def decode_keywords(args):
     """the decode keywords of SSDVGG.detect_last_launch for these arguments"""
     if args.decode == 'all':
-        return dict(decode='all', nms_top_k=args.nms_top_k, keep_top_k=args.keep_top_k)
+        return dict(decode='all', nms_top_k=args.nms_top_k, keep_top_k=args.keep_top_k, **soft_nms_keywords(args))
     return {}
+
+
+def soft_nms_keywords(args):
+    """the four soft_nms keywords of the decode entry points for --soft-nms and its companions"""
+    if getattr(args, 'soft_nms', 'off') == 'off':
+        return {}
+    return dict(soft_nms=args.soft_nms, soft_nms_iou=args.soft_nms_iou, soft_nms_sigma=args.soft_nms_sigma,
+                soft_nms_min_score=args.soft_nms_min_score)
+
+
+def nms_rule_text(args):
+    """what the banner's decode line adds for the suppression rule (nothing for the hard rule: the line stays as it was)"""
+    if getattr(args, 'soft_nms', 'off') == 'off':
+        return ''
+    min_score = 'the threshold' if args.soft_nms_min_score is None else '%g' % args.soft_nms_min_score
+    if args.soft_nms == 'linear':
+        return ', soft nms linear, iou %g, min score %s' % (args.soft_nms_iou, min_score)
+    return ', soft nms gaussian, sigma %g, min score %s' % (args.soft_nms_sigma, min_score)
 
 
 def resolve_class_names(num_classes, source_names=None, stored=None):
@@ -290,9 +328,10 @@ def main(argv=None):
     print('[i] Pascal summary:    ', args.pascal_summary)
     print('[i] Annotate:          ', args.annotate)
     if args.tile_decode != 'argmax':
-        print('[i] Tile decode:       ', '%s (nms top k %d, keep top k %d)' % (args.tile_decode, args.nms_top_k, args.keep_top_k))
+        print('[i] Tile decode:       ', '%s (nms top k %d, keep top k %d%s)' % (args.tile_decode, args.nms_top_k, args.keep_top_k,
+                                                                                   nms_rule_text(args)))
     if args.decode != 'argmax':
-        print('[i] Decode:            ', '%s (nms top k %d, keep top k %d)' % (args.decode, args.nms_top_k, args.keep_top_k))
+        print('[i] Decode:            ', '%s (nms top k %d, keep top k %d%s)' % (args.decode, args.nms_top_k, args.keep_top_k, nms_rule_text(args)))
 
     # ---- checkpoint lookup (infer.py:111-126) --------------------------------------------------
     ckpt = None

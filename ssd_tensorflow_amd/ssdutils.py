@@ -174,11 +174,53 @@ def check_tile_decode(decode, tile_cap=200, max_out=200):
     return decode
 
 
-def detection_output_tiles(pred, preset, tiles, thr, nms_top_k=400, keep_top_k=200, edge_margin=2, out_cap=None):
+SOFT_NMS_KINDS = {'linear': 1, 'gaussian': 2}      # ssd_nms_params.kind (0 = hard)
+
+
+class NmsParams(C.Structure):
+    """ssd_nms_params of the C header"""
+    _fields_ = [('kind', C.c_int), ('iou_thr', C.c_float), ('sigma', C.c_float), ('min_score', C.c_float)]
+
+
+def soft_nms_params(soft_nms, soft_nms_iou=0.45, soft_nms_sigma=0.5, soft_nms_min_score=None, thr=0.0):
+    """The four soft_nms keywords of the decode entry points -> NmsParams, or None for soft_nms=None (the hard rule: the caller
+    then goes through the entry point it went through before there was a choice).  soft_nms_min_score None = the call's
+    confidence threshold.  The values are refused by the library, which names the field."""
+    if soft_nms is None:
+        return None
+    if soft_nms not in SOFT_NMS_KINDS:
+        raise ValueError("soft_nms must be None, 'linear' or 'gaussian' (got %r)" % (soft_nms,))
+    min_score = thr if soft_nms_min_score is None else soft_nms_min_score
+    return NmsParams(SOFT_NMS_KINDS[soft_nms], float(soft_nms_iou), float(soft_nms_sigma), float(min_score))
+
+
+def soft_nms_boxes(conf, box_abs, kind='linear', iou=0.45, sigma=0.5, min_score=0.0):
+    """ssd_soft_nms_boxes: Soft-NMS alone on one list of n <= 1024 boxes [n, 4] = (xmin, xmax, ymin, ymax) on the 1000 grid with
+    confidences conf [n] >= 0.  Returns (order, conf): the input indices in pick order and their decayed scores."""
+    conf = np.ascontiguousarray(conf, np.float32).reshape(-1)
+    box = np.ascontiguousarray(box_abs, np.int32).reshape(-1, 4)
+    if box.shape[0] != conf.shape[0]:
+        raise ValueError('one box per confidence')
+    nms = soft_nms_params(kind, iou, sigma, min_score)
+    if nms is None:
+        raise ValueError("kind must be 'linear' or 'gaussian'")
+    n = conf.shape[0]
+    order = np.zeros(max(n, 1), np.int32)
+    out = np.zeros(max(n, 1), np.float32)
+    nk = C.c_int(0)
+    check(lib.ssd_soft_nms_boxes(_lib.device(), n, np_ptr(box), np_ptr(conf), C.cast(C.pointer(nms), C.c_void_p), np_ptr(order),
+                                 np_ptr(out), C.byref(nk)))
+    return order[:nk.value].copy(), out[:nk.value].copy()
+
+
+def detection_output_tiles(pred, preset, tiles, thr, nms_top_k=400, keep_top_k=200, edge_margin=2, out_cap=None, soft_nms=None,
+                           soft_nms_iou=0.45, soft_nms_sigma=0.5, soft_nms_min_score=None):
     """ssd_detout_tiles on host predictions: pred [n_tiles, A, C+5], tiles = [(image, Tile, (W, H))] with the images
     ascending from 0.  Every (anchor, class) pair of every tile is a candidate; per class one NMS over the picture's tiles, the
     best keep_top_k of the picture.  Returns one dict per picture (conf, cls, idx, tile, box) in global confidence order (ties:
-    lower tile, lower anchor, lower class)."""
+    lower tile, lower anchor, lower class).  soft_nms = 'linear' | 'gaussian': Soft-NMS in the place of that NMS
+    (ssd_detout_tiles_soft); conf is then the decayed score."""
+    nms = soft_nms_params(soft_nms, soft_nms_iou, soft_nms_sigma, soft_nms_min_score, thr)
     from .tiling import tile_structs
     pred = np.ascontiguousarray(pred, np.float32)
     if pred.ndim != 3 or pred.shape[0] != len(tiles):
@@ -195,9 +237,13 @@ def detection_output_tiles(pred, preset, tiles, thr, nms_top_k=400, keep_top_k=2
     oconf = np.zeros((g, n), np.float32)
     ocls, oidx, otile = (np.zeros((g, n), np.int32) for _ in range(3))
     obox = np.zeros((g, n, 4), np.int32)
-    check(lib.ssd_detout_tiles(_pname(p), nv - 5, _lib.device(), np_ptr(pred), C.cast(tile_structs(tiles), C.c_void_p), n_tiles, n_images,
-                               float(thr), int(nms_top_k), keep_top_k, int(edge_margin), out_cap, np_ptr(ocount), np_ptr(oconf),
-                               np_ptr(ocls), np_ptr(oidx), np_ptr(otile), np_ptr(obox)))
+    args = (_pname(p), nv - 5, _lib.device(), np_ptr(pred), C.cast(tile_structs(tiles), C.c_void_p), n_tiles, n_images, float(thr),
+            int(nms_top_k), keep_top_k, int(edge_margin), out_cap, np_ptr(ocount), np_ptr(oconf), np_ptr(ocls), np_ptr(oidx),
+            np_ptr(otile), np_ptr(obox))
+    if nms is None:
+        check(lib.ssd_detout_tiles(*args))
+    else:
+        check(lib.ssd_detout_tiles_soft(*args, C.cast(C.pointer(nms), C.c_void_p)))
     out = []
     for i in range(n_images):
         m = min(int(ocount[i]), out_cap)
@@ -205,15 +251,19 @@ def detection_output_tiles(pred, preset, tiles, thr, nms_top_k=400, keep_top_k=2
     return out
 
 
-def detect_tiles(pred, preset, tiles, thr, tile_cap=200, max_out=200, edge_margin=2, decode='argmax', nms_top_k=400, keep_top_k=200):
+def detect_tiles(pred, preset, tiles, thr, tile_cap=200, max_out=200, edge_margin=2, decode='argmax', nms_top_k=400, keep_top_k=200,
+                 soft_nms=None, soft_nms_iou=0.45, soft_nms_sigma=0.5, soft_nms_min_score=None):
     """Tiled detection on host predictions: pred [n_tiles, A, C+5], one row of anchors per tile; tiles = [(image, Tile, (W, H))]
     (tiling.plan_tiles), the images ascending from 0.  Every tile is decoded (decode_boxes, the first tile_cap records), the
     records of a picture are merged on the GPU (ssd_merge_tiles: edge drop, the picture's 1000 grid, one NMS over all tiles).
     The mirror of detect_batch; returns one dict per picture: conf, cls, idx, tile, box.
     decode='all': every class of an anchor is a candidate (detection_output_tiles with nms_top_k / keep_top_k; tile_cap and
-    max_out do not apply)."""
+    max_out do not apply).  soft_nms belongs to decode='all' (DESIGN.md 38)."""
     if check_tile_decode(decode, tile_cap, max_out) == 'all':
-        return detection_output_tiles(pred, preset, tiles, thr, nms_top_k, keep_top_k, edge_margin)
+        return detection_output_tiles(pred, preset, tiles, thr, nms_top_k, keep_top_k, edge_margin, None, soft_nms, soft_nms_iou,
+                                      soft_nms_sigma, soft_nms_min_score)
+    if soft_nms is not None:
+        raise ValueError("soft_nms needs decode='all': the argmax decode keeps the hard rule")
     pred = np.ascontiguousarray(pred, np.float32)
     if pred.ndim != 3 or pred.shape[0] != len(tiles):
         raise ValueError('pred must be [n_tiles, A, C+5] with one entry per tile')
@@ -232,11 +282,16 @@ def detect_tiles(pred, preset, tiles, thr, tile_cap=200, max_out=200, edge_margi
     return merge_tile_lists(tiles, count, conf, cls, idx, box, tile_cap, max_out, edge_margin)
 
 
-def detection_output_batch(pred, preset, confidence_threshold=0.01, nms_top_k=400, keep_top_k=200, out_cap=None):
+def detection_output_batch(pred, preset, confidence_threshold=0.01, nms_top_k=400, keep_top_k=200, out_cap=None, soft_nms=None,
+                           soft_nms_iou=0.45, soft_nms_sigma=0.5, soft_nms_min_score=None):
     """The SSD paper's DetectionOutput for pred [b, A, C+5] on the GPU (ssd_detection_output): every (anchor,
     class) pair that reaches the threshold is a candidate, the best nms_top_k per class, NMS per class, the best keep_top_k
     of the image.  Returns what detect_batch returns, in global confidence order (ties: lower anchor, then lower class); an
-    anchor may appear under several classes."""
+    anchor may appear under several classes.  soft_nms = 'linear' | 'gaussian' (DESIGN.md 38): Soft-NMS in the place of the
+    NMS (ssd_detection_output_soft) -- a neighbour's score decays by 1 - iou above soft_nms_iou, or by exp(-iou^2 /
+    soft_nms_sigma); picks are re-ranked after every decay and end below soft_nms_min_score (None: the confidence threshold);
+    conf is the decayed score."""
+    nms = soft_nms_params(soft_nms, soft_nms_iou, soft_nms_sigma, soft_nms_min_score, confidence_threshold)
     pred = np.ascontiguousarray(pred, np.float32)
     if pred.ndim == 2:
         pred = pred[None]
@@ -252,8 +307,12 @@ def detection_output_batch(pred, preset, confidence_threshold=0.01, nms_top_k=40
     cls = np.zeros((b, n), np.int32)
     idx = np.zeros((b, n), np.int32)
     box = np.zeros((b, n, 4), np.int32)
-    check(lib.ssd_detection_output(_pname(p), nv - 5, _lib.device(), np_ptr(pred), b, float(confidence_threshold), int(nms_top_k),
-                                   keep_top_k, out_cap, np_ptr(count), np_ptr(conf), np_ptr(cls), np_ptr(idx), np_ptr(box)))
+    args = (_pname(p), nv - 5, _lib.device(), np_ptr(pred), b, float(confidence_threshold), int(nms_top_k), keep_top_k, out_cap,
+            np_ptr(count), np_ptr(conf), np_ptr(cls), np_ptr(idx), np_ptr(box))
+    if nms is None:
+        check(lib.ssd_detection_output(*args))
+    else:
+        check(lib.ssd_detection_output_soft(*args, C.cast(C.pointer(nms), C.c_void_p)))
     out = []
     for i in range(b):
         m = min(int(count[i]), out_cap)
@@ -261,17 +320,19 @@ def detection_output_batch(pred, preset, confidence_threshold=0.01, nms_top_k=40
     return out
 
 
-def detection_output(pred, anchors_or_preset, confidence_threshold=0.01, lid2name={}, nms_top_k=400, keep_top_k=200):
+def detection_output(pred, anchors_or_preset, confidence_threshold=0.01, lid2name={}, nms_top_k=400, keep_top_k=200, soft_nms=None,
+                     soft_nms_iou=0.45, soft_nms_sigma=0.5, soft_nms_min_score=None):
     """DetectionOutput for one image: the list of (confidence, Box) that decode_boxes + suppress_overlaps return, decoded the
     way the SSD paper does (every class of an anchor, not its argmax class alone).  `anchors_or_preset`: a preset, its name, or
-    the anchor list (only its length is used)."""
+    the anchor list (only its length is used).  soft_nms: see detection_output_batch."""
     if isinstance(anchors_or_preset, str):
         p = get_preset_by_name(anchors_or_preset)
     elif isinstance(anchors_or_preset, SSDPreset):
         p = anchors_or_preset
     else:
         p = _preset_for(len(anchors_or_preset))
-    det = detection_output_batch(np.asarray(pred, np.float32), p, confidence_threshold, nms_top_k, keep_top_k)[0]
+    det = detection_output_batch(np.asarray(pred, np.float32), p, confidence_threshold, nms_top_k, keep_top_k, None, soft_nms,
+                                 soft_nms_iou, soft_nms_sigma, soft_nms_min_score)[0]
     return boxes_from_detection(det, lid2name)
 
 

@@ -907,21 +907,31 @@ class SSDVGG:
         return cap, mo, out_cap
 
     def detect_last_launch(self, b, confidence_threshold=0.5, detections_cap=200, max_out=None, nms=True, decode='argmax',
-                           nms_top_k=400, keep_top_k=200):
+                           nms_top_k=400, keep_top_k=200, soft_nms=None, soft_nms_iou=0.45, soft_nms_sigma=0.5, soft_nms_min_score=None):
         """Enqueue decode + NMS of the last step's result and the copy of its (small) output; returns a
         ticket whose get() yields what detect_last returns.  Two output slots alternate in the handle, so a
         caller may launch the next batch before it collects this one (infer.py:225-235, pipelined).
         decode='argmax': the reference's decode_boxes + suppress_overlaps (one candidate per anchor).  decode='all': the SSD
         paper's DetectionOutput (ssd_detect_last_all_dev) -- every class of an anchor is a candidate, the best
         nms_top_k per class, NMS per class, the best keep_top_k of the image in global confidence order; detections_cap,
-        max_out and nms do not apply and must be left at their defaults."""
+        max_out and nms do not apply and must be left at their defaults.  soft_nms = 'linear' | 'gaussian' (decode='all' only,
+        DESIGN.md 38): Soft-NMS in the place of the NMS per class (ssd_detect_last_all_soft_dev; ssdutils.detection_output_batch
+        describes the keywords); the boolean `nms` keeps its meaning for the argmax decode."""
+        from .ssdutils import soft_nms_params
+        soft = soft_nms_params(soft_nms, soft_nms_iou, soft_nms_sigma, soft_nms_min_score, confidence_threshold)
+        if soft is not None and decode != 'all':
+            raise ValueError("soft_nms needs decode='all': the argmax decode keeps the hard rule")
         count_dev = C.c_void_p(); conf_dev = C.c_void_p(); cls_dev = C.c_void_p(); box_dev = C.c_void_p()
         if decode == 'all':
             if detections_cap != 200 or max_out is not None or nms is not True:
                 raise ValueError("decode='all' takes nms_top_k and keep_top_k; detections_cap, max_out and nms do not apply")
             out_cap = max(int(keep_top_k), 1)
-            check(lib.ssd_detect_last_all_dev(self._h, b, float(confidence_threshold), int(nms_top_k), int(keep_top_k), out_cap,
-                                              C.byref(count_dev), C.byref(conf_dev), C.byref(cls_dev), None, C.byref(box_dev)))
+            args = (self._h, b, float(confidence_threshold), int(nms_top_k), int(keep_top_k), out_cap, C.byref(count_dev),
+                    C.byref(conf_dev), C.byref(cls_dev), None, C.byref(box_dev))
+            if soft is None:
+                check(lib.ssd_detect_last_all_dev(*args))
+            else:
+                check(lib.ssd_detect_last_all_soft_dev(*args, C.cast(C.pointer(soft), C.c_void_p)))
         elif decode == 'argmax':
             cap, mo, out_cap = self._det_caps(detections_cap, max_out)
             check(lib.ssd_detect_last_dev(self._h, b, float(confidence_threshold), cap, mo, out_cap, 1 if nms else 0,
@@ -964,12 +974,13 @@ class SSDVGG:
         return _Annotated(host, done, offs, shapes, dst if keep_device else None, stream if keep_device else None)
 
     def detect_last(self, b, confidence_threshold=0.5, detections_cap=200, max_out=None, nms=True, decode='argmax', nms_top_k=400,
-                    keep_top_k=200):
+                    keep_top_k=200, soft_nms=None, soft_nms_iou=0.45, soft_nms_sigma=0.5, soft_nms_min_score=None):
         """decode + NMS of the last step's result without leaving the GPU (train.py:275-277); decode='all': see
         detect_last_launch."""
         # (copies: a caller of this synchronous form may keep the result across any number of later passes)
         return [{k: v.copy() for k, v in d.items()}
-                for d in self.detect_last_launch(b, confidence_threshold, detections_cap, max_out, nms, decode, nms_top_k, keep_top_k).get()]
+                for d in self.detect_last_launch(b, confidence_threshold, detections_cap, max_out, nms, decode, nms_top_k, keep_top_k,
+                                                 soft_nms, soft_nms_iou, soft_nms_sigma, soft_nms_min_score).get()]
 
     # ------------------------------------------------------------------ Session.run routing
     def _run(self, fetches, feed):

@@ -121,11 +121,16 @@ class TiledDetector:
     collects these.
     decode='all' (DESIGN.md 28): every class of an anchor is a candidate.  ssd_detout_tiles_add_dev follows every infer_dev and one
     ssd_detout_tiles_merge_dev ends the pass: the same ticket and output sets, out_cap = keep_top_k, the detections in global
-    confidence order.  tile_cap and max_out belong to 'argmax': other values than their defaults raise."""
+    confidence order.  tile_cap and max_out belong to 'argmax': other values than their defaults raise.
+    soft_nms = 'linear' | 'gaussian' (decode='all' only): the merge's NMS per class becomes Soft-NMS
+    (ssd_detout_tiles_merge_soft_dev); soft_nms_min_score None = threshold."""
 
     def __init__(self, net, tile, overlap=0.25, whole=True, edge_margin=2, threshold=0.5, tile_cap=200, max_out=200, decode='argmax',
-                 nms_top_k=400, keep_top_k=200):
-        from .ssdutils import check_tile_decode
+                 nms_top_k=400, keep_top_k=200, soft_nms=None, soft_nms_iou=0.45, soft_nms_sigma=0.5, soft_nms_min_score=None):
+        from .ssdutils import check_tile_decode, soft_nms_params
+        self.soft = soft_nms_params(soft_nms, soft_nms_iou, soft_nms_sigma, soft_nms_min_score, threshold)
+        if self.soft is not None and decode != 'all':
+            raise ValueError("soft_nms needs decode='all': the argmax decode keeps the hard rule")
         plan_tiles(tile, tile, tile, overlap, whole)         # (validates tile and overlap)
         self.decode = check_tile_decode(decode, tile_cap, max_out)
         self.nms_top_k, self.keep_top_k = int(nms_top_k), int(keep_top_k)
@@ -255,10 +260,13 @@ class TiledDetector:
                                              L['idx'][k:].data_ptr(), L['box'][k:].data_ptr(), self._det_ws.data_ptr(), ptr or None))
                 k += b
             if self.decode == 'all':
-                check(lib.ssd_detout_tiles_merge_dev(nfg, structs, n_tiles, n_images, self.nms_top_k, self.keep_top_k, out_cap,
-                                                     d['count'].data_ptr(), d['conf'].data_ptr(), d['cls'].data_ptr(), d['idx'].data_ptr(),
-                                                     d['tile'].data_ptr(), d['box'].data_ptr(), self._all_ws.data_ptr(),
-                                                     self._all_ws.numel(), ptr or None))
+                args = (nfg, structs, n_tiles, n_images, self.nms_top_k, self.keep_top_k, out_cap, d['count'].data_ptr(),
+                        d['conf'].data_ptr(), d['cls'].data_ptr(), d['idx'].data_ptr(), d['tile'].data_ptr(), d['box'].data_ptr(),
+                        self._all_ws.data_ptr(), self._all_ws.numel())
+                if self.soft is None:
+                    check(lib.ssd_detout_tiles_merge_dev(*args, ptr or None))
+                else:
+                    check(lib.ssd_detout_tiles_merge_soft_dev(*args, C.cast(C.pointer(self.soft), C.c_void_p), ptr or None))
             else:
                 check(lib.ssd_merge_tiles_dev(structs, n_tiles, n_images, cap, L['count'].data_ptr(),
                                               L['conf'].data_ptr(), L['cls'].data_ptr(), L['idx'].data_ptr(), L['box'].data_ptr(),
@@ -336,7 +344,8 @@ def check_arguments(parser, args):
 def decode_keywords(args):
     """the decode keywords of TiledDetector for these arguments"""
     if args.tile_decode == 'all':
-        return dict(decode='all', nms_top_k=args.nms_top_k, keep_top_k=args.keep_top_k)
+        from .infer import soft_nms_keywords
+        return dict(decode='all', nms_top_k=args.nms_top_k, keep_top_k=args.keep_top_k, **soft_nms_keywords(args))
     return {}
 
 
