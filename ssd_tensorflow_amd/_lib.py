@@ -110,6 +110,8 @@ SIGNATURES = {
     'ssd_arena_floats': (sz, [cstr, i32]),
     'ssd_augment_ws_bytes': (sz, [i32, i32, i32]),
     'ssd_augment_batch_dev': (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+    'ssd_augment_cells_ws_bytes': (sz, [i32, i32, i32]),
+    'ssd_augment_cells_dev': (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     'ssd_annotate_rect': (i32, [vp, i32, i32, vp]),
     'ssd_annotate_glyph': (i32, [i32, vp]),
     'ssd_annotate_style_create': (i32, [i32, i32, vp, vp, C.POINTER(vp)]),

@@ -1079,6 +1079,16 @@ int ssd_augment_batch_dev(const unsigned char* images_dev, const ssd_augment_par
     API_END
 }
 
+size_t ssd_augment_cells_ws_bytes(int n_cells, int out_w, int out_h) { return augment_cells_ws_bytes(n_cells, out_w, out_h); }
+
+int ssd_augment_cells_dev(const unsigned char* images_dev, const ssd_augment_params* params, const ssd_augment_cell* cells, int n_cells, int b,
+                          int out_w, int out_h, float* out_dev, void* ws_dev, void* stream) {
+    API_BEGIN
+    SSD_REQUIRE(images_dev && params && cells && out_dev && ws_dev, "null argument");
+    augment_cells(images_dev, params, cells, n_cells, b, out_w, out_h, out_dev, ws_dev, (hipStream_t)stream);
+    API_END
+}
+
 // ---------------------------------------------------------------------------------- drawing
 struct ssd_annotate_style_s {
     ssd::AnnotateStyle* style;

@@ -15,6 +15,8 @@
 // HBM-bound: 3 x 4 bytes written per output pixel, a few source bytes read per tap through L2.
 // Compiled with -ffp-contract=off: the HSV round trip and the truncations to uint8 are not FMA-safe.
 #include "augment.h"
+#include <algorithm>
+#include <vector>
 
 namespace ssd {
 
@@ -114,17 +116,10 @@ __device__ static int axis_taps(int src, int dst, int alg, int d, int* idx, floa
     return T;
 }
 
-__global__ __launch_bounds__(256) void augment_taps_kernel(const ssd_augment_params* __restrict__ prm, int b, int out_w, int out_h, TapTable t) {
-    const int per = out_w + out_h;
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= b * per) return;
-    const int img = gid / per, r = gid - img * per;
-    const int axis = r >= out_w;                 // 0: x, 1: y
-    const int d = axis ? r - out_w : r;
-    const int dst = axis ? out_h : out_w;
-    const ssd_augment_params& p = prm[img];
+// the taps of destination coordinate d of one axis of picture `img` (a sample of ssd_augment_batch_dev, a cell of
+// ssd_augment_cells_dev): `dst` is the side of the rectangle the picture is resized to
+__device__ __forceinline__ void augment_taps_one(const ssd_augment_params& p, int img, int axis, int d, int dst, int pitch, const TapTable& t) {
     const int src = axis ? p.crop_h : p.crop_w;
-    const int pitch = out_w > out_h ? out_w : out_h;
     const size_t plane = (size_t)(img * 2 + axis);
     int li[AUG_TMAX];
     float lw[AUG_TMAX];
@@ -134,6 +129,31 @@ __global__ __launch_bounds__(256) void augment_taps_kernel(const ssd_augment_par
         t.idx[(plane * AUG_TMAX + i) * pitch + d] = li[i];
         t.w[(plane * AUG_TMAX + i) * pitch + d] = lw[i];
     }
+}
+
+__global__ __launch_bounds__(256) void augment_taps_kernel(const ssd_augment_params* __restrict__ prm, int b, int out_w, int out_h, TapTable t) {
+    const int per = out_w + out_h;
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= b * per) return;
+    const int img = gid / per, r = gid - img * per;
+    const int axis = r >= out_w;                 // 0: x, 1: y
+    const int d = axis ? r - out_w : r;
+    const int dst = axis ? out_h : out_w;
+    const int pitch = out_w > out_h ? out_w : out_h;
+    augment_taps_one(prm[img], img, axis, d, dst, pitch, t);
+}
+
+// ssd_augment_cells_dev: one grid row per cell over the w + h coordinates of the cell's own two axes (the table keeps the sample's
+// pitch: a cell is never larger than its sample)
+__global__ __launch_bounds__(256) void augment_taps_cells_kernel(const ssd_augment_params* __restrict__ prm, const ssd_augment_cell* __restrict__ cells,
+                                                                 int out_w, int out_h, TapTable t) {
+    const int ci = blockIdx.y;
+    const int cw = cells[ci].w, ch = cells[ci].h;
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= cw + ch) return;
+    const int axis = r >= cw;
+    const int pitch = out_w > out_h ? out_w : out_h;
+    augment_taps_one(prm[ci], ci, axis, axis ? r - cw : r, axis ? ch : cw, pitch, t);
 }
 
 // ---- photometric chain on one uint8 BGR pixel (oracle/augment.py brightness / contrast / hue / saturation) ----
@@ -269,11 +289,20 @@ __global__ __launch_bounds__(256) void augment_photometric_kernel(const unsigned
 // the NX indices and weights in registers and issues the NX pixel loads of a row back to back from clamped addresses -- visibility
 // and the canvas colour are selected afterwards -- before the NX * 3 FMAs in the order the oracle prescribes.  Same sums bit for bit
 // (tests/test_gpu_augment.py).  An image whose photometric chain runs per tap (larger than the pre-pass buffer) keeps the loop form.
+// Where a picture's result lands in `out`: the whole sample (ssd_augment_batch_dev) or one cell of it (ssd_augment_cells_dev).  Everything
+// the parameter struct calls "output" is local to this rectangle: (ox, oy) count its pixels, the taps are those of its sides.
+struct AugDst {
+    int w;             // width of the rectangle: out_flip mirrors inside it
+    int pitch;         // of the tap table
+    int stride;        // pixels per row of `out` (the sample's width)
+    size_t base;       // pixel index of the rectangle's (0, 0) in `out`
+};
+
 template <int NX>
 __device__ __forceinline__ void augment_gather_body(const unsigned char* __restrict__ images, const ssd_augment_params& p, int img, int ox, int oy,
-                                                    int out_w, int out_h, const TapTable& t, const unsigned char* __restrict__ pre,
+                                                    const AugDst& dst, const TapTable& t, const unsigned char* __restrict__ pre,
                                                     float* __restrict__ out) {
-    const int pitch = out_w > out_h ? out_w : out_h;
+    const int pitch = dst.pitch;
     const size_t px_ = (size_t)(img * 2 + 0), py_ = (size_t)(img * 2 + 1);
     const int nx = t.n[px_ * pitch + ox], ny = t.n[py_ * pitch + oy];
     const int* xi = t.idx + px_ * AUG_TMAX * pitch + ox;       // tap i at xi[i * pitch]
@@ -375,9 +404,34 @@ __device__ __forceinline__ void augment_gather_body(const unsigned char* __restr
     }
     // steps behind ResizeTransform act on the resized array (its rows 0 / 1), a flip behind it mirrors the output columns
     for (int i = 0; i < p.n_post; ++i) photometric_step(p.post_kind[i], p.post_val[i], oy, res);
-    const size_t gid = ((size_t)img * out_h + oy) * out_w + (p.out_flip ? out_w - 1 - ox : ox);
+    const size_t gid = dst.base + (size_t)oy * dst.stride + (p.out_flip ? dst.w - 1 - ox : ox);
     float* o = out + gid * 3;
     for (int c = 0; c < 3; ++c) o[c] = res[c];
+}
+
+// the instantiation of a picture's pixel: picture `img` of the tap table and the pre-pass buffer, pixel (ox, oy) of its rectangle
+__device__ __forceinline__ void augment_gather_pixel(const unsigned char* __restrict__ images, const ssd_augment_params& p, int img, int ox, int oy,
+                                                     const AugDst& dst, const TapTable& t, const unsigned char* __restrict__ pre,
+                                                     float* __restrict__ out) {
+    // the widest column tap count of the image: uniform per workgroup (nearest 1, linear / enlarging area 2, cubic 4, Lanczos 8,
+    // shrinking area up to 16)
+    int nxmax;
+    const double sx = (double)p.crop_w / (double)dst.w;
+    if (p.resize_alg == ALG_NEAREST) nxmax = 1;
+    else if (p.resize_alg == ALG_LINEAR || (p.resize_alg == ALG_AREA && sx < 1.0)) nxmax = 2;
+    else if (p.resize_alg == ALG_CUBIC) nxmax = 4;
+    else if (p.resize_alg == ALG_LANCZOS4) nxmax = 8;
+    else nxmax = AUG_TMAX;
+    if (p.resize_alg == ALG_AREA && sx >= 1.0) nxmax = sx <= 2.0 ? 4 : (sx <= 6.0 ? 8 : 16);      // at most floor(scale) + 2 taps
+    const bool per_tap = aug_has_photometric(p) && !aug_uses_pre(p);
+    const int nx = t.n[(size_t)(img * 2) * dst.pitch + ox];
+    // (shrinking by more than 6x -- 16 taps, 2000-pixel sources -- keeps the loop form: its 16 doubles of weights would set the
+    // register allocation, and with it the resident waves, of every other case)
+    if (per_tap || nxmax > 8 || nx > nxmax) augment_gather_body<0>(images, p, img, ox, oy, dst, t, pre, out);
+    else if (nxmax == 1) augment_gather_body<1>(images, p, img, ox, oy, dst, t, pre, out);
+    else if (nxmax == 2) augment_gather_body<2>(images, p, img, ox, oy, dst, t, pre, out);
+    else if (nxmax == 4) augment_gather_body<4>(images, p, img, ox, oy, dst, t, pre, out);
+    else augment_gather_body<8>(images, p, img, ox, oy, dst, t, pre, out);
 }
 
 __global__ __launch_bounds__(256) void augment_gather_kernel(const unsigned char* __restrict__ images, const ssd_augment_params* __restrict__ prm,
@@ -387,27 +441,26 @@ __global__ __launch_bounds__(256) void augment_gather_kernel(const unsigned char
     const int pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= out_w * out_h) return;
     const int ox = pix % out_w, oy = pix / out_w;
-    const ssd_augment_params& p = prm[img];
-    // the widest column tap count of the image: uniform per workgroup (nearest 1, linear / enlarging area 2, cubic 4, Lanczos 8,
-    // shrinking area up to 16)
-    int nxmax;
-    const double sx = (double)p.crop_w / (double)out_w;
-    if (p.resize_alg == ALG_NEAREST) nxmax = 1;
-    else if (p.resize_alg == ALG_LINEAR || (p.resize_alg == ALG_AREA && sx < 1.0)) nxmax = 2;
-    else if (p.resize_alg == ALG_CUBIC) nxmax = 4;
-    else if (p.resize_alg == ALG_LANCZOS4) nxmax = 8;
-    else nxmax = AUG_TMAX;
-    if (p.resize_alg == ALG_AREA && sx >= 1.0) nxmax = sx <= 2.0 ? 4 : (sx <= 6.0 ? 8 : 16);      // at most floor(scale) + 2 taps
-    const bool per_tap = aug_has_photometric(p) && !aug_uses_pre(p);
-    const int pitch = out_w > out_h ? out_w : out_h;
-    const int nx = t.n[(size_t)(img * 2) * pitch + ox];
-    // (shrinking by more than 6x -- 16 taps, 2000-pixel sources -- keeps the loop form: its 16 doubles of weights would set the
-    // register allocation, and with it the resident waves, of every other case)
-    if (per_tap || nxmax > 8 || nx > nxmax) augment_gather_body<0>(images, p, img, ox, oy, out_w, out_h, t, pre, out);
-    else if (nxmax == 1) augment_gather_body<1>(images, p, img, ox, oy, out_w, out_h, t, pre, out);
-    else if (nxmax == 2) augment_gather_body<2>(images, p, img, ox, oy, out_w, out_h, t, pre, out);
-    else if (nxmax == 4) augment_gather_body<4>(images, p, img, ox, oy, out_w, out_h, t, pre, out);
-    else augment_gather_body<8>(images, p, img, ox, oy, out_w, out_h, t, pre, out);
+    const AugDst dst = {out_w, out_w > out_h ? out_w : out_h, out_w, (size_t)img * out_h * out_w};
+    augment_gather_pixel(images, prm[img], img, ox, oy, dst, t, pre, out);
+}
+
+// ssd_augment_cells_dev: one grid row per cell (blockIdx.y), a workgroup = 256 consecutive pixels of the CELL.  The grid is as wide as
+// the largest cell needs: the workgroups past a smaller one leave.  The cell, and with it the parameter struct and the instantiation,
+// is a function of blockIdx alone, so the dispatch stays a scalar branch as in the kernel above; what differs per lane is the output
+// index, computed from the cell's rectangle (the 64 consecutive cell pixels of a wave wrap cell rows wherever the cell's width is no
+// multiple of 64, and a row of the cell is `stride` pixels from the next in the sample).
+__global__ __launch_bounds__(256) void augment_gather_cells_kernel(const unsigned char* __restrict__ images, const ssd_augment_params* __restrict__ prm,
+                                                                   const ssd_augment_cell* __restrict__ cells, int out_w, int out_h, TapTable t,
+                                                                   const unsigned char* __restrict__ pre, float* __restrict__ out) {
+    const int ci = blockIdx.y;
+    const int cw = cells[ci].w, npix = cw * cells[ci].h;
+    if ((int)(blockIdx.x * blockDim.x) >= npix) return;
+    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= npix) return;
+    const int ox = pix % cw, oy = pix / cw;
+    const AugDst dst = {cw, out_w > out_h ? out_w : out_h, out_w, ((size_t)cells[ci].sample * out_h + cells[ci].y0) * out_w + cells[ci].x0};
+    augment_gather_pixel(images, prm[ci], ci, ox, oy, dst, t, pre, out);
 }
 
 size_t augment_ws_bytes(int b, int out_w, int out_h) {
@@ -416,58 +469,149 @@ size_t augment_ws_bytes(int b, int out_w, int out_h) {
            (size_t)b * AUG_PRE_BYTES;
 }
 
-void augment_batch(const unsigned char* images_dev, const ssd_augment_params* params_host, int b, int out_w, int out_h, float* out_dev,
-                   void* ws, hipStream_t s) {
-    SSD_REQUIRE(b >= 1 && out_w >= 1 && out_h >= 1, "augment: empty batch");
-    for (int i = 0; i < b; ++i) {
-        const ssd_augment_params& p = params_host[i];
-        SSD_REQUIRE(p.src_w >= 1 && p.src_h >= 1 && p.crop_w >= 1 && p.crop_h >= 1, "augment: image %d has an empty source or crop window", i);
-        SSD_REQUIRE(p.resize_alg >= 0 && p.resize_alg <= 4, "augment: image %d: unknown resize algorithm %d", i, p.resize_alg);
-        SSD_REQUIRE(p.n_distort >= 0 && p.n_distort <= 3, "augment: image %d: distort chain length %d", i, p.n_distort);
-        SSD_REQUIRE(p.n_extra >= 0 && p.n_extra <= 16, "augment: image %d: %d extra photometric steps", i, p.n_extra);
-        SSD_REQUIRE(p.n_post >= 0 && p.n_post <= 4, "augment: image %d: %d steps behind the resize", i, p.n_post);
-        for (int k = 0; k < p.n_post; ++k) SSD_REQUIRE(p.post_kind[k] >= 0 && p.post_kind[k] <= 4, "augment: image %d: post step kind %d", i, p.post_kind[k]);
-        SSD_REQUIRE(p.fill_from >= 0 && p.fill_from <= p.n_extra, "augment: image %d: fill_from %d of %d extra steps", i, p.fill_from, p.n_extra);
-        SSD_REQUIRE(p.clip_x0 >= 0 && p.clip_y0 >= 0 && p.clip_x1 <= p.src_w && p.clip_y1 <= p.src_h && p.clip_x0 <= p.clip_x1 && p.clip_y0 <= p.clip_y1,
-                    "augment: image %d: visible window %d..%d x %d..%d outside the %d x %d image", i, p.clip_x0, p.clip_x1, p.clip_y0, p.clip_y1, p.src_w, p.src_h);
-        for (int k = 0; k < p.n_extra; ++k) SSD_REQUIRE(p.extra_kind[k] >= 0 && p.extra_kind[k] <= 4, "augment: image %d: extra step kind %d", i, p.extra_kind[k]);
-        for (int c = 0; c < 3; ++c) SSD_REQUIRE(p.reorder[c] >= 0 && p.reorder[c] <= 2, "augment: image %d: channel permutation", i);
-        const double sx = (double)p.crop_w / out_w, sy = (double)p.crop_h / out_h;
-        SSD_REQUIRE(p.resize_alg != ALG_AREA || (sx <= AUG_TMAX - 2 && sy <= AUG_TMAX - 2), "augment: image %d shrinks by more than %dx (INTER_AREA tap table)",
-                    i, AUG_TMAX - 2);
-        const int fw = p.expand_on ? p.exp_w : p.src_w, fh = p.expand_on ? p.exp_h : p.src_h;
-        SSD_REQUIRE(p.crop_x0 >= 0 && p.crop_y0 >= 0 && p.crop_x0 + p.crop_w <= fw && p.crop_y0 + p.crop_h <= fh, "augment: image %d: crop window outside the frame", i);
-    }
-    const size_t rows = (size_t)b * 2 * (out_w > out_h ? out_w : out_h);
-    char* base = static_cast<char*>(ws);
+// the checks of one parameter struct whose result is out_w x out_h (a sample, or a cell of one)
+static void augment_check_params(const ssd_augment_params& p, int i, int out_w, int out_h) {
+    SSD_REQUIRE(p.src_w >= 1 && p.src_h >= 1 && p.crop_w >= 1 && p.crop_h >= 1, "augment: image %d has an empty source or crop window", i);
+    SSD_REQUIRE(p.resize_alg >= 0 && p.resize_alg <= 4, "augment: image %d: unknown resize algorithm %d", i, p.resize_alg);
+    SSD_REQUIRE(p.n_distort >= 0 && p.n_distort <= 3, "augment: image %d: distort chain length %d", i, p.n_distort);
+    SSD_REQUIRE(p.n_extra >= 0 && p.n_extra <= 16, "augment: image %d: %d extra photometric steps", i, p.n_extra);
+    SSD_REQUIRE(p.n_post >= 0 && p.n_post <= 4, "augment: image %d: %d steps behind the resize", i, p.n_post);
+    for (int k = 0; k < p.n_post; ++k) SSD_REQUIRE(p.post_kind[k] >= 0 && p.post_kind[k] <= 4, "augment: image %d: post step kind %d", i, p.post_kind[k]);
+    SSD_REQUIRE(p.fill_from >= 0 && p.fill_from <= p.n_extra, "augment: image %d: fill_from %d of %d extra steps", i, p.fill_from, p.n_extra);
+    SSD_REQUIRE(p.clip_x0 >= 0 && p.clip_y0 >= 0 && p.clip_x1 <= p.src_w && p.clip_y1 <= p.src_h && p.clip_x0 <= p.clip_x1 && p.clip_y0 <= p.clip_y1,
+                "augment: image %d: visible window %d..%d x %d..%d outside the %d x %d image", i, p.clip_x0, p.clip_x1, p.clip_y0, p.clip_y1, p.src_w, p.src_h);
+    for (int k = 0; k < p.n_extra; ++k) SSD_REQUIRE(p.extra_kind[k] >= 0 && p.extra_kind[k] <= 4, "augment: image %d: extra step kind %d", i, p.extra_kind[k]);
+    for (int c = 0; c < 3; ++c) SSD_REQUIRE(p.reorder[c] >= 0 && p.reorder[c] <= 2, "augment: image %d: channel permutation", i);
+    const double sx = (double)p.crop_w / out_w, sy = (double)p.crop_h / out_h;
+    SSD_REQUIRE(p.resize_alg != ALG_AREA || (sx <= AUG_TMAX - 2 && sy <= AUG_TMAX - 2), "augment: image %d shrinks by more than %dx (INTER_AREA tap table)",
+                i, AUG_TMAX - 2);
+    const int fw = p.expand_on ? p.exp_w : p.src_w, fh = p.expand_on ? p.exp_h : p.src_h;
+    SSD_REQUIRE(p.crop_x0 >= 0 && p.crop_y0 >= 0 && p.crop_x0 + p.crop_w <= fw && p.crop_y0 + p.crop_h <= fh, "augment: image %d: crop window outside the frame", i);
+}
+
+// the workspace of n pictures: tap table, the parameter structs, the pre-pass buffers
+struct AugWs {
     TapTable t;
-    t.idx = reinterpret_cast<int*>(base);
-    t.w = reinterpret_cast<float*>(base + rows * AUG_TMAX * sizeof(int));
-    t.n = reinterpret_cast<int*>(base + rows * AUG_TMAX * (sizeof(int) + sizeof(float)));
+    ssd_augment_params* prm;
+    unsigned char* pre;
+};
+static AugWs augment_carve(void* ws, int n, int out_w, int out_h) {
+    const size_t rows = (size_t)n * 2 * (out_w > out_h ? out_w : out_h);
+    char* base = static_cast<char*>(ws);
+    AugWs a;
+    a.t.idx = reinterpret_cast<int*>(base);
+    a.t.w = reinterpret_cast<float*>(base + rows * AUG_TMAX * sizeof(int));
+    a.t.n = reinterpret_cast<int*>(base + rows * AUG_TMAX * (sizeof(int) + sizeof(float)));
     const size_t prm_off = ((rows * AUG_TMAX * 8 + rows * 4 + 255) / 256) * 256;
-    ssd_augment_params* prm = reinterpret_cast<ssd_augment_params*>(base + prm_off);
-    unsigned char* pre = reinterpret_cast<unsigned char*>(base + prm_off + ((size_t)b * sizeof(ssd_augment_params) + 255) / 256 * 256);
-    HIP_OK(hipMemcpyAsync(prm, params_host, (size_t)b * sizeof(ssd_augment_params), hipMemcpyHostToDevice, s));
+    a.prm = reinterpret_cast<ssd_augment_params*>(base + prm_off);
+    a.pre = reinterpret_cast<unsigned char*>(base + prm_off + ((size_t)n * sizeof(ssd_augment_params) + 255) / 256 * 256);
+    return a;
+}
+
+// pass 0 over n pictures (samples or cells alike: it works in the SOURCE frame)
+static void augment_launch_photometric(const unsigned char* images_dev, const ssd_augment_params* params_host, int n, const AugWs& a, hipStream_t s) {
     int pre_pixels = 0;      // the largest image pass 0 has to transform (0: no image needs it)
-    for (int i = 0; i < b; ++i) {
+    for (int i = 0; i < n; ++i) {
         const ssd_augment_params& p = params_host[i];
         const size_t bytes = (size_t)p.src_w * p.src_h * 3;
         if ((p.brightness_on || p.n_distort > 0 || p.n_extra > 0) && bytes <= AUG_PRE_BYTES && p.src_w * p.src_h > pre_pixels) pre_pixels = p.src_w * p.src_h;
     }
     if (pre_pixels > 0) {
-        ProfScope prof("augment_photometric", 0.0, (double)b * pre_pixels * 6, s);
+        // (the profile's byte figure is the grid's reach, pictures x the largest one, as it has been for ssd_augment_batch_dev)
+        ProfScope prof("augment_photometric", 0.0, (double)n * pre_pixels * 6, s);
         const int gx = cdiv(pre_pixels, 256 * 4) < 1 ? 1 : cdiv(pre_pixels, 256 * 4);      // four strided pixels per thread
-        hipLaunchKernelGGL(augment_photometric_kernel, dim3(gx, b), dim3(256), 0, s, images_dev, prm, pre);
+        hipLaunchKernelGGL(augment_photometric_kernel, dim3(gx, n), dim3(256), 0, s, images_dev, a.prm, a.pre);
     }
+}
+
+void augment_batch(const unsigned char* images_dev, const ssd_augment_params* params_host, int b, int out_w, int out_h, float* out_dev,
+                   void* ws, hipStream_t s) {
+    SSD_REQUIRE(b >= 1 && out_w >= 1 && out_h >= 1, "augment: empty batch");
+    for (int i = 0; i < b; ++i) augment_check_params(params_host[i], i, out_w, out_h);
+    const AugWs a = augment_carve(ws, b, out_w, out_h);
+    HIP_OK(hipMemcpyAsync(a.prm, params_host, (size_t)b * sizeof(ssd_augment_params), hipMemcpyHostToDevice, s));
+    augment_launch_photometric(images_dev, params_host, b, a, s);
     {
         const int n = b * (out_w + out_h);
         ProfScope prof("augment_taps", 0.0, (double)n * AUG_TMAX * 8, s);
-        hipLaunchKernelGGL(augment_taps_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, prm, b, out_w, out_h, t);
+        hipLaunchKernelGGL(augment_taps_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, a.prm, b, out_w, out_h, a.t);
     }
     {
         const size_t total = (size_t)b * out_w * out_h;
         ProfScope prof("augment_gather", 0.0, (double)total * 12, s);
-        hipLaunchKernelGGL(augment_gather_kernel, dim3(cdiv(out_w * out_h, 256), b), dim3(256), 0, s, images_dev, prm, b, out_w, out_h, t, pre, out_dev);
+        hipLaunchKernelGGL(augment_gather_kernel, dim3(cdiv(out_w * out_h, 256), b), dim3(256), 0, s, images_dev, a.prm, b, out_w, out_h, a.t, a.pre, out_dev);
+    }
+    HIP_OK(hipGetLastError());
+}
+
+// ---- cells: several pictures per output sample (ssd_augment_cells_dev) ----
+constexpr int AUG_MAX_CELLS = 16;      // per sample
+
+static size_t augment_cells_off(int n_cells, int out_w, int out_h) { return (augment_ws_bytes(n_cells, out_w, out_h) + 255) / 256 * 256; }
+
+size_t augment_cells_ws_bytes(int n_cells, int out_w, int out_h) {
+    if (n_cells < 1 || out_w < 1 || out_h < 1) return 0;
+    return augment_cells_off(n_cells, out_w, out_h) + ((size_t)n_cells * sizeof(ssd_augment_cell) + 255) / 256 * 256;
+}
+
+// Every sample 0 .. b-1 is tiled by its cells: each cell inside the sample, pairwise disjoint, the areas summing to the sample's -- so
+// no pixel of `out` stays unwritten and none is written twice.  Host arithmetic only.
+static void augment_check_cells(const ssd_augment_params* params_host, const ssd_augment_cell* cells, int n_cells, int b, int out_w, int out_h) {
+    SSD_REQUIRE(b >= 1 && out_w >= 1 && out_h >= 1, "augment cells: empty batch");
+    SSD_REQUIRE(n_cells >= 1, "augment cells: no cells");
+    SSD_REQUIRE(n_cells <= AUG_MAX_CELLS * b, "augment cells: %d cells for %d samples (at most %d per sample)", n_cells, b, AUG_MAX_CELLS);
+    std::vector<int> count(b, 0), member((size_t)b * AUG_MAX_CELLS);
+    std::vector<long long> area(b, 0);
+    for (int i = 0; i < n_cells; ++i) {
+        const ssd_augment_cell& c = cells[i];
+        SSD_REQUIRE(c.sample >= 0 && c.sample < b, "augment cells: cell %d names sample %d of %d", i, c.sample, b);
+        SSD_REQUIRE(c.w >= 1 && c.h >= 1, "augment cells: cell %d is empty (%d x %d)", i, c.w, c.h);
+        SSD_REQUIRE(c.x0 >= 0 && c.y0 >= 0 && c.x0 <= out_w - c.w && c.y0 <= out_h - c.h, "augment cells: cell %d (%d x %d at %d, %d) lies outside the %d x %d sample",
+                    i, c.w, c.h, c.x0, c.y0, out_w, out_h);
+        SSD_REQUIRE(count[c.sample] < AUG_MAX_CELLS, "augment cells: sample %d has more than %d cells", c.sample, AUG_MAX_CELLS);
+        member[(size_t)c.sample * AUG_MAX_CELLS + count[c.sample]++] = i;
+        area[c.sample] += (long long)c.w * c.h;
+        augment_check_params(params_host[i], i, c.w, c.h);
+    }
+    for (int sm = 0; sm < b; ++sm) {
+        SSD_REQUIRE(count[sm] >= 1, "augment cells: sample %d has no cell", sm);
+        for (int u = 0; u < count[sm]; ++u)
+            for (int v = u + 1; v < count[sm]; ++v) {
+                const ssd_augment_cell& p = cells[member[(size_t)sm * AUG_MAX_CELLS + u]];
+                const ssd_augment_cell& q = cells[member[(size_t)sm * AUG_MAX_CELLS + v]];
+                const bool apart = p.x0 + p.w <= q.x0 || q.x0 + q.w <= p.x0 || p.y0 + p.h <= q.y0 || q.y0 + q.h <= p.y0;
+                SSD_REQUIRE(apart, "augment cells: cells %d and %d of sample %d overlap", member[(size_t)sm * AUG_MAX_CELLS + u],
+                            member[(size_t)sm * AUG_MAX_CELLS + v], sm);
+            }
+        SSD_REQUIRE(area[sm] == (long long)out_w * out_h, "augment cells: the cells of sample %d cover %lld of its %lld pixels (a gap)", sm, area[sm],
+                    (long long)out_w * out_h);
+    }
+}
+
+void augment_cells(const unsigned char* images_dev, const ssd_augment_params* params_host, const ssd_augment_cell* cells_host, int n_cells, int b,
+                   int out_w, int out_h, float* out_dev, void* ws, hipStream_t s) {
+    augment_check_cells(params_host, cells_host, n_cells, b, out_w, out_h);      // before any HIP call
+    const AugWs a = augment_carve(ws, n_cells, out_w, out_h);
+    ssd_augment_cell* cells = reinterpret_cast<ssd_augment_cell*>(static_cast<char*>(ws) + augment_cells_off(n_cells, out_w, out_h));
+    HIP_OK(hipMemcpyAsync(a.prm, params_host, (size_t)n_cells * sizeof(ssd_augment_params), hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(cells, cells_host, (size_t)n_cells * sizeof(ssd_augment_cell), hipMemcpyHostToDevice, s));
+    augment_launch_photometric(images_dev, params_host, n_cells, a, s);
+    int side = 0, pixels = 0;      // the longest w + h and the largest area of a cell: the grids' widths
+    long long coords = 0;          // tap-table columns written: the sum of w + h over the cells
+    for (int i = 0; i < n_cells; ++i) {
+        side = std::max(side, cells_host[i].w + cells_host[i].h);
+        coords += cells_host[i].w + cells_host[i].h;
+        pixels = std::max(pixels, cells_host[i].w * cells_host[i].h);
+    }
+    {
+        ProfScope prof("augment_taps_cells", 0.0, (double)coords * AUG_TMAX * 8, s);
+        hipLaunchKernelGGL(augment_taps_cells_kernel, dim3(cdiv(side, 256), n_cells), dim3(256), 0, s, a.prm, cells, out_w, out_h, a.t);
+    }
+    {
+        const size_t total = (size_t)b * out_w * out_h;
+        ProfScope prof("augment_gather_cells", 0.0, (double)total * 12, s);
+        hipLaunchKernelGGL(augment_gather_cells_kernel, dim3(cdiv(pixels, 256), n_cells), dim3(256), 0, s, images_dev, a.prm, cells, out_w, out_h, a.t,
+                           a.pre, out_dev);
     }
     HIP_OK(hipGetLastError());
 }

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Training driver: the counterpart of the reference's train.py loop (train.py:247-343) over
 the HIP library.  Same flags (train.py:55-80) plus --preset / --synthetic-train / --synthetic-valid /
---augment / --decoder / --cache-gb / --dtype / --ema-decay / --allreduce-bucket-mb / --allreduce-dtype.  Scalar summaries go to <tensorboard-dir>/<name>/scalars.jsonl
+--augment / --mosaic / --decoder / --cache-gb / --dtype / --ema-decay / --allreduce-bucket-mb / --allreduce-dtype.  Scalar summaries go to <tensorboard-dir>/<name>/scalars.jsonl
 (summaries.py), the annotated image summaries as PNG files; TensorBoard event files are out of scope.
 
     python -m ssd_tensorflow_amd.train --name run1 --epochs 2 --batch-size 8
@@ -225,6 +225,9 @@ def main(argv=None):
     parser.add_argument('--num-workers', type=int, default=0, help='number of parallel generators')
     parser.add_argument('--decoder', default='pillow', choices=['pillow', 'gpu'], help='a real --data-dir: pillow = the workers decode the files; gpu = they run the Huffman stage only and the GPU decodes in front of the augmentation kernel')
     parser.add_argument('--cache-gb', type=float, default=0, help='--decoder gpu: keep up to this many GB of decoded pictures in HBM; a cached picture costs no file read, no decode and no upload from its second epoch on (0 = off)')
+    parser.add_argument('--mosaic', type=float, default=0.0, help='mosaic augmentation: the probability that a training sample becomes a 2 x 2 mosaic of its own picture and three partners, each through the train recipe, composed on the GPU (DESIGN.md 39); needs a real --data-dir or --augment true; 0 = off')
+    parser.add_argument('--mosaic-center', type=float, nargs=2, default=[0.3, 0.7], metavar=('LO', 'HI'), help='--mosaic: the range of the mosaic centre, as fractions of the sample\'s sides')
+    parser.add_argument('--mosaic-off-epochs', type=int, default=0, help='--mosaic: the last N epochs of the run train without mosaics')
     parser.add_argument('--preset', default='vgg300')
     parser.add_argument('--data-source', default='pascal_voc', help='data source module for a real --data-dir')
     add_ap_arguments(parser)
@@ -246,6 +249,8 @@ def main(argv=None):
     parser.add_argument('--allreduce-dtype', default='f32', choices=['f32', 'bf16'], help='data parallel: bf16 = the filter gradients cross the links as bf16 messages of half the bytes (fp32 masters, momentum and arenas untouched)')
     parser.add_argument('--allreduce-bucket-mb', type=float, default=44, help='data parallel: all-reduce finished gradient ranges of >= this many MB while backward still runs (0 = one all-reduce after backward); 44 = three buckets: heads ... mod_conv6 | conv5_x + conv4_3/4_2 | the rest')
     args = parser.parse_args(argv)
+    if args.mosaic and not (args.augment or args.data_dir not in (None, '', 'synthetic', 'shapes')):
+        print('[!] --mosaic needs the transform path: a real --data-dir or --augment true'); return 1
 
     rank, local, world = parallel.init()
     import torch
@@ -352,11 +357,14 @@ def main(argv=None):
     say('[i] Weight EMA:           ', 'off' if args.ema_decay == 0 else 'decay %g; validation and its AP run on the average' % args.ema_decay)
     if args.cache_gb < 0 or (args.cache_gb and args.decoder != 'gpu'):
         print('[!] --cache-gb keeps pictures decoded on the GPU: it needs --decoder gpu and a size >= 0'); return 1
+    say('[i] Mosaic:               ', 'off' if not args.mosaic else 'probability %g, centre in %g..%g of the sides, off in the last %d epochs' % (
+        args.mosaic, args.mosaic_center[0], args.mosaic_center[1], args.mosaic_off_epochs))
     try:
         td = TrainingData(args.data_dir, args.preset, args.synthetic_train, args.synthetic_valid, rank=rank, world=world,
                           augment=args.augment, device=local, data_source=args.data_source,
                           synthetic_classes=args.synthetic_classes, decoder=args.decoder, cache_bytes=int(args.cache_gb * 1e9), match=args.match,
-                          shapes_size=[float(v) for v in args.shapes_size.split(';')])
+                          shapes_size=[float(v) for v in args.shapes_size.split(';')], mosaic=args.mosaic, mosaic_center=tuple(args.mosaic_center),
+                          mosaic_off_epochs=args.mosaic_off_epochs, epochs=args.epochs)
     except (RuntimeError, ValueError) as e:
         print('[!] Unable to load training data:', str(e)); return 1                       # train.py:155-161
     say('[i] # training samples:   ', td.num_train)
@@ -459,6 +467,7 @@ def main(argv=None):
         for e in range(start_epoch, args.epochs):
             td.epoch = e
             loop.run_epoch(td.train_generator, True, training_loss, training_ap_calc, e > 0, training_imgs)
+            fs = dict(td.feeder_stats)        # (of the training generator: the validation generator replaces them)
             with net.averaged_weights():      # (nothing without --ema-decay)
                 loop.run_epoch(td.valid_generator, False, validation_loss, validation_ap_calc, e > 0, validation_imgs)
             # ---- summaries (train.py:311-331) -----------------------------------------------------
@@ -468,6 +477,10 @@ def main(argv=None):
                 e + 1, args.epochs, tl['total'], tl['localization'], tl['confidence'], tl['l2']))
             say('[i] Valid {:>2}/{}  total {:.4f}  localization {:.4f}  confidence {:.4f}  l2 {:.4f}'.format(
                 e + 1, args.epochs, vl['total'], vl['localization'], vl['confidence'], vl['l2']))
+            if args.mosaic:
+                say('[i] Feed  {:>2}/{}  decoded {}  fallbacks {}  cache hits {}  mosaics {}  cells {}  area fallbacks {}'.format(
+                    e + 1, args.epochs, fs.get('decoded', 0), fs.get('fallbacks', 0), fs.get('cache_hits', 0), fs.get('mosaics', 0), fs.get('cells', 0),
+                    fs.get('area_fallbacks', 0)))
             if loop.grad_norms is not None:
                 gn = loop.grad_norms.push(e + 1)
                 say('[i] Grad  {:>2}/{}  norm median {:.4g}  max {:.4g}  clipped {}  skipped {}  of {} updates'.format(

@@ -41,6 +41,11 @@ decoder='gpu' (DESIGN.md 17): the workers run only the Huffman stage of a JPEG (
 coefficients; the feeder launches ssd_jpeg_decode_batch_dev in front of the augmentation kernel, so the pixels are born in HBM too.
 cache_bytes > 0 keeps them there (_SourceArena): from the second epoch on a cached sample costs its worker no file and the bus
 nothing but its parameter record and boxes.
+
+mosaic > 0: with that probability a training sample is a 2 x 2 mosaic of its own picture and three partners.  A
+batch is then a plan list of up to four source pictures per sample plus 'cells' (where each lands) and 'src_idx' (which picture of
+the data set each is); the decode, the cache and the fallback work per source picture, ssd_augment_cells_dev composes the samples,
+and slots, staging, arena scratch and workspace are sized for four sources per sample.
 """
 import multiprocessing as mp
 import os
@@ -142,47 +147,121 @@ class _Recipe:
             return dict({'images': np.stack(imgs)}, **_gt_packed(gts, td.num_classes)), gts
         from . import transforms as T
         host_tfs = [t for t in self.transforms if not isinstance(t, T.LabelCreatorTransform)]
-        loader = host_tfs[0]
-        preset_images = getattr(loader, 'images', None)
-        plans, gts = [], []
-        try:
-            for k, i in enumerate(idx):
-                s = self.sample_at(int(i))
-                if not isinstance(s, Sample):                    # synthetic: the pixels travel with the record
-                    loader.images, sample = s
-                else:
-                    loader.images, sample = preset_images, s
-                if self.gpu_decode:                                  # the file is read once per sample, or not at all
-                    loader.kept = None
-                    if known and k in known and isinstance(s, Sample):
-                        loader.kept = (s.filename, T.DeferredJpeg(None, known[k], s.filename))
-                random.seed(td._sample_seed(self.salt, epoch, int(i)))
-                # run_transforms until at least one anchor is positive, at most 50 times (training_data.py:88-98);
-                # the label of a try is only LOOKED at there (num_bg < rows), so the test runs on the host and the
-                # label vectors of the whole batch are encoded once, on the GPU
-                for _ in range(50):
-                    args = (None, None, sample)
-                    for t in host_tfs:
-                        args = t(*args)
-                    if has_positive_anchor(td.preset, args[2].boxes, td.match):
-                        break
-                plans.append(args[0]); gts.append(args[2].boxes)
-        finally:
-            loader.images = preset_images
-            if self.gpu_decode:
-                loader.kept = None
+        mosaics = td.mosaic_prob(self, epoch) > 0            # (False: nothing new is drawn, no new array travels)
+        sources = self.sources(epoch, idx) if mosaics else [([int(i)], None) for i in idx]
+        return self._plan_sources(epoch, sources, known, host_tfs, mosaics)
+
+    def _pack(self, plans, gts, extra=None):
+        """The planned pictures and the samples' boxes as the arrays that travel.  extra (a batch with mosaics): 'cells' [n_src][5]
+        int32 (sample, x0, y0, w, h), 'src_idx' (the data set index of every source picture) and 'mosaic_stats'."""
+        from . import transforms as T
+        td = self.td
         W, H = td.preset.image_size.w, td.preset.image_size.h
+        extra = extra or {}
+        cells = extra.get('cells')
         if not self.gpu_decode:
-            arr, packed = T.plan_params(plans, W, H)
-            return dict({'params': np.frombuffer(arr, np.uint8).copy(), 'packed': packed}, **_gt_packed(gts, td.num_classes)), gts
+            arr, packed = T.plan_params(plans, W, H, cells=cells)
+            return dict({'params': np.frombuffer(arr, np.uint8).copy(), 'packed': packed}, **extra, **_gt_packed(gts, td.num_classes)), gts
         coef, descs = self._entropy_stage(plans)
-        arr, packed = T.plan_params(plans, W, H)
+        arr, packed = T.plan_params(plans, W, H, cells=cells)
         kind = np.array([SRC_PIXELS if p.jpeg is None else SRC_COEF if p.jpeg.data is not None else SRC_CACHED for p in plans], np.int32)
         for d, k in zip(descs, np.flatnonzero(kind == SRC_COEF)):
             d.dst_off = arr[k].src_off
         return dict({'params': np.frombuffer(arr, np.uint8).copy(), 'packed': packed, 'coef': coef,
                      'descs': np.frombuffer(b''.join(bytes(d) for d in descs), np.uint8).copy(), 'src_kind': kind},
-                    **_gt_packed(gts, td.num_classes)), gts
+                    **extra, **_gt_packed(gts, td.num_classes)), gts
+
+    # ---- mosaic augmentation (DESIGN.md 39) ------------------------------------------------------------------------------
+    def sources(self, epoch, idx):
+        """Per sample of idx: (the data set indices of its source pictures -- itself, or itself and its three partners --, the
+        mosaic centre or None).  A pure function of (seed, epoch, index): the parent computes it without running a transform (the
+        arena's `known` table of a task), the worker that plans the batch computes the same."""
+        from . import transforms as T
+        td = self.td
+        p = td.mosaic_prob(self, epoch)
+        W, H = td.preset.image_size.w, td.preset.image_size.h
+        out = []
+        for i in idx:
+            d = T.mosaic_draw(td._sample_seed(self.salt, epoch, int(i)), p, self.total, W, H, td.mosaic_center) if p > 0 else None
+            out.append(([int(i)], None) if d is None else ([int(i)] + d[0], d[1]))
+        return out
+
+    def _plan_sources(self, epoch, sources, known, host_tfs, mosaics):
+        """The transform path of _plan.  sources: per sample (its source pictures, the mosaic centre or None).  A sample that is no
+        mosaic runs the transform list seeded from its sample seed, as ever (with mosaics it is also booked as the one cell
+        (0, 0, W, H)); a mosaic's four cells run the cell transform list (transforms.mosaic_cell_transforms), each seeded from
+        (sample seed, try, cell).  Either is redrawn (<= 50 times) until at least one anchor is positive (training_data.py:88-98;
+        the label of a try is only LOOKED at there, so the test runs on the host and the label vectors of the whole batch are
+        encoded once, on the GPU); a mosaic's test sees the MERGED boxes and redraws the four recipes, never the partners.
+        known: {position in the batch's flat source list: (h, w)}."""
+        from . import transforms as T
+        td = self.td
+        W, H = td.preset.image_size.w, td.preset.image_size.h
+        loader = host_tfs[0]
+        preset_images = getattr(loader, 'images', None)
+        cell_tfs, resize = T.mosaic_cell_transforms(self.transforms) if mosaics else (None, None)
+        plans, gts, cells, src_idx = [], [], [], []
+        stats = np.zeros(3, np.int64)          # mosaics, cells, area_fallbacks
+
+        def load(i, pos):                      # the loader's state for source picture i at position pos of the flat source list
+            s = self.sample_at(i)
+            if not isinstance(s, Sample):                        # synthetic: the pixels travel with the record
+                loader.images, sample = s
+            else:
+                loader.images, sample = preset_images, s
+            if self.gpu_decode:                                  # the file is read once per sample, or not at all
+                loader.kept = None
+                if known and pos in known and isinstance(s, Sample):
+                    loader.kept = (s.filename, T.DeferredJpeg(None, known[pos], s.filename))
+            return sample
+
+        try:
+            for k, (srcs, centre) in enumerate(sources):
+                seed = td._sample_seed(self.salt, epoch, srcs[0])
+                pos = len(plans)
+                if centre is None:
+                    sample = load(srcs[0], pos)
+                    random.seed(seed)
+                    for _ in range(50):
+                        args = (None, None, sample)
+                        for t in host_tfs:
+                            args = t(*args)
+                        if has_positive_anchor(td.preset, args[2].boxes, td.match):
+                            break
+                    plans.append(args[0]); gts.append(args[2].boxes)
+                    cells.append((k, 0, 0, W, H)); src_idx.append(srcs[0])
+                    stats[1] += 1
+                    continue
+                layout = T.mosaic_layout(centre[0], centre[1], W, H)
+                kept = [None] * 4              # decoder='gpu': each file is read once per sample, whatever the number of tries
+                for tries in range(50):
+                    got, merged, fell = [], [], 0
+                    for c, (src, cell) in enumerate(zip(srcs, layout)):
+                        sample = load(src, pos + c)
+                        if self.gpu_decode and kept[c] is not None:
+                            loader.kept = kept[c]
+                        random.seed((seed << 16) | (tries << 4) | (c + 1))
+                        args = (None, None, sample)
+                        for t in cell_tfs:
+                            args = t(*args)
+                        if self.gpu_decode:
+                            kept[c] = loader.kept
+                        data, _, gt, f = T.mosaic_cell_resize(resize, args[0], args[1], args[2], cell[2], cell[3])
+                        got.append(data); fell += f
+                        merged += [T.mosaic_box(b, cell, W, H) for b in gt.boxes]
+                    if has_positive_anchor(td.preset, merged, td.match):
+                        break
+                plans += got; gts.append(merged)
+                cells += [(k,) + cell for cell in layout]; src_idx += srcs
+                stats += (1, 4, fell)
+        finally:
+            loader.images = preset_images
+            if self.gpu_decode:
+                loader.kept = None
+        if not mosaics:
+            return self._pack(plans, gts)
+        return self._pack(plans, gts, {'cells': np.array(cells, np.int32).reshape(-1, 5), 'src_idx': np.array(src_idx, np.int64),
+                                       'mosaic_stats': stats})
 
     @staticmethod
     def _entropy_stage(plans):
@@ -223,7 +302,7 @@ class _Recipe:
             return batch_size * (H * W * 3 * 4 + 4096) + 8192
         # (decoder='gpu': a sample travels as pixels OR as coefficients, and the coefficients' bound is the larger one)
         per_image = max(td._max_image_bytes, td._max_coef_bytes + 512 if self.gpu_decode else 0)
-        return batch_size * (per_image + 16 + 256 + 4096) + 8192
+        return td.sources_per_batch(self, batch_size) * (per_image + 16 + 256 + 4096) + 8192
 
 
 def _worker_main(recipe, tasks, results, anchors_abs=None):
@@ -268,6 +347,7 @@ class _SourceArena:
         self.max_image_bytes = int(max_image_bytes)
         self.image_bytes = (self.max_image_bytes + 16 + 255) // 256 * 256
         self.buf, self.batch = None, 0
+        self.scale = {'train': 1, 'valid': 1}      # source pictures per sample of a data set's batches (a mosaic has four)
         self.table = {}                        # (data set, sample index) -> (byte offset, h, w)
         self.used = 0
         self.event, self.event_stream = None, None
@@ -282,7 +362,7 @@ class _SourceArena:
                 return
             if self.buf is not None and busy:
                 raise RuntimeError('a larger batch size needs a larger source arena: finish the live generators first')
-            size = self.cache_bytes + 2 * (DEVICE_SLOTS + 1) * batch_size * self.image_bytes
+            size = self.cache_bytes + (DEVICE_SLOTS + 1) * sum(self.scale.values()) * batch_size * self.image_bytes
             buf = torch.empty((size,), dtype=torch.uint8, device=dev)
             cur = torch.cuda.current_stream(dev)
             if self.buf is not None and self.used:
@@ -296,9 +376,9 @@ class _SourceArena:
 
     def region(self, which, slot):
         """(byte offset, bytes) of the scratch of a data set's device slot (None: its serial generator)"""
-        r = (0 if which == 'train' else DEVICE_SLOTS + 1) + (0 if slot is None else 1 + slot)
-        n = self.batch * self.image_bytes
-        return self.cache_bytes + r * n, n
+        n = self.scale[which] * self.batch * self.image_bytes
+        first = 0 if which == 'train' else (DEVICE_SLOTS + 1) * self.scale['train'] * self.batch * self.image_bytes
+        return self.cache_bytes + first + (0 if slot is None else 1 + slot) * n, n
 
 
 class _SharedImageCache:
@@ -494,7 +574,10 @@ class TrainingData:
     def __init__(self, data_dir=None, preset='vgg300', num_train=64, num_valid=16, seed=1234, rank=0, world=1,
                  augment=False, sampler_trials=50, expand_prob=0.5, device=0, device_tensors=True,
                  data_source='pascal_voc', valid_fraction=0.025, images=None, synthetic_classes=20, decoder='pillow', cache_bytes=0,
-                 match='reference', shapes_size=(0.2, 0.5)):
+                 match='reference', shapes_size=(0.2, 0.5), mosaic=0.0, mosaic_center=(0.3, 0.7), mosaic_off_epochs=0, epochs=None):
+        """mosaic: the probability that a TRAINING sample becomes a 2 x 2 mosaic of its own picture and three partners
+        (needs the transform path: a real data_dir or augment=True); mosaic_center: the range of the centre as fractions of the
+        sample's sides; mosaic_off_epochs: the last N of `epochs` (the run's epoch count, which the driver passes) train without."""
         match_id(match)                        # 'reference' or 'paper' (DESIGN.md 29); anything else: ValueError
         self.match = match
         lo, hi = (float(v) for v in shapes_size)   # 'shapes': the rectangles' sides, as fractions of the frame
@@ -506,6 +589,15 @@ class TrainingData:
         if int(cache_bytes) < 0 or (cache_bytes and decoder != 'gpu'):
             raise ValueError("cache_bytes keeps pictures decoded on the GPU: it needs decoder='gpu' and a size >= 0")
         self.decoder, self.cache_bytes = decoder, int(cache_bytes)
+        self.mosaic = float(mosaic)
+        lo_c, hi_c = (float(v) for v in mosaic_center)
+        if not 0.0 <= self.mosaic <= 1.0:
+            raise ValueError('mosaic is a probability (got %r)' % (mosaic,))
+        if not 0.0 < lo_c <= hi_c < 1.0:
+            raise ValueError('mosaic_center must be (lo, hi) with 0 < lo <= hi < 1 (got %r)' % (mosaic_center,))
+        if int(mosaic_off_epochs) < 0 or (int(mosaic_off_epochs) > 0 and self.mosaic > 0 and epochs is None):
+            raise ValueError('mosaic_off_epochs counts back from the end of the run: it needs epochs, the number of epochs')
+        self.mosaic_center, self.mosaic_off_epochs, self.epochs = (lo_c, hi_c), int(mosaic_off_epochs), epochs
         self._arena = None
         self._max_coef_bytes = 0
         self.preset = get_preset_by_name(preset) if isinstance(preset, str) else preset
@@ -518,7 +610,9 @@ class TrainingData:
         # where a prefetched epoch's time went (seconds, reset by every gen_batch call with workers): the consumer waiting
         # for a batch, the feeder thread waiting for the workers / for a free device slot / uploading
         # decoder='gpu': samples whose JPEG the GPU decoded / that travelled as pixels / that were served from the arena
-        self.feeder_stats = dict(consumer_wait=0.0, worker_wait=0.0, slot_wait=0.0, upload=0.0, batches=0, decoded=0, fallbacks=0, cache_hits=0)
+        # mosaic > 0: samples that became mosaics / cells planned (a plain sample is one) / INTER_AREA cells that fell back to INTER_LINEAR
+        self.feeder_stats = dict(consumer_wait=0.0, worker_wait=0.0, slot_wait=0.0, upload=0.0, batches=0, decoded=0, fallbacks=0, cache_hits=0,
+                                 mosaics=0, cells=0, area_fallbacks=0)
         from . import transforms as T
         # 'shapes': the learnable synthetic set (textured rectangles, class = texture; _shapes_canvas) -- same plumbing as
         # 'synthetic', whose uniform-noise images carry nothing a detector could learn
@@ -570,6 +664,9 @@ class TrainingData:
             else:
                 self.train_samples = self.valid_samples = None
                 self._recipes = {'train': _Recipe(self, 'train', num_train, 0), 'valid': _Recipe(self, 'valid', num_valid, 1 << 20)}
+        if self.mosaic > 0 and self._recipes['train'].transforms is None:
+            raise ValueError('mosaic needs the transform path: a real data_dir or augment=True')
+        self._scale_arena()
         self.train_generator = self._make_generator(self._recipes['train'])
         self.valid_generator = self._make_generator(self._recipes['valid'])
 
@@ -592,12 +689,38 @@ class TrainingData:
             r.dev = None
         if self._arena is not None:            # the cached pictures go with the buffer
             self._arena = _SourceArena(self.cache_bytes, self._arena.max_image_bytes)
+            self._scale_arena()
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+    # ---- mosaic augmentation -------------------------------------------------------------------------------------------------
+    def mosaic_prob(self, recipe, epoch):
+        """The mosaic probability of a data set in an epoch: validation never mosaics, nor do the last mosaic_off_epochs epochs."""
+        if self.mosaic <= 0 or recipe.which != 'train' or recipe.transforms is None:
+            return 0.0
+        if self.mosaic_off_epochs > 0 and int(epoch) >= int(self.epochs) - self.mosaic_off_epochs:
+            return 0.0
+        return self.mosaic
+
+    def sources_per_batch(self, recipe, batch_size):
+        """How many source pictures a batch of a data set can carry: what the slots, the staging tensors, the source arena's scratch
+        and the kernels' workspace are sized for."""
+        return batch_size * (4 if self.mosaic > 0 and recipe.which == 'train' and recipe.transforms is not None else 1)
+
+    def _scale_arena(self):
+        """the arena's scratch regions per data set: the training set's hold four sources per sample with mosaics, the validation
+        set's keep their size"""
+        if self._arena is not None:
+            self._arena.scale = {w: self.sources_per_batch(r, 1) for w, r in self._recipes.items()}
+
+    def _note_mosaics(self, stats, arrays):
+        if 'mosaic_stats' in arrays:
+            m = arrays['mosaic_stats']
+            stats['mosaics'] += int(m[0]); stats['cells'] += int(m[1]); stats['area_fallbacks'] += int(m[2])
 
     def _sample_seed(self, salt, epoch, index):
         """The seed of sample #index's decisions in `epoch` of data set `salt`: one integer whose 32-bit words all
@@ -701,19 +824,24 @@ class TrainingData:
         dev = torch.device('cuda', self.device)
         W, H = self.preset.image_size.w, self.preset.image_size.h
         A, nv = self.preset.num_anchors, self.num_classes + 5
-        d = {'batch': batch_size, 'stream': torch.cuda.Stream(device=dev),
+        n_src = self.sources_per_batch(recipe, batch_size)
+        ws_bytes = lib.ssd_augment_ws_bytes(batch_size, W, H) if n_src == batch_size else lib.ssd_augment_cells_ws_bytes(n_src, W, H)
+        d = {'batch': batch_size, 'sources': n_src, 'stream': torch.cuda.Stream(device=dev),
              'images': [torch.empty((batch_size, H, W, 3), dtype=torch.float32, device=dev) for _ in range(DEVICE_SLOTS)],
              'labels': [torch.empty((batch_size, A, nv), dtype=torch.float32, device=dev) for _ in range(DEVICE_SLOTS)],
              'packed': [None] * DEVICE_SLOTS, 'enc_ws': [None] * DEVICE_SLOTS, 'jpeg_ws': [None] * DEVICE_SLOTS,
-             'ws': [torch.empty((lib.ssd_augment_ws_bytes(batch_size, W, H),), dtype=torch.uint8, device=dev) for _ in range(DEVICE_SLOTS)]}
+             'ws': [torch.empty((ws_bytes,), dtype=torch.uint8, device=dev) for _ in range(DEVICE_SLOTS)]}
         recipe.dev = d
         return d
 
-    def _known(self, recipe, idx):
-        """{position in idx: (h, w)} of the samples whose pixels lie in the arena (what a task tells its worker), else None"""
+    def _known(self, recipe, idx, epoch=0):
+        """{position in the batch's source list: (h, w)} of the source pictures that lie in the arena (what a task tells its worker),
+        else None.  The source list is idx itself, or with mosaics every sample's picture and partners (_Recipe.sources)."""
         arena = self._arena
         if arena is None or not arena.table or not recipe.gpu_decode:
             return None
+        if self.mosaic_prob(recipe, epoch) > 0:
+            idx = [i for srcs, _ in recipe.sources(epoch, idx) for i in srcs]
         hits = {k: arena.table.get((recipe.which, int(i))) for k, i in enumerate(idx)}
         return {k: (e[1], e[2]) for k, e in hits.items() if e is not None} or None
 
@@ -730,6 +858,7 @@ class TrainingData:
         arena, stats = self._arena, recipe.stats          # (the stats of THIS data set's generator: two may be live)
         dev = torch.device('cuda', self.device)
         cur = torch.cuda.current_stream(dev)
+        idx = arrays['src_idx'] if 'src_idx' in arrays else idx      # per SOURCE picture: a mosaic's partners are cached like any sample
         b = len(idx)
         kind = arrays['src_kind']
         params = (T._Params * b).from_buffer_copy(arrays['params'].tobytes())
@@ -806,6 +935,9 @@ class TrainingData:
         dev = torch.device('cuda', self.device)
         W, H = self.preset.image_size.w, self.preset.image_size.h
         ring = ring if slot is not None else None
+        cells = arrays.get('cells')
+        n_src = b if cells is None else int(cells.shape[0])
+        ws_bytes = lambda: lib.ssd_augment_ws_bytes(b, W, H) if cells is None else lib.ssd_augment_cells_ws_bytes(n_src, W, H)
         if 'images' in arrays:
             src = torch.from_numpy(arrays['images'])
             if ring is not None:
@@ -822,24 +954,39 @@ class TrainingData:
                     images, ws = ring['images'][slot][:b], ring['ws'][slot]
                 else:
                     images = torch.empty((b, H, W, 3), dtype=torch.float32, device=dev)
-                    ws = torch.empty((lib.ssd_augment_ws_bytes(b, W, H),), dtype=torch.uint8, device=dev)
+                    ws = torch.empty((ws_bytes(),), dtype=torch.uint8, device=dev)
                 params = np.frombuffer(params, np.uint8)
             elif ring is not None:
                 if ring['packed'][slot] is None or ring['packed'][slot].numel() < packed.size:
-                    ring['packed'][slot] = torch.empty((max(packed.size, ring['batch'] * (self._max_image_bytes + 16)),), dtype=torch.uint8, device=dev)
+                    ring['packed'][slot] = torch.empty((max(packed.size, ring['sources'] * (self._max_image_bytes + 16)),), dtype=torch.uint8, device=dev)
                 staged = ring['packed'][slot][:packed.size]
                 staged.copy_(torch.from_numpy(packed), non_blocking=True)
                 images, ws = ring['images'][slot][:b], ring['ws'][slot]
             else:
                 staged = torch.from_numpy(packed).to(dev)
                 images = torch.empty((b, H, W, 3), dtype=torch.float32, device=dev)
-                ws = torch.empty((lib.ssd_augment_ws_bytes(b, W, H),), dtype=torch.uint8, device=dev)
-            check(lib.ssd_augment_batch_dev(staged.data_ptr(), C.c_void_p(params.ctypes.data), b, W, H, images.data_ptr(), ws.data_ptr(),
-                                            torch.cuda.current_stream(dev).cuda_stream))
+                ws = torch.empty((ws_bytes(),), dtype=torch.uint8, device=dev)
+            self._augment(staged.data_ptr(), C.c_void_p(params.ctypes.data), cells, b, images, ws, torch.cuda.current_stream(dev).cuda_stream)
             if not self.device_tensors:
                 images = images.cpu().numpy()
         labels = self._labels(gts, out=ring['labels'][slot][:b] if ring is not None else None)
         return images, labels
+
+    def _augment(self, src_ptr, params, cells, b, images, ws, stream):
+        """The batch's augmentation kernels: one picture per sample (ssd_augment_batch_dev, whenever the batch carries no cells), or
+        the sources into their cells (ssd_augment_cells_dev)."""
+        import ctypes as C
+        from ._lib import lib, check
+        W, H = self.preset.image_size.w, self.preset.image_size.h
+        if cells is None:
+            check(lib.ssd_augment_batch_dev(src_ptr, params, b, W, H, images.data_ptr(), ws.data_ptr(), stream))
+            return
+        cells = np.ascontiguousarray(cells, np.int32)
+        need = lib.ssd_augment_cells_ws_bytes(int(cells.shape[0]), W, H)
+        if ws.numel() < need:
+            raise RuntimeError('a batch of %d source pictures needs %d bytes of augmentation workspace, the slot has %d' % (cells.shape[0], need, ws.numel()))
+        check(lib.ssd_augment_cells_dev(src_ptr, params, C.c_void_p(cells.ctypes.data), int(cells.shape[0]), b, W, H, images.data_ptr(), ws.data_ptr(),
+                                        stream))
 
     def _upload_async(self, ring, slot_arr, arrays, gts, dslot, recipe=None, idx=None):
         """The prefetching feeder's upload: ONE host-to-device transfer of the slot's used prefix (source bytes, parameter
@@ -863,7 +1010,7 @@ class TrainingData:
         staged = ring['packed'][dslot]
         if staged is None or staged.numel() < need:
             per_image = max(getattr(self, '_max_image_bytes', 0), self._max_coef_bytes + 512 if self._max_coef_bytes else 0)
-            cap = max(need, ring['batch'] * (per_image + 16 + 256 + 4096) + 8192)
+            cap = max(need, ring['sources'] * (per_image + 16 + 256 + 4096) + 8192)
             staged = ring['packed'][dslot] = torch.empty((cap,), dtype=torch.uint8, device=dev)
         staged[:need].copy_(torch.from_numpy(slot_arr[lo:hi]), non_blocking=True)
         sp = staged.data_ptr() - lo
@@ -873,11 +1020,9 @@ class TrainingData:
         elif 'descs' in arrays:
             part = lambda k: staged[offs[k] - lo:offs[k] - lo + arrays[k].nbytes] if arrays[k].nbytes else staged[:0]
             src, params = self._decode_sources(recipe, idx, arrays, dslot, ring, part('coef'), part('packed'))
-            check(lib.ssd_augment_batch_dev(src.data_ptr(), C.cast(params, C.c_void_p), b, W, H, images.data_ptr(),
-                                            ring['ws'][dslot].data_ptr(), stream))
+            self._augment(src.data_ptr(), C.cast(params, C.c_void_p), arrays.get('cells'), b, images, ring['ws'][dslot], stream)
         else:
-            check(lib.ssd_augment_batch_dev(sp + offs['packed'], C.c_void_p(arrays['params'].ctypes.data), b, W, H, images.data_ptr(),
-                                            ring['ws'][dslot].data_ptr(), stream))
+            self._augment(sp + offs['packed'], C.c_void_p(arrays['params'].ctypes.data), arrays.get('cells'), b, images, ring['ws'][dslot], stream)
         ntot = int(arrays['gcls'].shape[0])
         mid = match_id(self.match)
         ws_need = lib.ssd_encode_labels_ws_bytes_ex(ntot, b, mid)
@@ -902,6 +1047,7 @@ class TrainingData:
             if num_workers and num_workers > 0 and (self.device_tensors or self._upload_hook is not None):
                 yield from self._prefetched(recipe, batches, self.epoch, batch_size, int(num_workers))
                 return
+            self.feeder_stats.update(mosaics=0, cells=0, area_fallbacks=0)
             if arena is not None:
                 self.feeder_stats.update(decoded=0, fallbacks=0, cache_hits=0)
                 recipe.stats = self.feeder_stats
@@ -910,7 +1056,8 @@ class TrainingData:
                     self.global_count = count
                     yield None, None, []
                     continue
-                arrays, gts = recipe.plan(self.epoch, idx, self._known(recipe, idx) if arena is not None else None)
+                arrays, gts = recipe.plan(self.epoch, idx, self._known(recipe, idx, self.epoch) if arena is not None else None)
+                self._note_mosaics(self.feeder_stats, arrays)
                 images, labels = self._upload(arrays, gts, recipe=recipe, idx=idx)
                 self.global_count = count
                 yield images, labels, gts
@@ -946,7 +1093,7 @@ class TrainingData:
             dev_free.put((s, None))
         cancel = threading.Event()
         stats = self.feeder_stats = dict(consumer_wait=0.0, worker_wait=0.0, slot_wait=0.0, upload=0.0, host_slot_wait=0.0, batches=0,
-                                         decoded=0, fallbacks=0, cache_hits=0)
+                                         decoded=0, fallbacks=0, cache_hits=0, mosaics=0, cells=0, area_fallbacks=0)
         cached = use_gpu and recipe.gpu_decode
         recipe.stats = stats
         clock = time.perf_counter
@@ -975,7 +1122,7 @@ class TrainingData:
                         else:
                             slot = pool.free_slots.pop()
                             pool.outstanding[(gen, next_submit)] = slot
-                            pool.tasks.put((gen, next_submit, slot, epoch, np.asarray(idx), self._known(recipe, idx) if cached else None))
+                            pool.tasks.put((gen, next_submit, slot, epoch, np.asarray(idx), self._known(recipe, idx, epoch) if cached else None))
                         next_submit += 1
                     if next_upload in done:
                         item = done.pop(next_upload)
@@ -995,6 +1142,7 @@ class TrainingData:
                                     return
                         t1 = clock()
                         stats['slot_wait'] += t1 - t0
+                        self._note_mosaics(stats, arrays)
                         if use_gpu:
                             slot_arr = pool.results.array_pool[hslot]
                             in_slot = all(isinstance(v, np.ndarray) and v.base is not None and

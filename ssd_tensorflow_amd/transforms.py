@@ -535,12 +535,18 @@ class _Params(C.Structure):
                 ('n_post', C.c_int), ('post_kind', C.c_int * MAX_POST), ('post_val', C.c_float * MAX_POST), ('out_flip', C.c_int)]
 
 
+class _Cell(C.Structure):
+    """ssd_augment_cell (include/ssdvgg_hip.h): picture i of a batch lands in this rectangle of output sample `sample`"""
+    _fields_ = [('sample', C.c_int), ('x0', C.c_int), ('y0', C.c_int), ('w', C.c_int), ('h', C.c_int)]
+
+
 def _step_val(kind, val):
     return float(val[0] + 4 * val[1] + 16 * val[2]) if kind == 4 else float(val)      # a permutation travels as a base-4 code
 
 
-def plan_params(plans, width, height, src_offs=None):
-    """(ctypes array of ssd_augment_params, packed uint8 image bytes) for a list of ImagePlans.  Plans whose pixels are device
+def plan_params(plans, width, height, src_offs=None, cells=None):
+    """(ctypes array of ssd_augment_params, packed uint8 image bytes) for a list of ImagePlans.  cells ([n][5] rows of sample, x0,
+    y0, w, h: ssd_augment_cells_dev): plan i resizes to ITS cell's w x h instead of width x height.  Plans whose pixels are device
     sources must all lie in one device buffer: src_off is their offset in it and the packed array is None.
     Deferred JPEGs may stand among host arrays: src_off is then an offset in the batch's source region, where the caller decodes
     the JPEGs and copies the host arrays; `packed` holds the host arrays alone, in order, each padded to 16 bytes.  src_offs gives
@@ -573,8 +579,9 @@ def plan_params(plans, width, height, src_offs=None):
     for i, p in enumerate(plans):
         if p.resize is None:
             raise ValueError('plan %d was not resized: the batch needs one output size (ResizeTransform last)' % i)
-        if (p.resize[0], p.resize[1]) != (width, height):
-            raise ValueError('plan %d resizes to %s, the batch is %s' % (i, p.resize[:2], (width, height)))
+        want = (width, height) if cells is None else (int(cells[i][3]), int(cells[i][4]))
+        if (p.resize[0], p.resize[1]) != want:
+            raise ValueError('plan %d resizes to %s, %s' % (i, p.resize[:2], 'the batch is %s' % (want,) if cells is None else 'its cell is %s' % (want,)))
         q = arr[i]
         q.src_off = offs[i]; q.src_w = p.src.w; q.src_h = p.src.h
         q.brightness_on = int(p.brightness is not None); q.brightness_delta = p.brightness or 0
@@ -635,6 +642,100 @@ def augment_batch(plans, width, height, device=0, out=None, return_images=False)
     if return_images:
         return out, images, [int(arr[i].src_off) for i in range(b)]
     return out
+
+
+def cells_array(cells):
+    """[n][5] int32 rows (sample, x0, y0, w, h) -> (ctypes array of ssd_augment_cell, the int32 array that backs it)"""
+    a = np.ascontiguousarray(np.asarray(cells, np.int32).reshape(-1, 5))
+    return (_Cell * a.shape[0]).from_buffer(a), a
+
+
+def augment_cells(plans, cells, b, width, height, device=0, out=None):
+    """Run ImagePlans into the cells of b output samples (ssd_augment_cells_dev), on torch's current stream: plan i, resized to its
+    cell's w x h, lands at (x0, y0) of sample cells[i][0].  The cells of every sample must tile it.  Returns a torch float32 tensor
+    [b, height, width, 3] on `device` (out: the tensor to fill)."""
+    import torch
+    if any(getattr(p, 'jpeg', None) is not None for p in plans):
+        raise ValueError('augment_cells runs plans whose pixels exist; deferred JPEGs are decoded by the training feeder (training_data.py)')
+    carr, cnp = cells_array(cells)
+    if cnp.shape[0] != len(plans):
+        raise ValueError('%d cells for %d plans' % (cnp.shape[0], len(plans)))
+    arr, packed = plan_params(plans, width, height, cells=cnp)
+    dev = torch.device('cuda', device)
+    images = torch.from_numpy(packed).to(dev) if packed is not None else plans[0].device_src[0]
+    if images.device != dev:
+        raise ValueError('the device sources lie on %s, the batch runs on %s' % (images.device, dev))
+    if out is None:
+        out = torch.empty((b, height, width, 3), dtype=torch.float32, device=dev)
+    ws = torch.empty((max(lib.ssd_augment_cells_ws_bytes(len(plans), width, height), 1),), dtype=torch.uint8, device=dev)
+    check(lib.ssd_augment_cells_dev(images.data_ptr(), C.cast(arr, C.c_void_p), C.cast(carr, C.c_void_p), len(plans), b, width, height,
+                                    out.data_ptr(), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# mosaic augmentation (DESIGN.md 39): four differently augmented pictures in the four cells of one sample
+# ------------------------------------------------------------------------------------------------
+MOSAIC_SALT = 0x6d6f7361          # 'mosa': keeps the mosaic draws apart from the sample's own stream
+AREA_MAX_SHRINK = 14              # INTER_AREA's tap table (csrc/augment.hip AUG_TMAX - 2)
+
+
+def mosaic_layout(mx, my, width, height):
+    """The four cells (x0, y0, w, h) of the centre (mx, my), 1 <= mx < width, 1 <= my < height, in the order top-left, top-right,
+    bottom-left, bottom-right: they tile the sample."""
+    mx, my = int(mx), int(my)
+    if not (1 <= mx < width and 1 <= my < height):
+        raise ValueError('a mosaic centre must leave every cell a pixel: (%d, %d) in %d x %d' % (mx, my, width, height))
+    return [(0, 0, mx, my), (mx, 0, width - mx, my), (0, my, mx, height - my), (mx, my, width - mx, height - my)]
+
+
+def mosaic_draw(sample_seed, prob, total, width, height, center=(0.3, 0.7)):
+    """The mosaic decision of one training sample: None, or (the three partners' sample indices, the centre (mx, my)).  A pure
+    function of its arguments: the draws come from a private generator seeded from the sample's seed (TrainingData._sample_seed) and
+    a constant, in the order decision, partners, centre x, centre y.  The partners are uniform over range(total) and may repeat; the
+    centre is uniform over the whole pixels of [round(lo W), round(hi W)] x [round(lo H), round(hi H)], kept inside 1 .. side - 1."""
+    if prob <= 0:
+        return None
+    rng = random.Random((int(sample_seed) << 32) | MOSAIC_SALT)
+    if not rng.random() < prob:
+        return None
+    partners = [rng.randrange(total) for _ in range(3)]
+    lo, hi = center
+    clamp = lambda v, side: min(max(int(v), 1), side - 1)
+    mx = rng.randint(clamp(round(lo * width), width), clamp(round(hi * width), width))
+    my = rng.randint(clamp(round(lo * height), height), clamp(round(hi * height), height))
+    return partners, (mx, my)
+
+
+def mosaic_box(box, cell, width, height):
+    """A box proportional to its cell (x0, y0, w, h) as a box proportional to the width x height sample (Python floats)."""
+    x0, y0, cw, ch = cell
+    return box_like(box, Point((x0 + box.center.x * cw) / width, (y0 + box.center.y * ch) / height),
+                    Size(box.size.w * cw / width, box.size.h * ch / height))
+
+
+def mosaic_cell_transforms(transforms):
+    """The training transform list as a mosaic cell runs it: ExpandTransform does not fire (the mosaic already zooms out), the label
+    is made from the merged boxes and ResizeTransform is applied by mosaic_cell_resize to the cell's size.  -> (list, the resize)"""
+    def is_expand(t):
+        return isinstance(t, ExpandTransform) or (isinstance(t, RandomTransform) and isinstance(t.transform, ExpandTransform))
+    resize = [t for t in transforms if isinstance(t, ResizeTransform)]
+    if len(resize) != 1 or transforms[-1] is not resize[0]:
+        raise ValueError('a mosaic needs a transform list that ends in its one ResizeTransform')
+    return [t for t in transforms if not is_expand(t) and not isinstance(t, (LabelCreatorTransform, ResizeTransform))], resize[0]
+
+
+def mosaic_cell_resize(resize, data, label, gt, cw, ch):
+    """ResizeTransform onto a cw x ch cell: the same draw of the algorithm; INTER_AREA that would shrink the frame by more than the
+    tap table allows (14x: a thin cell at a corner centre) becomes INTER_LINEAR.  -> (data, label, gt, 1 if that happened else 0)"""
+    cell = ResizeTransform(width=cw, height=ch, algorithms=resize.algorithms)
+    frame = data.size
+    data, label, gt = cell(data, label, gt)
+    fell = 0
+    if data.resize[2] == INTER_AREA and (frame.w > AREA_MAX_SHRINK * cw or frame.h > AREA_MAX_SHRINK * ch):
+        data.resize = (data.resize[0], data.resize[1], INTER_LINEAR)
+        fell = 1
+    return data, label, gt, fell
 
 
 # ------------------------------------------------------------------------------------------------

@@ -13,6 +13,11 @@ directly and joined after the epoch, so the difference is theirs) and in the tra
 and consumer), and the bytes of the batch's arrays that go up per batch.  Nothing is sized from the machine's core count.
 
     python tools/feeder_rate.py [--files 512] [--rounds 5] [--batch 32] [--workers 4] [--out profiles/feeder_decode_rate.txt]
+
+--mosaic P [P ...] measures every decoder once per mosaic probability, all interleaved in the same rounds -- name
+0 among them: it is the yardstick of the same run -- and adds the mosaics and cells per epoch and the images/s against P = 0:
+
+    python tools/feeder_rate.py --mosaic 0 0.5 1 --out profiles/mosaic_feeder_rate.txt
 """
 import argparse
 import os
@@ -87,7 +92,8 @@ def epoch(td, epoch_no, batch, workers, uploads):
     st = td.feeder_stats
     return dict(rate=(n - first) / wall, worker_ms=(cpu_children() - c0) / n * 1e3, parent_ms=(time.process_time() - p0) / n * 1e3,
                 h2d=statistics.mean(sum(u.values()) for u in uploads), arrays=sorted({k for u in uploads for k, v in u.items() if v}),
-                decoded=st['decoded'], fallbacks=st['fallbacks'], cache_hits=st['cache_hits'], n=n)
+                decoded=st['decoded'], fallbacks=st['fallbacks'], cache_hits=st['cache_hits'], n=n,
+                mosaics=st.get('mosaics', 0), cells=st.get('cells', 0), area_fallbacks=st.get('area_fallbacks', 0))
 
 
 def main():
@@ -96,10 +102,12 @@ def main():
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--workers', type=int, default=4)
+    ap.add_argument('--mosaic', type=float, nargs='+', default=None, help='mosaic probabilities to measure every decoder at (0 = the yardstick)')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'feeder_decode_rate.txt'))
     args = ap.parse_args()
     import torch
     from ssd_tensorflow_amd.training_data import TrainingData
+    wide = 40 if args.mosaic else 26          # the name column: the rows of a --mosaic run carry the probability
     uploads = []
 
     def watched(td):
@@ -115,12 +123,16 @@ def main():
     with tempfile.TemporaryDirectory() as d:
         make_voc_tree(d, args.files, args.batch)
         kw = dict(preset='vgg300', valid_fraction=0)
-        tds = {'pillow': watched(TrainingData(d, **kw)),
-               'gpu': watched(TrainingData(d, decoder='gpu', **kw)),
-               'gpu + cache, epoch >= 2': watched(TrainingData(d, decoder='gpu', cache_bytes=args.files * 500 * 375 * 3 + (1 << 20), **kw))}
+        tds = {}
+        for p in args.mosaic or [None]:
+            tag = '' if p is None else ', mosaic %g' % p
+            mk = {} if p is None else dict(mosaic=p)
+            tds['pillow' + tag] = watched(TrainingData(d, **kw, **mk))
+            tds['gpu' + tag] = watched(TrainingData(d, decoder='gpu', **kw, **mk))
+            tds['gpu + cache, epoch >= 2' + tag] = watched(TrainingData(d, decoder='gpu', cache_bytes=args.files * 500 * 375 * 3 + (1 << 20), **kw, **mk))
         for name, td in tds.items():           # warm-up: code paths, allocations; fills the cache
             first = epoch(td, 0, args.batch, args.workers, uploads)
-            print('warm-up %-24s %8.0f images/s' % (name, first['rate']), flush=True)
+            print('warm-up %-*s %8.0f images/s' % (wide - 2, name, first['rate']), flush=True)
         rows = {name: [] for name in tds}
         for r in range(args.rounds):
             for name, td in tds.items():
@@ -133,17 +145,32 @@ def main():
              '%s, torch %s; %d interleaved rounds in one process, medians (min .. max)' % (torch.cuda.get_device_name(0), torch.__version__, args.rounds),
              'worker CPU: user + system time of the joined worker processes; parent CPU: time.process_time of the training process',
              '',
-             '%-26s %22s %28s %28s %16s' % ('decoder', 'images/s', 'worker CPU ms/sample', 'parent CPU ms/sample', 'H2D bytes/batch')]
+             '%-*s %22s %28s %28s %16s' % (wide, 'decoder', 'images/s', 'worker CPU ms/sample', 'parent CPU ms/sample', 'H2D bytes/batch')]
     med = lambda v: '%.3f (%.3f .. %.3f)' % (statistics.median(v), min(v), max(v))
     for name, rs in rows.items():
         rate = [r['rate'] for r in rs]
-        lines.append('%-26s %22s %28s %28s %16.0f' % (name, '%.0f (%.0f .. %.0f)' % (statistics.median(rate), min(rate), max(rate)),
+        lines.append('%-*s %22s %28s %28s %16.0f' % (wide, name, '%.0f (%.0f .. %.0f)' % (statistics.median(rate), min(rate), max(rate)),
                                                       med([r['worker_ms'] for r in rs]), med([r['parent_ms'] for r in rs]),
                                                       statistics.median(r['h2d'] for r in rs)))
     lines.append('')
     for name, rs in rows.items():
-        lines.append('%-26s arrays that go up: %s; per epoch decoded %d, fallbacks %d, cache hits %d of %d samples' %
-                     (name, ', '.join(rs[-1]['arrays']), rs[-1]['decoded'], rs[-1]['fallbacks'], rs[-1]['cache_hits'], rs[-1]['n']))
+        lines.append('%-*s arrays that go up: %s; per epoch decoded %d, fallbacks %d, cache hits %d of %d samples' %
+                     (wide, name, ', '.join(rs[-1]['arrays']), rs[-1]['decoded'], rs[-1]['fallbacks'], rs[-1]['cache_hits'], rs[-1]['n']))
+    if args.mosaic and 0 in args.mosaic:
+        # against P = 0 of the same run: a sample is one delivered image whatever it was composed of; the bf16 step takes 6.8 ms at
+        # batch 32 (README), so a feeder hides behind it while it delivers more than batch / 6.8 ms images/s
+        need = args.batch / 6.8e-3
+        lines += ['', 'against mosaic 0 of the same run (a mosaic is ONE delivered image made of four source pictures); the bf16 step of 6.8 ms at '
+                  'batch %d consumes %.0f images/s:' % (args.batch, need)]
+        for dec in ('pillow', 'gpu', 'gpu + cache, epoch >= 2'):
+            base = [r['rate'] for r in rows[dec + ', mosaic 0']]
+            for p in args.mosaic:
+                rs = rows[dec + ', mosaic %g' % p]
+                rate = [r['rate'] for r in rs]
+                apart = 'separate' if max(rate) < min(base) or min(rate) > max(base) else 'overlap'
+                lines.append('%-40s %.2f x mosaic 0 (rounds %s); %d mosaics, %d cells, %d area fallbacks per epoch; %s the bf16 step' % (
+                    dec + ', mosaic %g' % p, statistics.median(rate) / statistics.median(base), apart, rs[-1]['mosaics'], rs[-1]['cells'],
+                    rs[-1]['area_fallbacks'], 'hides behind' if min(rate) > need else 'does NOT hide behind'))
     text = '\n'.join(lines) + '\n'
     print(text)
     with open(args.out, 'w') as f:
